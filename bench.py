@@ -6,8 +6,8 @@ resident in HBM: conditioning precompute -> Euler flow steps with CFG (2 network
 per step, batched) -> VAE decode -> full HiFi-GAN decode.
 
   --workload c2 (default)  BASELINE configs[1]: batch 8 x 20 s clips, 50 flow steps, bf16 DiT + fp32 VAE/vocoder (`value`: fp32 products on the f32 MFMA,
-                           F(2,3) minimal filtering where it applies); the same passes with the direct fp32 kernels (`fp32_direct`) and the
-                           bf16x3 VAE/vocoder (`split`) are timed in their own regions
+                           F(2,3) minimal filtering where it applies); with --full the same passes with the direct fp32 kernels (`fp32_direct`)
+                           and the bf16x3 VAE/vocoder (`split`) are timed in their own regions
   --workload c3            BASELINE configs[2]: Band-MoE stress, num_experts = 8, batch 32 (48 128 token rows per CFG branch)
   --workload c5            BASELINE configs[4]: long-form, batch 4 x 120 s (T = 4500 latent frames in windows of 1500 tokens,
                            cross-faded) + VAE decode of the whole latent + halo'd chunked vocoding
@@ -15,11 +15,18 @@ per step, batched) -> VAE decode -> full HiFi-GAN decode.
 N > 1: one process per GPU (`python bench.py --gpus N` spawns them itself; under torch.distributed.run it joins the ranks it
 is given), clips sharded by rank (weak scaling), weights broadcast once from rank 0 over RCCL, no data-path collective.
 
-    python bench.py --gpus 1 --steps 2 --warmup 1
+    python bench.py --gpus 1 --steps 2 --warmup 1 [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps 2 --warmup 1 --full
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (`value`, `ms_per_step`, ...); --dump-outputs DIR
+also writes the last timed step's latent, mel and waveform.  Everything else - the secondary VAE / vocoder precisions, the
+per-class kernel pass and roofline, the live PMC traffic passes, the oracle parity check, the CPU baseline, device telemetry
+and the side file (--detail) - runs with --full only.
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import ctypes as C
 import json
 import os
@@ -110,13 +117,14 @@ def compact_line(out: dict, detail_path: str | None) -> str:
         rfp = pc.get("routing_flips") or {}
         line["parity_check"] = {"ok": pc.get("ok"), "tol": pc.get("tol"), "worst": worst, "clips_x_passes_checked": len(cp),
                                 "routing_flips_per_block": rfp.get("per_block"), "routing_decisions_per_block": rfp.get("decisions_per_block")}
-    line["roofline"] = {"bound": rf.get("bound"), "kernel": rf.get("kernel"), "achieved": _r(rf.get("achieved")), "peak": rf.get("peak"),
-                        "unit": rf.get("unit"), "frac": _r(rf.get("frac"), 4), "traffic": _r(rf.get("traffic")),
-                        "algorithmic_bytes_per_launch": _r(rf.get("algorithmic_bytes_per_launch")), "avg_launch_us": _r(rf.get("avg_launch_us"), 5),
-                        "path_frac": _r(pr.get("frac"), 4), "path_ideal_ms": _r(pr.get("ideal_ms_per_pass"), 5),
-                        "path_frac_direct_equivalent": _r(pr.get("direct_equivalent_frac"), 4),
-                        "groups": [{"group": g["group"].split(" (")[0][:48], "ms_per_pass": _r(g.get("ms_per_pass"), 4), "frac": _r(g.get("frac_of_mfma_peak"), 3)}
-                                   for g in (rf.get("groups") or [])]}
+    if "roofline" in out:                 # (--full)
+        line["roofline"] = {"bound": rf.get("bound"), "kernel": rf.get("kernel"), "achieved": _r(rf.get("achieved")), "peak": rf.get("peak"),
+                            "unit": rf.get("unit"), "frac": _r(rf.get("frac"), 4), "traffic": _r(rf.get("traffic")),
+                            "algorithmic_bytes_per_launch": _r(rf.get("algorithmic_bytes_per_launch")), "avg_launch_us": _r(rf.get("avg_launch_us"), 5),
+                            "path_frac": _r(pr.get("frac"), 4), "path_ideal_ms": _r(pr.get("ideal_ms_per_pass"), 5),
+                            "path_frac_direct_equivalent": _r(pr.get("direct_equivalent_frac"), 4),
+                            "groups": [{"group": g["group"].split(" (")[0][:48], "ms_per_pass": _r(g.get("ms_per_pass"), 4), "frac": _r(g.get("frac_of_mfma_peak"), 3)}
+                                       for g in (rf.get("groups") or [])]}
     cb = out.get("cpu_baseline")
     if cb is not None:
         rfa = cb.get("reference_faithful") or {}
@@ -147,7 +155,7 @@ def compact_line(out: dict, detail_path: str | None) -> str:
         s = json.dumps(line, separators=(",", ":"))
     if len(s) > LINE_MAX:
         line["config"] = {"workload": str(cfg.get("workload"))[:200]}
-        line["roofline"].pop("groups", None)
+        line.get("roofline", {}).pop("groups", None)
         s = json.dumps(line, separators=(",", ":"))
     assert len(s) <= LINE_MAX and "\n" not in s, len(s)
     return s
@@ -332,7 +340,7 @@ class Telemetry:
         return out
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
@@ -347,8 +355,8 @@ def parse():
                     help="VAE + vocoder arithmetic: 'fp32' = the literal 'fp32 vocoder' of configs[1] on v_mfma_f32_32x32x2_f32 (157 TFLOP/s roof); "
                          "'split' = fp32 I/O, every product as bf16 hi/lo pairs on the bf16 MFMA pipe (bf16x3, <= 3e-5 of exact fp32; priced "
                          "against bf16 peak / 3); 'fp32mf' = fp32 with F(2,3) minimal filtering on the stride-1 k = 3 / 7 / 11 layers (fp32 products, ~1.45x "
-                         "fewer; conv1d_f32w.hip); 'both' (default) = the timed region runs with fp32mf (`value`: configs[1]'s fp32 vocoder) and then the same K "
-                         "passes run with the direct fp32 kernels (`fp32_direct` sub-object) and with split (`split`), each with its own oracle check")
+                         "fewer; conv1d_f32w.hip); 'both' (default) = the timed region runs with fp32mf (`value`: configs[1]'s fp32 vocoder) and, with --full, the same K "
+                         "passes then run with the direct fp32 kernels (`fp32_direct` sub-object) and with split (`split`), each with its own oracle check")
     ap.add_argument("--no-pmc", action="store_true", help="do not spawn the rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (N = 1, default c2 command, "
                                                           "rocprofv3 on PATH) that measure roofline.traffic in this run; fall back to the committed summary")
     ap.add_argument("--pmc-timeout", type=float, default=150.0)
@@ -363,9 +371,19 @@ def parse():
     ap.add_argument("--cpu-timeout", type=float, default=240.0)
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"),
-                    help="side file for the per-class / per-group / per-kernel tables (the stdout line stays <= 4 KB and names this path)")
+                    help="--full: side file for the per-class / per-group / per-kernel tables (the stdout line stays <= 4 KB and names this path)")
     ap.add_argument("--save-out", default=None, help="directory: every rank writes the waveforms of its last pass (clip-indexed .npy)")
-    a = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: secondary VAE / vocoder precisions (with --vocoder-precision both), the isolated per-class "
+                         "kernel pass and roofline, live PMC traffic, the oracle parity check, the CPU baseline, telemetry and the --detail side file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last step's outputs (latent, mel, wav; float32, <= 64 MB in all, a fixed seeded sample "
+                         "of what does not fit) as DIR/<name>.npy")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.profile_timed and not a.full:
+        ap.error("--profile-timed reports under `roofline`, which only --full computes")
     dflt = {"c2": (8, 4, 20.0, 2), "c3": (32, 8, 20.0, 2), "c5": (4, 4, 120.0, 1)}[a.workload]
     a.batch = dflt[0] if a.batch is None else a.batch
     a.experts = dflt[1] if a.experts is None else a.experts
@@ -542,6 +560,28 @@ def parity_check(z0, mel0, fixture="bench_clip0.npz"):
             "against": f"tests/golden/{fixture} (CPU oracle replay of clip 0, pass 0: same seed, same device-keyed router noise)"}
 
 
+DUMP_BUDGET = 63 * 1000 * 1000          # bytes of array data: 64 MB in all with room for the .npy headers
+
+
+def dump_outputs(arrays, out_dir, budget=DUMP_BUDGET, suffix=""):
+    """--dump-outputs: every array (name -> numpy) as out_dir/<name><suffix>.npy in float32, at most `budget` bytes in all.  Arrays are
+    taken smallest first; one larger than an even share of what is left is replaced by a fixed sample of its flattened elements (indices
+    drawn by a generator seeded with the array's size, sorted), so the same arguments always write the same elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(((n, np.ascontiguousarray(a, dtype=np.float32)) for n, a in arrays.items()), key=lambda kv: kv[1].nbytes)
+    left, written = budget, {}
+    for i, (name, a) in enumerate(items):
+        share = left // (len(items) - i)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(a.size).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+        left -= a.nbytes
+        written[name] = a.shape
+    return written
+
+
 def main():
     args = parse()
     if args.cpu_baseline_worker:
@@ -601,9 +641,10 @@ def main():
     # primary = the precision `value` is measured in: configs[1]'s fp32 VAE / vocoder - since round 6 with F(2,3) minimal filtering on the
     # layers it applies to (fp32 products on the f32 MFMA, ~1.45x fewer; held to the same bounds against the reference's outputs as the
     # direct kernels, tests/test_gpu_path.py).  Secondaries, each timed in its own region of the same K passes and verified the same way:
-    # "fp32" = the direct fp32 kernels (rounds 4-5's `value`), "split" = bf16x3.
+    # "fp32" = the direct fp32 kernels (rounds 4-5's `value`), "split" = bf16x3.  The secondaries run with --full only.
+    full = args.full
     prim = "fp32mf" if args.vocoder_precision == "both" else args.vocoder_precision
-    secs = ["fp32", "split"] if args.vocoder_precision == "both" else []
+    secs = ["fp32", "split"] if args.vocoder_precision == "both" and full else []
     CLS = classes_for(prim)
     ctx = Context(device)
     S = max(1, args.streams)
@@ -698,7 +739,7 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    keep_passes = {0, 1, args.steps - 1}
+    keep_passes = {0, 1, args.steps - 1} if full else {args.steps - 1}      # (the oracle checks of --full read passes 0 and 1)
     lib = L.load()
     torch.cuda.synchronize()
     log(f"engines built ({S} stream(s) x {Bs} clips of {clip_seconds:.1f} s, E={args.experts}); warmup")
@@ -777,7 +818,7 @@ def main():
         L.check(lib.vb_prof_enable(0), "prof")
         return {c: tuple(v) for c, v in tot.items()}
 
-    if not args.no_isolated:
+    if full and not args.no_isolated:
         w = workers[0] if S == 1 else make_worker(B, rank * B, share=workers[0]["eng"])
         run_worker(w, [-100])
         torch.cuda.synchronize()
@@ -818,14 +859,23 @@ def main():
     # the dominant class bracketed inside the timed region (slower: the event records and ~6000 host launches per pass).
     if args.profile_timed:
         L.check(lib.vb_prof_enable((1 << dominant) | (8 << 8)), "prof")
-    log(f"warmup done; dominant class = {CLS[dominant][0]}; timing {args.steps} step(s)")
+    log("warmup done; " + (f"dominant class = {CLS[dominant][0]}; " if full else "") + f"timing {args.steps} step(s)")
 
     barrier()
-    with Telemetry() as tele:
+    tele = Telemetry() if full else None
+    with tele or contextlib.nullcontext():
         t0 = time.perf_counter()
         run_passes(list(range(args.steps)))
         barrier()
         elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        # what the timed path handed back in its last step, clips in global order (workers hold consecutive clip ranges)
+        last = args.steps - 1
+        arrays = {"latent": torch.cat([w["kept"][last][0] for w in workers]).cpu().numpy(),
+                  "mel": torch.cat([w["kept"][last][1] for w in workers]).cpu().numpy(),
+                  "wav": torch.cat([w["wav"] for w in workers]).cpu().numpy()}
+        shapes = dump_outputs(arrays, args.dump_outputs, DUMP_BUDGET // world, f"_rank{rank}" if world > 1 else "")
+        log(f"outputs of timed step {last} written to {args.dump_outputs}: {shapes}")
     per_rank_ms = [1e3 * elapsed / args.steps]
     if world > 1:
         import torch.distributed as dist
@@ -914,7 +964,7 @@ def main():
         return par
 
     parity, parity_sec = None, {}
-    if rank == 0 and not args.no_parity_check and args.flow_steps == 50 and args.scale == 3.0 and args.precision == "bf16" and args.steps >= 1:
+    if full and rank == 0 and not args.no_parity_check and args.flow_steps == 50 and args.scale == 3.0 and args.precision == "bf16" and args.steps >= 1:
         # one oracle fixture per workload shape: 20 s clips with 4 / 8 experts (clip 0 does not depend on the batch it rides in), and
         # the 120 s long-form clip whose window rows / noise keys depend on the batch (4).  A failure anywhere fails the run (exit code 3).
         parity = verify(workers, f"{prim} VAE / vocoder", True)
@@ -935,11 +985,11 @@ def main():
         # the committed PMC passes were taken on the default command (c2, 8 clips): for any other workload the per-launch figure does not apply
         pmc_applies = args.workload == "c2" and B == 8 and args.experts == 4 and abs(clip_seconds - 20.0) < 1e-9
         traffic, traffic_file, traffic_how, traffic_table = None, None, None, None
-        if pmc_applies and world == 1 and not args.no_pmc:
+        if full and pmc_applies and world == 1 and not args.no_pmc:
             log("PMC traffic passes (rocprofv3 child runs)")
             traffic, traffic_how, traffic_table = pmc_traffic_live(pmc_cls, args.pmc_timeout, prim, iso["launches_per_pass"] if iso else None)
             log(f"traffic: {traffic} ({traffic_how})")
-        if traffic is None and pmc_applies:
+        if full and traffic is None and pmc_applies:
             live_why = traffic_how
             traffic, traffic_file = pmc_traffic(pmc_cls)
             traffic_how = (f"file: {traffic_file} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, FETCH doubled per the gfx950 note"
@@ -984,30 +1034,31 @@ def main():
                        "sampler_loop": ("hipGraph replay (%d graph(s) on rank 0)" % sum(w["eng"].graphs() for w in workers))
                        if any(w["eng"].graphs() for w in workers) else "eager launches",
                        "streams_per_gpu": S, "parallelism": f"batch-shard x{world} ({S} concurrent sub-batches of {Bs} clips per GPU)"},
-            "parity_check": parity,
-            "device": {"name": torch.cuda.get_device_name(device), "clocks_during_timed_region": tele.summary(device)},
-            "roofline": {"bound": "mfma", "kernel": name, "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
-                         "how": ("dominant group = largest GPU time per pass (the two convolution classes count as one group, like the six GEMM kernels "
-                                 "count as one class); achieved = algorithmic flops of its launches / their durations, from the event-timed launches "
-                                 "of each of its classes scaled to the class's launch count, measured in this run with every class ALONE on the GPU "
-                                 "(one stream, whole batch, launches bracketed by HIP events on the launch stream in rotating phases over "
-                                 f"{PROF_PASSES} passes so that EVERY launch is timed - the GEMM class twice, the others seven times - and never "
-                                 "two neighbours in one pass: totals, not a scaled sample); `classes` and `groups` list every class / group the "
-                                 "same way") if iso else "timed-region launches (no isolated pass)",
-                         "avg_launch_us": iso["avg_launch_us"] if iso else ((1e3 * ms / nt) if nt else None),
-                         "traffic": traffic, "traffic_per_kernel": traffic_table,
-                         "traffic_source": traffic_how if pmc_applies else
-                                           "none for this workload: the PMC passes cover the default c2 command only",
-                         "algorithmic_bytes_per_launch": (iso["algorithmic_mb_per_launch"] * 1e6) if iso else None,
-                         "timed_region": ({"achieved": conc, "frac": conc / peak, "avg_launch_us": (1e3 * ms / nt) if nt else None,
-                                           "launches_per_step": n / max(args.steps, 1), "timed_launches": nt,
-                                           "note": "every 8th launch of the dominant class bracketed by HIP events INSIDE the timed region; with "
-                                                   "streams_per_gpu > 1 a launch shares the GPU with the other sub-batch's kernels, so its "
-                                                   "duration includes that overlap (not a kernel-quality figure)"} if args.profile_timed else
-                                          "not event-bracketed: the timed region replays the sampler loop as a hipGraph (run with --profile-timed "
-                                          "for eager launches + in-region events)"),
-                         "classes": table, "groups": [{k: v for k, v in g.items() if k != "class_ids"} for g in groups]},
         }
+        if full:
+            out["parity_check"] = parity
+            out["device"] = {"name": torch.cuda.get_device_name(device), "clocks_during_timed_region": tele.summary(device)}
+            out["roofline"] = {"bound": "mfma", "kernel": name, "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
+                               "how": ("dominant group = largest GPU time per pass (the two convolution classes count as one group, like the six GEMM kernels "
+                                       "count as one class); achieved = algorithmic flops of its launches / their durations, from the event-timed launches "
+                                       "of each of its classes scaled to the class's launch count, measured in this run with every class ALONE on the GPU "
+                                       "(one stream, whole batch, launches bracketed by HIP events on the launch stream in rotating phases over "
+                                       f"{PROF_PASSES} passes so that EVERY launch is timed - the GEMM class twice, the others seven times - and never "
+                                       "two neighbours in one pass: totals, not a scaled sample); `classes` and `groups` list every class / group the "
+                                       "same way") if iso else "timed-region launches (no isolated pass)",
+                               "avg_launch_us": iso["avg_launch_us"] if iso else ((1e3 * ms / nt) if nt else None),
+                               "traffic": traffic, "traffic_per_kernel": traffic_table,
+                               "traffic_source": traffic_how if pmc_applies else
+                                                 "none for this workload: the PMC passes cover the default c2 command only",
+                               "algorithmic_bytes_per_launch": (iso["algorithmic_mb_per_launch"] * 1e6) if iso else None,
+                               "timed_region": ({"achieved": conc, "frac": conc / peak, "avg_launch_us": (1e3 * ms / nt) if nt else None,
+                                                 "launches_per_step": n / max(args.steps, 1), "timed_launches": nt,
+                                                 "note": "every 8th launch of the dominant class bracketed by HIP events INSIDE the timed region; with "
+                                                         "streams_per_gpu > 1 a launch shares the GPU with the other sub-batch's kernels, so its "
+                                                         "duration includes that overlap (not a kernel-quality figure)"} if args.profile_timed else
+                                                "not event-bracketed: the timed region replays the sampler loop as a hipGraph (run with --profile-timed "
+                                                "for eager launches + in-region events)"),
+                               "classes": table, "groups": [{k: v for k, v in g.items() if k != "class_ids"} for g in groups]}
         if groups:
             # the whole path against its roofs: every group's algorithmic flops per pass at the dense MFMA peak of its arithmetic (bf16 2.5 PF,
             # f32 157.3 TF), summed, over the measured time of a pass - the number a round should move (round 4: 67.9 ms ideal / 143.4 = 0.47)
@@ -1042,14 +1093,15 @@ def main():
                 ideal_d = pr_["ideal_ms_per_pass"] - dom_group["ideal_ms_per_pass_at_mfma_peak"] + dgf / dom_group["mfma_peak_tflops"]
                 pr_["direct_equivalent_ideal_ms_per_pass"] = ideal_d
                 pr_["direct_equivalent_frac"] = ideal_d / pr_["ms_per_step"]
-        if world == 1 and not args.no_cpu_baseline and args.workload == "c2":
+        if full and world == 1 and not args.no_cpu_baseline and args.workload == "c2":
             log("cpu baseline (subprocess, bounded)")
             out["cpu_baseline"] = cpu_baseline_subprocess(args)
-        detail_path = args.detail
+        detail_path = args.detail if full else None        # a plain run's line holds all it measured
         try:
-            os.makedirs(os.path.dirname(os.path.abspath(detail_path)) or ".", exist_ok=True)
-            with open(detail_path, "w") as f:
-                json.dump(out, f, indent=1)
+            if detail_path:
+                os.makedirs(os.path.dirname(os.path.abspath(detail_path)) or ".", exist_ok=True)
+                with open(detail_path, "w") as f:
+                    json.dump(out, f, indent=1)
         except OSError as e:                     # a read-only checkout must not cost the line
             log(f"could not write {detail_path}: {e}")
             detail_path = None

@@ -526,9 +526,28 @@ def use_reference_paths():
             del sys.modules[m]
 
 
+def gen_config_digest():
+    """the reference's configs/vocal2music.yaml as digests only (tests/helpers.py:config_hash), never its text: every key path, the model
+    tree without its checkpoint path (a path on its authors' machines), and the three model sub-configs the product reads"""
+    import copy
+    import json
+    import yaml
+    from tests.helpers import config_hash, config_key_paths
+    ref = yaml.safe_load(open(os.path.join(REF, "configs", "vocal2music.yaml")))
+    model = copy.deepcopy(ref["model"])
+    del model["params"]["first_stage_config"]["params"]["ckpt_path"]
+    p = ref["model"]["params"]
+    out = {"key_paths": sorted(config_hash(list(k)) for k in config_key_paths(ref)), "model_without_ckpt_path": config_hash(model),
+           "unet_config": config_hash(p["unet_config"]), "cond_stage_config": config_hash(p["cond_stage_config"]),
+           "first_stage_ddconfig": config_hash(p["first_stage_config"]["params"]["ddconfig"])}
+    with open(os.path.join(GOLD, "reference_config_digest.json"), "w") as f:
+        json.dump(out, f, indent=1)
+
+
 def main():
     assert os.path.isdir(REF), "the reference is only available in the build container"
     os.makedirs(GOLD, exist_ok=True)
+    gen_config_digest()
     install_stubs()
     use_reference_paths()
     torch.set_grad_enabled(False)

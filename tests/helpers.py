@@ -86,6 +86,31 @@ def check_digest(t, g, prefix, rtol):
     assert float(err) <= 10 * rtol * mx, (prefix, float(err), mx)
 
 
+def config_hash(obj) -> str:
+    """sha256 of a parsed config tree (or of one key path / value) in canonical JSON: oracle/gen_golden.py:gen_config_digest stores these
+    for the reference's configs/vocal2music.yaml, so the config tests need neither the reference nor a copy of its text"""
+    import hashlib
+    import json
+    return hashlib.sha256(json.dumps(obj, sort_keys=True, separators=(",", ":")).encode()).hexdigest()
+
+
+def config_key_paths(tree, prefix=()):
+    """every mapping key of a parsed config as a tuple path, nested keys included"""
+    out = []
+    if isinstance(tree, dict):
+        for k, v in tree.items():
+            out.append(prefix + (k,))
+            out += config_key_paths(v, prefix + (k,))
+    return out
+
+
+def config_restrict(tree, paths, prefix=()):
+    """the part of `tree` made of the given key paths (values below the deepest listed key kept whole)"""
+    if not isinstance(tree, dict):
+        return tree
+    return {k: config_restrict(v, paths, prefix + (k,)) for k, v in tree.items() if prefix + (k,) in paths}
+
+
 _LOAD_CHILD = r'''
 import sys, time, torch
 a = torch.randn(4096, 4096, device="cuda", dtype=torch.bfloat16)

@@ -21,7 +21,7 @@ def _bench(args, env_extra, timeout=900):
     env.pop("RANK", None); env.pop("WORLD_SIZE", None); env.pop("LOCAL_RANK", None)
     import tempfile
     detail = os.path.join(tempfile.mkdtemp(prefix="vb_bench_"), "bench_detail.json")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--detail", detail] + args, capture_output=True, text=True, timeout=timeout,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--detail", detail] + args, capture_output=True, text=True, timeout=timeout,
                        env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     # the driver's contract (round 5's 21 KB line came back `parsed: null`): the LAST stdout line is the one JSON object, <= 4 KB

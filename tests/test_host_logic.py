@@ -350,6 +350,37 @@ def test_bench_line_is_one_short_json_line():
     assert json.loads(bench.compact_line(bare, None))["roofline"]["frac"] == 0.5
 
 
+def test_bench_plain_run_options_and_output_dump(tmp_path):
+    """A plain `bench.py` run times the K steps and prints the contract keys only; --full adds the rest.  --dump-outputs writes float32
+    .npy files of at most 64 MB in all, the same elements on every run (c3's 32 clips do not fit whole: the waveform is sampled)."""
+    import json
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert a.steps == 7 and a.warmup == 3 and not a.full and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full and a.dump_outputs == str(tmp_path)
+    for bad in (["--steps", "0"], ["--profile-timed"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+    rng = np.random.default_rng(5)
+    arrays = {"latent": rng.standard_normal((32, 20, 752)), "mel": rng.standard_normal((32, 80, 1504)).astype(np.float32),
+              "wav": rng.standard_normal((32, 1, 481280)).astype(np.float32)}
+    runs = []
+    for d in (tmp_path / "a", tmp_path / "b"):
+        shapes = bench.dump_outputs(arrays, str(d))
+        assert shapes["latent"] == (32, 20, 752) and shapes["mel"] == (32, 80, 1504) and len(shapes["wav"]) == 1
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64e6
+        runs.append({n: np.load(d / f"{n}.npy") for n in arrays})
+    for n in arrays:
+        assert runs[0][n].dtype == np.float32 and np.array_equal(runs[0][n], runs[1][n]), n
+    assert np.array_equal(runs[0]["latent"], arrays["latent"].astype(np.float32))
+    assert np.isin(runs[0]["wav"], arrays["wav"].reshape(-1)).all()
+    plain = {"metric": "m", "value": 1.5, "unit": "mel-s/s", "n_gpus": 1, "steps": 7, "warmup": 3, "ms_per_step": 2.0, "higher_is_better": True,
+             "scaling": "weak", "vs_baseline": None, "dtype": "d", "data": "x", "config": {"workload": "w"}}
+    d = json.loads(bench.compact_line(plain, None))
+    assert d["ms_per_step"] == 2.0 and d["steps"] == 7 and "roofline" not in d and "parity_check" not in d
+
+
 def _model_keys(tree, prefix=""):
     out = set()
     if isinstance(tree, dict):
@@ -393,22 +424,30 @@ def test_full_key_config_takes_the_reference_constructor_paths():
     assert trimmed.model.params.cond_stage_config == cfg.model.params.cond_stage_config
 
 
-REF_YAML = "/root/reference/configs/vocal2music.yaml"
-
-
-@pytest.mark.skipif(not os.path.exists(REF_YAML), reason="the reference checkout is not on this box")
-def test_reference_yaml_loads_unchanged():
-    """"the YAML file loads unchanged".  The reference's own configs/vocal2music.yaml:1-128 through the three calls of
-    initialize_model; and the committed full-key config must cover its whole `model:` key set, so the GPU box runs the same paths."""
-    cfg, warns = _check_boundary_config(REF_YAML)
+def test_reference_yaml_loads_unchanged(golden_dir, tmp_path):
+    """"the YAML file loads unchanged".  The reference's own configs/vocal2music.yaml:1-128, held as digests
+    (tests/golden/reference_config_digest.json, oracle/gen_golden.py:gen_config_digest): the committed full-key config must cover its
+    every key, so the GPU box runs the same paths; the reference's tree rebuilt from those keys must equal it in every model value bar
+    the checkpoint path, and go through the three calls of initialize_model."""
+    import json
+    import yaml
+    from tests.helpers import config_hash, config_key_paths, config_restrict
+    g = json.load(open(os.path.join(golden_dir, "reference_config_digest.json")))
+    ours = yaml.safe_load(open(os.path.join(ROOT, "configs", "vocal2music_full.yaml")))
+    by_hash = {config_hash(list(k)): k for k in config_key_paths(ours)}
+    missing = set(g["key_paths"]) - set(by_hash)
+    assert not missing, f"{len(missing)} key path(s) of the reference's config are not in configs/vocal2music_full.yaml"
+    ref = config_restrict(ours, {by_hash[h] for h in g["key_paths"]})
+    model = json.loads(json.dumps(ref["model"]))
+    del model["params"]["first_stage_config"]["params"]["ckpt_path"]
+    assert config_hash(model) == g["model_without_ckpt_path"]
+    (tmp_path / "vocal2music.yaml").write_text(yaml.safe_dump(ref, sort_keys=False))
+    cfg, warns = _check_boundary_config(str(tmp_path / "vocal2music.yaml"))
     assert any("ckpt_path" in x for x in warns)
-    ours = vm.load_config(os.path.join(ROOT, "configs", "vocal2music_full.yaml"))
-    ref_keys, our_keys = _model_keys(dict(cfg.model)), _model_keys(dict(ours.model))
-    assert ref_keys <= our_keys, sorted(ref_keys - our_keys)
-    assert set(cfg.keys()) <= set(ours.keys())
+    p = ours["model"]["params"]
     for k in ("unet_config", "cond_stage_config"):
-        assert cfg.model.params[k] == ours.model.params[k]
-    assert cfg.model.params.first_stage_config.params.ddconfig == ours.model.params.first_stage_config.params.ddconfig
+        assert config_hash(p[k]) == g[k], k
+    assert config_hash(p["first_stage_config"]["params"]["ddconfig"]) == g["first_stage_ddconfig"]
 
 
 def test_oracle_long_form_restatement_matches_the_product_plan():

@@ -12,7 +12,7 @@ for envs in "$@"; do
   i=$((i+1))
   cd /tmp
   if [ "$envs" = "-" ]; then e=""; else e="$envs"; fi
-  env $e timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ab$i -o b -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-isolated --no-pmc --streams 1 ${BENCH_ARGS:-} > $O/ab$i.log 2>&1
+  env $e timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ab$i -o b -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-isolated --no-pmc --streams 1 ${BENCH_ARGS:-} > $O/ab$i.log 2>&1
   cd $R
   f=$(find $O/ab$i -name "*kernel_stats.csv" | head -1)
   echo "== [$envs]  $(grep -o '"value": [0-9.]*' $O/ab$i.log | head -1)  $(grep -o '"ok": [a-z]*' $O/ab$i.log | head -1)"

@@ -16,12 +16,12 @@ echo "gpu tests exit: $?" >> $O/gpu_tests.log
 tail -6 $O/gpu_tests.log
 timeout 300 python __graft_entry__.py --smoke 2>&1 | tail -2 | tee $O/smoke.log
 fi
-timeout 900 python bench.py > $O/bench_c2.json 2> $O/bench_c2.err
-timeout 400 python bench.py --workload c3 --steps 1 --warmup 1 --no-cpu-baseline > $O/bench_c3.json 2> $O/bench_c3.err
-timeout 400 python bench.py --workload c5 --steps 1 --warmup 1 --no-cpu-baseline > $O/bench_c5.json 2> $O/bench_c5.err
-timeout 300 python bench.py --batch 1 --streams 1 --steps 4 --warmup 2 --no-cpu-baseline --no-pmc > $O/bench_b1.json 2> $O/bench_b1.err
-timeout 300 python bench.py --batch 2 --streams 1 --steps 4 --warmup 2 --no-cpu-baseline --no-pmc > $O/bench_b2.json 2> $O/bench_b2.err
-timeout 300 python bench.py --streams 1 --steps 3 --warmup 1 --no-cpu-baseline --no-pmc > $O/bench_s1.json 2> $O/bench_s1.err
+timeout 900 python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err
+timeout 400 python bench.py --full --workload c3 --steps 1 --warmup 1 --no-cpu-baseline > $O/bench_c3.json 2> $O/bench_c3.err
+timeout 400 python bench.py --full --workload c5 --steps 1 --warmup 1 --no-cpu-baseline > $O/bench_c5.json 2> $O/bench_c5.err
+timeout 300 python bench.py --full --batch 1 --streams 1 --steps 4 --warmup 2 --no-cpu-baseline --no-pmc > $O/bench_b1.json 2> $O/bench_b1.err
+timeout 300 python bench.py --full --batch 2 --streams 1 --steps 4 --warmup 2 --no-cpu-baseline --no-pmc > $O/bench_b2.json 2> $O/bench_b2.err
+timeout 300 python bench.py --full --streams 1 --steps 3 --warmup 1 --no-cpu-baseline --no-pmc > $O/bench_s1.json 2> $O/bench_s1.err
 for f in c2 c3 c5 b1 b2 s1; do python - <<PY
 import json
 try:
@@ -36,7 +36,7 @@ PY
 done
 cd /tmp
 prof() { # name args passes
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$1 -o b -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-isolated --no-pmc --no-parity-check $2 > $O/$1.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$1 -o b -- python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-isolated --no-pmc --no-parity-check $2 > $O/$1.log 2>&1
   f=$(find $O/$1 -name "*kernel_stats.csv" | head -1)
   cp "$f" $O/${1}_kernel_stats.csv
   python $R/tools/prof_summary.py $O/${1}_kernel_stats.csv ${3:-2} 16

@@ -13,12 +13,12 @@ echo "gpu tests exit: $?" >> $O/gpu_tests.log
 tail -4 $O/gpu_tests.log
 timeout 300 python __graft_entry__.py --smoke 2>&1 | tail -2 | tee $O/smoke.log
 # (the stdout line of every run is the <= 4 KB driver line -> bench_<f>.line.json; the tables are in the side file bench_<f>.json)
-timeout 600 python bench.py --detail $O/bench_c2.json > $O/bench_c2.line.json 2> $O/bench_c2.err
-timeout 300 python bench.py --batch 1 --streams 1 --steps 4 --warmup 2 --no-cpu-baseline --no-pmc --detail $O/bench_b1.json > $O/bench_b1.line.json 2> $O/bench_b1.err
-timeout 300 python bench.py --streams 1 --steps 3 --warmup 1 --no-cpu-baseline --no-pmc --no-isolated --detail $O/bench_s1.json > $O/bench_s1.line.json 2> $O/bench_s1.err
+timeout 600 python bench.py --full --detail $O/bench_c2.json > $O/bench_c2.line.json 2> $O/bench_c2.err
+timeout 300 python bench.py --full --batch 1 --streams 1 --steps 4 --warmup 2 --no-cpu-baseline --no-pmc --detail $O/bench_b1.json > $O/bench_b1.line.json 2> $O/bench_b1.err
+timeout 300 python bench.py --full --streams 1 --steps 3 --warmup 1 --no-cpu-baseline --no-pmc --no-isolated --detail $O/bench_s1.json > $O/bench_s1.line.json 2> $O/bench_s1.err
 if [ "${2:-}" = "all" ]; then
-  timeout 400 python bench.py --workload c3 --steps 2 --warmup 1 --no-cpu-baseline --no-pmc --detail $O/bench_c3.json > $O/bench_c3.line.json 2> $O/bench_c3.err
-  timeout 400 python bench.py --workload c5 --steps 2 --warmup 1 --no-cpu-baseline --no-pmc --detail $O/bench_c5.json > $O/bench_c5.line.json 2> $O/bench_c5.err
+  timeout 400 python bench.py --full --workload c3 --steps 2 --warmup 1 --no-cpu-baseline --no-pmc --detail $O/bench_c3.json > $O/bench_c3.line.json 2> $O/bench_c3.err
+  timeout 400 python bench.py --full --workload c5 --steps 2 --warmup 1 --no-cpu-baseline --no-pmc --detail $O/bench_c5.json > $O/bench_c5.line.json 2> $O/bench_c5.err
 fi
 for f in c2 b1 s1 c3 c5; do [ -f $O/bench_$f.json ] || continue; python - <<PY
 import json
@@ -39,7 +39,7 @@ PY
 done
 cd /tmp
 prof() { # name args passes
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$1 -o b -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-isolated --no-pmc --no-parity-check $2 > $O/$1.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$1 -o b -- python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-isolated --no-pmc --no-parity-check $2 > $O/$1.log 2>&1
   f=$(find $O/$1 -name "*kernel_stats.csv" | head -1)
   cp "$f" $O/${1}_kernel_stats.csv
   python $R/tools/prof_summary.py $O/${1}_kernel_stats.csv ${3:-3} 14

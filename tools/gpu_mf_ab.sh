@@ -9,7 +9,7 @@ mkdir -p gpurun_out/mf_ab
 export TMPDIR=/tmp
 O=gpurun_out/mf_ab
 line() { python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', d['value'], d['ms_per_step'], d['parity_check']['ok'])"; }
-bench() { timeout 400 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-pmc --no-isolated --detail $O/d.json "$@" 2>> $O/err.log; }
+bench() { timeout 400 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-pmc --no-isolated --detail $O/d.json "$@" 2>> $O/err.log; }
 case "${1:-layers}" in
   layers)
     timeout 900 python -m pytest tests/test_gpu_kernels.py -m gpu -q -x -p no:cacheprovider -k "minimal_filtering" 2>&1 | tail -3
@@ -21,6 +21,6 @@ case "${1:-layers}" in
     shift
     for i in 1 2; do
       bench --vocoder-precision fp32mf | line default
-      env "$@" timeout 400 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-pmc --no-isolated --detail $O/d.json --vocoder-precision fp32mf 2>> $O/err.log | line "$*"
+      env "$@" timeout 400 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-pmc --no-isolated --detail $O/d.json --vocoder-precision fp32mf 2>> $O/err.log | line "$*"
     done ;;
 esac

@@ -5,6 +5,7 @@
 set -u
 TAG=${1:-sq}
 shift || true
+set -- --full "$@"      # the counter pass covers every timed region of the full benchmark run
 mkdir -p gpurun_out/$TAG
 export TMPDIR=/tmp
 R=$PWD

@@ -12,7 +12,7 @@ HAVE=$(python -c "import torch; print(torch.cuda.device_count())" 2>/dev/null ||
 echo "visible GPUs: $HAVE"
 for n in $GPUS; do
   if [ "$n" -gt "$HAVE" ]; then echo "N=$n: skipped ($HAVE GPUs visible)"; continue; fi
-  timeout 1200 python bench.py --gpus $n --steps $STEPS --warmup $WARM --no-cpu-baseline --no-pmc --no-isolated --detail $O/n$n.detail.json > $O/n$n.json 2> $O/n$n.err
+  timeout 1200 python bench.py --full --gpus $n --steps $STEPS --warmup $WARM --no-cpu-baseline --no-pmc --no-isolated --detail $O/n$n.detail.json > $O/n$n.json 2> $O/n$n.err
   echo "N=$n exit $?"; grep '^{' $O/n$n.json | tail -1
 done
 python - <<PY
