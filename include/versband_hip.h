@@ -185,10 +185,11 @@ int vb_sample_graphs(vb_ctx* ctx);
 typedef struct { int channels; int tmul; int square; } vb_buf_desc;   /* square: 1 = [T*tmul]^2 floats, 2 = channels x roundup(T*tmul, 32),
                                                                          3 = channels x (T*tmul + 448) (transposed planes with halo) */
 /* VB_OP_SPLIT_PLANES: x (f32 [B][rows][cols], rows = Co, cols = Ci, -1 = the buffer's time length) -> out = split-bf16
- * planes [2][B][rows][roundup(cols, 32)]; a later VB_OP_CONV with w_buf = that buffer and ci_pad = -1 uses them as
+ * planes [2][B][rows][roundup(cols, 32)]; a later VB_OP_CONV with w_buf = that buffer and wfmt = VB_WFMT_BUF_X3 uses them as
  * per-batch weights on the bf16x3 kernel (the VAE decoder's single-head attention) */
-/* VB_OP_RESPAIR: fused HiFi-GAN ResBlock1 pair (vocoder/hifigan/modules/hifigan.py ResBlock1.forward), Ci = Co = 32 or 64:
- * out = beta*out + alpha*(x + bias2 + conv2_k( lrelu( bias + conv1_{k,dil}( lrelu(x) ) ) )), w_x3 / w2_x3 split planes */
+/* VB_OP_RESPAIR: fused HiFi-GAN ResBlock1 pair (vocoder/hifigan/modules/hifigan.py ResBlock1.forward), Ci = Co:
+ * out = beta*out + alpha*(x + bias2 + conv2_k( lrelu( bias + conv1_{k,dil}( lrelu(x) ) ) )); the first convolution's weights sit in
+ * the slot of the op's format, the second's in w2 (same format) */
 /* VB_OP_GN_APPLY: out = GroupNorm affine of x from `stats` (+ swish when in_act == VB_ACT_GN_SWISH), same layout */
 /* VB_OP_AA_ACT: BigVGAN anti-aliased Snake / SnakeBeta (vocoder/bigvgan/alias_free_torch/act.py): out = down2(snake(up2(x))), Ci channels,
  * gn_gamma = alpha (exp'ed when log-scale), gn_beta = 1 / (beta + 1e-9), w = the 12-tap Kaiser-sinc filter */
@@ -197,21 +198,40 @@ typedef struct { int channels; int tmul; int square; } vb_buf_desc;   /* square:
 enum { VB_OP_CONV = 0, VB_OP_GN_STATS = 1, VB_OP_SOFTMAX_T = 2, VB_OP_SPLIT_PLANES = 3, VB_OP_RESPAIR = 4, VB_OP_GN_APPLY = 5, VB_OP_AA_ACT = 6,
        VB_OP_XT_PLANES = 7 };
 enum { VB_ACT_NONE = 0, VB_ACT_LRELU = 1, VB_ACT_GN_SWISH = 2, VB_ACT_TANH = 3, VB_ACT_GN = 4 };
+/* Weight format of an op (vb_net_op.wfmt):
+ *   F32     w: fp32 packed [phase][tap][Ci][Co]                       (pack.py:pack_conv / pack_conv_transpose)
+ *   X3      w_x3: split-bf16 planes [2][phase][tap][Co][ci_pad]       (pack.py:pack_conv_x3; ci_pad = Ci rounded up to 32)
+ *   MF      w_mf: fp32 F(2,3) minimal-filtering pseudo-taps [P][Ci][Co] of the same filter, 16-byte aligned (pack.py:pack_conv_mf)
+ *   BUF_F32 w_buf: per-batch fp32 weights written by earlier ops      (the VAE attention's products)
+ *   BUF_X3  w_buf: per-batch split planes from a VB_OP_SPLIT_PLANES
+ * Allowed (kind, wfmt) pairs and the weight fields each reads; vb_net_load refuses any other pair, a NULL in a field the pair reads,
+ * and a non-NULL weight pointer (w, w_x3, w_mf, w2) or a w_buf id in a field it does not read:
+ *   CONV     F32      w                              the exact-fp32 kernels
+ *   CONV     X3       w_x3, ci_pad, w                the bf16x3 kernels; w feeds the one-output-channel kernel (Co = 1: conv_post)
+ *   CONV     MF       w_mf, w                        conv1d_f32w_kernel where launch_conv1d's run-time conditions hold, else the direct kernels on w
+ *   CONV     BUF_F32  w_buf                          exact fp32
+ *   CONV     BUF_X3   w_buf                          bf16x3
+ *   RESPAIR  F32      w, w2, bias, bias2             respair_f32_kernel, C = 32 / 64 / 128
+ *   RESPAIR  X3       w_x3, ci_pad, w2, bias, bias2  respair_x3 (split planes [2][k][C][C]), C = 32 / 64
+ *   RESPAIR  MF       w_mf, w2, bias, bias2          respair_f32w_kernel (both 16-byte aligned), C = 32 / 64
+ *   AA_ACT   NONE     w (the filter)
+ *   other    NONE     -
+ * It also refuses an X3 op whose ci_pad is not Ci rounded up to 32, MF weights that are not 16-byte aligned, and a RESPAIR without
+ * Ci == Co or whose x / out differ in time length (buffer tmul; in_tmul / out_tmul for the I/O ids).  The failing op's index is in
+ * vb_last_error().  Conditions that depend on T or on buffer addresses are checked when the op runs. */
+enum { VB_WFMT_NONE = 0, VB_WFMT_F32 = 1, VB_WFMT_X3 = 2, VB_WFMT_MF = 3, VB_WFMT_BUF_F32 = 4, VB_WFMT_BUF_X3 = 5 };
 #define VB_BUF_INPUT (-2)
 #define VB_BUF_OUTPUT (-3)
 typedef struct {
     int kind;
+    int wfmt;                             /* VB_WFMT_*: which weight fields the op reads (table above) */
     int x, out, res, stats, w_buf;        /* buffer ids, -1 = none */
     const float* w; const float* bias; const float* gn_gamma; const float* gn_beta;
     int Ci, Co, ksize, dil, pad, upsample2, in_act, out_act, out_transposed, tr_stride, tr_pad, tr_k, gn_groups;
     float in_slope, out_slope, alpha, beta, acc_scale;
-    const void* w_x3; int ci_pad;   /* optional split-bf16 weights [2][phase][tap][Co][ci_pad]: selects the bf16x3 MFMA conv kernel */
-    const void* w2_x3; const float* bias2;   /* VB_OP_RESPAIR: second convolution (w_x3 == NULL: exact-fp32 pair, w and w2_x3 are the fp32
-                                              * packed [k][Ci][Co] weights of the two convolutions; channels 32 / 64 / 128; ci_pad == -2: both are
-                                              * minimal-filtering pseudo-tap weights [P][C][C] and the pair runs respair_f32w_kernel, C = 32).
-                                              * VB_OP_CONV with w_x3 == NULL: optional fp32 minimal-filtering weights [P][Ci][Co] of the
-                                              * same filter (versband_amd/pack.py:pack_conv_mf) - the layer then runs conv1d_f32w_kernel
-                                              * (fp32 products, F(2,3): ~1.4-1.5x fewer of them) where its conditions hold */
+    const void* w_x3; int ci_pad;            /* X3: split-bf16 weights and their padded input-channel count */
+    const float* w_mf;                       /* MF: F(2,3) pseudo-tap weights */
+    const void* w2; const float* bias2;      /* VB_OP_RESPAIR: the second convolution's weights (in the op's format) and bias */
     int in_stride, in_phase;                 /* VB_OP_CONV: the convolution reads x[i*in_stride + in_phase] (0/1 = plain) */
     int x_planes;                            /* VB_OP_CONV: x is a VB_OP_XT_PLANES buffer (upsample2 then describes how it was made) */
 } vb_net_op;
@@ -317,8 +337,8 @@ int vb_conv1d_f32(const float* x, const float* w, const float* bias, int B, int 
                   const void* w_x3, int ci_pad, void* stream);
 /* Conv1d in fp32 with 1-D minimal filtering (conv1d_f32w.hip; the HiFi-GAN ResBlock convolutions, vocoder/hifigan/modules/hifigan.py:27-64):
  * out = beta*out + alpha*(conv_{k,dil,pad}(act(x)) + bias + res); w = packed [k][Ci][Co] (the fallback when the layer is not eligible),
- * w_mf = the same filter as F(2,3) pseudo-taps [P][Ci][Co] (pack.py:pack_conv_mf).  k = 3 / 5 / 7 / 11, stride 1, Ci % 16 == 0, Co >= 64,
- * T % 4 == 0.  Agrees with vb_conv1d_f32 to fp32 roundoff, not bit for bit. */
+ * w_mf = the same filter as F(2,3) pseudo-taps [P][Ci][Co] (pack.py:pack_conv_mf).  k = 3 / 5 / 7 / 11, stride 1, Ci % 16 == 0, Co % 4 == 0,
+ * Co >= 32, T % 4 == 0.  Agrees with vb_conv1d_f32 to fp32 roundoff, not bit for bit. */
 int vb_conv1d_f32_mf(const float* x, const float* w, const float* w_mf, const float* bias, int B, int Ci, int T_in, int Co, int ksize, int dil,
                      int pad, int T_out, int in_act, float in_slope, const float* res, float alpha, float beta, float* out, void* stream);
 /* HiFi-GAN ResBlock1 pair in exact fp32, one launch (vocoder/hifigan/modules/hifigan.py:27-64; respair_f32.hip):
@@ -327,7 +347,8 @@ int vb_conv1d_f32_mf(const float* x, const float* w, const float* w_mf, const fl
 int vb_respair_f32(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, int B, int C, int T, int k, int dil,
                    float slope, float alpha, float beta, float* out, void* stream);
 /* The same pair with F(2,3) minimal filtering in both convolutions (respair_f32w.hip): w1_mf / w2_mf = pseudo-tap weights [P][C][C]
- * (pack.py:pack_conv_mf); C = 32, k = 3 / 7 / 11, (k-1)*dil <= 60, T % 4 == 0.  Equals two vb_conv1d_f32_mf launches bit for bit. */
+ * (pack.py:pack_conv_mf); C = 32 / 64, k = 3 / 7 / 11, (k-1)*dil <= 60, T % 4 == 0.  Agrees with two vb_conv1d_f32_mf launches to fp32
+ * roundoff, not bit for bit. */
 int vb_respair_f32_mf(const float* x, const float* w1_mf, const float* b1, const float* w2_mf, const float* b2, int B, int C, int T, int k, int dil,
                       float slope, float alpha, float beta, float* out, void* stream);
 /* counter-based Gumbel draws: out[rows][w], rows = n_branch*B*T */

@@ -69,16 +69,18 @@ class BufDesc(C.Structure):
 
 
 class NetOp(C.Structure):
-    _fields_ = ([("kind", c_int)] + [(n, c_int) for n in ("x", "out", "res", "stats", "w_buf")]
+    _fields_ = ([("kind", c_int), ("wfmt", c_int)] + [(n, c_int) for n in ("x", "out", "res", "stats", "w_buf")]
                 + [(n, c_void_p) for n in ("w", "bias", "gn_gamma", "gn_beta")]
                 + [(n, c_int) for n in ("Ci", "Co", "ksize", "dil", "pad", "upsample2", "in_act", "out_act", "out_transposed",
                                         "tr_stride", "tr_pad", "tr_k", "gn_groups")]
                 + [(n, c_float) for n in ("in_slope", "out_slope", "alpha", "beta", "acc_scale")]
-                + [("w_x3", c_void_p), ("ci_pad", c_int), ("w2_x3", c_void_p), ("bias2", c_void_p), ("in_stride", c_int), ("in_phase", c_int), ("x_planes", c_int)])
+                + [("w_x3", c_void_p), ("ci_pad", c_int), ("w_mf", c_void_p), ("w2", c_void_p), ("bias2", c_void_p), ("in_stride", c_int),
+                   ("in_phase", c_int), ("x_planes", c_int)])
 
 
 OP_CONV, OP_GN_STATS, OP_SOFTMAX_T, OP_SPLIT_PLANES, OP_RESPAIR, OP_GN_APPLY, OP_AA_ACT, OP_XT_PLANES = 0, 1, 2, 3, 4, 5, 6, 7
 ACT_NONE, ACT_LRELU, ACT_GN_SWISH, ACT_TANH, ACT_GN = 0, 1, 2, 3, 4
+WFMT_NONE, WFMT_F32, WFMT_X3, WFMT_MF, WFMT_BUF_F32, WFMT_BUF_X3 = 0, 1, 2, 3, 4, 5
 BUF_INPUT, BUF_OUTPUT = -2, -3
 NET_VAE, NET_VOCODER, NET_VAE_ENCODER = 0, 1, 2
 

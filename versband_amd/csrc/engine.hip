@@ -708,7 +708,6 @@ static int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float*
                 a.T_in = o.upsample2 ? tlen(o.x) / 2 : tlen(o.x);
             }
             a.Ci = o.Ci > 0 ? o.Ci : tlen(o.x);            // dynamic channel counts: the VAE attention contracts over T
-            if (o.w_buf != -1) { a.w = ptr(o.w_buf); a.w_bstride = bstride(o.w_buf); } else { a.w = o.w; }
             a.bias = o.bias; a.Co = o.Co > 0 ? o.Co : tlen(o.out); a.ksize = o.ksize; a.dil = o.dil; a.pad = o.pad; a.upsample2 = o.upsample2;
             a.in_stride = o.in_stride > 1 ? o.in_stride : 1; a.in_phase = o.in_phase;
             a.in_act = o.in_act; a.in_slope = o.in_slope;
@@ -721,17 +720,24 @@ static int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float*
             if (o.res != -1) { a.res = ptr(o.res); a.res_bstride = bstride(o.res); }
             a.alpha = o.alpha; a.beta = o.beta; a.acc_scale = o.acc_scale; a.out_act = o.out_act; a.out_slope = o.out_slope;
             a.out_transposed = o.out_transposed; a.B = B; a.tr_stride = o.tr_stride; a.tr_pad = o.tr_pad; a.tr_k = o.tr_k;
-            if (o.w_buf != -1 && o.ci_pad == -1) {
+            // weights by format (vb_net_load checked the fields); launch_conv1d picks the kernel
+            switch (o.wfmt) {
+            case VB_WFMT_F32: a.w = o.w; break;
+            case VB_WFMT_MF: a.w = o.w; a.w_mf = o.w_mf; break;      // w: the direct kernels where conv1d_f32w_kernel's run-time conditions fail
+            case VB_WFMT_X3: {
+                const int phases = o.tr_stride > 1 ? o.tr_stride : 1;
+                const int ntaps = o.tr_stride > 1 ? (o.tr_k + o.tr_stride - 1) / o.tr_stride : o.ksize;
+                a.w = o.w;                                            // (the one-output-channel kernel reads the fp32 copy)
+                a.wp = (const bf16_t*)o.w_x3; a.Ci_pad = o.ci_pad; a.wp_plane = (int64_t)phases * ntaps * a.Co * o.ci_pad;
+                break;
+            }
+            case VB_WFMT_BUF_F32: a.w = ptr(o.w_buf); a.w_bstride = bstride(o.w_buf); break;
+            case VB_WFMT_BUF_X3:
                 // per-batch split planes [2][B][Co][Ci_pad] written by an earlier VB_OP_SPLIT_PLANES
                 a.Ci_pad = (a.Ci + 31) / 32 * 32;
                 a.wp = reinterpret_cast<const bf16_t*>(ptr(o.w_buf)); a.wp_bstride = (int64_t)a.Co * a.Ci_pad;
-                a.wp_plane = (int64_t)B * a.wp_bstride; a.w = nullptr;
-            } else if (o.w_x3 && o.w_buf == -1) {
-                const int phases = o.tr_stride > 1 ? o.tr_stride : 1;
-                const int ntaps = o.tr_stride > 1 ? (o.tr_k + o.tr_stride - 1) / o.tr_stride : o.ksize;
-                a.wp = (const bf16_t*)o.w_x3; a.Ci_pad = o.ci_pad; a.wp_plane = (int64_t)phases * ntaps * a.Co * o.ci_pad;
-            } else if (o.w2_x3 && o.w_buf == -1) {
-                a.w_mf = (const float*)o.w2_x3;        // fp32 minimal-filtering weights (VB_OP_CONV, w_x3 == NULL): conv1d_f32w_kernel where it applies
+                a.wp_plane = (int64_t)B * a.wp_bstride;
+                break;
             }
             VB_TRY(launch_conv1d(a, st));
         } else if (o.kind == VB_OP_GN_APPLY) {
@@ -745,23 +751,20 @@ static int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float*
         } else if (o.kind == VB_OP_AA_ACT) {
             VB_TRY(launch_aa_act(ptr(o.x), o.gn_gamma, o.gn_beta, o.w, B, o.Ci, tlen(o.x), ptr(o.out), st));
         } else if (o.kind == VB_OP_RESPAIR) {
-            if (!o.w_x3) {
-                // exact-fp32 pair (fp32 vocoder): w / w2_x3 are the fp32 packed [k][Ci][Co] weights of the two convolutions
+            if (o.wfmt == VB_WFMT_X3) {
+                RespairArgs r;
+                r.x = ptr(o.x); r.out = ptr(o.out); r.B = B; r.C = o.Ci; r.T = tlen(o.x); r.k = o.ksize; r.dil = o.dil;
+                r.w1 = (const bf16_t*)o.w_x3; r.w2 = (const bf16_t*)o.w2; r.b1 = o.bias; r.b2 = o.bias2;
+                r.slope = o.in_slope; r.alpha = o.alpha; r.beta = o.beta;
+                VB_TRY(launch_respair(r, st));
+            } else {
                 RespairF32Args r;
                 r.x = ptr(o.x); r.out = ptr(o.out); r.B = B; r.C = o.Ci; r.T = tlen(o.x); r.k = o.ksize; r.dil = o.dil;
-                r.w1 = o.w; r.w2 = (const float*)o.w2_x3; r.b1 = o.bias; r.b2 = o.bias2;
+                r.w1 = o.wfmt == VB_WFMT_MF ? o.w_mf : o.w; r.w2 = (const float*)o.w2; r.b1 = o.bias; r.b2 = o.bias2;
                 r.slope = o.in_slope; r.alpha = o.alpha; r.beta = o.beta;
-                if (!r.w1 || !r.w2 || !r.b1 || !r.b2 || tlen(o.out) != r.T) VB_FAIL(VB_E_INVALID, "net op %zu: incomplete fp32 respair", oi);
-                if (o.ci_pad == -2) VB_TRY(launch_respair_f32w(r, st));      // w / w2_x3 are minimal-filtering pseudo-tap weights (fp32mf)
+                if (o.wfmt == VB_WFMT_MF) VB_TRY(launch_respair_f32w(r, st));
                 else VB_TRY(launch_respair_f32(r, st));
-                continue;
             }
-            RespairArgs r;
-            r.x = ptr(o.x); r.out = ptr(o.out); r.B = B; r.C = o.Ci; r.T = tlen(o.x); r.k = o.ksize; r.dil = o.dil;
-            r.w1 = (const bf16_t*)o.w_x3; r.w2 = (const bf16_t*)o.w2_x3; r.b1 = o.bias; r.b2 = o.bias2;
-            r.slope = o.in_slope; r.alpha = o.alpha; r.beta = o.beta;
-            if (!r.w1 || !r.w2 || !r.b1 || !r.b2 || tlen(o.out) != r.T) VB_FAIL(VB_E_INVALID, "net op %zu: incomplete respair", oi);
-            VB_TRY(launch_respair(r, st));
         } else if (o.kind == VB_OP_SPLIT_PLANES) {
             const int rows = o.Co > 0 ? o.Co : tlen(o.x), cols = o.Ci > 0 ? o.Ci : tlen(o.x);
             const int cpad = (cols + 31) / 32 * 32;
@@ -779,7 +782,7 @@ static int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float*
 extern "C" {
 
 const char* vb_last_error(void) { return g_vb_err; }
-int vb_abi_version(void) { return 2; }
+int vb_abi_version(void) { return 3; }
 // (vb_source_digest() lives in a two-line translation unit versband_amd/build.py generates: csrc/build/vb_digest.cpp)
 int vb_has_experiments(void) {
 #ifdef VB_EXPERIMENTS
@@ -1137,18 +1140,64 @@ int vb_melnet_forward(vb_ctx* ctx, const float* wav, int B, int L, int center, f
     return VB_OK;
 }
 
+// the weight fields each allowed (kind, wfmt) pair of include/versband_hip.h reads; -1 = the pair is not allowed
+enum { NW_W = 1, NW_X3 = 2, NW_MF = 4, NW_W2 = 8, NW_BUF = 16 };
+static int net_op_fields(int kind, int wfmt) {
+    switch (kind) {
+    case VB_OP_CONV:
+        switch (wfmt) {
+        case VB_WFMT_F32: return NW_W;
+        case VB_WFMT_X3: return NW_X3 | NW_W;
+        case VB_WFMT_MF: return NW_MF | NW_W;
+        case VB_WFMT_BUF_F32: case VB_WFMT_BUF_X3: return NW_BUF;
+        }
+        return -1;
+    case VB_OP_RESPAIR:
+        switch (wfmt) {
+        case VB_WFMT_F32: return NW_W | NW_W2;
+        case VB_WFMT_X3: return NW_X3 | NW_W2;
+        case VB_WFMT_MF: return NW_MF | NW_W2;
+        }
+        return -1;
+    case VB_OP_AA_ACT: return wfmt == VB_WFMT_NONE ? NW_W : -1;
+    case VB_OP_GN_STATS: case VB_OP_SOFTMAX_T: case VB_OP_SPLIT_PLANES: case VB_OP_GN_APPLY: case VB_OP_XT_PLANES:
+        return wfmt == VB_WFMT_NONE ? 0 : -1;
+    }
+    return -1;
+}
+
 int vb_net_load(vb_ctx* ctx, int which, const vb_net_op* ops, int n_ops, const vb_buf_desc* bufs, int n_bufs, int in_channels,
                 int out_channels, int in_tmul, int out_tmul) {
     if (!ctx || which < 0 || which > 2 || !ops || n_ops < 1 || in_tmul < 1 || out_tmul < 1) VB_FAIL(VB_E_INVALID, "net_load: bad argument");
-    NetProgram& n = ctx->nets[which];
-    n.ops.assign(ops, ops + n_ops);
-    n.bufs.assign(bufs, bufs + n_bufs);
+    auto tmul = [&](int id) { return id == VB_BUF_INPUT ? in_tmul : (id == VB_BUF_OUTPUT ? out_tmul : bufs[id].tmul); };
     for (int i = 0; i < n_ops; ++i) {
         const vb_net_op& o = ops[i];
         const int ids[5] = {o.x, o.out, o.res, o.stats, o.w_buf};
         for (int id : ids)
             if (id >= n_bufs || (id < -3)) VB_FAIL(VB_E_INVALID, "net_load: op %d references buffer %d of %d", i, id, n_bufs);
+        const int f = net_op_fields(o.kind, o.wfmt);
+        if (f < 0) VB_FAIL(VB_E_INVALID, "net_load: op %d: kind %d has no weight format %d", i, o.kind, o.wfmt);
+        const struct { int bit; bool set; const char* name; } slots[] = {
+            {NW_W, o.w != nullptr, "w"}, {NW_X3, o.w_x3 != nullptr, "w_x3"}, {NW_MF, o.w_mf != nullptr, "w_mf"}, {NW_W2, o.w2 != nullptr, "w2"},
+            {NW_BUF, o.w_buf != -1, "w_buf"}};
+        for (const auto& sl : slots)
+            if (sl.set != ((f & sl.bit) != 0))
+                VB_FAIL(VB_E_INVALID, "net_load: op %d (kind %d, weight format %d): %s is %s", i, o.kind, o.wfmt, sl.name,
+                        sl.set ? "set but not read" : "missing");
+        if (o.wfmt == VB_WFMT_X3 && o.ci_pad != (o.Ci + 31) / 32 * 32)
+            VB_FAIL(VB_E_INVALID, "net_load: op %d: split weights padded to %d input channels, not %d rounded up to 32", i, o.ci_pad, o.Ci);
+        if (o.wfmt == VB_WFMT_MF && ((reinterpret_cast<uintptr_t>(o.w_mf) & 15) || (reinterpret_cast<uintptr_t>(o.w2) & 15)))
+            VB_FAIL(VB_E_INVALID, "net_load: op %d: minimal-filtering weights are not 16-byte aligned", i);
+        if (o.kind == VB_OP_RESPAIR) {
+            if (!o.bias || !o.bias2) VB_FAIL(VB_E_INVALID, "net_load: op %d: respair without both biases", i);
+            if (o.Ci != o.Co) VB_FAIL(VB_E_INVALID, "net_load: op %d: respair with Ci %d != Co %d", i, o.Ci, o.Co);
+            if (o.x == -1 || o.out == -1 || tmul(o.x) != tmul(o.out))
+                VB_FAIL(VB_E_INVALID, "net_load: op %d: respair input and output differ in length", i);
+        }
     }
+    NetProgram& n = ctx->nets[which];
+    n.ops.assign(ops, ops + n_ops);
+    n.bufs.assign(bufs, bufs + n_bufs);
     n.in_ch = in_channels; n.out_ch = out_channels; n.in_tmul = in_tmul; n.out_tmul = out_tmul; n.loaded = true;
     return VB_OK;
 }

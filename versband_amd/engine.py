@@ -260,16 +260,27 @@ class T5Engine:
 # ---------------------------------------------------------------------------
 
 
+def mf_conv_eligible(w: Tensor, Ci: int, Co: int, k: int, dil: int, in_act: int, upsample2: int, out_transposed: int, tr_stride: int,
+                     in_stride: int) -> bool:
+    """Whether an "fp32mf" convolution also carries F(2,3) minimal-filtering weights: weights packed [k][Ci][Co], stride 1, no
+    upsampling, channel-major output, k = 3 / 5 / 7 / 11 with dil <= 8 and (k - 1) * dil <= 60, Ci % 16 == 0, Co % 4 == 0, Co >= 64
+    (conv1d_f32w_kernel runs 64- or 128-channel output tiles), input activation none / LeakyReLU.  launch_conv1d re-checks at run time
+    what depends on T and on the buffers (T % 4 == 0, 16-byte aligned x / out / res / weights) and runs the direct kernels on w where
+    those fail; it would also take Co >= 32."""
+    return (tr_stride == 1 and in_stride == 1 and not upsample2 and not out_transposed and k in (3, 5, 7, 11) and dil <= 8 and
+            (k - 1) * dil <= 60 and Ci % 16 == 0 and Co % 4 == 0 and Co >= 64 and in_act in (L.ACT_NONE, L.ACT_LRELU) and
+            tuple(w.shape) == (k, Ci, Co))
+
+
 class NetBuilder:
     """Flattens a conv network into the vb_net_op list executed by the C++ runtime."""
 
     def __init__(self, device, precision: str = "split"):
         assert precision in ("split", "fp32", "fp32mf")
         self.device = device
-        # "split": bf16x3 MFMA conv kernel (fp32-class); "fp32": exact f32 MFMA kernel; "fp32mf": the fp32 op list with F(2,3) minimal
-        # filtering on the stride-1 k = 3 / 5 / 7 / 11 convolutions of >= 128 output channels (one tile shape: 128 co; narrower layers are faster direct) (fp32 products, ~1.45x fewer; conv1d_f32w.hip)
-        self.mf = precision == "fp32mf"
-        self.precision = "fp32" if self.mf else precision
+        # "split": bf16x3 MFMA conv kernels (fp32-class); "fp32": the exact-fp32 MFMA kernels; "fp32mf": the fp32 op list in which the
+        # layers of mf_conv_eligible and the 32 / 64-channel pairs run F(2,3) minimal filtering (fp32 products, ~1.45x fewer)
+        self.precision = precision
         self.ops: List[L.NetOp] = []
         self.bufs: List[Tuple[int, int, int]] = []
         self.free: Dict[Tuple[int, int, int], List[int]] = {}
@@ -303,29 +314,36 @@ class NetBuilder:
         """f32 [B][rows][cols] buffer -> split-bf16 planes [2][B][rows][roundup(cols,32)] (-1 = the buffer's time length)."""
         self.ops.append(L.NetOp(kind=L.OP_SPLIT_PLANES, x=x, out=out, res=-1, stats=-1, w_buf=-1, Ci=cols, Co=rows))
 
+    def weights(self, w: Optional[Tensor], w_buf: int = -1, mf: bool = False, fallback: bool = True) -> dict:
+        """One layer's weights packed for this builder's precision -> the op's format fields (include/versband_hip.h, VB_WFMT_*).
+        w: fp32 packed [phase][tap][Ci][Co]; w_buf: per-batch weights in a buffer instead (split: written by split_planes); mf: the
+        layer qualifies for minimal filtering (fp32mf only); fallback: an X3 / MF conv keeps w as well (what the one-output-channel
+        kernel and the direct kernels read)."""
+        if w_buf != -1:
+            return dict(wfmt=L.WFMT_BUF_X3 if self.precision == "split" else L.WFMT_BUF_F32)
+        if self.precision == "split":
+            planes, ci_pad = pack.pack_conv_x3(w.to(self.device))
+            self.keep.append(planes)
+            f = dict(wfmt=L.WFMT_X3, w_x3=planes.data_ptr(), ci_pad=ci_pad)
+        elif self.precision == "fp32mf" and mf:
+            f = dict(wfmt=L.WFMT_MF, w_mf=self._t(pack.pack_conv_mf(w.permute(2, 1, 0))))      # (w arrives packed [k][Ci][Co])
+        else:
+            return dict(wfmt=L.WFMT_F32, w=self._t(w))
+        if fallback:
+            f["w"] = self._t(w)
+        return f
+
     def respair(self, x: int, out: int, ch: int, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, k: int, dil: int, slope: float,
                 alpha: float, beta: float):
-        """Fused HiFi-GAN ResBlock1 pair (w1/w2 fp32 packed [k][Ci][Co]); narrow stages only (ch = 32 or 64; fp32 mode: 32 / 64 / 128)."""
-        if self.precision == "fp32" and self.mf and ch in (32, 64) and k in (3, 7, 11) and not os.environ.get("VB_MF_PAIRS_OFF"):
-            # fp32mf: both convolutions of the pair by F(2,3) minimal filtering, intermediate in LDS (respair_f32w.hip); ci_pad = -2 marks the
-            # weights as pseudo-taps [P][C][C]
-            self.ops.append(L.NetOp(kind=L.OP_RESPAIR, x=x, out=out, res=-1, stats=-1, w_buf=-1, w=self._t(pack.pack_conv_mf(w1.permute(2, 1, 0))),
-                                    bias=self._t(b1), bias2=self._t(b2), Ci=ch, Co=ch, ksize=k, dil=dil, in_slope=slope, alpha=alpha, beta=beta,
-                                    w_x3=None, w2_x3=self._t(pack.pack_conv_mf(w2.permute(2, 1, 0))), ci_pad=-2))
-            return
-        if self.precision == "fp32":
-            # exact-fp32 pair kernel (respair_f32.hip): the packed fp32 weights go in as they are
-            self.ops.append(L.NetOp(kind=L.OP_RESPAIR, x=x, out=out, res=-1, stats=-1, w_buf=-1, w=self._t(w1), bias=self._t(b1),
-                                    bias2=self._t(b2), Ci=ch, Co=ch, ksize=k, dil=dil, in_slope=slope, alpha=alpha, beta=beta,
-                                    w_x3=None, w2_x3=self._t(w2), ci_pad=ch))
-            return
-        p1, c1 = pack.pack_conv_x3(w1.to(self.device))
-        p2, c2 = pack.pack_conv_x3(w2.to(self.device))
-        assert c1 == ch and c2 == ch
-        self.keep += [p1, p2]
-        self.ops.append(L.NetOp(kind=L.OP_RESPAIR, x=x, out=out, res=-1, stats=-1, w_buf=-1, bias=self._t(b1), bias2=self._t(b2),
-                                Ci=ch, Co=ch, ksize=k, dil=dil, in_slope=slope, alpha=alpha, beta=beta, w_x3=p1.data_ptr(),
-                                w2_x3=p2.data_ptr(), ci_pad=ch))
+        """Fused HiFi-GAN ResBlock1 pair (w1/w2 fp32 packed [k][Ci][Co]); narrow stages only (ch = 32 or 64; fp32 mode: 32 / 64 / 128).
+        fp32mf: the 32 / 64-channel pairs of k = 3 / 7 / 11 run minimal filtering in both convolutions (respair_f32w.hip),
+        VB_MF_PAIRS_OFF=1 the direct pair kernel."""
+        mf = ch in (32, 64) and k in (3, 7, 11) and not os.environ.get("VB_MF_PAIRS_OFF")
+        f = self.weights(w1, mf=mf, fallback=False)
+        slot = {L.WFMT_F32: "w", L.WFMT_X3: "w_x3", L.WFMT_MF: "w_mf"}[f["wfmt"]]     # the second convolution's weights go to w2
+        f["w2"] = self.weights(w2, mf=mf, fallback=False)[slot]
+        self.ops.append(L.NetOp(kind=L.OP_RESPAIR, x=x, out=out, res=-1, stats=-1, w_buf=-1, bias=self._t(b1), bias2=self._t(b2), Ci=ch, Co=ch,
+                                ksize=k, dil=dil, in_slope=slope, alpha=alpha, beta=beta, **f))
 
     def aa_act(self, x: int, out: int, ch: int, alpha: Tensor, beta: Optional[Tensor], logscale: bool):
         """BigVGAN Activation1d(Snake / SnakeBeta): out = down2(act(up2(x))) (alias_free_torch/act.py)."""
@@ -344,8 +362,7 @@ class NetBuilder:
     def conv(self, x: int, out: int, Ci: int, Co: int, w: Optional[Tensor] = None, bias: Optional[Tensor] = None, k: int = 1,
              dil: int = 1, pad: int = 0, res: int = -1, stats: int = -1, gamma=None, beta_gn=None, in_act=L.ACT_NONE,
              in_slope=0.0, out_act=L.ACT_NONE, out_slope=0.0, upsample2=0, out_transposed=0, w_buf=-1, alpha=1.0, beta=0.0,
-             acc_scale=1.0, tr_stride=1, tr_pad=0, tr_k=0, groups=32, w_buf_planes=False, in_stride=1, in_phase=0, x_is_planes=False):
-        w_x3, ci_pad = None, (-1 if w_buf_planes else 0)
+             acc_scale=1.0, tr_stride=1, tr_pad=0, tr_k=0, groups=32, in_stride=1, in_phase=0, x_is_planes=False):
         tmp = -1
         x_planes = int(bool(x_is_planes))
         if (self.precision == "split" and not x_planes and w is not None and w_buf == -1 and x >= 0 and Co >= self.XT_MIN_CO and Ci % 32 == 0
@@ -354,27 +371,19 @@ class NetBuilder:
             # tile of the convolution DMAs its window from there, instead of each tile redoing norm / swish / split while staging
             tmp = self.xt_planes(x, Ci, stats, gamma, beta_gn, in_act, in_slope, upsample2, groups)
             x, stats, gamma, beta_gn, in_act, x_planes = tmp, -1, None, None, L.ACT_NONE, 1
-        if (self.precision == "fp32" and in_act in (L.ACT_GN_SWISH, L.ACT_GN) and stats >= 0 and w is not None and w_buf == -1 and x >= 0
+        if (self.precision != "split" and in_act in (L.ACT_GN_SWISH, L.ACT_GN) and stats >= 0 and w is not None and w_buf == -1 and x >= 0
                 and Ci % 16 == 0 and Co % 4 == 0 and in_stride == 1 and tr_stride == 1 and not os.environ.get("VB_FP32_NO_PREPASS")):
             # exact-fp32 mode: GroupNorm (+ swish) is applied ONCE by gn_apply_kernel and the DMA-fed fp32 kernel (conv1d_f32g_kernel)
             # reads the activated tensor; the register-staged kernel redid norm + swish + expf for every output-channel tile
             # (12 times on the 1536-channel layers: 2.3 ms for an 85-GFLOP layer).  VB_FP32_NO_PREPASS=1 keeps the old op list (A/B).
             tmp = self.gn_apply(x, Ci, stats, gamma, beta_gn, in_act, groups)
             x, stats, gamma, beta_gn, in_act = tmp, -1, None, None, L.ACT_NONE
-        if self.precision == "split" and w is not None and w_buf == -1:
-            planes, ci_pad = pack.pack_conv_x3(w.to(self.device))
-            self.keep.append(planes)
-            w_x3 = planes.data_ptr()
-        w_mf = None
-        if (self.mf and w is not None and w_buf == -1 and tr_stride == 1 and in_stride == 1 and not upsample2 and not out_transposed and
-                k in (3, 5, 7, 11) and (k - 1) * dil <= 60 and dil <= 8 and Ci % 16 == 0 and Co % 4 == 0 and Co >= 64 and
-                in_act in (L.ACT_NONE, L.ACT_LRELU) and w.shape == (k, Ci, Co)):
-            w_mf = self._t(pack.pack_conv_mf(w.permute(2, 1, 0)))          # (w arrives packed [k][Ci][Co])
-        op = L.NetOp(kind=L.OP_CONV, x=x, out=out, res=res, stats=stats, w_buf=w_buf, w=self._t(w), bias=self._t(bias), w2_x3=w_mf,
-                     gn_gamma=self._t(gamma), gn_beta=self._t(beta_gn), Ci=Ci, Co=Co, ksize=k, dil=dil, pad=pad,
-                     upsample2=upsample2, in_act=in_act, out_act=out_act, out_transposed=out_transposed, tr_stride=tr_stride,
-                     tr_pad=tr_pad, tr_k=tr_k, gn_groups=groups, in_slope=in_slope, out_slope=out_slope, alpha=alpha, beta=beta,
-                     acc_scale=acc_scale, w_x3=w_x3, ci_pad=ci_pad, in_stride=in_stride, in_phase=in_phase, x_planes=x_planes)
+        mf = w is not None and mf_conv_eligible(w, Ci, Co, k, dil, in_act, upsample2, out_transposed, tr_stride, in_stride)
+        op = L.NetOp(kind=L.OP_CONV, x=x, out=out, res=res, stats=stats, w_buf=w_buf, bias=self._t(bias), gn_gamma=self._t(gamma),
+                     gn_beta=self._t(beta_gn), Ci=Ci, Co=Co, ksize=k, dil=dil, pad=pad, upsample2=upsample2, in_act=in_act,
+                     out_act=out_act, out_transposed=out_transposed, tr_stride=tr_stride, tr_pad=tr_pad, tr_k=tr_k, gn_groups=groups,
+                     in_slope=in_slope, out_slope=out_slope, alpha=alpha, beta=beta, acc_scale=acc_scale, in_stride=in_stride,
+                     in_phase=in_phase, x_planes=x_planes, **self.weights(w, w_buf, mf))
         self.ops.append(op)
         self.release(tmp)
 
@@ -510,14 +519,14 @@ def _vae_block_builders(nb: "NetBuilder", g: Dict[str, Tensor]):
             nb.split_planes(q, qp, rows=-1, cols=c)                            # q^T [T][C] -> planes
             nb.split_planes(v, vp, rows=c, cols=-1)                            # v [C][T] -> planes, T padded
             tmp = [qp, vp]
-            nb.conv(k, s, c, -1, w_buf=qp, w_buf_planes=True, acc_scale=float(int(c) ** (-0.5)))
+            nb.conv(k, s, c, -1, w_buf=qp, acc_scale=float(int(c) ** (-0.5)))
         else:
             nb.conv(k, s, c, -1, w_buf=q, acc_scale=float(int(c) ** (-0.5)))  # w[b,i,j] = sum_c q[c,i] k[c,j] * C^-0.5
         pT = nb.buf(0, tm, True)
         nb.softmax_t(s, pT)
         a = nb.buf(c, tm)
         if split:
-            nb.conv(pT, a, -1, c, w_buf=vp, w_buf_planes=True)
+            nb.conv(pT, a, -1, c, w_buf=vp)
         else:
             nb.conv(pT, a, -1, c, w_buf=v)                                     # h[c,i] = sum_j v^T[j,c] P[i,j]
         out = nb.buf(c, tm)
