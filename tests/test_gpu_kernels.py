@@ -493,6 +493,106 @@ def test_fp32_minimal_filtering_switches(lib, monkeypatch):
         lib.vb_tune_reload()
 
 
+def _at(t, off):
+    """t on the device, starting `off` floats into a larger (256-B aligned) allocation: the same values at another alignment"""
+    buf = torch.full((t.numel() + 4,), float("nan"), device="cuda")
+    v = buf[off:off + t.numel()].view(t.shape)
+    v.copy_(t)
+    _KEEP.append(buf)
+    return v
+
+
+@pytest.mark.parametrize("C,k,dil", [(64, 3, 1), (64, 7, 3), (64, 11, 5), (128, 3, 1), (128, 7, 3), (128, 11, 5)])
+def test_fp32_minimal_filtering_falls_back_to_the_direct_kernel(lib, C, k, dil):
+    """vb_conv1d_f32_mf takes the minimal-filtering kernel only when the run allows it (conv1d_f32.hip, use_mf: T % 4 == 0, row strides % 4,
+    16-B aligned x / out / res, Ci % 16 == 0, Co >= 32); otherwise it runs the direct kernels on w - the call must then return exactly the bits
+    of vb_conv1d_f32 on the same pointers (odd latent lengths of the VAE and chunk windows of long-form vocoding take this path), and stay at
+    fp32 roundoff from float64.  Control: the same layer at T = 1000 with aligned buffers takes minimal filtering, so it must NOT equal the
+    direct kernel - otherwise a dispatcher that never took it would pass.  (Misaligned buffers go only where the direct kernels read them
+    every day: test_conv1d_f32, T = 37 / 50.)"""
+    B = 2
+    pad = (k - 1) * dil // 2
+
+    def layer(Ci, Co, T):
+        w = rnd((Co, Ci, k), f"fw{Ci}_{Co}_{k}", 1.0 / (Ci * k) ** 0.5)
+        x, b, r = rnd((B, Ci, T), f"fx{Ci}_{T}"), rnd((Co,), f"fb{Co}"), rnd((B, Co, T), f"fr{Co}_{T}")
+        ref = F.conv1d(F.leaky_relu(x.double(), 0.1), w.double(), b.double(), dilation=dil, padding=pad) + r.double()
+        return x, w, b, r, ref
+
+    def both(x, wpk, wmf, b, r, out, Ci, Co, T):
+        """(minimal-filtering call, direct call) into the same output buffer, alpha = 1, beta = 0"""
+        out.fill_(float("nan"))
+        L.check(lib.vb_conv1d_f32_mf(L.ptr(x), L.ptr(wpk), L.ptr(wmf), L.ptr(b), B, Ci, T, Co, k, dil, pad, T, 1, 0.1, L.ptr(r), 1.0, 0.0,
+                                     L.ptr(out), L.stream_ptr()), "conv mf")
+        sync()
+        mf = out.clone()
+        out.fill_(float("nan"))
+        L.check(lib.vb_conv1d_f32(L.ptr(x), L.ptr(wpk), L.ptr(b), B, Ci, T, Co, k, dil, pad, 1, 0, 0, T, 1, 0.1, L.ptr(r), L.ptr(out), None, 0,
+                                  L.stream_ptr()), "conv")
+        sync()
+        return mf, out.clone()
+
+    def run(Ci, Co, T, offs=(0, 0, 0)):
+        x, w, b, r, ref = layer(Ci, Co, T)
+        wpk, wmf, bd = dev(pack.pack_conv(w)), dev(pack.pack_conv_mf(w)), dev(b)
+        xd, rd = _at(x, offs[0]), _at(r, offs[2])
+        out = _at(torch.zeros(B, Co, T), offs[1])
+        mf, direct = both(xd, wpk, wmf, bd, rd, out, Ci, Co, T)
+        return mf, direct, ref
+
+    # control: eligible run -> minimal filtering (different bits, same distance from float64)
+    mf, direct, ref = run(C, C, 1000)
+    assert torch.isfinite(mf).all() and not torch.equal(mf, direct), "the eligible run did not take minimal filtering"
+    assert rel_l2(mf, ref) < 2e-6 and rel_l2(direct, ref) < 2e-6, describe("conv mf (control) vs float64", mf, ref)
+    assert float((mf - direct).abs().max()) < 4e-6 * float(ref.abs().max()), describe("mf vs direct (control)", mf, direct)
+    cases = [("T=1001", C, C, 1001, (0, 0, 0)), ("T=1002", C, C, 1002, (0, 0, 0)), ("T=1003", C, C, 1003, (0, 0, 0)),
+             ("Co=16", C, 16, 1000, (0, 0, 0)), ("Ci=24", 24, C, 1000, (0, 0, 0))]
+    for off in (1, 2, 3):
+        cases += [(f"x+{off}", C, C, 1000, (off, 0, 0)), (f"out+{off}", C, C, 1000, (0, off, 0)), (f"res+{off}", C, C, 1000, (0, 0, off))]
+    for name, Ci, Co, T, offs in cases:
+        mf, direct, ref = run(Ci, Co, T, offs)
+        assert torch.isfinite(mf).all()
+        assert torch.equal(mf, direct), describe(f"{name}: fallback vs direct kernel", mf, direct)
+        assert rel_l2(mf, ref) < 2e-6, describe(f"{name}: fallback vs float64", mf, ref)
+
+
+@pytest.mark.parametrize("C,k,dil", [(32, 3, 1), (32, 11, 5), (64, 7, 3)])
+def test_fp32_minimal_filtering_pair_refuses_ineligible_runs(lib, C, k, dil):
+    """vb_respair_f32_mf has no fallback (its only weights are the pseudo-taps): T % 4 != 0, a misaligned x or out, or x == out (neighbouring
+    workgroups re-read the halo) must be refused with VB_E_INVALID before any launch - the output buffer keeps its sentinel bits - instead of
+    computing from misread windows."""
+    from versband_amd._lib import VersbandError
+    B = 2
+    w1, w2 = rnd((C, C, k), "rw1", 1.0 / (C * k) ** 0.5), rnd((C, C, k), "rw2", 1.0 / (C * k) ** 0.5)
+    m1, m2, b1, b2 = dev(pack.pack_conv_mf(w1)), dev(pack.pack_conv_mf(w2)), dev(rnd((C,), "rb1")), dev(rnd((C,), "rb2"))
+
+    def call(x, out, T):
+        return lib.vb_respair_f32_mf(L.ptr(x), L.ptr(m1), L.ptr(b1), L.ptr(m2), L.ptr(b2), B, C, T, k, dil, 0.1, 1.0, 0.0, L.ptr(out),
+                                     L.stream_ptr())
+
+    sentinel = torch.full((B, C, 1000), -1234.5)
+    # the eligible call runs (so a refusal below is the run-time condition, not a broken call)
+    x, out = _at(rnd((B, C, 1000), "rx1000"), 0), _at(sentinel, 0)
+    L.check(call(x, out, 1000), "respair_f32_mf")
+    sync()
+    assert torch.isfinite(out).all() and not torch.equal(out.cpu(), sentinel)
+    cases = [(f"T={T}", T, 0, 0, False) for T in (1001, 1002, 1003)]
+    cases += [(f"x+{o}", 1000, o, 0, False) for o in (1, 2, 3)] + [(f"out+{o}", 1000, 0, o, False) for o in (1, 2, 3)]
+    cases += [("x == out", 1000, 0, 0, True)]
+    for name, T, xo, oo, inplace in cases:
+        s = torch.full((B, C, T), -1234.5)
+        x, out = _at(rnd((B, C, T), f"rx{T}"), xo), _at(s, oo)
+        if inplace:
+            x = out
+            s = out.cpu()
+        rc = call(x, out, T)
+        assert rc == -1, f"{name}: rc {rc}, expected VB_E_INVALID (-1)"
+        with pytest.raises(VersbandError):
+            L.check(rc, f"respair_f32_mf {name}")
+        sync()
+        assert torch.equal(out.cpu(), s), f"{name}: the refused call wrote to its output"
+
+
 def test_one_tap_conv_is_stable_beside_a_second_gpu_process(lib):
     """Round 5: in front of the second-last ring step of a 1-tap layer on the 4-stage weight ring the counted vmcnt wait let the window's
     last DMA piece fly (conv1d_f32g.hip, `lag`): whole wrong 64 x 128 tiles, but only while something else kept the memory system busy -

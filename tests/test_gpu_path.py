@@ -100,8 +100,15 @@ def test_sample_cfg_and_decode_vs_reference_golden(ctx, engines, sds):
     assert l1 < 1e-3, f"mel L1 {l1:.3e}; " + describe("mel vs reference", mel, g["mel"])
 
 
-@pytest.mark.parametrize("prec,tol", [("fp32", 2e-5), ("split", 2e-4)])
+def _f64(sd):
+    """a state dict in float64: the oracle follows the dtype of its inputs"""
+    return {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
+
+
+@pytest.mark.parametrize("prec,tol", [("fp32", 2e-5), ("fp32mf", 2e-5), ("split", 2e-4)])
 def test_vae_decode_vs_golden_and_oracle(ctx, prec, tol):
+    """T = 151: the latent-rate layers fall back from minimal filtering to the direct kernels in fp32mf (length not a multiple of 4);
+    T = 148: every eligible layer runs minimal filtering, the length still not a tile multiple.  Oracle in float64."""
     from versband_amd.engine import build_vae_decoder
     sdv = synth.make_state_dict(synth.vae_decoder_shapes(synth.VAEConfig()), SEED + 1)
     vae = build_vae_decoder(ctx, sdv, precision=prec)
@@ -109,19 +116,25 @@ def test_vae_decode_vs_golden_and_oracle(ctx, prec, tol):
     mel = vae.run(torch.from_numpy(g["z"]))
     torch.cuda.synchronize()
     assert rel_l2(mel, g["mel"]) < tol, describe("vae_decode vs reference", mel, g["mel"])
-    # ragged length (not a tile multiple) vs the oracle
-    z = torch.from_numpy(synth.prng.normal(77, 1 * 20 * 151).reshape(1, 20, 151))
-    ref = ref_cpu.vae_decode(sdv, z)
-    mel = vae.run(z)
-    torch.cuda.synchronize()
-    assert mel.shape == ref.shape
-    assert rel_l2(mel, ref) < tol, describe("vae_decode T=151 vs oracle", mel, ref)
+    if prec == "fp32mf":                                  # (the mode really took the minimal-filtering kernels)
+        mel32 = build_vae_decoder(ctx, sdv, precision="fp32").run(torch.from_numpy(g["z"]))
+        torch.cuda.synchronize()
+        assert not torch.equal(mel, mel32)
+    # ragged lengths (not a tile multiple) vs the oracle
+    for T in (151, 148):
+        z = torch.from_numpy(synth.prng.normal(77, 1 * 20 * T).reshape(1, 20, T))
+        ref = ref_cpu.vae_decode(_f64(sdv), z.double())
+        mel = vae.run(z)
+        torch.cuda.synchronize()
+        assert mel.shape == ref.shape
+        assert rel_l2(mel, ref) < tol, describe(f"vae_decode T={T} vs oracle", mel, ref)
 
 
-@pytest.mark.parametrize("prec,tol", [("fp32", 2e-5), ("split", 2e-4)])
+@pytest.mark.parametrize("prec,tol", [("fp32", 2e-5), ("fp32mf", 2e-5), ("split", 2e-4)])
 def test_vae_encode_vs_golden_and_oracle(ctx, prec, tol):
     """Encoder1D (k5 ResnetBlocks, stride-2 Downsample1D as two polyphase convolutions, mid attention) +
-    quant_conv through vb_vae_encode; posterior sample/mode through the reference-named API."""
+    quant_conv through vb_vae_encode; posterior sample/mode through the reference-named API.  T_mel = 302 (151 latent frames: those
+    layers fall back to the direct kernels in fp32mf) and 296 (every eligible layer runs minimal filtering); oracle in float64."""
     from versband_amd.engine import build_vae_encoder
     from versband_amd.model import DiagonalGaussianDistribution
     sde = synth.make_state_dict(synth.vae_encoder_shapes(synth.VAEConfig()), SEED + 3)
@@ -133,20 +146,27 @@ def test_vae_encode_vs_golden_and_oracle(ctx, prec, tol):
     post = DiagonalGaussianDistribution(mom)
     assert rel_l2(post.sample(torch.from_numpy(g["eps"])), g["z"]) < tol
     assert rel_l2(post.mode(), g["mode"]) < tol
-    # ragged mel length (T_mel = 302 -> 151 latent frames, not a tile multiple) vs the oracle
-    x = torch.from_numpy(synth.prng.normal(78, 1 * 80 * 302).reshape(1, 80, 302))
-    ref = ref_cpu.vae_encode(sde, x)
-    mom = enc.run(x)
-    torch.cuda.synchronize()
-    assert mom.shape == ref.shape
-    assert rel_l2(mom, ref) < tol, describe("vae_encode T_mel=302 vs oracle", mom, ref)
+    if prec == "fp32mf":                                  # (the mode really took the minimal-filtering kernels)
+        mom32 = build_vae_encoder(ctx, sde, precision="fp32").run(torch.from_numpy(g["x"]))
+        torch.cuda.synchronize()
+        assert not torch.equal(mom, mom32)
+    # ragged mel lengths (not a tile multiple) vs the oracle
+    for T_mel in (302, 296):
+        x = torch.from_numpy(synth.prng.normal(78, 1 * 80 * T_mel).reshape(1, 80, T_mel))
+        ref = ref_cpu.vae_encode(_f64(sde), x.double())
+        mom = enc.run(x)
+        torch.cuda.synchronize()
+        assert mom.shape == ref.shape
+        assert rel_l2(mom, ref) < tol, describe(f"vae_encode T_mel={T_mel} vs oracle", mom, ref)
     with pytest.raises(ValueError):
         enc.run(torch.zeros(1, 80, 301))          # odd mel length cannot be halved (the reference pads to a multiple of 8 upstream)
 
 
 @pytest.mark.parametrize("tag", ["v1", "rb2"])
-@pytest.mark.parametrize("prec,tol", [("fp32", 2e-5), ("split", 2e-4)])
+@pytest.mark.parametrize("prec,tol", [("fp32", 2e-5), ("fp32mf", 2e-5), ("split", 2e-4)])
 def test_hifigan_vs_golden_and_oracle(ctx, tag, prec, tol):
+    """B = 2, T = 37: conv_pre falls back to the direct kernel in fp32mf; B = 3, T = 36: every eligible layer runs minimal filtering.
+    Oracle in float64."""
     from versband_amd.engine import build_hifigan
     cfg = synth.HifiGanConfig() if tag == "v1" else synth.HifiGanConfig(
         resblock="2", upsample_rates=(8, 8, 5), upsample_kernel_sizes=(16, 16, 11), upsample_initial_channel=128,
@@ -158,11 +178,17 @@ def test_hifigan_vs_golden_and_oracle(ctx, tag, prec, tol):
     torch.cuda.synchronize()
     assert wav.shape == g["wav"].shape
     assert rel_l2(wav, g["wav"]) < tol, describe("hifigan vs reference", wav, g["wav"])
-    mel = torch.from_numpy(synth.prng.uniform(5, 2 * 80 * 37, -5.0, 1.5).reshape(2, 80, 37))
-    ref = ref_cpu.hifigan_forward(sd, cfg.as_hparams(), mel)
-    wav = net.run(mel)
-    torch.cuda.synchronize()
-    assert rel_l2(wav, ref) < tol, describe("hifigan B=2 T=37 vs oracle", wav, ref)
+    if prec == "fp32mf":                                  # (the mode really took the minimal-filtering kernels)
+        wav32 = build_hifigan(ctx, sd, cfg.as_hparams(), precision="fp32").run(torch.from_numpy(g["mel"]))
+        torch.cuda.synchronize()
+        assert not torch.equal(wav, wav32)
+    for B, T in ((2, 37), (3, 36)):
+        mel = torch.from_numpy(synth.prng.uniform(5, B * 80 * T, -5.0, 1.5).reshape(B, 80, T))
+        ref = ref_cpu.hifigan_forward(_f64(sd), cfg.as_hparams(), mel.double())
+        wav = net.run(mel)
+        torch.cuda.synchronize()
+        assert wav.shape == ref.shape
+        assert rel_l2(wav, ref) < tol, describe(f"hifigan B={B} T={T} vs oracle", wav, ref)
 
 
 def test_reference_api_end_to_end_vs_oracle(tmp_path):
@@ -683,8 +709,9 @@ def test_fullsize_reference_digests(ctx, engines):
     torch.cuda.synchronize()
     check_digest(wav32, g, "voc_wav_", 2e-6)       # measured: 1.2e-6 / 1.7e-8 (split: 7.5e-6 / 1.4e-6)
     # fp32 with F(2,3) minimal filtering (round 6, conv1d_f32w.hip: the VAE's 3-tap layers, the generator's 64 / 128 / 256-channel ResBlock
-    # convolutions - its 64-channel pairs run as two minimal-filtering launches, the 32-channel pairs stay fused and direct): fp32 products,
-    # ~1.45x fewer; held to the SAME bounds against the reference's own outputs as the direct fp32 kernels
+    # convolutions - its 64-channel pairs run as two minimal-filtering launches, the 32-channel pairs fused with minimal filtering in both
+    # convolutions, respair_f32w.hip): fp32 products, ~1.45x fewer; held to the SAME bounds against the reference's own outputs as the direct
+    # fp32 kernels
     melmf = build_vae_decoder(ctx, synth.make_state_dict(synth.vae_decoder_shapes(vcfg), SEED + 1), precision="fp32mf").run(z)
     check_digest(melmf, g, "vae_mel_", 2e-6)
     wavmf = build_hifigan(ctx, synth.make_state_dict(synth.hifigan_shapes(hcfg), SEED + 2), hcfg.as_hparams(), precision="fp32mf").run(melmf)

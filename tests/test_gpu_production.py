@@ -28,12 +28,12 @@ def ctx():
 
 @pytest.fixture(scope="module")
 def prod(ctx):
-    """bf16 production engine + VAE decoder on the synthetic checkpoints bench.py uses."""
+    """bf16 production engine + VAE decoder on the synthetic checkpoints bench.py uses, the decoder in the arithmetic CFM ships (fp32mf)."""
     from versband_amd.engine import DiTEngine, build_vae_decoder
     dcfg = synth.DiTConfig()
     sd = synth.make_state_dict(synth.dit_shapes(dcfg), SEED)
     sdv = synth.make_state_dict(synth.vae_decoder_shapes(synth.VAEConfig()), SEED + 1)
-    return dict(sd=sd, sdv=sdv, eng=DiTEngine(ctx, dcfg, sd, precision="bf16"), vae=build_vae_decoder(ctx, sdv))
+    return dict(sd=sd, sdv=sdv, eng=DiTEngine(ctx, dcfg, sd, precision="bf16"), vae=build_vae_decoder(ctx, sdv, precision="fp32mf"))
 
 
 def _oracle_trajectory(sd, inp, scale, steps, noise_steps):
@@ -243,6 +243,62 @@ def test_vocoder_stage_bits_are_stable_beside_a_second_gpu_process_at_8_clips(ct
         return mel.clone(), wav.clone()
 
     _repeat_beside_load(run, ("mel", "waveform"), 6, 60)
+
+
+@pytest.fixture(scope="module")
+def clip7_oracle(prod):
+    """float64 oracle of the bench geometry's clip 7 (T = 752): VAE decode (~1 s) and HiFi-GAN on that mel (~15 s on 16 threads),
+    computed once for both precisions of the 8-clip test"""
+    def f64(sd):
+        return {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
+    hcfg = synth.HifiGanConfig()
+    z = clip_batch(1, 752, 80, clip0=7)["x_latent"].double()
+    mel = ref_cpu.vae_decode(f64(prod["sdv"]), z)
+    wav = ref_cpu.hifigan_forward(f64(synth.make_state_dict(synth.hifigan_shapes(hcfg), SEED + 2)), hcfg.as_hparams(), mel)
+    return mel, wav
+
+
+@pytest.mark.parametrize("vprec", ["fp32", "fp32mf"])
+def test_vae_vocoder_rows_are_batch_invariant_and_float64_close_at_8_clips(ctx, prod, clip7_oracle, vprec):
+    """The bench's VAE decoder + HiFi-GAN over 8 clips of 20 s (T = 752, mel 1504).  The fp32 conv tile depends on the batch
+    (conv1d_f32g.hip, g_pick_tile: 128 x 96 VAE tiles at 8 clips, 64 x 128 / 64 x 64 at one or two) and "never changes a bit of the
+    result"; every other op of these nets (GN statistics and apply, softmax, transposed convolutions, conv1d_f32w / respair_f32w, whose
+    tiles follow Co) computes a clip from that clip alone.  So row r of the 8-, 3- and 2-clip batches must equal the one-clip run of
+    clip r bit for bit, mel and waveform.  The last row of the 8-clip batch (clip 7: a batch-offset or tail-tile bug shows there) is held
+    against the float64 oracle at the suite's net-level fp32 bound, rel-L2 <= 2e-5, and elementwise, max-abs <= 1e-4 x max|ref|, so
+    that one wrong tile cannot hide in the norm.  Measured on MI355X (rel-L2 / max-abs over max|ref|): fp32 mel 3.9e-6 / 3.8e-6, waveform
+    4.9e-6 / 5.8e-6; fp32mf mel 2.8e-6 / 2.7e-6, waveform 3.6e-6 / 3.9e-6 - and every row bitwise equal to its one-clip run in both."""
+    from versband_amd.engine import build_hifigan, build_vae_decoder
+    hcfg = synth.HifiGanConfig()
+    vae = build_vae_decoder(ctx, prod["sdv"], precision=vprec)
+    voc = build_hifigan(ctx, synth.make_state_dict(synth.hifigan_shapes(hcfg), SEED + 2), hcfg.as_hparams(), precision=vprec)
+    z8 = clip_batch(8, 752, 80)["x_latent"]
+
+    def run(z):
+        mel = vae.run(z.to("cuda:0").contiguous())
+        wav = voc.run(mel)
+        torch.cuda.synchronize()
+        return mel.cpu(), wav.cpu()
+
+    batches = {B: run(z8[:B]) for B in (8, 3, 2)}
+    for r in range(8):
+        z1 = clip_batch(1, 752, 80, clip0=r)["x_latent"]
+        assert torch.equal(z1[0], z8[r])
+        mel1, wav1 = run(z1)
+        assert torch.isfinite(mel1).all() and torch.isfinite(wav1).all()
+        for B, (mel, wav) in batches.items():
+            if r < B:
+                assert torch.equal(mel[r], mel1[0]), describe(f"{vprec} mel: clip {r} in a batch of {B} vs alone", mel[r], mel1[0])
+                assert torch.equal(wav[r], wav1[0]), describe(f"{vprec} waveform: clip {r} in a batch of {B} vs alone", wav[r], wav1[0])
+    mel_ref, wav_ref = clip7_oracle
+    mel, wav = batches[8][0][7:8], batches[8][1][7:8]
+    em, ew = rel_l2(mel, mel_ref), rel_l2(wav, wav_ref)
+    am = float((mel.double() - mel_ref).abs().max()) / float(mel_ref.abs().max())
+    aw = float((wav.double() - wav_ref).abs().max()) / float(wav_ref.abs().max())
+    print(f"\n[{vprec}, 8 clips, clip 7 vs float64] mel rel-L2 {em:.3e}, max-abs/max|ref| {am:.3e}; "
+          f"waveform rel-L2 {ew:.3e}, max-abs/max|ref| {aw:.3e}")
+    assert em <= 2e-5 and am <= 1e-4, describe(f"{vprec} mel, clip 7 of 8 vs float64", mel, mel_ref)
+    assert ew <= 2e-5 and aw <= 1e-4, describe(f"{vprec} waveform, clip 7 of 8 vs float64", wav, wav_ref)
 
 
 def test_e8_dit_bits_are_stable_beside_a_second_gpu_process(ctx):
