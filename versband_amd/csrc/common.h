@@ -108,3 +108,5 @@ static inline void vb_set_max_lds_once(OnceFlags& f, const void* kernel, int byt
 }
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+// (host) the address can be moved as 16-byte lane accesses: float4 loads / stores, 16-B DMA pieces
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }

@@ -1,7 +1,10 @@
-// Device-side pieces shared by the convolution kernels (conv1d_f32.hip: register-staged fp32 + split-bf16 kernels; conv1d_f32g.hip: the
-// DMA-fed exact-fp32 kernel): the launch descriptor and the two epilogues.
+// What the convolution kernels share (conv1d_f32.hip: register-staged fp32 + split-bf16 kernels and the launch route; conv1d_f32g.hip:
+// the DMA-fed exact-fp32 kernel; conv1d_f32w.hip: its minimal-filtering form): the launch descriptor, the two epilogues and, host side,
+// what the two DMA-fed launchers have in common.
 #pragma once
 #include "kernels.h"
+
+#define GK 16                      // input channels per chunk of the DMA-fed kernels (= CK: the accumulation order of conv1d_f32_kernel)
 
 struct ConvDev {
     const float* x; int64_t x_bstride; int Ci, T_in, x_bmod;
@@ -175,12 +178,26 @@ __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[TM
     }
 }
 
+// ---- host side -------------------------------------------------------------
+// Input the window DMA of the ring kernels can fetch: unit input stride, no clip folding (x_bmod), an input transform the in-place pass over
+// the landed window knows (none / LeakyReLU), whole GK-channel chunks, output channels in quads (16-byte lanes of the weight DMA).
+// quad_rows: the window moves as 16-byte pieces, so rows start 16-byte aligned (conv1d_f32g's upsampled form moves 4-byte pieces: false).
+static inline bool conv_dma_input(const ConvArgs& a, const ConvDev& d, bool quad_rows) {
+    return !a.x_bmod && d.in_stride == 1 && (a.in_act == ACT_NONE || a.in_act == ACT_LRELU) && a.Ci % GK == 0 && a.Co % 4 == 0 &&
+           (!quad_rows || (a.T_in % 4 == 0 && a.x_bstride % 4 == 0 && aligned16(a.x)));
+}
+// XCD work-group numbering of the ring kernels: block L serves unit (L >> 3) % g_tbx * 8 + (L & 7) of channel tile (L >> 3) / g_tbx, so one
+// XCD keeps a (time tile, clip, phase) unit for all its channel tiles.  Fills d.g_* and returns the grid size.
+static inline int conv_xcd_grid(ConvDev& d, int n_count, int t_tile, int co_tile, int B) {
+    d.g_nt = cdiv(n_count, t_tile); d.g_nco = cdiv(d.Co, co_tile);
+    d.g_ntb = d.g_nt * B * d.phases; d.g_tbx = cdiv(d.g_ntb, 8);
+    return 8 * d.g_tbx * d.g_nco;
+}
 
-// conv1d_f32g.hip: DMA-fed exact-fp32 kernel (shared weights, Ci % 16 == 0, Co % 4 == 0, in_act none / LeakyReLU, unit input stride,
-// halo <= 60, 16-byte aligned rows unless upsample2)
-#define GK 16                      // input channels per chunk (= CK: the accumulation order of conv1d_f32_kernel)
+// conv1d_f32g.hip: DMA-fed exact-fp32 kernel, bit-identical to conv1d_f32_kernel.  _eligible: ALL of a kernel's launch conditions
+bool conv1d_f32g_eligible(const ConvArgs& a, const ConvDev& d);
 void launch_conv1d_f32g(ConvDev& d, int n_count, int B, int upsample2, hipStream_t st);
 // conv1d_f32w.hip: the same rings with F(2,3) minimal filtering (k = 3 / 5 / 7 / 11, stride 1): fp32 products, ~1.4-1.5x fewer of them
-bool conv1d_f32w_supported(int ksize, int dil);
+bool conv1d_f32w_eligible(const ConvArgs& a, const ConvDev& d);
 int conv1d_f32w_pseudo_taps(int ksize);
 void launch_conv1d_f32w(ConvDev& d, int B, hipStream_t st);

@@ -445,8 +445,8 @@ __global__ void __launch_bounds__(256) conv1d_co1_kernel(const ConvDev p) {
     }
 }
 
-int launch_conv1d(const ConvArgs& a, hipStream_t st) {
-    ConvDev d;
+// ---- launch_conv1d: descriptor (+ the checks that fail the call; n_count = output positions per phase) -> route -> launch
+static int conv1d_fill(const ConvArgs& a, ConvDev& d, int& n_count) {
     d.x = a.x; d.x_bstride = a.x_bstride; d.Ci = a.Ci; d.T_in = a.T_in; d.x_bmod = a.x_bmod;
     d.w = a.w; d.w_bstride = a.w_bstride; d.bias = a.bias; d.Co = a.Co; d.dil = a.dil; d.pad = a.pad;
     d.upsample2 = a.upsample2; d.in_act = a.in_act; d.in_slope = a.in_slope;
@@ -461,7 +461,6 @@ int launch_conv1d(const ConvArgs& a, hipStream_t st) {
     if (a.xt && (a.Ci % CK3 || a.tr_stride > 1 || a.in_stride > 1 || !a.wp || a.x_bmod || a.pad > XT_HEAD))
         VB_FAIL(VB_E_INVALID, "conv1d: XT input needs Ci %% 32 == 0, stride 1, split weights, pad <= %d", XT_HEAD);
     d.stage_epi = 0;
-    int n_count;
     if (a.tr_stride > 1) {
         d.phases = a.tr_stride; d.tr_pad = a.tr_pad; d.ntaps = (a.tr_k + a.tr_stride - 1) / a.tr_stride; d.dil = 1;
         n_count = cdiv(a.T_out, a.tr_stride);
@@ -472,67 +471,96 @@ int launch_conv1d(const ConvArgs& a, hipStream_t st) {
     if ((d.ntaps - 1) * d.dil > XHALO) VB_FAIL(VB_E_INVALID, "conv1d: halo %d exceeds %d", (d.ntaps - 1) * d.dil, XHALO);
     if (a.out_transposed && (a.Co % 4)) VB_FAIL(VB_E_INVALID, "conv1d: transposed output needs Co%%4==0");
     if ((a.in_act == ACT_GN_SWISH || a.in_act == ACT_GN) && (a.Ci % a.gn_groups)) VB_FAIL(VB_E_INVALID, "conv1d: Ci %% groups");
-    // Wide layers over pre-activated transposed planes ARE GEMMs (rows = clip x time, K = taps x Ci, both operands K-contiguous
-    // already): the DMA-fed 128 x 128 GEMM kernel walks K tap by tap (GemmArgs::conv_*), three bf16 passes for the split precision,
-    // bias + residual in a channel-major epilogue.  Measured on these shapes (tools/conv_as_gemm_calib.py): 750-840 TFLOP/s of bf16
-    // MFMA work against ~385 of this file's kernel, which stages weights through registers and synchronises per (tap, 32 channels).
-    if (a.xt && a.wp && a.Co >= 384 && a.Ci % 64 == 0 && a.Ci_pad == a.Ci && a.Co % 4 == 0 && d.phases == 1 && !a.wp_bstride && !a.w_bstride &&
-        a.alpha == 1.f && a.beta == 0.f && a.acc_scale == 1.f && a.out_act == ACT_NONE && !a.out_transposed && !a.add &&
-        a.out_bstride == (int64_t)a.Co * a.T_out && (!a.res || a.res_bstride == a.out_bstride) &&
-        a.T_out == (a.upsample2 ? 2 * a.T_in : a.T_in) && (int64_t)a.B * a.T_out < (1 << 21) && a.Co < (1 << 21) && !vb_tune().conv_gemm_off) {
-        // (B * T_out / Co beyond launch_gemm's reciprocal-divide range fall through to the conv kernels - ADVICE r3)
-        GemmArgs g;
-        g.A = a.xt; g.a_plane = d.xt_plane; g.lda = a.Ci; g.B = a.wp; g.b_plane = a.wp_plane; g.ldb = a.Ci_pad;
-        g.M = a.B * a.T_out; g.N = a.Co; g.K = d.ntaps * a.Ci; g.nseg = 3; g.ngroups = a.B;
-        g.group_rows = a.T_out; g.T = a.T_out; g.epi = EPI_F32_CT; g.bias = a.bias; g.out32 = a.out; g.res32 = a.res;
-        g.conv_ci = a.Ci; g.conv_dil = d.dil; g.conv_agrp = d.xt_Tp; g.conv_arow0 = XT_HEAD - a.pad; g.conv_btap = (int64_t)a.Co * a.Ci_pad;
-        g.prof_class = 2;
-        return launch_gemm(g, st);
-    }
-    // staged epilogue (split-bf16 kernel): plain [b][co][t] output whose rows start 16-B aligned
-    d.stage_epi = (a.tr_stride <= 1 && !a.out_transposed && a.T_out % 4 == 0 && a.out_bstride % 4 == 0 &&
-                   (!a.res || a.res_bstride % 4 == 0) && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0 &&
-                   (!a.res || (reinterpret_cast<uintptr_t>(a.res) & 15) == 0) && !vb_tune().conv_direct_epi) ? 1 : 0;
-    // minimal filtering (conv1d_f32w_kernel): the DMA-fed fp32 kernel's conditions + stride 1, shared weights, the staged epilogue, wide layers
-    const bool use_mf = a.w_mf && !a.wp && !a.w_bstride && !a.x_bmod && d.in_stride == 1 && d.phases == 1 && !a.upsample2 &&
-                        (a.in_act == ACT_NONE || a.in_act == ACT_LRELU) && a.Ci % GK == 0 && a.Co % 4 == 0 && a.Co >= 32 && d.stage_epi &&
-                        conv1d_f32w_supported(a.ksize, a.dil) && a.T_in % 4 == 0 && a.x_bstride % 4 == 0 &&
-                        (reinterpret_cast<uintptr_t>(a.x) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.w_mf) & 15) == 0 && !vb_tune().conv_mf_off;
+    return VB_OK;
+}
+
+// Wide layers over pre-activated transposed planes ARE GEMMs (rows = clip x time, K = taps x Ci, both operands K-contiguous
+// already): the DMA-fed 128 x 128 GEMM kernel walks K tap by tap (GemmArgs::conv_*), three bf16 passes for the split precision,
+// bias + residual in a channel-major epilogue.  Measured on these shapes (tools/conv_as_gemm_calib.py): 750-840 TFLOP/s of bf16
+// MFMA work against ~385 of this file's kernel, which stages weights through registers and synchronises per (tap, 32 channels).
+// (B * T_out / Co beyond launch_gemm's reciprocal-divide range fall through to the conv kernels - ADVICE r3)
+static bool conv1d_as_gemm_eligible(const ConvArgs& a, const ConvDev& d) {
+    return a.xt && a.wp && a.Co >= 384 && a.Ci % 64 == 0 && a.Ci_pad == a.Ci && a.Co % 4 == 0 && d.phases == 1 && !a.wp_bstride && !a.w_bstride &&
+           a.alpha == 1.f && a.beta == 0.f && a.acc_scale == 1.f && a.out_act == ACT_NONE && !a.out_transposed && !a.add &&
+           a.out_bstride == (int64_t)a.Co * a.T_out && (!a.res || a.res_bstride == a.out_bstride) &&
+           a.T_out == (a.upsample2 ? 2 * a.T_in : a.T_in) && (int64_t)a.B * a.T_out < (1 << 21) && a.Co < (1 << 21);
+}
+static int launch_conv1d_as_gemm(const ConvArgs& a, const ConvDev& d, hipStream_t st) {
+    GemmArgs g;
+    g.A = a.xt; g.a_plane = d.xt_plane; g.lda = a.Ci; g.B = a.wp; g.b_plane = a.wp_plane; g.ldb = a.Ci_pad;
+    g.M = a.B * a.T_out; g.N = a.Co; g.K = d.ntaps * a.Ci; g.nseg = 3; g.ngroups = a.B;
+    g.group_rows = a.T_out; g.T = a.T_out; g.epi = EPI_F32_CT; g.bias = a.bias; g.out32 = a.out; g.res32 = a.res;
+    g.conv_ci = a.Ci; g.conv_dil = d.dil; g.conv_agrp = d.xt_Tp; g.conv_arow0 = XT_HEAD - a.pad; g.conv_btap = (int64_t)a.Co * a.Ci_pad;
+    g.prof_class = 2;
+    return launch_gemm(g, st);
+}
+// staged epilogue (conv_epilogue_staged; the minimal-filtering kernel has no other): plain [b][co][t] output whose rows start 16-B aligned
+static bool conv1d_stage_epi_eligible(const ConvArgs& a) {
+    return a.tr_stride <= 1 && !a.out_transposed && a.T_out % 4 == 0 && a.out_bstride % 4 == 0 && (!a.res || a.res_bstride % 4 == 0) &&
+           aligned16(a.out) && (!a.res || aligned16(a.res));
+}
+// conv1d_co1_kernel: one output channel of an ordinary stride-1 convolution, shared fp32 weights, input transform none / LeakyReLU
+static bool conv1d_co1_eligible(const ConvArgs& a, const ConvDev& d) {
+    return a.Co == 1 && a.w && !a.w_bstride && !a.x_bmod && d.phases == 1 && d.in_stride == 1 && !a.upsample2 && !a.out_transposed &&
+           (a.in_act == ACT_NONE || a.in_act == ACT_LRELU);
+}
+// conv1d_x3_kernel: split-bf16 weights are there - and per clip where the fp32 ones are
+static bool conv1d_x3_eligible(const ConvArgs& a) { return a.wp && (!a.w_bstride || a.wp_bstride); }
+
+enum ConvRoute { CONV_AS_GEMM, CONV_F32W, CONV_CO1, CONV_X3_XT, CONV_X3, CONV_F32G, CONV_F32 };
+// Which kernel runs: the first candidate, in this order, whose conditions hold and whose A/B knob has not switched it off; the register-staged
+// fp32 kernel takes everything.  Settles d.stage_epi on the way (VB_CONV_DIRECT_EPI=1: the direct epilogue - no minimal filtering then).
+static ConvRoute conv1d_route(const ConvArgs& a, ConvDev& d) {
+    const VbTune& tune = vb_tune();
+    if (conv1d_as_gemm_eligible(a, d) && !tune.conv_gemm_off) return CONV_AS_GEMM;
+    d.stage_epi = (conv1d_stage_epi_eligible(a) && !tune.conv_direct_epi) ? 1 : 0;
+    if (conv1d_f32w_eligible(a, d) && !tune.conv_mf_off) return CONV_F32W;
+    if (conv1d_co1_eligible(a, d) && !tune.conv_f32_old) return CONV_CO1;             // (VB_CONV_F32_OLD=1: the MFMA kernels)
+    if (conv1d_x3_eligible(a)) return a.xt ? CONV_X3_XT : CONV_X3;
+    // exact fp32, DMA-fed; VB_CONV_F32_OLD=1 keeps the register-staged kernel (bit-identical, tests compare the two)
+    if (conv1d_f32g_eligible(a, d) && !tune.conv_f32_old) return CONV_F32G;
+    return CONV_F32;
+}
+
+int launch_conv1d(const ConvArgs& a, hipStream_t st) {
+    ConvDev d;
+    int n_count;
+    VB_TRY(conv1d_fill(a, d, n_count));
+    const ConvRoute route = conv1d_route(a, d);
+    if (route == CONV_AS_GEMM) return launch_conv1d_as_gemm(a, d, st);      // (launch_gemm profiles itself: GemmArgs::prof_class)
     // (flops of the profiler's class table: EXECUTED MFMA work - the minimal-filtering kernel runs pseudo-taps / 2 products per output)
-    const double taps_eff = use_mf ? 0.5 * conv1d_f32w_pseudo_taps(a.ksize) : (a.tr_stride > 1 ? (double)a.tr_k / a.tr_stride : (double)a.ksize);
+    const double taps_eff = route == CONV_F32W ? 0.5 * conv1d_f32w_pseudo_taps(a.ksize) : (a.tr_stride > 1 ? (double)a.tr_k / a.tr_stride : (double)a.ksize);
     ProfScope prof(2, 2.0 * a.B * a.Co * a.Ci * (double)a.T_out * taps_eff,
-                   4.0 * a.B * ((double)a.Ci * a.T_in * (a.xt ? 1.0 : 1.0) + (double)a.Co * a.T_out * (1.0 + (a.res ? 1.0 : 0.0) + (a.beta != 0.f ? 1.0 : 0.0)))
+                   4.0 * a.B * ((double)a.Ci * a.T_in + (double)a.Co * a.T_out * (1.0 + (a.res ? 1.0 : 0.0) + (a.beta != 0.f ? 1.0 : 0.0)))
                        + 4.0 * (double)a.Co * a.Ci * (a.tr_stride > 1 ? a.tr_k : a.ksize), st);
-    if (use_mf) {
-        d.ww = a.w_mf;
-        launch_conv1d_f32w(d, a.B, st);
-    } else if (a.Co == 1 && a.w && !a.w_bstride && !a.x_bmod && d.phases == 1 && d.in_stride == 1 && !a.upsample2 && !a.out_transposed &&
-        (a.in_act == ACT_NONE || a.in_act == ACT_LRELU) && !vb_tune().conv_f32_old) {
-        hipLaunchKernelGGL(conv1d_co1_kernel, dim3(cdiv(a.T_out, C1_TT), a.B), dim3(256), 0, st, d);       // (VB_CONV_F32_OLD=1: the MFMA kernels)
-    } else if (a.wp && (!a.w_bstride || a.wp_bstride)) {
-        if (a.Ci_pad % CK3) VB_FAIL(VB_E_INVALID, "conv1d: split weights need Ci_pad %% %d == 0", CK3);
-        // one workgroup of the 128co x 256t tile per CU (92 KB LDS): a grid a little over 256 workgroups (every VAE level at
-        // B = 8 makes 288) runs as two rounds at 56 % - the 128co x 128t tile (71 KB, two per CU) halves the granule
-        const int64_t blocks = (int64_t)cdiv(n_count, 256) * cdiv(a.Co, 128) * a.B * d.phases;
-        const double eff = (double)blocks / (double)(cdiv(blocks, 256) * 256);
-        if (a.xt) {
-            if (a.Co <= 64) VB_FAIL(VB_E_INVALID, "conv1d: XT input is built for Co > 64 (wide layers)");
-            if (eff < 0.7) launch_cfg_xt<2, 2, 2, 1>(d, n_count, a.B, st);
-            else launch_cfg_xt<2, 2, 2, 2>(d, n_count, a.B, st);
-        } else if (a.Co > 64 && eff < 0.7) launch_cfg_x3<2, 2, 2, 1>(d, n_count, a.B, st);
-        else if (a.Co > 64) launch_cfg_x3<2, 2, 2, 2>(d, n_count, a.B, st);
-        else if (a.Co > 32) launch_cfg_x3<2, 2, 1, 2>(d, n_count, a.B, st);
-        else launch_cfg_x3<1, 4, 1, 2>(d, n_count, a.B, st);
-    } else if (!a.wp && a.w_bstride % 4 == 0 && !a.x_bmod && d.in_stride == 1 && (a.in_act == ACT_NONE || a.in_act == ACT_LRELU) && a.Ci % GK == 0 &&
-               a.Co % 4 == 0 && (d.ntaps - 1) * d.dil <= 60 && (reinterpret_cast<uintptr_t>(a.w) & 15) == 0 &&
-               (a.upsample2 ? (a.Co > 64 && d.phases == 1)
-                            : (a.T_in % 4 == 0 && a.x_bstride % 4 == 0 && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0)) &&
-               !vb_tune().conv_f32_old) {
-        // exact fp32, DMA-fed (conv1d_f32g_kernel); VB_CONV_F32_OLD=1 keeps the register-staged kernel (bit-identical, tests compare the two)
-        launch_conv1d_f32g(d, n_count, a.B, a.upsample2, st);
-    } else if (a.Co > 64) launch_cfg<2, 2, 2, 2>(d, n_count, a.B, st);
-    else if (a.Co > 32) launch_cfg<2, 2, 1, 2>(d, n_count, a.B, st);
-    else launch_cfg<1, 4, 1, 2>(d, n_count, a.B, st);
+    switch (route) {
+        case CONV_AS_GEMM: break;      // (left above)
+        case CONV_F32W: d.ww = a.w_mf; launch_conv1d_f32w(d, a.B, st); break;
+        case CONV_CO1: hipLaunchKernelGGL(conv1d_co1_kernel, dim3(cdiv(a.T_out, C1_TT), a.B), dim3(256), 0, st, d); break;
+        case CONV_X3_XT:
+        case CONV_X3: {
+            if (a.Ci_pad % CK3) VB_FAIL(VB_E_INVALID, "conv1d: split weights need Ci_pad %% %d == 0", CK3);
+            // one workgroup of the 128co x 256t tile per CU (92 KB LDS): a grid a little over 256 workgroups (every VAE level at
+            // B = 8 makes 288) runs as two rounds at 56 % - the 128co x 128t tile (71 KB, two per CU) halves the granule
+            const int64_t blocks = (int64_t)cdiv(n_count, 256) * cdiv(a.Co, 128) * a.B * d.phases;
+            const double eff = (double)blocks / (double)(cdiv(blocks, 256) * 256);
+            if (route == CONV_X3_XT) {
+                if (a.Co <= 64) VB_FAIL(VB_E_INVALID, "conv1d: XT input is built for Co > 64 (wide layers)");
+                if (eff < 0.7) launch_cfg_xt<2, 2, 2, 1>(d, n_count, a.B, st);
+                else launch_cfg_xt<2, 2, 2, 2>(d, n_count, a.B, st);
+            } else if (a.Co > 64 && eff < 0.7) launch_cfg_x3<2, 2, 2, 1>(d, n_count, a.B, st);
+            else if (a.Co > 64) launch_cfg_x3<2, 2, 2, 2>(d, n_count, a.B, st);
+            else if (a.Co > 32) launch_cfg_x3<2, 2, 1, 2>(d, n_count, a.B, st);
+            else launch_cfg_x3<1, 4, 1, 2>(d, n_count, a.B, st);
+            break;
+        }
+        case CONV_F32G: launch_conv1d_f32g(d, n_count, a.B, a.upsample2, st); break;
+        case CONV_F32:
+            if (a.Co > 64) launch_cfg<2, 2, 2, 2>(d, n_count, a.B, st);
+            else if (a.Co > 32) launch_cfg<2, 2, 1, 2>(d, n_count, a.B, st);
+            else launch_cfg<1, 4, 1, 2>(d, n_count, a.B, st);
+            break;
+    }
     VB_CHECK_LAUNCH();
     return VB_OK;
 }

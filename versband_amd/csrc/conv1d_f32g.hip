@@ -5,14 +5,11 @@
 #include <type_traits>
 
 #include "conv1d_dev.h"
+#include "dma_ring.h"
 #include "lds_asm.h"
 
-template <int I, int N, class F> __device__ __forceinline__ void g_static_for(F&& f) {
-    if constexpr (I < N) { f(std::integral_constant<int, I>{}); g_static_for<I + 1, N>(f); }
-}
-
 // ---------------------------------------------------------------------------------------------------------
-// DMA-fed exact-fp32 kernel (round 4).  conv1d_f32_kernel above multiplies at 80-93 % of the f32 MFMA rate PER TAP (measured at 8
+// DMA-fed exact-fp32 kernel (round 4).  conv1d_f32_kernel (conv1d_f32.hip) multiplies at 80-93 % of the f32 MFMA rate PER TAP (measured at 8
 // clips: +54 us per tap at 32 channels = 146 TF/s, +114 at 64, +125 at 128) but every layer pays 650-800 us before its first tap and
 // after its last one: the window of every 16-channel chunk goes global -> registers -> transform -> LDS with nothing in flight, weights
 // go through registers once per tap, and the epilogue moves 4-byte lane accesses - the vocoder's 72 ResBlock convolutions spend as long
@@ -25,28 +22,8 @@ template <int I, int N, class F> __device__ __forceinline__ void g_static_for(F&
 //   * the [b][co][t] result leaves through the staged 16-byte epilogue of the split-bf16 kernel (conv_epilogue_staged);
 //   * workgroups are numbered so that one XCD keeps a (time tile, clip) unit for ALL its output-channel tiles: the window is fetched
 //     into one L2, the (small) weights into all of them.
-// Conditions (launch_conv1d falls back to conv1d_f32_kernel otherwise): shared or per-clip fp32 weights (16-B aligned), Ci % 16 == 0, Co % 4 == 0, in_act none / LeakyReLU,
-// unit input stride, halo <= 60, 16-byte aligned rows (T_in % 4 == 0) unless the input is upsampled (UPS: 4-byte DMA pieces).
+// Conditions: conv1d_f32g_eligible below (launch_conv1d falls back to conv1d_f32_kernel otherwise).
 // ---------------------------------------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) void* g_lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* g_glb_ptr_t;
-template <int N> __device__ __forceinline__ void g_wait_vmcnt() {
-    static_assert(N >= 0 && N < 64, "vmcnt is 6 bits");
-    __builtin_amdgcn_s_waitcnt(0x0f70 | (N & 15) | ((N >> 4) << 14));
-}
-// counted wait in front of ring step t: `ahead` (<= 2) younger weight tiles (+ one window chunk when xin) may stay in flight
-template <int WPW, int XPW> __device__ __forceinline__ void g_wait_tile(int ahead, bool xin) {
-    if (xin) {
-        if (ahead >= 2) g_wait_vmcnt<2 * WPW + XPW>();
-        else if (ahead == 1) g_wait_vmcnt<WPW + XPW>();
-        else g_wait_vmcnt<XPW>();
-    } else {
-        if (ahead >= 2) g_wait_vmcnt<2 * WPW>();
-        else if (ahead == 1) g_wait_vmcnt<WPW>();
-        else g_wait_vmcnt<0>();
-    }
-}
-
 // NSW = weight-tile ring stages (4: three tiles in flight; 3: two - 49 KB of LDS with the 96-sample tile, three workgroups per CU)
 // ABL (experiments build, timing only - results are wrong): 1 = no fragment reads, 2 = no DMA, 4 = no barrier, 8 = no MFMAs, 16 = no epilogue
 // NT = taps per phase as a template parameter (0: runtime loop)
@@ -60,7 +37,7 @@ __global__ void __launch_bounds__(256, 3) conv1d_f32g_kernel(const ConvDev p) { 
     constexpr int NWI = CO_TILE / 16;                     // 1-KB DMA pieces per weight tile
     constexpr int WPW = NWI >= 4 ? NWI / 4 : 1;           // ... per wave (narrow tiles: the waves repeat each other's pieces)
     constexpr int XPW = UPS ? 4 * NP : NP;                // window pieces per wave and chunk (16-B lanes: 4 rows of 64 positions per piece)
-    static_assert(NSW == 3 || NSW == 4, "g_wait_tile counts at most two tiles ahead");
+    static_assert(NSW == 3 || NSW == 4, "wait_tile counts at most two tiles ahead");
     static_assert((2 * XST + NSW * WT) * sizeof(float) >= 4 * 32 * CE_PITCH * sizeof(float), "staging patches must fit in the rings (contiguous)");
     extern __shared__ __attribute__((aligned(16))) float g_lds[];
     float* lx = g_lds;
@@ -131,13 +108,13 @@ __global__ void __launch_bounds__(256, 3) conv1d_f32g_kernel(const ConvDev p) { 
             // (VB_CONV_XNT=1: the window - read by one or two workgroups - with the non-temporal policy, so that it does not displace the weights
             //  every workgroup re-reads from L2; A/B of round 5, profiles/r05_conv_window_nt.txt)
             if (p.x_nt) {
-                if constexpr (UPS) __builtin_amdgcn_global_load_lds((g_glb_ptr_t)(src + xsrc[i]), (g_lds_ptr_t)(dst + ii * 64), 4, 0, 2);
-                else __builtin_amdgcn_global_load_lds((g_glb_ptr_t)(src + xsrc[i]), (g_lds_ptr_t)(dst + ii * 256), 16, 0, 2);
+                if constexpr (UPS) __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + xsrc[i]), (lds_ptr_t)(dst + ii * 64), 4, 0, 2);
+                else __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + xsrc[i]), (lds_ptr_t)(dst + ii * 256), 16, 0, 2);
                 continue;
             }
 #endif
-            if constexpr (UPS) __builtin_amdgcn_global_load_lds((g_glb_ptr_t)(src + xsrc[i]), (g_lds_ptr_t)(dst + ii * 64), 4, 0, 0);
-            else __builtin_amdgcn_global_load_lds((g_glb_ptr_t)(src + xsrc[i]), (g_lds_ptr_t)(dst + ii * 256), 16, 0, 0);
+            if constexpr (UPS) __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + xsrc[i]), (lds_ptr_t)(dst + ii * 64), 4, 0, 0);
+            else __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + xsrc[i]), (lds_ptr_t)(dst + ii * 256), 16, 0, 0);
         }
     };
     // Once per chunk, by the lanes that DMA'd the quads, after the wave's own DMA has landed and in front of the barrier that publishes the
@@ -152,10 +129,10 @@ __global__ void __launch_bounds__(256, 3) conv1d_f32g_kernel(const ConvDev p) { 
             const unsigned a0 = lds_u32(lx + (ch & 1) * XST + wave * XPW * 64 + lane);
             float v[XPW];
             if (act) {
-                g_static_for<0, XPW>([&](auto ic) { constexpr int I = decltype(ic)::value; lds_rd32<I * 256>(v[I], a0); });
+                static_for<0, XPW>([&](auto ic) { constexpr int I = decltype(ic)::value; lds_rd32<I * 256>(v[I], a0); });
                 LDS_WAIT(0);
             }
-            g_static_for<0, XPW>([&](auto ic) {
+            static_for<0, XPW>([&](auto ic) {
                 constexpr int I = decltype(ic)::value;
                 const bool oob = (xoob >> I) & 1;
                 if (act) { lds_pin(v[I]); lds_wr32<I * 256>(a0, oob ? 0.f : fmaxf(v[I], v[I] * slope)); }
@@ -166,10 +143,10 @@ __global__ void __launch_bounds__(256, 3) conv1d_f32g_kernel(const ConvDev p) { 
             lds_u32x4 v[XPW];
             const lds_u32x4 zero = {0u, 0u, 0u, 0u};
             if (act) {
-                g_static_for<0, XPW>([&](auto ic) { constexpr int I = decltype(ic)::value; lds_rd128<I * 1024>(v[I], a0); });
+                static_for<0, XPW>([&](auto ic) { constexpr int I = decltype(ic)::value; lds_rd128<I * 1024>(v[I], a0); });
                 LDS_WAIT(0);
             }
-            g_static_for<0, XPW>([&](auto ic) {
+            static_for<0, XPW>([&](auto ic) {
                 constexpr int I = decltype(ic)::value;
                 const bool oob = (xoob >> I) & 1;
                 if (act) { lds_pin(v[I]); lds_wr128<I * 1024>(a0, oob ? zero : lds_lrelu128_apply(v[I], slope)); }
@@ -195,7 +172,7 @@ __global__ void __launch_bounds__(256, 3) conv1d_f32g_kernel(const ConvDev p) { 
 #pragma unroll
         for (int i = 0; i < WPW; ++i) {
             const int ii = (wave * WPW + i) % NWI;
-            __builtin_amdgcn_global_load_lds((g_glb_ptr_t)(src + wsrc[i]), (g_lds_ptr_t)(dst + ii * 256), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + wsrc[i]), (lds_ptr_t)(dst + ii * 256), 16, 0, 0);
         }
     };
 
@@ -239,8 +216,8 @@ __global__ void __launch_bounds__(256, 3) conv1d_f32g_kernel(const ConvDev p) { 
         auto fload = [&](auto kc) {
             constexpr int KK = decltype(kc)::value, S = KK % 3;
             if constexpr (ABL & 1) return;
-            g_static_for<0, TM>([&](auto ic) { constexpr int I = decltype(ic)::value; lds_rd32<(2 * KK * CO_TILE + I * 32) * 4>(a[S][I], waddr); });
-            g_static_for<0, TN>([&](auto jc) { constexpr int J = decltype(jc)::value; lds_rd32<(2 * KK * XP + J * 32) * 4>(bb[S][J], xaddr); });
+            static_for<0, TM>([&](auto ic) { constexpr int I = decltype(ic)::value; lds_rd32<(2 * KK * CO_TILE + I * 32) * 4>(a[S][I], waddr); });
+            static_for<0, TN>([&](auto jc) { constexpr int J = decltype(jc)::value; lds_rd32<(2 * KK * XP + J * 32) * 4>(bb[S][J], xaddr); });
         };
         fload(std::integral_constant<int, 0>{});
         fload(std::integral_constant<int, 1>{});
@@ -257,7 +234,7 @@ __global__ void __launch_bounds__(256, 3) conv1d_f32g_kernel(const ConvDev p) { 
                 else acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(da[i], dbv[jn], acc[i][jn], 0, 0, 0);
             }
         __builtin_amdgcn_sched_barrier(0);
-        g_static_for<0, GK / 2>([&](auto kc) {
+        static_for<0, GK / 2>([&](auto kc) {
             constexpr int KK = decltype(kc)::value, S = KK % 3;
             if constexpr (KK + 1 < GK / 2) LDS_WAIT(TM + TN); else LDS_WAIT(0);
 #pragma unroll
@@ -299,14 +276,14 @@ __global__ void __launch_bounds__(256, 3) conv1d_f32g_kernel(const ConvDev p) { 
             const unsigned xa_ch = xa0 + (ch & 1) * (XST * 4);
             auto chunk = [&](auto lastc) {
                 constexpr bool LAST = decltype(lastc)::value;
-                g_static_for<0, NT>([&](auto jc) {
+                static_for<0, NT>([&](auto jc) {
                     constexpr int J = decltype(jc)::value;
                     constexpr int AH = LAST ? (NT - 1 - J < NSW - 2 ? NT - 1 - J : NSW - 2) : NSW - 2;      // younger weight tiles that may fly
                     if constexpr (J == 0) {
-                        g_wait_vmcnt<(AH < NT ? AH : NT) * WPW>();
+                        wait_vmcnt<(AH < NT ? AH : NT) * WPW>();
                         if (act || xoob) { fix_x(ch); LDS_WAIT(0); }
                     } else {
-                        g_wait_vmcnt<AH * WPW + ((!LAST && J <= NSW - 2) ? XPW : 0)>();
+                        wait_vmcnt<AH * WPW + ((!LAST && J <= NSW - 2) ? XPW : 0)>();
                     }
                     if constexpr (!(ABL & 4)) __builtin_amdgcn_s_barrier();
                     if constexpr (J == 0 && !LAST) issue_x(ch + 1);
@@ -332,14 +309,14 @@ __global__ void __launch_bounds__(256, 3) conv1d_f32g_kernel(const ConvDev p) { 
             // tiles beside a second GPU process, profiles/r05_conv_tail_race.txt.)
             const int lag = NSW - 2 - p.ntaps;
 #ifdef VB_EXPERIMENTS
-            if (p.old_tail_wait) g_wait_tile<WPW, XPW>(ch == 0 ? ahead_all : min(ahead_all, p.ntaps), false);      // the round-4 count (tools/flake_conv.py)
+            if (p.old_tail_wait) wait_tile<WPW, XPW>(ch == 0 ? ahead_all : min(ahead_all, p.ntaps), false);      // the round-4 count (tools/flake_conv.py)
             else
 #endif
-            g_wait_tile<WPW, XPW>(ch == 0 || lag <= 0 ? ahead_all : max(ahead_all - lag, 0), false);
+            wait_tile<WPW, XPW>(ch == 0 || lag <= 0 ? ahead_all : max(ahead_all - lag, 0), false);
             if (act || xoob) { fix_x(ch); LDS_WAIT(0); }
         } else {
             // window ch + 1 was issued at this chunk's first tap, in front of tile (t - j + NSW - 1): younger than tile t while j <= NSW - 2
-            g_wait_tile<WPW, XPW>(ahead_all, ch + 1 < nchunks && j <= NSW - 2);
+            wait_tile<WPW, XPW>(ahead_all, ch + 1 < nchunks && j <= NSW - 2);
         }
         if constexpr (!(ABL & 4)) __builtin_amdgcn_s_barrier();    // tile t (and the window) landed everywhere; everyone finished tile t - 1
         if (j == 0 && ch + 1 < nchunks) issue_x(ch + 1);
@@ -377,8 +354,7 @@ template <int WM, int WN, int TM, int TN, bool UPS, int NSW = 4, int ABL = 0, in
 static void launch_cfg_g(ConvDev& d, int n_count, int B, hipStream_t st) {
     constexpr int CO_TILE = WM * TM * 32, T_TILE = WN * TN * 32, XP = (T_TILE + 64 + 63) / 64 * 64;
     constexpr int BYTES = (2 * GK * XP + NSW * GK * CO_TILE) * (int)sizeof(float);
-    d.g_nt = cdiv(n_count, T_TILE); d.g_nco = cdiv(d.Co, CO_TILE);
-    d.g_ntb = d.g_nt * B * d.phases; d.g_tbx = cdiv(d.g_ntb, 8);
+    const int grid = conv_xcd_grid(d, n_count, T_TILE, CO_TILE, B);
     static OnceFlags once;
     vb_set_max_lds_once(once, (const void*)conv1d_f32g_kernel<WM, WN, TM, TN, UPS, NSW, ABL, NT>, BYTES);
     int bytes = BYTES;
@@ -388,7 +364,7 @@ static void launch_cfg_g(ConvDev& d, int n_count, int B, hipStream_t st) {
     d.old_tail_wait = getenv("VB_F32G_OLDWAIT") ? 1 : 0;
     d.x_nt = getenv("VB_CONV_XNT") ? 1 : 0;
 #endif
-    hipLaunchKernelGGL((conv1d_f32g_kernel<WM, WN, TM, TN, UPS, NSW, ABL, NT>), dim3(8 * d.g_tbx * d.g_nco), dim3(256), bytes, st, d);
+    hipLaunchKernelGGL((conv1d_f32g_kernel<WM, WN, TM, TN, UPS, NSW, ABL, NT>), dim3(grid), dim3(256), bytes, st, d);
 }
 // Tile choice for wide layers (Co > 64).  Every configuration walks chunks, taps and channel pairs in the same order - the choice never
 // changes a bit of the result - so it is free to follow the launch's size: the busiest CU's load (workgroups on it x tile area) over a
@@ -421,7 +397,14 @@ static void launch_cfg_g_taps(ConvDev& d, int n_count, int B, hipStream_t st) {
     else if (nt == 11) launch_cfg_g<WM, WN, TM, TN, false, NSW, 0, 11>(d, n_count, B, st);
     else launch_cfg_g<WM, WN, TM, TN, false, NSW>(d, n_count, B, st);
 }
-// picks the tile and launches; the caller (launch_conv1d) has checked the kernel's conditions
+// The kernel's launch conditions: fp32 weights, shared or per clip, 16-byte aligned (tiles and clip strides); an input the window DMA can
+// fetch - as 16-byte pieces of aligned rows, or upsampled as 4-byte pieces (UPS; wide single-phase layers only: the 128-channel tiles);
+// halo <= 60 (window pitch = tile + 64 with <= 3 positions of alignment slack).
+bool conv1d_f32g_eligible(const ConvArgs& a, const ConvDev& d) {
+    return !a.wp && a.w_bstride % 4 == 0 && aligned16(a.w) && conv_dma_input(a, d, !a.upsample2) && (d.ntaps - 1) * d.dil <= 60 &&
+           (!a.upsample2 || (a.Co > 64 && d.phases == 1));
+}
+// picks the tile and launches; the caller (launch_conv1d) has checked conv1d_f32g_eligible
 void launch_conv1d_f32g(ConvDev& d, int n_count, int B, int upsample2, hipStream_t st) {
     if (upsample2) {
         const int64_t w128 = (int64_t)cdiv(n_count, 128) * cdiv(d.Co, 128) * B, w96 = (int64_t)cdiv(n_count, 96) * cdiv(d.Co, 128) * B;

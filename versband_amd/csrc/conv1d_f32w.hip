@@ -31,18 +31,8 @@
 #include <type_traits>
 
 #include "conv1d_dev.h"
+#include "dma_ring.h"
 #include "lds_asm.h"
-
-template <int I, int N, class F> __device__ __forceinline__ void w_static_for(F&& f) {
-    if constexpr (I < N) { f(std::integral_constant<int, I>{}); w_static_for<I + 1, N>(f); }
-}
-typedef __attribute__((address_space(3))) void* w_lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* w_glb_ptr_t;
-template <int N> __device__ __forceinline__ void w_wait_vmcnt() {
-    static_assert(N >= 0 && N < 64, "vmcnt is 6 bits");
-    __builtin_amdgcn_s_waitcnt(0x0f70 | (N & 15) | ((N >> 4) << 14));
-}
-
 #include "mf_taps.h"
 
 #define MF_PITCH 68          // floats per staged channel row (64 positions + 4)
@@ -120,7 +110,7 @@ __global__ void __launch_bounds__(256, OCC) conv1d_f32w_kernel(const ConvDev p) 
         float* dst = lx + stage * XST;
 #pragma unroll
         for (int i = 0; i < XPW; ++i)
-            __builtin_amdgcn_global_load_lds((w_glb_ptr_t)(src + xsrc[i]), (w_lds_ptr_t)(dst + (wave * XPW + i) * 256), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + xsrc[i]), (lds_ptr_t)(dst + (wave * XPW + i) * 256), 16, 0, 0);
     };
     const bool act = p.in_act == ACT_LRELU;
     auto fix_x = [&](int stage) {     // zero padding + LeakyReLU in place, by the lanes whose own DMA brought the quads
@@ -128,10 +118,10 @@ __global__ void __launch_bounds__(256, OCC) conv1d_f32w_kernel(const ConvDev p) 
         lds_u32x4 v[XPW];
         const lds_u32x4 zero = {0u, 0u, 0u, 0u};
         if (act) {
-            w_static_for<0, XPW>([&](auto ic) { constexpr int I = decltype(ic)::value; lds_rd128<I * 1024>(v[I], a0); });
+            static_for<0, XPW>([&](auto ic) { constexpr int I = decltype(ic)::value; lds_rd128<I * 1024>(v[I], a0); });
             LDS_WAIT(0);
         }
-        w_static_for<0, XPW>([&](auto ic) {
+        static_for<0, XPW>([&](auto ic) {
             constexpr int I = decltype(ic)::value;
             const bool oob = (xoob >> I) & 1;
             if (act) { lds_pin(v[I]); lds_wr128<I * 1024>(a0, oob ? zero : lds_lrelu128_apply(v[I], slope)); }
@@ -152,7 +142,7 @@ __global__ void __launch_bounds__(256, OCC) conv1d_f32w_kernel(const ConvDev p) 
         float* dst = lw + slot * WT;
 #pragma unroll
         for (int i = 0; i < WPW; ++i)
-            __builtin_amdgcn_global_load_lds((w_glb_ptr_t)(src + (int64_t)i * RPI * p.Co + wsrc0), (w_lds_ptr_t)(dst + (wave * WPW + i) * 256), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + (int64_t)i * RPI * p.Co + wsrc0), (lds_ptr_t)(dst + (wave * WPW + i) * 256), 16, 0, 0);
     };
 
     f32x16 acc[4][TM];
@@ -191,19 +181,19 @@ __global__ void __launch_bounds__(256, OCC) conv1d_f32w_kernel(const ConvDev p) 
         const unsigned xa_ch = xa0 + xs * (XST * 4);
         const int chn = ch + 1 < nchunks ? ch + 1 : 0;          // source of the weight tiles a step issues for the next chunk
         const int chx = ch + NXS - 1 < nchunks ? ch + NXS - 1 : 0;      // ... and of the window it issues (NXS - 1 chunks ahead)
-        w_static_for<0, P>([&](auto jc) {
+        static_for<0, P>([&](auto jc) {
             constexpr int J = decltype(jc)::value;
             constexpr MfTap TP = mf_tap(K, J);
             constexpr int PACC = mf_tap(K, (J + P - 1) % P).acc;        // the accumulator of the held-back pair (previous step)
             constexpr int AH = NSW - 2;                                   // younger weight tiles that may fly
             if constexpr (J == 0) {
-                w_wait_vmcnt<AH * WPW>();
+                wait_vmcnt<AH * WPW>();
 #ifdef VB_EXPERIMENTS
                 if (!(p.mf_abl & 1))
 #endif
                 if (act || xoob) { fix_x(xs); LDS_WAIT(0); }
             } else {
-                w_wait_vmcnt<AH * WPW + (J <= NSW - 2 ? XPW : 0)>();
+                wait_vmcnt<AH * WPW + (J <= NSW - 2 ? XPW : 0)>();
             }
             __builtin_amdgcn_s_barrier();
             if constexpr (J == 0) {       // window ch + NXS - 1 -> the stage chunk ch - 1 has just left
@@ -214,7 +204,7 @@ __global__ void __launch_bounds__(256, OCC) conv1d_f32w_kernel(const ConvDev p) 
                 float* dst = lx + xsn * XST;
 #pragma unroll
                 for (int i = 0; i < XPW; ++i)
-                    __builtin_amdgcn_global_load_lds((w_glb_ptr_t)(src + xsrc[i]), (w_lds_ptr_t)(dst + (wave * XPW + i) * 256), 16, 0, 0);
+                    __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + xsrc[i]), (lds_ptr_t)(dst + (wave * XPW + i) * 256), 16, 0, 0);
                 }
             }
             if constexpr (J + NSW - 1 < P) issue_w(ch, J + NSW - 1, nslot);
@@ -228,7 +218,7 @@ __global__ void __launch_bounds__(256, OCC) conv1d_f32w_kernel(const ConvDev p) 
                 float a[3][TM], xa[3], xb[3];
                 auto fload = [&](auto kc) {
                     constexpr int KK = decltype(kc)::value, S = KK % 3;
-                    w_static_for<0, TM>([&](auto ic) { constexpr int I = decltype(ic)::value; lds_rd32<(2 * KK * CO_TILE + I * 32) * 4>(a[S][I], waddr); });
+                    static_for<0, TM>([&](auto ic) { constexpr int I = decltype(ic)::value; lds_rd32<(2 * KK * CO_TILE + I * 32) * 4>(a[S][I], waddr); });
                     lds_rd32<(2 * KK * XP) * 4>(xa[S], xaddr_a);
                     if constexpr (TP.op != 2) lds_rd32<(2 * KK * XP) * 4>(xb[S], xaddr_b);
                 };
@@ -238,7 +228,7 @@ __global__ void __launch_bounds__(256, OCC) conv1d_f32w_kernel(const ConvDev p) 
 #pragma unroll
                 for (int i = 0; i < TM; ++i) MFMA_ACC(acc[PACC][i], da[i], dbv);
                 __builtin_amdgcn_sched_barrier(0);
-                w_static_for<0, GK / 2>([&](auto kc) {
+                static_for<0, GK / 2>([&](auto kc) {
                     constexpr int KK = decltype(kc)::value, S = KK % 3;
                     if constexpr (KK + 1 < GK / 2) LDS_WAIT(NR); else LDS_WAIT(0);
 #pragma unroll
@@ -266,7 +256,7 @@ __global__ void __launch_bounds__(256, OCC) conv1d_f32w_kernel(const ConvDev p) 
         if (++xs == NXS) xs = 0;
         if (++xsn == NXS) xsn = 0;
     }
-    w_wait_vmcnt<0>();                   // the loads the last chunk issued for a chunk that does not exist
+    wait_vmcnt<0>();                   // the loads the last chunk issued for a chunk that does not exist
     {
         constexpr int LACC = mf_tap(K, P - 1).acc;
 #pragma unroll
@@ -348,14 +338,13 @@ static void launch_w(ConvDev& d, int B, hipStream_t st) {
     constexpr int NXS = 2, NSW = 3;      // (the kernel's ring depths)
     constexpr int BYTES = (NXS * GK * XP + NSW * GK * CO_TILE) * (int)sizeof(float);
     const int T_TILE = WN * 2 * ((32 / d.dil) * d.dil);
-    d.g_nt = cdiv(d.T_out, T_TILE); d.g_nco = cdiv(d.Co, CO_TILE);
-    d.g_ntb = d.g_nt * B; d.g_tbx = cdiv(d.g_ntb, 8);
+    const int grid = conv_xcd_grid(d, d.T_out, T_TILE, CO_TILE, B);      // (phases == 1)
 #ifdef VB_EXPERIMENTS
     d.mf_abl = getenv("VB_F32W_ABL") ? atoi(getenv("VB_F32W_ABL")) : 0;
 #endif
     static OnceFlags once;
     vb_set_max_lds_once(once, (const void*)conv1d_f32w_kernel<K, OCC, WN>, BYTES);
-    hipLaunchKernelGGL((conv1d_f32w_kernel<K, OCC, WN>), dim3(8 * d.g_tbx * d.g_nco), dim3(256), BYTES, st, d);
+    hipLaunchKernelGGL((conv1d_f32w_kernel<K, OCC, WN>), dim3(grid), dim3(256), BYTES, st, d);
 }
 template <int OCC, int WN>
 static void launch_w_k(ConvDev& d, int B, hipStream_t st) {
@@ -367,10 +356,18 @@ static void launch_w_k(ConvDev& d, int B, hipStream_t st) {
     }
 }
 
-bool conv1d_f32w_supported(int ksize, int dil) { return (ksize == 3 || ksize == 5 || ksize == 7 || ksize == 11) && dil >= 1 && dil <= 8 && (ksize - 1) * dil <= 60; }
+// The kernel's launch conditions: shared minimal-filtering weights (16-byte aligned) and no others of another format; an ordinary stride-1
+// convolution (one phase, no upsampling) over an input the window DMA can fetch as 16-byte pieces; the kernel sizes the pseudo-tap table is
+// instantiated for, dilation <= 8 (MFMA columns per dilation class), halo <= 60; at least one 32-channel MFMA tile of outputs, which
+// leave through the kernel's own staged epilogue only (d.stage_epi).
+bool conv1d_f32w_eligible(const ConvArgs& a, const ConvDev& d) {
+    return a.w_mf && aligned16(a.w_mf) && !a.wp && !a.w_bstride && d.phases == 1 && !a.upsample2 && conv_dma_input(a, d, true) &&
+           (a.ksize == 3 || a.ksize == 5 || a.ksize == 7 || a.ksize == 11) && a.dil >= 1 && a.dil <= 8 && (a.ksize - 1) * a.dil <= 60 &&
+           a.Co >= 32 && d.stage_epi;
+}
 int conv1d_f32w_pseudo_taps(int ksize) { return mf_ntaps(ksize); }
 
-// the caller (launch_conv1d) has checked the conditions it shares with conv1d_f32g_kernel.  Two builds of the same code: <= 168 VGPRs (three
+// the caller (launch_conv1d) has checked conv1d_f32w_eligible.  Two builds of the same code: <= 168 VGPRs (three
 // workgroups per CU, 49 KB of LDS each) and <= 256 (two).  Two per CU measured 1 % faster end to end (1174 against 1163 mel-s/s, same box):
 // the default; VB_MF_OCC=3 selects the other (A/B knob)
 void launch_conv1d_f32w(ConvDev& d, int B, hipStream_t st) {

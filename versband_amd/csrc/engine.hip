@@ -1186,7 +1186,7 @@ int vb_net_load(vb_ctx* ctx, int which, const vb_net_op* ops, int n_ops, const v
                         sl.set ? "set but not read" : "missing");
         if (o.wfmt == VB_WFMT_X3 && o.ci_pad != (o.Ci + 31) / 32 * 32)
             VB_FAIL(VB_E_INVALID, "net_load: op %d: split weights padded to %d input channels, not %d rounded up to 32", i, o.ci_pad, o.Ci);
-        if (o.wfmt == VB_WFMT_MF && ((reinterpret_cast<uintptr_t>(o.w_mf) & 15) || (reinterpret_cast<uintptr_t>(o.w2) & 15)))
+        if (o.wfmt == VB_WFMT_MF && (!aligned16(o.w_mf) || !aligned16(o.w2)))
             VB_FAIL(VB_E_INVALID, "net_load: op %d: minimal-filtering weights are not 16-byte aligned", i);
         if (o.kind == VB_OP_RESPAIR) {
             if (!o.bias || !o.bias2) VB_FAIL(VB_E_INVALID, "net_load: op %d: respair without both biases", i);

@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "dma_ring.h"
 
 #define BM 128
 #define BN 128
@@ -632,17 +633,10 @@ __global__ void __launch_bounds__(NTHREADS) gemm_bf16_kernel(const GemmDev p) {
 // involution.  NST stages: tiles t+1 .. t+NST-1 are in flight while tile t is multiplied; the wait is a COUNTED
 // s_waitcnt vmcnt((NST-2)*loads_per_tile) + a raw s_barrier, so the DMA queue is never drained inside the loop.
 // Needs K % BKT == 0 (no zero fill on this path); out-of-range rows read a clamped valid row and are never stored.
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* glb_ptr_t;
 
 template <int BKT> __device__ __forceinline__ int lds_off_t(int row, int c) {
     if constexpr (BKT == 64) return row * 128 + ((c ^ ((row >> 1) & 7)) << 4);
     else return row * 64 + ((c ^ ((row >> 2) & 3)) << 4);
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-    static_assert(N >= 0 && N < 64, "vmcnt is 6 bits");
-    // s_waitcnt simm16 (gfx9): vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt_hi[15:14]; only vmcnt is counted here
-    __builtin_amdgcn_s_waitcnt(0x0f70 | (N & 15) | ((N >> 4) << 14));
 }
 
 // which epilogues of the 128x128 kernel go through LDS (staged_epilogue) instead of storing from the MFMA layout

@@ -14,7 +14,6 @@
 // ordered) wait.  LDS operations of one wave return in order, so "N younger ones in flight" is exact.
 #pragma once
 #include <stdint.h>
-#include <type_traits>
 
 __device__ __forceinline__ unsigned lds_u32(const void* p) {
     return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
@@ -54,7 +53,4 @@ __device__ __forceinline__ lds_u32x4 lds_lrelu128_apply(const lds_u32x4& v, floa
     r.x = __builtin_bit_cast(unsigned, lds_lrelu_bits(v.x, slope)); r.y = __builtin_bit_cast(unsigned, lds_lrelu_bits(v.y, slope));
     r.z = __builtin_bit_cast(unsigned, lds_lrelu_bits(v.z, slope)); r.w = __builtin_bit_cast(unsigned, lds_lrelu_bits(v.w, slope));
     return r;
-}
-template <int I, int N, class F> __device__ __forceinline__ void lds_static_for(F&& f) {
-    if constexpr (I < N) { f(std::integral_constant<int, I>{}); lds_static_for<I + 1, N>(f); }
 }

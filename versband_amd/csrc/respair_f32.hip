@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "dma_ring.h"
 #include "lds_asm.h"
 
 #define PF_T 128            // intermediate positions per workgroup (4 waves x 32)
@@ -28,27 +29,6 @@
 #define PF_HP 144           // intermediate pitch: 128 + (k-1 <= 16)
 #define PF_GK 16
 #define PF_EP 36
-
-typedef __attribute__((address_space(3))) void* pf_lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* pf_glb_ptr_t;
-template <int N> __device__ __forceinline__ void pf_wait_vmcnt() {
-    static_assert(N >= 0 && N < 64, "vmcnt is 6 bits");
-    __builtin_amdgcn_s_waitcnt(0x0f70 | (N & 15) | ((N >> 4) << 14));
-}
-template <int WPW, int XPW> __device__ __forceinline__ void pf_wait_tile(int ahead, bool xin) {
-    if (xin) {
-        if (ahead >= 2) pf_wait_vmcnt<2 * WPW + XPW>();
-        else if (ahead == 1) pf_wait_vmcnt<WPW + XPW>();
-        else pf_wait_vmcnt<XPW>();
-    } else {
-        if (ahead >= 2) pf_wait_vmcnt<2 * WPW>();
-        else if (ahead == 1) pf_wait_vmcnt<WPW>();
-        else pf_wait_vmcnt<0>();
-    }
-}
-template <int I, int N, class F> __device__ __forceinline__ void pf_static_for(F&& f) {
-    if constexpr (I < N) { f(std::integral_constant<int, I>{}); pf_static_for<I + 1, N>(f); }
-}
 
 struct PairF32Dev {
     const float* x; float* out; int64_t bstride; int T;
@@ -61,14 +41,6 @@ struct PairF32Dev {
     int x_nt;          // window DMA with the non-temporal policy (VB_CONV_XNT, see conv1d_f32g.hip)
 #endif
 };
-
-// one output element: the arithmetic of conv_out_value (conv1d_f32.hip) with acc_scale = 1 and no output activation
-__device__ __forceinline__ float pairf_out_value(const PairF32Dev& p, float acc, float bias, float res, float old) {
-#pragma clang fp contract(off)
-    float val = acc + bias;
-    val = val + res;
-    return fmaf(val, p.alpha, p.beta * old);
-}
 
 // C = 32*CH channels; a ring step multiplies TPS taps of one 16-channel chunk (at 32 channels a one-tap step is 8 MFMAs = 512 cycles
 // between two barriers, and the step's fixed costs - barrier, DMA issue, the first fragment round trip - were 40 % of it: four taps,
@@ -88,7 +60,7 @@ __global__ void __launch_bounds__(256) respair_f32_kernel(const PairF32Dev p) {
     constexpr int NP = PF_XP / 64;
     constexpr int XPW = NP;
     constexpr int XH = (2 * XST > C * PF_HP) ? 2 * XST : C * PF_HP;     // window ring and intermediate share storage
-    static_assert(NSW == 3 || NSW == 4, "pf_wait_tile counts at most two tiles ahead");
+    static_assert(NSW == 3 || NSW == 4, "wait_tile counts at most two tiles ahead");
     static_assert(XH * sizeof(float) >= 4 * 32 * PF_EP * sizeof(float), "staging patches must fit");
     extern __shared__ __attribute__((aligned(16))) float pf_lds[];
     float* lx = pf_lds;                                // conv1: window ring; then h[c][PF_HP]; then the epilogue patches
@@ -128,9 +100,9 @@ __global__ void __launch_bounds__(256) respair_f32_kernel(const PairF32Dev p) {
 #pragma unroll
         for (int i = 0; i < XPW; ++i) {
 #ifdef VB_EXPERIMENTS
-            if (p.x_nt) { __builtin_amdgcn_global_load_lds((pf_glb_ptr_t)(src + xsrc[i]), (pf_lds_ptr_t)(dst + (wave * XPW + i) * 256), 16, 0, 2); continue; }
+            if (p.x_nt) { __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + xsrc[i]), (lds_ptr_t)(dst + (wave * XPW + i) * 256), 16, 0, 2); continue; }
 #endif
-            __builtin_amdgcn_global_load_lds((pf_glb_ptr_t)(src + xsrc[i]), (pf_lds_ptr_t)(dst + (wave * XPW + i) * 256), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + xsrc[i]), (lds_ptr_t)(dst + (wave * XPW + i) * 256), 16, 0, 0);
         }
     };
     // once per chunk, by the lanes that DMA'd the quads (after the wave's own DMA landed, in front of the publishing barrier): zeros over
@@ -141,9 +113,9 @@ __global__ void __launch_bounds__(256) respair_f32_kernel(const PairF32Dev p) {
         const unsigned a0 = lds_u32(lx + (ch & 1) * XST + wave * XPW * 256 + lane * 4);
         lds_u32x4 v[XPW];
         const lds_u32x4 zero = {0u, 0u, 0u, 0u};
-        pf_static_for<0, XPW>([&](auto ic) { constexpr int I = decltype(ic)::value; lds_rd128<I * 1024>(v[I], a0); });
+        static_for<0, XPW>([&](auto ic) { constexpr int I = decltype(ic)::value; lds_rd128<I * 1024>(v[I], a0); });
         LDS_WAIT(0);
-        pf_static_for<0, XPW>([&](auto ic) {
+        static_for<0, XPW>([&](auto ic) {
             constexpr int I = decltype(ic)::value;
             lds_pin(v[I]);
             lds_wr128<I * 1024>(a0, ((xoob >> I) & 1) ? zero : lds_lrelu128_apply(v[I], slope));
@@ -163,7 +135,7 @@ __global__ void __launch_bounds__(256) respair_f32_kernel(const PairF32Dev p) {
             const int tap = piece / PPT, sub = piece - tap * PPT;
             const int j = min(s * TPS + tap, p.k - 1);          // taps beyond k: a valid block, never multiplied
             const float* src = wsrc + ((int64_t)j * C + ch * PF_GK) * C + sub * 256 + lane * 4;
-            __builtin_amdgcn_global_load_lds((pf_glb_ptr_t)src, (pf_lds_ptr_t)(dst + piece * 256), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((glb_ptr_t)src, (lds_ptr_t)(dst + piece * 256), 16, 0, 0);
         }
     };
 
@@ -191,11 +163,11 @@ __global__ void __launch_bounds__(256) respair_f32_kernel(const PairF32Dev p) {
             // (the window went out NS steps ago in front of tile t - NS + NSW - 1: see conv1d_f32g.hip for the count; conv1's tiles follow
             //  conv0's, so the end-of-sequence case - ahead_all < NSW - 2 - cannot meet a window here, the form is kept the same anyway)
             const int lag = NSW - 2 - NS;
-            pf_wait_tile<WPW, XPW>(ch == 0 || lag <= 0 ? ahead_all : max(ahead_all - lag, 0), false);
+            wait_tile<WPW, XPW>(ch == 0 || lag <= 0 ? ahead_all : max(ahead_all - lag, 0), false);
             fix_x(ch);
             LDS_WAIT(0);
         } else {
-            pf_wait_tile<WPW, XPW>(ahead_all, conv == 0 && ch + 1 < NCH && s <= NSW - 2);
+            wait_tile<WPW, XPW>(ahead_all, conv == 0 && ch + 1 < NCH && s <= NSW - 2);
         }
         if constexpr (!(ABL & 4)) __builtin_amdgcn_s_barrier();    // tile t (and the window) landed everywhere; everyone finished tile t - 1
         if (conv == 0 && s == 0 && ch + 1 < NCH) issue_x(ch + 1);
@@ -228,7 +200,7 @@ __global__ void __launch_bounds__(256) respair_f32_kernel(const PairF32Dev p) {
         auto fload = [&](auto mc) {
             constexpr int M = decltype(mc)::value, TP = M / 8, KK = M % 8, S = M % 3;
             if constexpr (ABL & 1) return;
-            pf_static_for<0, CH>([&](auto ic) {
+            static_for<0, CH>([&](auto ic) {
                 constexpr int I = decltype(ic)::value;
                 lds_rd32<((TP * PF_GK + 2 * KK) * C + I * 32) * 4>(fa[S][I], waddr);
             });
@@ -236,7 +208,7 @@ __global__ void __launch_bounds__(256) respair_f32_kernel(const PairF32Dev p) {
         };
         fload(std::integral_constant<int, 0>{});
         fload(std::integral_constant<int, 1>{});
-        pf_static_for<0, NM>([&](auto mc) {
+        static_for<0, NM>([&](auto mc) {
             constexpr int M = decltype(mc)::value, S = M % 3;
             if constexpr (M + 1 < NM) LDS_WAIT(CH + 1); else LDS_WAIT(0);
 #pragma unroll
@@ -257,7 +229,7 @@ __global__ void __launch_bounds__(256) respair_f32_kernel(const PairF32Dev p) {
         const unsigned waddr = lds_u32(lw + slot * WT + l31 + g * C);
         const unsigned b0 = CONV ? lds_u32(lx + (ch * PF_GK + g) * PF_HP + s * TPS + 32 * wave + l31)
                                  : lds_u32(lx + (ch & 1) * XST + g * PF_XP + aoff + s * TPS * p.dil + 32 * wave + l31);
-        pf_static_for<1, TPS + 1>([&](auto ntc) {
+        static_for<1, TPS + 1>([&](auto ntc) {
             if (ntap == decltype(ntc)::value) body(convc, ntc, waddr, b0, CONV ? 4u : (unsigned)(p.dil * 4));
         });
     };
@@ -296,15 +268,15 @@ __global__ void __launch_bounds__(256) respair_f32_kernel(const PairF32Dev p) {
             constexpr int CONV = decltype(convc)::value;
             constexpr bool LASTCH = decltype(lastc)::value, FIRST1 = decltype(firstc)::value;      // last chunk of this convolution; conv2's first chunk
             const unsigned bch = CONV ? ha0 + ch * (PF_GK * PF_HP * 4) : xa0 + (ch & 1) * (XST * 4);
-            pf_static_for<0, KNS>([&](auto sc) {
+            static_for<0, KNS>([&](auto sc) {
                 constexpr int S = decltype(sc)::value;
                 constexpr int AH = (CONV == 1 && LASTCH) ? (KNS - 1 - S < NSW - 2 ? KNS - 1 - S : NSW - 2) : NSW - 2;   // younger weight tiles that may fly
                 if constexpr (CONV == 0 && S == 0) {
-                    pf_wait_vmcnt<(AH < KNS ? AH : KNS) * WPW>();
+                    wait_vmcnt<(AH < KNS ? AH : KNS) * WPW>();
                     fix_x(ch);
                     LDS_WAIT(0);
                 } else {
-                    pf_wait_vmcnt<AH * WPW + ((CONV == 0 && !LASTCH && S <= NSW - 2) ? XPW : 0)>();
+                    wait_vmcnt<AH * WPW + ((CONV == 0 && !LASTCH && S <= NSW - 2) ? XPW : 0)>();
                 }
                 if constexpr (!(ABL & 4)) __builtin_amdgcn_s_barrier();
                 if constexpr (CONV == 0 && S == 0 && !LASTCH) issue_x(ch + 1);
@@ -391,7 +363,7 @@ __global__ void __launch_bounds__(256) respair_f32_kernel(const PairF32Dev p) {
                     const float o4[4] = {ov[q].x, ov[q].y, ov[q].z, ov[q].w};
                     float o[4];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = pairf_out_value(p, a4[e], bv[q], r4[e], o4[e]);
+                    for (int e = 0; e < 4; ++e) o[e] = pair_out_value(p.alpha, p.beta, a4[e], bv[q], r4[e], o4[e]);
                     *reinterpret_cast<float4*>(ob + (int64_t)co * p.T + n) = make_float4(o[0], o[1], o[2], o[3]);
                 }
             }
@@ -414,7 +386,7 @@ __global__ void __launch_bounds__(256) respair_f32_kernel(const PairF32Dev p) {
             for (int r = 0; r < 16; ++r) {
                 const int co = i * 32 + 4 * g + 8 * (r >> 2) + (r & 3);
                 if (!nok) continue;
-                ob[(int64_t)co * p.T + n] = pairf_out_value(p, acc[i][r], bv[r], rv[r], ov[r]);
+                ob[(int64_t)co * p.T + n] = pair_out_value(p.alpha, p.beta, acc[i][r], bv[r], rv[r], ov[r]);
             }
         }
     }
@@ -432,8 +404,7 @@ static void launch_pair_f32(const PairF32Dev& d, dim3 grid, hipStream_t st) {
 
 bool respair_f32_supported(const RespairF32Args& a) {
     return (a.C == 32 || a.C == 64 || a.C == 128) && a.k >= 1 && (a.k & 1) && a.k <= 17 && (a.k - 1) * a.dil <= 60 && a.T % 4 == 0 &&
-           (reinterpret_cast<uintptr_t>(a.x) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.w1) & 15) == 0 &&
-           (reinterpret_cast<uintptr_t>(a.w2) & 15) == 0;
+           aligned16(a.x) && aligned16(a.w1) && aligned16(a.w2);
 }
 
 int launch_respair_f32(const RespairF32Args& a, hipStream_t st) {
@@ -443,7 +414,7 @@ int launch_respair_f32(const RespairF32Args& a, hipStream_t st) {
     d.x = a.x; d.out = a.out; d.bstride = (int64_t)a.C * a.T; d.T = a.T; d.k = a.k; d.dil = a.dil;
     d.w1 = a.w1; d.w2 = a.w2; d.b1 = a.b1; d.b2 = a.b2; d.slope = a.slope; d.alpha = a.alpha; d.beta = a.beta;
     const int TT = (PF_T - (a.k - 1)) & ~3;
-    d.staged = ((reinterpret_cast<uintptr_t>(a.out) & 15) == 0 && !vb_tune().conv_direct_epi) ? 1 : 0;
+    d.staged = (aligned16(a.out) && !vb_tune().conv_direct_epi) ? 1 : 0;
 #ifdef VB_EXPERIMENTS
     d.x_nt = getenv("VB_CONV_XNT") ? 1 : 0;
 #endif
@@ -475,8 +446,6 @@ int launch_respair_f32(const RespairF32Args& a, hipStream_t st) {
         }
         if (done) { VB_CHECK_LAUNCH(); return VB_OK; }
     }
-#endif
-#ifdef VB_EXPERIMENTS
     if (const char* e = getenv("VB_PAIRF_CFG")) {           // ring shapes measured and not adopted (tools/conv_f32_ablate.py)
         const int v = atoi(e);
         if (a.C == 64 && v == 1) { launch_pair_f32<2, 1, 4>(d, grid, st); VB_CHECK_LAUNCH(); return VB_OK; }     // 53 KB: three workgroups per CU, one tap per step

@@ -24,21 +24,12 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "dma_ring.h"
 #include "lds_asm.h"
 #include "mf_taps.h"
 
 #define PW_GK 16
 #define PW_EP 68             // staged epilogue patch pitch (64 positions + 4)
-
-typedef __attribute__((address_space(3))) void* pw_lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* pw_glb_ptr_t;
-template <int N> __device__ __forceinline__ void pw_wait_vmcnt() {
-    static_assert(N >= 0 && N < 64, "vmcnt is 6 bits");
-    __builtin_amdgcn_s_waitcnt(0x0f70 | (N & 15) | ((N >> 4) << 14));
-}
-template <int I, int N, class F> __device__ __forceinline__ void pw_static_for(F&& f) {
-    if constexpr (I < N) { f(std::integral_constant<int, I>{}); pw_static_for<I + 1, N>(f); }
-}
 
 struct PairWDev {
     const float* x; float* out; int64_t bstride; int T;
@@ -47,13 +38,6 @@ struct PairWDev {
     const float* b1; const float* b2;
     float slope, alpha, beta;
 };
-
-__device__ __forceinline__ float pairw_out_value(const PairWDev& p, float acc, float bias, float res, float old) {
-#pragma clang fp contract(off)
-    float val = acc + bias;          // conv_out_value (conv1d_dev.h) with acc_scale = 1, no output activation
-    val = val + res;
-    return fmaf(val, p.alpha, p.beta * old);
-}
 
 template <int K, int TPS, int C>
 __global__ void __launch_bounds__(256, 2) respair_f32w_kernel(const PairWDev p) {
@@ -112,8 +96,8 @@ __global__ void __launch_bounds__(256, 2) respair_f32w_kernel(const PairWDev p) 
     auto issue_x = [&](int ch) {
 #pragma unroll
         for (int i = 0; i < XPW; ++i)
-            __builtin_amdgcn_global_load_lds((pw_glb_ptr_t)(xb + (int64_t)ch * PW_GK * p.T + xsrc[i]),
-                                             (pw_lds_ptr_t)(lx + (ch & 1) * XST + (wave * XPW + i) * 256), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((glb_ptr_t)(xb + (int64_t)ch * PW_GK * p.T + xsrc[i]),
+                                             (lds_ptr_t)(lx + (ch & 1) * XST + (wave * XPW + i) * 256), 16, 0, 0);
     };
     issue_x(0);
     issue_x(1);
@@ -121,9 +105,9 @@ __global__ void __launch_bounds__(256, 2) respair_f32w_kernel(const PairWDev p) 
         const unsigned a0 = lds_u32(lx + (ch & 1) * XST + wave * XPW * 256 + lane * 4);
         lds_u32x4 v[XPW];
         const lds_u32x4 zero = {0u, 0u, 0u, 0u};
-        pw_static_for<0, XPW>([&](auto ic) { constexpr int I = decltype(ic)::value; lds_rd128<I * 1024>(v[I], a0); });
+        static_for<0, XPW>([&](auto ic) { constexpr int I = decltype(ic)::value; lds_rd128<I * 1024>(v[I], a0); });
         LDS_WAIT(0);
-        pw_static_for<0, XPW>([&](auto ic) {
+        static_for<0, XPW>([&](auto ic) {
             constexpr int I = decltype(ic)::value;
             lds_pin(v[I]);
             lds_wr128<I * 1024>(a0, ((xoob >> I) & 1) ? zero : lds_lrelu128_apply(v[I], slope));
@@ -144,7 +128,7 @@ __global__ void __launch_bounds__(256, 2) respair_f32w_kernel(const PairWDev p) 
             int j = S * TPS + tap;
             if (j > P - 1) j = P - 1;                  // pseudo-taps beyond P: a valid block, never multiplied
             const float* src = wsrc + ((int64_t)j * C + CH * PW_GK) * C + sub * 256 + lane * 4;
-            __builtin_amdgcn_global_load_lds((pw_glb_ptr_t)src, (pw_lds_ptr_t)(dst + piece * 256), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((glb_ptr_t)src, (lds_ptr_t)(dst + piece * 256), 16, 0, 0);
         }
     };
     issue_w(std::integral_constant<int, 0>{});
@@ -193,13 +177,13 @@ __global__ void __launch_bounds__(256, 2) respair_f32w_kernel(const PairWDev p) 
 
     // ---- the unrolled schedule.  Issue order: windows 0, 1, tiles 0, 1; then per step [window c + 1 at conv1 chunk c's first step, c >= 1], tile t + 2.
     // In front of step t the loads younger than tile t are: the window step t - 1 issued (if it did) and tile t + 1.
-    pw_static_for<0, NT>([&](auto tc) {
+    static_for<0, NT>([&](auto tc) {
         constexpr int T_ = decltype(tc)::value;
         constexpr int CONV = T_ / (NCH * KNS), CH = (T_ / KNS) % NCH, S = T_ % KNS, SLOT = T_ % NSW;
         constexpr int TP_ = T_ > 0 ? T_ - 1 : 0;        // the previous step: did it request a window?
         constexpr bool PREV_WIN = T_ > 0 && (TP_ / (NCH * KNS)) == 0 && (TP_ % KNS) == 0 && ((TP_ / KNS) % NCH) >= 1 && ((TP_ / KNS) % NCH) + 1 < NCH;
         constexpr int AHEAD = (NT - 1 - T_) < (NSW - 2) ? (NT - 1 - T_) : (NSW - 2);       // younger weight tiles that may fly
-        pw_wait_vmcnt<AHEAD * WPW + (PREV_WIN ? XPW : 0)>();
+        wait_vmcnt<AHEAD * WPW + (PREV_WIN ? XPW : 0)>();
         if constexpr (CONV == 0 && S == 0) { fix_x(CH); LDS_WAIT(0); }
         __builtin_amdgcn_s_barrier();          // tile T_ (and its window) landed everywhere; everyone finished step T_ - 1
         if constexpr (CONV == 0 && S == 0 && CH >= 1 && CH + 1 < NCH) issue_x(CH + 1);      // -> the stage chunk CH - 1 has left
@@ -225,7 +209,7 @@ __global__ void __launch_bounds__(256, 2) respair_f32w_kernel(const PairWDev p) 
         };
         fload(std::integral_constant<int, 0>{});
         fload(std::integral_constant<int, 1>{});
-        pw_static_for<0, NM>([&](auto mc) {
+        static_for<0, NM>([&](auto mc) {
             constexpr int MM = decltype(mc)::value, SS = MM % 3;
             constexpr MfTap MT = mf_tap(K, J0 + MM / 8);
             if constexpr (MM + 1 < NM) {
@@ -281,8 +265,8 @@ __global__ void __launch_bounds__(256, 2) respair_f32w_kernel(const PairWDev p) 
                 for (int q = 0; q < 4; ++q) {
                     const int co = wc * 32 + rr + 4 * (kh * 4 + q);
                     float4 o;
-                    o.x = pairw_out_value(p, v[q].x, bv[q], rv[q].x, ov[q].x); o.y = pairw_out_value(p, v[q].y, bv[q], rv[q].y, ov[q].y);
-                    o.z = pairw_out_value(p, v[q].z, bv[q], rv[q].z, ov[q].z); o.w = pairw_out_value(p, v[q].w, bv[q], rv[q].w, ov[q].w);
+                    o.x = pair_out_value(p.alpha, p.beta, v[q].x, bv[q], rv[q].x, ov[q].x); o.y = pair_out_value(p.alpha, p.beta, v[q].y, bv[q], rv[q].y, ov[q].y);
+                    o.z = pair_out_value(p.alpha, p.beta, v[q].z, bv[q], rv[q].z, ov[q].z); o.w = pair_out_value(p.alpha, p.beta, v[q].w, bv[q], rv[q].w, ov[q].w);
                     *reinterpret_cast<float4*>(ob + (int64_t)co * p.T + n) = o;
                 }
             }
@@ -304,8 +288,7 @@ static void launch_pair_w(const PairWDev& d, int B, hipStream_t st) {
 
 bool respair_f32w_supported(const RespairF32Args& a) {
     return (a.C == 32 || a.C == 64) && (a.k == 3 || a.k == 7 || a.k == 11) && a.dil >= 1 && a.dil <= 8 && (a.k - 1) * a.dil <= 60 && a.T % 4 == 0 &&
-           (reinterpret_cast<uintptr_t>(a.x) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0 &&
-           (reinterpret_cast<uintptr_t>(a.w1) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.w2) & 15) == 0;
+           aligned16(a.x) && aligned16(a.out) && aligned16(a.w1) && aligned16(a.w2);
 }
 
 // a.w1 / a.w2 are the minimal-filtering pseudo-tap weights of the two convolutions ([P][C][C], pack.py:pack_conv_mf)

@@ -13,6 +13,7 @@
 //   * conv2 over hT, + b2 + residual x, alpha/beta accumulation into the MRF sum, coalesced stores (a lane owns one t).
 // Same operand precision as conv1d_x3_kernel (operand error 2^-17, fp32 accumulate).
 #include "kernels.h"
+#include "dma_ring.h"
 
 #define RP_T 128            // intermediate positions per workgroup (4 waves x 32)
 #define RP_HALO 64          // max (k-1)*dil of conv1
@@ -27,14 +28,6 @@ struct PairDev {
     float slope, alpha, beta;
     int staged;               // 16-B (staged) epilogue: T % 4 == 0 and 16-B aligned tensors
 };
-
-// one output element (pinned arithmetic: the direct and the staged epilogue must round alike)
-__device__ __forceinline__ float pair_out_value(const PairDev& p, float acc, float bias, float res, float old) {
-#pragma clang fp contract(off)
-    float val = acc + bias;
-    val = val + res;
-    return fmaf(val, p.alpha, p.beta * old);
-}
 
 template <int CH>      // C = 32*CH channels
 __global__ void __launch_bounds__(256) respair_x3_kernel(const PairDev p) {
@@ -239,7 +232,7 @@ __global__ void __launch_bounds__(256) respair_x3_kernel(const PairDev p) {
                     const float o4[4] = {ov[k].x, ov[k].y, ov[k].z, ov[k].w};
                     float q[4];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) q[e] = pair_out_value(p, a4[e], bv[k], r4[e], o4[e]);
+                    for (int e = 0; e < 4; ++e) q[e] = pair_out_value(p.alpha, p.beta, a4[e], bv[k], r4[e], o4[e]);
                     *reinterpret_cast<float4*>(ob + (int64_t)co * p.T + n) = make_float4(q[0], q[1], q[2], q[3]);
                 }
             }
@@ -263,7 +256,7 @@ __global__ void __launch_bounds__(256) respair_x3_kernel(const PairDev p) {
             for (int r = 0; r < 16; ++r) {
                 const int co = i * 32 + 4 * g + 8 * (r >> 2) + (r & 3);
                 if (!nok) continue;
-                ob[(int64_t)co * p.T + n] = pair_out_value(p, acc[i][r], bv[r], rv[r], ov[r]);
+                ob[(int64_t)co * p.T + n] = pair_out_value(p.alpha, p.beta, acc[i][r], bv[r], rv[r], ov[r]);
             }
         }
     }
@@ -279,8 +272,7 @@ int launch_respair(const RespairArgs& a, hipStream_t st) {
     d.w1 = a.w1; d.w2 = a.w2; d.w_plane = (int64_t)a.k * a.C * a.C; d.b1 = a.b1; d.b2 = a.b2;
     d.slope = a.slope; d.alpha = a.alpha; d.beta = a.beta;
     const int TT = (RP_T - (a.k - 1)) & ~3;
-    d.staged = (a.T % 4 == 0 && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0 &&
-                !vb_tune().conv_direct_epi) ? 1 : 0;
+    d.staged = (a.T % 4 == 0 && aligned16(a.x) && aligned16(a.out) && !vb_tune().conv_direct_epi) ? 1 : 0;
     dim3 grid(cdiv(a.T, TT), 1, a.B);
     // two convolutions' worth of flops (the recomputed halo of conv1 is not counted)
     ProfScope prof(3, 2.0 * 2.0 * a.B * (double)a.C * a.C * a.k * (double)a.T,

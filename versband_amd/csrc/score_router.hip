@@ -14,15 +14,9 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "dma_ring.h"
 #include "router_dev.h"
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* glb_ptr_t;
-
-template <int N> __device__ __forceinline__ void sr_wait_vmcnt() {
-    static_assert(N >= 0 && N < 64, "vmcnt is 6 bits");
-    __builtin_amdgcn_s_waitcnt(0x0f70 | (N & 15) | ((N >> 4) << 14));
-}
 // byte offset of 16-B chunk c of tile row `row` in a BK = 32 operand image (64 B per row; chunk XOR-swizzled by the row)
 __device__ __forceinline__ int sr_off(int row, int c) { return row * 64 + ((c ^ ((row >> 2) & 3)) << 4); }
 
@@ -101,8 +95,8 @@ __global__ void __launch_bounds__(256) score_router_kernel(const ScoreRouterDev 
         if (t < KT) issue(t);
     const int frow = lane & 31, fk = lane >> 5;
     for (int t = 0; t < KT; ++t) {
-        if (t + 1 < KT) sr_wait_vmcnt<PPW>();         // tile t landed, tile t + 1 may stay in flight
-        else sr_wait_vmcnt<0>();
+        if (t + 1 < KT) wait_vmcnt<PPW>();         // tile t landed, tile t + 1 may stay in flight
+        else wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();                 // ... everywhere; everyone is done reading stage (t - 1) % NST
         if (t + SR_NST - 1 < KT) issue(t + SR_NST - 1);
         const unsigned char* As = sr_lds + (t % SR_NST) * STAGE;
