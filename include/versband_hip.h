@@ -173,6 +173,27 @@ int vb_euler_cfg_step(float* x, const float* v, int B, int64_t per_item, float c
 int vb_sample_cfg(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
                   const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_noise* noise, float* traj,
                   void* ws, void* stream);
+/* The same sampler with a KNOWN REGION held on the model's probability path (inpainting, continuation; build-defined, the reference has
+ * none).  The flow-matching model is trained on x_t = t x1 + (1 - (1 - sigma_min) t) x0 (ldm/models/diffusion/cfm1_audio.py:38-43).  After
+ * the Euler step k that ends at time tn = t_next[k], every element (b, c, t) of the state becomes, in fp32 and in exactly this arithmetic,
+ *     xn = fmaf(dt, e, x)                                        (the plain update; e = the CFG-combined velocity)
+ *     r  = fmaf(tn, ref, (1 - (1 - sigma_min) * tn) * x0)
+ *     x  = fmaf(m, r, (1 - m) * xn)                              m = mask[b][t]
+ * so m = 0 leaves xn and m = 1 gives r, both bit for bit; a fractional m is a soft edge (the caller's choice).  The free tokens evolve
+ * under the DiT, whose self-attention sees the known tokens at the right noise level at every step.  On entry the state is projected
+ * the same way at t_0 = t_next[0] - dt_table[0] (exact on a linspace grid): x = fmaf(m, r(t_0), (1 - m) x) - it matters when the call
+ * starts inside the path (t_start); at t_0 = 0 with x = x0 it changes nothing.  traj[0] is the projected state.
+ *   ref, x0  f32 [B][C][T]  the known content (sampler latent scale) and the noise the sampler started from (device)
+ *   mask     f32 [B][T]     in [0, 1] (device; not range-checked here)
+ *   t_next   f32 [n_steps]  time after each step; host OR device, copied like dt_table
+ * The final state of a kept token at t = 1 is ref + sigma_min * x0, NOT ref: that is the end point of the path the model was trained on.
+ * keep == NULL is exactly vb_sample_cfg.  Graph capture works as below; the key also holds ref, x0, mask and sigma_min, so a call with
+ * other buffers captures its own graph and a plain call never replays a keep graph.  The fused (one launch per step) and the separate
+ * (n_branch == 1, VB_EULER_LAUNCH) update forms are bit-identical. */
+typedef struct { const float* ref; const float* x0; const float* mask; const float* t_next; float sigma_min; } vb_keep;
+int vb_sample_cfg_keep(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
+                       const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_keep* keep,
+                       const vb_noise* noise, float* traj, void* ws, void* stream);
 /* The step loop of vb_sample_cfg is captured into a hipGraph the second time a call arrives with the same buffers / shape on a
  * capturable (non-default) stream and replayed from then on (noise key via device memory: any seed / clip base replays).
  * Number of instantiated graphs this context holds (0 = every call so far ran eagerly): */
@@ -338,7 +359,7 @@ int vb_conv1d_f32(const float* x, const float* w, const float* bias, int B, int 
 /* Conv1d in fp32 with 1-D minimal filtering (conv1d_f32w.hip; the HiFi-GAN ResBlock convolutions, vocoder/hifigan/modules/hifigan.py:27-64):
  * out = beta*out + alpha*(conv_{k,dil,pad}(act(x)) + bias + res); w = packed [k][Ci][Co] (the fallback when the layer is not eligible),
  * w_mf = the same filter as F(2,3) pseudo-taps [P][Ci][Co] (pack.py:pack_conv_mf).  k = 3 / 5 / 7 / 11, stride 1, Ci % 16 == 0, Co % 4 == 0,
- * Co >= 32, T % 4 == 0.  Agrees with vb_conv1d_f32 to fp32 roundoff, not bit for bit. */
+ * Co >= 32, T % 4 == 0 (anything else runs the direct kernels on w).  Agrees with vb_conv1d_f32 to fp32 roundoff, not bit for bit. */
 int vb_conv1d_f32_mf(const float* x, const float* w, const float* w_mf, const float* bias, int B, int Ci, int T_in, int Co, int ksize, int dil,
                      int pad, int T_out, int in_act, float in_slope, const float* res, float alpha, float beta, float* out, void* stream);
 /* HiFi-GAN ResBlock1 pair in exact fp32, one launch (vocoder/hifigan/modules/hifigan.py:27-64; respair_f32.hip):
@@ -348,7 +369,7 @@ int vb_respair_f32(const float* x, const float* w1, const float* b1, const float
                    float slope, float alpha, float beta, float* out, void* stream);
 /* The same pair with F(2,3) minimal filtering in both convolutions (respair_f32w.hip): w1_mf / w2_mf = pseudo-tap weights [P][C][C]
  * (pack.py:pack_conv_mf); C = 32 / 64, k = 3 / 7 / 11, (k-1)*dil <= 60, T % 4 == 0.  Agrees with two vb_conv1d_f32_mf launches to fp32
- * roundoff, not bit for bit. */
+ * roundoff (about a third of the elements differ by one ulp, < 4e-6 of the output's max-abs), not bit for bit. */
 int vb_respair_f32_mf(const float* x, const float* w1_mf, const float* b1, const float* w2_mf, const float* b2, int B, int C, int T, int k, int dil,
                       float slope, float alpha, float beta, float* out, void* stream);
 /* counter-based Gumbel draws: out[rows][w], rows = n_branch*B*T */

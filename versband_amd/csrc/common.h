@@ -43,6 +43,20 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// Known-region blend of the sampler (vb_sample_cfg_keep): a token marked as known is put back on the model's probability path
+// x_t = t x1 + (1 - (1 - sigma_min) t) x0 (cfm1_audio.py:38-43) after every Euler step.  keep_path is r(t) for the known content `ref`
+// and the call's start noise `x0`, keep_blend mixes it into the solver's state with the mask value m in [0, 1]: m = 0 returns xn and
+// m = 1 returns r bit for bit.  The fused (rowlin.hip), unfused and entry-projection kernels (elementwise.hip) all go through these
+// two, with contraction off, so they round alike.
+__device__ __forceinline__ float keep_path(float t, float sigma_min, float ref, float x0) {
+#pragma clang fp contract(off)
+    return fmaf(t, ref, (1.f - (1.f - sigma_min) * t) * x0);
+}
+__device__ __forceinline__ float keep_blend(float m, float r, float xn) {
+#pragma clang fp contract(off)
+    return fmaf(m, r, (1.f - m) * xn);
+}
+
 // ---- host side -------------------------------------------------------------
 extern thread_local char g_vb_err[512];
 #ifndef VB_OK

@@ -337,6 +337,48 @@ int launch_euler_cfg(float* x, const float* v, int B, int64_t per, float cfg_sca
     VB_CHECK_LAUNCH();
     return VB_OK;
 }
+// The same update with a known region (vb_sample_cfg_keep, the paths that do not fuse it into FinalLayer): the two fused multiply-adds
+// of euler_cfg_kernel, then the blend of common.h at t = tn_table[step] - bit-identical to final_layer_kernel<NQ, true, true>
+__global__ void euler_cfg_keep_kernel(float* x, const float* __restrict__ v, int64_t n, int64_t per, int T, float cfg_scale,
+                                      const float* dt_table, const int* step, int has_uncond, const EulerKeep kp) {
+    const int k = *step;
+    const float dt = dt_table[k], tn = kp.tn_table[k];
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float e = v[i];
+    if (has_uncond) {
+        float eu = v[n + i];
+        e = fmaf(cfg_scale, e - eu, eu);
+    }
+    const float xn = fmaf(dt, e, x[i]);
+    const int64_t b = i / per;
+    const float m = kp.mask[b * T + (i - b * per) % T];
+    x[i] = keep_blend(m, keep_path(tn, kp.sigma_min, kp.ref[i], kp.x0[i]), xn);
+}
+int launch_euler_cfg_keep(float* x, const float* v, int B, int64_t per, int T, float cfg_scale, const float* dt_table, const int* step,
+                          int has_uncond, const EulerKeep& keep, hipStream_t st) {
+    int64_t n = (int64_t)B * per;
+    hipLaunchKernelGGL(euler_cfg_keep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, v, n, per, T, cfg_scale, dt_table,
+                       step, has_uncond, keep);
+    VB_CHECK_LAUNCH();
+    return VB_OK;
+}
+// known region on entry: the state a call starts from is put on the path at t_0 = tn_table[0] - dt_table[0] (exact for a linspace
+// grid: the difference of neighbouring grid points is); a no-op at t_0 = 0 with x = x0
+__global__ void keep_project_kernel(float* x, int64_t n, int64_t per, int T, const float* dt_table, const EulerKeep kp) {
+    const float t0 = kp.tn_table[0] - dt_table[0];
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t b = i / per;
+    const float m = kp.mask[b * T + (i - b * per) % T];
+    x[i] = keep_blend(m, keep_path(t0, kp.sigma_min, kp.ref[i], kp.x0[i]), x[i]);
+}
+int launch_keep_project(float* x, int B, int64_t per, int T, const float* dt_table, const EulerKeep& keep, hipStream_t st) {
+    int64_t n = (int64_t)B * per;
+    hipLaunchKernelGGL(keep_project_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, n, per, T, dt_table, keep);
+    VB_CHECK_LAUNCH();
+    return VB_OK;
+}
 // step bookkeeping for graph replay: (reset) step=0 or step+=1; t_idx_cur[:] = t_table[step]
 __global__ void step_advance_kernel(int* step, int64_t* t_idx_cur, const int64_t* t_table, int n_steps, int Beff, int reset) {
     __shared__ int s;

@@ -160,6 +160,7 @@ struct NetProgram {
 struct SampleGraph {
     const void* x = nullptr; const void* cond = nullptr; const void* ws = nullptr;
     int B = 0, nb = 0, T = 0, L = 0, n_steps = 0; float cfg_scale = 0.f; unsigned tune_gen = 0;
+    const void* keep_ref = nullptr; const void* keep_x0 = nullptr; const void* keep_mask = nullptr; float sigma_min = 0.f;   // vb_sample_cfg_keep (all null: a plain call)
     int seen = 0;                         // calls with this key so far (the first runs eagerly, the second captures)
     bool failed = false;                  // capture was refused once (e.g. legacy default stream): stay eager
     hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
@@ -246,6 +247,7 @@ static CondL carve_cond(void* base, const vb_dit_config& c, int B, int nb, int T
 #define PRE_STEPS 64      // sampler steps whose adaLN / gate vectors are tabulated up front
 struct WsL {
     int* step; int64_t* t_idx_cur; int64_t* t_table; float* dt_table;
+    float* tn_table;                                                // vb_sample_cfg_keep: t after every step (carved last: no other offset moves)
     float *temb0, *temb, *mod_all, *hl, *h, *cq32, *mc, *ma, *y32, *g1, *g2, *g3, *v;
     bf16_t* modA;                                                   // A operand (planes) of the adaLN tabulation GEMM
     float *temb0_s, *temb_s, *hl_s, *mod_s; int64_t* row_step;     // per-sample tables of the conditioning vectors of every step
@@ -320,6 +322,7 @@ static WsL carve_ws(void* base, const vb_dit_config& c, int B, int nb, int T, in
     o.mod_s = cv.take<float>((size_t)PRE_STEPS * Beff * o.MODW);
     o.row_step = cv.take<int64_t>((size_t)PRE_STEPS * Beff);
     o.modA = cv.take<bf16_t>((size_t)2 * PRE_STEPS * Beff * c.hidden);
+    o.tn_table = cv.take<float>(1024);
     o.total = cv.off;
     return o;
 }
@@ -427,7 +430,7 @@ static int dit_precompute(vb_ctx* ctx, const float* t5, const int64_t* midi, con
 // DiT: one evaluation (both CFG branches batched: rows [0,B) cond, [B,2B) uncond)
 // ------------------------------------------------------------------------------------------
 // sampler only: FinalLayer + CFG + Euler update + step advance as one launch (launch_final_layer_euler) - x is updated in place, v is not written
-struct EulerFuse { float* x; float cfg_scale; const float* dt_table; int k; int* step; int64_t* t_idx_cur; const int64_t* t_table; int n_steps; };
+struct EulerFuse { float* x; float cfg_scale; const float* dt_table; int k; int* step; int64_t* t_idx_cur; const int64_t* t_table; int n_steps; const EulerKeep* keep; };
 static bool euler_fusable(const vb_ctx* ctx, int n_branch) {
     return n_branch == 2 && ctx->w.final_w && final_layer_fused_ok(ctx->cfg.hidden, ctx->cfg.in_channels) && !vb_tune().final_gemm && !vb_tune().euler_launch;
 }
@@ -632,7 +635,7 @@ static int dit_forward(vb_ctx* ctx, const float* x, const int64_t* t_idx, const 
     const float* modf = mod_all + (size_t)c.depth * 6 * D;
     if (ef) {
         VB_TRY(launch_final_layer_euler(s.h, modf, modf + D, MODW, w.final_w, w.final_b, N, D, T, c.in_channels, 1e-6f, ef->x, ef->cfg_scale, ef->dt_table,
-                                        ef->k, ef->step, ef->t_idx_cur, ef->t_table, ef->n_steps, Beff, st));
+                                        ef->k, ef->step, ef->t_idx_cur, ef->t_table, ef->n_steps, Beff, st, ef->keep));
     } else if (w.final_w && final_layer_fused_ok(D, c.in_channels) && !vb_tune().final_gemm) {
         // one wave per token row: LayerNorm + modulate in registers, the 768 x 20 projection against LDS-resident weights (exact fp32)
         VB_TRY(launch_final_layer_fused(s.h, modf, modf + D, MODW, w.final_w, w.final_b, N, D, T, c.in_channels, 1e-6f, v_out, st));
@@ -897,8 +900,9 @@ int vb_euler_cfg_step(float* x, const float* v, int B, int64_t per_item, float c
 }
 // the launches of one sampler call after its tables are in place: tabulation of the per-step conditioning vectors, then n_steps x
 // [step bookkeeping, one network evaluation of both CFG branches, Euler + guidance update]   (cfm1_audio_sampler.py:107-116)
+// keep != nullptr (vb_sample_cfg_keep): every update also puts the known tokens back on the probability path at the time after the step
 static int sample_steps(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps, float cfg_scale,
-                        const vb_noise* noise, float* traj, void* ws, hipStream_t st) {
+                        const vb_keep* keep, const vb_noise* noise, float* traj, void* ws, hipStream_t st) {
     const vb_dit_config& c = ctx->cfg;
     WsL s = carve_ws(ws, c, B, n_branch, T, L);
     const int Beff = B * n_branch;
@@ -941,14 +945,17 @@ static int sample_steps(vb_ctx* ctx, float* x, const void* cond, int B, int n_br
     //  inside the captured graph; a per-block switch would need its own clear.  The device step counter s.step ends a call at n_steps with the
     //  fused Euler launch and at n_steps - 1 with the separate launches; nothing reads it after the call, launch_step_ctl resets it at k == 0.)
     const bool fuse = euler_fusable(ctx, n_branch);
+    EulerKeep kp{};
+    if (keep) kp = EulerKeep{keep->ref, keep->x0, keep->mask, s.tn_table, keep->sigma_min};
     for (int k = 0; k < n_steps; ++k) {
         RoctxRange rs("euler_step");
         if (!fuse || k == 0) VB_TRY(launch_step_ctl(s.step, s.t_idx_cur, s.t_table, n_steps, Beff, k == 0, st));
-        EulerFuse ef{x, cfg_scale, s.dt_table, k, s.step, s.t_idx_cur, s.t_table, n_steps};
+        EulerFuse ef{x, cfg_scale, s.dt_table, k, s.step, s.t_idx_cur, s.t_table, n_steps, keep ? &kp : nullptr};
         VB_TRY(dit_forward(ctx, x, s.t_idx_cur, cond, noise, k, s.step, B, n_branch, T, L, s.v, nullptr, ws, false,
                            tab ? s.mod_s + (size_t)k * Beff * MODW : nullptr, tab ? s.hl_s + (size_t)k * c.depth * 2 : nullptr, st, k * c.depth,
                            fuse ? &ef : nullptr));
-        if (!fuse) VB_TRY(launch_euler_cfg(x, s.v, B, per, cfg_scale, s.dt_table, s.step, 0.f, n_branch == 2, st));
+        if (!fuse && keep) VB_TRY(launch_euler_cfg_keep(x, s.v, B, per, T, cfg_scale, s.dt_table, s.step, n_branch == 2, kp, st));
+        else if (!fuse) VB_TRY(launch_euler_cfg(x, s.v, B, per, cfg_scale, s.dt_table, s.step, 0.f, n_branch == 2, st));
         if (traj) VB_HIP(hipMemcpyAsync(traj + (size_t)(k + 1) * B * per, x, (size_t)B * per * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     return VB_OK;
@@ -957,8 +964,14 @@ static int sample_steps(vb_ctx* ctx, float* x, const void* cond, int B, int n_br
 int vb_sample_cfg(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
                   const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_noise* noise, float* traj, void* ws,
                   void* stream) {
+    return vb_sample_cfg_keep(ctx, x, cond, B, n_branch, T, L, n_steps, t_idx_table, dt_table, cfg_scale, nullptr, noise, traj, ws, stream);
+}
+int vb_sample_cfg_keep(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
+                       const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_keep* keep, const vb_noise* noise,
+                       float* traj, void* ws, void* stream) {
     if (!ctx || !ctx->dit_loaded) VB_FAIL(VB_E_STATE, "sample_cfg: DiT not loaded");
     if (n_steps < 1 || n_steps > 1024) VB_FAIL(VB_E_INVALID, "sample_cfg: n_steps=%d", n_steps);
+    if (keep && (!keep->ref || !keep->x0 || !keep->mask || !keep->t_next)) VB_FAIL(VB_E_INVALID, "sample_cfg_keep: ref, x0, mask and t_next must all be given");
     VB_HIP(hipSetDevice(ctx->device));
     RoctxRange rr("vb_sample_cfg");
     hipStream_t st = (hipStream_t)stream;
@@ -968,6 +981,12 @@ int vb_sample_cfg(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, 
     // (tables may live on the host or on the device; a host caller must keep them alive until the stream has consumed them)
     VB_HIP(hipMemcpyAsync(s.t_table, t_idx_table, (size_t)n_steps * sizeof(int64_t), hipMemcpyDefault, st));
     VB_HIP(hipMemcpyAsync(s.dt_table, dt_table, (size_t)n_steps * sizeof(float), hipMemcpyDefault, st));
+    if (keep) {
+        // the times travel like the step sizes do (a device table read behind the step counter); the entry projection runs here, outside
+        // the captured loop, so that traj[0] is the state the first evaluation sees
+        VB_HIP(hipMemcpyAsync(s.tn_table, keep->t_next, (size_t)n_steps * sizeof(float), hipMemcpyDefault, st));
+        VB_TRY(launch_keep_project(x, B, per, T, s.dt_table, EulerKeep{keep->ref, keep->x0, keep->mask, s.tn_table, keep->sigma_min}, st));
+    }
     if (traj) VB_HIP(hipMemcpyAsync(traj, x, (size_t)B * per * sizeof(float), hipMemcpyDeviceToDevice, st));
     // the noise key travels through device memory (the router reads it behind the step counter): nothing a replayed graph bakes in
     VB_TRY(launch_sampler_params(s.step, noise ? noise->seed : 0, noise ? noise->clip_base : 0, noise ? noise->nfe : 0, st));
@@ -983,7 +1002,9 @@ int vb_sample_cfg(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, 
         SampleGraph* e = nullptr;
         for (SampleGraph& gph : ctx->graphs)
             if (gph.x == x && gph.cond == cond && gph.ws == ws && gph.B == B && gph.nb == n_branch && gph.T == T && gph.L == L &&
-                gph.n_steps == n_steps && gph.cfg_scale == cfg_scale && gph.tune_gen == vb_tune_generation()) { e = &gph; break; }
+                gph.n_steps == n_steps && gph.cfg_scale == cfg_scale && gph.tune_gen == vb_tune_generation() &&
+                gph.keep_ref == (keep ? keep->ref : nullptr) && gph.keep_x0 == (keep ? keep->x0 : nullptr) &&
+                gph.keep_mask == (keep ? keep->mask : nullptr) && gph.sigma_min == (keep ? keep->sigma_min : 0.f)) { e = &gph; break; }
         if (!e) {
             if (ctx->graphs.size() >= 8) {          // evict the least recently used entry
                 size_t lru = 0;
@@ -994,6 +1015,7 @@ int vb_sample_cfg(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, 
             }
             SampleGraph n; n.x = x; n.cond = cond; n.ws = ws; n.B = B; n.nb = n_branch; n.T = T; n.L = L; n.n_steps = n_steps; n.cfg_scale = cfg_scale;
             n.tune_gen = vb_tune_generation();      // a captured graph bakes the knob-dependent kernel selection in
+            if (keep) { n.keep_ref = keep->ref; n.keep_x0 = keep->x0; n.keep_mask = keep->mask; n.sigma_min = keep->sigma_min; }
             ctx->graphs.push_back(n);
             e = &ctx->graphs.back();
         }
@@ -1001,7 +1023,7 @@ int vb_sample_cfg(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, 
         e->seen += 1;
         if (!e->exec && !e->failed && e->seen >= 2) {
             if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                const int rc = sample_steps(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, noise, nullptr, ws, st);
+                const int rc = sample_steps(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, keep, noise, nullptr, ws, st);
                 hipGraph_t gr = nullptr;
                 const hipError_t ee = hipStreamEndCapture(st, &gr);
                 if (rc == VB_OK && ee == hipSuccess && gr && hipGraphInstantiate(&e->exec, gr, nullptr, nullptr, 0) == hipSuccess) {
@@ -1021,7 +1043,7 @@ int vb_sample_cfg(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, 
             return VB_OK;
         }
     }
-    return sample_steps(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, noise, traj, ws, st);
+    return sample_steps(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, keep, noise, traj, ws, st);
 }
 int vb_sample_graphs(vb_ctx* ctx) {
     int n = 0;

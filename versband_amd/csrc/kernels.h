@@ -191,11 +191,19 @@ int launch_final_layer(const float* h, const float* shift, const float* scale, i
 bool final_layer_fused_ok(int D, int C);
 int launch_final_layer_fused(const float* h, const float* shift, const float* scale, int mod_ld, const float* W, const float* bias,
                              int rows, int D, int T, int C, float eps, float* out, hipStream_t st);
+// known region of a sampler call (vb_keep with its time table on the device): ref / x0 [B][C][T], mask [B][T], tn_table[k] = t after step k
+struct EulerKeep { const float* ref; const float* x0; const float* mask; const float* tn_table; float sigma_min; };
+// (keep != nullptr: the known tokens are put back on the probability path in the same launch - common.h:keep_path / keep_blend)
 int launch_final_layer_euler(const float* h, const float* shift, const float* scale, int mod_ld, const float* W, const float* bias,
                              int rows, int D, int T, int C, float eps, float* x, float cfg_scale, const float* dt_table, int k, int* step,
-                             int64_t* t_idx_cur, const int64_t* t_table, int n_steps, int Beff, hipStream_t st);
+                             int64_t* t_idx_cur, const int64_t* t_table, int n_steps, int Beff, hipStream_t st, const EulerKeep* keep = nullptr);
 int launch_euler_cfg(float* x, const float* v, int B, int64_t per, float cfg_scale, const float* dt_table, const int* step,
                      float dt_val, int has_uncond, hipStream_t st);
+// the Euler + guidance update of launch_euler_cfg followed by the known-region blend at t = tn_table[*step] (x [B][C][T], per = C * T)
+int launch_euler_cfg_keep(float* x, const float* v, int B, int64_t per, int T, float cfg_scale, const float* dt_table, const int* step,
+                          int has_uncond, const EulerKeep& keep, hipStream_t st);
+// projection on entry: x <- blend(mask, r(t_0), x) with t_0 = tn_table[0] - dt_table[0]
+int launch_keep_project(float* x, int B, int64_t per, int T, const float* dt_table, const EulerKeep& keep, hipStream_t st);
 int launch_router(Planes cq, const float* Wg, const float* bg, const float* la, int la_mod_rows, const float* hl, int hl_ld,
                   const float* g1, const float* g2, const float* g3, int N, int T, int D, int E, int* ic, int* ia, float* mc,
                   float* ma, float* lc_out, int B, uint64_t seed, int64_t clip_base, int nfe_base, const int* step, int block,

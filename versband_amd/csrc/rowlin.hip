@@ -147,11 +147,16 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
 // multiply-adds); the velocity tensor is never written.  Block 0 also advances the sampler's device-side step counter and the timestep
 // indices for the NEXT step (step_advance_kernel's work): nothing in this launch reads them.  Saves two launches per Euler step.
 struct FinalEuler { float* x; float cfg_scale; const float* dt_table; int k; int* step; int64_t* t_idx_cur; const int64_t* t_table; int n_steps, Beff; };
-template <int NQ, bool EUL = false>      // D = 256 * NQ
+// KEEP (vb_sample_cfg_keep): the updated value is blended with the known region's point on the probability path at t = tn_table[k]
+// (common.h:keep_path / keep_blend; three more loads per output element) - a third instance with its own argument block, so the other
+// two keep their kernel arguments and compile to the code they had.
+struct FinalEulerKeep : FinalEuler { EulerKeep kp; };
+template <int NQ, bool EUL = false, bool KEEP = false>      // D = 256 * NQ
 __global__ void __launch_bounds__(256) final_layer_kernel(const float* __restrict__ h, const float* __restrict__ shift,
                                                          const float* __restrict__ scale, int mod_ld, const float* __restrict__ W,
                                                          const float* __restrict__ bias, int rows, int T, int C, float eps, float* out,
-                                                         const FinalEuler fe) {
+                                                         const std::conditional_t<KEEP, FinalEulerKeep, FinalEuler> fe) {
+    static_assert(EUL || !KEEP, "the known-region blend belongs to the Euler update");
     constexpr int D = 256 * NQ;
     extern __shared__ __attribute__((aligned(16))) float wl[];      // [C][D]
     for (int id = threadIdx.x * 4; id < C * D; id += 1024) *reinterpret_cast<float4*>(wl + id) = *reinterpret_cast<const float4*>(W + id);
@@ -221,13 +226,21 @@ __global__ void __launch_bounds__(256) final_layer_kernel(const float* __restric
             const float bv = bias ? bias[lane] : 0.f;
             if constexpr (EUL) {
                 const float dt = fe.dt_table[fe.k];
+                float tn = 0.f;
+                if constexpr (KEEP) tn = fe.kp.tn_table[fe.k];
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
                     if (row0 + j < half) {
                         const float vc = res[j] + bv, vu = res[2 + j] + bv;
                         const float e = fmaf(fe.cfg_scale, vc - vu, vu);
                         float* xp = fe.x + ((int64_t)bb[j] * C + lane) * T + tt[j];
-                        *xp = fmaf(dt, e, *xp);
+                        if constexpr (KEEP) {
+                            const int64_t xi = xp - fe.x;
+                            const float m = fe.kp.mask[(int64_t)bb[j] * T + tt[j]];
+                            *xp = keep_blend(m, keep_path(tn, fe.kp.sigma_min, fe.kp.ref[xi], fe.kp.x0[xi]), fmaf(dt, e, *xp));
+                        } else {
+                            *xp = fmaf(dt, e, *xp);
+                        }
                     }
             } else {
 #pragma unroll
@@ -265,14 +278,22 @@ int launch_final_layer_fused(const float* h, const float* shift, const float* sc
 // FinalLayer + CFG + Euler update + step advance in one launch (see FinalEuler): rows = 2 x (B T) token rows, conditional half first
 int launch_final_layer_euler(const float* h, const float* shift, const float* scale, int mod_ld, const float* W, const float* bias,
                              int rows, int D, int T, int C, float eps, float* x, float cfg_scale, const float* dt_table, int k, int* step,
-                             int64_t* t_idx_cur, const int64_t* t_table, int n_steps, int Beff, hipStream_t st) {
+                             int64_t* t_idx_cur, const int64_t* t_table, int n_steps, int Beff, hipStream_t st, const EulerKeep* keep) {
     if (!final_layer_fused_ok(D, C) || (rows & 1) || !x || !dt_table) VB_FAIL(VB_E_INVALID, "final_layer_euler: D=%d C=%d rows=%d unsupported", D, C, rows);
     const size_t sh = (size_t)C * D * sizeof(float);
     const int grid = min(cdiv(rows / 2, 8), 512);
     FinalEuler fe{x, cfg_scale, dt_table, k, step, t_idx_cur, t_table, n_steps, Beff};
-    static OnceFlags attr[4];
+    static OnceFlags attr[4], attr_keep[4];
     auto go = [&](auto nq) {
         constexpr int NQ = decltype(nq)::value;
+        if (keep) {
+            FinalEulerKeep fek;
+            static_cast<FinalEuler&>(fek) = fe; fek.kp = *keep;
+            vb_set_max_lds_once(attr_keep[NQ - 1], reinterpret_cast<const void*>(final_layer_kernel<NQ, true, true>), 96 * 1024);
+            hipLaunchKernelGGL((final_layer_kernel<NQ, true, true>), dim3(grid), dim3(256), sh, st, h, shift, scale, mod_ld, W, bias, rows, T > 0 ? T : 1, C,
+                               eps, (float*)nullptr, fek);
+            return;
+        }
         vb_set_max_lds_once(attr[NQ - 1], reinterpret_cast<const void*>(final_layer_kernel<NQ, true>), 96 * 1024);
         hipLaunchKernelGGL((final_layer_kernel<NQ, true>), dim3(grid), dim3(256), sh, st, h, shift, scale, mod_ld, W, bias, rows, T > 0 ? T : 1, C, eps,
                            (float*)nullptr, fe);

@@ -189,9 +189,48 @@ class DiTEngine:
                                             L.ptr(v), L.ptr(routes), L.ptr(ws), L.stream_ptr()), "vb_dit_forward")
         return (v, routes) if return_routes else v
 
+    def _keep_struct(self, keep, B: int, T: int, n: int):
+        """validate a known-region block (ref, x0, mask, t_next, sigma_min) - a tuple or a dict of those names - and lay it out as vb_keep.
+        Conforming device tensors are passed as they are (their addresses key the captured graph); returns (struct, references to hold)."""
+        dev = self.ctx.device
+        names = ("ref", "x0", "mask", "t_next", "sigma_min")
+        if isinstance(keep, dict):
+            if set(keep) != set(names):
+                raise ValueError(f"keep: expected the keys {names}, got {tuple(keep)}")
+            keep = tuple(keep[k] for k in names)
+        if len(keep) != 5:
+            raise ValueError("keep: expected (ref, x0, mask, t_next, sigma_min)")
+        ref, x0k, mask, t_next, sigma_min = keep
+        shape = (B, self.cfg.in_channels, T)
+        for name, t, want in (("ref", ref, shape), ("x0", x0k, shape), ("mask", mask, (B, T))):
+            if not torch.is_tensor(t):
+                raise TypeError(f"keep: {name} must be a tensor")
+            if tuple(t.shape) != want:
+                raise ValueError(f"keep: {name} has shape {tuple(t.shape)}, expected {want}")
+            if t.dtype != torch.float32:
+                raise TypeError(f"keep: {name} must be float32, got {t.dtype}")
+            if t.device.type != "cpu" and t.device != dev:
+                raise ValueError(f"keep: {name} lives on {t.device}, the engine on {dev}")
+        if mask.numel() and (float(mask.min()) < 0.0 or float(mask.max()) > 1.0 or bool(torch.isnan(mask).any())):
+            raise ValueError("keep: mask values must lie in [0, 1]")
+        t_next = [float(v) for v in (t_next.tolist() if torch.is_tensor(t_next) else t_next)]
+        if len(t_next) != n:
+            raise ValueError(f"keep: t_next has {len(t_next)} entries for {n} steps")
+        ref, x0k, mask = [t.to(dev).contiguous() for t in (ref, x0k, mask)]
+        tkey = ("t_next", tuple(t_next))
+        if tkey not in self._tables:
+            if len(self._tables) > 16:
+                self._tables.clear()
+            self._tables[tkey] = (torch.tensor(t_next, dtype=torch.float32, device=dev),)
+        tn = self._tables[tkey][0]
+        ks = L.Keep(ref.data_ptr(), x0k.data_ptr(), mask.data_ptr(), tn.data_ptr(), float(sigma_min))
+        return ks, (ref, x0k, mask, tn)
+
     def sample_cfg(self, x0: Tensor, cond: dict, t_idx_table: Sequence[int], dt_table: Sequence[float], scale: float,
-                   noise=None, seed: int = 0, clip_base: int = 0, return_traj: bool = False):
-        """n Euler steps with classifier-free guidance; x0 [B,C,T] is not modified."""
+                   noise=None, seed: int = 0, clip_base: int = 0, return_traj: bool = False, keep=None):
+        """n Euler steps with classifier-free guidance; x0 [B,C,T] is not modified.
+        keep = (ref [B,C,T], x0 [B,C,T], mask [B,T] in [0,1], t_next [n], sigma_min) or a dict of those names holds the masked tokens on
+        the probability path t ref + (1 - (1 - sigma_min) t) x0 after every step (vb_sample_cfg_keep; t_next = model.euler_times)."""
         dev = self.ctx.device
         B, nb, T, Lc = cond["B"], cond["nb"], cond["T"], cond["L"]
         self._check_cond(cond)
@@ -209,10 +248,16 @@ class DiTEngine:
             self._tables[tkey] = (torch.tensor(tkey[0], dtype=torch.int64, device=dev), torch.tensor(tkey[1], dtype=torch.float32, device=dev))
         tt, dd = self._tables[tkey]
         traj = torch.empty(n + 1, *x.shape, dtype=torch.float32, device=dev) if return_traj else None
-        ns, keep = self._noise_struct(noise, seed, clip_base, 0)
+        ns, held = self._noise_struct(noise, seed, clip_base, 0)
         ws = self._workspace(B, nb, T, Lc)
-        L.check(self.ctx.lib.vb_sample_cfg(self.ctx.handle, L.ptr(x), L.ptr(cond["buf"]), B, nb, T, Lc, n, L.ptr(tt), L.ptr(dd), float(scale),
-                                           C.byref(ns), L.ptr(traj), L.ptr(ws), L.stream_ptr()), "vb_sample_cfg")
+        if keep is None:
+            L.check(self.ctx.lib.vb_sample_cfg(self.ctx.handle, L.ptr(x), L.ptr(cond["buf"]), B, nb, T, Lc, n, L.ptr(tt), L.ptr(dd), float(scale),
+                                               C.byref(ns), L.ptr(traj), L.ptr(ws), L.stream_ptr()), "vb_sample_cfg")
+        else:
+            ks, held_keep = self._keep_struct(keep, B, T, n)
+            L.check(self.ctx.lib.vb_sample_cfg_keep(self.ctx.handle, L.ptr(x), L.ptr(cond["buf"]), B, nb, T, Lc, n, L.ptr(tt), L.ptr(dd),
+                                                    float(scale), C.byref(ks), C.byref(ns), L.ptr(traj), L.ptr(ws), L.stream_ptr()),
+                    "vb_sample_cfg_keep")
         x = x.clone()
         return (x, traj) if return_traj else x
 

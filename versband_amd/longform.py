@@ -6,6 +6,9 @@ The reference cannot go past max_len = 1500 latent tokens (40 s): its RoPE table
 `overlap` tokens; every window is an independent "clip" for the sampler (own slice of the midi/beats
 tracks, same caption, own slice of the start noise), so all windows of all clips run as ONE batch
 through vb_sample_cfg.  Window latents are cross-faded linearly over the overlaps.  The VAE decoder is
+(sample_long(mode="continue") gives up that batching for coherence: the windows of a clip are sampled in order and each holds its
+overlap with the previous one on the model's probability path - vb_sample_cfg_keep - so the new tokens are generated in agreement with
+the music that is already there, and the windows are stitched without a cross-fade.)  The VAE decoder is
 applied to the whole latent (it is length-agnostic), the HiFi-GAN - fully convolutional - is run in
 chunks with a halo larger than its receptive field and the chunks are stitched (overlap-discard), which
 reproduces whole-clip vocoding exactly.
@@ -70,9 +73,28 @@ def crossfade_windows(parts: Sequence[Tensor], plan: Sequence[Tuple[int, int]], 
     return acc / wsum
 
 
+def plan_continue(plan: Sequence[Tuple[int, int]]) -> List[Tuple[int, int, int]]:
+    """[(start, length, known)] of mode="continue": window w holds its first `known` tokens - its whole overlap with window w - 1, which
+    for the last window of plan_windows may be more than `overlap` - and contributes [start + known, start + length) to the result, so
+    the contributions cover [0, T) exactly once."""
+    out, end = [], 0
+    for s, n in plan:
+        assert s <= end, "windows must not leave a gap"
+        out.append((s, n, end - s))
+        end = s + n
+    return out
+
+
 def sample_long(engine, x0: Tensor, t5_cond: Tensor, t5_uncond: Tensor, midi: Tensor, beats: Tensor, t_idx_table, dt_table,
-                scale: float, window: int = 1500, overlap: int = 128, seed: int = 0, clip_base: int = 0) -> Tensor:
-    """x0 [B,C,T], t5_* [B,L,1024], midi/beats [B,1,2T] -> z [B,C,T] for T beyond the DiT's max_len."""
+                scale: float, window: int = 1500, overlap: int = 128, seed: int = 0, clip_base: int = 0, mode: str = "crossfade",
+                t_next=None, sigma_min: float = 1e-4, return_windows: bool = False):
+    """x0 [B,C,T], t5_* [B,L,1024], midi/beats [B,1,2T] -> z [B,C,T] for T beyond the DiT's max_len.
+    mode "crossfade" (default): all windows as one batch of independent clips, latents cross-faded over the overlaps.
+    mode "continue": windows in order, each with its overlap held on the probability path of the previous window's result (needs
+    t_next = model.euler_times of the same grid as the step tables, and the model's sigma_min); no cross-fade.  return_windows (continue
+    mode only) also returns every window's full result, overlaps included: (z, [z_w [B,C,n]])."""
+    if mode not in ("crossfade", "continue"):
+        raise ValueError(f"sample_long: mode {mode!r} (crossfade | continue)")
     B, C, T = x0.shape
     window = min(window, engine.cfg.max_len)
     plan = plan_windows(T, window, overlap)
@@ -85,6 +107,13 @@ def sample_long(engine, x0: Tensor, t5_cond: Tensor, t5_uncond: Tensor, midi: Te
         pad = 2 * T - midi.shape[1]
         midi = torch.cat([midi, midi[:, -1:].expand(B, pad)], dim=1)
         beats = torch.cat([beats, beats[:, -1:].expand(B, pad)], dim=1)
+    if return_windows and mode != "continue":
+        raise ValueError("sample_long: return_windows belongs to mode=\"continue\"")
+    if mode == "continue":
+        if t_next is None:
+            raise ValueError('sample_long(mode="continue") needs t_next (model.euler_times of the step tables\' grid)')
+        return _sample_continue(engine, x0, t5_cond, t5_uncond, midi, beats, t_idx_table, dt_table, scale, plan, seed, clip_base, t_next,
+                                sigma_min, return_windows)
     # windows become extra batch rows: row = w * B + b
     xw = torch.cat([x0[:, :, s:s + n] for s, _ in plan], dim=0)
     mw = torch.cat([midi[:, 2 * s:2 * (s + n)] for s, _ in plan], dim=0)
@@ -98,6 +127,38 @@ def sample_long(engine, x0: Tensor, t5_cond: Tensor, t5_uncond: Tensor, midi: Te
         return crossfade_windows_hip(engine.ctx.lib, zw, plan, B, T)
     parts = [zw[i * B:(i + 1) * B] for i in range(nw)]
     return crossfade_windows(parts, plan, T)
+
+
+def _sample_continue(engine, x0, t5_cond, t5_uncond, midi, beats, t_idx_table, dt_table, scale, plan, seed, clip_base, t_next, sigma_min,
+                     return_windows=False):
+    """mode="continue" of sample_long: one sampler call of B rows per window.  Window w's noise key is the one it has as rows
+    [w*B, (w+1)*B) of the cross-fade batch, so window 0 equals today's window 0."""
+    B, C, T = x0.shape
+    nw = len(plan)
+    dev = engine.ctx.device
+    out = torch.empty(B, C, T, dtype=torch.float32, device=dev)
+    t5 = torch.cat([t5_cond, t5_uncond], dim=0)
+    # one set of known-region buffers per window length: stable addresses let the later windows replay the captured step loop
+    bufs, parts = {}, []
+    for w, (s, n, known) in enumerate(plan_continue(plan)):
+        xw = x0[:, :, s:s + n].to(dev, torch.float32).contiguous()
+        cond = engine.precompute_cond(t5, midi[:, 2 * s:2 * (s + n)].contiguous(), beats[:, 2 * s:2 * (s + n)].contiguous(), n, persistent=True)
+        keep = None
+        if known > 0:
+            if n not in bufs:
+                bufs[n] = tuple(torch.zeros(shape, dtype=torch.float32, device=dev) for shape in ((B, C, n), (B, C, n), (B, n)))
+            ref, xn, mask = bufs[n]
+            ref.zero_()
+            ref[:, :, :known] = out[:, :, s:s + known]
+            xn.copy_(xw)
+            mask.zero_()
+            mask[:, :known] = 1.0
+            keep = (ref, xn, mask, t_next, sigma_min)
+        zw = engine.sample_cfg(xw, cond, t_idx_table, dt_table, scale, seed=seed, clip_base=clip_base * nw + w * B, keep=keep)
+        out[:, :, s + known:s + n] = zw[:, :, known:]
+        if return_windows:
+            parts.append(zw)
+    return (out, parts) if return_windows else out
 
 
 def vocode_chunked(vocoder_net, mel: Tensor, chunk: int = 2048, halo: int = 32) -> Tensor:

@@ -412,6 +412,54 @@ def euler_tables(timesteps: int, t_start: Optional[int] = None):
     return idx, dts
 
 
+def euler_times(timesteps: int, t_start: Optional[int] = None) -> List[float]:
+    """the time after each step of euler_tables(timesteps, t_start): float32, accumulated t += dt like the solver loop does (the
+    table a known-region call hands to vb_sample_cfg_keep as t_next)"""
+    t_span = torch.linspace(0, 1, timesteps)
+    if t_start is not None:
+        t_span = t_span[t_start:]
+    out = []
+    t = t_span[0]
+    for k in range(len(t_span) - 1):
+        dt = t_span[k + 1] - t
+        t = t + dt
+        out.append(float(t))
+    return out
+
+
+def keep_block(x_known, keep_mask, keep_noise, x_latent, t_start, shape, timesteps, sigma_min):
+    """the known-region arguments of CFMSampler.sample_cfg -> the (ref, x0, mask, t_next, sigma_min) block of DiTEngine.sample_cfg, or None
+    when no region is given.  x_known is in the sampler's latent scale; keep_mask [B,T] or [T]; keep_noise is the start noise of the
+    path the known tokens are held on: x_latent when the call starts from the noise (t_start is None), required otherwise."""
+    if x_known is None and keep_mask is None:
+        if keep_noise is not None:
+            raise ValueError("keep_noise without x_known / keep_mask")
+        return None
+    if x_known is None or keep_mask is None:
+        raise ValueError("x_known and keep_mask go together")
+    if keep_noise is None:
+        if t_start is not None:
+            raise ValueError("keep_noise is required with t_start: the state the call starts from is not the noise the known region's "
+                             "path is built on (nothing is re-drawn silently)")
+        if x_latent is None:
+            raise ValueError("keep_noise (or x_latent, the start noise) is required with x_known")
+        keep_noise = x_latent
+    B, _, T = shape
+    if tuple(x_known.shape) != tuple(shape):
+        raise ValueError(f"x_known has shape {tuple(x_known.shape)}, expected {tuple(shape)}")
+    if tuple(keep_noise.shape) != tuple(shape):
+        raise ValueError(f"keep_noise has shape {tuple(keep_noise.shape)}, expected {tuple(shape)}")
+    mask = keep_mask.to(torch.float32)
+    if mask.dim() == 1:
+        mask = mask.unsqueeze(0).expand(B, -1)
+    if tuple(mask.shape) != (B, T):
+        raise ValueError(f"keep_mask has shape {tuple(keep_mask.shape)}, expected ({B}, {T}) or ({T},)")
+    if mask.numel() and (float(mask.min()) < 0.0 or float(mask.max()) > 1.0 or bool(torch.isnan(mask).any())):
+        raise ValueError("keep_mask values must lie in [0, 1]")
+    return (x_known.to(torch.float32).contiguous(), keep_noise.to(torch.float32).contiguous(), mask.contiguous(),
+            euler_times(timesteps, t_start), float(sigma_min))
+
+
 class CFMSampler(object):
     def __init__(self, model, num_timesteps, schedule="linear", **kwargs):
         self.model = model
@@ -439,27 +487,35 @@ class CFMSampler(object):
 
     @torch.no_grad()
     def sample_cfg(self, cond, unconditional_guidance_scale, unconditional_conditioning, batch_size=16, timesteps=None, shape=None,
-                   x_latent=None, t_start=None, gumbel_noise=None, seed=None, clip_base=0, **kwargs):
+                   x_latent=None, t_start=None, gumbel_noise=None, seed=None, clip_base=0, x_known=None, keep_mask=None, keep_noise=None,
+                   **kwargs):
         """:87-116.  Extra kwargs (S=, x_T=, verbose=) are tolerated and ignored like the reference does
         (SURVEY Q1/Q2).  gumbel_noise/seed/clip_base are additions: injected router noise for parity, or the
-        (seed, global clip index) that keys the on-device counter-based draws."""
+        (seed, global clip index) that keys the on-device counter-based draws.
+        x_known / keep_mask / keep_noise (addition; inpainting, continuation): tokens where keep_mask [B,T] or [T] is 1 are held on the
+        probability path from keep_noise to x_known (the sampler's latent scale, what get_first_stage_encoding returns) and end at
+        x_known + sigma_min * keep_noise; the others are generated in agreement with them.  keep_noise defaults to the start noise
+        when t_start is None and is required with t_start."""
         shape = self._shape(shape, batch_size)
-        idx, dts = euler_tables(25 if timesteps is None else timesteps, t_start)
+        timesteps = 25 if timesteps is None else timesteps
+        idx, dts = euler_tables(timesteps, t_start)
         dev = self.model.device
         x0 = torch.randn(shape, device=dev) if x_latent is None else x_latent
+        keep = keep_block(x_known, keep_mask, keep_noise, x0, t_start, shape, timesteps, self.model.sigma_min)
         conds = [cond] if unconditional_conditioning is None else [cond, unconditional_conditioning]
         pc = self.model._precompute(conds, shape[-1])
         if seed is None:
             seed = int(torch.initial_seed()) & 0xFFFFFFFF
         x, traj = self.model.dit_engine().sample_cfg(x0, pc, idx, dts, float(unconditional_guidance_scale), noise=gumbel_noise,
-                                                     seed=seed, clip_base=clip_base, return_traj=True)
+                                                     seed=seed, clip_base=clip_base, return_traj=True, keep=keep)
         return traj[-1], traj
 
     @torch.no_grad()
-    def sample(self, cond, batch_size=16, timesteps=None, shape=None, x_latent=None, t_start=None, **kwargs):
+    def sample(self, cond, batch_size=16, timesteps=None, shape=None, x_latent=None, t_start=None, x_known=None, keep_mask=None,
+               keep_noise=None, **kwargs):
         """:49-80 (no guidance)."""
         return self.sample_cfg(cond, 1.0, None, batch_size=batch_size, timesteps=timesteps, shape=shape, x_latent=x_latent,
-                               t_start=t_start, **kwargs)
+                               t_start=t_start, x_known=x_known, keep_mask=keep_mask, keep_noise=keep_noise, **kwargs)
 
 
 # ---------------------------------------------------------------------------
