@@ -19,9 +19,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libversband_hip.so")
-SOURCES = ["gemm_bf16.hip", "attention.hip", "conv1d_f32.hip", "conv1d_f32g.hip", "conv1d_f32w.hip", "respair_x3.hip", "respair_f32.hip", "respair_f32w.hip", "t5.hip", "melnet.hip", "elementwise.hip", "rowlin.hip",
+SOURCES = ["gemm_bf16.hip", "band_ffn.hip", "attention.hip", "conv1d_f32.hip", "conv1d_f32g.hip", "conv1d_f32w.hip", "respair_x3.hip", "respair_f32.hip", "respair_f32w.hip", "t5.hip", "melnet.hip", "elementwise.hip", "rowlin.hip",
            "engine.hip"]
-EXPERIMENT_SOURCES = ["score_router.hip"]
+EXPERIMENT_SOURCES = ["score_router.hip", "gemm_bf16_pk.hip"]
 EXPERIMENTS = bool(os.environ.get("VB_BUILD_EXPERIMENTS"))
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"] + (["-DVB_EXPERIMENTS"] if EXPERIMENTS else [])
 # the kernels whose loops read or rescale their MFMA accumulators keep them in VGPRs (hipcc otherwise parks them in AGPRs and copies them
