@@ -68,8 +68,8 @@ def test_library_carries_the_digest_of_its_sources(monkeypatch):
 
 
 def _product_knobs():
-    """VB_* environment switches the PRODUCT library reads (engine.hip:tune_load, outside the VB_EXPERIMENTS block)"""
-    src = open(os.path.join(ROOT, "versband_amd", "csrc", "engine.hip")).read()
+    """VB_* environment switches the PRODUCT library reads (runtime.hip:tune_load, outside the VB_EXPERIMENTS block)"""
+    src = open(os.path.join(ROOT, "versband_amd", "csrc", "runtime.hip")).read()
     body = src[src.index("static void tune_load()"):]
     body = body[:body.index("g_tune = t;")]
     product = re.sub(r"#ifdef VB_EXPERIMENTS.*?#endif", "", body, flags=re.S)

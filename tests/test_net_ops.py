@@ -31,7 +31,7 @@ ENV_SWITCHES = ("VB_FP32_PAIRS", "VB_MF_PAIRS_OFF", "VB_LRELU_IN_WINDOW", "VB_FP
 
 
 def load_rule_violation(o, tmul):
-    """vb_net_load's per-op checks (engine.hip); None when the op passes them"""
+    """vb_net_load's per-op checks (convnet.hip); None when the op passes them"""
     reads = READS.get((o.kind, o.wfmt))
     if reads is None:
         return "unknown (kind, wfmt) pair"

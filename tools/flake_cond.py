@@ -30,7 +30,7 @@ try:
     eng = DiTEngine(Context(device), dcfg, synth.make_state_dict(synth.dit_shapes(dcfg), 1234), precision="bf16")
     inp = clip_batch(B, T, Lc)
     t5 = torch.cat([inp["t5_cond"], inp["t5_uncond"]])
-    # carve_cond (engine.hip): region name -> [start, end)
+    # carve_cond (dit.hip): region name -> [start, end)
     D, heads, depth, E, nb = dcfg.hidden_size, dcfg.num_heads, dcfg.depth, dcfg.num_experts, 2
     Beff, hd, Lpad, NS, np_ = B * nb, D // heads, (Lc + 63) // 64 * 64, Lc * heads, 1      # bf16: one plane
     regions, off = [], 0

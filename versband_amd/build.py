@@ -20,7 +20,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libversband_hip.so")
 SOURCES = ["gemm_bf16.hip", "band_ffn.hip", "attention.hip", "conv1d_f32.hip", "conv1d_f32g.hip", "conv1d_f32w.hip", "respair_x3.hip", "respair_f32.hip", "respair_f32w.hip", "t5.hip", "melnet.hip", "elementwise.hip", "rowlin.hip",
-           "engine.hip"]
+           "runtime.hip", "dit.hip", "sampler.hip", "convnet.hip", "abi_units.hip"]
 EXPERIMENT_SOURCES = ["score_router.hip", "gemm_bf16_pk.hip"]
 EXPERIMENTS = bool(os.environ.get("VB_BUILD_EXPERIMENTS"))
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"] + (["-DVB_EXPERIMENTS"] if EXPERIMENTS else [])

@@ -1,0 +1,98 @@
+// C-ABI wrappers of single kernels (tests, tools and the parity harness call them; the engines do not).
+#include "engine.h"
+
+extern "C" {
+
+int vb_rmsnorm_modulate(const float* h, const float* w, const float* shift, const float* scale, int mod_ld, int rows, int D, int T,
+                        float eps, void* out_planes, int np, void* stream) {
+    return launch_rmsnorm_mod(h, w, shift, scale, mod_ld, rows, D, T, eps, mkp((bf16_t*)out_planes, (int64_t)rows * D, np),
+                              (hipStream_t)stream);
+}
+int vb_router_top1(const float* logits, const float* gumbel, int N, int E, int32_t* idx, void* stream) {
+    return launch_router_top1(logits, gumbel, N, E, idx, (hipStream_t)stream);
+}
+int vb_route_bucket_scratch_ints(int N, int E) { return bucket_scratch_ints(N, E); }
+int vb_route_bucket_pairs(const int32_t* ic, const int32_t* ia, int N, int E, int32_t* group_off, int32_t* perm, int32_t* pair_off,
+                          int32_t* pair_pa, void* stream) {
+    if (!pair_off || !pair_pa) VB_FAIL(VB_E_INVALID, "route_bucket_pairs: null pair outputs");
+    return launch_bucket(ic, ia, N, E, group_off, perm, (hipStream_t)stream, pair_off, pair_pa);
+}
+int vb_route_bucket(const int32_t* ic, const int32_t* ia, int N, int E, int32_t* group_off, int32_t* perm, void* stream) {
+    return launch_bucket(ic, ia, N, E, group_off, perm, (hipStream_t)stream);
+}
+int vb_gemm_bf16(const void* A, const void* Bw, const float* bias, int M, int N, int K, int np, float* C, void* stream) {
+    GemmArgs g = gemm_operands(A, (int64_t)M * K, K, Bw, (int64_t)N * K, K, M, N, K, np == 2 ? 3 : 1);
+    g.epi = EPI_F32; g.bias = bias; g.out32 = C; g.ldc32 = N;
+    return launch_gemm(g, (hipStream_t)stream);
+}
+int vb_grouped_swiglu(const void* u, const int32_t* perm, const int32_t* group_off, int G, int n_slots, const void* w13,
+                      const void* w2, const float* row_scale, int D, int H, int np, void* hidden, float* out, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const int nseg = np == 2 ? 3 : 1;
+    GemmArgs g = gemm_operands(u, (int64_t)n_slots * D, D, w13, (int64_t)G * 2 * H * D, D, n_slots, 2 * H, D, nseg);
+    g.a_rows = perm; g.b_group_stride = (int64_t)2 * H * D; g.ngroups = G; g.group_off = group_off;
+    g.epi = EPI_SWIGLU; g.out = mkp((bf16_t*)hidden, (int64_t)n_slots * H, np); g.ldc = H;
+    VB_TRY(launch_gemm(g, st));
+    g = gemm_operands(hidden, (int64_t)n_slots * H, H, w2, (int64_t)G * D * H, H, n_slots, D, H, nseg);
+    g.b_group_stride = (int64_t)D * H; g.ngroups = G; g.group_off = group_off;
+    g.epi = EPI_SCATTER_F32; g.out32 = out; g.ldc32 = D; g.rows_out = perm; g.row_scale = row_scale;
+    return launch_gemm(g, st);
+}
+int vb_attention(const void* q, const void* k, const void* vt, const void* ky, const void* vyt, const float* cross_w, int B, int T,
+                 int Tpad, int L, int Lpad, int H, int hd, int np, void* out, void* stream) {
+    AttnArgs a;
+    const int64_t ND = (int64_t)B * T * H * hd;
+    a.q = wpl(q, ND, np); a.k = wpl(k, ND, np); a.vt = wpl(vt, (int64_t)B * H * hd * Tpad, np);
+    a.ky = wpl(ky, (int64_t)B * L * H * hd, np); a.vyt = wpl(vyt, (int64_t)B * H * hd * Lpad, np);
+    a.cross_w = cross_w; a.out = wpl(out, ND, np); a.B = B; a.T = T; a.Tpad = Tpad; a.L = L; a.Lpad = Lpad; a.H = H; a.hd = hd;
+    a.has_self = k != nullptr; a.has_cross = ky != nullptr; a.kv_batch_mod = 0; a.scale = 1.0f / sqrtf((float)hd);
+    return launch_attention(a, (hipStream_t)stream);
+}
+int vb_conv1d_f32(const float* x, const float* w, const float* bias, int B, int Ci, int T_in, int Co, int ksize, int dil, int pad,
+                  int tr_stride, int tr_pad, int tr_k, int T_out, int in_act, float in_slope, const float* res, float* out,
+                  const void* w_x3, int ci_pad, void* stream) {
+    ConvArgs a;
+    if (w_x3) {
+        const int phases = tr_stride > 1 ? tr_stride : 1;
+        const int ntaps = tr_stride > 1 ? (tr_k + tr_stride - 1) / tr_stride : ksize;
+        a.wp = (const bf16_t*)w_x3; a.Ci_pad = ci_pad; a.wp_plane = (int64_t)phases * ntaps * Co * ci_pad;
+    }
+    a.x = x; a.x_bstride = (int64_t)Ci * T_in; a.Ci = Ci; a.T_in = T_in; a.w = w; a.bias = bias; a.Co = Co; a.ksize = ksize;
+    a.dil = dil; a.pad = pad; a.in_act = in_act; a.in_slope = in_slope; a.out = out; a.out_bstride = (int64_t)Co * T_out;
+    a.T_out = T_out; a.res = res; a.res_bstride = (int64_t)Co * T_out; a.B = B; a.tr_stride = tr_stride; a.tr_pad = tr_pad; a.tr_k = tr_k;
+    return launch_conv1d(a, (hipStream_t)stream);
+}
+int vb_conv1d_f32_mf(const float* x, const float* w, const float* w_mf, const float* bias, int B, int Ci, int T_in, int Co, int ksize, int dil,
+                     int pad, int T_out, int in_act, float in_slope, const float* res, float alpha, float beta, float* out, void* stream) {
+    if (!x || !w || !w_mf || !out || B < 1 || T_in < 1) VB_FAIL(VB_E_INVALID, "conv1d_f32_mf: null pointer or B/T < 1");
+    ConvArgs a;
+    a.x = x; a.x_bstride = (int64_t)Ci * T_in; a.Ci = Ci; a.T_in = T_in; a.w = w; a.w_mf = w_mf; a.bias = bias; a.Co = Co; a.ksize = ksize;
+    a.dil = dil; a.pad = pad; a.in_act = in_act; a.in_slope = in_slope; a.out = out; a.out_bstride = (int64_t)Co * T_out;
+    a.T_out = T_out; a.res = res; a.res_bstride = (int64_t)Co * T_out; a.B = B; a.alpha = alpha; a.beta = beta;
+    return launch_conv1d(a, (hipStream_t)stream);
+}
+int vb_respair_f32(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, int B, int C, int T, int k, int dil,
+                   float slope, float alpha, float beta, float* out, void* stream) {
+    if (!x || !w1 || !b1 || !w2 || !b2 || !out || B < 1 || T < 1) VB_FAIL(VB_E_INVALID, "respair_f32: null pointer or B/T < 1");
+    RespairF32Args a;
+    a.x = x; a.out = out; a.B = B; a.C = C; a.T = T; a.k = k; a.dil = dil; a.w1 = w1; a.w2 = w2; a.b1 = b1; a.b2 = b2;
+    a.slope = slope; a.alpha = alpha; a.beta = beta;
+    return launch_respair_f32(a, (hipStream_t)stream);
+}
+int vb_respair_f32_mf(const float* x, const float* w1_mf, const float* b1, const float* w2_mf, const float* b2, int B, int C, int T, int k, int dil,
+                      float slope, float alpha, float beta, float* out, void* stream) {
+    if (!x || !w1_mf || !b1 || !w2_mf || !b2 || !out || B < 1 || T < 1) VB_FAIL(VB_E_INVALID, "respair_f32_mf: null pointer or B/T < 1");
+    RespairF32Args a;
+    a.x = x; a.out = out; a.B = B; a.C = C; a.T = T; a.k = k; a.dil = dil; a.w1 = w1_mf; a.w2 = w2_mf; a.b1 = b1; a.b2 = b2;
+    a.slope = slope; a.alpha = alpha; a.beta = beta;
+    return launch_respair_f32w(a, (hipStream_t)stream);
+}
+int vb_fill_gumbel(float* out, int B, int n_branch, int T, int width, uint64_t seed, int64_t clip_base, int nfe, int block, int gate,
+                   void* stream) {
+    return launch_fill_gumbel(out, B, n_branch, T, width, seed, clip_base, nfe, nullptr, block, gate, (hipStream_t)stream);
+}
+int vb_cast_planes(const float* x, int64_t n, void* out, int np, void* stream) {
+    return launch_cast_planes(x, n, mkp((bf16_t*)out, n, np), (hipStream_t)stream);
+}
+
+}  // extern "C"

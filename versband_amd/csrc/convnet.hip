@@ -1,0 +1,239 @@
+// Conv-net executor (VAE encoder / decoder, HiFi-GAN generator): a loaded op list run over buffers carved from the caller's workspace,
+// vb_net_load's validation, and the entry points that run a net.
+#include "engine.h"
+
+static size_t net_ws_bytes(const NetProgram& n, int B, int T, std::vector<size_t>* offs) {
+    size_t off = 0;
+    if (offs) offs->clear();
+    for (const vb_buf_desc& d : n.bufs) {
+        size_t tl = (size_t)T * d.tmul;
+        size_t el = d.square == 1 ? tl * tl : (d.square == 2 ? (size_t)d.channels * ((tl + 31) / 32 * 32)
+                                  : (d.square == 3 ? (size_t)d.channels * (tl + XT_HEAD + XT_TAIL) : (size_t)d.channels * tl));
+        if (offs) offs->push_back(off);
+        off = align_up(off + el * B * sizeof(float));
+    }
+    return off;
+}
+int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, void* ws, hipStream_t st) {
+    NetProgram& n = ctx->nets[which];
+    if (!n.loaded) VB_FAIL(VB_E_STATE, "net %d not loaded", which);
+    VB_HIP(hipSetDevice(ctx->device));
+    std::vector<size_t> offs;
+    net_ws_bytes(n, B, T, &offs);
+    auto ptr = [&](int id) -> float* {
+        if (id == VB_BUF_INPUT) return const_cast<float*>(in);
+        if (id == VB_BUF_OUTPUT) return out;
+        if (id < 0) return nullptr;
+        return reinterpret_cast<float*>(static_cast<char*>(ws) + offs[id]);
+    };
+    auto tlen = [&](int id) -> int {
+        if (id == VB_BUF_INPUT) return T * n.in_tmul;
+        if (id == VB_BUF_OUTPUT) return T * n.out_tmul;
+        return T * n.bufs[id].tmul;
+    };
+    auto chans = [&](int id) -> int {
+        if (id == VB_BUF_INPUT) return n.in_ch;
+        if (id == VB_BUF_OUTPUT) return n.out_ch;
+        return n.bufs[id].channels;
+    };
+    auto bstride = [&](int id) -> int64_t {
+        if (id >= 0 && n.bufs[id].square == 1) return (int64_t)tlen(id) * tlen(id);
+        return (int64_t)chans(id) * tlen(id);
+    };
+    for (size_t oi = 0; oi < n.ops.size(); ++oi) {
+        const vb_net_op& o = n.ops[oi];
+        if (o.kind == VB_OP_GN_STATS) {
+            float* stp = ptr(o.stats);
+            VB_TRY(launch_gn_stats(ptr(o.x), B, o.Ci, tlen(o.x), o.gn_groups, 1e-6f, stp, stp + (size_t)B * o.gn_groups, st));
+        } else if (o.kind == VB_OP_SOFTMAX_T) {
+            VB_TRY(launch_softmax_rows_t(ptr(o.x), B, tlen(o.x), tlen(o.x), ptr(o.out), st));
+        } else if (o.kind == VB_OP_CONV) {
+            ConvArgs a;
+            a.x = ptr(o.x); a.x_bstride = bstride(o.x); a.T_in = tlen(o.x);
+            if (o.x_planes) {
+                // input written by VB_OP_XT_PLANES: its buffer's time length is the (upsampled) length the planes were made for
+                a.xt = reinterpret_cast<const bf16_t*>(ptr(o.x));
+                a.T_in = o.upsample2 ? tlen(o.x) / 2 : tlen(o.x);
+            }
+            a.Ci = o.Ci > 0 ? o.Ci : tlen(o.x);            // dynamic channel counts: the VAE attention contracts over T
+            a.bias = o.bias; a.Co = o.Co > 0 ? o.Co : tlen(o.out); a.ksize = o.ksize; a.dil = o.dil; a.pad = o.pad; a.upsample2 = o.upsample2;
+            a.in_stride = o.in_stride > 1 ? o.in_stride : 1; a.in_phase = o.in_phase;
+            a.in_act = o.in_act; a.in_slope = o.in_slope;
+            if (o.stats >= 0) {
+                float* stp = ptr(o.stats);
+                a.gn_mean = stp; a.gn_rstd = stp + (size_t)B * o.gn_groups; a.gn_gamma = o.gn_gamma; a.gn_beta = o.gn_beta;
+                a.gn_groups = o.gn_groups;
+            }
+            a.out = ptr(o.out); a.out_bstride = bstride(o.out); a.T_out = tlen(o.out);
+            if (o.res != -1) { a.res = ptr(o.res); a.res_bstride = bstride(o.res); }
+            a.alpha = o.alpha; a.beta = o.beta; a.acc_scale = o.acc_scale; a.out_act = o.out_act; a.out_slope = o.out_slope;
+            a.out_transposed = o.out_transposed; a.B = B; a.tr_stride = o.tr_stride; a.tr_pad = o.tr_pad; a.tr_k = o.tr_k;
+            // weights by format (vb_net_load checked the fields); launch_conv1d picks the kernel
+            switch (o.wfmt) {
+            case VB_WFMT_F32: a.w = o.w; break;
+            case VB_WFMT_MF: a.w = o.w; a.w_mf = o.w_mf; break;      // w: the direct kernels where conv1d_f32w_kernel's run-time conditions fail
+            case VB_WFMT_X3: {
+                const int phases = o.tr_stride > 1 ? o.tr_stride : 1;
+                const int ntaps = o.tr_stride > 1 ? (o.tr_k + o.tr_stride - 1) / o.tr_stride : o.ksize;
+                a.w = o.w;                                            // (the one-output-channel kernel reads the fp32 copy)
+                a.wp = (const bf16_t*)o.w_x3; a.Ci_pad = o.ci_pad; a.wp_plane = (int64_t)phases * ntaps * a.Co * o.ci_pad;
+                break;
+            }
+            case VB_WFMT_BUF_F32: a.w = ptr(o.w_buf); a.w_bstride = bstride(o.w_buf); break;
+            case VB_WFMT_BUF_X3:
+                // per-batch split planes [2][B][Co][Ci_pad] written by an earlier VB_OP_SPLIT_PLANES
+                a.Ci_pad = (a.Ci + 31) / 32 * 32;
+                a.wp = reinterpret_cast<const bf16_t*>(ptr(o.w_buf)); a.wp_bstride = (int64_t)a.Co * a.Ci_pad;
+                a.wp_plane = (int64_t)B * a.wp_bstride;
+                break;
+            }
+            VB_TRY(launch_conv1d(a, st));
+        } else if (o.kind == VB_OP_GN_APPLY) {
+            float* stp = ptr(o.stats);
+            VB_TRY(launch_gn_apply(ptr(o.x), stp, stp + (size_t)B * o.gn_groups, o.gn_gamma, o.gn_beta, B, o.Ci, tlen(o.x), o.gn_groups,
+                                   o.in_act == ACT_GN_SWISH ? 1 : 0, ptr(o.out), st));
+        } else if (o.kind == VB_OP_XT_PLANES) {
+            const float* stp = o.stats >= 0 ? ptr(o.stats) : nullptr;
+            VB_TRY(launch_xt_planes(ptr(o.x), stp, stp ? stp + (size_t)B * o.gn_groups : nullptr, o.gn_gamma, o.gn_beta, o.gn_groups, o.in_act, o.in_slope,
+                                    o.upsample2, B, o.Ci, tlen(o.x), reinterpret_cast<bf16_t*>(ptr(o.out)), st));
+        } else if (o.kind == VB_OP_AA_ACT) {
+            VB_TRY(launch_aa_act(ptr(o.x), o.gn_gamma, o.gn_beta, o.w, B, o.Ci, tlen(o.x), ptr(o.out), st));
+        } else if (o.kind == VB_OP_RESPAIR) {
+            if (o.wfmt == VB_WFMT_X3) {
+                RespairArgs r;
+                r.x = ptr(o.x); r.out = ptr(o.out); r.B = B; r.C = o.Ci; r.T = tlen(o.x); r.k = o.ksize; r.dil = o.dil;
+                r.w1 = (const bf16_t*)o.w_x3; r.w2 = (const bf16_t*)o.w2; r.b1 = o.bias; r.b2 = o.bias2;
+                r.slope = o.in_slope; r.alpha = o.alpha; r.beta = o.beta;
+                VB_TRY(launch_respair(r, st));
+            } else {
+                RespairF32Args r;
+                r.x = ptr(o.x); r.out = ptr(o.out); r.B = B; r.C = o.Ci; r.T = tlen(o.x); r.k = o.ksize; r.dil = o.dil;
+                r.w1 = o.wfmt == VB_WFMT_MF ? o.w_mf : o.w; r.w2 = (const float*)o.w2; r.b1 = o.bias; r.b2 = o.bias2;
+                r.slope = o.in_slope; r.alpha = o.alpha; r.beta = o.beta;
+                if (o.wfmt == VB_WFMT_MF) VB_TRY(launch_respair_f32w(r, st));
+                else VB_TRY(launch_respair_f32(r, st));
+            }
+        } else if (o.kind == VB_OP_SPLIT_PLANES) {
+            const int rows = o.Co > 0 ? o.Co : tlen(o.x), cols = o.Ci > 0 ? o.Ci : tlen(o.x);
+            const int cpad = (cols + 31) / 32 * 32;
+            VB_TRY(launch_split_rows(ptr(o.x), (int64_t)B * rows, cols, cpad, reinterpret_cast<bf16_t*>(ptr(o.out)), (int64_t)B * rows * cpad, st));
+        } else {
+            VB_FAIL(VB_E_INVALID, "net op %zu: bad kind %d", oi, o.kind);
+        }
+    }
+    return VB_OK;
+}
+
+// the weight fields each allowed (kind, wfmt) pair of include/versband_hip.h reads; -1 = the pair is not allowed
+enum { NW_W = 1, NW_X3 = 2, NW_MF = 4, NW_W2 = 8, NW_BUF = 16 };
+static int net_op_fields(int kind, int wfmt) {
+    switch (kind) {
+    case VB_OP_CONV:
+        switch (wfmt) {
+        case VB_WFMT_F32: return NW_W;
+        case VB_WFMT_X3: return NW_X3 | NW_W;
+        case VB_WFMT_MF: return NW_MF | NW_W;
+        case VB_WFMT_BUF_F32: case VB_WFMT_BUF_X3: return NW_BUF;
+        }
+        return -1;
+    case VB_OP_RESPAIR:
+        switch (wfmt) {
+        case VB_WFMT_F32: return NW_W | NW_W2;
+        case VB_WFMT_X3: return NW_X3 | NW_W2;
+        case VB_WFMT_MF: return NW_MF | NW_W2;
+        }
+        return -1;
+    case VB_OP_AA_ACT: return wfmt == VB_WFMT_NONE ? NW_W : -1;
+    case VB_OP_GN_STATS: case VB_OP_SOFTMAX_T: case VB_OP_SPLIT_PLANES: case VB_OP_GN_APPLY: case VB_OP_XT_PLANES:
+        return wfmt == VB_WFMT_NONE ? 0 : -1;
+    }
+    return -1;
+}
+
+extern "C" {
+
+int vb_net_load(vb_ctx* ctx, int which, const vb_net_op* ops, int n_ops, const vb_buf_desc* bufs, int n_bufs, int in_channels,
+                int out_channels, int in_tmul, int out_tmul) {
+    if (!ctx || which < 0 || which > 2 || !ops || n_ops < 1 || in_tmul < 1 || out_tmul < 1) VB_FAIL(VB_E_INVALID, "net_load: bad argument");
+    auto tmul = [&](int id) { return id == VB_BUF_INPUT ? in_tmul : (id == VB_BUF_OUTPUT ? out_tmul : bufs[id].tmul); };
+    for (int i = 0; i < n_ops; ++i) {
+        const vb_net_op& o = ops[i];
+        const int ids[5] = {o.x, o.out, o.res, o.stats, o.w_buf};
+        for (int id : ids)
+            if (id >= n_bufs || (id < -3)) VB_FAIL(VB_E_INVALID, "net_load: op %d references buffer %d of %d", i, id, n_bufs);
+        const int f = net_op_fields(o.kind, o.wfmt);
+        if (f < 0) VB_FAIL(VB_E_INVALID, "net_load: op %d: kind %d has no weight format %d", i, o.kind, o.wfmt);
+        const struct { int bit; bool set; const char* name; } slots[] = {
+            {NW_W, o.w != nullptr, "w"}, {NW_X3, o.w_x3 != nullptr, "w_x3"}, {NW_MF, o.w_mf != nullptr, "w_mf"}, {NW_W2, o.w2 != nullptr, "w2"},
+            {NW_BUF, o.w_buf != -1, "w_buf"}};
+        for (const auto& sl : slots)
+            if (sl.set != ((f & sl.bit) != 0))
+                VB_FAIL(VB_E_INVALID, "net_load: op %d (kind %d, weight format %d): %s is %s", i, o.kind, o.wfmt, sl.name,
+                        sl.set ? "set but not read" : "missing");
+        if (o.wfmt == VB_WFMT_X3 && o.ci_pad != (o.Ci + 31) / 32 * 32)
+            VB_FAIL(VB_E_INVALID, "net_load: op %d: split weights padded to %d input channels, not %d rounded up to 32", i, o.ci_pad, o.Ci);
+        if (o.wfmt == VB_WFMT_MF && (!aligned16(o.w_mf) || !aligned16(o.w2)))
+            VB_FAIL(VB_E_INVALID, "net_load: op %d: minimal-filtering weights are not 16-byte aligned", i);
+        if (o.kind == VB_OP_RESPAIR) {
+            if (!o.bias || !o.bias2) VB_FAIL(VB_E_INVALID, "net_load: op %d: respair without both biases", i);
+            if (o.Ci != o.Co) VB_FAIL(VB_E_INVALID, "net_load: op %d: respair with Ci %d != Co %d", i, o.Ci, o.Co);
+            if (o.x == -1 || o.out == -1 || tmul(o.x) != tmul(o.out))
+                VB_FAIL(VB_E_INVALID, "net_load: op %d: respair input and output differ in length", i);
+        }
+    }
+    NetProgram& n = ctx->nets[which];
+    n.ops.assign(ops, ops + n_ops);
+    n.bufs.assign(bufs, bufs + n_bufs);
+    n.in_ch = in_channels; n.out_ch = out_channels; n.in_tmul = in_tmul; n.out_tmul = out_tmul; n.loaded = true;
+    return VB_OK;
+}
+size_t vb_net_workspace_bytes(vb_ctx* ctx, int which, int B, int T) {
+    if (!ctx || which < 0 || which > 2 || !ctx->nets[which].loaded) return 0;
+    return net_ws_bytes(ctx->nets[which], B, T, nullptr);
+}
+int vb_vae_decode(vb_ctx* ctx, const float* z, int B, int T, float* mel, void* ws, void* stream) {
+    if (!ctx) VB_FAIL(VB_E_INVALID, "vae_decode: null ctx");
+    RoctxRange rr("vb_vae_decode");
+    return net_run(ctx, VB_NET_VAE, z, B, T, mel, ws, (hipStream_t)stream);
+}
+int vb_vae_encode(vb_ctx* ctx, const float* mel, int B, int T, float* moments, void* ws, void* stream) {
+    if (!ctx) VB_FAIL(VB_E_INVALID, "vae_encode: null ctx");
+    RoctxRange rr("vb_vae_encode");
+    return net_run(ctx, VB_NET_VAE_ENCODER, mel, B, T, moments, ws, (hipStream_t)stream);
+}
+int vb_hifigan_forward(vb_ctx* ctx, const float* mel, int B, int T, float* wav, void* ws, void* stream) {
+    if (!ctx) VB_FAIL(VB_E_INVALID, "hifigan_forward: null ctx");
+    RoctxRange rr("vb_hifigan_forward");
+    return net_run(ctx, VB_NET_VOCODER, mel, B, T, wav, ws, (hipStream_t)stream);
+}
+int vb_crossfade_windows(const float* parts, const int32_t* starts, int nw, int B, int C, int n, int T, float* out, void* stream) {
+    if (!parts || !starts || !out || nw < 1 || B < 1 || C < 1 || n < 1 || T < 1) VB_FAIL(VB_E_INVALID, "crossfade_windows: null pointer or nw/B/C/n/T < 1");
+    return launch_crossfade_windows(parts, starts, nw, B, C, n, T, out, (hipStream_t)stream);
+}
+int vb_hifigan_forward_chunked(vb_ctx* ctx, const float* mel, int B, int T, int chunk, int halo, float* wav, void* ws, float* scratch_in,
+                               float* scratch_out, void* stream) {
+    if (!ctx) VB_FAIL(VB_E_INVALID, "hifigan_forward_chunked: null ctx");
+    if (chunk < 1 || halo < 0) VB_FAIL(VB_E_INVALID, "hifigan_forward_chunked: chunk=%d halo=%d", chunk, halo);
+    NetProgram& n = ctx->nets[VB_NET_VOCODER];
+    if (!n.loaded) VB_FAIL(VB_E_STATE, "hifigan_forward_chunked: no vocoder loaded");
+    hipStream_t st = (hipStream_t)stream;
+    RoctxRange rr("vb_hifigan_forward_chunked");
+    if (T <= chunk + 2 * halo) return net_run(ctx, VB_NET_VOCODER, mel, B, T, wav, ws, st);
+    VB_HIP(hipSetDevice(ctx->device));
+    const int hop = n.out_tmul, rows_in = B * n.in_ch, rows_out = B * n.out_ch;
+    for (int s = 0; s < T; s += chunk) {
+        // frames [lo, hi) = the chunk with its context; every row (clip, channel) of the slice is gathered into a contiguous tensor, the
+        // generator runs on it, and the samples of [s, e) are scattered into the whole-clip waveform (strided 2-D copies, no kernel)
+        const int e = s + chunk < T ? s + chunk : T;
+        const int lo = s - halo > 0 ? s - halo : 0, hi = e + halo < T ? e + halo : T;
+        const int tc = hi - lo;
+        VB_HIP(hipMemcpy2DAsync(scratch_in, (size_t)tc * sizeof(float), mel + lo, (size_t)T * sizeof(float), (size_t)tc * sizeof(float), rows_in,
+                                hipMemcpyDeviceToDevice, st));
+        VB_TRY(net_run(ctx, VB_NET_VOCODER, scratch_in, B, tc, scratch_out, ws, st));
+        VB_HIP(hipMemcpy2DAsync(wav + (size_t)s * hop, (size_t)T * hop * sizeof(float), scratch_out + (size_t)(s - lo) * hop,
+                                (size_t)tc * hop * sizeof(float), (size_t)(e - s) * hop * sizeof(float), rows_out, hipMemcpyDeviceToDevice, st));
+    }
+    return VB_OK;
+}
+
+}  // extern "C"

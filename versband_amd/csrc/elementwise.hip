@@ -423,11 +423,10 @@ template <int PP, bool SC, int TPW, int KPL = 16, int EE = 0>
 static void launch_router_v(dim3 grid, size_t lds, hipStream_t st, const RouterDev& a) {
     hipLaunchKernelGGL((router_kernel<PP, SC, TPW, KPL, EE>), grid, dim3(256), lds, st, a);
 }
-int launch_router(Planes cq, const float* Wg, const float* bg, const float* la, int la_mod_rows, const float* hl, int hl_ld,
-                  const float* g1, const float* g2, const float* g3, int N, int T, int D, int E, int* ic, int* ia, float* mc,
-                  float* ma, float* lc_out, int B, uint64_t seed, int64_t clip_base, int nfe_base, const int* step, int block,
-                  hipStream_t st, const float* sc, int NS, int Hh, int* cnt, int cnt_G, int cnt_pairs) {
-    const int Bq = B > 0 ? B : 1;
+int launch_router(const RouterDev& in, hipStream_t st) {
+    RouterDev a = in;
+    a.B = in.B > 0 ? in.B : 1; a.NS = in.sc ? in.NS : 0; a.Hh = in.sc ? in.Hh : 1;
+    const int N = a.N, D = a.D, E = a.E, NS = in.NS, Hh = in.Hh;
     // tokens per wave: TWO (round 3; rounds 1-2: four).  Two tokens side by side amortise the noise generator and the arg-max, keep the
     // wave's registers at half of the four-token form and put twice the waves on a SIMD: same box, 12032 tokens 23.1 -> 20.0 us, whole
     // runs +1.2 % (8 clips, two streams), +2.9 % (E = 8, 32 clips), +1.8 % (4 x 120 s).  A launch that would not even put one workgroup on
@@ -442,12 +441,7 @@ int launch_router(Planes cq, const float* Wg, const float* bg, const float* la, 
     const bool two = forced ? forced == 2 && 2 * E + 2 <= 32 : 2 * E + 2 <= 32;
     const dim3 grid(cdiv(N, 4 * (small ? 1 : (two ? 2 : RT_TPW_MAX))));
     const int pp = 2 * E + 2 <= 16 ? 4 : (2 * E + 2 <= 32 ? 2 : 1);
-    RouterDev a;
-    a.cq = cq; a.Wg = Wg; a.bg = bg; a.la = la; a.la_rows = la_mod_rows; a.hl = hl; a.hl_ld = hl_ld; a.g1 = g1; a.g2 = g2; a.g3 = g3;
-    a.N = N; a.T = T; a.D = D; a.E = E; a.ic = ic; a.ia = ia; a.mc = mc; a.ma = ma; a.lc_out = lc_out; a.B = Bq; a.seed = seed;
-    a.clip_base = clip_base; a.nfe_base = nfe_base; a.step = step; a.block = block; a.sc = sc; a.NS = sc ? NS : 0; a.Hh = sc ? Hh : 1;
-    a.cnt = cnt; a.cnt_G = cnt_G; a.cnt_pairs = cnt_pairs;
-    if (sc) {
+    if (a.sc) {
         // folded caption gate: logits from attention scores + per-clip VW (see router_tokens)
         if (NS % 64 || NS > 1024 || Hh < 1 || Hh > 64 || (Hh & (Hh - 1))) VB_FAIL(VB_E_INVALID, "router: NS=%d heads=%d unsupported", NS, Hh);
         const bool fixed = NS == 640 && !vb_tune().router_generic;

@@ -1,0 +1,142 @@
+// What the host translation units of libversband_hip.so share (runtime.hip, dit.hip, sampler.hip, convnet.hip, abi_units.hip and the
+// host drivers at the end of t5.hip / melnet.hip): the context, the workspace carver, the DiT layouts and the calls that cross files.
+// No device allocation happens on the host side: all scratch is carved out of caller buffers (sizes from *_bytes()).
+#pragma once
+#include <tuple>
+#include <vector>
+
+#include "../../include/versband_hip.h"
+#include "kernels.h"
+
+struct NetProgram {
+    std::vector<vb_net_op> ops;
+    std::vector<vb_buf_desc> bufs;
+    int in_ch = 0, out_ch = 0, in_tmul = 1, out_tmul = 1;
+    bool loaded = false;
+};
+// one captured + instantiated step loop of vb_sample_cfg (hipGraph), keyed by everything the launches bake in
+struct SampleGraph {
+    struct Key {
+        const void* x = nullptr; const void* cond = nullptr; const void* ws = nullptr;
+        int B = 0, nb = 0, T = 0, L = 0, n_steps = 0; float cfg_scale = 0.f;
+        unsigned tune_gen = 0;            // a captured graph bakes the knob-dependent kernel selection in
+        const void* keep_ref = nullptr; const void* keep_x0 = nullptr; const void* keep_mask = nullptr; float sigma_min = 0.f;   // vb_sample_cfg_keep (all null: a plain call)
+        auto tie() const { return std::tie(x, cond, ws, B, nb, T, L, n_steps, cfg_scale, tune_gen, keep_ref, keep_x0, keep_mask, sigma_min); }
+        bool operator==(const Key& o) const { return tie() == o.tie(); }
+    } key;
+    int seen = 0;                         // calls with this key so far (the first runs eagerly, the second captures)
+    bool failed = false;                  // capture was refused once (e.g. legacy default stream): stay eager
+    hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
+    uint64_t last_use = 0;
+    void destroy() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+        exec = nullptr; graph = nullptr;
+    }
+};
+struct vb_ctx {
+    int device = 0;
+    std::vector<SampleGraph> graphs; uint64_t graph_clock = 0;
+    bool dit_loaded = false;
+    vb_dit_config cfg;
+    vb_dit_weights w;
+    NetProgram nets[3];
+    bool t5_loaded = false;
+    vb_t5_config t5cfg;
+    vb_t5_weights t5w;
+    bool mel_loaded = false;
+    vb_mel_config melcfg;
+    const float* mel_dft = nullptr; const float* mel_basis_t = nullptr;
+};
+
+static inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+struct Carver {
+    char* base; size_t off = 0;
+    explicit Carver(void* b) : base(static_cast<char*>(b)) {}
+    template <typename T> T* take(size_t n) {
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off = align_up(off + n * sizeof(T));
+        return p;
+    }
+};
+static inline int pad64(int x) { return (x + 63) / 64 * 64; }
+static inline Planes mkp(bf16_t* p, int64_t numel, int np) { return Planes{p, numel, np}; }
+static inline Planes wpl(const void* p, int64_t numel, int np) { return Planes{(bf16_t*)p, numel, np}; }
+
+// ---- runtime.hip ----------------------------------------------------------------------------
+// roctx range (rocprofv3 --marker-trace); the profiler's marker library is looked up at run time
+struct RoctxRange {
+    bool on;
+    explicit RoctxRange(const char* name);
+    ~RoctxRange();
+};
+bool prof_enabled();      // the per-launch HIP-event profiler (vb_prof_enable) is on: the sampler then stays eager
+
+// ---- dit.hip: layouts, one network evaluation -------------------------------------------------
+struct CondL {
+    float* ac; float* cemb;
+    bf16_t* ky[VB_MAX_DEPTH]; bf16_t* vyt[VB_MAX_DEPTH]; bf16_t* kc[VB_MAX_DEPTH]; bf16_t* vct[VB_MAX_DEPTH];
+    float* la[VB_MAX_DEPTH];
+    // folded caption gate (see router_kernel<.., true>): per clip and block the caption keys with the MoE q-projection folded in
+    // (planes [Beff][NS = L*heads][D], row = key*heads + head), the q-bias part of the scores and the gate-contracted values
+    bf16_t* mf[VB_MAX_DEPTH]; float* cb[VB_MAX_DEPTH]; float* vw[VB_MAX_DEPTH]; int* clip_off; int NS; bool fold;
+    bf16_t* pin_w;       // proj_in weights as a GEMM operand: split planes [2][D][PIN_KP], k = tap * 32 + ci (conv_w_to_gemm_kernel)
+    int64_t n_k, n_vt; int Lpad;
+    size_t total;
+};
+#define T_FREQ_ROWS 1000  // rows of vb_dit_weights.t_freq_table (pack.timestep_table); other indices are computed in the kernel
+#define PRE_STEPS 64      // sampler steps whose adaLN / gate vectors are tabulated up front
+struct WsL {
+    int* step; int64_t* t_idx_cur; int64_t* t_table; float* dt_table;
+    float* tn_table;                                                // vb_sample_cfg_keep: t after every step (carved last: no other offset moves)
+    float *temb0, *temb, *mod_all, *hl, *h, *cq32, *mc, *ma, *y32, *g1, *g2, *g3, *v;
+    bf16_t* modA;                                                   // A operand (planes) of the adaLN tabulation GEMM
+    float *temb0_s, *temb_s, *hl_s, *mod_s; int64_t* row_step;     // per-sample tables of the conditioning vectors of every step
+    bf16_t *u, *q, *k, *vt, *a, *qm, *cqa, *Hs, *y, *Hf, *pin_a;
+    int *ic, *ia, *group_off, *perm, *pair_off, *pair_pa;
+    // precompute temporaries
+    float *tA, *tB, *tC, *tD, *tE, *cap_pre, *cap32, *pooled, *pooled_ln;
+    bf16_t *t5p, *gel, *capp, *yp;
+    int64_t n_tok, n_vt; int Tpad, MODW;
+    size_t total;
+};
+CondL carve_cond(void* base, const vb_dit_config& c, int B, int nb, int T, int L);
+WsL carve_ws(void* base, const vb_dit_config& c, int B, int nb, int T, int L);
+
+// Every choice one network evaluation makes, stated once (dit_plan): each member is a function of the loaded model, the knobs and
+// (B, nb, T, L) alone, so precompute, evaluation and sampler cannot disagree, and none depends on anything that varies between the
+// blocks or the steps of a call.
+enum FinalRoute {
+    FINAL_EULER_FUSED,   // FinalLayer + CFG + Euler update + step advance as one launch: only with DitEval::euler (the sampler);
+                         // an evaluation without it takes FINAL_FUSED, whose conditions this route includes
+    FINAL_FUSED,         // one wave per token row, projection against LDS-resident weights
+    FINAL_GEMM,          // LayerNorm + modulate to split planes, projection on the MFMA GEMM
+    FINAL_ROWS           // the generic kernel
+};
+struct DitPlan {
+    const vb_dit_weights* w = nullptr;
+    bool router_counts = false, w2_pair = false, band_fused = false, proj_in_split_w = false, proj_in_gemm = false;
+    bool fold_layout = false, score_fused = false;
+    FinalRoute final_route = FINAL_ROWS;
+    // block i takes the folded caption gate: the layout holds its operands and the pack carries the folded weights
+    bool gate_fold(int i) const { return fold_layout && w->blocks[i].wqt_s && w->blocks[i].bq_s; }
+};
+DitPlan dit_plan(const vb_ctx* ctx, int B, int nb, int T, int L);
+
+// sampler only: FinalLayer + CFG + Euler update + step advance as one launch (launch_final_layer_euler) - x is updated in place, v is not written
+struct EulerFuse { float* x; float cfg_scale; const float* dt_table; int k; int* step; int64_t* t_idx_cur; const int64_t* t_table; int n_steps; const EulerKeep* keep; };
+// one network evaluation (both CFG branches batched: rows [0,B) cond, [B,2B) uncond); a caller fills what it uses
+struct DitEval {
+    const float* x = nullptr; const int64_t* t_idx = nullptr; const void* cond = nullptr; void* ws = nullptr;
+    int B = 0, nb = 0, T = 0, L = 0;
+    const vb_noise* noise = nullptr; int noise_step = 0; const int* step_ptr = nullptr;
+    float* v_out = nullptr; int32_t* route_out = nullptr;
+    bool zero_vt = false;                                       // clear the padded V^T planes first (a stand-alone call)
+    const float* pre_mod = nullptr; const float* pre_hl = nullptr;   // this step's rows of the sampler's tabulated conditioning vectors
+    int evals_before = -1;                                      // block evaluations already done in this call (< 0: stand-alone, see DitPlan::router_counts)
+    const EulerFuse* euler = nullptr;
+};
+int dit_forward(vb_ctx* ctx, const DitEval& ev, hipStream_t st);
+
+// ---- convnet.hip ----------------------------------------------------------------------------
+int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, void* ws, hipStream_t st);

@@ -53,6 +53,13 @@ struct GemmArgs {
     const float* rope_cos = nullptr; const float* rope_sin = nullptr;
     int H = 1, hd = 1, Tpad = 0, D = 0;
 };
+// the ten operand fields every launch sets; a call site then adds what distinguishes it (epilogue, outputs, groups)
+static inline GemmArgs gemm_operands(const void* A, int64_t a_plane, int lda, const void* B, int64_t b_plane, int ldb, int M, int N, int K, int nseg) {
+    GemmArgs g;
+    g.A = (const bf16_t*)A; g.a_plane = a_plane; g.lda = lda; g.B = (const bf16_t*)B; g.b_plane = b_plane; g.ldb = ldb;
+    g.M = M; g.N = N; g.K = K; g.nseg = nseg;
+    return g;
+}
 int launch_gemm(const GemmArgs& a, hipStream_t st);
 // routed experts, second product of BOTH groups in one launch over (caption, acoustic) pair buckets (bf16, E <= 4; moe_w2_pair_kernel):
 // out[tok][:] = Hs[caption slot] W2[c]^T + Hs[acoustic slot] W2[E + a]^T  with the gate weights m_c / m_a already folded into the
@@ -204,10 +211,23 @@ int launch_euler_cfg_keep(float* x, const float* v, int B, int64_t per, int T, f
                           int has_uncond, const EulerKeep& keep, hipStream_t st);
 // projection on entry: x <- blend(mask, r(t_0), x) with t_0 = tn_table[0] - dt_table[0]
 int launch_keep_project(float* x, int B, int64_t per, int T, const float* dt_table, const EulerKeep& keep, hipStream_t st);
-int launch_router(Planes cq, const float* Wg, const float* bg, const float* la, int la_mod_rows, const float* hl, int hl_ld,
-                  const float* g1, const float* g2, const float* g3, int N, int T, int D, int E, int* ic, int* ia, float* mc,
-                  float* ma, float* lc_out, int B, uint64_t seed, int64_t clip_base, int nfe_base, const int* step, int block,
-                  hipStream_t st, const float* sc = nullptr, int NS = 0, int Hh = 1, int* cnt = nullptr, int cnt_G = 0, int cnt_pairs = 0);
+// Band-MoE router: call arguments and the kernel's argument block in one (the device side is router_dev.h).
+// SC = true: "folded" caption gate.  The token features are not materialised at all: `sc` holds the token's attention
+// SCORES against its clip's caption keys for all heads ([N][NS], NS = L * Hh, column = key * Hh + head; scale, q-projection
+// and q-bias already inside - one grouped GEMM against per-clip folded keys), `Wg` holds per clip VW[key*Hh+head][e] =
+// value_row(head) . (gate weight row e restricted to the head), so   logit_e = sum_heads sum_keys softmax(scores)_key VW_e.
+struct RouterDev {
+    Planes cq = {nullptr, 0, 1}; const float* Wg = nullptr; const float* bg = nullptr; const float* la = nullptr; int la_rows = 0; const float* hl = nullptr; int hl_ld = 0;
+    const float* g1 = nullptr; const float* g2 = nullptr; const float* g3 = nullptr; int N = 0, T = 0, D = 0, E = 0;
+    int* ic = nullptr; int* ia = nullptr; float* mc = nullptr; float* ma = nullptr; float* lc_out = nullptr; int B = 0;
+    uint64_t seed = 0; int64_t clip_base = 0; int nfe_base = 0; const int* step = nullptr; int block = 0; const float* sc = nullptr; int NS = 0, Hh = 1;
+    // bucket counts as a side product (round 5): cnt[(n / RT_CNT_BLOCK) * cnt_G + group] += 1 for the token's expert pair (cnt_pairs) or its two
+    // expert groups - what bucket_count_kernel computed in a launch of its own; the table must be zero on entry (launch_bucket's place kernel
+    // clears the table of the NEXT launch).  Integer atomics: the sums do not depend on their order.
+    int* cnt = nullptr; int cnt_G = 0; int cnt_pairs = 0;
+};
+// (B <= 0 is taken as 1; NS / Hh count only with sc)
+int launch_router(const RouterDev& a, hipStream_t st);
 // fused caption-gate scores + router (score_router.hip): bf16 token features x per-clip folded keys -> routing decisions, the
 // [N][NS] score matrix stays in LDS.  Bit-identical to launch_gemm(EPI_F32 scores) + launch_router(sc = scores).
 struct ScoreRouterArgs {

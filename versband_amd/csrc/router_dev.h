@@ -1,7 +1,7 @@
 // Device side of the Band-MoE router, shared by router_kernel (elementwise.hip) and the fused score + router kernel
 // (score_router.hip): one wave decides RT_TPW consecutive tokens.
 #pragma once
-#include "common.h"
+#include "kernels.h"
 
 // ---------------------------------------------------------------------------
 // Gumbel noise generator for the production path: G = -log(-log(1-u)), u from splitmix64
@@ -62,19 +62,7 @@ __device__ __forceinline__ float reduce_logits(const float (&part)[PE], int lane
 //   torch.max) ; (m_c, m_a) = softmax(hl[b] + G1).   G* are Gumbel draws (-log Exp(1)).
 // ---------------------------------------------------------------------------
 #define RT_TPW_MAX 4  // tokens per wave (4 when the launch fills the chip anyway; 1 for small batches: 4x the waves, a quarter of the latency)
-// SC = true: "folded" caption gate.  The token features are not materialised at all: `sc` holds the token's attention
-// SCORES against its clip's caption keys for all heads ([N][NS], NS = L * Hh, column = key * Hh + head; scale, q-projection
-// and q-bias already inside - one grouped GEMM against per-clip folded keys), `Wg` holds per clip VW[key*Hh+head][e] =
-// value_row(head) . (gate weight row e restricted to the head), so   logit_e = sum_heads sum_keys softmax(scores)_key VW_e.
-struct RouterDev {
-    Planes cq; const float* Wg; const float* bg; const float* la; int la_rows; const float* hl; int hl_ld;
-    const float* g1; const float* g2; const float* g3; int N, T, D, E; int* ic; int* ia; float* mc; float* ma; float* lc_out; int B;
-    uint64_t seed; int64_t clip_base; int nfe_base; const int* step; int block; const float* sc; int NS, Hh;
-    // bucket counts as a side product (round 5): cnt[(n / RT_CNT_BLOCK) * cnt_G + group] += 1 for the token's expert pair (cnt_pairs) or its two
-    // expert groups - what bucket_count_kernel computed in a launch of its own; the table must be zero on entry (launch_bucket's place kernel
-    // clears the table of the NEXT launch).  Integer atomics: the sums do not depend on their order.
-    int* cnt; int cnt_G; int cnt_pairs;
-};
+// (struct RouterDev, the kernels' argument block, is declared in kernels.h: launch_router's callers fill it)
 #define RT_CNT_BLOCK 256      // = BK_T of the bucket kernels (elementwise.hip)
 // Phase B of the router for the RT_TPW tokens n0 .. of one wave: noise draws, arg-max, high-level gate.  A token needs 2E+2 "slots"
 // (E caption-gate, E acoustic-gate, 2 high-level-gate values): PP tokens are laid side by side in the wave (SPT = 64/PP lanes each), so

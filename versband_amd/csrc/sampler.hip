@@ -1,0 +1,168 @@
+// CFG / Euler sampler (cfm1_audio_sampler.py:107-116): the step loop around dit_forward and its hipGraph cache.
+#include "engine.h"
+
+// the launches of one sampler call after its tables are in place: tabulation of the per-step conditioning vectors, then n_steps x
+// [step bookkeeping, one network evaluation of both CFG branches, Euler + guidance update]   (cfm1_audio_sampler.py:107-116)
+// keep != nullptr (vb_sample_cfg_keep): every update also puts the known tokens back on the probability path at the time after the step
+static int sample_steps(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps, float cfg_scale,
+                        const vb_keep* keep, const vb_noise* noise, float* traj, void* ws, hipStream_t st) {
+    const vb_dit_config& c = ctx->cfg;
+    const DitPlan plan = dit_plan(ctx, B, n_branch, T, L);
+    WsL s = carve_ws(ws, c, B, n_branch, T, L);
+    const int Beff = B * n_branch;
+    const int64_t per = (int64_t)c.in_channels * T;
+    // (a kernel, not hipMemsetAsync: the captured step loop then consists of kernel nodes only)
+    VB_TRY(launch_fill_f32(reinterpret_cast<float*>(s.vt), (int64_t)s.n_vt * c.np / 2, 0.f, st));
+    // The timestep embedding, every block's adaLN modulation and the high-level gate logits depend on (t_k, caption)
+    // only: tabulate them for ALL steps in four launches instead of four GEMVs inside every network evaluation.
+    const bool tab = n_steps <= PRE_STEPS;
+    const int D = c.hidden, MODW = s.MODW;
+    if (tab) {
+        const vb_dit_weights& w = ctx->w;
+        CondL cd = carve_cond(const_cast<void*>(cond), c, B, n_branch, T, L);
+        VB_TRY(launch_gemv_rows_idx(w.t_freq_table, 256, s.t_table, nullptr, 0, 1, w.t_mlp0_w, w.t_mlp0_b, n_steps, D, 256, 0, s.temb0_s, D, st, T_FREQ_ROWS));
+        VB_TRY(launch_gemv_rows(s.temb0_s, D, nullptr, 0, 1, w.t_mlp2_w, w.t_mlp2_b, n_steps, D, D, 1, s.temb_s, D, st));
+        VB_TRY(launch_iota_div(s.row_step, n_steps * Beff, Beff, st));
+        if (w.adaln_wp) {
+            // [steps x samples][768] x [19968][768]^T in split-bf16 (fp32-class) on the MFMA GEMM: 0.2 ms instead of 2.2 ms per call
+            const int rows = n_steps * Beff;
+            const int64_t apl = (int64_t)rows * D;
+            VB_TRY(launch_silu_sum_planes(s.temb_s, cd.cemb, rows, D, Beff, s.modA, apl, st));
+            GemmArgs g = gemm_operands(s.modA, apl, D, w.adaln_wp, (int64_t)MODW * D, D, rows, MODW, D, 3);
+            g.epi = EPI_F32; g.bias = w.adaln_b; g.out32 = s.mod_s; g.ldc32 = MODW;
+            VB_TRY(launch_gemm(g, st));
+        } else {
+            VB_TRY(launch_gemv_rows_idx(s.temb_s, D, s.row_step, cd.cemb, D, Beff, w.adaln_w, w.adaln_b, n_steps * Beff, MODW, D, 1, s.mod_s, MODW, st));
+        }
+        VB_TRY(launch_gemv_rows(s.temb_s, D, nullptr, 0, 1, w.hl_w, w.hl_b, n_steps, c.depth * 2, D, 0, s.hl_s, c.depth * 2, st));
+    }
+    // the router's count tables, cleared once per call inside the captured graph (DitPlan::router_counts)
+    if (plan.router_counts) {
+        const int N = (int)s.n_tok;
+        VB_TRY(launch_fill_f32(reinterpret_cast<float*>(bucket_counts(s.perm, N, 0)), bucket_counts_ints(N), 0.f, st));
+    }
+    // FinalLayer, CFG combination, Euler update and the step counter's advance as ONE launch per step (round 5; VB_EULER_LAUNCH=1 keeps the three
+    // launches: same arithmetic, bit-identical)
+    // (the device step counter s.step ends a call at n_steps with the fused Euler launch and at n_steps - 1 with the separate launches; nothing
+    //  reads it after the call, launch_step_ctl resets it at k == 0)
+    const bool fuse = plan.final_route == FINAL_EULER_FUSED;
+    EulerKeep kp{};
+    if (keep) kp = EulerKeep{keep->ref, keep->x0, keep->mask, s.tn_table, keep->sigma_min};
+    for (int k = 0; k < n_steps; ++k) {
+        RoctxRange rs("euler_step");
+        if (!fuse || k == 0) VB_TRY(launch_step_ctl(s.step, s.t_idx_cur, s.t_table, n_steps, Beff, k == 0, st));
+        EulerFuse ef{x, cfg_scale, s.dt_table, k, s.step, s.t_idx_cur, s.t_table, n_steps, keep ? &kp : nullptr};
+        DitEval ev;
+        ev.x = x; ev.t_idx = s.t_idx_cur; ev.cond = cond; ev.ws = ws; ev.B = B; ev.nb = n_branch; ev.T = T; ev.L = L;
+        ev.noise = noise; ev.noise_step = k; ev.step_ptr = s.step; ev.v_out = s.v;
+        if (tab) { ev.pre_mod = s.mod_s + (size_t)k * Beff * MODW; ev.pre_hl = s.hl_s + (size_t)k * c.depth * 2; }
+        ev.evals_before = k * c.depth;
+        if (fuse) ev.euler = &ef;
+        VB_TRY(dit_forward(ctx, ev, st));
+        if (!fuse && keep) VB_TRY(launch_euler_cfg_keep(x, s.v, B, per, T, cfg_scale, s.dt_table, s.step, n_branch == 2, kp, st));
+        else if (!fuse) VB_TRY(launch_euler_cfg(x, s.v, B, per, cfg_scale, s.dt_table, s.step, 0.f, n_branch == 2, st));
+        if (traj) VB_HIP(hipMemcpyAsync(traj + (size_t)(k + 1) * B * per, x, (size_t)B * per * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+    return VB_OK;
+}
+
+// the cache entry of this call's key: found, or inserted over the least recently used of 8
+static SampleGraph* graph_entry(vb_ctx* ctx, const SampleGraph::Key& key) {
+    SampleGraph* e = nullptr;
+    for (SampleGraph& gph : ctx->graphs)
+        if (gph.key == key) { e = &gph; break; }
+    if (!e) {
+        if (ctx->graphs.size() >= 8) {
+            size_t lru = 0;
+            for (size_t i = 1; i < ctx->graphs.size(); ++i) if (ctx->graphs[i].last_use < ctx->graphs[lru].last_use) lru = i;
+            ctx->graphs[lru].destroy();
+            ctx->graphs.erase(ctx->graphs.begin() + lru);
+        }
+        ctx->graphs.emplace_back();
+        e = &ctx->graphs.back();
+        e->key = key;
+    }
+    e->last_use = ++ctx->graph_clock;
+    e->seen += 1;
+    return e;
+}
+
+extern "C" {
+
+int vb_euler_cfg_step(float* x, const float* v, int B, int64_t per_item, float cfg_scale, float dt, int has_uncond, void* stream) {
+    return launch_euler_cfg(x, v, B, per_item, cfg_scale, nullptr, nullptr, dt, has_uncond, (hipStream_t)stream);
+}
+int vb_sample_cfg(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
+                  const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_noise* noise, float* traj, void* ws,
+                  void* stream) {
+    return vb_sample_cfg_keep(ctx, x, cond, B, n_branch, T, L, n_steps, t_idx_table, dt_table, cfg_scale, nullptr, noise, traj, ws, stream);
+}
+int vb_sample_cfg_keep(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
+                       const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_keep* keep, const vb_noise* noise,
+                       float* traj, void* ws, void* stream) {
+    if (!ctx || !ctx->dit_loaded) VB_FAIL(VB_E_STATE, "sample_cfg: DiT not loaded");
+    if (n_steps < 1 || n_steps > 1024) VB_FAIL(VB_E_INVALID, "sample_cfg: n_steps=%d", n_steps);
+    if (keep && (!keep->ref || !keep->x0 || !keep->mask || !keep->t_next)) VB_FAIL(VB_E_INVALID, "sample_cfg_keep: ref, x0, mask and t_next must all be given");
+    VB_HIP(hipSetDevice(ctx->device));
+    RoctxRange rr("vb_sample_cfg");
+    hipStream_t st = (hipStream_t)stream;
+    const vb_dit_config& c = ctx->cfg;
+    WsL s = carve_ws(ws, c, B, n_branch, T, L);
+    const int64_t per = (int64_t)c.in_channels * T;
+    // (tables may live on the host or on the device; a host caller must keep them alive until the stream has consumed them)
+    VB_HIP(hipMemcpyAsync(s.t_table, t_idx_table, (size_t)n_steps * sizeof(int64_t), hipMemcpyDefault, st));
+    VB_HIP(hipMemcpyAsync(s.dt_table, dt_table, (size_t)n_steps * sizeof(float), hipMemcpyDefault, st));
+    if (keep) {
+        // the times travel like the step sizes do (a device table read behind the step counter); the entry projection runs here, outside
+        // the captured loop, so that traj[0] is the state the first evaluation sees
+        VB_HIP(hipMemcpyAsync(s.tn_table, keep->t_next, (size_t)n_steps * sizeof(float), hipMemcpyDefault, st));
+        VB_TRY(launch_keep_project(x, B, per, T, s.dt_table, EulerKeep{keep->ref, keep->x0, keep->mask, s.tn_table, keep->sigma_min}, st));
+    }
+    if (traj) VB_HIP(hipMemcpyAsync(traj, x, (size_t)B * per * sizeof(float), hipMemcpyDeviceToDevice, st));
+    // the noise key travels through device memory (the router reads it behind the step counter): nothing a replayed graph bakes in
+    VB_TRY(launch_sampler_params(s.step, noise ? noise->seed : 0, noise ? noise->clip_base : 0, noise ? noise->nfe : 0, st));
+
+    // ---- the step loop as ONE hipGraph (cfm1_audio_sampler.py:107-116 is ~3000 dependent launches at 50 steps): a call whose
+    // buffers and shape were seen before replays the captured, instantiated graph - one host call instead of thousands, which is
+    // what bounds small batches and several concurrent streams (the HIP runtime serialises launches of different host threads).
+    // Eager when: a trajectory or injected noise arrays are requested (parity path), the per-launch HIP-event profiler is on, the
+    // stream cannot capture (legacy default stream), VB_NO_GRAPH is set, or the key is new (its first call also warms every
+    // kernel's one-time attributes outside a capture).
+    const bool graphable = !vb_tune().no_graph && !prof_enabled() && !traj && !(noise && noise->g1) && n_steps <= PRE_STEPS && st != nullptr;
+    if (graphable) {
+        SampleGraph::Key key;
+        key.x = x; key.cond = cond; key.ws = ws; key.B = B; key.nb = n_branch; key.T = T; key.L = L; key.n_steps = n_steps; key.cfg_scale = cfg_scale;
+        key.tune_gen = vb_tune_generation();
+        if (keep) { key.keep_ref = keep->ref; key.keep_x0 = keep->x0; key.keep_mask = keep->mask; key.sigma_min = keep->sigma_min; }
+        SampleGraph* e = graph_entry(ctx, key);
+        if (!e->exec && !e->failed && e->seen >= 2) {
+            if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+                const int rc = sample_steps(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, keep, noise, nullptr, ws, st);
+                hipGraph_t gr = nullptr;
+                const hipError_t ee = hipStreamEndCapture(st, &gr);
+                if (rc == VB_OK && ee == hipSuccess && gr && hipGraphInstantiate(&e->exec, gr, nullptr, nullptr, 0) == hipSuccess) {
+                    e->graph = gr;
+                } else {
+                    if (gr) (void)hipGraphDestroy(gr);
+                    e->exec = nullptr; e->failed = true;
+                    (void)hipGetLastError();
+                }
+            } else {
+                e->failed = true;
+                (void)hipGetLastError();
+            }
+        }
+        if (e->exec) {
+            VB_HIP(hipGraphLaunch(e->exec, st));
+            return VB_OK;
+        }
+    }
+    return sample_steps(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, keep, noise, traj, ws, st);
+}
+int vb_sample_graphs(vb_ctx* ctx) {
+    int n = 0;
+    if (ctx) for (const SampleGraph& g : ctx->graphs) n += g.exec != nullptr;
+    return n;
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // Caption-gate scores + Band-MoE router in ONE launch (gfx950, bf16 production mode).
 //
-// The folded caption gate (engine.hip, vocal2music_moe.py:119-151) was two launches: a grouped GEMM writing every token's attention
+// The folded caption gate (dit.hip, vocal2music_moe.py:119-151) was two launches: a grouped GEMM writing every token's attention
 // scores against its clip's caption keys for all heads ([N][NS] fp32, NS = L * heads = 640: 30.8 MB per block evaluation at 8 clips)
 // and the router kernel reading them back (softmax per head, contraction with the per-clip VW, Gumbel arg-max).  Here a workgroup
 // owns 64 tokens of one clip and ALL NS score columns, so the scores never leave the CU:

@@ -3,7 +3,7 @@
 // 80 x 80 x 64 per (caption, head) - 0.4 MFLOP - so it runs as a plain fp32 kernel, one workgroup per (caption, head), with
 // q, k, v of the head in LDS.  HF semantics (transformers T5Attention): scores = q k^T + position_bias, NO 1/sqrt(d) scaling,
 // softmax in fp32, no mask (the reference passes none, ldm/modules/encoders/modules.py:221).
-#include "kernels.h"
+#include "engine.h"
 
 __global__ void gather_rows_kernel(const int64_t* __restrict__ idx, const float* __restrict__ table, int rows, int D, int vocab, float* out) {
     const int r = blockIdx.x;
@@ -77,3 +77,69 @@ int launch_t5_attention(Planes qkv, const float* pos_bias, int pos_len, int B, i
     VB_CHECK_LAUNCH();
     return VB_OK;
 }
+
+// ---- host driver: T5 text encoder ----------------------------------------------------------------------
+struct T5Ws { float* h; bf16_t* nrm; bf16_t* qkv; bf16_t* att; bf16_t* ff; size_t total; };
+static T5Ws carve_t5(void* base, const vb_t5_config& c, int B, int L) {
+    T5Ws o;
+    Carver cv(base);
+    const size_t R = (size_t)B * L, inner = (size_t)c.heads * c.d_kv;
+    o.h = cv.take<float>(R * c.d_model);
+    o.nrm = cv.take<bf16_t>(2 * R * c.d_model);
+    o.qkv = cv.take<bf16_t>(2 * R * 3 * inner);
+    o.att = cv.take<bf16_t>(2 * R * inner);
+    o.ff = cv.take<bf16_t>(2 * R * c.d_ff);
+    o.total = cv.off;
+    return o;
+}
+extern "C" {
+
+int vb_t5_load(vb_ctx* ctx, const vb_t5_config* cfg, const vb_t5_weights* w) {
+    if (!ctx || !cfg || !w) VB_FAIL(VB_E_INVALID, "t5_load: null argument");
+    if (cfg->layers < 1 || cfg->layers > VB_T5_MAX_LAYERS) VB_FAIL(VB_E_INVALID, "t5_load: layers %d", cfg->layers);
+    if (cfg->d_kv != 64) VB_FAIL(VB_E_INVALID, "t5_load: d_kv %d unsupported (attention kernel is built for 64)", cfg->d_kv);
+    if (cfg->d_model % 64 || cfg->d_ff % 64 || cfg->d_model > 1024) VB_FAIL(VB_E_INVALID, "t5_load: d_model %d / d_ff %d", cfg->d_model, cfg->d_ff);
+    ctx->t5cfg = *cfg;
+    ctx->t5w = *w;
+    ctx->t5_loaded = true;
+    return VB_OK;
+}
+size_t vb_t5_workspace_bytes(const vb_t5_config* cfg, int B, int L) { return carve_t5(nullptr, *cfg, B, L).total; }
+int vb_t5_encode(vb_ctx* ctx, const int64_t* ids, int B, int L, float* out, void* ws, void* stream) {
+    if (!ctx || !ctx->t5_loaded) VB_FAIL(VB_E_STATE, "t5_encode: T5 not loaded");
+    VB_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const vb_t5_config& c = ctx->t5cfg;
+    const vb_t5_weights& w = ctx->t5w;
+    if (L > w.pos_len) VB_FAIL(VB_E_INVALID, "t5_encode: L=%d exceeds the position-bias table (%d)", L, w.pos_len);
+    T5Ws s = carve_t5(ws, c, B, L);
+    const int R = B * L, D = c.d_model, inner = c.heads * c.d_kv;
+    VB_TRY(launch_gather_rows(ids, w.embed, R, D, c.vocab, s.h, st));
+    Planes nrm = mkp(s.nrm, (int64_t)R * D, 2), qkv = mkp(s.qkv, (int64_t)R * 3 * inner, 2), att = mkp(s.att, (int64_t)R * inner, 2);
+    Planes ff = mkp(s.ff, (int64_t)R * c.d_ff, 2);
+    for (int i = 0; i < c.layers; ++i) {
+        const vb_t5_layer& lw = w.layers[i];
+        // x += O(softmax(Q K^T + bias) V),  Q/K/V from T5LayerNorm(x)   (T5LayerSelfAttention)
+        VB_TRY(launch_rmsnorm_mod(s.h, lw.ln0, nullptr, nullptr, 0, R, D, L, c.eps, nrm, st));
+        GemmArgs g = gemm_operands(nrm.p, nrm.plane, D, lw.wqkv, (int64_t)3 * inner * D, D, R, 3 * inner, D, 3);
+        g.epi = EPI_PLANES; g.out = qkv; g.ldc = 3 * inner;
+        VB_TRY(launch_gemm(g, st));
+        VB_TRY(launch_t5_attention(qkv, w.pos_bias, w.pos_len, B, L, c.heads, c.d_kv, att, st));
+        g = gemm_operands(att.p, att.plane, inner, lw.wo, (int64_t)D * inner, inner, R, D, inner, 3);
+        g.epi = EPI_RESID_GATE; g.out32 = s.h; g.ldc32 = D; g.gate = w.ones; g.gate_ld = 0; g.T = L;
+        VB_TRY(launch_gemm(g, st));
+        // x += Wo(gelu_new(Wi0 n) * Wi1 n),  n = T5LayerNorm(x)   (T5LayerFF, gated-gelu)
+        VB_TRY(launch_rmsnorm_mod(s.h, lw.ln1, nullptr, nullptr, 0, R, D, L, c.eps, nrm, st));
+        g = gemm_operands(nrm.p, nrm.plane, D, lw.wi, (int64_t)2 * c.d_ff * D, D, R, 2 * c.d_ff, D, 3);
+        g.epi = EPI_GEGLU; g.out = ff; g.ldc = c.d_ff;
+        VB_TRY(launch_gemm(g, st));
+        g = gemm_operands(ff.p, ff.plane, c.d_ff, lw.wo_ff, (int64_t)D * c.d_ff, c.d_ff, R, D, c.d_ff, 3);
+        g.epi = EPI_RESID_GATE; g.out32 = s.h; g.ldc32 = D; g.gate = w.ones; g.gate_ld = 0; g.T = L;
+        VB_TRY(launch_gemm(g, st));
+    }
+    VB_TRY(launch_rmsnorm_mod(s.h, w.final_ln, nullptr, nullptr, 0, R, D, L, c.eps, nrm, st));
+    VB_TRY(launch_planes_to_f32(nrm, (int64_t)R * D, out, st));
+    return VB_OK;
+}
+
+}  // extern "C"
