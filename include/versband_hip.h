@@ -194,6 +194,23 @@ typedef struct { const float* ref; const float* x0; const float* mask; const flo
 int vb_sample_cfg_keep(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
                        const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_keep* keep,
                        const vb_noise* noise, float* traj, void* ws, void* stream);
+/* The same sampler with PER-ROW guidance scale and noise key: rows that differ in guidance scale (the scales of one item) or whose global
+ * clip indices are not contiguous (items sharded rank::world, same-length items picked out of a manifest) share one call.  All rows of a
+ * call still share T and L.
+ *   cfg_scale  f32 [B]    (device) row b is guided by cfg_scale[b]: e = fmaf(cfg_scale[b], v_c - v_u, v_u) in the fused update and in the
+ *                         keep update, e = v_u + cfg_scale[b] * (v_c - v_u) in the separate plain launch (VB_EULER_LAUNCH) - the arithmetic
+ *                         of the scalar call, form for form, so row b equals the scalar call with that scale bit for bit.  The scalar
+ *                         argument is ignored.  With n_branch == 1 there is nothing to guide and the array is not read.
+ *   clip       int64 [B]  (device) row b of BOTH branches draws its router noise from the stream of global clip clip[b] instead of
+ *                         noise->clip_base + b; seed and nfe stay per call.  With injected noise arrays (noise->g1) the ids are unused.
+ * Either member may be NULL; rows == NULL or both NULL is exactly vb_sample_cfg_keep (which, like vb_sample_cfg, forwards here).  Both
+ * arrays are read from device memory when the kernels run, and the graph key holds the two POINTERS (and 0 in place of the scalar scale
+ * beside cfg_scale): rewriting the arrays in place and calling again replays the same graph with the new values, a call with other row
+ * buffers, or with none, captures its own graph and never replays a rows graph. */
+typedef struct { const float* cfg_scale; const int64_t* clip; } vb_rows;
+int vb_sample_cfg_rows(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
+                       const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_rows* rows, const vb_keep* keep,
+                       const vb_noise* noise, float* traj, void* ws, void* stream);
 /* The step loop of vb_sample_cfg is captured into a hipGraph the second time a call arrives with the same buffers / shape on a
  * capturable (non-default) stream and replayed from then on (noise key via device memory: any seed / clip base replays).
  * Number of instantiated graphs this context holds (0 = every call so far ran eagerly): */

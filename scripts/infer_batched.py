@@ -1,0 +1,205 @@
+#!/usr/bin/env python3
+"""AccompBand inference with batched sampler calls: the CLI of scripts/test_final.py plus `--items_per_batch N`.
+
+scripts/test_final.py samples one item and one guidance scale per sampler call.  Here consecutive items of equal length, all their guided
+scales and all their samples ride as rows of ONE call with a per-row guidance scale and noise key (vb_sample_cfg_rows, planned by
+versband_amd.harness.plan_row_batches), and the batch is decoded and vocoded on the device.  The files - names, order, bytes, clap.csv - are
+those of scripts/test_final.py.  The work goes group by group: a group's items are loaded, sampled, written and dropped before the next
+group is formed, so memory does not grow with the manifest and a crash loses one group.  `--items_per_batch 1` (the default) makes the
+calls of test_final.py's loop, one per (item, scale).  `--synthetic_frames` additionally accepts a comma list that cycles over the
+synthetic items; every other flag is test_final.py's and is parsed by its parser.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+for p in (ROOT, HERE):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import test_final as loop  # noqa: E402
+from versband_amd import dist as vdist  # noqa: E402
+from versband_amd.harness import (MEL_DOWNSAMPLE, InferDataset, check_items_per_batch, parse_frames,  # noqa: E402
+                                  plan_row_batches, save_rows_to_tsv, stream_groups, write_wav_pcm16)
+from versband_amd.model import normalize_loudness  # noqa: E402
+
+
+def parse_args(argv=None):
+    """--items_per_batch and --synthetic_frames are taken out of the command line here; every other flag goes through test_final.py's own
+    parser (which reads sys.argv and is not ours to change: it sees the remaining arguments for the length of its call)"""
+    from unittest import mock
+    own = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    own.add_argument("--items_per_batch", type=int, default=1,
+                     help="consecutive items of equal length that share ONE sampler call per group - all their guided scales and samples as "
+                          "rows of one batch, decoded and vocoded on the device; the files are byte-identical to the per-item loop's "
+                          "(default 1: that loop's calls).  items x guided scales x n_samples may not exceed 32 rows")
+    own.add_argument("--synthetic_frames", type=str, default="1500",
+                     help="mel frames of a synthetic item: one integer, or a comma list that cycles over the items (150,150,230)")
+    argv = list(sys.argv[1:] if argv is None else argv)
+    if "-h" in argv or "--help" in argv:
+        own.print_help()
+        print("\nand every flag of scripts/test_final.py:\n")
+    mine, rest = own.parse_known_args(argv)
+    with mock.patch.object(sys, "argv", [sys.argv[0]] + rest):
+        args = loop.parse_args()
+    args.items_per_batch, args.synthetic_frames = mine.items_per_batch, parse_frames(mine.synthetic_frames)
+    check_items_per_batch(args.items_per_batch, list(dict.fromkeys(_scales(args))), args.n_samples)
+    return args
+
+
+def _scales(args):
+    return [float(s) for s in args.scales.split("-")] if args.scales else [args.scale]
+
+
+class SyntheticDataset:
+    """test_final.py's synthetic items, item i with frames[i % len(frames)] mel frames"""
+
+    def __init__(self, n, frames, seed):
+        self.n, self.frames, self.seed = n, [int(f) for f in frames], seed
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        return loop.SyntheticDataset(self.n, self.frames[i % len(self.frames)], self.seed)[i]
+
+
+def _item_conditioning(sampler, item, n, device, guided):
+    """the conditioning of one item's n samples as the per-item loop builds it: (cond, uncond or None)"""
+    midi, beats, acoustic = item["midi"].to(device), item["beats"].to(device), item["acoustic"].to(device)
+    cap = item["caption"]
+    cond_in = {"caption": torch.stack([cap] * n) if torch.is_tensor(cap) else [cap] * n,
+               "acoustic": {"acoustic": torch.stack([acoustic] * n), "midi": torch.stack([midi] * n).long(),
+                            "beats": torch.stack([beats] * n).long()}, "name": [item["name"]] * n}
+    c = sampler.model.get_learned_conditioning(cond_in)
+    uc = None
+    if guided:
+        ucap = item.get("uncond_caption", "")
+        uc_in = dict(cond_in)
+        uc_in["caption"] = torch.stack([ucap] * n) if torch.is_tensor(ucap) else [ucap] * n
+        uc = sampler.model.get_learned_conditioning(uc_in)
+    return c, uc
+
+
+def _cat_conditioning(parts):
+    """row-wise concatenation of learned conditionings (caption embeddings, index tracks, names)"""
+    return {"caption": torch.cat([c["caption"] for c in parts]),
+            "acoustic": {k: torch.cat([c["acoustic"][k] for c in parts]) for k in ("acoustic", "midi", "beats")},
+            "name": [nm for c in parts for nm in c["name"]]}
+
+
+def sample_group(args, sampler, vocoder, group, scales, device):
+    """the sampler calls of harness.plan_row_batches for ONE group of same-length items: group = [(global index, item)].  A row is what
+    test_final.py computes for (item, scale, sample): the item's conditioning and start noise (the same for every scale of an item), its
+    own guidance scale and its global clip index gi * n_samples + k as noise key - so the rows, and after the batched decode and vocoder
+    the files, equal the loop's.  Returns {(position in the group, scale): [(mel [80,T], wav numpy)] per sample}."""
+    n = args.n_samples
+    embed_dim = sampler.model.first_stage_model.embed_dim
+    indices, items = [gi for gi, _ in group], [it for _, it in group]
+    lengths = [int(it["acoustic"].shape[1] / MEL_DOWNSAMPLE) for it in items]
+    has_guided = any(s != 1.0 for s in scales)
+    conds = [_item_conditioning(sampler, it, n, device, has_guided) for it in items]
+    starts = [torch.randn(n, embed_dim, lengths[p], generator=torch.Generator().manual_seed(args.seed + gi)).to(device) for p, gi in enumerate(indices)]
+    generated = {}
+    for call in plan_row_batches(lengths, list(dict.fromkeys(scales)), n, args.items_per_batch, indices):
+        rows = call["rows"]
+        runs = [(p, s) for p, s, k in rows if k == 0]                          # rows come as runs of n samples of one (item, scale)
+        c = _cat_conditioning([conds[p][0] for p, _ in runs])
+        uc = _cat_conditioning([conds[p][1] for p, _ in runs]) if call["n_branch"] == 2 else None
+        x = torch.cat([starts[p] for p, _ in runs])
+        scale = [s for _, s, _ in rows] if call["n_branch"] == 2 else 1.0
+        z, _ = sampler.sample_cfg(cond=c, unconditional_guidance_scale=scale, unconditional_conditioning=uc, batch_size=len(rows),
+                                  shape=[embed_dim, call["length"]], x_latent=x, timesteps=args.ddim_steps + 1, seed=args.seed,
+                                  clip_ids=call["clip_ids"])
+        mel = sampler.model.decode_first_stage(z)
+        wav = vocoder.spec2wav_batch(mel).cpu().numpy()
+        for r, (p, s, k) in enumerate(rows):
+            generated.setdefault((p, s), []).append((mel[r], wav[r]))
+    return generated
+
+
+def write_item(args, rank, item_idx, item, scales, generated, rows, mel_rows, mel_net):
+    """the files of one item in the per-item loop's order and under its names (test_final.py: gen_song, reference :424-457)"""
+    cap = item["caption"]
+    gt_vocal, gt_accomp = loop._load_ground_truth(item)
+    for scale in scales:
+        out_dir = os.path.join(args.save_dir, f"cond_gtcodec_accomp_scale_{scale}")
+        for k, (spec, wav) in enumerate(generated[scale]):
+            stem = os.path.join(out_dir, f"{rank}-{item_idx:04d}[{k}]")
+            wav = normalize_loudness(wav, -23)
+            if gt_vocal is not None:
+                min_length = min(wav.shape[0], gt_vocal.shape[0])
+                wav = wav[:min_length]
+                gt_vocal = normalize_loudness(gt_vocal, -23)[:min_length]
+                gt_accomp = normalize_loudness(gt_accomp, -23)
+                write_wav_pcm16(stem + "[gt_vocal].wav", gt_vocal, args.sample_rate)
+                write_wav_pcm16(stem + "[song].wav", wav[:min_length] + gt_vocal[:min_length], args.sample_rate)
+                write_wav_pcm16(stem + "[gt_accomp].wav", gt_accomp, args.sample_rate)
+            write_wav_pcm16(stem + "[accomp].wav", wav, args.sample_rate)
+            rows.append({"audio_path": stem + "[accomp].wav", "caption": cap if isinstance(cap, str) else item["name"], "name": item["name"]})
+            if mel_net is not None:
+                back = mel_net(np.asarray(wav, dtype=np.float32))[0]
+                f = min(back.shape[1], spec.shape[1])
+                d = back[:, :f] - spec[:, :f].to(back.device)
+                row = {"name": item["name"], "scale": scale, "sample": k, "mel_l1_vs_decoded": float((d - d.mean()).abs().mean())}
+                if gt_accomp is not None:
+                    ref = mel_net(np.asarray(gt_accomp, dtype=np.float32))[0]
+                    f = min(back.shape[1], ref.shape[1])
+                    row["mel_l1_vs_gt_accomp"] = float((back[:, :f] - ref[:, :f]).abs().mean())
+                mel_rows.append(row)
+
+
+@torch.no_grad()
+def gen_song(rank, args):
+    """gen_song of scripts/test_final.py, group by group: form a group, sample it, write its files, drop it"""
+    device = torch.device("cuda:0" if vdist.one_device() else f"cuda:{int(rank)}")
+    torch.cuda.set_device(device)
+    vdist.init(rank, args.num_gpus, device, master_port=args.master_port)
+    dataset = SyntheticDataset(args.synthetic, args.synthetic_frames, args.seed) if args.synthetic else \
+        InferDataset(args.manifest_path, args.other_condition, seed=args.seed)
+    if rank == 0 and not args.synthetic:
+        print("note: 'Musical:' caption sentences come from versband_amd.harness.CaptionGenerator2 - same facts, NOT the reference's wording (see --help)")
+    indices = vdist.shard_indices(len(dataset), rank, args.num_gpus)
+    sampler = loop.initialize_model(args, device, rank)
+    vocoder = loop.make_vocoder(args, device, os.path.join(args.save_dir, f".synthetic_vocoder_{rank}"), rank)
+    mel_net = None
+    if args.eval_mel:
+        from preprocess.NAT_mel import MelNet
+        mel_net = MelNet(loop.MEL_HPARAMS, device=device)
+    scales = _scales(args)
+    rows, mel_rows = [], []
+    item_idx = 0
+    loaded = ((gi, dataset[gi]) for gi in indices)                  # lazily, in shard order: an item is read when its group is formed
+    for group in stream_groups(loaded, lambda e: int(e[1]["acoustic"].shape[1] / MEL_DOWNSAMPLE), args.items_per_batch):
+        generated = sample_group(args, sampler, vocoder, group, scales, device)
+        for p, (gi, item) in enumerate(group):
+            write_item(args, rank, item_idx, item, scales, {s: generated[(p, s)] for s in scales}, rows, mel_rows, mel_net)
+            item_idx += 1
+        del generated                                               # the group's conditioning, start noise, mels and wavs end here
+    tag = "" if args.num_gpus == 1 else f".{rank}"
+    csv_path = os.path.join(args.save_dir, f"clap{tag}.csv")
+    save_rows_to_tsv(rows, ["audio_path", "caption", "name"], csv_path)
+    if mel_rows:
+        save_rows_to_tsv(mel_rows, ["name", "scale", "sample", "mel_l1_vs_decoded", "mel_l1_vs_gt_accomp"],
+                         os.path.join(args.save_dir, f"mel_l1{tag}.tsv"))
+    print(f"[rank {rank}] wrote {len(rows)} generated clips, {csv_path}")
+    if args.num_gpus > 1:
+        import torch.distributed as dist
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+if __name__ == "__main__":
+    args = parse_args()
+    if args.num_gpus > 1:
+        import torch.multiprocessing as mp
+        mp.spawn(gen_song, nprocs=args.num_gpus, args=(args,))
+    else:
+        gen_song(0, args=args)

@@ -64,6 +64,10 @@ class Keep(C.Structure):
     _fields_ = [("ref", c_void_p), ("x0", c_void_p), ("mask", c_void_p), ("t_next", c_void_p), ("sigma_min", c_float)]
 
 
+class Rows(C.Structure):
+    _fields_ = [("cfg_scale", c_void_p), ("clip", c_void_p)]
+
+
 class MelConfig(C.Structure):
     _fields_ = [("n_fft", c_int), ("hop", c_int), ("n_mels", c_int)]
 
@@ -108,6 +112,7 @@ PROTOTYPES = {
     "vb_euler_cfg_step": (c_int, [P, P, c_int, c_i64, c_float, c_float, c_int, P]),
     "vb_sample_cfg": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_float, C.POINTER(Noise), P, P, P]),
     "vb_sample_cfg_keep": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_float, C.POINTER(Keep), C.POINTER(Noise), P, P, P]),
+    "vb_sample_cfg_rows": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_float, C.POINTER(Rows), C.POINTER(Keep), C.POINTER(Noise), P, P, P]),
     "vb_sample_graphs": (c_int, [P]),
     "vb_net_load": (c_int, [P, c_int, C.POINTER(NetOp), c_int, C.POINTER(BufDesc), c_int, c_int, c_int, c_int, c_int]),
     "vb_net_workspace_bytes": (c_size_t, [P, c_int, c_int, c_int]),

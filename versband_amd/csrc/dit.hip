@@ -374,7 +374,7 @@ static int score_router_fused(const Eval& e, int i) {
     sr.la_rows = e.ev.B * e.ev.T; sr.hl = e.hl + i * 2; sr.hl_ld = e.hl_ld; sr.g1 = gn.g1; sr.g2 = gn.g2; sr.g3 = gn.g3; sr.Beff = e.Beff; sr.B = e.ev.B; sr.T = e.ev.T;
     sr.K = e.D; sr.NS = cd.NS; sr.Hh = e.c.heads; sr.E = e.E; sr.ic = s.ic; sr.ia = s.ia; sr.mc = s.mc; sr.ma = s.ma;
     sr.seed = noise ? noise->seed : 0; sr.clip_base = noise ? noise->clip_base : 0; sr.nfe_base = noise ? noise->nfe : 0;
-    sr.step = e.ev.step_ptr; sr.block = i;
+    sr.step = e.ev.step_ptr; sr.block = i; sr.clip_rows = e.ev.clip_rows;
     return launch_score_router(sr, e.st);
 }
 #endif
@@ -417,7 +417,7 @@ static int caption_gate_and_route(const Eval& e, int i) {
         r.cq = e.cqa; r.Wg = fold ? cd.vw[i] : bw.wcg; r.bg = bw.bcg; r.la = cd.la[i]; r.la_rows = B * T; r.hl = e.hl + i * 2; r.hl_ld = e.hl_ld;
         r.g1 = gn.g1; r.g2 = gn.g2; r.g3 = gn.g3; r.N = N; r.T = T; r.D = D; r.E = E; r.ic = s.ic; r.ia = s.ia; r.mc = s.mc; r.ma = s.ma; r.B = B;
         r.seed = noise ? noise->seed : 0; r.clip_base = noise ? noise->clip_base : 0; r.nfe_base = noise ? noise->nfe : 0;
-        r.step = e.ev.step_ptr; r.block = i; r.sc = fold ? s.y32 : nullptr; r.NS = cd.NS; r.Hh = c.heads;
+        r.step = e.ev.step_ptr; r.block = i; r.sc = fold ? s.y32 : nullptr; r.NS = cd.NS; r.Hh = c.heads; r.clip_rows = e.ev.clip_rows;
         r.cnt = e.p.router_counts ? e.counts(i) : nullptr; r.cnt_G = e.p.w2_pair ? E * E : 2 * E; r.cnt_pairs = e.p.w2_pair ? 1 : 0;
         VB_TRY(launch_router(r, e.st));
     }
@@ -488,7 +488,7 @@ static int final_layer(const Eval& e) {
     switch (e.p.final_route == FINAL_EULER_FUSED && !ef ? FINAL_FUSED : e.p.final_route) {
     case FINAL_EULER_FUSED:
         return launch_final_layer_euler(s.h, modf, modf + D, MODW, w.final_w, w.final_b, N, D, T, c.in_channels, 1e-6f, ef->x, ef->cfg_scale, ef->dt_table,
-                                        ef->k, ef->step, ef->t_idx_cur, ef->t_table, ef->n_steps, e.Beff, e.st, ef->keep);
+                                        ef->k, ef->step, ef->t_idx_cur, ef->t_table, ef->n_steps, e.Beff, e.st, ef->keep, ef->scale_rows);
     case FINAL_FUSED:
         // one wave per token row: LayerNorm + modulate in registers, the 768 x 20 projection against LDS-resident weights (exact fp32)
         return launch_final_layer_fused(s.h, modf, modf + D, MODW, w.final_w, w.final_b, N, D, T, c.in_channels, 1e-6f, v_out, e.st);

@@ -363,6 +363,47 @@ int launch_euler_cfg_keep(float* x, const float* v, int B, int64_t per, int T, f
     VB_CHECK_LAUNCH();
     return VB_OK;
 }
+// One guidance scale per clip (vb_sample_cfg_rows under VB_EULER_LAUNCH): clip b = i / per takes scale_rows[b].  Each kernel repeats the
+// expression of its scalar form above - they differ (a product and a sum there, fmaf in the keep form) and stay that way.
+__global__ void euler_cfg_rows_kernel(float* x, const float* __restrict__ v, int64_t n, int64_t per, const float* __restrict__ scale_rows,
+                                      const float* dt_table, const int* step) {
+    const float dt = dt_table[*step];
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float cfg_scale = scale_rows[i / per];
+    float e = v[i];
+    float eu = v[n + i];
+    e = eu + cfg_scale * (e - eu);
+    x[i] = x[i] + dt * e;
+}
+int launch_euler_cfg_rows(float* x, const float* v, int B, int64_t per, const float* scale_rows, const float* dt_table, const int* step, hipStream_t st) {
+    int64_t n = (int64_t)B * per;
+    hipLaunchKernelGGL(euler_cfg_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, v, n, per, scale_rows, dt_table, step);
+    VB_CHECK_LAUNCH();
+    return VB_OK;
+}
+__global__ void euler_cfg_keep_rows_kernel(float* x, const float* __restrict__ v, int64_t n, int64_t per, int T, const float* __restrict__ scale_rows,
+                                           const float* dt_table, const int* step, const EulerKeep kp) {
+    const int k = *step;
+    const float dt = dt_table[k], tn = kp.tn_table[k];
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t b = i / per;
+    float e = v[i];
+    float eu = v[n + i];
+    e = fmaf(scale_rows[b], e - eu, eu);
+    const float xn = fmaf(dt, e, x[i]);
+    const float m = kp.mask[b * T + (i - b * per) % T];
+    x[i] = keep_blend(m, keep_path(tn, kp.sigma_min, kp.ref[i], kp.x0[i]), xn);
+}
+int launch_euler_cfg_keep_rows(float* x, const float* v, int B, int64_t per, int T, const float* scale_rows, const float* dt_table, const int* step,
+                               const EulerKeep& keep, hipStream_t st) {
+    int64_t n = (int64_t)B * per;
+    hipLaunchKernelGGL(euler_cfg_keep_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, v, n, per, T, scale_rows, dt_table,
+                       step, keep);
+    VB_CHECK_LAUNCH();
+    return VB_OK;
+}
 // known region on entry: the state a call starts from is put on the path at t_0 = tn_table[0] - dt_table[0] (exact for a linspace
 // grid: the difference of neighbouring grid points is); a no-op at t_0 = 0 with x = x0
 __global__ void keep_project_kernel(float* x, int64_t n, int64_t per, int T, const float* dt_table, const EulerKeep kp) {
@@ -810,6 +851,7 @@ int launch_conv_w_to_gemm(const bf16_t* w3, int64_t w3_plane, int taps, int D, i
 }
 
 // element (row n = (branch*B + b)*T + t, e) of stream (seed, clip_base + b, nfe, branch, block, gate)
+// (vb_fill_gumbel only: not on the sampler's path, whose router draws inside router_phase_b - so it takes no per-row clip ids)
 __global__ void fill_gumbel_kernel(float* out, int B, int n_branch, int T, int width, uint64_t seed, int64_t clip_base,
                                    int nfe_base, const int* step, int block, int gate) {
     const int64_t n_el = (int64_t)n_branch * B * T * width;

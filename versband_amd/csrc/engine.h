@@ -21,7 +21,8 @@ struct SampleGraph {
         int B = 0, nb = 0, T = 0, L = 0, n_steps = 0; float cfg_scale = 0.f;
         unsigned tune_gen = 0;            // a captured graph bakes the knob-dependent kernel selection in
         const void* keep_ref = nullptr; const void* keep_x0 = nullptr; const void* keep_mask = nullptr; float sigma_min = 0.f;   // vb_sample_cfg_keep (all null: a plain call)
-        auto tie() const { return std::tie(x, cond, ws, B, nb, T, L, n_steps, cfg_scale, tune_gen, keep_ref, keep_x0, keep_mask, sigma_min); }
+        const void* rows_scale = nullptr; const void* rows_clip = nullptr;   // vb_sample_cfg_rows: the two POINTERS (cfg_scale is 0 beside rows_scale); their contents are read when the kernels run
+        auto tie() const { return std::tie(x, cond, ws, B, nb, T, L, n_steps, cfg_scale, tune_gen, keep_ref, keep_x0, keep_mask, sigma_min, rows_scale, rows_clip); }
         bool operator==(const Key& o) const { return tie() == o.tie(); }
     } key;
     int seen = 0;                         // calls with this key so far (the first runs eagerly, the second captures)
@@ -124,12 +125,14 @@ struct DitPlan {
 DitPlan dit_plan(const vb_ctx* ctx, int B, int nb, int T, int L);
 
 // sampler only: FinalLayer + CFG + Euler update + step advance as one launch (launch_final_layer_euler) - x is updated in place, v is not written
-struct EulerFuse { float* x; float cfg_scale; const float* dt_table; int k; int* step; int64_t* t_idx_cur; const int64_t* t_table; int n_steps; const EulerKeep* keep; };
+// (scale_rows: per-clip guidance scales of vb_sample_cfg_rows, device [B]; null = cfg_scale for every clip)
+struct EulerFuse { float* x; float cfg_scale; const float* dt_table; int k; int* step; int64_t* t_idx_cur; const int64_t* t_table; int n_steps; const EulerKeep* keep; const float* scale_rows; };
 // one network evaluation (both CFG branches batched: rows [0,B) cond, [B,2B) uncond); a caller fills what it uses
 struct DitEval {
     const float* x = nullptr; const int64_t* t_idx = nullptr; const void* cond = nullptr; void* ws = nullptr;
     int B = 0, nb = 0, T = 0, L = 0;
     const vb_noise* noise = nullptr; int noise_step = 0; const int* step_ptr = nullptr;
+    const int64_t* clip_rows = nullptr;                         // vb_sample_cfg_rows: device [B] global clip ids of the router noise (null: noise->clip_base + b)
     float* v_out = nullptr; int32_t* route_out = nullptr;
     bool zero_vt = false;                                       // clear the padded V^T planes first (a stand-alone call)
     const float* pre_mod = nullptr; const float* pre_hl = nullptr;   // this step's rows of the sampler's tabulated conditioning vectors

@@ -203,12 +203,20 @@ struct EulerKeep { const float* ref; const float* x0; const float* mask; const f
 // (keep != nullptr: the known tokens are put back on the probability path in the same launch - common.h:keep_path / keep_blend)
 int launch_final_layer_euler(const float* h, const float* shift, const float* scale, int mod_ld, const float* W, const float* bias,
                              int rows, int D, int T, int C, float eps, float* x, float cfg_scale, const float* dt_table, int k, int* step,
-                             int64_t* t_idx_cur, const int64_t* t_table, int n_steps, int Beff, hipStream_t st, const EulerKeep* keep = nullptr);
+                             int64_t* t_idx_cur, const int64_t* t_table, int n_steps, int Beff, hipStream_t st, const EulerKeep* keep = nullptr,
+                             const float* scale_rows = nullptr);
+// (scale_rows != nullptr, vb_sample_cfg_rows: device [B] guidance scales, token row m of clip b takes scale_rows[b] and cfg_scale is unused -
+//  instances of their own, the scalar ones keep their arguments)
 int launch_euler_cfg(float* x, const float* v, int B, int64_t per, float cfg_scale, const float* dt_table, const int* step,
                      float dt_val, int has_uncond, hipStream_t st);
 // the Euler + guidance update of launch_euler_cfg followed by the known-region blend at t = tn_table[*step] (x [B][C][T], per = C * T)
 int launch_euler_cfg_keep(float* x, const float* v, int B, int64_t per, int T, float cfg_scale, const float* dt_table, const int* step,
                           int has_uncond, const EulerKeep& keep, hipStream_t st);
+// the two updates above with one guidance scale per clip (scale_rows: device [B]; vb_sample_cfg_rows under VB_EULER_LAUNCH): each in the
+// arithmetic of its scalar form
+int launch_euler_cfg_rows(float* x, const float* v, int B, int64_t per, const float* scale_rows, const float* dt_table, const int* step, hipStream_t st);
+int launch_euler_cfg_keep_rows(float* x, const float* v, int B, int64_t per, int T, const float* scale_rows, const float* dt_table, const int* step,
+                               const EulerKeep& keep, hipStream_t st);
 // projection on entry: x <- blend(mask, r(t_0), x) with t_0 = tn_table[0] - dt_table[0]
 int launch_keep_project(float* x, int B, int64_t per, int T, const float* dt_table, const EulerKeep& keep, hipStream_t st);
 // Band-MoE router: call arguments and the kernel's argument block in one (the device side is router_dev.h).
@@ -221,6 +229,8 @@ struct RouterDev {
     const float* g1 = nullptr; const float* g2 = nullptr; const float* g3 = nullptr; int N = 0, T = 0, D = 0, E = 0;
     int* ic = nullptr; int* ia = nullptr; float* mc = nullptr; float* ma = nullptr; float* lc_out = nullptr; int B = 0;
     uint64_t seed = 0; int64_t clip_base = 0; int nfe_base = 0; const int* step = nullptr; int block = 0; const float* sc = nullptr; int NS = 0, Hh = 1;
+    // vb_sample_cfg_rows: device [B] global clip ids - row b of every branch draws from the stream of clip clip_rows[b] instead of clip_base + b
+    const int64_t* clip_rows = nullptr;
     // bucket counts as a side product (round 5): cnt[(n / RT_CNT_BLOCK) * cnt_G + group] += 1 for the token's expert pair (cnt_pairs) or its two
     // expert groups - what bucket_count_kernel computed in a launch of its own; the table must be zero on entry (launch_bucket's place kernel
     // clears the table of the NEXT launch).  Integer atomics: the sums do not depend on their order.
@@ -240,6 +250,7 @@ struct ScoreRouterArgs {
     int Beff = 0, B = 0, T = 0, K = 0, NS = 0, Hh = 1, E = 0;
     int* ic = nullptr; int* ia = nullptr; float* mc = nullptr; float* ma = nullptr;
     uint64_t seed = 0; int64_t clip_base = 0; int nfe_base = 0; const int* step = nullptr; int block = 0;
+    const int64_t* clip_rows = nullptr;              // as RouterDev::clip_rows
 };
 bool score_router_supported(int NS, int K, int E, int Hh);
 int launch_score_router(const ScoreRouterArgs& a, hipStream_t st);

@@ -76,6 +76,7 @@ __device__ __forceinline__ void router_phase_b(const RouterDev& a, const int n0,
     const int T = a.T, E = a.E, B = a.B, block = a.block;
     int* ic = a.ic; int* ia = a.ia; float* mc = a.mc; float* ma = a.ma; float* lc_out = a.lc_out;
     uint64_t seed = a.seed; int64_t clip_base = a.clip_base; int nfe_base = a.nfe_base; const int* step = a.step;
+    const int64_t* __restrict__ clip_rows = a.clip_rows;
     const int lane = threadIdx.x & 63;
     constexpr int SPT = 64 / PP;
     const bool gen = g1 == nullptr;
@@ -94,7 +95,7 @@ __device__ __forceinline__ void router_phase_b(const RouterDev& a, const int n0,
         const int nn = valid ? n : N - 1;
         const int bb = nn / T, tt = nn - bb * T;
         const int branch = bb / B;
-        const int64_t clip = clip_base + (bb - branch * B);
+        const int64_t clip = clip_rows ? clip_rows[bb - branch * B] : clip_base + (bb - branch * B);     // (vb_sample_cfg_rows: the row's own global clip)
         const int gate = sl < E ? 1 : (sl < 2 * E ? 2 : 0);
         const int slot = sl < E ? sl : (sl < 2 * E ? sl - E : sl - 2 * E);
         // this lane's side input: caption gate bias / acoustic gate logit / high-level gate logit; and its noise value

@@ -151,12 +151,20 @@ struct FinalEuler { float* x; float cfg_scale; const float* dt_table; int k; int
 // (common.h:keep_path / keep_blend; three more loads per output element) - a third instance with its own argument block, so the other
 // two keep their kernel arguments and compile to the code they had.
 struct FinalEulerKeep : FinalEuler { EulerKeep kp; };
-template <int NQ, bool EUL = false, bool KEEP = false>      // D = 256 * NQ
+// ROWS (vb_sample_cfg_rows): one guidance scale per clip, scale_rows[b] read per TOKEN - a wave's two tokens belong to different clips
+// when T is odd; one more 4-byte load per output row.  Two more instances (plain / keep) with their own argument blocks: the three above
+// keep their kernel arguments and compile to the code they had.
+struct FinalEulerRows : FinalEuler { const float* scale_rows; };
+struct FinalEulerKeepRows : FinalEulerKeep { const float* scale_rows; };
+template <bool KEEP, bool ROWS>
+using FinalEulerArgs = std::conditional_t<ROWS, std::conditional_t<KEEP, FinalEulerKeepRows, FinalEulerRows>, std::conditional_t<KEEP, FinalEulerKeep, FinalEuler>>;
+template <int NQ, bool EUL = false, bool KEEP = false, bool ROWS = false>      // D = 256 * NQ
 __global__ void __launch_bounds__(256) final_layer_kernel(const float* __restrict__ h, const float* __restrict__ shift,
                                                          const float* __restrict__ scale, int mod_ld, const float* __restrict__ W,
                                                          const float* __restrict__ bias, int rows, int T, int C, float eps, float* out,
-                                                         const std::conditional_t<KEEP, FinalEulerKeep, FinalEuler> fe) {
+                                                         const FinalEulerArgs<KEEP, ROWS> fe) {
     static_assert(EUL || !KEEP, "the known-region blend belongs to the Euler update");
+    static_assert(EUL || !ROWS, "the guidance scales belong to the Euler update");
     constexpr int D = 256 * NQ;
     extern __shared__ __attribute__((aligned(16))) float wl[];      // [C][D]
     for (int id = threadIdx.x * 4; id < C * D; id += 1024) *reinterpret_cast<float4*>(wl + id) = *reinterpret_cast<const float4*>(W + id);
@@ -232,7 +240,9 @@ __global__ void __launch_bounds__(256) final_layer_kernel(const float* __restric
                 for (int j = 0; j < 2; ++j)
                     if (row0 + j < half) {
                         const float vc = res[j] + bv, vu = res[2 + j] + bv;
-                        const float e = fmaf(fe.cfg_scale, vc - vu, vu);
+                        float sb = fe.cfg_scale;
+                        if constexpr (ROWS) sb = fe.scale_rows[bb[j]];      // (bb[j] < B: rows 0 / 1 of the group are tokens of the conditional half)
+                        const float e = fmaf(sb, vc - vu, vu);
                         float* xp = fe.x + ((int64_t)bb[j] * C + lane) * T + tt[j];
                         if constexpr (KEEP) {
                             const int64_t xi = xp - fe.x;
@@ -278,14 +288,31 @@ int launch_final_layer_fused(const float* h, const float* shift, const float* sc
 // FinalLayer + CFG + Euler update + step advance in one launch (see FinalEuler): rows = 2 x (B T) token rows, conditional half first
 int launch_final_layer_euler(const float* h, const float* shift, const float* scale, int mod_ld, const float* W, const float* bias,
                              int rows, int D, int T, int C, float eps, float* x, float cfg_scale, const float* dt_table, int k, int* step,
-                             int64_t* t_idx_cur, const int64_t* t_table, int n_steps, int Beff, hipStream_t st, const EulerKeep* keep) {
+                             int64_t* t_idx_cur, const int64_t* t_table, int n_steps, int Beff, hipStream_t st, const EulerKeep* keep,
+                             const float* scale_rows) {
     if (!final_layer_fused_ok(D, C) || (rows & 1) || !x || !dt_table) VB_FAIL(VB_E_INVALID, "final_layer_euler: D=%d C=%d rows=%d unsupported", D, C, rows);
     const size_t sh = (size_t)C * D * sizeof(float);
     const int grid = min(cdiv(rows / 2, 8), 512);
     FinalEuler fe{x, cfg_scale, dt_table, k, step, t_idx_cur, t_table, n_steps, Beff};
-    static OnceFlags attr[4], attr_keep[4];
+    static OnceFlags attr[4], attr_keep[4], attr_rows[4], attr_keep_rows[4];
     auto go = [&](auto nq) {
         constexpr int NQ = decltype(nq)::value;
+        if (scale_rows && keep) {
+            FinalEulerKeepRows fekr;
+            static_cast<FinalEuler&>(fekr) = fe; fekr.kp = *keep; fekr.scale_rows = scale_rows;
+            vb_set_max_lds_once(attr_keep_rows[NQ - 1], reinterpret_cast<const void*>(final_layer_kernel<NQ, true, true, true>), 96 * 1024);
+            hipLaunchKernelGGL((final_layer_kernel<NQ, true, true, true>), dim3(grid), dim3(256), sh, st, h, shift, scale, mod_ld, W, bias, rows, T > 0 ? T : 1, C,
+                               eps, (float*)nullptr, fekr);
+            return;
+        }
+        if (scale_rows) {
+            FinalEulerRows fer;
+            static_cast<FinalEuler&>(fer) = fe; fer.scale_rows = scale_rows;
+            vb_set_max_lds_once(attr_rows[NQ - 1], reinterpret_cast<const void*>(final_layer_kernel<NQ, true, false, true>), 96 * 1024);
+            hipLaunchKernelGGL((final_layer_kernel<NQ, true, false, true>), dim3(grid), dim3(256), sh, st, h, shift, scale, mod_ld, W, bias, rows, T > 0 ? T : 1, C,
+                               eps, (float*)nullptr, fer);
+            return;
+        }
         if (keep) {
             FinalEulerKeep fek;
             static_cast<FinalEuler&>(fek) = fe; fek.kp = *keep;

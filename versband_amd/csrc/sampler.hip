@@ -4,8 +4,9 @@
 // the launches of one sampler call after its tables are in place: tabulation of the per-step conditioning vectors, then n_steps x
 // [step bookkeeping, one network evaluation of both CFG branches, Euler + guidance update]   (cfm1_audio_sampler.py:107-116)
 // keep != nullptr (vb_sample_cfg_keep): every update also puts the known tokens back on the probability path at the time after the step
+// rows (vb_sample_cfg_rows; either member may be null): clip b is guided by rows.cfg_scale[b] and draws its router noise as clip rows.clip[b]
 static int sample_steps(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps, float cfg_scale,
-                        const vb_keep* keep, const vb_noise* noise, float* traj, void* ws, hipStream_t st) {
+                        const vb_rows& rows, const vb_keep* keep, const vb_noise* noise, float* traj, void* ws, hipStream_t st) {
     const vb_dit_config& c = ctx->cfg;
     const DitPlan plan = dit_plan(ctx, B, n_branch, T, L);
     WsL s = carve_ws(ws, c, B, n_branch, T, L);
@@ -51,15 +52,19 @@ static int sample_steps(vb_ctx* ctx, float* x, const void* cond, int B, int n_br
     for (int k = 0; k < n_steps; ++k) {
         RoctxRange rs("euler_step");
         if (!fuse || k == 0) VB_TRY(launch_step_ctl(s.step, s.t_idx_cur, s.t_table, n_steps, Beff, k == 0, st));
-        EulerFuse ef{x, cfg_scale, s.dt_table, k, s.step, s.t_idx_cur, s.t_table, n_steps, keep ? &kp : nullptr};
+        EulerFuse ef{x, cfg_scale, s.dt_table, k, s.step, s.t_idx_cur, s.t_table, n_steps, keep ? &kp : nullptr, rows.cfg_scale};
         DitEval ev;
         ev.x = x; ev.t_idx = s.t_idx_cur; ev.cond = cond; ev.ws = ws; ev.B = B; ev.nb = n_branch; ev.T = T; ev.L = L;
-        ev.noise = noise; ev.noise_step = k; ev.step_ptr = s.step; ev.v_out = s.v;
+        ev.noise = noise; ev.noise_step = k; ev.step_ptr = s.step; ev.v_out = s.v; ev.clip_rows = rows.clip;
         if (tab) { ev.pre_mod = s.mod_s + (size_t)k * Beff * MODW; ev.pre_hl = s.hl_s + (size_t)k * c.depth * 2; }
         ev.evals_before = k * c.depth;
         if (fuse) ev.euler = &ef;
         VB_TRY(dit_forward(ctx, ev, st));
-        if (!fuse && keep) VB_TRY(launch_euler_cfg_keep(x, s.v, B, per, T, cfg_scale, s.dt_table, s.step, n_branch == 2, kp, st));
+        // (one branch: there is nothing to guide, the scales are unused)
+        const bool scale_rows = rows.cfg_scale && n_branch == 2;
+        if (!fuse && keep && scale_rows) VB_TRY(launch_euler_cfg_keep_rows(x, s.v, B, per, T, rows.cfg_scale, s.dt_table, s.step, kp, st));
+        else if (!fuse && scale_rows) VB_TRY(launch_euler_cfg_rows(x, s.v, B, per, rows.cfg_scale, s.dt_table, s.step, st));
+        else if (!fuse && keep) VB_TRY(launch_euler_cfg_keep(x, s.v, B, per, T, cfg_scale, s.dt_table, s.step, n_branch == 2, kp, st));
         else if (!fuse) VB_TRY(launch_euler_cfg(x, s.v, B, per, cfg_scale, s.dt_table, s.step, 0.f, n_branch == 2, st));
         if (traj) VB_HIP(hipMemcpyAsync(traj + (size_t)(k + 1) * B * per, x, (size_t)B * per * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
@@ -95,11 +100,18 @@ int vb_euler_cfg_step(float* x, const float* v, int B, int64_t per_item, float c
 int vb_sample_cfg(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
                   const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_noise* noise, float* traj, void* ws,
                   void* stream) {
-    return vb_sample_cfg_keep(ctx, x, cond, B, n_branch, T, L, n_steps, t_idx_table, dt_table, cfg_scale, nullptr, noise, traj, ws, stream);
+    return vb_sample_cfg_rows(ctx, x, cond, B, n_branch, T, L, n_steps, t_idx_table, dt_table, cfg_scale, nullptr, nullptr, noise, traj, ws, stream);
 }
 int vb_sample_cfg_keep(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
                        const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_keep* keep, const vb_noise* noise,
                        float* traj, void* ws, void* stream) {
+    return vb_sample_cfg_rows(ctx, x, cond, B, n_branch, T, L, n_steps, t_idx_table, dt_table, cfg_scale, nullptr, keep, noise, traj, ws, stream);
+}
+int vb_sample_cfg_rows(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
+                       const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_rows* rows_in, const vb_keep* keep,
+                       const vb_noise* noise, float* traj, void* ws, void* stream) {
+    const vb_rows rows = rows_in ? *rows_in : vb_rows{nullptr, nullptr};
+    if (rows.cfg_scale) cfg_scale = 0.f;          // unused beside the array; one value in the graph key
     if (!ctx || !ctx->dit_loaded) VB_FAIL(VB_E_STATE, "sample_cfg: DiT not loaded");
     if (n_steps < 1 || n_steps > 1024) VB_FAIL(VB_E_INVALID, "sample_cfg: n_steps=%d", n_steps);
     if (keep && (!keep->ref || !keep->x0 || !keep->mask || !keep->t_next)) VB_FAIL(VB_E_INVALID, "sample_cfg_keep: ref, x0, mask and t_next must all be given");
@@ -134,10 +146,11 @@ int vb_sample_cfg_keep(vb_ctx* ctx, float* x, const void* cond, int B, int n_bra
         key.x = x; key.cond = cond; key.ws = ws; key.B = B; key.nb = n_branch; key.T = T; key.L = L; key.n_steps = n_steps; key.cfg_scale = cfg_scale;
         key.tune_gen = vb_tune_generation();
         if (keep) { key.keep_ref = keep->ref; key.keep_x0 = keep->x0; key.keep_mask = keep->mask; key.sigma_min = keep->sigma_min; }
+        key.rows_scale = rows.cfg_scale; key.rows_clip = rows.clip;
         SampleGraph* e = graph_entry(ctx, key);
         if (!e->exec && !e->failed && e->seen >= 2) {
             if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                const int rc = sample_steps(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, keep, noise, nullptr, ws, st);
+                const int rc = sample_steps(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, rows, keep, noise, nullptr, ws, st);
                 hipGraph_t gr = nullptr;
                 const hipError_t ee = hipStreamEndCapture(st, &gr);
                 if (rc == VB_OK && ee == hipSuccess && gr && hipGraphInstantiate(&e->exec, gr, nullptr, nullptr, 0) == hipSuccess) {
@@ -157,7 +170,7 @@ int vb_sample_cfg_keep(vb_ctx* ctx, float* x, const void* cond, int B, int n_bra
             return VB_OK;
         }
     }
-    return sample_steps(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, keep, noise, traj, ws, st);
+    return sample_steps(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, rows, keep, noise, traj, ws, st);
 }
 int vb_sample_graphs(vb_ctx* ctx) {
     int n = 0;

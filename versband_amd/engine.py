@@ -93,6 +93,7 @@ class DiTEngine:
         self._tables: Dict[tuple, Tuple[Tensor, Tensor]] = {}    # device copies of the (t_idx, dt) step tables
         self._pcond: Dict[tuple, list] = {}                      # persistent conditioning buffers: key -> [buffer, generation]
         self._xbuf: Dict[tuple, Tensor] = {}                     # engine-owned sampler state (stable address for graph replay)
+        self._rowbuf: Dict[tuple, Tensor] = {}                   # staged per-row scales / clip ids: (B, kind) -> device tensor (stable address)
 
     # -- buffers -----------------------------------------------------------
     def _workspace(self, B, nb, T, Lc) -> Tensor:
@@ -226,13 +227,75 @@ class DiTEngine:
         ks = L.Keep(ref.data_ptr(), x0k.data_ptr(), mask.data_ptr(), tn.data_ptr(), float(sigma_min))
         return ks, (ref, x0k, mask, tn)
 
-    def sample_cfg(self, x0: Tensor, cond: dict, t_idx_table: Sequence[int], dt_table: Sequence[float], scale: float,
-                   noise=None, seed: int = 0, clip_base: int = 0, return_traj: bool = False, keep=None):
+    def _rows_struct(self, scale, clip_ids, B: int, clip_base: int = 0):
+        """validate per-row guidance scales / global clip ids and lay them out as vb_rows.  A conforming device tensor (float32 / int64,
+        [B], contiguous, on the engine's device) is passed as it is - its address keys the captured graph, as with `keep`; host values are
+        staged into an engine-owned device buffer reused per (B, kind), so repeated calls replay.  Host values are checked for finiteness;
+        a device tensor is not read here (that would be a device-to-host sync in front of every replay): its contents are the caller's
+        contract.  A plain number as `scale` is today's scalar path (no array).  Returns (struct or None, scalar scale, references to hold)."""
+        dev = self.ctx.device
+        held = []
+
+        def rows(name, v, dtype, kind):
+            if torch.is_tensor(v):
+                if v.dtype != dtype:
+                    raise TypeError(f"{name} must be {str(dtype).replace('torch.', '')}, got {str(v.dtype).replace('torch.', '')}")
+                if v.dim() != 1 or v.numel() != B:
+                    raise ValueError(f"{name} has shape {tuple(v.shape)}, expected ({B},)")
+                if v.device.type != "cpu" and v.device != dev:
+                    raise ValueError(f"{name} lives on {v.device}, the engine on {dev}")
+                if v.device == dev and v.is_contiguous():       # (not read here: no device-to-host sync on the replay path)
+                    held.append(v)
+                    return v
+                if kind == "scale" and v.device.type == "cpu" and not bool(torch.isfinite(v).all()):
+                    raise ValueError(f"{name} must be finite")
+                vals = v
+            else:
+                try:
+                    vals = list(v)
+                except TypeError:
+                    what = "a number, a sequence or a float32 tensor" if kind == "scale" else "a sequence or an int64 tensor"
+                    raise TypeError(f"{name} must be {what} of {B} values, got {type(v).__name__}") from None
+                if len(vals) != B:
+                    raise ValueError(f"{name} has {len(vals)} entries for {B} rows")
+                if kind == "scale":
+                    if any(isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)) for s in vals):
+                        raise TypeError(f"{name} must hold numbers")
+                    if not all(np.isfinite(float(s)) for s in vals):
+                        raise ValueError(f"{name} must be finite")
+                    vals = torch.tensor([float(s) for s in vals], dtype=torch.float32)
+                else:
+                    if any(isinstance(s, bool) or not isinstance(s, (int, np.integer)) for s in vals):
+                        raise TypeError(f"{name} must hold integers")
+                    vals = torch.tensor([int(s) for s in vals], dtype=torch.int64)
+            key = (B, kind)
+            if key not in self._rowbuf:
+                self._rowbuf[key] = torch.empty(B, dtype=dtype, device=dev)
+            self._rowbuf[key].copy_(vals)
+            return self._rowbuf[key]
+
+        s_rows = c_rows = None
+        if isinstance(scale, bool) or not isinstance(scale, (int, float, np.integer, np.floating)):
+            s_rows = rows("scale", scale, torch.float32, "scale")
+        if clip_ids is not None:
+            if clip_base:
+                raise ValueError("clip_ids and a non-zero clip_base do not go together: the ids are global clip indices")
+            c_rows = rows("clip_ids", clip_ids, torch.int64, "clip")
+        if s_rows is None and c_rows is None:
+            return None, float(scale), held
+        rs = L.Rows(s_rows.data_ptr() if s_rows is not None else None, c_rows.data_ptr() if c_rows is not None else None)
+        return rs, 0.0 if s_rows is not None else float(scale), held + [s_rows, c_rows]
+
+    def sample_cfg(self, x0: Tensor, cond: dict, t_idx_table: Sequence[int], dt_table: Sequence[float], scale,
+                   noise=None, seed: int = 0, clip_base: int = 0, return_traj: bool = False, keep=None, clip_ids=None):
         """n Euler steps with classifier-free guidance; x0 [B,C,T] is not modified.
+        scale: one number for the batch, or B values (sequence / float32 tensor): row b is guided by scale[b].  clip_ids: B global clip
+        indices (sequence / int64 tensor): row b draws its router noise as clip clip_ids[b] instead of clip_base + b (vb_sample_cfg_rows).
         keep = (ref [B,C,T], x0 [B,C,T], mask [B,T] in [0,1], t_next [n], sigma_min) or a dict of those names holds the masked tokens on
         the probability path t ref + (1 - (1 - sigma_min) t) x0 after every step (vb_sample_cfg_keep; t_next = model.euler_times)."""
         dev = self.ctx.device
         B, nb, T, Lc = cond["B"], cond["nb"], cond["T"], cond["L"]
+        rs, scale, held_rows = self._rows_struct(scale, clip_ids, B, clip_base)
         self._check_cond(cond)
         xkey = (B, self.cfg.in_channels, T)
         assert tuple(x0.shape) == xkey, (tuple(x0.shape), xkey)
@@ -250,7 +313,12 @@ class DiTEngine:
         traj = torch.empty(n + 1, *x.shape, dtype=torch.float32, device=dev) if return_traj else None
         ns, held = self._noise_struct(noise, seed, clip_base, 0)
         ws = self._workspace(B, nb, T, Lc)
-        if keep is None:
+        if rs is not None:
+            ks, held_keep = self._keep_struct(keep, B, T, n) if keep is not None else (None, None)
+            L.check(self.ctx.lib.vb_sample_cfg_rows(self.ctx.handle, L.ptr(x), L.ptr(cond["buf"]), B, nb, T, Lc, n, L.ptr(tt), L.ptr(dd),
+                                                    float(scale), C.byref(rs), C.byref(ks) if ks is not None else None, C.byref(ns),
+                                                    L.ptr(traj), L.ptr(ws), L.stream_ptr()), "vb_sample_cfg_rows")
+        elif keep is None:
             L.check(self.ctx.lib.vb_sample_cfg(self.ctx.handle, L.ptr(x), L.ptr(cond["buf"]), B, nb, T, Lc, n, L.ptr(tt), L.ptr(dd), float(scale),
                                                C.byref(ns), L.ptr(traj), L.ptr(ws), L.stream_ptr()), "vb_sample_cfg")
         else:

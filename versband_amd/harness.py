@@ -122,6 +122,81 @@ def write_wav_pcm16(path, wav, sr: int) -> None:
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# batching of the inference loop (scripts/infer_batched.py --items_per_batch)
+# ------------------------------------------------------------------------------------------------------------------
+MAX_ROWS_PER_CALL = 32          # rows of one batched sampler call (--items_per_batch is checked against it)
+
+
+def parse_frames(text) -> List[int]:
+    """--synthetic_frames: one integer (every item has that many mel frames, as always) or a comma list that cycles over the items"""
+    try:
+        frames = [int(v) for v in str(text).split(",")]
+    except ValueError:
+        raise ValueError(f"--synthetic_frames: expected an integer or a comma list of integers, got {text!r}") from None
+    if not frames or any(f < 1 for f in frames):
+        raise ValueError(f"--synthetic_frames: frame counts must be positive, got {text!r}")
+    return frames
+
+
+def check_items_per_batch(items_per_batch: int, scales, n_samples: int) -> None:
+    """the largest call of plan_row_batches must stay within MAX_ROWS_PER_CALL rows"""
+    guided = [s for s in scales if s != 1.0]
+    rows = items_per_batch * max(len(guided), 1) * n_samples
+    if items_per_batch < 1:
+        raise ValueError(f"--items_per_batch must be at least 1, got {items_per_batch}")
+    if items_per_batch > 1 and rows > MAX_ROWS_PER_CALL:
+        raise ValueError(f"--items_per_batch {items_per_batch} x {max(len(guided), 1)} guided scales x {n_samples} samples = {rows} rows per sampler "
+                         f"call; at most {MAX_ROWS_PER_CALL} fit (lower --items_per_batch to {max(1, MAX_ROWS_PER_CALL // (max(len(guided), 1) * n_samples))})")
+
+
+def stream_groups(items, length_of, items_per_batch: int):
+    """the grouping rule, incrementally: consecutive items of equal length, up to items_per_batch of them, as lists in the order given.
+    `items` may be a lazy iterable (the CLI loads a manifest item only when its group is formed); length_of(item) is its latent length."""
+    group = []
+    for it in items:
+        if group and (len(group) >= items_per_batch or length_of(it) != length_of(group[0])):
+            yield group
+            group = []
+        group.append(it)
+    if group:
+        yield group
+
+
+def plan_row_batches(lengths, scales, n_samples: int, items_per_batch: int, indices=None) -> List[dict]:
+    """The sampler calls of the inference loop as a list of
+        {"n_branch": 1 | 2, "length": latent length, "items": [positions], "rows": [(position, scale, sample)], "clip_ids": [...]}
+    lengths[p] is the latent length of the p-th item of this rank's shard, indices[p] its global index (default p); the global clip of a
+    row is indices[p] * n_samples + sample, whatever call and slot it rides in.
+    Consecutive items (shard order) of equal length form a group of up to items_per_batch items.  Per group there is ONE guided call
+    (n_branch = 2; rows = items x scales != 1.0 x samples, item-major, scales in the order given) and, where the scales hold 1.0, one
+    unguided call (n_branch = 1; rows = items x samples).  items_per_batch = 1 is the per-item loop as it always ran: one call per
+    (item, scale) in the order of `scales`, rows = the item's samples."""
+    check_items_per_batch(items_per_batch, scales, n_samples)
+    lengths = [int(v) for v in lengths]
+    indices = list(range(len(lengths))) if indices is None else [int(v) for v in indices]
+    if len(indices) != len(lengths):
+        raise ValueError(f"plan_row_batches: {len(lengths)} lengths for {len(indices)} indices")
+
+    def call(nb, items, row_scales):
+        rows = [(p, s, k) for p in items for s in row_scales for k in range(n_samples)]
+        return {"n_branch": nb, "length": lengths[items[0]], "items": list(items), "rows": rows,
+                "clip_ids": [indices[p] * n_samples + k for p, _, k in rows]}
+
+    calls = []
+    if items_per_batch == 1:
+        for p in range(len(lengths)):
+            calls += [call(1 if s == 1.0 else 2, [p], [s]) for s in scales]
+        return calls
+    guided = [s for s in scales if s != 1.0]
+    for items in stream_groups(range(len(lengths)), lengths.__getitem__, items_per_batch):
+        if guided:
+            calls.append(call(2, items, guided))
+        if len(guided) < len(scales):
+            calls.append(call(1, items, [1.0]))
+    return calls
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # caption text (the "Musical: ..." half of the prompt)
 # ------------------------------------------------------------------------------------------------------------------
 _PITCH_CLASSES = ["C", "C-sharp", "D", "E-flat", "E", "F", "F-sharp", "G", "A-flat", "A", "B-flat", "B"]

@@ -488,14 +488,16 @@ class CFMSampler(object):
     @torch.no_grad()
     def sample_cfg(self, cond, unconditional_guidance_scale, unconditional_conditioning, batch_size=16, timesteps=None, shape=None,
                    x_latent=None, t_start=None, gumbel_noise=None, seed=None, clip_base=0, x_known=None, keep_mask=None, keep_noise=None,
-                   **kwargs):
+                   clip_ids=None, **kwargs):
         """:87-116.  Extra kwargs (S=, x_T=, verbose=) are tolerated and ignored like the reference does
         (SURVEY Q1/Q2).  gumbel_noise/seed/clip_base are additions: injected router noise for parity, or the
         (seed, global clip index) that keys the on-device counter-based draws.
         x_known / keep_mask / keep_noise (addition; inpainting, continuation): tokens where keep_mask [B,T] or [T] is 1 are held on the
         probability path from keep_noise to x_known (the sampler's latent scale, what get_first_stage_encoding returns) and end at
         x_known + sigma_min * keep_noise; the others are generated in agreement with them.  keep_noise defaults to the start noise
-        when t_start is None and is required with t_start."""
+        when t_start is None and is required with t_start.
+        unconditional_guidance_scale may hold one value per row (sequence / float32 tensor) and clip_ids one global clip index per row
+        (addition; DiTEngine.sample_cfg): rows of different scales or non-contiguous clips then share the call."""
         shape = self._shape(shape, batch_size)
         timesteps = 25 if timesteps is None else timesteps
         idx, dts = euler_tables(timesteps, t_start)
@@ -506,16 +508,19 @@ class CFMSampler(object):
         pc = self.model._precompute(conds, shape[-1])
         if seed is None:
             seed = int(torch.initial_seed()) & 0xFFFFFFFF
-        x, traj = self.model.dit_engine().sample_cfg(x0, pc, idx, dts, float(unconditional_guidance_scale), noise=gumbel_noise,
-                                                     seed=seed, clip_base=clip_base, return_traj=True, keep=keep)
+        scale = unconditional_guidance_scale
+        if isinstance(scale, (int, float, np.integer, np.floating)) and not isinstance(scale, bool):
+            scale = float(scale)
+        x, traj = self.model.dit_engine().sample_cfg(x0, pc, idx, dts, scale, noise=gumbel_noise,
+                                                     seed=seed, clip_base=clip_base, return_traj=True, keep=keep, clip_ids=clip_ids)
         return traj[-1], traj
 
     @torch.no_grad()
     def sample(self, cond, batch_size=16, timesteps=None, shape=None, x_latent=None, t_start=None, x_known=None, keep_mask=None,
-               keep_noise=None, **kwargs):
+               keep_noise=None, clip_ids=None, **kwargs):
         """:49-80 (no guidance)."""
         return self.sample_cfg(cond, 1.0, None, batch_size=batch_size, timesteps=timesteps, shape=shape, x_latent=x_latent,
-                               t_start=t_start, x_known=x_known, keep_mask=keep_mask, keep_noise=keep_noise, **kwargs)
+                               t_start=t_start, x_known=x_known, keep_mask=keep_mask, keep_noise=keep_noise, clip_ids=clip_ids, **kwargs)
 
 
 # ---------------------------------------------------------------------------
