@@ -189,7 +189,7 @@ int vb_sample_cfg(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, 
  * The final state of a kept token at t = 1 is ref + sigma_min * x0, NOT ref: that is the end point of the path the model was trained on.
  * keep == NULL is exactly vb_sample_cfg.  Graph capture works as below; the key also holds ref, x0, mask and sigma_min, so a call with
  * other buffers captures its own graph and a plain call never replays a keep graph.  The fused (one launch per step) and the separate
- * (n_branch == 1, VB_EULER_LAUNCH) update forms are bit-identical. */
+ * (n_branch == 1, VB_EULER_LAUNCH) update forms are one device function - the same two fused multiply-adds - and bit-identical. */
 typedef struct { const float* ref; const float* x0; const float* mask; const float* t_next; float sigma_min; } vb_keep;
 int vb_sample_cfg_keep(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
                        const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_keep* keep,
@@ -197,10 +197,11 @@ int vb_sample_cfg_keep(vb_ctx* ctx, float* x, const void* cond, int B, int n_bra
 /* The same sampler with PER-ROW guidance scale and noise key: rows that differ in guidance scale (the scales of one item) or whose global
  * clip indices are not contiguous (items sharded rank::world, same-length items picked out of a manifest) share one call.  All rows of a
  * call still share T and L.
- *   cfg_scale  f32 [B]    (device) row b is guided by cfg_scale[b]: e = fmaf(cfg_scale[b], v_c - v_u, v_u) in the fused update and in the
- *                         keep update, e = v_u + cfg_scale[b] * (v_c - v_u) in the separate plain launch (VB_EULER_LAUNCH) - the arithmetic
- *                         of the scalar call, form for form, so row b equals the scalar call with that scale bit for bit.  The scalar
- *                         argument is ignored.  With n_branch == 1 there is nothing to guide and the array is not read.
+ *   cfg_scale  f32 [B]    (device) row b is guided by cfg_scale[b]: e = fmaf(cfg_scale[b], v_c - v_u, v_u), the fused multiply-add
+ *                         evaluation of v_u + cfg_scale[b] * (v_c - v_u), in EVERY update form - fused into FinalLayer, with a known region,
+ *                         the separate launch (VB_EULER_LAUNCH): all are the same two fused multiply-adds, the arithmetic of the scalar
+ *                         call, so row b equals the scalar call with that scale bit for bit.  The scalar argument is ignored.  With
+ *                         n_branch == 1 there is nothing to guide and the array is not read.
  *   clip       int64 [B]  (device) row b of BOTH branches draws its router noise from the stream of global clip clip[b] instead of
  *                         noise->clip_base + b; seed and nfe stay per call.  With injected noise arrays (noise->g1) the ids are unused.
  * Either member may be NULL; rows == NULL or both NULL is exactly vb_sample_cfg_keep (which, like vb_sample_cfg, forwards here).  Both

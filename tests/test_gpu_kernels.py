@@ -231,6 +231,37 @@ def test_rmsnorm_modulate(lib, npl):
     assert rel_l2(got, ref) < tol, describe("rmsnorm_modulate", got, ref)
 
 
+@pytest.mark.parametrize("has_uncond", [0, 1])
+def test_euler_cfg_step_matches_float64(lib, has_uncond):
+    """vb_euler_cfg_step (dt by value, no step table): x += dt (v_u + s (v_c - v_u)), or x += dt v without an unconditional half, against
+    the float64 evaluation.  The kernel rounds three times (the difference and two fused multiply-adds), each by at most 2^-24 of its
+    result, so per element |err| <= 2^-23 (|x| + dt (|v_u| + |s| |v_c - v_u|)) - derived, not measured.  1480 elements: the last of the
+    six 256-thread blocks is partial.  Without an unconditional half, v holds B * per_item elements and a NaN guard follows it in the
+    same allocation: the second half must never be read."""
+    B, per = 2, 20 * 37
+    n, dt, s = B * per, 0.25, 3.0
+    x, v = rnd((n,), "euler_x").float(), rnd((2 * n,), "euler_v").float()
+    nv = (1 + has_uncond) * n
+    vbuf = torch.full((nv + n,), float("nan"))
+    vbuf[:nv] = v[:nv]
+    xd = dev(x.clone())
+    L.check(lib.vb_euler_cfg_step(L.ptr(xd), L.ptr(dev(vbuf)), B, per, s, dt, has_uncond, L.stream_ptr()), "euler_cfg_step")
+    sync()
+    got = xd.cpu().double()
+    x64, vc = x.double(), v[:n].double()
+    if has_uncond:
+        vu = v[n:].double()
+        ref = x64 + dt * (vu + s * (vc - vu))
+        bound = 2.0 ** -23 * (x64.abs() + dt * (vu.abs() + abs(s) * (vc - vu).abs()))
+    else:
+        ref = x64 + dt * vc
+        bound = 2.0 ** -23 * (x64.abs() + dt * vc.abs())
+    assert torch.isfinite(got).all(), "the update read past the conditional half of v"
+    err = (got - ref).abs()
+    print(f"euler_cfg_step has_uncond={has_uncond}: max |err| / bound = {float((err / bound).max()):.3f}")
+    assert bool((err <= bound).all()), f"{int((err > bound).sum())} of {n} elements outside the bound (worst ratio {float((err / bound).max()):.3f})"
+
+
 @pytest.mark.parametrize("E", [4, 8])
 def test_router_top1_bit_exact(lib, E):
     N = 5000

@@ -1,8 +1,9 @@
 """Per-row guidance scale and noise key on the GPU (vb_sample_cfg_rows, through the C ABI): rows that differ in guidance scale or whose
 global clip indices are not contiguous share one sampler call, and each row is what its own call would have computed.
 
-Every comparison here is bit for bit (torch.equal).  The per-row kernels repeat the arithmetic of the scalar ones form for form
-(fmaf(s, v_c - v_u, v_u) fused and with a known region, v_u + s (v_c - v_u) in the separate plain launch), a clip's network evaluation
+Every comparison here is bit for bit (torch.equal).  Every update form - scalar or per-row scale, fused into FinalLayer or a launch of
+its own, with or without a known region - is the same two fused multiply-adds (fmaf(s, v_c - v_u, v_u), then fmaf(dt, e, x): one device
+function, common.h:euler_cfg_update), a clip's network evaluation
 does not depend on its batch slot (tests/test_gpu_keep.py), and the router noise is a counter-based function of (seed, global clip, ...):
 nothing is left that could round differently."""
 import os

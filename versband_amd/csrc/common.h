@@ -46,7 +46,7 @@ __device__ __forceinline__ float wave_max(float v) {
 // Known-region blend of the sampler (vb_sample_cfg_keep): a token marked as known is put back on the model's probability path
 // x_t = t x1 + (1 - (1 - sigma_min) t) x0 (cfm1_audio.py:38-43) after every Euler step.  keep_path is r(t) for the known content `ref`
 // and the call's start noise `x0`, keep_blend mixes it into the solver's state with the mask value m in [0, 1]: m = 0 returns xn and
-// m = 1 returns r bit for bit.  The fused (rowlin.hip), unfused and entry-projection kernels (elementwise.hip) all go through these
+// m = 1 returns r bit for bit.  The fused (rowlin.hip), unfused and entry-projection kernels (sampler_step.hip) all go through these
 // two, with contraction off, so they round alike.
 __device__ __forceinline__ float keep_path(float t, float sigma_min, float ref, float x0) {
 #pragma clang fp contract(off)
@@ -55,6 +55,17 @@ __device__ __forceinline__ float keep_path(float t, float sigma_min, float ref, 
 __device__ __forceinline__ float keep_blend(float m, float r, float xn) {
 #pragma clang fp contract(off)
     return fmaf(m, r, (1.f - m) * xn);
+}
+// One Euler step under classifier-free guidance (cfm1_audio.py:154-160: v = v_u + s (v_c - v_u); x += dt v), stated once: the fused
+// FinalLayer epilogue (rowlin.hip) and the stand-alone update (sampler_step.hip) both call it, so every form - scalar or per-row scale,
+// with or without a known region - is the same two fused multiply-adds, and fused equals separate launches bit for bit by construction.
+struct KeepAt { float m, tn, sigma_min, ref, x0; };      // the known region at one element: mask value, time after the step, path operands
+template <bool KEEP>
+__device__ __forceinline__ float euler_cfg_update(float x, float v_c, float v_u, bool has_uncond, float s, float dt, const KeepAt& ka) {
+    const float e = has_uncond ? fmaf(s, v_c - v_u, v_u) : v_c;
+    const float xn = fmaf(dt, e, x);
+    if constexpr (KEEP) return keep_blend(ka.m, keep_path(ka.tn, ka.sigma_min, ka.ref, ka.x0), xn);
+    else return xn;
 }
 
 // ---- host side -------------------------------------------------------------

@@ -484,11 +484,10 @@ static int final_layer(const Eval& e) {
     const int T = e.ev.T, D = e.D, N = e.N, MODW = e.MODW;
     float* v_out = e.ev.v_out;
     const float* modf = e.mod_all + (size_t)c.depth * 6 * D;
-    const EulerFuse* ef = e.ev.euler;
-    switch (e.p.final_route == FINAL_EULER_FUSED && !ef ? FINAL_FUSED : e.p.final_route) {
+    const EulerStep* es = e.ev.euler;
+    switch (e.p.final_route == FINAL_EULER_FUSED && !es ? FINAL_FUSED : e.p.final_route) {
     case FINAL_EULER_FUSED:
-        return launch_final_layer_euler(s.h, modf, modf + D, MODW, w.final_w, w.final_b, N, D, T, c.in_channels, 1e-6f, ef->x, ef->cfg_scale, ef->dt_table,
-                                        ef->k, ef->step, ef->t_idx_cur, ef->t_table, ef->n_steps, e.Beff, e.st, ef->keep, ef->scale_rows);
+        return launch_final_layer_euler(s.h, modf, modf + D, MODW, w.final_w, w.final_b, N, D, T, c.in_channels, 1e-6f, *es, e.st);
     case FINAL_FUSED:
         // one wave per token row: LayerNorm + modulate in registers, the 768 x 20 projection against LDS-resident weights (exact fp32)
         return launch_final_layer_fused(s.h, modf, modf + D, MODW, w.final_w, w.final_b, N, D, T, c.in_channels, 1e-6f, v_out, e.st);

@@ -124,9 +124,6 @@ struct DitPlan {
 };
 DitPlan dit_plan(const vb_ctx* ctx, int B, int nb, int T, int L);
 
-// sampler only: FinalLayer + CFG + Euler update + step advance as one launch (launch_final_layer_euler) - x is updated in place, v is not written
-// (scale_rows: per-clip guidance scales of vb_sample_cfg_rows, device [B]; null = cfg_scale for every clip)
-struct EulerFuse { float* x; float cfg_scale; const float* dt_table; int k; int* step; int64_t* t_idx_cur; const int64_t* t_table; int n_steps; const EulerKeep* keep; const float* scale_rows; };
 // one network evaluation (both CFG branches batched: rows [0,B) cond, [B,2B) uncond); a caller fills what it uses
 struct DitEval {
     const float* x = nullptr; const int64_t* t_idx = nullptr; const void* cond = nullptr; void* ws = nullptr;
@@ -137,7 +134,7 @@ struct DitEval {
     bool zero_vt = false;                                       // clear the padded V^T planes first (a stand-alone call)
     const float* pre_mod = nullptr; const float* pre_hl = nullptr;   // this step's rows of the sampler's tabulated conditioning vectors
     int evals_before = -1;                                      // block evaluations already done in this call (< 0: stand-alone, see DitPlan::router_counts)
-    const EulerFuse* euler = nullptr;
+    const EulerStep* euler = nullptr;                           // sampler only: FinalLayer does this step's update in the same launch (x in place, v_out not written)
 };
 int dit_forward(vb_ctx* ctx, const DitEval& ev, hipStream_t st);
 

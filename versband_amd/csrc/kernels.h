@@ -155,70 +155,75 @@ bool respair_f32w_supported(const RespairF32Args& a);
 int launch_respair_f32w(const RespairF32Args& a, hipStream_t st);
 
 // ---------------------------------------------------------------------------
-// small kernels
+// elementwise.hip: norms, casts and small helpers of the DiT, T5 and the sampler's tabulation; rowlin.hip, t5.hip, melnet.hip
 // ---------------------------------------------------------------------------
 int launch_rmsnorm_mod(const float* h, const float* w, const float* shift, const float* scale, int mod_ld,
                        int rows, int D, int T, float eps, Planes out, hipStream_t st);
 int launch_layernorm(const float* x, const float* w, const float* b, int rows, int D, float eps, float* out32, Planes outp,
                      hipStream_t st);
 int launch_cast_planes(const float* x, int64_t n, Planes out, hipStream_t st);
-// f32 [rows][cols] -> split-bf16 planes [2][rows][cpad] (cpad % 4 == 0, columns >= cols zero filled)
-int launch_silu_sum_planes(const float* temb, const float* cemb, int rows, int D, int nsample, bf16_t* out, int64_t plane, hipStream_t st);
+int launch_planes_to_f32(Planes in, int64_t n, float* out, hipStream_t st);
+int launch_fill_f32(float* p, int64_t n, float v, hipStream_t st);
+int launch_mean_rows(const float* x, int B, int L, int D, float* out, hipStream_t st);
+int launch_embed_t(const int64_t* idx, const float* table, int B, int T, int D, int vocab, float* out, hipStream_t st);   // (indices clamped to [0, vocab))
+int launch_pool_add(const float* a, const float* b, int B, int C, int T_in, float* out, hipStream_t st);
+int launch_transpose_bct_btc(const float* in, int B, int C, int T_in, int T_out, float* out, hipStream_t st);
+// proj_in as a GEMM: latent windows as K-contiguous split planes, conv weights re-laid as a GEMM operand
+int launch_im2col_latent(const float* x, int B, int C, int T, int taps, int pad, int KP, bf16_t* out, int64_t plane, hipStream_t st);
+int launch_conv_w_to_gemm(const bf16_t* w3, int64_t w3_plane, int taps, int D, int KP, bf16_t* out, hipStream_t st);
+int launch_rows_dot(const float* x, const float* W, const float* bias, int N, int D, int E, float* out, hipStream_t st);
 // LayerNorm (no affine, eps) + adaLN modulate -> split-bf16 planes (FinalLayer input, vocal2music_moe.py:287-291)
 int launch_layernorm_mod_planes(const float* h, const float* shift, const float* scale, int mod_ld, int rows, int D, int T, float eps,
                                 Planes out, hipStream_t st);
-// T5 (t5.hip)
-int launch_gather_rows(const int64_t* idx, const float* table, int rows, int D, int vocab, float* out, hipStream_t st);
-int launch_t5_attention(Planes qkv, const float* pos_bias, int pos_len, int B, int L, int heads, int dkv, Planes out, hipStream_t st);
-// transposed split planes for the DMA-fed conv path (see xt_planes_kernel): rows of the padded image
-#define XT_HEAD 64
-#define XT_TAIL 384
-static inline int xt_rows(int T_eff) { return T_eff + XT_HEAD + XT_TAIL; }
-int launch_xt_planes(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int groups, int act,
-                     float slope, int upsample2, int B, int C, int T_in, bf16_t* out, hipStream_t st);
-// log-mel front-end (melnet.hip)
-int launch_stft_frames(const float* wav, int B, int L, int hop, int pad, int pad2, int J, float* X, hipStream_t st);
-int launch_mel_tail(const float* spec, int B, int T, int Co4, int nb, int im_off, const float* basisT, int n_mels, float* mel, hipStream_t st);
-int launch_aa_act(const float* x, const float* alpha, const float* inv_beta, const float* filt, int B, int C, int T, float* out, hipStream_t st);
-int launch_gn_apply(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int B, int C, int T,
-                    int groups, int swish, float* out, hipStream_t st);
-int launch_split_rows(const float* x, int64_t rows, int cols, int cpad, bf16_t* out, int64_t plane, hipStream_t st);
-int launch_planes_to_f32(Planes in, int64_t n, float* out, hipStream_t st);
+int launch_silu_sum_planes(const float* temb, const float* cemb, int rows, int D, int nsample, bf16_t* out, int64_t plane, hipStream_t st);
+int launch_iota_div(int64_t* out, int n, int div, hipStream_t st);
+// row linears (rowlin.hip)
 int launch_gemv_rows(const float* x, int x_ld, const float* x2, int x2_ld, int x2_mod, const float* W, const float* bias,
                      int R, int N, int K, int act_in, float* out, int out_ld, hipStream_t st);
 int launch_gemv_rows_idx(const float* x, int x_ld, const int64_t* idx, const float* x2, int x2_ld, int x2_mod, const float* W,
                          const float* bias, int R, int N, int K, int act_in, float* out, int out_ld, hipStream_t st, int sin_rows = 0);
 // (sin_rows > 0: x is the timestep-sinusoid table with that many rows; indices outside it are evaluated on the fly)
-int launch_mean_rows(const float* x, int B, int L, int D, float* out, hipStream_t st);
-int launch_embed_t(const int64_t* idx, const float* table, int B, int T, int D, int vocab, float* out, hipStream_t st);   // (indices clamped to [0, vocab))
-int launch_pool_add(const float* a, const float* b, int B, int C, int T_in, float* out, hipStream_t st);
-int launch_transpose_bct_btc(const float* in, int B, int C, int T_in, int T_out, float* out, hipStream_t st);
 int launch_final_layer(const float* h, const float* shift, const float* scale, int mod_ld, const float* W, const float* bias,
                        int rows, int D, int T, int C, float eps, float* out, hipStream_t st);
 bool final_layer_fused_ok(int D, int C);
 int launch_final_layer_fused(const float* h, const float* shift, const float* scale, int mod_ld, const float* W, const float* bias,
                              int rows, int D, int T, int C, float eps, float* out, hipStream_t st);
+// T5 (t5.hip)
+int launch_gather_rows(const int64_t* idx, const float* table, int rows, int D, int vocab, float* out, hipStream_t st);
+int launch_t5_attention(Planes qkv, const float* pos_bias, int pos_len, int B, int L, int heads, int dkv, Planes out, hipStream_t st);
+// log-mel front-end (melnet.hip)
+int launch_stft_frames(const float* wav, int B, int L, int hop, int pad, int pad2, int J, float* X, hipStream_t st);
+int launch_mel_tail(const float* spec, int B, int T, int Co4, int nb, int im_off, const float* basisT, int n_mels, float* mel, hipStream_t st);
+
+// ---------------------------------------------------------------------------
+// sampler_step.hip: the sampler's update and step bookkeeping (+ the fused form of the update, rowlin.hip)
+// ---------------------------------------------------------------------------
 // known region of a sampler call (vb_keep with its time table on the device): ref / x0 [B][C][T], mask [B][T], tn_table[k] = t after step k
 struct EulerKeep { const float* ref; const float* x0; const float* mask; const float* tn_table; float sigma_min; };
-// (keep != nullptr: the known tokens are put back on the probability path in the same launch - common.h:keep_path / keep_blend)
+// One step's CFG + Euler update, described once for both of its launches: x [B][C][T] += dt_table[step] * (v_u + s (v_c - v_u)) with
+// s = cfg_scale, or scale_rows[b] (vb_sample_cfg_rows: device [B], cfg_scale is then unused), then - keep != nullptr - the known tokens
+// put back on the probability path (common.h:keep_path / keep_blend).  Every form is the same two fused multiply-adds
+// (common.h:euler_cfg_update).  The fields from k on are the step advance the fused launch does for the NEXT step: host step index k,
+// device counter `step` (null: no advance) and t_idx_cur[0..Beff) = t_table[min(k + 1, n_steps - 1)].
+struct EulerStep {
+    float* x = nullptr; float cfg_scale = 0.f; const float* scale_rows = nullptr; const float* dt_table = nullptr;
+    const EulerKeep* keep = nullptr;
+    int k = 0; int* step = nullptr; int64_t* t_idx_cur = nullptr; const int64_t* t_table = nullptr; int n_steps = 0, Beff = 0;
+};
+// FinalLayer + the update + the step advance as one launch (rows = 2 x (B T) token rows, conditional half first; reads es.k, not *es.step)
 int launch_final_layer_euler(const float* h, const float* shift, const float* scale, int mod_ld, const float* W, const float* bias,
-                             int rows, int D, int T, int C, float eps, float* x, float cfg_scale, const float* dt_table, int k, int* step,
-                             int64_t* t_idx_cur, const int64_t* t_table, int n_steps, int Beff, hipStream_t st, const EulerKeep* keep = nullptr,
-                             const float* scale_rows = nullptr);
-// (scale_rows != nullptr, vb_sample_cfg_rows: device [B] guidance scales, token row m of clip b takes scale_rows[b] and cfg_scale is unused -
-//  instances of their own, the scalar ones keep their arguments)
-int launch_euler_cfg(float* x, const float* v, int B, int64_t per, float cfg_scale, const float* dt_table, const int* step,
-                     float dt_val, int has_uncond, hipStream_t st);
-// the Euler + guidance update of launch_euler_cfg followed by the known-region blend at t = tn_table[*step] (x [B][C][T], per = C * T)
-int launch_euler_cfg_keep(float* x, const float* v, int B, int64_t per, int T, float cfg_scale, const float* dt_table, const int* step,
-                          int has_uncond, const EulerKeep& keep, hipStream_t st);
-// the two updates above with one guidance scale per clip (scale_rows: device [B]; vb_sample_cfg_rows under VB_EULER_LAUNCH): each in the
-// arithmetic of its scalar form
-int launch_euler_cfg_rows(float* x, const float* v, int B, int64_t per, const float* scale_rows, const float* dt_table, const int* step, hipStream_t st);
-int launch_euler_cfg_keep_rows(float* x, const float* v, int B, int64_t per, int T, const float* scale_rows, const float* dt_table, const int* step,
-                               const EulerKeep& keep, hipStream_t st);
+                             int rows, int D, int T, int C, float eps, const EulerStep& es, hipStream_t st);
+// the update as a launch of its own over v [2B or B][per] (per = C * T; has_uncond = 0: v holds B rows and no scale is read):
+// dt = es.dt_table[*es.step], or dt_val when es.dt_table is null; the step-advance fields are not used (launch_step_ctl)
+int launch_euler_cfg(const EulerStep& es, const float* v, int B, int64_t per, int T, int has_uncond, float dt_val, hipStream_t st);
 // projection on entry: x <- blend(mask, r(t_0), x) with t_0 = tn_table[0] - dt_table[0]
 int launch_keep_project(float* x, int B, int64_t per, int T, const float* dt_table, const EulerKeep& keep, hipStream_t st);
+int launch_sampler_params(int* step, uint64_t seed, int64_t clip_base, int nfe_base, hipStream_t st);   // step[4..9]: noise key of the call
+int launch_step_ctl(int* step, int64_t* t_idx_cur, const int64_t* t_table, int n_steps, int Beff, int reset, hipStream_t st);
+
+// ---------------------------------------------------------------------------
+// routing.hip: Band-MoE router and bucketing (+ the fused score + router kernel, score_router.hip)
+// ---------------------------------------------------------------------------
 // Band-MoE router: call arguments and the kernel's argument block in one (the device side is router_dev.h).
 // SC = true: "folded" caption gate.  The token features are not materialised at all: `sc` holds the token's attention
 // SCORES against its clip's caption keys for all heads ([N][NS], NS = L * Hh, column = key * Hh + head; scale, q-projection
@@ -254,7 +259,6 @@ struct ScoreRouterArgs {
 };
 bool score_router_supported(int NS, int K, int E, int Hh);
 int launch_score_router(const ScoreRouterArgs& a, hipStream_t st);
-int launch_iota_div(int64_t* out, int n, int div, hipStream_t st);
 // (pair_off / pair_pa non-null, E*E <= 16: rank by (caption, acoustic) expert PAIR; both expert-group orders derive from it - see
 //  bucket_place_kernel.  pair_off [E*E + 1], pair_pa [N] = acoustic slot of the token in pair / caption slot p)
 // counts_ready (round 5): the per-256-token-block group counts were already accumulated by the router (RouterDev::cnt) - the count launch is
@@ -268,18 +272,26 @@ int bucket_counts_ints(int N);           // ints of both tables together (to cle
 int launch_gate_fold(Planes kc, Planes vct, const float* bq_s, const float* wcg, int Beff, int L, int Lpad, int Hh, int hd, int E,
                      float* cbias, float* vw, hipStream_t st);
 int launch_iota_mul(int* out, int n, int mul, hipStream_t st);
-// proj_in as a GEMM (elementwise.hip): latent windows as K-contiguous split planes, conv weights re-laid as a GEMM operand
-int launch_im2col_latent(const float* x, int B, int C, int T, int taps, int pad, int KP, bf16_t* out, int64_t plane, hipStream_t st);
-int launch_conv_w_to_gemm(const bf16_t* w3, int64_t w3_plane, int taps, int D, int KP, bf16_t* out, hipStream_t st);
 int launch_router_top1(const float* logits, const float* gumbel, int N, int E, int* idx, hipStream_t st);
 int launch_fill_gumbel(float* out, int B, int n_branch, int T, int width, uint64_t seed, int64_t clip_base, int nfe_base,
                        const int* step, int block, int gate, hipStream_t st);
-int launch_rows_dot(const float* x, const float* W, const float* bias, int N, int D, int E, float* out, hipStream_t st);
+
+// ---------------------------------------------------------------------------
+// net_glue.hip: what the conv-net executor runs between its convolutions
+// ---------------------------------------------------------------------------
 int launch_gn_stats(const float* x, int B, int C, int T, int groups, float eps, float* mean, float* rstd, hipStream_t st);
+int launch_gn_apply(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int B, int C, int T,
+                    int groups, int swish, float* out, hipStream_t st);
+// transposed split planes for the DMA-fed conv path (see xt_planes_kernel): rows of the padded image
+#define XT_HEAD 64
+#define XT_TAIL 384
+static inline int xt_rows(int T_eff) { return T_eff + XT_HEAD + XT_TAIL; }
+int launch_xt_planes(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int groups, int act,
+                     float slope, int upsample2, int B, int C, int T_in, bf16_t* out, hipStream_t st);
+int launch_aa_act(const float* x, const float* alpha, const float* inv_beta, const float* filt, int B, int C, int T, float* out, hipStream_t st);
+// f32 [rows][cols] -> split-bf16 planes [2][rows][cpad] (cpad % 4 == 0, columns >= cols zero filled)
+int launch_split_rows(const float* x, int64_t rows, int cols, int cpad, bf16_t* out, int64_t plane, hipStream_t st);
 int launch_softmax_rows_t(const float* s, int B, int R, int Ccols, float* out_t, hipStream_t st);
-int launch_sampler_params(int* step, uint64_t seed, int64_t clip_base, int nfe_base, hipStream_t st);   // step[4..9]: noise key of the call
-int launch_step_ctl(int* step, int64_t* t_idx_cur, const int64_t* t_table, int n_steps, int Beff, int reset, hipStream_t st);
-int launch_fill_f32(float* p, int64_t n, float v, hipStream_t st);
 int launch_crossfade_windows(const float* parts, const int* starts, int nw, int B, int C, int n, int T, float* out, hipStream_t st);   // starts: HOST array
 
 // ---------------------------------------------------------------------------

@@ -1,0 +1,310 @@
+// Glue kernels of the conv-net executor (gfx950), called by convnet.hip only (VAE, HiFi-GAN / BigVGAN, long-form windows): GroupNorm
+// statistics and apply, the pre-activated transposed planes of the DMA-fed convs, the anti-aliased periodic activation, the split
+// planes and the transposed softmax of the VAE attention, and the cross-fade of long-form windows.
+#include "kernels.h"
+
+// ---------------------------------------------------------------------------
+// GroupNorm statistics (autoencoder1d.py:165-166): one block per (b, group); the group's
+// channels are contiguous in [B][C][T].  Two-pass mean / biased variance.
+// ---------------------------------------------------------------------------
+#define GS_T 1024
+__global__ void __launch_bounds__(GS_T) gn_stats_kernel(const float* __restrict__ x, int C, int T, int groups, float eps, float* mean,
+                                                       float* rstd) {
+    __shared__ float red[GS_T / 64];
+    __shared__ float s_mean;
+    const int bg = blockIdx.x;
+    const int64_t n = (int64_t)(C / groups) * T;
+    const float* p = x + (int64_t)bg * n;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool vec = (n & 3) == 0 && ((reinterpret_cast<uintptr_t>(p) & 15) == 0);
+    const int64_t n4 = vec ? n / 4 : 0;
+    float s = 0.f;
+    for (int64_t i = threadIdx.x; i < n4; i += GS_T) {
+        const float4 v = reinterpret_cast<const float4*>(p)[i];
+        s += (v.x + v.y) + (v.z + v.w);
+    }
+    for (int64_t i = n4 * 4 + threadIdx.x; i < n; i += GS_T) s += p[i];
+    s = wave_sum(s);
+    if (lane == 0) red[wave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.f;
+        for (int w = 0; w < GS_T / 64; ++w) t += red[w];
+        s_mean = t / (float)n;
+    }
+    __syncthreads();
+    const float m = s_mean;
+    float v = 0.f;
+    for (int64_t i = threadIdx.x; i < n4; i += GS_T) {
+        const float4 q = reinterpret_cast<const float4*>(p)[i];
+        const float d0 = q.x - m, d1 = q.y - m, d2 = q.z - m, d3 = q.w - m;
+        v += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+    }
+    for (int64_t i = n4 * 4 + threadIdx.x; i < n; i += GS_T) { float d = p[i] - m; v += d * d; }
+    v = wave_sum(v);
+    __syncthreads();
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.f;
+        for (int w = 0; w < GS_T / 64; ++w) t += red[w];
+        mean[bg] = m;
+        rstd[bg] = rsqrtf(t / (float)n + eps);
+    }
+}
+int launch_gn_stats(const float* x, int B, int C, int T, int groups, float eps, float* mean, float* rstd, hipStream_t st) {
+    if (C % groups) VB_FAIL(VB_E_INVALID, "gn_stats: C%%groups");
+    hipLaunchKernelGGL(gn_stats_kernel, dim3(B * groups), dim3(GS_T), 0, st, x, C, T, groups, eps, mean, rstd);
+    VB_CHECK_LAUNCH();
+    return VB_OK;
+}
+
+// GroupNorm affine (+ swish) applied once, for the wide VAE layers: the conv kernels can fuse it into their staging, but a
+// layer with Co/128 output-channel tiles would then redo the exp/div of every input element Co/128 times
+__global__ void __launch_bounds__(256) gn_apply_kernel(const float* __restrict__ x, const float* __restrict__ mean,
+                                                      const float* __restrict__ rstd, const float* __restrict__ gamma,
+                                                      const float* __restrict__ beta, int C, int T, int groups, int swish, float* out) {
+    const int row = blockIdx.y;                 // b * C + c
+    const int b = row / C, c = row - b * C;
+    const int grp = c / (C / groups);
+    const float rs = rstd[b * groups + grp] * gamma[c];
+    const float sh = beta[c] - mean[b * groups + grp] * rs;
+    const float* xr = x + (int64_t)row * T;
+    float* orow = out + (int64_t)row * T;
+    for (int t = (blockIdx.x * 256 + threadIdx.x) * 4; t < T; t += gridDim.x * 1024) {
+        if (t + 3 < T && (T & 3) == 0) {
+            const float4 v = *reinterpret_cast<const float4*>(xr + t);
+            float o[4] = {v.x * rs + sh, v.y * rs + sh, v.z * rs + sh, v.w * rs + sh};
+            if (swish) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) o[k] = o[k] / (1.f + __expf(-o[k]));
+            }
+            *reinterpret_cast<float4*>(orow + t) = make_float4(o[0], o[1], o[2], o[3]);
+        } else {
+            for (int k = t; k < min(t + 4, T); ++k) {
+                float o = xr[k] * rs + sh;
+                if (swish) o = o / (1.f + __expf(-o));
+                orow[k] = o;
+            }
+        }
+    }
+}
+int launch_gn_apply(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int B, int C, int T,
+                    int groups, int swish, float* out, hipStream_t st) {
+    if (C % groups) VB_FAIL(VB_E_INVALID, "gn_apply: C %% groups");
+    hipLaunchKernelGGL(gn_apply_kernel, dim3(cdiv(T, 1024), B * C), dim3(256), 0, st, x, mean, rstd, gamma, beta, C, T, groups, swish, out);
+    VB_CHECK_LAUNCH();
+    return VB_OK;
+}
+
+// Pre-pass for wide conv layers: x f32 [B][C][T] -> activated, split-bf16, TRANSPOSED planes [2][B][Tp][C] (C contiguous), with
+// XT_HEAD zero rows in front and zero rows behind (Tp = T_eff + XT_HEAD + XT_TAIL), so the conv kernel can DMA its input window
+// straight into LDS: the pointwise transform (GroupNorm affine, swish, LeakyReLU), the hi/lo split, the transpose and the zero
+// padding happen ONCE here instead of once per output-channel tile of the convolution (12 tiles on the 1536-channel layers).
+__global__ void __launch_bounds__(256) xt_planes_kernel(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                       const float* __restrict__ gamma, const float* __restrict__ beta, int groups, int act,
+                                                       float slope, int upsample2, int C, int T_in, int Tp, bf16_t* out, int64_t plane) {
+    __shared__ float tile[64][65];
+    const int b = blockIdx.z, c0 = blockIdx.y * 64, r0 = blockIdx.x * 64;          // r = row of the padded image
+    const int T_eff = upsample2 ? 2 * T_in : T_in;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int cpg = groups > 0 ? C / groups : 1;
+    {
+        const int t = r0 + tx - XT_HEAD;
+        const bool tin = t >= 0 && t < T_eff;
+        const int ts = upsample2 ? (t >> 1) : t;
+        for (int cc = ty; cc < 64; cc += 4) {
+            const int c = c0 + cc;
+            float v = 0.f;
+            if (tin && c < C) {
+                v = x[((int64_t)b * C + c) * T_in + ts];
+                if (act == ACT_GN || act == ACT_GN_SWISH) {
+                    const int grp = c / cpg;
+                    const float rs = rstd[b * groups + grp] * gamma[c];
+                    v = v * rs + (beta[c] - mean[b * groups + grp] * rs);
+                    if (act == ACT_GN_SWISH) v = v / (1.f + __expf(-v));
+                } else if (act == ACT_LRELU) {
+                    v = v > 0.f ? v : v * slope;
+                }
+            }
+            tile[tx][cc] = v;
+        }
+    }
+    __syncthreads();
+    const int tr = threadIdx.x >> 2, cg = (threadIdx.x & 3) * 16;
+    const int r = r0 + tr;
+    if (r < Tp && c0 + cg < C) {
+        bf16x8 hi[2], lo[2];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const float v = tile[tr][cg + e];
+            const bf16_t h = f2bf(v);
+            hi[e >> 3][e & 7] = h;
+            lo[e >> 3][e & 7] = f2bf(v - bf2f(h));
+        }
+        bf16_t* dst = out + ((int64_t)b * Tp + r) * C + c0 + cg;
+        *reinterpret_cast<bf16x8*>(dst) = hi[0];
+        *reinterpret_cast<bf16x8*>(dst + 8) = hi[1];
+        *reinterpret_cast<bf16x8*>(dst + plane) = lo[0];
+        *reinterpret_cast<bf16x8*>(dst + plane + 8) = lo[1];
+    }
+}
+int launch_xt_planes(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int groups, int act,
+                     float slope, int upsample2, int B, int C, int T_in, bf16_t* out, hipStream_t st) {
+    if (C % 16) VB_FAIL(VB_E_INVALID, "xt_planes: C %% 16");
+    const int Tp = xt_rows(upsample2 ? 2 * T_in : T_in);
+    hipLaunchKernelGGL(xt_planes_kernel, dim3(cdiv(Tp, 64), cdiv(C, 64), B), dim3(256), 0, st, x, mean, rstd, gamma, beta, groups, act, slope,
+                       upsample2, C, T_in, Tp, out, (int64_t)B * Tp * C);
+    VB_CHECK_LAUNCH();
+    return VB_OK;
+}
+
+// BigVGAN anti-aliased periodic activation (alias_free_torch Activation1d, ratio 2, 12-tap Kaiser-sinc filter f):
+//   up[v]  = 2 * sum_i xp[i] f[v + 15 - 2 i]          xp = x replicate-padded by 5          (UpSample1d, resample.py:10-32)
+//   s[v]   = up[v] + inv_beta * sin^2(alpha * up[v])                                         (Snake / SnakeBeta, activations.py)
+//   out[t] = sum_k f[k] s[clamp(2 t + k - 5, 0, 2T-1)]                                       (DownSample1d / LowPassFilter1d)
+// One workgroup = 256 outputs of one (batch, channel) row: the 523 intermediate samples are computed once into LDS.
+#define AA_TT 256
+__global__ void __launch_bounds__(256) aa_act_kernel(const float* __restrict__ x, const float* __restrict__ alpha, const float* __restrict__ inv_beta,
+                                                    const float* __restrict__ filt, int C, int T, float* out) {
+    __shared__ float xs[AA_TT + 16];
+    __shared__ float ss[2 * AA_TT + 16];
+    __shared__ float f[12];
+    const int row = blockIdx.y, c = row % C;
+    const int t0 = blockIdx.x * AA_TT;
+    const float* xr = x + (int64_t)row * T;
+    const int tid = threadIdx.x;
+    if (tid < 12) f[tid] = filt[tid];
+    for (int j = tid; j < AA_TT + 16; j += 256) {
+        int pos = t0 - 6 + j;
+        pos = pos < 0 ? 0 : (pos > T - 1 ? T - 1 : pos);
+        xs[j] = xr[pos];
+    }
+    __syncthreads();
+    const float a = alpha[c], ib = inv_beta[c];
+    for (int q = tid; q < 2 * AA_TT + 11; q += 256) {
+        int v = 2 * t0 - 5 + q;
+        v = v < 0 ? 0 : (v > 2 * T - 1 ? 2 * T - 1 : v);
+        const int i_lo = (v + 5) >> 1;                      // ceil((v + 4) / 2)
+        float up = 0.f;
+#pragma unroll
+        for (int m = 0; m < 6; ++m) {
+            const int i = i_lo + m;
+            const int tap = v + 15 - 2 * i;                 // 11 - (v+5)%2 ... >= 0 by construction for m < 6
+            if (tap >= 0 && tap < 12) up += xs[i - t0 + 1] * f[tap];
+        }
+        up *= 2.f;
+        const float sn = sinf(up * a);
+        ss[q] = up + ib * (sn * sn);
+    }
+    __syncthreads();
+    const int t = t0 + tid;
+    if (t < T) {
+        float acc = 0.f;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) acc += f[k] * ss[2 * tid + k];
+        out[(int64_t)row * T + t] = acc;
+    }
+}
+int launch_aa_act(const float* x, const float* alpha, const float* inv_beta, const float* filt, int B, int C, int T, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(aa_act_kernel, dim3(cdiv(T, AA_TT), B * C), dim3(256), 0, st, x, alpha, inv_beta, filt, C, T, out);
+    VB_CHECK_LAUNCH();
+    return VB_OK;
+}
+
+// f32 [rows][cols] -> split-bf16 planes [2][rows][cpad] (VB_OP_SPLIT_PLANES: per-batch weights of the VAE attention)
+__global__ void split_rows_kernel(const float* __restrict__ x, int64_t rows, int cols, int cpad, bf16_t* out, int64_t plane) {
+    const int q = cpad >> 2;
+    const int64_t total = rows * q;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = i / q;
+        const int c = (int)(i - r * q) * 4;
+        float v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = (c + k < cols) ? x[r * cols + c + k] : 0.f;
+        bf16x4 hi, lo;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { hi[k] = f2bf(v[k]); lo[k] = f2bf(v[k] - bf2f(hi[k])); }
+        *reinterpret_cast<bf16x4*>(out + r * cpad + c) = hi;
+        *reinterpret_cast<bf16x4*>(out + plane + r * cpad + c) = lo;
+    }
+}
+int launch_split_rows(const float* x, int64_t rows, int cols, int cpad, bf16_t* out, int64_t plane, hipStream_t st) {
+    if (cpad % 4 || cpad < cols) VB_FAIL(VB_E_INVALID, "split_rows: cpad=%d cols=%d", cpad, cols);
+    int64_t blocks = (rows * (cpad / 4) + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(split_rows_kernel, dim3((int)blocks), dim3(256), 0, st, x, rows, cols, cpad, out, plane);
+    VB_CHECK_LAUNCH();
+    return VB_OK;
+}
+
+// softmax over the last dim of s[B][R][Cc], written transposed: out_t[b][c][r]
+__global__ void __launch_bounds__(256) softmax_rows_t_kernel(const float* __restrict__ s, int R, int Cc, float* out_t) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int b = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    if (row >= R) return;
+    const float* p = s + ((int64_t)b * R + row) * Cc;
+    float m = -INFINITY;
+    for (int c = lane; c < Cc; c += 64) m = fmaxf(m, p[c]);
+    m = wave_max(m);
+    float sum = 0.f;
+    for (int c = lane; c < Cc; c += 64) sum += expf(p[c] - m);
+    sum = wave_sum(sum);
+    const float inv = 1.f / sum;
+    for (int c = lane; c < Cc; c += 64) out_t[((int64_t)b * Cc + c) * R + row] = expf(p[c] - m) * inv;
+}
+int launch_softmax_rows_t(const float* s, int B, int R, int Ccols, float* out_t, hipStream_t st) {
+    hipLaunchKernelGGL(softmax_rows_t_kernel, dim3(cdiv(R, 4), B), dim3(256), 0, st, s, R, Ccols, out_t);
+    VB_CHECK_LAUNCH();
+    return VB_OK;
+}
+
+
+// ---------------------------------------------------------------------------
+// long-form generation (BASELINE configs[4], build-defined: versband_amd/longform.py): cross-fade of the window results
+//   out[b][c][t] = sum_w wgt_w(t) * parts[w*B + b][c][t - s_w] / sum_w wgt_w(t)
+// wgt = 1 inside a window, linear ramps (k+1)/(ov+1) over the overlap with the previous window and 1 - (k+1)/(ov+1) over the overlap
+// with the next one (the interior points of linspace(0, 1, ov + 2)), the minimum of the two where both apply - window order and
+// arithmetic of longform.crossfade_windows (the torch restatement the oracle fixture was generated with).
+// ---------------------------------------------------------------------------
+struct XfadeStarts { int s[64]; };
+__global__ void __launch_bounds__(256) crossfade_windows_kernel(const float* __restrict__ parts, XfadeStarts st, int nw, int B, int C, int n, int T,
+                                                                float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)B * C * T) return;
+    const int t = (int)(i % T);
+    const int64_t bc = i / T;
+    const int b = (int)(bc / C), c = (int)(bc - (int64_t)b * C);
+    float acc = 0.f, wsum = 0.f;
+    for (int w = 0; w < nw; ++w) {
+        const int s = st.s[w], u = t - s;
+        if (u < 0 || u >= n) continue;
+        float wt = 1.f;
+        if (w > 0) {
+            const int ov = st.s[w - 1] + n - s;
+            if (ov > 0 && u < ov) wt = (float)(u + 1) / (float)(ov + 1);
+        }
+        if (w + 1 < nw) {
+            const int ov = s + n - st.s[w + 1];
+            if (ov > 0 && u >= n - ov) wt = fminf(wt, 1.f - (float)(u - (n - ov) + 1) / (float)(ov + 1));
+        }
+        acc += parts[(((int64_t)w * B + b) * C + c) * n + u] * wt;
+        wsum += wt;
+    }
+    out[i] = acc / wsum;
+}
+int launch_crossfade_windows(const float* parts, const int* starts, int nw, int B, int C, int n, int T, float* out, hipStream_t st) {
+    if (nw < 1 || nw > 64) VB_FAIL(VB_E_INVALID, "crossfade: %d windows (1..64)", nw);
+    XfadeStarts xs;
+    for (int w = 0; w < 64; ++w) xs.s[w] = w < nw ? starts[w] : 0;
+    for (int w = 0; w < nw; ++w)
+        if (xs.s[w] < 0 || xs.s[w] + n > T || (w > 0 && (xs.s[w] <= xs.s[w - 1] || xs.s[w] > xs.s[w - 1] + n)))
+            VB_FAIL(VB_E_INVALID, "crossfade: window %d at %d (length %d) does not continue the cover of [0, %d)", w, xs.s[w], n, T);
+    if (xs.s[0] != 0 || xs.s[nw - 1] + n != T) VB_FAIL(VB_E_INVALID, "crossfade: the windows do not cover [0, %d)", T);
+    const int64_t tot = (int64_t)B * C * T;
+    hipLaunchKernelGGL(crossfade_windows_kernel, dim3(cdiv(tot, 256)), dim3(256), 0, st, parts, xs, nw, B, C, n, T, out);
+    VB_CHECK_LAUNCH();
+    return VB_OK;
+}

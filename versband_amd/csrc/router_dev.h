@@ -1,4 +1,4 @@
-// Device side of the Band-MoE router, shared by router_kernel (elementwise.hip) and the fused score + router kernel
+// Device side of the Band-MoE router, shared by router_kernel (routing.hip) and the fused score + router kernel
 // (score_router.hip): one wave decides RT_TPW consecutive tokens.
 #pragma once
 #include "kernels.h"
@@ -63,7 +63,7 @@ __device__ __forceinline__ float reduce_logits(const float (&part)[PE], int lane
 // ---------------------------------------------------------------------------
 #define RT_TPW_MAX 4  // tokens per wave (4 when the launch fills the chip anyway; 1 for small batches: 4x the waves, a quarter of the latency)
 // (struct RouterDev, the kernels' argument block, is declared in kernels.h: launch_router's callers fill it)
-#define RT_CNT_BLOCK 256      // = BK_T of the bucket kernels (elementwise.hip)
+#define RT_CNT_BLOCK 256      // = BK_T of the bucket kernels (routing.hip)
 // Phase B of the router for the RT_TPW tokens n0 .. of one wave: noise draws, arg-max, high-level gate.  A token needs 2E+2 "slots"
 // (E caption-gate, E acoustic-gate, 2 high-level-gate values): PP tokens are laid side by side in the wave (SPT = 64/PP lanes each), so
 // the counter-based noise generator, the index arithmetic and the arg-max loops run once per PP tokens.  logit_of(t0, tokq, sl) returns

@@ -143,8 +143,8 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
 }
 // EUL (round 5): the CFG combination and the Euler update in the same launch (cfm1_audio.py:154-160: v = v_u + s (v_c - v_u); x += dt v) -
 // a wave takes TWO tokens of the conditional half and the same two of the unconditional half (rows m and m + rows / 2), so it holds
-// both branches' velocities of its tokens and updates x [B][C][T] in place with the arithmetic of euler_cfg_kernel (two fused
-// multiply-adds); the velocity tensor is never written.  Block 0 also advances the sampler's device-side step counter and the timestep
+// both branches' velocities of its tokens and updates x [B][C][T] in place through common.h:euler_cfg_update, the two fused
+// multiply-adds of the stand-alone update (sampler_step.hip); the velocity tensor is never written.  Block 0 also advances the sampler's device-side step counter and the timestep
 // indices for the NEXT step (step_advance_kernel's work): nothing in this launch reads them.  Saves two launches per Euler step.
 struct FinalEuler { float* x; float cfg_scale; const float* dt_table; int k; int* step; int64_t* t_idx_cur; const int64_t* t_table; int n_steps, Beff; };
 // KEEP (vb_sample_cfg_keep): the updated value is blended with the known region's point on the probability path at t = tn_table[k]
@@ -234,23 +234,21 @@ __global__ void __launch_bounds__(256) final_layer_kernel(const float* __restric
             const float bv = bias ? bias[lane] : 0.f;
             if constexpr (EUL) {
                 const float dt = fe.dt_table[fe.k];
-                float tn = 0.f;
-                if constexpr (KEEP) tn = fe.kp.tn_table[fe.k];
+                KeepAt ka{};
+                if constexpr (KEEP) { ka.tn = fe.kp.tn_table[fe.k]; ka.sigma_min = fe.kp.sigma_min; }
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
                     if (row0 + j < half) {
                         const float vc = res[j] + bv, vu = res[2 + j] + bv;
                         float sb = fe.cfg_scale;
                         if constexpr (ROWS) sb = fe.scale_rows[bb[j]];      // (bb[j] < B: rows 0 / 1 of the group are tokens of the conditional half)
-                        const float e = fmaf(sb, vc - vu, vu);
                         float* xp = fe.x + ((int64_t)bb[j] * C + lane) * T + tt[j];
                         if constexpr (KEEP) {
                             const int64_t xi = xp - fe.x;
-                            const float m = fe.kp.mask[(int64_t)bb[j] * T + tt[j]];
-                            *xp = keep_blend(m, keep_path(tn, fe.kp.sigma_min, fe.kp.ref[xi], fe.kp.x0[xi]), fmaf(dt, e, *xp));
-                        } else {
-                            *xp = fmaf(dt, e, *xp);
+                            ka.m = fe.kp.mask[(int64_t)bb[j] * T + tt[j]];
+                            ka.ref = fe.kp.ref[xi]; ka.x0 = fe.kp.x0[xi];
                         }
+                        *xp = euler_cfg_update<KEEP>(*xp, vc, vu, true, sb, dt, ka);
                     }
             } else {
 #pragma unroll
@@ -287,46 +285,30 @@ int launch_final_layer_fused(const float* h, const float* shift, const float* sc
 }
 // FinalLayer + CFG + Euler update + step advance in one launch (see FinalEuler): rows = 2 x (B T) token rows, conditional half first
 int launch_final_layer_euler(const float* h, const float* shift, const float* scale, int mod_ld, const float* W, const float* bias,
-                             int rows, int D, int T, int C, float eps, float* x, float cfg_scale, const float* dt_table, int k, int* step,
-                             int64_t* t_idx_cur, const int64_t* t_table, int n_steps, int Beff, hipStream_t st, const EulerKeep* keep,
-                             const float* scale_rows) {
-    if (!final_layer_fused_ok(D, C) || (rows & 1) || !x || !dt_table) VB_FAIL(VB_E_INVALID, "final_layer_euler: D=%d C=%d rows=%d unsupported", D, C, rows);
+                             int rows, int D, int T, int C, float eps, const EulerStep& es, hipStream_t st) {
+    if (!final_layer_fused_ok(D, C) || (rows & 1) || !es.x || !es.dt_table) VB_FAIL(VB_E_INVALID, "final_layer_euler: D=%d C=%d rows=%d unsupported", D, C, rows);
     const size_t sh = (size_t)C * D * sizeof(float);
     const int grid = min(cdiv(rows / 2, 8), 512);
-    FinalEuler fe{x, cfg_scale, dt_table, k, step, t_idx_cur, t_table, n_steps, Beff};
-    static OnceFlags attr[4], attr_keep[4], attr_rows[4], attr_keep_rows[4];
-    auto go = [&](auto nq) {
+    const FinalEuler base{es.x, es.cfg_scale, es.dt_table, es.k, es.step, es.t_idx_cur, es.t_table, es.n_steps, es.Beff};
+    // one instance (NQ, KEEP, ROWS): its own argument block, its LDS attribute set once, its launch
+    auto go = [&](auto nq, auto keep, auto by_rows) {
         constexpr int NQ = decltype(nq)::value;
-        if (scale_rows && keep) {
-            FinalEulerKeepRows fekr;
-            static_cast<FinalEuler&>(fekr) = fe; fekr.kp = *keep; fekr.scale_rows = scale_rows;
-            vb_set_max_lds_once(attr_keep_rows[NQ - 1], reinterpret_cast<const void*>(final_layer_kernel<NQ, true, true, true>), 96 * 1024);
-            hipLaunchKernelGGL((final_layer_kernel<NQ, true, true, true>), dim3(grid), dim3(256), sh, st, h, shift, scale, mod_ld, W, bias, rows, T > 0 ? T : 1, C,
-                               eps, (float*)nullptr, fekr);
-            return;
-        }
-        if (scale_rows) {
-            FinalEulerRows fer;
-            static_cast<FinalEuler&>(fer) = fe; fer.scale_rows = scale_rows;
-            vb_set_max_lds_once(attr_rows[NQ - 1], reinterpret_cast<const void*>(final_layer_kernel<NQ, true, false, true>), 96 * 1024);
-            hipLaunchKernelGGL((final_layer_kernel<NQ, true, false, true>), dim3(grid), dim3(256), sh, st, h, shift, scale, mod_ld, W, bias, rows, T > 0 ? T : 1, C,
-                               eps, (float*)nullptr, fer);
-            return;
-        }
-        if (keep) {
-            FinalEulerKeep fek;
-            static_cast<FinalEuler&>(fek) = fe; fek.kp = *keep;
-            vb_set_max_lds_once(attr_keep[NQ - 1], reinterpret_cast<const void*>(final_layer_kernel<NQ, true, true>), 96 * 1024);
-            hipLaunchKernelGGL((final_layer_kernel<NQ, true, true>), dim3(grid), dim3(256), sh, st, h, shift, scale, mod_ld, W, bias, rows, T > 0 ? T : 1, C,
-                               eps, (float*)nullptr, fek);
-            return;
-        }
-        vb_set_max_lds_once(attr[NQ - 1], reinterpret_cast<const void*>(final_layer_kernel<NQ, true>), 96 * 1024);
-        hipLaunchKernelGGL((final_layer_kernel<NQ, true>), dim3(grid), dim3(256), sh, st, h, shift, scale, mod_ld, W, bias, rows, T > 0 ? T : 1, C, eps,
-                           (float*)nullptr, fe);
+        constexpr bool KEEP = decltype(keep)::value, ROWS = decltype(by_rows)::value;
+        FinalEulerArgs<KEEP, ROWS> fe;
+        static_cast<FinalEuler&>(fe) = base;
+        if constexpr (KEEP) fe.kp = *es.keep;
+        if constexpr (ROWS) fe.scale_rows = es.scale_rows;
+        static OnceFlags attr;
+        vb_set_max_lds_once(attr, reinterpret_cast<const void*>(final_layer_kernel<NQ, true, KEEP, ROWS>), 96 * 1024);
+        hipLaunchKernelGGL((final_layer_kernel<NQ, true, KEEP, ROWS>), dim3(grid), dim3(256), sh, st, h, shift, scale, mod_ld, W, bias, rows, T > 0 ? T : 1, C,
+                           eps, (float*)nullptr, fe);
     };
-    if (D == 256) go(std::integral_constant<int, 1>()); else if (D == 512) go(std::integral_constant<int, 2>());
-    else if (D == 768) go(std::integral_constant<int, 3>()); else go(std::integral_constant<int, 4>());
+    const std::true_type yes; const std::false_type no;
+    auto form = [&](auto nq) {
+        if (es.keep && es.scale_rows) go(nq, yes, yes); else if (es.scale_rows) go(nq, no, yes); else if (es.keep) go(nq, yes, no); else go(nq, no, no);
+    };
+    if (D == 256) form(std::integral_constant<int, 1>()); else if (D == 512) form(std::integral_constant<int, 2>());
+    else if (D == 768) form(std::integral_constant<int, 3>()); else form(std::integral_constant<int, 4>());
     VB_CHECK_LAUNCH();
     return VB_OK;
 }

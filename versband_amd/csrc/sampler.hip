@@ -49,23 +49,22 @@ static int sample_steps(vb_ctx* ctx, float* x, const void* cond, int B, int n_br
     const bool fuse = plan.final_route == FINAL_EULER_FUSED;
     EulerKeep kp{};
     if (keep) kp = EulerKeep{keep->ref, keep->x0, keep->mask, s.tn_table, keep->sigma_min};
+    EulerStep es;
+    es.x = x; es.cfg_scale = cfg_scale; es.dt_table = s.dt_table; es.keep = keep ? &kp : nullptr;
+    es.scale_rows = n_branch == 2 ? rows.cfg_scale : nullptr;      // (one branch: there is nothing to guide, the scales are unused)
+    es.step = s.step; es.t_idx_cur = s.t_idx_cur; es.t_table = s.t_table; es.n_steps = n_steps; es.Beff = Beff;
     for (int k = 0; k < n_steps; ++k) {
         RoctxRange rs("euler_step");
         if (!fuse || k == 0) VB_TRY(launch_step_ctl(s.step, s.t_idx_cur, s.t_table, n_steps, Beff, k == 0, st));
-        EulerFuse ef{x, cfg_scale, s.dt_table, k, s.step, s.t_idx_cur, s.t_table, n_steps, keep ? &kp : nullptr, rows.cfg_scale};
+        es.k = k;
         DitEval ev;
         ev.x = x; ev.t_idx = s.t_idx_cur; ev.cond = cond; ev.ws = ws; ev.B = B; ev.nb = n_branch; ev.T = T; ev.L = L;
         ev.noise = noise; ev.noise_step = k; ev.step_ptr = s.step; ev.v_out = s.v; ev.clip_rows = rows.clip;
         if (tab) { ev.pre_mod = s.mod_s + (size_t)k * Beff * MODW; ev.pre_hl = s.hl_s + (size_t)k * c.depth * 2; }
         ev.evals_before = k * c.depth;
-        if (fuse) ev.euler = &ef;
+        if (fuse) ev.euler = &es;
         VB_TRY(dit_forward(ctx, ev, st));
-        // (one branch: there is nothing to guide, the scales are unused)
-        const bool scale_rows = rows.cfg_scale && n_branch == 2;
-        if (!fuse && keep && scale_rows) VB_TRY(launch_euler_cfg_keep_rows(x, s.v, B, per, T, rows.cfg_scale, s.dt_table, s.step, kp, st));
-        else if (!fuse && scale_rows) VB_TRY(launch_euler_cfg_rows(x, s.v, B, per, rows.cfg_scale, s.dt_table, s.step, st));
-        else if (!fuse && keep) VB_TRY(launch_euler_cfg_keep(x, s.v, B, per, T, cfg_scale, s.dt_table, s.step, n_branch == 2, kp, st));
-        else if (!fuse) VB_TRY(launch_euler_cfg(x, s.v, B, per, cfg_scale, s.dt_table, s.step, 0.f, n_branch == 2, st));
+        if (!fuse) VB_TRY(launch_euler_cfg(es, s.v, B, per, T, n_branch == 2, 0.f, st));
         if (traj) VB_HIP(hipMemcpyAsync(traj + (size_t)(k + 1) * B * per, x, (size_t)B * per * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     return VB_OK;
@@ -95,7 +94,9 @@ static SampleGraph* graph_entry(vb_ctx* ctx, const SampleGraph::Key& key) {
 extern "C" {
 
 int vb_euler_cfg_step(float* x, const float* v, int B, int64_t per_item, float cfg_scale, float dt, int has_uncond, void* stream) {
-    return launch_euler_cfg(x, v, B, per_item, cfg_scale, nullptr, nullptr, dt, has_uncond, (hipStream_t)stream);
+    EulerStep es;
+    es.x = x; es.cfg_scale = cfg_scale;
+    return launch_euler_cfg(es, v, B, per_item, 1, has_uncond, dt, (hipStream_t)stream);
 }
 int vb_sample_cfg(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
                   const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_noise* noise, float* traj, void* ws,

@@ -78,7 +78,7 @@ def randint(seed: int, n: int, lo: int, hi: int, offset: int = 0) -> np.ndarray:
 
 
 # ---------------------------------------------------------------------------
-# The library's own router-noise stream (csrc/elementwise.hip: gumbel_draw), restated on the host so that a production run
+# The library's own router-noise stream (csrc/router_dev.h: gumbel_draw), restated on the host so that a production run
 # (noise drawn on the device, keyed by (seed, global clip, evaluation, branch, block, gate, token, slot)) can be replayed by
 # the CPU oracle.  The integer pipeline is exact; u -> Exp(1) uses float32 log1p like the kernel (a last-ulp libm difference
 # moves a Gumbel value by ~1e-7 relative: it can flip a hard route only at an exact near-tie).
