@@ -660,6 +660,36 @@ def test_fp32_dma_conv_transpose_is_bit_identical(lib, monkeypatch, B, Ci, T, Co
     assert rel_l2(new, ref) < 2e-6, describe("conv_transpose1d fp32 dma", new, ref)
 
 
+@pytest.mark.parametrize("act", [0, 1])
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("T_in", [20, 200])
+def test_fp32_dma_conv_upsampled_window_is_bit_identical(lib, monkeypatch, T_in, B, act):
+    """conv1d_f32g_kernel's upsampled window (nearest-neighbour x2 in front of a k = 3 convolution: 4-byte DMA pieces from idx >> 1, its own
+    in-place pass; the VAE decoder's upsample layers) as a one-op conv-net program: same bits as the register-staged kernel
+    (VB_CONV_F32_OLD=1), both fp32-roundoff close to float64.  T_in = 20: one tile, both clip ends inside one window; 200: several tiles,
+    a ragged last one."""
+    from versband_amd.engine import Context, ConvNet, NetBuilder
+    Ci, Co, k = 16, 128, 3
+    x, w, b = rnd((B, Ci, T_in), "ux"), rnd((Co, Ci, k), "uw", 1.0 / (Ci * k) ** 0.5), rnd((Co,), "ub")
+    nb = NetBuilder(torch.device("cuda:0"), "fp32")
+    nb.conv(L.BUF_INPUT, L.BUF_OUTPUT, Ci, Co, pack.pack_conv(w), b, k=k, pad=1, upsample2=1,
+            in_act=L.ACT_LRELU if act else L.ACT_NONE, in_slope=0.1 if act else 0.0)
+    net = ConvNet(Context("cuda:0"), L.NET_VAE, nb, Ci, Co, 2)
+    new = net.run(x).clone()
+    monkeypatch.setenv("VB_CONV_F32_OLD", "1")
+    lib.vb_tune_reload()
+    old = net.run(x).clone()
+    monkeypatch.delenv("VB_CONV_F32_OLD")
+    lib.vb_tune_reload()
+    sync()
+    assert new.shape == (B, Co, 2 * T_in)
+    assert torch.isfinite(new).all() and torch.equal(new, old), f"DMA-fed vs register-staged differ by {float((new - old).abs().max()):.3e}"
+    xin = F.leaky_relu(x.double(), 0.1) if act else x.double()
+    ref = F.conv1d(F.interpolate(xin, scale_factor=2, mode="nearest"), w.double(), b.double(), padding=1)
+    assert rel_l2(new, ref) < 2e-6, describe("conv1d fp32 dma upsampled", new, ref)
+    assert rel_l2(old, ref) < 2e-6, describe("conv1d fp32 register-staged upsampled", old, ref)
+
+
 @pytest.mark.parametrize("B,C,T,k,dil,alpha,beta", [(2, 32, 1000, 3, 1, 1.0, 0.0), (1, 32, 472, 11, 5, 1.0 / 3, 1.0), (2, 64, 600, 7, 3, 1.0, 0.0),
                                                    (1, 64, 244, 11, 5, 1.0 / 3, 1.0), (1, 64, 128, 3, 5, 1.0 / 3, 0.0),
                                                    (1, 128, 360, 7, 1, 1.0, 0.0), (2, 128, 120, 11, 3, 1.0 / 3, 1.0),

@@ -1,6 +1,6 @@
 // What the convolution kernels share (conv1d_f32.hip: register-staged fp32 + split-bf16 kernels and the launch route; conv1d_f32g.hip:
-// the DMA-fed exact-fp32 kernel; conv1d_f32w.hip: its minimal-filtering form): the launch descriptor, the two epilogues and, host side,
-// what the two DMA-fed launchers have in common.
+// the DMA-fed exact-fp32 kernel; conv1d_f32w.hip: its minimal-filtering form): the launch descriptor, the two epilogues, the XCD work-group
+// numbering of the DMA-fed kernels (host and device half) and, host side, what their two launchers have in common.
 #pragma once
 #include "kernels.h"
 
@@ -192,6 +192,15 @@ static inline int conv_xcd_grid(ConvDev& d, int n_count, int t_tile, int co_tile
     d.g_nt = cdiv(n_count, t_tile); d.g_nco = cdiv(d.Co, co_tile);
     d.g_ntb = d.g_nt * B * d.phases; d.g_tbx = cdiv(d.g_ntb, 8);
     return 8 * d.g_tbx * d.g_nco;
+}
+// ... and its inverse on the device: this block's channel tile and unit; false for the blocks that pad the last row of eight (they return).
+// conv1d_f32g_kernel reads u as (time tile, clip, phase), conv1d_f32w_kernel as (time tile, clip).
+__device__ __forceinline__ bool conv_xcd_unit(const ConvDev& p, int& ct, int& u) {
+    const int L = blockIdx.x, j = L >> 3;
+    ct = j / p.g_tbx;
+    const int ul = j - ct * p.g_tbx;
+    u = ul * 8 + (L & 7);
+    return u < p.g_ntb;
 }
 
 // conv1d_f32g.hip: DMA-fed exact-fp32 kernel, bit-identical to conv1d_f32_kernel.  _eligible: ALL of a kernel's launch conditions

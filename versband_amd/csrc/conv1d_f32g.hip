@@ -7,6 +7,7 @@
 #include "conv1d_dev.h"
 #include "dma_ring.h"
 #include "lds_asm.h"
+#include "ring_window.h"
 
 // ---------------------------------------------------------------------------------------------------------
 // DMA-fed exact-fp32 kernel (round 4).  conv1d_f32_kernel (conv1d_f32.hip) multiplies at 80-93 % of the f32 MFMA rate PER TAP (measured at 8
@@ -16,8 +17,9 @@
 // there as in their MFMAs (profiles/r04_open_fp32voc_kernel_stats.csv).  This kernel keeps the arithmetic - same 16-channel chunks,
 // chunk -> tap -> channel-pair order, one v_mfma_f32_32x32x2_f32 per pair: BIT-IDENTICAL results - and changes how operands arrive:
 //   * the raw window of a chunk is DMA'd (global_load_lds, 16 B per lane) into a two-stage LDS ring one chunk ahead; LeakyReLU (in place)
-//     and zero padding by the lanes that own the quads, once their own DMA has landed and in front of the barrier that publishes the chunk; GroupNorm + swish inputs are pre-activated by gn_apply_kernel (the builder
-//     emits it in fp32 mode: the old kernel redid norm + swish + expf once per output-channel tile, 12x on the 1536-channel layers);
+//     and zero padding by the lanes that own the quads (ring_window.h: the feed all four fp32 ring kernels share); GroupNorm + swish inputs
+//     are pre-activated by gn_apply_kernel (the builder emits it in fp32 mode: the old kernel redid norm + swish + expf once per
+//     output-channel tile, 12x on the 1536-channel layers);
 //   * weight tiles [16 ci][CO_TILE] stream through a 4-stage ring, three tiles in flight, counted vmcnt + one raw s_barrier per tap;
 //   * the [b][co][t] result leaves through the staged 16-byte epilogue of the split-bf16 kernel (conv_epilogue_staged);
 //   * workgroups are numbered so that one XCD keeps a (time tile, clip) unit for ALL its output-channel tiles: the window is fetched
@@ -47,13 +49,12 @@ __global__ void __launch_bounds__(256, 3) conv1d_f32g_kernel(const ConvDev p) { 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 5, l31 = lane & 31;
     const int wm = wave / WN, wn = wave % WN;
-    // block -> (channel tile, unit): XCD x = L & 7 serves the units x, x + 8, ... for every channel tile
+    // block -> (channel tile, unit = (time tile, clip, phase)): conv1d_dev.h, beside the numbering.  (The decode stays in its own block
+    // with the results assigned, not const-initialised: hipcc allocates the runtime-tap instances of the wide tiles differently otherwise.)
     int b, ph, n0, co0;
     {
-        const int L = blockIdx.x, j = L >> 3;
-        const int ct = j / p.g_tbx, ul = j - ct * p.g_tbx;
-        const int u = ul * 8 + (L & 7);
-        if (u >= p.g_ntb) return;
+        int ct, u;
+        if (!conv_xcd_unit(p, ct, u)) return;
         const int z = u / p.g_nt;
         n0 = (u - z * p.g_nt) * T_TILE;
         b = z / p.phases; ph = z - b * p.phases;
@@ -73,87 +74,27 @@ __global__ void __launch_bounds__(256, 3) conv1d_f32g_kernel(const ConvDev p) { 
     }
     if (n0 >= n_count) return;
 
-    const int T_eff = UPS ? 2 * p.T_in : p.T_in;
     const int start = n0 + in_off;
     const int start_al = UPS ? start : (start & ~3);      // 16-B pieces start on a quad of the row (rows are 16-B aligned)
     const int aoff = start - start_al;
     const float* xbase = p.x + (int64_t)b * p.x_bstride;
     const float* wbase = p.w + (int64_t)b * p.w_bstride + (int64_t)ph * p.ntaps * p.Ci * p.Co;      // (w_bstride: per-clip operands, VAE attention)
     float slope = p.in_act == ACT_LRELU ? p.in_slope : 1.f;            // max(v, 1 v) = v: no branch in the fragment path
-    asm volatile("v_mov_b32 %0, %0" : "+v"(slope));                     // (kept in a VGPR: as an SGPR operand hipcc re-waits lgkmcnt(0) for
-                                                                        //  its s_load in front of every use inside the loop)
+    vgpr_pin(slope);
 
-    // ---- window DMA: piece i of this wave -> lane's source offset inside the clip (chunk 0) and whether it lies inside [0, T_eff)
-    int xsrc[XPW];
-    unsigned xoob = 0;
-#pragma unroll
-    for (int i = 0; i < XPW; ++i) {
-        const int ii = wave * XPW + i;
-        int ci, pos;
-        if constexpr (UPS) { ci = ii / NP; pos = (ii - ci * NP) * 64 + lane; }
-        else { const int q = ii * 4 + (lane >> 4); ci = q / NP; pos = (q - ci * NP) * 64 + (lane & 15) * 4; }
-        const int idx = start_al + pos;
-        const bool ok = idx >= 0 && idx < T_eff;           // (quads never straddle an end: T_eff % 4 == 0)
-        xsrc[i] = ci * p.T_in + (ok ? (UPS ? (idx >> 1) : idx) : 0);
-        xoob |= ok ? 0u : (1u << i);                       // per lane: a bit per piece
-    }
+    // ---- window DMA and the in-place pass (zero padding + LeakyReLU) over what landed: ring_window.h
+    RingWindow<XPW, NP, UPS> win;
+    win.setup(wave, lane, start_al, p.T_in);
     auto issue_x = [&](int ch) {
         if constexpr (ABL & 2) return;
-        const float* src = xbase + (int64_t)ch * GK * p.T_in;
-        float* dst = lx + (ch & 1) * XST;
-#pragma unroll
-        for (int i = 0; i < XPW; ++i) {
-            const int ii = wave * XPW + i;
+        bool nt = false;
 #ifdef VB_EXPERIMENTS
-            // (VB_CONV_XNT=1: the window - read by one or two workgroups - with the non-temporal policy, so that it does not displace the weights
-            //  every workgroup re-reads from L2; A/B of round 5, profiles/r05_conv_window_nt.txt)
-            if (p.x_nt) {
-                if constexpr (UPS) __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + xsrc[i]), (lds_ptr_t)(dst + ii * 64), 4, 0, 2);
-                else __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + xsrc[i]), (lds_ptr_t)(dst + ii * 256), 16, 0, 2);
-                continue;
-            }
+        nt = p.x_nt;
 #endif
-            if constexpr (UPS) __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + xsrc[i]), (lds_ptr_t)(dst + ii * 64), 4, 0, 0);
-            else __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + xsrc[i]), (lds_ptr_t)(dst + ii * 256), 16, 0, 0);
-        }
+        win.issue(xbase + (int64_t)ch * GK * p.T_in, lx + (ch & 1) * XST, nt);
     };
-    // Once per chunk, by the lanes that DMA'd the quads, after the wave's own DMA has landed and in front of the barrier that publishes the
-    // chunk: zeros over the out-of-range quads (padding) and LeakyReLU IN PLACE - not on the B fragments inside the MFMA loop: v_mul +
-    // 2 v_max per fragment were 6 VALU instructions per 4 MFMAs, and VALU instructions issued between a SIMD's MFMAs cost matrix-pipe
-    // time (tools/probe/f32_loop_probe: 149 -> 136 TF/s with them; here 36 VALU + 6 LDS instructions per thread and chunk replace 48 per
-    // tap).  Same operation on the same values: bit-identical.  The LDS accesses come from inline asm: an ordinary one makes hipcc drain
-    // the DMA ring with vmcnt(0) in front of it (lds_asm.h); the wave has waited for exactly these pieces itself.
     const bool act = p.in_act == ACT_LRELU;
-    auto fix_x = [&](int ch) {
-        if constexpr (UPS) {
-            const unsigned a0 = lds_u32(lx + (ch & 1) * XST + wave * XPW * 64 + lane);
-            float v[XPW];
-            if (act) {
-                static_for<0, XPW>([&](auto ic) { constexpr int I = decltype(ic)::value; lds_rd32<I * 256>(v[I], a0); });
-                LDS_WAIT(0);
-            }
-            static_for<0, XPW>([&](auto ic) {
-                constexpr int I = decltype(ic)::value;
-                const bool oob = (xoob >> I) & 1;
-                if (act) { lds_pin(v[I]); lds_wr32<I * 256>(a0, oob ? 0.f : fmaxf(v[I], v[I] * slope)); }
-                else if (oob) lds_wr32<I * 256>(a0, 0.f);
-            });
-        } else {
-            const unsigned a0 = lds_u32(lx + (ch & 1) * XST + wave * XPW * 256 + lane * 4);
-            lds_u32x4 v[XPW];
-            const lds_u32x4 zero = {0u, 0u, 0u, 0u};
-            if (act) {
-                static_for<0, XPW>([&](auto ic) { constexpr int I = decltype(ic)::value; lds_rd128<I * 1024>(v[I], a0); });
-                LDS_WAIT(0);
-            }
-            static_for<0, XPW>([&](auto ic) {
-                constexpr int I = decltype(ic)::value;
-                const bool oob = (xoob >> I) & 1;
-                if (act) { lds_pin(v[I]); lds_wr128<I * 1024>(a0, oob ? zero : lds_lrelu128_apply(v[I], slope)); }
-                else if (oob) lds_wr128<I * 1024>(a0, zero);
-            });
-        }
-    };
+    auto fix_x = [&](int ch) { win.fix(lx + (ch & 1) * XST, act, slope); };
     // ---- weight DMA: tile (chunk, tap) = 16 rows of CO_TILE floats, 1-KB pieces of 256 / CO_TILE rows
     constexpr int RPI = 256 / CO_TILE, LPR = CO_TILE / 4;
     int wsrc[WPW];
@@ -281,7 +222,7 @@ __global__ void __launch_bounds__(256, 3) conv1d_f32g_kernel(const ConvDev p) { 
                     constexpr int AH = LAST ? (NT - 1 - J < NSW - 2 ? NT - 1 - J : NSW - 2) : NSW - 2;      // younger weight tiles that may fly
                     if constexpr (J == 0) {
                         wait_vmcnt<(AH < NT ? AH : NT) * WPW>();
-                        if (act || xoob) { fix_x(ch); LDS_WAIT(0); }
+                        if (act || win.xoob) { fix_x(ch); LDS_WAIT(0); }
                     } else {
                         wait_vmcnt<AH * WPW + ((!LAST && J <= NSW - 2) ? XPW : 0)>();
                     }
@@ -313,7 +254,7 @@ __global__ void __launch_bounds__(256, 3) conv1d_f32g_kernel(const ConvDev p) { 
             else
 #endif
             wait_tile<WPW, XPW>(ch == 0 || lag <= 0 ? ahead_all : max(ahead_all - lag, 0), false);
-            if (act || xoob) { fix_x(ch); LDS_WAIT(0); }
+            if (act || win.xoob) { fix_x(ch); LDS_WAIT(0); }
         } else {
             // window ch + 1 was issued at this chunk's first tap, in front of tile (t - j + NSW - 1): younger than tile t while j <= NSW - 2
             wait_tile<WPW, XPW>(ahead_all, ch + 1 < nchunks && j <= NSW - 2);
@@ -397,6 +338,25 @@ static void launch_cfg_g_taps(ConvDev& d, int n_count, int B, hipStream_t st) {
     else if (nt == 11) launch_cfg_g<WM, WN, TM, TN, false, NSW, 0, 11>(d, n_count, B, st);
     else launch_cfg_g<WM, WN, TM, TN, false, NSW>(d, n_count, B, st);
 }
+#ifdef VB_EXPERIMENTS
+// VB_F32G_ABL (read per launch: tools/conv_f32_ablate.py flips it between launches): the timing-only ablation instances of one wide
+// tile (3-stage ring, runtime-tap loop).  Returns whether it launched.
+static int f32g_abl() { const char* e = getenv("VB_F32G_ABL"); return e ? atoi(e) : 0; }
+template <int WM, int WN, int TM, int TN>
+static bool launch_cfg_g_abl(int abl, ConvDev& d, int n_count, int B, hipStream_t st) {
+    switch (abl) {
+        case 1: launch_cfg_g<WM, WN, TM, TN, false, 3, 1>(d, n_count, B, st); return true;
+        case 2: launch_cfg_g<WM, WN, TM, TN, false, 3, 2>(d, n_count, B, st); return true;
+        case 4: launch_cfg_g<WM, WN, TM, TN, false, 3, 4>(d, n_count, B, st); return true;
+        case 8: launch_cfg_g<WM, WN, TM, TN, false, 3, 8>(d, n_count, B, st); return true;
+        case 16: launch_cfg_g<WM, WN, TM, TN, false, 3, 16>(d, n_count, B, st); return true;
+        case 3: launch_cfg_g<WM, WN, TM, TN, false, 3, 3>(d, n_count, B, st); return true;
+        case 7: launch_cfg_g<WM, WN, TM, TN, false, 3, 7>(d, n_count, B, st); return true;
+        case 6: launch_cfg_g<WM, WN, TM, TN, false, 3, 6>(d, n_count, B, st); return true;
+        default: return false;
+    }
+}
+#endif
 // The kernel's launch conditions: fp32 weights, shared or per clip, 16-byte aligned (tiles and clip strides); an input the window DMA can
 // fetch - as 16-byte pieces of aligned rows, or upsampled as 4-byte pieces (UPS; wide single-phase layers only: the 128-channel tiles);
 // halo <= 60 (window pitch = tile + 64 with <= 3 positions of alignment slack).
@@ -420,20 +380,8 @@ void launch_conv1d_f32g(ConvDev& d, int n_count, int B, int upsample2, hipStream
         switch (g_pick_tile(n_count, d.Co, B, d.phases)) {
             case 1:
 #ifdef VB_EXPERIMENTS
-                if (const char* e = getenv("VB_F32G_ABL")) {      // timing-only ablations of the 128 x 96 tile (the VAE's layers; runtime-tap loop)
-                    switch (atoi(e)) {
-                        case 1: launch_cfg_g<4, 1, 1, 3, false, 3, 1>(d, n_count, B, st); return;
-                        case 2: launch_cfg_g<4, 1, 1, 3, false, 3, 2>(d, n_count, B, st); return;
-                        case 4: launch_cfg_g<4, 1, 1, 3, false, 3, 4>(d, n_count, B, st); return;
-                        case 8: launch_cfg_g<4, 1, 1, 3, false, 3, 8>(d, n_count, B, st); return;
-                        case 16: launch_cfg_g<4, 1, 1, 3, false, 3, 16>(d, n_count, B, st); return;
-                        case 3: launch_cfg_g<4, 1, 1, 3, false, 3, 3>(d, n_count, B, st); return;
-                        case 7: launch_cfg_g<4, 1, 1, 3, false, 3, 7>(d, n_count, B, st); return;
-                        case 6: launch_cfg_g<4, 1, 1, 3, false, 3, 6>(d, n_count, B, st); return;
-                        case 100: launch_cfg_g_taps<2, 2, 2, 2, 3>(d, n_count, B, st); return;      // the 128 x 128 tile on this launch
-                        default: break;
-                    }
-                }
+                if (f32g_abl() == 100) { launch_cfg_g_taps<2, 2, 2, 2, 3>(d, n_count, B, st); return; }      // the 128 x 128 tile on this launch
+                if (launch_cfg_g_abl<4, 1, 1, 3>(f32g_abl(), d, n_count, B, st)) return;
 #endif
                 launch_cfg_g_taps<4, 1, 1, 3, 3>(d, n_count, B, st); break;
             case 2: launch_cfg_g<2, 2, 1, 2, false, 4>(d, n_count, B, st); break;
@@ -444,19 +392,7 @@ void launch_conv1d_f32g(ConvDev& d, int n_count, int B, int upsample2, hipStream
 #endif
             default:
 #ifdef VB_EXPERIMENTS
-                if (const char* e = getenv("VB_F32G_ABL")) {      // timing-only ablations of the 128 x 128 tile (tools/conv_f32_ablate.py)
-                    switch (atoi(e)) {
-                        case 1: launch_cfg_g<2, 2, 2, 2, false, 3, 1>(d, n_count, B, st); return;
-                        case 2: launch_cfg_g<2, 2, 2, 2, false, 3, 2>(d, n_count, B, st); return;
-                        case 4: launch_cfg_g<2, 2, 2, 2, false, 3, 4>(d, n_count, B, st); return;
-                        case 8: launch_cfg_g<2, 2, 2, 2, false, 3, 8>(d, n_count, B, st); return;
-                        case 16: launch_cfg_g<2, 2, 2, 2, false, 3, 16>(d, n_count, B, st); return;
-                        case 3: launch_cfg_g<2, 2, 2, 2, false, 3, 3>(d, n_count, B, st); return;
-                        case 7: launch_cfg_g<2, 2, 2, 2, false, 3, 7>(d, n_count, B, st); return;
-                        case 6: launch_cfg_g<2, 2, 2, 2, false, 3, 6>(d, n_count, B, st); return;
-                        default: break;
-                    }
-                }
+                if (launch_cfg_g_abl<2, 2, 2, 2>(f32g_abl(), d, n_count, B, st)) return;
 #endif
                 launch_cfg_g_taps<2, 2, 2, 2, 3>(d, n_count, B, st);     // 3-stage ring: 49 KB, three workgroups per CU (31.3 -> 30.4 ms per pass against 4 stages / two)
         }

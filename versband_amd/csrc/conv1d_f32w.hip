@@ -26,13 +26,15 @@
 // Dilation d: outputs u and u + d pair up.  A wave's 32 MFMA columns are v = (q, r), r < d, q < 32 / d; column v owns outputs 2 d q + r and
 // 2 d q + r + d of the wave's 2 * VW positions, VW = (32 / d) d (32 for d = 1, 30 for d = 3 / 5: two idle columns).  Tile = 128 co x 4 VW positions,
 // 4 waves as 2 x 2, wave = 64 co x 2 VW positions, accumulators 4 m's x 2 co tiles x 16 = 128 VGPRs (two workgroups per CU).
-// Ring, DMA pieces, counted vmcnt, fragment pipeline and XCD numbering: conv1d_f32g_kernel's unrolled-tap form with NT = pseudo-taps.
+// Ring, counted vmcnt, fragment pipeline and XCD numbering: conv1d_f32g_kernel's unrolled-tap form with NT = pseudo-taps; the window feed is
+// ring_window.h's, as there.
 #include <stdlib.h>
 #include <type_traits>
 
 #include "conv1d_dev.h"
 #include "dma_ring.h"
 #include "lds_asm.h"
+#include "ring_window.h"
 #include "mf_taps.h"
 
 #define MF_PITCH 68          // floats per staged channel row (64 positions + 4)
@@ -73,10 +75,8 @@ __global__ void __launch_bounds__(256, OCC) conv1d_f32w_kernel(const ConvDev p) 
     const int T_TILE = WN * 2 * VW;
     int b, n0, co0;
     {
-        const int L = blockIdx.x, j = L >> 3;
-        const int ct = j / p.g_tbx, ul = j - ct * p.g_tbx;
-        const int u = ul * 8 + (L & 7);
-        if (u >= p.g_ntb) return;
+        int ct, u;                       // block -> (channel tile, unit = (time tile, clip)): conv1d_dev.h, beside the numbering
+        if (!conv_xcd_unit(p, ct, u)) return;
         b = u / p.g_nt;
         n0 = (u - b * p.g_nt) * T_TILE;
         co0 = ct * CO_TILE;
@@ -90,44 +90,13 @@ __global__ void __launch_bounds__(256, OCC) conv1d_f32w_kernel(const ConvDev p) 
     const float* xbase = p.x + (int64_t)b * p.x_bstride;
     const float* wbase = p.ww;
     float slope = p.in_act == ACT_LRELU ? p.in_slope : 1.f;
-    asm volatile("v_mov_b32 %0, %0" : "+v"(slope));
+    vgpr_pin(slope);
 
-    // ---- window DMA (conv1d_f32g_kernel: 16-B lanes, four rows of 64 positions per 1-KB piece)
-    int xsrc[XPW];
-    unsigned xoob = 0;
-#pragma unroll
-    for (int i = 0; i < XPW; ++i) {
-        const int ii = wave * XPW + i;
-        const int q = ii * 4 + (lane >> 4);
-        const int ci = q / NP, pos = (q - ci * NP) * 64 + (lane & 15) * 4;
-        const int idx = start_al + pos;
-        const bool ok = idx >= 0 && idx < p.T_in;
-        xsrc[i] = ci * p.T_in + (ok ? idx : 0);
-        xoob |= ok ? 0u : (1u << i);
-    }
-    auto issue_x = [&](int ch, int stage) {
-        const float* src = xbase + (int64_t)ch * GK * p.T_in;
-        float* dst = lx + stage * XST;
-#pragma unroll
-        for (int i = 0; i < XPW; ++i)
-            __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + xsrc[i]), (lds_ptr_t)(dst + (wave * XPW + i) * 256), 16, 0, 0);
-    };
+    // ---- window DMA (16-B lanes, four rows of 64 positions per 1-KB piece) and the in-place pass over what landed: ring_window.h
+    RingWindow<XPW, NP> win;
+    win.setup(wave, lane, start_al, p.T_in);
+    auto issue_x = [&](int ch, int stage) { win.issue(xbase + (int64_t)ch * GK * p.T_in, lx + stage * XST); };
     const bool act = p.in_act == ACT_LRELU;
-    auto fix_x = [&](int stage) {     // zero padding + LeakyReLU in place, by the lanes whose own DMA brought the quads
-        const unsigned a0 = lds_u32(lx + stage * XST + wave * XPW * 256 + lane * 4);
-        lds_u32x4 v[XPW];
-        const lds_u32x4 zero = {0u, 0u, 0u, 0u};
-        if (act) {
-            static_for<0, XPW>([&](auto ic) { constexpr int I = decltype(ic)::value; lds_rd128<I * 1024>(v[I], a0); });
-            LDS_WAIT(0);
-        }
-        static_for<0, XPW>([&](auto ic) {
-            constexpr int I = decltype(ic)::value;
-            const bool oob = (xoob >> I) & 1;
-            if (act) { lds_pin(v[I]); lds_wr128<I * 1024>(a0, oob ? zero : lds_lrelu128_apply(v[I], slope)); }
-            else if (oob) lds_wr128<I * 1024>(a0, zero);
-        });
-    };
     // ---- weight DMA: tile (chunk, pseudo-tap) = 16 rows of 128 floats
     constexpr int RPI = 256 / CO_TILE, LPR = CO_TILE / 4;
     int wsrc0;                            // piece 0 of this wave; piece i lies RPI * i rows further on (a scalar offset)
@@ -191,7 +160,7 @@ __global__ void __launch_bounds__(256, OCC) conv1d_f32w_kernel(const ConvDev p) 
 #ifdef VB_EXPERIMENTS
                 if (!(p.mf_abl & 1))
 #endif
-                if (act || xoob) { fix_x(xs); LDS_WAIT(0); }
+                if (act || win.xoob) { win.fix(lx + xs * XST, act, slope); LDS_WAIT(0); }
             } else {
                 wait_vmcnt<AH * WPW + (J <= NSW - 2 ? XPW : 0)>();
             }
@@ -200,12 +169,7 @@ __global__ void __launch_bounds__(256, OCC) conv1d_f32w_kernel(const ConvDev p) 
 #ifdef VB_EXPERIMENTS
                 if (!(p.mf_abl & 4))
 #endif
-                {                const float* src = xbase + (int64_t)chx * GK * p.T_in;
-                float* dst = lx + xsn * XST;
-#pragma unroll
-                for (int i = 0; i < XPW; ++i)
-                    __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + xsrc[i]), (lds_ptr_t)(dst + (wave * XPW + i) * 256), 16, 0, 0);
-                }
+                issue_x(chx, xsn);
             }
             if constexpr (J + NSW - 1 < P) issue_w(ch, J + NSW - 1, nslot);
             else issue_w(chn, J + NSW - 1 - P, nslot);

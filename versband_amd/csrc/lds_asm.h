@@ -24,6 +24,9 @@ template <int OFF> __device__ __forceinline__ void lds_rd32(float& v, unsigned a
 }
 #define LDS_WAIT(N) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N))
 __device__ __forceinline__ void lds_pin(float& v) { asm volatile("" : "+v"(v)); }
+// a wave-uniform value (the LeakyReLU slope of the ring kernels) kept in a VGPR: as an SGPR operand hipcc re-waits lgkmcnt(0) for its
+// s_load in front of every use inside the loop
+__device__ __forceinline__ void vgpr_pin(float& v) { asm volatile("v_mov_b32 %0, %0" : "+v"(v)); }
 
 // 16-byte form (bf16 MFMA fragments)
 typedef unsigned lds_u32x4 __attribute__((ext_vector_type(4)));

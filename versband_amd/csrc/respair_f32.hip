@@ -12,7 +12,7 @@
 //   * conv1: the raw window of x (128 + (k-1) d positions) arrives by DMA (global_load_lds, 16-B lanes) one 16-channel chunk ahead, the
 //     weight tiles [TPS taps][16 ci][C co] of BOTH convolutions stream through one 3- or 4-stage ring (counted vmcnt, one raw s_barrier per
 //     ring step = TPS taps of a chunk: 32 / 16 MFMAs per wave at 32 / 64 channels); fragments by inline-asm ds_read_b32 two channel pairs ahead with exact lgkmcnt
-//     (lds_asm.h); LeakyReLU is applied in place once per chunk by the lanes that DMA'd it; a wave owns 32 intermediate positions x all channels;
+//     (lds_asm.h); LeakyReLU is applied in place once per chunk by the lanes that DMA'd it (ring_window.h); a wave owns 32 intermediate positions x all channels;
 //   * + b1, LeakyReLU, zero outside [0,T) (conv2 pads the ACTIVATED intermediate) -> LDS h[c][m] (aliases the window ring);
 //   * conv2 over h, + b2 + residual x, alpha / beta accumulation into the MRF sum through the staged 16-byte epilogue.
 // Same chunk -> tap -> channel-pair accumulation order and the same epilogue arithmetic as conv1d_f32_kernel / conv1d_f32g_kernel:
@@ -23,6 +23,7 @@
 #include "kernels.h"
 #include "dma_ring.h"
 #include "lds_asm.h"
+#include "ring_window.h"
 
 #define PF_T 128            // intermediate positions per workgroup (4 waves x 32)
 #define PF_XP 192           // window pitch: 128 + halo (<= 60) + alignment slack (<= 3)
@@ -79,48 +80,21 @@ __global__ void __launch_bounds__(256) respair_f32_kernel(const PairF32Dev p) {
     const int aoff = x0 - start_al;
     const float* xb = p.x + (int64_t)b * p.bstride;
     float slope = p.slope;
-    asm volatile("v_mov_b32 %0, %0" : "+v"(slope));       // VGPR copy: an SGPR operand makes hipcc re-wait lgkmcnt(0) in front of every use
+    vgpr_pin(slope);
 
-    int xsrc[XPW];
-    unsigned xoob = 0;
-#pragma unroll
-    for (int i = 0; i < XPW; ++i) {
-        const int ii = wave * XPW + i;
-        const int q = ii * 4 + (lane >> 4);
-        const int ci = q / NP, pos = (q - ci * NP) * 64 + (lane & 15) * 4;
-        const int idx = start_al + pos;
-        const bool ok = idx >= 0 && idx < p.T;
-        xsrc[i] = ci * p.T + (ok ? idx : 0);
-        xoob |= ok ? 0u : (1u << i);
-    }
+    // ---- window DMA and LeakyReLU + zero padding in place over what landed: ring_window.h (the pairs always activate).  The residual is
+    // read from global memory, not from this window.
+    RingWindow<XPW, NP> win;
+    win.setup(wave, lane, start_al, p.T);
     auto issue_x = [&](int ch) {
         if constexpr (ABL & 2) return;
-        const float* src = xb + (int64_t)ch * PF_GK * p.T;
-        float* dst = lx + (ch & 1) * XST;
-#pragma unroll
-        for (int i = 0; i < XPW; ++i) {
+        bool nt = false;
 #ifdef VB_EXPERIMENTS
-            if (p.x_nt) { __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + xsrc[i]), (lds_ptr_t)(dst + (wave * XPW + i) * 256), 16, 0, 2); continue; }
+        nt = p.x_nt;
 #endif
-            __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + xsrc[i]), (lds_ptr_t)(dst + (wave * XPW + i) * 256), 16, 0, 0);
-        }
+        win.issue(xb + (int64_t)ch * PF_GK * p.T, lx + (ch & 1) * XST, nt);
     };
-    // once per chunk, by the lanes that DMA'd the quads (after the wave's own DMA landed, in front of the publishing barrier): zeros over
-    // the out-of-range quads and LeakyReLU in place (conv1d_f32g.hip: VALU instructions between a SIMD's MFMAs cost matrix-pipe time; 36 VALU
-    // + 6 LDS instructions per thread and chunk instead of 3 per B fragment; inline-asm LDS accesses so that hipcc does not drain the DMA
-    // ring with vmcnt(0) in front of them).  The residual is read from global memory, not from this window.
-    auto fix_x = [&](int ch) {
-        const unsigned a0 = lds_u32(lx + (ch & 1) * XST + wave * XPW * 256 + lane * 4);
-        lds_u32x4 v[XPW];
-        const lds_u32x4 zero = {0u, 0u, 0u, 0u};
-        static_for<0, XPW>([&](auto ic) { constexpr int I = decltype(ic)::value; lds_rd128<I * 1024>(v[I], a0); });
-        LDS_WAIT(0);
-        static_for<0, XPW>([&](auto ic) {
-            constexpr int I = decltype(ic)::value;
-            lds_pin(v[I]);
-            lds_wr128<I * 1024>(a0, ((xoob >> I) & 1) ? zero : lds_lrelu128_apply(v[I], slope));
-        });
-    };
+    auto fix_x = [&](int ch) { win.fix(lx + (ch & 1) * XST, std::true_type{}, slope); };
     // ring tile = (convolution, chunk, step): taps [s TPS, s TPS + TPS) of 16 input channels; a tap's [16][C] block is contiguous
     constexpr int NCH = C / PF_GK;
     const int NS = (p.k + TPS - 1) / TPS;             // steps per chunk

@@ -16,7 +16,7 @@
 // LDS: window ring 2 x [16 ci][320] (both 16-channel chunks of x are requested up front), the intermediate h[32][272] aliases it, weight ring of 3 tiles
 // [TPS pseudo-taps][16 ci][32 co] (TPS = 4: 32 MFMAs per ring step and wave; k = 3 has 4 pseudo-taps in all and runs TPS = 2) = 64 KB, two workgroups
 // per CU.  The whole schedule - 2 convolutions x 2 chunks x ceil(P / TPS) ring steps - is unrolled: every wait count, tap offset and tile index is an
-// immediate.  Ring / fragment pipeline / counted vmcnt as in respair_f32_kernel.
+// immediate.  Ring / fragment pipeline / counted vmcnt as in respair_f32_kernel; window feed: ring_window.h.
 // C = 64: the waves are 2 (time) x 2 (channel halves) - a wave computes 32 of the 64 output channels of its 64 positions in BOTH convolutions, so the
 // accumulators stay 4 x 16 registers; runs of M = 4 VW = 128 / 120 intermediate positions, window pitch 192, h[64][144] = 37 KB, tiles of TPS = 2 pseudo-taps
 // [2][16][64] = 8 KB: 61 KB, two workgroups per CU; the four 16-channel windows go through the two-stage ring (chunk c + 1 is requested at chunk c's first step).
@@ -26,6 +26,7 @@
 #include "kernels.h"
 #include "dma_ring.h"
 #include "lds_asm.h"
+#include "ring_window.h"
 #include "mf_taps.h"
 
 #define PW_GK 16
@@ -78,41 +79,15 @@ __global__ void __launch_bounds__(256, 2) respair_f32w_kernel(const PairWDev p) 
     const int aoff = x0 - start_al;
     const float* xb = p.x + (int64_t)b * p.bstride;
     float slope = p.slope;
-    asm volatile("v_mov_b32 %0, %0" : "+v"(slope));
+    vgpr_pin(slope);
 
-    // ---- window DMA: chunk c -> stage c & 1, 16-B lanes, four rows of 64 positions per piece; chunks 0 and 1 now
-    unsigned xoob = 0;
-    int xsrc[XPW];
-#pragma unroll
-    for (int i = 0; i < XPW; ++i) {
-        const int ii = wave * XPW + i;
-        const int q = ii * 4 + (lane >> 4);
-        const int ci = q / NP, pos = (q - ci * NP) * 64 + (lane & 15) * 4;
-        const int idx = start_al + pos;
-        const bool ok = idx >= 0 && idx < p.T;
-        xsrc[i] = ci * p.T + (ok ? idx : 0);
-        xoob |= ok ? 0u : (1u << i);
-    }
-    auto issue_x = [&](int ch) {
-#pragma unroll
-        for (int i = 0; i < XPW; ++i)
-            __builtin_amdgcn_global_load_lds((glb_ptr_t)(xb + (int64_t)ch * PW_GK * p.T + xsrc[i]),
-                                             (lds_ptr_t)(lx + (ch & 1) * XST + (wave * XPW + i) * 256), 16, 0, 0);
-    };
+    // ---- window DMA: chunk c -> stage c & 1, chunks 0 and 1 now; LeakyReLU + zero padding in place over what landed: ring_window.h
+    RingWindow<XPW, NP> win;
+    win.setup(wave, lane, start_al, p.T);
+    auto issue_x = [&](int ch) { win.issue(xb + (int64_t)ch * PW_GK * p.T, lx + (ch & 1) * XST); };
     issue_x(0);
     issue_x(1);
-    auto fix_x = [&](int ch) {        // zero padding + LeakyReLU in place, by the lanes whose own DMA brought the quads
-        const unsigned a0 = lds_u32(lx + (ch & 1) * XST + wave * XPW * 256 + lane * 4);
-        lds_u32x4 v[XPW];
-        const lds_u32x4 zero = {0u, 0u, 0u, 0u};
-        static_for<0, XPW>([&](auto ic) { constexpr int I = decltype(ic)::value; lds_rd128<I * 1024>(v[I], a0); });
-        LDS_WAIT(0);
-        static_for<0, XPW>([&](auto ic) {
-            constexpr int I = decltype(ic)::value;
-            lds_pin(v[I]);
-            lds_wr128<I * 1024>(a0, ((xoob >> I) & 1) ? zero : lds_lrelu128_apply(v[I], slope));
-        });
-    };
+    auto fix_x = [&](int ch) { win.fix(lx + (ch & 1) * XST, std::true_type{}, slope); };
     // ---- weight DMA: tile t = (conv, chunk, step): pseudo-taps [s TPS, s TPS + TPS) of 16 input channels; a piece = 256 consecutive floats of the
     // pseudo-tap's [16 ci][C co] block
     constexpr int PPT = PW_GK * C / 256;                // pieces per pseudo-tap
