@@ -243,6 +243,7 @@ enum { VB_ACT_NONE = 0, VB_ACT_LRELU = 1, VB_ACT_GN_SWISH = 2, VB_ACT_TANH = 3, 
  *   MF      w_mf: fp32 F(2,3) minimal-filtering pseudo-taps [P][Ci][Co] of the same filter, 16-byte aligned (pack.py:pack_conv_mf)
  *   BUF_F32 w_buf: per-batch fp32 weights written by earlier ops      (the VAE attention's products)
  *   BUF_X3  w_buf: per-batch split planes from a VB_OP_SPLIT_PLANES
+ *   BF16    w_x3: ONE plane [phase][tap][Co][ci_pad] of round-to-nearest bf16 weights - plane 0 of X3 (pack.py:pack_conv_bf16)
  * Allowed (kind, wfmt) pairs and the weight fields each reads; vb_net_load refuses any other pair, a NULL in a field the pair reads,
  * and a non-NULL weight pointer (w, w_x3, w_mf, w2) or a w_buf id in a field it does not read:
  *   CONV     F32      w                              the exact-fp32 kernels
@@ -253,12 +254,16 @@ enum { VB_ACT_NONE = 0, VB_ACT_LRELU = 1, VB_ACT_GN_SWISH = 2, VB_ACT_TANH = 3, 
  *   RESPAIR  F32      w, w2, bias, bias2             respair_f32_kernel, C = 32 / 64 / 128
  *   RESPAIR  X3       w_x3, ci_pad, w2, bias, bias2  respair_x3 (split planes [2][k][C][C]), C = 32 / 64
  *   RESPAIR  MF       w_mf, w2, bias, bias2          respair_f32w_kernel (both 16-byte aligned), C = 32 / 64
+ *   CONV     BF16     w_x3, ci_pad, w (Co = 1 only)  conv1d_bf16_kernel (one plane [phase][tap][Co][ci_pad]); w feeds the one-output-channel kernel
+ *   RESPAIR  BF16     w_x3, ci_pad, w2, bias, bias2  respair_bf16_kernel (one plane [k][C][C] each), C = 32 / 64
  *   AA_ACT   NONE     w (the filter)
  *   other    NONE     -
- * It also refuses an X3 op whose ci_pad is not Ci rounded up to 32, MF weights that are not 16-byte aligned, and a RESPAIR without
+ * BF16 is the single-pass bf16 mode: every product is RN_bf16(weight) * RN_bf16(activated input), accumulated in fp32 - outside the 1e-3
+ * parity contract by design (see vb_conv1d_bf16).  A BF16 CONV carries w exactly when Co == 1; a BF16 RESPAIR with C outside 32 / 64 is refused.
+ * It also refuses an X3 / BF16 op whose ci_pad is not Ci rounded up to 32, MF weights that are not 16-byte aligned, and a RESPAIR without
  * Ci == Co or whose x / out differ in time length (buffer tmul; in_tmul / out_tmul for the I/O ids).  The failing op's index is in
  * vb_last_error().  Conditions that depend on T or on buffer addresses are checked when the op runs. */
-enum { VB_WFMT_NONE = 0, VB_WFMT_F32 = 1, VB_WFMT_X3 = 2, VB_WFMT_MF = 3, VB_WFMT_BUF_F32 = 4, VB_WFMT_BUF_X3 = 5 };
+enum { VB_WFMT_NONE = 0, VB_WFMT_F32 = 1, VB_WFMT_X3 = 2, VB_WFMT_MF = 3, VB_WFMT_BUF_F32 = 4, VB_WFMT_BUF_X3 = 5, VB_WFMT_BF16 = 6 };
 #define VB_BUF_INPUT (-2)
 #define VB_BUF_OUTPUT (-3)
 typedef struct {
@@ -390,6 +395,24 @@ int vb_respair_f32(const float* x, const float* w1, const float* b1, const float
  * roundoff (about a third of the elements differ by one ulp, < 4e-6 of the output's max-abs), not bit for bit. */
 int vb_respair_f32_mf(const float* x, const float* w1_mf, const float* b1, const float* w2_mf, const float* b2, int B, int C, int T, int k, int dil,
                       float slope, float alpha, float beta, float* out, void* stream);
+/* Conv1d / ConvTranspose1d in single-pass bf16 (conv1d_bf16.hip), the arithmetic of the conv nets' "bf16" precision, stated exactly:
+ *   out = beta*out + alpha*( sum_{ci,j} RN_bf16(W)[j][co][ci] * RN_bf16( act_in(x)[ci][t + j*dil - pad] ) + bias + res )
+ * act_in = none / LeakyReLU / GroupNorm affine (+ swish) from gn_mean / gn_rstd [B][gn_groups] and gn_gamma / gn_beta [Ci], applied to the
+ * nearest-x2 upsampled (upsample2) or strided (x[i*in_stride + in_phase]) input and padded with zeros AFTER the activation; the
+ * activations are rounded to bf16 (round to nearest even) after it; products are exact in fp32 and accumulated in fp32, so only the
+ * accumulation order is free.  w_bf16 = ONE plane [phase][tap][Co][ci_pad] (pack.py:pack_conv_bf16, ci_pad = Ci rounded up to 32,
+ * 16-byte aligned); the remaining arguments as vb_conv1d_f32.  Not within the 1e-3 parity contract (operand error 2^-9). */
+int vb_conv1d_bf16(const float* x, const void* w_bf16, int ci_pad, const float* bias, int B, int Ci, int T_in, int Co, int ksize, int dil,
+                   int pad, int tr_stride, int tr_pad, int tr_k, int T_out, int upsample2, int in_stride, int in_phase, int in_act,
+                   float in_slope, const float* gn_mean, const float* gn_rstd, const float* gn_gamma, const float* gn_beta, int gn_groups,
+                   const float* res, float alpha, float beta, float* out, void* stream);
+/* HiFi-GAN ResBlock1 pair in single-pass bf16, one launch (respair_bf16.hip):
+ *   out = beta*out + alpha*(x + b2 + conv2_{k,1}( RN_bf16( lrelu(b1 + conv1_{k,dil}( RN_bf16(lrelu(x)) )) ) ))
+ * both convolutions with RN-bf16 weights (w1_bf16 / w2_bf16: one plane [k][C co][C ci] each, pack.py:pack_conv_bf16), exact products, fp32
+ * accumulation; the intermediate is rounded to bf16 once and zero outside [0, T).  x / out [B][C][T] (distinct buffers); C = 32 / 64, odd k,
+ * (k-1)*dil <= 64.  Equals two vb_conv1d_bf16 launches up to the accumulation order. */
+int vb_respair_bf16(const float* x, const void* w1_bf16, const float* b1, const void* w2_bf16, const float* b2, int B, int C, int T, int k,
+                    int dil, float slope, float alpha, float beta, float* out, void* stream);
 /* counter-based Gumbel draws: out[rows][w], rows = n_branch*B*T */
 int vb_fill_gumbel(float* out, int B, int n_branch, int T, int width, uint64_t seed, int64_t clip_base, int nfe, int block, int gate,
                    void* stream);

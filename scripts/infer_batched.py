@@ -32,8 +32,9 @@ from versband_amd.model import normalize_loudness  # noqa: E402
 
 
 def parse_args(argv=None):
-    """--items_per_batch and --synthetic_frames are taken out of the command line here; every other flag goes through test_final.py's own
-    parser (which reads sys.argv and is not ours to change: it sees the remaining arguments for the length of its call)"""
+    """--items_per_batch, --synthetic_frames and --vocoder_precision are taken out of the command line here; every other flag goes through
+    test_final.py's own parser (which reads sys.argv and is not ours to change: it sees the remaining arguments for the length of its call).
+    --vocoder_precision is that parser's flag with one more choice, "bf16", the preview mode only this CLI offers."""
     from unittest import mock
     own = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
     own.add_argument("--items_per_batch", type=int, default=1,
@@ -42,6 +43,9 @@ def parse_args(argv=None):
                           "(default 1: that loop's calls).  items x guided scales x n_samples may not exceed 32 rows")
     own.add_argument("--synthetic_frames", type=str, default="1500",
                      help="mel frames of a synthetic item: one integer, or a comma list that cycles over the items (150,150,230)")
+    own.add_argument("--vocoder_precision", type=str, default="fp32mf", choices=["fp32mf", "fp32", "split", "bf16"],
+                     help="VAE + vocoder arithmetic: test_final.py's fp32mf (default) / fp32 / split, and bf16 = ONE bf16 pass per convolution (bf16 "
+                          "operands, fp32 accumulation): preview quality, outside the 1e-3 parity bound")
     argv = list(sys.argv[1:] if argv is None else argv)
     if "-h" in argv or "--help" in argv:
         own.print_help()
@@ -50,6 +54,7 @@ def parse_args(argv=None):
     with mock.patch.object(sys, "argv", [sys.argv[0]] + rest):
         args = loop.parse_args()
     args.items_per_batch, args.synthetic_frames = mine.items_per_batch, parse_frames(mine.synthetic_frames)
+    args.vocoder_precision = mine.vocoder_precision
     check_items_per_batch(args.items_per_batch, list(dict.fromkeys(_scales(args))), args.n_samples)
     return args
 

@@ -88,7 +88,7 @@ class NetOp(C.Structure):
 
 OP_CONV, OP_GN_STATS, OP_SOFTMAX_T, OP_SPLIT_PLANES, OP_RESPAIR, OP_GN_APPLY, OP_AA_ACT, OP_XT_PLANES = 0, 1, 2, 3, 4, 5, 6, 7
 ACT_NONE, ACT_LRELU, ACT_GN_SWISH, ACT_TANH, ACT_GN = 0, 1, 2, 3, 4
-WFMT_NONE, WFMT_F32, WFMT_X3, WFMT_MF, WFMT_BUF_F32, WFMT_BUF_X3 = 0, 1, 2, 3, 4, 5
+WFMT_NONE, WFMT_F32, WFMT_X3, WFMT_MF, WFMT_BUF_F32, WFMT_BUF_X3, WFMT_BF16 = 0, 1, 2, 3, 4, 5, 6
 BUF_INPUT, BUF_OUTPUT = -2, -3
 NET_VAE, NET_VOCODER, NET_VAE_ENCODER = 0, 1, 2
 
@@ -141,6 +141,9 @@ PROTOTYPES = {
     "vb_conv1d_f32_mf": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P, c_float, c_float, P, P]),
     "vb_respair_f32_mf": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, P, P]),
     "vb_respair_f32": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, P, P]),
+    "vb_conv1d_bf16": (c_int, [P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                               c_int, c_float, P, P, P, P, c_int, P, c_float, c_float, P, P]),
+    "vb_respair_bf16": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, P, P]),
     "vb_fill_gumbel": (c_int, [P, c_int, c_int, c_int, c_int, c_u64, c_i64, c_int, c_int, c_int, P]),
     "vb_cast_planes": (c_int, [P, c_i64, P, c_int, P]),
 }

@@ -87,6 +87,31 @@ int vb_respair_f32_mf(const float* x, const float* w1_mf, const float* b1, const
     a.slope = slope; a.alpha = alpha; a.beta = beta;
     return launch_respair_f32w(a, (hipStream_t)stream);
 }
+int vb_conv1d_bf16(const float* x, const void* w_bf16, int ci_pad, const float* bias, int B, int Ci, int T_in, int Co, int ksize, int dil,
+                   int pad, int tr_stride, int tr_pad, int tr_k, int T_out, int upsample2, int in_stride, int in_phase, int in_act,
+                   float in_slope, const float* gn_mean, const float* gn_rstd, const float* gn_gamma, const float* gn_beta, int gn_groups,
+                   const float* res, float alpha, float beta, float* out, void* stream) {
+    if (!x || !w_bf16 || !out || B < 1 || T_in < 1 || T_out < 1 || Ci < 1 || Co < 1) VB_FAIL(VB_E_INVALID, "conv1d_bf16: null pointer or B/T/Ci/Co < 1");
+    if ((in_act == ACT_GN || in_act == ACT_GN_SWISH) && (!gn_mean || !gn_rstd || !gn_gamma || !gn_beta || gn_groups < 1))
+        VB_FAIL(VB_E_INVALID, "conv1d_bf16: GroupNorm input without its statistics / affine");
+    ConvArgs a;
+    a.wp = (const bf16_t*)w_bf16; a.Ci_pad = ci_pad; a.wp_bf16 = true;
+    a.x = x; a.x_bstride = (int64_t)Ci * T_in; a.Ci = Ci; a.T_in = T_in; a.bias = bias; a.Co = Co; a.ksize = ksize;
+    a.dil = dil; a.pad = pad; a.upsample2 = upsample2; a.in_stride = in_stride > 1 ? in_stride : 1; a.in_phase = in_phase;
+    a.in_act = in_act; a.in_slope = in_slope; a.gn_mean = gn_mean; a.gn_rstd = gn_rstd; a.gn_gamma = gn_gamma; a.gn_beta = gn_beta;
+    a.gn_groups = gn_groups > 0 ? gn_groups : 32;
+    a.out = out; a.out_bstride = (int64_t)Co * T_out; a.T_out = T_out; a.res = res; a.res_bstride = (int64_t)Co * T_out; a.B = B;
+    a.alpha = alpha; a.beta = beta; a.tr_stride = tr_stride; a.tr_pad = tr_pad; a.tr_k = tr_k;
+    return launch_conv1d(a, (hipStream_t)stream);
+}
+int vb_respair_bf16(const float* x, const void* w1_bf16, const float* b1, const void* w2_bf16, const float* b2, int B, int C, int T, int k,
+                    int dil, float slope, float alpha, float beta, float* out, void* stream) {
+    if (!x || !w1_bf16 || !b1 || !w2_bf16 || !b2 || !out || B < 1 || T < 1) VB_FAIL(VB_E_INVALID, "respair_bf16: null pointer or B/T < 1");
+    RespairArgs a;
+    a.x = x; a.out = out; a.B = B; a.C = C; a.T = T; a.k = k; a.dil = dil; a.w1 = (const bf16_t*)w1_bf16; a.w2 = (const bf16_t*)w2_bf16;
+    a.b1 = b1; a.b2 = b2; a.slope = slope; a.alpha = alpha; a.beta = beta;
+    return launch_respair_bf16(a, (hipStream_t)stream);
+}
 int vb_fill_gumbel(float* out, int B, int n_branch, int T, int width, uint64_t seed, int64_t clip_base, int nfe, int block, int gate,
                    void* stream) {
     return launch_fill_gumbel(out, B, n_branch, T, width, seed, clip_base, nfe, nullptr, block, gate, (hipStream_t)stream);

@@ -19,7 +19,7 @@ struct ConvDev {
     int out_act; float out_slope;
     int out_transposed; const float* add; int64_t add_bstride; int add_bmod;
     int phases, tr_pad;      // phases == 1: ordinary convolution
-    const bf16_t* wp; int64_t wp_plane; int Ci_pad;   // split-bf16 weights [2 planes][phase][tap][Co][Ci_pad]
+    const bf16_t* wp; int64_t wp_plane; int Ci_pad;   // split-bf16 weights [2 planes][phase][tap][Co][Ci_pad] (conv1d_bf16_kernel: plane 0 alone)
     int64_t wp_bstride;
     const bf16_t* xt; int64_t xt_plane; int xt_Tp;     // pre-activated transposed split planes of the input (XT mode)
     const float* ww;         // conv1d_f32w_kernel: minimal-filtering (F(2,3)) pseudo-tap weights [P][Ci][Co], pack.py:pack_conv_mf
@@ -210,3 +210,5 @@ void launch_conv1d_f32g(ConvDev& d, int n_count, int B, int upsample2, hipStream
 bool conv1d_f32w_eligible(const ConvArgs& a, const ConvDev& d);
 int conv1d_f32w_pseudo_taps(int ksize);
 void launch_conv1d_f32w(ConvDev& d, int B, hipStream_t st);
+// conv1d_bf16.hip: single-pass bf16 (RN-bf16 weights x RN-bf16 activated input, fp32 accumulation); d.wp = ONE plane [phase][tap][Co][Ci_pad]
+int launch_conv1d_bf16(const ConvDev& d, int n_count, int B, hipStream_t st);

@@ -458,6 +458,7 @@ static int conv1d_fill(const ConvArgs& a, ConvDev& d, int& n_count) {
     d.out_transposed = a.out_transposed; d.add = a.add; d.add_bstride = a.add_bstride; d.add_bmod = a.add_bmod;
     d.wp = a.wp; d.wp_plane = a.wp_plane; d.Ci_pad = a.Ci_pad; d.wp_bstride = a.wp_bstride;
     d.xt = a.xt; d.xt_Tp = xt_rows(a.upsample2 ? 2 * a.T_in : a.T_in); d.xt_plane = (int64_t)a.B * d.xt_Tp * a.Ci;
+    if (a.wp_bf16 && (!a.wp || a.xt || a.wp_bstride || a.w_mf)) VB_FAIL(VB_E_INVALID, "conv1d: bf16 weights are one shared plane (no XT input, no per-clip or minimal-filtering weights)");
     if (a.xt && (a.Ci % CK3 || a.tr_stride > 1 || a.in_stride > 1 || !a.wp || a.x_bmod || a.pad > XT_HEAD))
         VB_FAIL(VB_E_INVALID, "conv1d: XT input needs Ci %% 32 == 0, stride 1, split weights, pad <= %d", XT_HEAD);
     d.stage_epi = 0;
@@ -507,7 +508,7 @@ static bool conv1d_co1_eligible(const ConvArgs& a, const ConvDev& d) {
 // conv1d_x3_kernel: split-bf16 weights are there - and per clip where the fp32 ones are
 static bool conv1d_x3_eligible(const ConvArgs& a) { return a.wp && (!a.w_bstride || a.wp_bstride); }
 
-enum ConvRoute { CONV_AS_GEMM, CONV_F32W, CONV_CO1, CONV_X3_XT, CONV_X3, CONV_F32G, CONV_F32 };
+enum ConvRoute { CONV_AS_GEMM, CONV_F32W, CONV_CO1, CONV_BF16, CONV_X3_XT, CONV_X3, CONV_F32G, CONV_F32 };
 // Which kernel runs: the first candidate, in this order, whose conditions hold and whose A/B knob has not switched it off; the register-staged
 // fp32 kernel takes everything.  Settles d.stage_epi on the way (VB_CONV_DIRECT_EPI=1: the direct epilogue - no minimal filtering then).
 static ConvRoute conv1d_route(const ConvArgs& a, ConvDev& d) {
@@ -516,6 +517,7 @@ static ConvRoute conv1d_route(const ConvArgs& a, ConvDev& d) {
     d.stage_epi = (conv1d_stage_epi_eligible(a) && !tune.conv_direct_epi) ? 1 : 0;
     if (conv1d_f32w_eligible(a, d) && !tune.conv_mf_off) return CONV_F32W;
     if (conv1d_co1_eligible(a, d) && !tune.conv_f32_old) return CONV_CO1;             // (VB_CONV_F32_OLD=1: the MFMA kernels)
+    if (a.wp_bf16) return CONV_BF16;                                                  // one weight plane: no other kernel reads it
     if (conv1d_x3_eligible(a)) return a.xt ? CONV_X3_XT : CONV_X3;
     // exact fp32, DMA-fed; VB_CONV_F32_OLD=1 keeps the register-staged kernel (bit-identical, tests compare the two)
     if (conv1d_f32g_eligible(a, d) && !tune.conv_f32_old) return CONV_F32G;
@@ -537,6 +539,7 @@ int launch_conv1d(const ConvArgs& a, hipStream_t st) {
         case CONV_AS_GEMM: break;      // (left above)
         case CONV_F32W: d.ww = a.w_mf; launch_conv1d_f32w(d, a.B, st); break;
         case CONV_CO1: hipLaunchKernelGGL(conv1d_co1_kernel, dim3(cdiv(a.T_out, C1_TT), a.B), dim3(256), 0, st, d); break;
+        case CONV_BF16: VB_TRY(launch_conv1d_bf16(d, n_count, a.B, st)); break;
         case CONV_X3_XT:
         case CONV_X3: {
             if (a.Ci_pad % CK3) VB_FAIL(VB_E_INVALID, "conv1d: split weights need Ci_pad %% %d == 0", CK3);

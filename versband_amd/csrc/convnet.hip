@@ -79,6 +79,11 @@ int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, v
                 a.wp = (const bf16_t*)o.w_x3; a.Ci_pad = o.ci_pad; a.wp_plane = (int64_t)phases * ntaps * a.Co * o.ci_pad;
                 break;
             }
+            case VB_WFMT_BF16: {
+                a.w = o.w;                                            // (Co = 1 only: the one-output-channel kernel's fp32 weights)
+                a.wp = (const bf16_t*)o.w_x3; a.Ci_pad = o.ci_pad; a.wp_bf16 = true;         // (one plane: no plane stride)
+                break;
+            }
             case VB_WFMT_BUF_F32: a.w = ptr(o.w_buf); a.w_bstride = bstride(o.w_buf); break;
             case VB_WFMT_BUF_X3:
                 // per-batch split planes [2][B][Co][Ci_pad] written by an earlier VB_OP_SPLIT_PLANES
@@ -99,12 +104,13 @@ int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, v
         } else if (o.kind == VB_OP_AA_ACT) {
             VB_TRY(launch_aa_act(ptr(o.x), o.gn_gamma, o.gn_beta, o.w, B, o.Ci, tlen(o.x), ptr(o.out), st));
         } else if (o.kind == VB_OP_RESPAIR) {
-            if (o.wfmt == VB_WFMT_X3) {
+            if (o.wfmt == VB_WFMT_X3 || o.wfmt == VB_WFMT_BF16) {
                 RespairArgs r;
                 r.x = ptr(o.x); r.out = ptr(o.out); r.B = B; r.C = o.Ci; r.T = tlen(o.x); r.k = o.ksize; r.dil = o.dil;
                 r.w1 = (const bf16_t*)o.w_x3; r.w2 = (const bf16_t*)o.w2; r.b1 = o.bias; r.b2 = o.bias2;
                 r.slope = o.in_slope; r.alpha = o.alpha; r.beta = o.beta;
-                VB_TRY(launch_respair(r, st));
+                if (o.wfmt == VB_WFMT_BF16) VB_TRY(launch_respair_bf16(r, st));
+                else VB_TRY(launch_respair(r, st));
             } else {
                 RespairF32Args r;
                 r.x = ptr(o.x); r.out = ptr(o.out); r.B = B; r.C = o.Ci; r.T = tlen(o.x); r.k = o.ksize; r.dil = o.dil;
@@ -126,13 +132,14 @@ int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, v
 
 // the weight fields each allowed (kind, wfmt) pair of include/versband_hip.h reads; -1 = the pair is not allowed
 enum { NW_W = 1, NW_X3 = 2, NW_MF = 4, NW_W2 = 8, NW_BUF = 16 };
-static int net_op_fields(int kind, int wfmt) {
+static int net_op_fields(int kind, int wfmt, int Co) {
     switch (kind) {
     case VB_OP_CONV:
         switch (wfmt) {
         case VB_WFMT_F32: return NW_W;
         case VB_WFMT_X3: return NW_X3 | NW_W;
         case VB_WFMT_MF: return NW_MF | NW_W;
+        case VB_WFMT_BF16: return NW_X3 | (Co == 1 ? NW_W : 0);
         case VB_WFMT_BUF_F32: case VB_WFMT_BUF_X3: return NW_BUF;
         }
         return -1;
@@ -141,6 +148,7 @@ static int net_op_fields(int kind, int wfmt) {
         case VB_WFMT_F32: return NW_W | NW_W2;
         case VB_WFMT_X3: return NW_X3 | NW_W2;
         case VB_WFMT_MF: return NW_MF | NW_W2;
+        case VB_WFMT_BF16: return NW_X3 | NW_W2;
         }
         return -1;
     case VB_OP_AA_ACT: return wfmt == VB_WFMT_NONE ? NW_W : -1;
@@ -161,7 +169,7 @@ int vb_net_load(vb_ctx* ctx, int which, const vb_net_op* ops, int n_ops, const v
         const int ids[5] = {o.x, o.out, o.res, o.stats, o.w_buf};
         for (int id : ids)
             if (id >= n_bufs || (id < -3)) VB_FAIL(VB_E_INVALID, "net_load: op %d references buffer %d of %d", i, id, n_bufs);
-        const int f = net_op_fields(o.kind, o.wfmt);
+        const int f = net_op_fields(o.kind, o.wfmt, o.Co);
         if (f < 0) VB_FAIL(VB_E_INVALID, "net_load: op %d: kind %d has no weight format %d", i, o.kind, o.wfmt);
         const struct { int bit; bool set; const char* name; } slots[] = {
             {NW_W, o.w != nullptr, "w"}, {NW_X3, o.w_x3 != nullptr, "w_x3"}, {NW_MF, o.w_mf != nullptr, "w_mf"}, {NW_W2, o.w2 != nullptr, "w2"},
@@ -170,13 +178,14 @@ int vb_net_load(vb_ctx* ctx, int which, const vb_net_op* ops, int n_ops, const v
             if (sl.set != ((f & sl.bit) != 0))
                 VB_FAIL(VB_E_INVALID, "net_load: op %d (kind %d, weight format %d): %s is %s", i, o.kind, o.wfmt, sl.name,
                         sl.set ? "set but not read" : "missing");
-        if (o.wfmt == VB_WFMT_X3 && o.ci_pad != (o.Ci + 31) / 32 * 32)
+        if ((o.wfmt == VB_WFMT_X3 || o.wfmt == VB_WFMT_BF16) && o.ci_pad != (o.Ci + 31) / 32 * 32)
             VB_FAIL(VB_E_INVALID, "net_load: op %d: split weights padded to %d input channels, not %d rounded up to 32", i, o.ci_pad, o.Ci);
         if (o.wfmt == VB_WFMT_MF && (!aligned16(o.w_mf) || !aligned16(o.w2)))
             VB_FAIL(VB_E_INVALID, "net_load: op %d: minimal-filtering weights are not 16-byte aligned", i);
         if (o.kind == VB_OP_RESPAIR) {
             if (!o.bias || !o.bias2) VB_FAIL(VB_E_INVALID, "net_load: op %d: respair without both biases", i);
             if (o.Ci != o.Co) VB_FAIL(VB_E_INVALID, "net_load: op %d: respair with Ci %d != Co %d", i, o.Ci, o.Co);
+            if (o.wfmt == VB_WFMT_BF16 && o.Ci != 32 && o.Ci != 64) VB_FAIL(VB_E_INVALID, "net_load: op %d: bf16 respair with %d channels (32 or 64)", i, o.Ci);
             if (o.x == -1 || o.out == -1 || tmul(o.x) != tmul(o.out))
                 VB_FAIL(VB_E_INVALID, "net_load: op %d: respair input and output differ in length", i);
         }

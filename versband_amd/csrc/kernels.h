@@ -127,6 +127,7 @@ struct ConvArgs {
     // optional split-bf16 weights [2][phase][tap][Co][Ci_pad] (Ci_pad % 32 == 0): selects the bf16x3 MFMA kernel
     const bf16_t* wp = nullptr; int64_t wp_plane = 0; int Ci_pad = 0;
     int64_t wp_bstride = 0;          // per-batch split weights (bf16 elements inside a plane), VAE attention
+    bool wp_bf16 = false;            // wp holds ONE plane (the round-to-nearest bf16 weights): the single-pass bf16 kernel (conv1d_bf16.hip)
     // optional pre-activated transposed split planes of the input (xt_planes_kernel): [2][B][xt_rows(T_in)][Ci]; x / in_act /
     // GroupNorm fields are then ignored and the window is DMA'd straight into LDS
     const bf16_t* xt = nullptr;
@@ -142,6 +143,8 @@ struct RespairArgs {
     float slope = 0.1f, alpha = 1.f, beta = 0.f;
 };
 int launch_respair(const RespairArgs& a, hipStream_t st);
+// the same pair in single-pass bf16 (respair_bf16.hip): w1 / w2 = ONE plane [k][C][C] each, the intermediate rounded to bf16 once; C = 32 / 64
+int launch_respair_bf16(const RespairArgs& a, hipStream_t st);
 // the same pair in exact fp32 (respair_f32.hip; v_mfma_f32_32x32x2_f32, weights fp32 packed [k][Ci][Co]): C = 32 / 64 / 128
 struct RespairF32Args {
     const float* x = nullptr; float* out = nullptr; int B = 1, C = 0, T = 0, k = 3, dil = 1;

@@ -13,7 +13,7 @@
 //   * conv2 over hT, + b2 + residual x, alpha/beta accumulation into the MRF sum, coalesced stores (a lane owns one t).
 // Same operand precision as conv1d_x3_kernel (operand error 2^-17, fp32 accumulate).
 #include "kernels.h"
-#include "dma_ring.h"
+#include "respair_epi.h"
 
 #define RP_T 128            // intermediate positions per workgroup (4 waves x 32)
 #define RP_HALO 64          // max (k-1)*dil of conv1
@@ -193,73 +193,9 @@ __global__ void __launch_bounds__(256) respair_x3_kernel(const PairDev p) {
         taps(p.w2, ch * 32, &hT[ch][0][0], &hT[ch][1][0], 1);
     }
     fold_acc();
-    // ---- epilogue.  The accumulator gives a lane ONE output sample and 16 channels; moved like that every residual /
-    // accumulate-into load and every store is a 4-byte lane access.  When the rows are 16-B aligned (T % 4 == 0) each wave passes
-    // its 32 x 32 tiles through a private LDS patch instead (xh is free: conv2's last barrier is behind every wave) and comes
-    // back with 4 consecutive samples of one channel per lane - 16-byte accesses, whole 128-B lines per 8 lanes; same
-    // arithmetic per element (see conv_epilogue_staged in conv1d_f32.hip).
-    constexpr int EP = 36;
-    static_assert(sizeof(xh) >= 4 * 32 * EP * sizeof(float), "staging patches must fit");
-    if (p.staged) {
-        float* patch = reinterpret_cast<float*>(xh) + wave * (32 * EP);
-        const int rr = lane >> 3, t4 = (lane & 7) * 4;
-        const int nl = 32 * wave + t4;
-        const int n = n0 + nl;
-        const bool nok = nl < TT && n < p.T;
-        float* ob = p.out + (int64_t)b * p.bstride;
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) patch[(4 * g + 8 * (r >> 2) + (r & 3)) * EP + l31] = acc[i][r];
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            float4 v[4], rv[4], ov[4];
-            float bv[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int co = i * 32 + rr + 8 * k;
-                v[k] = *reinterpret_cast<const float4*>(patch + (rr + 8 * k) * EP + t4);
-                const int64_t oi = (int64_t)co * p.T + (nok ? n : 0);
-                rv[k] = nok ? *reinterpret_cast<const float4*>(xb + oi) : make_float4(0.f, 0.f, 0.f, 0.f);
-                ov[k] = (nok && p.beta != 0.f) ? *reinterpret_cast<const float4*>(ob + oi) : make_float4(0.f, 0.f, 0.f, 0.f);
-                bv[k] = p.b2[co];
-            }
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            if (nok) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int co = i * 32 + rr + 8 * k;
-                    const float a4[4] = {v[k].x, v[k].y, v[k].z, v[k].w}, r4[4] = {rv[k].x, rv[k].y, rv[k].z, rv[k].w};
-                    const float o4[4] = {ov[k].x, ov[k].y, ov[k].z, ov[k].w};
-                    float q[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) q[e] = pair_out_value(p.alpha, p.beta, a4[e], bv[k], r4[e], o4[e]);
-                    *reinterpret_cast<float4*>(ob + (int64_t)co * p.T + n) = make_float4(q[0], q[1], q[2], q[3]);
-                }
-            }
-        }
-    } else {
-        const int nl = 32 * wave + l31;
-        const int n = n0 + nl;
-        const bool nok = nl < TT && n < p.T;
-        float* ob = p.out + (int64_t)b * p.bstride;
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-            float rv[16], ov[16], bv[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = i * 32 + 4 * g + 8 * (r >> 2) + (r & 3);
-                rv[r] = nok ? xb[(int64_t)co * p.T + n] : 0.f;
-                ov[r] = (nok && p.beta != 0.f) ? ob[(int64_t)co * p.T + n] : 0.f;
-                bv[r] = p.b2[co];
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = i * 32 + 4 * g + 8 * (r >> 2) + (r & 3);
-                if (!nok) continue;
-                ob[(int64_t)co * p.T + n] = pair_out_value(p.alpha, p.beta, acc[i][r], bv[r], rv[r], ov[r]);
-            }
-        }
-    }
+    // ---- epilogue (respair_epi.h; xh is free: conv2's last barrier is behind every wave)
+    static_assert(sizeof(xh) >= PAIR_EPI_FLOATS * sizeof(float), "staging patches must fit");
+    pair_epilogue<CH>(acc, reinterpret_cast<float*>(xh), p.staged, xb, p.out + (int64_t)b * p.bstride, p.T, n0, TT, p.b2, p.alpha, p.beta);
 }
 
 

@@ -389,11 +389,14 @@ class NetBuilder:
     """Flattens a conv network into the vb_net_op list executed by the C++ runtime."""
 
     def __init__(self, device, precision: str = "split"):
-        assert precision in ("split", "fp32", "fp32mf")
+        assert precision in ("split", "fp32", "fp32mf", "bf16")
         self.device = device
         # "split": bf16x3 MFMA conv kernels (fp32-class); "fp32": the exact-fp32 MFMA kernels; "fp32mf": the fp32 op list in which the
-        # layers of mf_conv_eligible and the 32 / 64-channel pairs run F(2,3) minimal filtering (fp32 products, ~1.45x fewer)
+        # layers of mf_conv_eligible and the 32 / 64-channel pairs run F(2,3) minimal filtering (fp32 products, ~1.45x fewer);
+        # "bf16": the split op list without the DMA-fed input planes, every static-weight convolution and 32 / 64-channel pair in ONE
+        # bf16 pass (RN-bf16 weights x RN-bf16 activated input, fp32 accumulation: outside the 1e-3 parity contract, DESIGN.md section 2)
         self.precision = precision
+        self.x3_like = precision in ("split", "bf16")      # the op list's shape: fused input transforms, split planes for per-clip weights
         self.ops: List[L.NetOp] = []
         self.bufs: List[Tuple[int, int, int]] = []
         self.free: Dict[Tuple[int, int, int], List[int]] = {}
@@ -433,8 +436,13 @@ class NetBuilder:
         layer qualifies for minimal filtering (fp32mf only); fallback: an X3 / MF conv keeps w as well (what the one-output-channel
         kernel and the direct kernels read)."""
         if w_buf != -1:
-            return dict(wfmt=L.WFMT_BUF_X3 if self.precision == "split" else L.WFMT_BUF_F32)
-        if self.precision == "split":
+            return dict(wfmt=L.WFMT_BUF_X3 if self.x3_like else L.WFMT_BUF_F32)
+        if self.precision == "bf16":
+            plane, ci_pad = pack.pack_conv_bf16(w.to(self.device))
+            self.keep.append(plane)
+            f = dict(wfmt=L.WFMT_BF16, w_x3=plane.data_ptr(), ci_pad=ci_pad)
+            fallback = fallback and w.shape[-1] == 1       # no fp32 copy except where the op reads w (one output channel)
+        elif self.precision == "split":
             planes, ci_pad = pack.pack_conv_x3(w.to(self.device))
             self.keep.append(planes)
             f = dict(wfmt=L.WFMT_X3, w_x3=planes.data_ptr(), ci_pad=ci_pad)
@@ -453,7 +461,7 @@ class NetBuilder:
         VB_MF_PAIRS_OFF=1 the direct pair kernel."""
         mf = ch in (32, 64) and k in (3, 7, 11) and not os.environ.get("VB_MF_PAIRS_OFF")
         f = self.weights(w1, mf=mf, fallback=False)
-        slot = {L.WFMT_F32: "w", L.WFMT_X3: "w_x3", L.WFMT_MF: "w_mf"}[f["wfmt"]]     # the second convolution's weights go to w2
+        slot = {L.WFMT_F32: "w", L.WFMT_X3: "w_x3", L.WFMT_MF: "w_mf", L.WFMT_BF16: "w_x3"}[f["wfmt"]]     # the second convolution's weights go to w2
         f["w2"] = self.weights(w2, mf=mf, fallback=False)[slot]
         self.ops.append(L.NetOp(kind=L.OP_RESPAIR, x=x, out=out, res=-1, stats=-1, w_buf=-1, bias=self._t(b1), bias2=self._t(b2), Ci=ch, Co=ch,
                                 ksize=k, dil=dil, in_slope=slope, alpha=alpha, beta=beta, **f))
@@ -484,7 +492,7 @@ class NetBuilder:
             # tile of the convolution DMAs its window from there, instead of each tile redoing norm / swish / split while staging
             tmp = self.xt_planes(x, Ci, stats, gamma, beta_gn, in_act, in_slope, upsample2, groups)
             x, stats, gamma, beta_gn, in_act, x_planes = tmp, -1, None, None, L.ACT_NONE, 1
-        if (self.precision != "split" and in_act in (L.ACT_GN_SWISH, L.ACT_GN) and stats >= 0 and w is not None and w_buf == -1 and x >= 0
+        if (not self.x3_like and in_act in (L.ACT_GN_SWISH, L.ACT_GN) and stats >= 0 and w is not None and w_buf == -1 and x >= 0
                 and Ci % 16 == 0 and Co % 4 == 0 and in_stride == 1 and tr_stride == 1 and not os.environ.get("VB_FP32_NO_PREPASS")):
             # exact-fp32 mode: GroupNorm (+ swish) is applied ONCE by gn_apply_kernel and the DMA-fed fp32 kernel (conv1d_f32g_kernel)
             # reads the activated tensor; the register-staged kernel redid norm + swish + expf for every output-channel tile
@@ -614,10 +622,10 @@ def _vae_block_builders(nb: "NetBuilder", g: Dict[str, Tensor]):
         # "weights" are per-batch activations.  split mode: those activations are split into bf16 hi/lo planes on the
         # device (q as [T][C], v as [C][T padded to 32]) so the bf16x3 MFMA kernel does the products too.
         st = nb.gn_stats(x, c)
-        split = nb.precision == "split"
+        split = nb.x3_like       # (bf16: the per-clip products stay on the bf16x3 kernel, the q / k / v projections fuse the norm)
         q, k, v = nb.buf(c, tm), nb.buf(c, tm), nb.buf(c, tm)
         gam, bet = g[p + "norm.weight"], g[p + "norm.bias"]
-        xn = nb.xt_planes(x, c, st, gam, bet, L.ACT_GN, 0.0, 0) if (split and c >= nb.XT_MIN_CO and c % 32 == 0) else -1
+        xn = nb.xt_planes(x, c, st, gam, bet, L.ACT_GN, 0.0, 0) if (nb.precision == "split" and c >= nb.XT_MIN_CO and c % 32 == 0) else -1
         for name, dst, tr in (("q", q, 1 if split else 0), ("k", k, 0), ("v", v, 0 if split else 1)):
             w, b = cw(p + name)
             if xn >= 0:
@@ -778,7 +786,7 @@ def build_hifigan(ctx: Context, sd: Dict[str, Tensor], hp: dict, precision: str 
                 al, be = (1.0 / nk, 0.0 if j == 0 else 1.0) if last else (1.0, 0.0)
                 # (fp32 pair kernel: 16-byte window DMA needs T % 4 == 0 - guaranteed for every mel length, chunked runs included, when the
                 #  stage's length multiplier is a multiple of 4; other stages keep the two unfused launches)
-                fuse = (ch in fuse_pairs and (rk - 1) * d <= 64) if precision == "split" else \
+                fuse = (ch in fuse_pairs and (rk - 1) * d <= 64) if precision in ("split", "bf16") else \
                        (ch in fp32_pairs and (rk - 1) * d <= 60 and rk <= 17 and tm % 4 == 0)
                 if hp["resblock"] == "1" and fuse and rk % 2 == 1:
                     # narrowest, longest stage: both convolutions of the pair in one launch, intermediate kept in LDS

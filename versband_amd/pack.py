@@ -84,6 +84,18 @@ def pack_conv_x3(w_packed: Tensor, ci_multiple: int = 32):
     return to_planes(w.contiguous(), 2), cip
 
 
+def pack_conv_bf16(w_packed: Tensor, ci_multiple: int = 32):
+    """fp32 packed conv weights [..taps.., Ci, Co] -> ONE plane [1, taps, Co, Ci_pad] of round-to-nearest bf16 weights for the single-pass
+    bf16 conv kernels: bit-equal to plane 0 of pack_conv_x3 (the weight format of the "bf16" precision is "the first plane of X3").
+    Returns (plane, Ci_pad)."""
+    ci, co = w_packed.shape[-2], w_packed.shape[-1]
+    w = w_packed.reshape(-1, ci, co).permute(0, 2, 1).float()
+    cip = (ci + ci_multiple - 1) // ci_multiple * ci_multiple
+    if cip != ci:
+        w = torch.nn.functional.pad(w, (0, cip - ci))
+    return to_planes(w.contiguous(), 1), cip
+
+
 def fold_weight_norm(g: Tensor, v: Tensor) -> Tensor:
     """weight_norm(dim=0): w = g * v / ||v|| (the reference never removes weight norm:
     vocoder/hifigan/hifigan.py:15-18, so checkpoints carry weight_g / weight_v)."""
