@@ -535,7 +535,7 @@ def _at(t, off):
 
 @pytest.mark.parametrize("C,k,dil", [(64, 3, 1), (64, 7, 3), (64, 11, 5), (128, 3, 1), (128, 7, 3), (128, 11, 5)])
 def test_fp32_minimal_filtering_falls_back_to_the_direct_kernel(lib, C, k, dil):
-    """vb_conv1d_f32_mf takes the minimal-filtering kernel only when the run allows it (conv1d_f32.hip, use_mf: T % 4 == 0, row strides % 4,
+    """vb_conv1d_f32_mf takes the minimal-filtering kernel only when the run allows it (conv1d.hip, conv1d_route: T % 4 == 0, row strides % 4,
     16-B aligned x / out / res, Ci % 16 == 0, Co >= 32); otherwise it runs the direct kernels on w - the call must then return exactly the bits
     of vb_conv1d_f32 on the same pointers (odd latent lengths of the VAE and chunk windows of long-form vocoding take this path), and stay at
     fp32 roundoff from float64.  Control: the same layer at T = 1000 with aligned buffers takes minimal filtering, so it must NOT equal the
@@ -717,6 +717,36 @@ def test_fp32_respair_equals_two_fp32_convolutions(lib, B, C, T, k, dil, alpha, 
     assert rel_l2(fused, ref64) < 2e-6, describe("respair fp32", fused, ref64)
     if alpha == 1.0 and beta == 0.0:
         assert torch.equal(fused, t2), f"fused pair vs two launches differ by {float((fused - t2).abs().max()):.3e}"
+
+
+@pytest.mark.parametrize("B,C,T,k,dil,alpha,beta", [(2, 32, 1000, 3, 1, 1.0, 0.0), (1, 32, 203, 11, 5, 1.0 / 3, 1.0), (2, 64, 1000, 7, 3, 1.0, 0.0),
+                                                   (1, 64, 121, 3, 1, 1.0, 0.0)])
+def test_split_respair_matches_float64(lib, B, C, T, k, dil, alpha, beta):
+    """respair_x3_kernel (the split-bf16 ResBlock1 pair, otherwise reached only through whole vocoders) as a one-op VB_OP_RESPAIR / VB_WFMT_X3
+    program against x + b2 + conv2(lrelu(b1 + conv1_dil(lrelu(x)))) in float64: the staged epilogue with 8 workgroups per clip; T % 4 != 0
+    (direct epilogue) with the largest halo and the accumulate-into form; two channel chunks; one partial workgroup.  Bound: the 2e-5 of one
+    split-bf16 convolution (test_conv1d_f32): the kernel as it stood before the conv1d_staged.h / respair_dev.h extraction measures 2.935e-06,
+    1.316e-06, 2.633e-06 and 2.806e-06 for the four cases in order, every one under half of the bound (the pair chains two such convolutions;
+    were one over 1e-5 the bound would be twice the largest).  The test prints each case's rel-L2 in front of its assertion."""
+    from versband_amd.engine import Context, ConvNet, NetBuilder
+    x = rnd((B, C, T), "sx")
+    w1, w2 = rnd((C, C, k), "sw1", 1.0 / (C * k) ** 0.5), rnd((C, C, k), "sw2", 1.0 / (C * k) ** 0.5)
+    b1, b2 = rnd((C,), "sb1"), rnd((C,), "sb2")
+    acc0 = rnd((B, C, T), "sacc")
+    nb = NetBuilder(torch.device("cuda:0"), "split")
+    nb.respair(L.BUF_INPUT, L.BUF_OUTPUT, C, pack.pack_conv(w1), b1, pack.pack_conv(w2), b2, k, dil, 0.1, alpha, beta)
+    assert nb.ops[0].kind == L.OP_RESPAIR and nb.ops[0].wfmt == L.WFMT_X3
+    net = ConvNet(Context("cuda:0"), L.NET_VAE, nb, C, C, 1)
+    xd, out = dev(x), dev(acc0).clone()          # (the accumulate-into form reads `out`: the program runs on a pre-filled output)
+    L.check(net.ctx.lib.vb_vae_decode(net.ctx.handle, L.ptr(xd), B, T, L.ptr(out), L.ptr(net._workspace(B, T)), L.stream_ptr()), "respair net")
+    sync()
+    ref = F.conv1d(F.leaky_relu(F.conv1d(F.leaky_relu(x.double(), 0.1), w1.double(), b1.double(), dilation=dil, padding=(k - 1) * dil // 2), 0.1),
+                   w2.double(), b2.double(), padding=(k - 1) // 2) + x.double()
+    ref = alpha * ref + beta * acc0.double()
+    err = rel_l2(out, ref)
+    print(f"split respair B={B} C={C} T={T} k={k} dil={dil}: rel_l2 = {err:.3e}")
+    assert torch.isfinite(out).all()
+    assert err < 2e-5, describe("respair split-bf16", out, ref)
 
 
 @pytest.mark.parametrize("C", [32, 64])

@@ -19,7 +19,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libversband_hip.so")
-SOURCES = ["gemm_bf16.hip", "band_ffn.hip", "attention.hip", "conv1d_f32.hip", "conv1d_f32g.hip", "conv1d_f32w.hip", "conv1d_bf16.hip", "respair_x3.hip", "respair_bf16.hip", "respair_f32.hip", "respair_f32w.hip", "t5.hip", "melnet.hip", "elementwise.hip", "sampler_step.hip", "routing.hip", "net_glue.hip", "rowlin.hip",
+SOURCES = ["gemm_bf16.hip", "band_ffn.hip", "attention.hip", "conv1d.hip", "conv1d_f32.hip", "conv1d_x3.hip", "conv1d_f32g.hip", "conv1d_f32w.hip", "conv1d_bf16.hip", "respair_x3.hip", "respair_bf16.hip", "respair_f32.hip", "respair_f32w.hip", "t5.hip", "melnet.hip", "elementwise.hip", "sampler_step.hip", "routing.hip", "net_glue.hip", "rowlin.hip",
            "runtime.hip", "dit.hip", "sampler.hip", "convnet.hip", "abi_units.hip"]
 EXPERIMENT_SOURCES = ["score_router.hip", "gemm_bf16_pk.hip"]
 EXPERIMENTS = bool(os.environ.get("VB_BUILD_EXPERIMENTS"))
@@ -30,7 +30,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-res
 _VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 _AGPR = set(filter(None, os.environ.get("VB_BUILD_AGPR", "").split(",")))
 EXTRA_FLAGS = {f: list(_VGPR_FORM) for f in ("conv1d_f32g.hip", "conv1d_f32w.hip", "respair_f32.hip", "respair_f32w.hip", "attention.hip") if f not in _AGPR}
-# (measured without effect on the split-bf16 kernels - conv1d_f32.hip, respair_x3.hip: 28.96 / 14.24 ms per pass with the flag, 28.91 / 14.34 without -
+# (measured without effect on the split-bf16 kernels - conv1d_x3.hip, respair_x3.hip: 28.96 / 14.24 ms per pass with the flag, 28.91 / 14.34 without -
 #  whose accumulator copies sit in the per-chunk window staging, off the critical path; attention: 12.1 -> 10.9 ms per pass)
 MARKER = b"VB_SOURCE_DIGEST="
 PUBLIC_HEADER = os.path.join(HERE, "..", "include", "versband_hip.h")

@@ -1,0 +1,110 @@
+// Conv1d / polyphase ConvTranspose1d, host side: the launch descriptor with the checks that fail a call, the route among the conv kernels
+// (conv1d_f32.hip, conv1d_x3.hip, conv1d_bf16.hip, conv1d_f32g.hip, conv1d_f32w.hip, the GEMM for wide pre-transposed layers) and launch_conv1d.
+#include <stdlib.h>
+
+#include "kernels.h"
+#include "conv1d_staged.h"
+
+// ---- launch_conv1d: descriptor (+ the checks that fail the call; n_count = output positions per phase) -> route -> launch
+static int conv1d_fill(const ConvArgs& a, ConvDev& d, int& n_count) {
+    d.x = a.x; d.x_bstride = a.x_bstride; d.Ci = a.Ci; d.T_in = a.T_in; d.x_bmod = a.x_bmod;
+    d.w = a.w; d.w_bstride = a.w_bstride; d.bias = a.bias; d.Co = a.Co; d.dil = a.dil; d.pad = a.pad;
+    d.upsample2 = a.upsample2; d.in_act = a.in_act; d.in_slope = a.in_slope;
+    d.in_stride = a.in_stride > 0 ? a.in_stride : 1; d.in_phase = a.in_phase;
+    if (d.in_stride > 1 && (a.upsample2 || a.tr_stride > 1)) VB_FAIL(VB_E_INVALID, "conv1d: in_stride with upsample/transpose");
+    d.gn_mean = a.gn_mean; d.gn_rstd = a.gn_rstd; d.gn_gamma = a.gn_gamma; d.gn_beta = a.gn_beta; d.gn_groups = a.gn_groups;
+    d.out = a.out; d.out_bstride = a.out_bstride; d.T_out = a.T_out; d.res = a.res; d.res_bstride = a.res_bstride;
+    d.alpha = a.alpha; d.beta = a.beta; d.acc_scale = a.acc_scale; d.out_act = a.out_act; d.out_slope = a.out_slope;
+    d.out_transposed = a.out_transposed; d.add = a.add; d.add_bstride = a.add_bstride; d.add_bmod = a.add_bmod;
+    d.wp = a.wp; d.wp_plane = a.wp_plane; d.Ci_pad = a.Ci_pad; d.wp_bstride = a.wp_bstride;
+    d.xt = a.xt; d.xt_Tp = xt_rows(a.upsample2 ? 2 * a.T_in : a.T_in); d.xt_plane = (int64_t)a.B * d.xt_Tp * a.Ci;
+    if (a.wp_bf16 && (!a.wp || a.xt || a.wp_bstride || a.w_mf)) VB_FAIL(VB_E_INVALID, "conv1d: bf16 weights are one shared plane (no XT input, no per-clip or minimal-filtering weights)");
+    if (a.xt && (a.Ci % 32 || a.tr_stride > 1 || a.in_stride > 1 || !a.wp || a.x_bmod || a.pad > XT_HEAD))
+        VB_FAIL(VB_E_INVALID, "conv1d: XT input needs Ci %% 32 == 0, stride 1, split weights, pad <= %d", XT_HEAD);
+    d.stage_epi = 0;
+    if (a.tr_stride > 1) {
+        d.phases = a.tr_stride; d.tr_pad = a.tr_pad; d.ntaps = (a.tr_k + a.tr_stride - 1) / a.tr_stride; d.dil = 1;
+        n_count = cdiv(a.T_out, a.tr_stride);
+        if (a.out_transposed) VB_FAIL(VB_E_INVALID, "conv1d: transposed output not supported with tr_stride");
+    } else {
+        d.phases = 1; d.tr_pad = 0; d.ntaps = a.ksize; n_count = a.T_out;
+    }
+    if ((d.ntaps - 1) * d.dil > CONV_HALO) VB_FAIL(VB_E_INVALID, "conv1d: halo %d exceeds %d", (d.ntaps - 1) * d.dil, CONV_HALO);
+    if (a.out_transposed && (a.Co % 4)) VB_FAIL(VB_E_INVALID, "conv1d: transposed output needs Co%%4==0");
+    if ((a.in_act == ACT_GN_SWISH || a.in_act == ACT_GN) && (a.Ci % a.gn_groups)) VB_FAIL(VB_E_INVALID, "conv1d: Ci %% groups");
+    return VB_OK;
+}
+
+// Wide layers over pre-activated transposed planes ARE GEMMs (rows = clip x time, K = taps x Ci, both operands K-contiguous
+// already): the DMA-fed 128 x 128 GEMM kernel walks K tap by tap (GemmArgs::conv_*), three bf16 passes for the split precision,
+// bias + residual in a channel-major epilogue.  Measured on these shapes (tools/conv_as_gemm_calib.py): 750-840 TFLOP/s of bf16
+// MFMA work against ~385 of conv1d_x3_kernel, which stages weights through registers and synchronises per (tap, 32 channels).
+// (B * T_out / Co beyond launch_gemm's reciprocal-divide range fall through to the conv kernels - ADVICE r3)
+static bool conv1d_as_gemm_eligible(const ConvArgs& a, const ConvDev& d) {
+    return a.xt && a.wp && a.Co >= 384 && a.Ci % 64 == 0 && a.Ci_pad == a.Ci && a.Co % 4 == 0 && d.phases == 1 && !a.wp_bstride && !a.w_bstride &&
+           a.alpha == 1.f && a.beta == 0.f && a.acc_scale == 1.f && a.out_act == ACT_NONE && !a.out_transposed && !a.add &&
+           a.out_bstride == (int64_t)a.Co * a.T_out && (!a.res || a.res_bstride == a.out_bstride) &&
+           a.T_out == (a.upsample2 ? 2 * a.T_in : a.T_in) && (int64_t)a.B * a.T_out < (1 << 21) && a.Co < (1 << 21);
+}
+static int launch_conv1d_as_gemm(const ConvArgs& a, const ConvDev& d, hipStream_t st) {
+    GemmArgs g;
+    g.A = a.xt; g.a_plane = d.xt_plane; g.lda = a.Ci; g.B = a.wp; g.b_plane = a.wp_plane; g.ldb = a.Ci_pad;
+    g.M = a.B * a.T_out; g.N = a.Co; g.K = d.ntaps * a.Ci; g.nseg = 3; g.ngroups = a.B;
+    g.group_rows = a.T_out; g.T = a.T_out; g.epi = EPI_F32_CT; g.bias = a.bias; g.out32 = a.out; g.res32 = a.res;
+    g.conv_ci = a.Ci; g.conv_dil = d.dil; g.conv_agrp = d.xt_Tp; g.conv_arow0 = XT_HEAD - a.pad; g.conv_btap = (int64_t)a.Co * a.Ci_pad;
+    g.prof_class = 2;
+    return launch_gemm(g, st);
+}
+// staged epilogue (conv_epilogue_staged; the minimal-filtering kernel has no other): plain [b][co][t] output whose rows start 16-B aligned
+static bool conv1d_stage_epi_eligible(const ConvArgs& a) {
+    return a.tr_stride <= 1 && !a.out_transposed && a.T_out % 4 == 0 && a.out_bstride % 4 == 0 && (!a.res || a.res_bstride % 4 == 0) &&
+           aligned16(a.out) && (!a.res || aligned16(a.res));
+}
+// conv1d_co1_kernel: one output channel of an ordinary stride-1 convolution, shared fp32 weights, input transform none / LeakyReLU
+static bool conv1d_co1_eligible(const ConvArgs& a, const ConvDev& d) {
+    return a.Co == 1 && a.w && !a.w_bstride && !a.x_bmod && d.phases == 1 && d.in_stride == 1 && !a.upsample2 && !a.out_transposed &&
+           (a.in_act == ACT_NONE || a.in_act == ACT_LRELU);
+}
+// conv1d_x3_kernel: split-bf16 weights are there - and per clip where the fp32 ones are
+static bool conv1d_x3_eligible(const ConvArgs& a) { return a.wp && (!a.w_bstride || a.wp_bstride); }
+
+enum ConvRoute { CONV_AS_GEMM, CONV_F32W, CONV_CO1, CONV_BF16, CONV_X3_XT, CONV_X3, CONV_F32G, CONV_F32 };
+// Which kernel runs: the first candidate, in this order, whose conditions hold and whose A/B knob has not switched it off; the register-staged
+// fp32 kernel takes everything.  Settles d.stage_epi on the way (VB_CONV_DIRECT_EPI=1: the direct epilogue - no minimal filtering then).
+static ConvRoute conv1d_route(const ConvArgs& a, ConvDev& d) {
+    const VbTune& tune = vb_tune();
+    if (conv1d_as_gemm_eligible(a, d) && !tune.conv_gemm_off) return CONV_AS_GEMM;
+    d.stage_epi = (conv1d_stage_epi_eligible(a) && !tune.conv_direct_epi) ? 1 : 0;
+    if (conv1d_f32w_eligible(a, d) && !tune.conv_mf_off) return CONV_F32W;
+    if (conv1d_co1_eligible(a, d) && !tune.conv_f32_old) return CONV_CO1;             // (VB_CONV_F32_OLD=1: the MFMA kernels)
+    if (a.wp_bf16) return CONV_BF16;                                                  // one weight plane: no other kernel reads it
+    if (conv1d_x3_eligible(a)) return a.xt ? CONV_X3_XT : CONV_X3;
+    // exact fp32, DMA-fed; VB_CONV_F32_OLD=1 keeps the register-staged kernel (bit-identical, tests compare the two)
+    if (conv1d_f32g_eligible(a, d) && !tune.conv_f32_old) return CONV_F32G;
+    return CONV_F32;
+}
+
+int launch_conv1d(const ConvArgs& a, hipStream_t st) {
+    ConvDev d;
+    int n_count;
+    VB_TRY(conv1d_fill(a, d, n_count));
+    const ConvRoute route = conv1d_route(a, d);
+    if (route == CONV_AS_GEMM) return launch_conv1d_as_gemm(a, d, st);      // (launch_gemm profiles itself: GemmArgs::prof_class)
+    // (flops of the profiler's class table: EXECUTED MFMA work - the minimal-filtering kernel runs pseudo-taps / 2 products per output)
+    const double taps_eff = route == CONV_F32W ? 0.5 * conv1d_f32w_pseudo_taps(a.ksize) : (a.tr_stride > 1 ? (double)a.tr_k / a.tr_stride : (double)a.ksize);
+    ProfScope prof(2, 2.0 * a.B * a.Co * a.Ci * (double)a.T_out * taps_eff,
+                   4.0 * a.B * ((double)a.Ci * a.T_in + (double)a.Co * a.T_out * (1.0 + (a.res ? 1.0 : 0.0) + (a.beta != 0.f ? 1.0 : 0.0)))
+                       + 4.0 * (double)a.Co * a.Ci * (a.tr_stride > 1 ? a.tr_k : a.ksize), st);
+    switch (route) {
+        case CONV_AS_GEMM: break;      // (left above)
+        case CONV_F32W: d.ww = a.w_mf; launch_conv1d_f32w(d, a.B, st); break;
+        case CONV_CO1: launch_conv1d_co1(d, a.B, st); break;
+        case CONV_BF16: VB_TRY(launch_conv1d_bf16(d, conv_staged_tile(a.Co, n_count, a.B, d.phases), n_count, a.B, st)); break;
+        case CONV_X3_XT:
+        case CONV_X3: VB_TRY(launch_conv1d_x3(d, conv_staged_tile(a.Co, n_count, a.B, d.phases), n_count, a.B, route == CONV_X3_XT, st)); break;
+        case CONV_F32G: launch_conv1d_f32g(d, n_count, a.B, a.upsample2, st); break;
+        case CONV_F32: launch_conv1d_f32(d, n_count, a.B, st); break;
+    }
+    VB_CHECK_LAUNCH();
+    return VB_OK;
+}

@@ -1,10 +1,11 @@
-// What the convolution kernels share (conv1d_f32.hip: register-staged fp32 + split-bf16 kernels and the launch route; conv1d_f32g.hip:
-// the DMA-fed exact-fp32 kernel; conv1d_f32w.hip: its minimal-filtering form): the launch descriptor, the two epilogues, the XCD work-group
-// numbering of the DMA-fed kernels (host and device half) and, host side, what their two launchers have in common.
+// What the convolution kernels share (conv1d.hip: descriptor, route and launch; conv1d_f32.hip / conv1d_x3.hip / conv1d_bf16.hip: the
+// register-staged fp32, split-bf16 and bf16 kernels, whose common parts are in conv1d_staged.h; conv1d_f32g.hip: the DMA-fed exact-fp32 kernel;
+// conv1d_f32w.hip: its minimal-filtering form): the launch descriptor, the two epilogues, the XCD work-group numbering of the DMA-fed
+// kernels (host and device half), what their two launchers have in common and every kernel file's launcher.
 #pragma once
 #include "kernels.h"
 
-#define GK 16                      // input channels per chunk of the DMA-fed kernels (= CK: the accumulation order of conv1d_f32_kernel)
+constexpr int CONV_CK = 16;        // input channels per chunk of the exact-fp32 kernels, register-staged and DMA-fed: ONE accumulation order
 
 struct ConvDev {
     const float* x; int64_t x_bstride; int Ci, T_in, x_bmod;
@@ -180,10 +181,10 @@ __device__ __forceinline__ void conv_epilogue(const ConvDev& p, f32x16 (&acc)[TM
 
 // ---- host side -------------------------------------------------------------
 // Input the window DMA of the ring kernels can fetch: unit input stride, no clip folding (x_bmod), an input transform the in-place pass over
-// the landed window knows (none / LeakyReLU), whole GK-channel chunks, output channels in quads (16-byte lanes of the weight DMA).
+// the landed window knows (none / LeakyReLU), whole CONV_CK-channel chunks, output channels in quads (16-byte lanes of the weight DMA).
 // quad_rows: the window moves as 16-byte pieces, so rows start 16-byte aligned (conv1d_f32g's upsampled form moves 4-byte pieces: false).
 static inline bool conv_dma_input(const ConvArgs& a, const ConvDev& d, bool quad_rows) {
-    return !a.x_bmod && d.in_stride == 1 && (a.in_act == ACT_NONE || a.in_act == ACT_LRELU) && a.Ci % GK == 0 && a.Co % 4 == 0 &&
+    return !a.x_bmod && d.in_stride == 1 && (a.in_act == ACT_NONE || a.in_act == ACT_LRELU) && a.Ci % CONV_CK == 0 && a.Co % 4 == 0 &&
            (!quad_rows || (a.T_in % 4 == 0 && a.x_bstride % 4 == 0 && aligned16(a.x)));
 }
 // XCD work-group numbering of the ring kernels: block L serves unit (L >> 3) % g_tbx * 8 + (L & 7) of channel tile (L >> 3) / g_tbx, so one
@@ -210,5 +211,12 @@ void launch_conv1d_f32g(ConvDev& d, int n_count, int B, int upsample2, hipStream
 bool conv1d_f32w_eligible(const ConvArgs& a, const ConvDev& d);
 int conv1d_f32w_pseudo_taps(int ksize);
 void launch_conv1d_f32w(ConvDev& d, int B, hipStream_t st);
+// conv1d_f32.hip: the register-staged exact-fp32 kernel (takes everything) and the one-output-channel kernel
+void launch_conv1d_f32(const ConvDev& d, int n_count, int B, hipStream_t st);
+void launch_conv1d_co1(const ConvDev& d, int B, hipStream_t st);
+// The tiles (output channels x positions) of the two bf16-MFMA kernels; conv_staged_tile (conv1d_staged.h) picks one
+enum ConvTileId { CONV_TILE_128x128, CONV_TILE_128x64, CONV_TILE_64x128, CONV_TILE_32x256 };
+// conv1d_x3.hip: split-bf16 (hi*hi + lo*hi + hi*lo, fp32-class); xt: the window comes from pre-activated transposed planes (d.xt)
+int launch_conv1d_x3(const ConvDev& d, ConvTileId tile, int n_count, int B, bool xt, hipStream_t st);
 // conv1d_bf16.hip: single-pass bf16 (RN-bf16 weights x RN-bf16 activated input, fp32 accumulation); d.wp = ONE plane [phase][tap][Co][Ci_pad]
-int launch_conv1d_bf16(const ConvDev& d, int n_count, int B, hipStream_t st);
+int launch_conv1d_bf16(const ConvDev& d, ConvTileId tile, int n_count, int B, hipStream_t st);

@@ -4,7 +4,7 @@
 #include <stdlib.h>
 #include <type_traits>
 
-#include "conv1d_dev.h"
+#include "conv1d_staged.h"
 #include "dma_ring.h"
 #include "lds_asm.h"
 #include "ring_window.h"
@@ -35,7 +35,7 @@ __global__ void __launch_bounds__(256, 3) conv1d_f32g_kernel(const ConvDev p) { 
     constexpr int T_TILE = WN * TN * 32;
     constexpr int XP = (T_TILE + 64 + 63) / 64 * 64;      // window pitch (positions): tile + halo (<= 60) + alignment slack (<= 3)
     constexpr int NP = XP / 64;
-    constexpr int XST = GK * XP, WT = GK * CO_TILE;       // floats per window stage / weight tile
+    constexpr int XST = CONV_CK * XP, WT = CONV_CK * CO_TILE;       // floats per window stage / weight tile
     constexpr int NWI = CO_TILE / 16;                     // 1-KB DMA pieces per weight tile
     constexpr int WPW = NWI >= 4 ? NWI / 4 : 1;           // ... per wave (narrow tiles: the waves repeat each other's pieces)
     constexpr int XPW = UPS ? 4 * NP : NP;                // window pieces per wave and chunk (16-B lanes: 4 rows of 64 positions per piece)
@@ -60,18 +60,8 @@ __global__ void __launch_bounds__(256, 3) conv1d_f32g_kernel(const ConvDev p) { 
         b = z / p.phases; ph = z - b * p.phases;
         co0 = ct * CO_TILE;
     }
-    int in_off, out_off, out_stride, n_count;
-    if (p.phases == 1) {
-        in_off = -p.pad; out_off = 0; out_stride = 1; n_count = p.T_out;
-    } else {
-        const int u = p.phases;
-        const int d = p.tr_pad - ph;
-        const int q0 = d > 0 ? (d + u - 1) / u : 0;
-        in_off = q0 - (p.ntaps - 1);
-        out_off = q0 * u + ph - p.tr_pad;
-        out_stride = u;
-        n_count = (p.T_out - out_off + u - 1) / u;
-    }
+    const ConvPhase pp = conv_phase(p, ph);
+    const int in_off = pp.in_off, out_off = pp.out_off, out_stride = pp.out_stride, n_count = pp.n_count;
     if (n0 >= n_count) return;
 
     const int start = n0 + in_off;
@@ -91,7 +81,7 @@ __global__ void __launch_bounds__(256, 3) conv1d_f32g_kernel(const ConvDev p) { 
 #ifdef VB_EXPERIMENTS
         nt = p.x_nt;
 #endif
-        win.issue(xbase + (int64_t)ch * GK * p.T_in, lx + (ch & 1) * XST, nt);
+        win.issue(xbase + (int64_t)ch * CONV_CK * p.T_in, lx + (ch & 1) * XST, nt);
     };
     const bool act = p.in_act == ACT_LRELU;
     auto fix_x = [&](int ch) { win.fix(lx + (ch & 1) * XST, act, slope); };
@@ -108,7 +98,7 @@ __global__ void __launch_bounds__(256, 3) conv1d_f32g_kernel(const ConvDev p) { 
     }
     auto issue_w = [&](int ch, int j, int slot) {
         if constexpr (ABL & 2) return;
-        const float* src = wbase + ((int64_t)j * p.Ci + ch * GK) * p.Co;
+        const float* src = wbase + ((int64_t)j * p.Ci + ch * CONV_CK) * p.Co;
         float* dst = lw + slot * WT;
 #pragma unroll
         for (int i = 0; i < WPW; ++i) {
@@ -125,7 +115,7 @@ __global__ void __launch_bounds__(256, 3) conv1d_f32g_kernel(const ConvDev p) { 
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    const int nchunks = p.Ci / GK;
+    const int nchunks = p.Ci / CONV_CK;
     const int total = nchunks * p.ntaps;
     // prologue: window of chunk 0, then the first NSW - 1 weight tiles (issue order = retirement order)
     issue_x(0);
@@ -175,15 +165,15 @@ __global__ void __launch_bounds__(256, 3) conv1d_f32g_kernel(const ConvDev p) { 
                 else acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(da[i], dbv[jn], acc[i][jn], 0, 0, 0);
             }
         __builtin_amdgcn_sched_barrier(0);
-        static_for<0, GK / 2>([&](auto kc) {
+        static_for<0, CONV_CK / 2>([&](auto kc) {
             constexpr int KK = decltype(kc)::value, S = KK % 3;
-            if constexpr (KK + 1 < GK / 2) LDS_WAIT(TM + TN); else LDS_WAIT(0);
+            if constexpr (KK + 1 < CONV_CK / 2) LDS_WAIT(TM + TN); else LDS_WAIT(0);
 #pragma unroll
             for (int i = 0; i < TM; ++i) lds_pin(a[S][i]);
 #pragma unroll
             for (int jn = 0; jn < TN; ++jn) lds_pin(bb[S][jn]);
-            if constexpr (KK + 2 < GK / 2) fload(std::integral_constant<int, KK + 2>{});
-            if constexpr (KK + 1 < GK / 2) {
+            if constexpr (KK + 2 < CONV_CK / 2) fload(std::integral_constant<int, KK + 2>{});
+            if constexpr (KK + 1 < CONV_CK / 2) {
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -294,7 +284,7 @@ __global__ void __launch_bounds__(256, 3) conv1d_f32g_kernel(const ConvDev p) { 
 template <int WM, int WN, int TM, int TN, bool UPS, int NSW = 4, int ABL = 0, int NT = 0>
 static void launch_cfg_g(ConvDev& d, int n_count, int B, hipStream_t st) {
     constexpr int CO_TILE = WM * TM * 32, T_TILE = WN * TN * 32, XP = (T_TILE + 64 + 63) / 64 * 64;
-    constexpr int BYTES = (2 * GK * XP + NSW * GK * CO_TILE) * (int)sizeof(float);
+    constexpr int BYTES = (2 * CONV_CK * XP + NSW * CONV_CK * CO_TILE) * (int)sizeof(float);
     const int grid = conv_xcd_grid(d, n_count, T_TILE, CO_TILE, B);
     static OnceFlags once;
     vb_set_max_lds_once(once, (const void*)conv1d_f32g_kernel<WM, WN, TM, TN, UPS, NSW, ABL, NT>, BYTES);

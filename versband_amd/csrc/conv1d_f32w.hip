@@ -58,7 +58,7 @@ __global__ void __launch_bounds__(256, OCC) conv1d_f32w_kernel(const ConvDev p) 
     constexpr int TM = 2, WM = 4 / WN, NXS = 2, NSW = 3;
     constexpr int P = mf_ntaps(K);
     constexpr int CO_TILE = WM * TM * 32, XP = WN * 64 + 64, NP = XP / 64;
-    constexpr int XST = GK * XP, WT = GK * CO_TILE;
+    constexpr int XST = CONV_CK * XP, WT = CONV_CK * CO_TILE;
     constexpr int NWI = CO_TILE / 16, WPW = NWI / 4, XPW = NP;
     static_assert(P >= NSW - 1, "a step issues the tile NSW - 1 ahead: it lies in this chunk or the next one");
     static_assert((NXS * XST + NSW * WT) >= 4 * 32 * MF_PITCH, "the staging patches must fit in the rings");
@@ -95,7 +95,7 @@ __global__ void __launch_bounds__(256, OCC) conv1d_f32w_kernel(const ConvDev p) 
     // ---- window DMA (16-B lanes, four rows of 64 positions per 1-KB piece) and the in-place pass over what landed: ring_window.h
     RingWindow<XPW, NP> win;
     win.setup(wave, lane, start_al, p.T_in);
-    auto issue_x = [&](int ch, int stage) { win.issue(xbase + (int64_t)ch * GK * p.T_in, lx + stage * XST); };
+    auto issue_x = [&](int ch, int stage) { win.issue(xbase + (int64_t)ch * CONV_CK * p.T_in, lx + stage * XST); };
     const bool act = p.in_act == ACT_LRELU;
     // ---- weight DMA: tile (chunk, pseudo-tap) = 16 rows of 128 floats
     constexpr int RPI = 256 / CO_TILE, LPR = CO_TILE / 4;
@@ -107,7 +107,7 @@ __global__ void __launch_bounds__(256, OCC) conv1d_f32w_kernel(const ConvDev p) 
         wsrc0 = row * p.Co + cog;
     }
     auto issue_w = [&](int ch, int j, int slot) {
-        const float* src = wbase + ((int64_t)j * p.Ci + ch * GK) * p.Co;
+        const float* src = wbase + ((int64_t)j * p.Ci + ch * CONV_CK) * p.Co;
         float* dst = lw + slot * WT;
 #pragma unroll
         for (int i = 0; i < WPW; ++i)
@@ -122,7 +122,7 @@ __global__ void __launch_bounds__(256, OCC) conv1d_f32w_kernel(const ConvDev p) 
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[a][i][r] = 0.f;
 
-    const int nchunks = p.Ci / GK;
+    const int nchunks = p.Ci / CONV_CK;
 #pragma unroll
     for (int c = 0; c < NXS - 1; ++c) issue_x(c < nchunks ? c : 0, c);      // windows first: they retire first
 #pragma unroll
@@ -192,19 +192,19 @@ __global__ void __launch_bounds__(256, OCC) conv1d_f32w_kernel(const ConvDev p) 
 #pragma unroll
                 for (int i = 0; i < TM; ++i) MFMA_ACC(acc[PACC][i], da[i], dbv);
                 __builtin_amdgcn_sched_barrier(0);
-                static_for<0, GK / 2>([&](auto kc) {
+                static_for<0, CONV_CK / 2>([&](auto kc) {
                     constexpr int KK = decltype(kc)::value, S = KK % 3;
-                    if constexpr (KK + 1 < GK / 2) LDS_WAIT(NR); else LDS_WAIT(0);
+                    if constexpr (KK + 1 < CONV_CK / 2) LDS_WAIT(NR); else LDS_WAIT(0);
 #pragma unroll
                     for (int i = 0; i < TM; ++i) lds_pin(a[S][i]);
                     lds_pin(xa[S]);
                     if constexpr (TP.op != 2) lds_pin(xb[S]);
-                    if constexpr (KK + 2 < GK / 2) fload(std::integral_constant<int, KK + 2>{});
+                    if constexpr (KK + 2 < CONV_CK / 2) fload(std::integral_constant<int, KK + 2>{});
                     float bv;
                     if constexpr (TP.op == 0) bv = xa[S] - xb[S];
                     else if constexpr (TP.op == 1) bv = xa[S] + xb[S];
                     else bv = xa[S];
-                    if constexpr (KK + 1 < GK / 2) {
+                    if constexpr (KK + 1 < CONV_CK / 2) {
 #pragma unroll
                         for (int i = 0; i < TM; ++i) MFMA_ACC(acc[TP.acc][i], a[S][i], bv);
                     } else {
@@ -300,7 +300,7 @@ template <int K, int OCC, int WN>
 static void launch_w(ConvDev& d, int B, hipStream_t st) {
     constexpr int CO_TILE = (4 / WN) * 64, XP = WN * 64 + 64;
     constexpr int NXS = 2, NSW = 3;      // (the kernel's ring depths)
-    constexpr int BYTES = (NXS * GK * XP + NSW * GK * CO_TILE) * (int)sizeof(float);
+    constexpr int BYTES = (NXS * CONV_CK * XP + NSW * CONV_CK * CO_TILE) * (int)sizeof(float);
     const int T_TILE = WN * 2 * ((32 / d.dil) * d.dil);
     const int grid = conv_xcd_grid(d, d.T_out, T_TILE, CO_TILE, B);      // (phases == 1)
 #ifdef VB_EXPERIMENTS

@@ -1,5 +1,5 @@
 // What the kernels that DMA their tiles into LDS rings (global_load_lds + counted vmcnt) share: the compile-time loop, the counted waits,
-// the pointer types of the DMA builtin and the fused pairs' output element.  No inline assembly (that is lds_asm.h); the fp32 conv
+// the pointer types of the DMA builtin and the fused pairs' outputs per workgroup and output element.  No inline assembly (that is lds_asm.h); the fp32 conv
 // kernels' window feed, which needs both, is ring_window.h.
 #pragma once
 #include <type_traits>
@@ -31,6 +31,10 @@ template <int WPW, int XPW> __device__ __forceinline__ void wait_tile(int ahead,
         else wait_vmcnt<0>();
     }
 }
+
+// Outputs per workgroup of the fused ResBlock pairs (all four: respair_x3 / respair_bf16 / respair_f32 / respair_f32w): a run of `run`
+// intermediate positions less conv2's halo, a multiple of 4 (the epilogue moves 16-byte quads).  Kernel and launcher (the grid) both call it.
+__host__ __device__ constexpr int pair_run_outputs(int run, int k) { return (run - (k - 1)) & ~3; }
 
 // One output element of the fused ResBlock pairs (respair_x3 / respair_f32 / respair_f32w): conv_out_value (conv1d_dev.h) with acc_scale = 1
 // and no output activation - the same pinned arithmetic, so that a pair and the two unfused launches round alike.

@@ -135,7 +135,7 @@ struct ConvArgs {
     const float* w_mf = nullptr;
 };
 int launch_conv1d(const ConvArgs& a, hipStream_t st);
-// fused HiFi-GAN ResBlock1 pair (respair_x3.hip): out = beta*out + alpha*(x + b2 + conv2(lrelu(b1 + conv1_dil(lrelu(x)))))
+// fused HiFi-GAN ResBlock1 pair (respair_x3.hip; checks, descriptor and epilogue shared with the bf16 form: respair_dev.h): out = beta*out + alpha*(x + b2 + conv2(lrelu(b1 + conv1_dil(lrelu(x)))))
 struct RespairArgs {
     const float* x = nullptr; float* out = nullptr; int B = 1, C = 0, T = 0, k = 3, dil = 1;
     const bf16_t* w1 = nullptr; const bf16_t* w2 = nullptr;     // split planes [2][k][C][C]
@@ -143,7 +143,7 @@ struct RespairArgs {
     float slope = 0.1f, alpha = 1.f, beta = 0.f;
 };
 int launch_respair(const RespairArgs& a, hipStream_t st);
-// the same pair in single-pass bf16 (respair_bf16.hip): w1 / w2 = ONE plane [k][C][C] each, the intermediate rounded to bf16 once; C = 32 / 64
+// the same pair in single-pass bf16 (respair_bf16.hip; same window rules and checks, respair_dev.h): w1 / w2 = ONE plane [k][C][C] each, the intermediate rounded to bf16 once; C = 32 / 64
 int launch_respair_bf16(const RespairArgs& a, hipStream_t st);
 // the same pair in exact fp32 (respair_f32.hip; v_mfma_f32_32x32x2_f32, weights fp32 packed [k][Ci][Co]): C = 32 / 64 / 128
 struct RespairF32Args {

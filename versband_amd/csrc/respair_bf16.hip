@@ -16,27 +16,15 @@
 // 35 KB of LDS and 88 registers, C = 64 63 KB and 118 - four / two workgroups per CU, which __launch_bounds__(256, 4 / CH) holds the
 // compiler to.
 #include "kernels.h"
-#include "respair_epi.h"
+#include "respair_dev.h"
 
-#define RB_T 128            // intermediate positions per workgroup (4 waves x 32)
-#define RB_HALO 64          // max (k-1)*dil of conv1
-#define RB_XW (RB_T + RB_HALO)
-
-struct PairBf16Dev {
-    const float* x; float* out; int64_t bstride; int T;
-    int k, dil;
-    const bf16_t* w1; const bf16_t* w2;      // [k][C][C] each, ci contiguous
-    const float* b1; const float* b2;
-    float slope, alpha, beta;
-    int staged;               // 16-B (staged) epilogue: T % 4 == 0 and 16-B aligned tensors
-};
 
 template <int CH>      // C = 32*CH channels
-__global__ void __launch_bounds__(256, 4 / CH) respair_bf16_kernel(const PairBf16Dev p) {
+__global__ void __launch_bounds__(256, 4 / CH) respair_bf16_kernel(const PairDev p) {
     constexpr int C = 32 * CH;
     constexpr int P = C + 8;                 // bf16 elements per LDS row
     constexpr int G = 128 / C;               // taps per weight group
-    constexpr int XH_EL = RB_XW * P, WL_EL = G * C * P;
+    constexpr int XH_EL = PAIR_XW * P, WL_EL = G * C * P;
     // xT (the activated window, conv1 only) and hT (the activated intermediate, conv2 only) share the first XH_EL elements: hT is written
     // after the barrier that ends conv1's last tap group.  The epilogue's staging patches reuse the whole array.
     __shared__ __attribute__((aligned(16))) bf16_t smem[XH_EL + 2 * WL_EL];
@@ -46,12 +34,8 @@ __global__ void __launch_bounds__(256, 4 / CH) respair_bf16_kernel(const PairBf1
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 5, l31 = lane & 31;
     const int b = blockIdx.z;
-    const int h2 = (p.k - 1) / 2, h1 = (p.k - 1) * p.dil / 2;
-    const int TT = (RB_T - (p.k - 1)) & ~3;          // outputs per workgroup (a multiple of 4: the epilogue moves 16-B quads)
-    const int n0 = blockIdx.x * TT;                  // first output sample
-    const int m0 = n0 - h2;                          // first intermediate position
-    const int x0 = m0 - h1;                          // first window sample
-    const int xw_used = RB_T + (p.k - 1) * p.dil;
+    const PairRun r = pair_run(p);
+    const int TT = r.TT, n0 = r.n0, m0 = r.m0, x0 = r.x0, xw_used = r.xw_used;
     const float* xb = p.x + (int64_t)b * p.bstride;
     const int ngroups = (p.k + G - 1) / G;
 
@@ -115,7 +99,7 @@ __global__ void __launch_bounds__(256, 4 / CH) respair_bf16_kernel(const PairBf1
     // ---- window of x -> LeakyReLU -> bf16 -> xT[t][ci]: a wave owns C/4 CONSECUTIVE channels, a lane one window position per pass
     // (coalesced loads along t, 16-byte LDS writes)
     {
-        constexpr int NIT = RB_XW / 64, CPW = C / 4;
+        constexpr int NIT = PAIR_XW / 64, CPW = C / 4;
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             const int wpos = lane + 64 * it;
@@ -127,13 +111,13 @@ __global__ void __launch_bounds__(256, 4 / CH) respair_bf16_kernel(const PairBf1
             if (wpos >= xw_used) continue;
 #pragma unroll
             for (int h = 0; h < CPW / 8; ++h) {
-                bf16x8 v;
+                float v[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const float t = raw[8 * h + e];               // out-of-range samples were loaded as 0 and lrelu(0) = 0
-                    v[e] = f2bf(t > 0.f ? t : t * p.slope);
+                    v[e] = t > 0.f ? t : t * p.slope;
                 }
-                *reinterpret_cast<bf16x8*>(&xh[wpos * P + CPW * wave + 8 * h]) = v;
+                bf16_planes_store<1>(v, &xh[wpos * P + CPW * wave + 8 * h], 0);
             }
         }
     }
@@ -145,22 +129,9 @@ __global__ void __launch_bounds__(256, 4 / CH) respair_bf16_kernel(const PairBf1
     taps(p.w1, p.dil);
     {   // + b1, LeakyReLU, zero outside [0,T), bf16, to hT[t][c] (xT's storage: conv1's last barrier is behind every wave)
         const int m = m0 + 32 * wave + l31;
-        const bool inr = m >= 0 && m < p.T;
 #pragma unroll
         for (int i = 0; i < CH; ++i)
-#pragma unroll
-            for (int rg = 0; rg < 4; ++rg) {
-                const int c = i * 32 + 8 * rg + 4 * g;
-                bf16x4 hv;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float v = acc[i][rg * 4 + e] + p.b1[c + e];
-                    v = v > 0.f ? v : v * p.slope;
-                    if (!inr) v = 0.f;
-                    hv[e] = f2bf(v);
-                }
-                *reinterpret_cast<bf16x4*>(&xh[(32 * wave + l31) * P + c]) = hv;
-            }
+            pair_store_intermediate<1>(acc[i], p.b1 + i * 32, p.slope, m >= 0 && m < p.T, &xh[(32 * wave + l31) * P + i * 32], 0);
     }
     // ---- conv2 (dil 1) over the intermediate -> outputs n0 + [0,TT).  Rows 128 .. 127 + (k-1) of xh are read as well (stale window
     // values, inside the array): they only reach the output columns nl >= TT, which the epilogue drops.
@@ -169,28 +140,18 @@ __global__ void __launch_bounds__(256, 4 / CH) respair_bf16_kernel(const PairBf1
     __syncthreads();           // publishes hT and the first weight group
     zero_acc();
     taps(p.w2, 1);
-    // ---- epilogue (respair_epi.h; smem is free: conv2's last barrier is behind every wave)
+    // ---- epilogue (respair_dev.h; smem is free: conv2's last barrier is behind every wave)
     static_assert(sizeof(smem) >= PAIR_EPI_FLOATS * sizeof(float), "staging patches must fit");
     pair_epilogue<CH>(acc, reinterpret_cast<float*>(smem), p.staged, xb, p.out + (int64_t)b * p.bstride, p.T, n0, TT, p.b2, p.alpha, p.beta);
 }
 
 int launch_respair_bf16(const RespairArgs& a, hipStream_t st) {
-    if (a.C != 32 && a.C != 64) VB_FAIL(VB_E_INVALID, "respair_bf16: C=%d (32 or 64)", a.C);
-    if (a.k < 1 || (a.k & 1) == 0 || (a.k - 1) * a.dil > RB_HALO || a.k > 33) VB_FAIL(VB_E_INVALID, "respair_bf16: k=%d dil=%d", a.k, a.dil);
-    if (a.x == a.out) VB_FAIL(VB_E_INVALID, "respair_bf16: x and out must be distinct buffers (neighbouring workgroups re-read the halo)");
+    PairLaunch L;
+    VB_TRY(pair_fill(a, "respair_bf16", L));
     if (!aligned16(a.w1) || !aligned16(a.w2)) VB_FAIL(VB_E_INVALID, "respair_bf16: weights are not 16-byte aligned");
-    PairBf16Dev d;
-    d.x = a.x; d.out = a.out; d.bstride = (int64_t)a.C * a.T; d.T = a.T; d.k = a.k; d.dil = a.dil;
-    d.w1 = a.w1; d.w2 = a.w2; d.b1 = a.b1; d.b2 = a.b2;
-    d.slope = a.slope; d.alpha = a.alpha; d.beta = a.beta;
-    const int TT = (RB_T - (a.k - 1)) & ~3;
-    d.staged = (a.T % 4 == 0 && aligned16(a.x) && aligned16(a.out) && !vb_tune().conv_direct_epi) ? 1 : 0;
-    dim3 grid(cdiv(a.T, TT), 1, a.B);
-    // two convolutions' worth of flops (the recomputed halo of conv1 is not counted)
-    ProfScope prof(3, 2.0 * 2.0 * a.B * (double)a.C * a.C * a.k * (double)a.T,
-                   4.0 * a.B * (double)a.C * a.T * (2.0 + (a.beta != 0.f ? 1.0 : 0.0)) + 2.0 * 2.0 * a.k * a.C * a.C, st);
-    if (a.C == 32) hipLaunchKernelGGL(respair_bf16_kernel<1>, grid, dim3(256), 0, st, d);
-    else hipLaunchKernelGGL(respair_bf16_kernel<2>, grid, dim3(256), 0, st, d);
+    ProfScope prof(3, L.flops, L.act_bytes + 2.0 * 2.0 * a.k * a.C * a.C, st);
+    if (a.C == 32) hipLaunchKernelGGL(respair_bf16_kernel<1>, L.grid, dim3(256), 0, st, L.d);
+    else hipLaunchKernelGGL(respair_bf16_kernel<2>, L.grid, dim3(256), 0, st, L.d);
     VB_CHECK_LAUNCH();
     return VB_OK;
 }

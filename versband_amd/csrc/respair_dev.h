@@ -1,4 +1,5 @@
-// The epilogue of the split-bf16 / bf16 fused ResBlock1 pairs (respair_x3.hip, respair_bf16.hip), once:
+// What the split-bf16 and bf16 ResBlock1 pairs (respair_x3.hip, respair_bf16.hip) share: descriptor, run geometry (outputs per workgroup:
+// pair_run_outputs, dma_ring.h, as the fp32 pairs take it), the launcher's checks, and their epilogue, once:
 //   out = pair_out_value(alpha, beta, acc, b2[co], x, out)   for the workgroup's outputs n0 + [0, TT) of all 32*CH channels.
 // The MFMA accumulator gives a lane ONE output sample and 16 channels; moved like that every residual / accumulate-into load and every store
 // is a 4-byte lane access (the direct form, any T).  With 16-byte aligned rows (staged: T % 4 == 0, aligned tensors) each wave passes its
@@ -6,10 +7,70 @@
 // block barrier: only the wave's own writes precede its reads) and comes back with 4 consecutive samples of one channel per lane - 16-byte
 // accesses, whole 128-B lines per 8 lanes.  Same arithmetic per element in both forms (see conv_epilogue_staged, conv1d_dev.h).
 #pragma once
+#include "conv1d_staged.h"
 #include "dma_ring.h"
 
 #define PAIR_EP 36                                   // floats per staged channel row (32 + 4)
 #define PAIR_EPI_FLOATS (4 * 32 * PAIR_EP)           // four wave-private patches
+#define PAIR_T 128                                   // intermediate positions per workgroup of the x3 / bf16 pairs (4 waves x 32)
+#define PAIR_XW (PAIR_T + CONV_HALO)                 // window rows: conv1's halo (k-1)*dil <= CONV_HALO
+
+struct PairDev {
+    const float* x; float* out; int64_t bstride; int T;
+    int k, dil;
+    const bf16_t* w1; const bf16_t* w2; int64_t w_plane;      // [planes][k][C][C] each, ci contiguous (w_plane: unused by the one-plane form)
+    const float* b1; const float* b2;
+    float slope, alpha, beta;
+    int staged;               // 16-B (staged) epilogue: T % 4 == 0 and 16-B aligned tensors
+};
+// One workgroup's run: outputs n0 + [0, TT), intermediate positions m0 + [0, PAIR_T), window samples x0 + [0, xw_used)
+struct PairRun { int h1, h2, TT, n0, m0, x0, xw_used; };
+__device__ __forceinline__ PairRun pair_run(const PairDev& p) {
+    PairRun r;
+    r.h2 = (p.k - 1) / 2; r.h1 = (p.k - 1) * p.dil / 2;
+    r.TT = pair_run_outputs(PAIR_T, p.k);
+    r.n0 = blockIdx.x * r.TT;
+    r.m0 = r.n0 - r.h2;
+    r.x0 = r.m0 - r.h1;
+    r.xw_used = PAIR_T + (p.k - 1) * p.dil;
+    return r;
+}
+// b1, LeakyReLU, zero outside [0, T) (conv2 pads the ACTIVATED intermediate) and the operand rounding over the conv1 accumulators of channel
+// chunk i: this lane's intermediate position (row of hT, `pitch` bf16 each) and 4 x 4 channels from c0 on, NPL planes `plane` apart
+template <int NPL>
+__device__ __forceinline__ void pair_store_intermediate(const f32x16& acc, const float* b1, float slope, bool inr, bf16_t* row, int plane) {
+    const int g = (threadIdx.x & 63) >> 5;
+#pragma unroll
+    for (int rg = 0; rg < 4; ++rg) {
+        const int c = 8 * rg + 4 * g;
+        float v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            v[e] = acc[rg * 4 + e] + b1[c + e];
+            v[e] = v[e] > 0.f ? v[e] : v[e] * slope;
+            if (!inr) v[e] = 0.f;
+        }
+        bf16_planes_store<NPL>(v, row + c, plane);
+    }
+}
+
+// ---- host side: the argument checks of launch_respair / launch_respair_bf16 (`who` prefixes the messages), the descriptor, the grid and the
+// profiler's flops (two convolutions' worth; the recomputed halo of conv1 is not counted) and activation bytes
+struct PairLaunch { PairDev d; dim3 grid; double flops, act_bytes; };
+static inline int pair_fill(const RespairArgs& a, const char* who, PairLaunch& L) {
+    if (a.C != 32 && a.C != 64) VB_FAIL(VB_E_INVALID, "%s: C=%d (32 or 64)", who, a.C);
+    if (a.k < 1 || (a.k & 1) == 0 || (a.k - 1) * a.dil > CONV_HALO || a.k > 33) VB_FAIL(VB_E_INVALID, "%s: k=%d dil=%d", who, a.k, a.dil);
+    if (a.x == a.out) VB_FAIL(VB_E_INVALID, "%s: x and out must be distinct buffers (neighbouring workgroups re-read the halo)", who);
+    PairDev& d = L.d;
+    d.x = a.x; d.out = a.out; d.bstride = (int64_t)a.C * a.T; d.T = a.T; d.k = a.k; d.dil = a.dil;
+    d.w1 = a.w1; d.w2 = a.w2; d.w_plane = (int64_t)a.k * a.C * a.C; d.b1 = a.b1; d.b2 = a.b2;
+    d.slope = a.slope; d.alpha = a.alpha; d.beta = a.beta;
+    d.staged = (a.T % 4 == 0 && aligned16(a.x) && aligned16(a.out) && !vb_tune().conv_direct_epi) ? 1 : 0;
+    L.grid = dim3(cdiv(a.T, pair_run_outputs(PAIR_T, a.k)), 1, a.B);
+    L.flops = 2.0 * 2.0 * a.B * (double)a.C * a.C * a.k * (double)a.T;
+    L.act_bytes = 4.0 * a.B * (double)a.C * a.T * (2.0 + (a.beta != 0.f ? 1.0 : 0.0));
+    return VB_OK;
+}
 
 template <int CH>
 __device__ __forceinline__ void pair_epilogue(f32x16 (&acc)[CH], float* stage, int staged, const float* xb, float* ob, int T, int n0, int TT,

@@ -72,7 +72,7 @@ __global__ void __launch_bounds__(256) respair_f32_kernel(const PairF32Dev p) {
     const int g = lane >> 5, l31 = lane & 31;
     const int b = blockIdx.z;
     const int h2 = (p.k - 1) / 2, h1 = (p.k - 1) * p.dil / 2;
-    const int TT = (PF_T - (p.k - 1)) & ~3;           // outputs per workgroup (a multiple of 4: 16-B quads)
+    const int TT = pair_run_outputs(PF_T, p.k);       // outputs per workgroup (dma_ring.h)
     const int n0 = blockIdx.x * TT;                   // first output sample
     const int m0 = n0 - h2;                           // first intermediate position
     const int x0 = m0 - h1;                           // first window sample
@@ -387,7 +387,7 @@ int launch_respair_f32(const RespairF32Args& a, hipStream_t st) {
     PairF32Dev d;
     d.x = a.x; d.out = a.out; d.bstride = (int64_t)a.C * a.T; d.T = a.T; d.k = a.k; d.dil = a.dil;
     d.w1 = a.w1; d.w2 = a.w2; d.b1 = a.b1; d.b2 = a.b2; d.slope = a.slope; d.alpha = a.alpha; d.beta = a.beta;
-    const int TT = (PF_T - (a.k - 1)) & ~3;
+    const int TT = pair_run_outputs(PF_T, a.k);
     d.staged = (aligned16(a.out) && !vb_tune().conv_direct_epi) ? 1 : 0;
 #ifdef VB_EXPERIMENTS
     d.x_nt = getenv("VB_CONV_XNT") ? 1 : 0;

@@ -71,7 +71,7 @@ __global__ void __launch_bounds__(256, 2) respair_f32w_kernel(const PairWDev p) 
     const int VW = (32 / dil) * dil;
     const int M = WTW * 2 * VW;                         // intermediate positions per workgroup
     const int h2 = (K - 1) / 2, h1 = (K - 1) * dil / 2;
-    const int TT = (M - (K - 1)) & ~3;                  // outputs per workgroup
+    const int TT = pair_run_outputs(M, K);               // outputs per workgroup (dma_ring.h)
     const int n0 = blockIdx.x * TT;
     const int m0 = n0 - h2;
     const int x0 = m0 - h1;
@@ -255,7 +255,7 @@ static void launch_pair_w(const PairWDev& d, int B, hipStream_t st) {
     constexpr int XH = (2 * PW_GK * XP > C * HP ? 2 * PW_GK * XP : C * HP) > 4 * 32 * PW_EP ? (2 * PW_GK * XP > C * HP ? 2 * PW_GK * XP : C * HP) : 4 * 32 * PW_EP;
     constexpr int BYTES = (XH + 3 * TPS * PW_GK * C) * (int)sizeof(float);
     const int VW = (32 / d.dil) * d.dil;
-    const int TT = (WTW * 2 * VW - (K - 1)) & ~3;
+    const int TT = pair_run_outputs(WTW * 2 * VW, K);
     static OnceFlags once;
     vb_set_max_lds_once(once, (const void*)respair_f32w_kernel<K, TPS, C>, BYTES);
     hipLaunchKernelGGL((respair_f32w_kernel<K, TPS, C>), dim3(cdiv(d.T, TT), 1, B), dim3(256), BYTES, st, d);

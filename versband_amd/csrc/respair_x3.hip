@@ -13,21 +13,9 @@
 //   * conv2 over hT, + b2 + residual x, alpha/beta accumulation into the MRF sum, coalesced stores (a lane owns one t).
 // Same operand precision as conv1d_x3_kernel (operand error 2^-17, fp32 accumulate).
 #include "kernels.h"
-#include "respair_epi.h"
+#include "respair_dev.h"
 
-#define RP_T 128            // intermediate positions per workgroup (4 waves x 32)
-#define RP_HALO 64          // max (k-1)*dil of conv1
-#define RP_XW (RP_T + RP_HALO)
 #define RP_P 40             // bf16 elements per LDS row of a 32-channel chunk (32 + 8 pad: conflict-free 16-B fragment reads)
-
-struct PairDev {
-    const float* x; float* out; int64_t bstride; int T;
-    int k, dil;
-    const bf16_t* w1; const bf16_t* w2; int64_t w_plane;      // [2 planes][k][C][C] each, ci contiguous
-    const float* b1; const float* b2;
-    float slope, alpha, beta;
-    int staged;               // 16-B (staged) epilogue: T % 4 == 0 and 16-B aligned tensors
-};
 
 template <int CH>      // C = 32*CH channels
 __global__ void __launch_bounds__(256) respair_x3_kernel(const PairDev p) {
@@ -35,21 +23,17 @@ __global__ void __launch_bounds__(256) respair_x3_kernel(const PairDev p) {
     // xT (one ci chunk of the activated window, conv1 only) and hT (activated intermediate, all chunks, conv2 only) share
     // storage: hT is written after the barrier that ends conv1's last tap.  41 KB + weights instead of 72 KB: 3 workgroups
     // per CU at 32 channels, 2 at 64 - these kernels are a chain of short phases and live off co-resident workgroups.
-    constexpr int XT_EL = 2 * RP_XW * RP_P, HT_EL = CH * 2 * RP_T * RP_P;
+    constexpr int XT_EL = 2 * PAIR_XW * RP_P, HT_EL = CH * 2 * PAIR_T * RP_P;
     __shared__ __attribute__((aligned(16))) bf16_t xh[XT_EL > HT_EL ? XT_EL : HT_EL];
-    bf16_t (*xT)[RP_XW * RP_P] = reinterpret_cast<bf16_t (*)[RP_XW * RP_P]>(xh);
-    bf16_t (*hT)[2][RP_T * RP_P] = reinterpret_cast<bf16_t (*)[2][RP_T * RP_P]>(xh);
+    bf16_t (*xT)[PAIR_XW * RP_P] = reinterpret_cast<bf16_t (*)[PAIR_XW * RP_P]>(xh);
+    bf16_t (*hT)[2][PAIR_T * RP_P] = reinterpret_cast<bf16_t (*)[2][PAIR_T * RP_P]>(xh);
     __shared__ __attribute__((aligned(16))) bf16_t wl[2][2][C * RP_P];             // [buf][plane] one (tap, ci chunk) of weights
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 5, l31 = lane & 31;
     const int b = blockIdx.z;
-    const int h2 = (p.k - 1) / 2, h1 = (p.k - 1) * p.dil / 2;
-    const int TT = (RP_T - (p.k - 1)) & ~3;          // outputs per workgroup (a multiple of 4: the epilogue moves 16-B quads)
-    const int n0 = blockIdx.x * TT;                  // first output sample
-    const int m0 = n0 - h2;                          // first intermediate position
-    const int x0 = m0 - h1;                          // first window sample
-    const int xw_used = RP_T + (p.k - 1) * p.dil;
+    const PairRun r = pair_run(p);
+    const int TT = r.TT, n0 = r.n0, m0 = r.m0, x0 = r.x0, xw_used = r.xw_used;
     const float* xb = p.x + (int64_t)b * p.bstride;
 
     // weight tile of one (tap, ci chunk): C rows x 32 ci x 2 planes = C*8 pieces of 16 B
@@ -76,7 +60,7 @@ __global__ void __launch_bounds__(256) respair_x3_kernel(const PairDev p) {
     // activation window staging in two halves (loads of the next chunk fly while the taps of this one are multiplied)
     // (a wave owns 8 CONSECUTIVE channels of the chunk, a lane one window position per pass: coalesced loads along t, ONE 16-byte
     //  LDS write per plane and position - four bank-conflicted 4-byte writes of channel pairs before round 3)
-    constexpr int NIT = RP_XW / 64;
+    constexpr int NIT = PAIR_XW / 64;
     float raw[8][NIT];
     auto xload = [&](int c0) {
 #pragma unroll
@@ -96,16 +80,13 @@ __global__ void __launch_bounds__(256) respair_x3_kernel(const PairDev p) {
         for (int it = 0; it < NIT; ++it) {
             const int wpos = lane + 64 * it;
             if (wpos >= xw_used) continue;
-            bf16x8 hi, lo;
+            float v[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const float t = raw[e][it];                   // out-of-range samples were loaded as 0 and lrelu(0) = 0
-                const float v = t > 0.f ? t : t * p.slope;
-                hi[e] = f2bf(v);
-                lo[e] = f2bf(v - bf2f(hi[e]));
+                v[e] = t > 0.f ? t : t * p.slope;
             }
-            *reinterpret_cast<bf16x8*>(&xT[0][wpos * RP_P + 8 * wave]) = hi;
-            *reinterpret_cast<bf16x8*>(&xT[1][wpos * RP_P + 8 * wave]) = lo;
+            bf16_planes_store<2>(v, &xT[0][wpos * RP_P + 8 * wave], PAIR_XW * RP_P);
         }
     };
 
@@ -164,24 +145,9 @@ __global__ void __launch_bounds__(256) respair_x3_kernel(const PairDev p) {
     fold_acc();
     {   // + b1, LeakyReLU, zero outside [0,T), split, to hT[chunk][plane][t][c]
         const int m = m0 + 32 * wave + l31;
-        const bool inr = m >= 0 && m < p.T;
 #pragma unroll
         for (int i = 0; i < CH; ++i)
-#pragma unroll
-            for (int rg = 0; rg < 4; ++rg) {
-                const int c = 8 * rg + 4 * g;          // channel inside chunk i
-                bf16x4 hi, lo;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float v = acc[i][rg * 4 + e] + p.b1[i * 32 + c + e];
-                    v = v > 0.f ? v : v * p.slope;
-                    if (!inr) v = 0.f;
-                    hi[e] = f2bf(v);
-                    lo[e] = f2bf(v - bf2f(hi[e]));
-                }
-                *reinterpret_cast<bf16x4*>(&hT[i][0][(32 * wave + l31) * RP_P + c]) = hi;
-                *reinterpret_cast<bf16x4*>(&hT[i][1][(32 * wave + l31) * RP_P + c]) = lo;
-            }
+            pair_store_intermediate<2>(acc[i], p.b1 + i * 32, p.slope, m >= 0 && m < p.T, &hT[i][0][(32 * wave + l31) * RP_P], PAIR_T * RP_P);
     }
     // ---- conv2 (dil 1) over the intermediate -> outputs n0 + [0,TT)
     zero_acc();
@@ -193,30 +159,20 @@ __global__ void __launch_bounds__(256) respair_x3_kernel(const PairDev p) {
         taps(p.w2, ch * 32, &hT[ch][0][0], &hT[ch][1][0], 1);
     }
     fold_acc();
-    // ---- epilogue (respair_epi.h; xh is free: conv2's last barrier is behind every wave)
+    // ---- epilogue (respair_dev.h; xh is free: conv2's last barrier is behind every wave)
     static_assert(sizeof(xh) >= PAIR_EPI_FLOATS * sizeof(float), "staging patches must fit");
     pair_epilogue<CH>(acc, reinterpret_cast<float*>(xh), p.staged, xb, p.out + (int64_t)b * p.bstride, p.T, n0, TT, p.b2, p.alpha, p.beta);
 }
 
 
 int launch_respair(const RespairArgs& a, hipStream_t st) {
-    if (a.C != 32 && a.C != 64) VB_FAIL(VB_E_INVALID, "respair: C=%d (32 or 64)", a.C);
-    if (a.k < 1 || (a.k & 1) == 0 || (a.k - 1) * a.dil > RP_HALO || a.k > 33) VB_FAIL(VB_E_INVALID, "respair: k=%d dil=%d", a.k, a.dil);
-    if (a.x == a.out) VB_FAIL(VB_E_INVALID, "respair: x and out must be distinct buffers (neighbouring workgroups re-read the halo)");
-    PairDev d;
-    d.x = a.x; d.out = a.out; d.bstride = (int64_t)a.C * a.T; d.T = a.T; d.k = a.k; d.dil = a.dil;
-    d.w1 = a.w1; d.w2 = a.w2; d.w_plane = (int64_t)a.k * a.C * a.C; d.b1 = a.b1; d.b2 = a.b2;
-    d.slope = a.slope; d.alpha = a.alpha; d.beta = a.beta;
-    const int TT = (RP_T - (a.k - 1)) & ~3;
-    d.staged = (a.T % 4 == 0 && aligned16(a.x) && aligned16(a.out) && !vb_tune().conv_direct_epi) ? 1 : 0;
-    dim3 grid(cdiv(a.T, TT), 1, a.B);
-    // two convolutions' worth of flops (the recomputed halo of conv1 is not counted)
-    ProfScope prof(3, 2.0 * 2.0 * a.B * (double)a.C * a.C * a.k * (double)a.T,
-                   4.0 * a.B * (double)a.C * a.T * (2.0 + (a.beta != 0.f ? 1.0 : 0.0)) + 2.0 * 4.0 * a.k * a.C * a.C, st);
+    PairLaunch L;
+    VB_TRY(pair_fill(a, "respair", L));
+    ProfScope prof(3, L.flops, L.act_bytes + 2.0 * 4.0 * a.k * a.C * a.C, st);
     // (a persistent variant with both convolutions' weights resident in LDS and the next window prefetched was measured slower,
     //  460 / 900 / 1100 us against 440 / 620 / 830 us for k = 3 / 7 / 11: one workgroup per CU cannot hide its own phase latencies)
-    if (a.C == 32) hipLaunchKernelGGL(respair_x3_kernel<1>, grid, dim3(256), 0, st, d);
-    else hipLaunchKernelGGL(respair_x3_kernel<2>, grid, dim3(256), 0, st, d);
+    if (a.C == 32) hipLaunchKernelGGL(respair_x3_kernel<1>, L.grid, dim3(256), 0, st, L.d);
+    else hipLaunchKernelGGL(respair_x3_kernel<2>, L.grid, dim3(256), 0, st, L.d);
     VB_CHECK_LAUNCH();
     return VB_OK;
 }
