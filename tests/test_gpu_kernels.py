@@ -62,6 +62,61 @@ def test_gemm_bf16(lib, M, N, K, npl):
     assert rel_l2(Cd, ref) < tol, describe(f"gemm {M}x{N}x{K} np={npl}", Cd, ref)
 
 
+GEMM_TILES = (None, "22", "33", "11", "21")      # VB_GEMM_TILE: the launcher's choice, then 128 x 128, 192 x 192, 64 x 64 and 128 x 64 forced
+
+
+def _tile_routes(run):
+    """run() under every forced tile configuration; the knob is removed again whatever happens"""
+    outs = []
+    try:
+        for cfg in GEMM_TILES:
+            L.set_tuning(VB_GEMM_TILE=cfg)
+            outs.append(run())
+    finally:
+        L.set_tuning(VB_GEMM_TILE=None)
+    return outs
+
+
+def _gemm_f32(lib, A, B, bias, npl):
+    """vb_gemm_bf16 (EPI_F32 with bias) into a NaN-filled output -> result, float64 reference, test_gemm_bf16's tolerance"""
+    (M, K), N = A.shape, B.shape[0]
+    Ap, Bp, bd = dev(pack.to_planes(A, npl)), dev(pack.to_planes(B, npl)), dev(bias)
+
+    def run():
+        Cd = torch.full((M, N), float("nan"), device="cuda")
+        L.check(lib.vb_gemm_bf16(L.ptr(Ap), L.ptr(Bp), L.ptr(bd), M, N, K, npl, L.ptr(Cd), L.stream_ptr()), "gemm")
+        sync()
+        return Cd
+    if npl == 1:
+        return run, Ap[0].float().double().cpu() @ Bp[0].float().double().cpu().T + bias.double(), 2e-6
+    return run, A.double() @ B.double().T + bias.double(), 3e-5
+
+
+@pytest.mark.parametrize("K", [64, 128, 192])     # one k-tile, a short ring that never refills, a ring that wraps
+@pytest.mark.parametrize("npl", [1, 2])
+def test_gemm_tile_routes_agree_on_ragged_edges(lib, K, npl):
+    """M = 385, N = 388: one leftover row and four leftover columns at 64-, 128- and 192-wide tiles alike, and every route's row-tile
+    count is padded up to the 8 XCDs (blocks that return early).  Every tile route gives the same bits (the whole-DiT bit-identity tests
+    run at T = 752, where no launch has such an edge tile), and the first is within test_gemm_bf16's tolerance of the float64 product."""
+    M, N = 385, 388
+    run, ref, tol = _gemm_f32(lib, rnd((M, K), "rA"), rnd((N, K), "rB", 0.05), rnd((N,), "rbias"), npl)
+    outs = _tile_routes(run)
+    print(f"ragged gemm K={K} np={npl}: rel_l2 {rel_l2(outs[0], ref):.3e} (tol {tol:g})")
+    assert rel_l2(outs[0], ref) < tol, describe(f"ragged gemm K={K} np={npl}", outs[0], ref)
+    for cfg, other in zip(GEMM_TILES[1:], outs[1:]):
+        assert torch.equal(outs[0], other), describe(f"ragged gemm K={K} np={npl}: VB_GEMM_TILE={cfg} vs the default route", other, outs[0])
+
+
+@pytest.mark.parametrize("K", [96, 72])           # the 32-deep 4-stage ring; the register-staged kernel
+@pytest.mark.parametrize("npl", [1, 2])
+def test_gemm_ragged_edges_on_the_k32_ring_and_the_register_staged_kernel(lib, K, npl):
+    M, N = 385, 388
+    run, ref, tol = _gemm_f32(lib, rnd((M, K), "rA"), rnd((N, K), "rB", 0.05), rnd((N,), "rbias"), npl)
+    out = run()
+    print(f"ragged gemm K={K} np={npl}: rel_l2 {rel_l2(out, ref):.3e} (tol {tol:g})")
+    assert rel_l2(out, ref) < tol, describe(f"ragged gemm K={K} np={npl}", out, ref)
+
+
 # ---------------------------------------------------------------- conv ------
 CONV_CASES = [  # B, Ci, T, Co, k, dil, in_act, res
     (2, 20, 50, 1536, 5, 1, 0, False),
@@ -347,6 +402,49 @@ def test_grouped_swiglu(lib, npl):
         ref[sel] = ref_cpu.swiglu(u[sel].double(), w1[g].double(), w2[g].double(), w3[g].double()) * scale[sel].double().unsqueeze(1)
     tol = 8e-3 if npl == 1 else 4e-5
     assert rel_l2(out, ref) < tol, describe(f"grouped_swiglu np={npl}", out, ref)
+
+
+@pytest.mark.parametrize("npl", [1, 2])
+def test_grouped_swiglu_tile_routes_agree_on_ragged_groups(lib, npl):
+    """Grouped launches (group_off, gathered rows) whose groups are an empty one, a one-row one, one that ends one row into its second
+    64-row tile and one that ends one row past 192 = 3 x 64 rows: hidden planes and the scattered fp32 output are the same bits under every
+    tile route, and within test_grouped_swiglu's tolerance of its reference."""
+    D, H, G = 768, 512, 4
+    counts = [0, 1, 65, 193]
+    N = sum(counts)
+    order = torch.from_numpy(prng.randint(9, N, 0, 1 << 20)).argsort()          # the groups' tokens, scattered over the token order
+    idx = torch.empty(N, dtype=torch.int32)
+    idx[order] = torch.repeat_interleave(torch.arange(G, dtype=torch.int32), torch.tensor(counts))
+    u = rnd((N, D), "su")
+    w1, w3, w2 = rnd((G, H, D), "sw1", 0.04), rnd((G, H, D), "sw3", 0.04), rnd((G, D, H), "sw2", 0.04)
+    scale = rnd((N,), "ss").abs() + 0.1
+    off = torch.zeros(2 * G + 1, dtype=torch.int32, device="cuda")
+    perm = torch.zeros(2 * N + lib.vb_route_bucket_scratch_ints(N, G), dtype=torch.int32, device="cuda")
+    L.check(lib.vb_route_bucket(L.ptr(dev(idx)), L.ptr(dev(idx)), N, G, L.ptr(off), L.ptr(perm), L.stream_ptr()), "bucket")
+    sync()
+    assert off[:G + 1].tolist() == [0, 0, 1, 66, 259]
+    w13 = torch.stack([w1, w3], dim=2).reshape(G, 2 * H, D)
+    up, w13p, w2p, sd = dev(pack.to_planes(u, npl)), dev(pack.to_planes(w13, npl)), dev(pack.to_planes(w2, npl)), dev(scale)
+
+    def run():
+        hidden = torch.zeros(npl, N, H, dtype=torch.bfloat16, device="cuda")
+        out = torch.full((N, D), float("nan"), device="cuda")
+        L.check(lib.vb_grouped_swiglu(L.ptr(up), L.ptr(perm), L.ptr(off), G, N, L.ptr(w13p), L.ptr(w2p), L.ptr(sd), D, H, npl,
+                                      L.ptr(hidden), L.ptr(out), L.stream_ptr()), "grouped_swiglu")
+        sync()
+        return hidden, out
+    outs = _tile_routes(run)
+    ref = torch.zeros(N, D, dtype=torch.float64)
+    for g in range(G):
+        sel = (idx == g).nonzero().squeeze(1)
+        if sel.numel():
+            ref[sel] = ref_cpu.swiglu(u[sel].double(), w1[g].double(), w2[g].double(), w3[g].double()) * scale[sel].double().unsqueeze(1)
+    tol = 8e-3 if npl == 1 else 4e-5
+    print(f"ragged grouped_swiglu np={npl}: rel_l2 {rel_l2(outs[0][1], ref):.3e} (tol {tol:g})")
+    assert rel_l2(outs[0][1], ref) < tol, describe(f"ragged grouped_swiglu np={npl}", outs[0][1], ref)
+    for cfg, (hidden, out) in zip(GEMM_TILES[1:], outs[1:]):
+        assert torch.equal(outs[0][0], hidden), f"hidden planes: VB_GEMM_TILE={cfg} vs the default route"
+        assert torch.equal(outs[0][1], out), describe(f"scattered output: VB_GEMM_TILE={cfg} vs the default route", out, outs[0][1])
 
 
 def test_fill_gumbel_statistics_and_keying(lib):

@@ -1,7 +1,7 @@
 // Fused kernels of the Band-MoE feed-forwards (gfx950): the routed experts' second product as one pair-bucketed launch
-// (moe_w2_pair_kernel) and the band experts' whole FFN in one kernel (band_ffn_kernel, band_ffn96_kernel).  Ring, swizzle, P16 layout and
-// the gated-residual epilogue are the GEMM kernels' (gemm_dev.h).
-#include "gemm_dev.h"
+// (moe_w2_pair_kernel) and the band experts' whole FFN in one kernel (band_ffn_kernel, band_ffn96_kernel).  Tile walk, swizzle, DMA feed and
+// the MFMA step are the GEMM kernels' (gemm_tile.h), P16 layout and the gated-residual epilogue too (gemm_dev.h).
+#include "gemm_tile.h"
 
 // ---- routed experts, second product, ONE launch (vocal2music_moe.py:154-167: y = m_c FFN^c(u) + m_a FFN^a(u)) ------------------
 // The two w2 GEMMs (caption group: scatter m_c * H_c W2c^T as fp32; acoustic group: read it back, add m_a * H_a W2a^T, write bf16
@@ -22,78 +22,40 @@ struct PairDev {
 };
 template <int TN>
 __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) moe_w2_pair_kernel(const PairDev p) {
-    constexpr int BKT = 64, NST = 2, CH = 8, RS = 8;
+    constexpr int BKT = 64, NST = 2;
     constexpr int BNP = 64 * TN;                             // columns per tile
-    constexpr int SPA = 4, SPB = BNP / 32;                   // 1-KB DMA pieces per wave: A (128 rows), B (BNP rows)
-    constexpr int ABYTES = BM * BKT * 2, BBYTES = BNP * BKT * 2, STAGE = ABYTES + BBYTES;
-    __shared__ __attribute__((aligned(16))) unsigned char lds[NST * STAGE];
+    using Feed = TileFeed<BM, BNP, BKT, 4>;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[NST * Feed::STAGE];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 1, wc = wave & 1;
 
-    int g = 0, row0 = 0, rows_end = 0, tile_n;
-    {
-        const int L = blockIdx.x, nN = p.n_tiles;
-        const int jx = L >> 3;
-        tile_n = jx % nN;
-        int tmg = (jx / nN) * 8 + (L & 7);
-        bool found = false;
-        const int G = p.E * p.E;
-        for (int gi = 0; gi < G; ++gi) {
-            const int lo = p.pair_off[gi], hi = p.pair_off[gi + 1];
-            const int nt = (hi - lo + BM - 1) / BM;
-            if (tmg < nt) { g = gi; row0 = lo + tmg * BM; rows_end = hi; found = true; break; }
-            tmg -= nt;
-        }
-        if (!found) return;
-    }
+    int g = 0, row0 = 0, rows_end = 0, tile_n, rt;
+    const int tmg = tile_xcd_order(p.n_tiles, tile_n, rt);
+    if (!tile_group_search<BM>(p.pair_off, p.E * p.E, tmg, g, row0, rows_end)) return;
     const int ec = g / p.E, ea = g - ec * p.E;
     const int n0 = tile_n * BNP;
     const int KT = p.H / BKT;
     const int total = 2 * KT;
 
-    const bf16_t* asrc[2][SPA]; const bf16_t* bsrc[SPB];     // B: one pointer per piece, the expert half is a uniform offset
+    const bf16_t* asrc[2][Feed::PA]; const bf16_t* bsrc[Feed::PB];     // B: one pointer per piece, the expert half is a uniform offset
     const int64_t boff1 = (int64_t)(p.E + ea - ec) * p.w_stride;
-#pragma unroll
-    for (int i = 0; i < SPA; ++i) {
-        const int r = RS * (wave * SPA + i) + lane / CH;
-        const int c = (lane % CH) ^ ((r >> 1) & 7);
-        int slot = row0 + r;
-        if (slot >= rows_end) slot = row0;
-        asrc[0][i] = p.Hs + (int64_t)slot * p.ldh + c * 8;                    // caption half: the pair slots ARE the caption slots
-        asrc[1][i] = p.Hs + (int64_t)p.pair_pa[slot] * p.ldh + c * 8;         // acoustic half: gathered
-    }
-#pragma unroll
-    for (int i = 0; i < SPB; ++i) {
-        const int r = RS * (wave * SPB + i) + lane / CH;
-        const int c = (lane % CH) ^ ((r >> 1) & 7);
-        int nrow = n0 + p16_src_row(r);                   // P16 column layout: a lane ends up with 16 consecutive output columns
-        if (nrow >= p.D) nrow = 0;
-        bsrc[i] = p.W2 + (int64_t)ec * p.w_stride + (int64_t)nrow * p.ldw + c * 8;
-    }
+    Feed::rows(asrc[0], p.Hs, p.ldh, row0, rows_end, row0, false, wave, lane, [](int slot) { return slot; });          // caption half: the pair slots ARE the caption slots
+    Feed::rows(asrc[1], p.Hs, p.ldh, row0, rows_end, row0, false, wave, lane, [&](int slot) { return p.pair_pa[slot]; });   // acoustic half: gathered
+    // P16 column layout: a lane ends up with 16 consecutive output columns
+    Feed::rows(bsrc, p.W2 + (int64_t)ec * p.w_stride, p.ldw, n0, p.D, 0, true, wave, lane, [](int nrow) { return nrow; });
     auto issue = [&](int t) {
-        const int st = t % NST;
         const int half = t >= KT ? 1 : 0;
         const int k0 = (t - half * KT) * BKT;
-        unsigned char* sa = lds + st * STAGE;
+        const bf16_t* ap[Feed::PA];
 #pragma unroll
-        for (int i = 0; i < SPA; ++i) {
-            const bf16_t* ap = half ? asrc[1][i] : asrc[0][i];
-            __builtin_amdgcn_global_load_lds((glb_ptr_t)(ap + k0), (lds_ptr_t)(sa + (wave * SPA + i) * 1024), 16, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < SPB; ++i)
-            __builtin_amdgcn_global_load_lds((glb_ptr_t)(bsrc[i] + (half ? boff1 : 0) + k0), (lds_ptr_t)(sa + ABYTES + (wave * SPB + i) * 1024), 16, 0, 0);
+        for (int i = 0; i < Feed::PA; ++i) ap[i] = half ? asrc[1][i] : asrc[0][i];
+        Feed::issue(ap, bsrc, wave, lds + (t % NST) * Feed::STAGE, k0, (half ? boff1 : 0) + k0);
     };
 
     f32x16 acc[2][TN];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    acc_zero(acc);
 
     issue(0);
     const int frow = lane & 31, fk = lane >> 5;
@@ -102,27 +64,16 @@ __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(2
         wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();           // tile t landed everywhere; everyone finished reading stage (t-1)%NST
         if (t + 1 < total) issue(t + 1);
-        const unsigned char* As = lds + st * STAGE;
-        const unsigned char* Bs = As + ABYTES;
+        const unsigned char* As = lds + st * Feed::STAGE;
+        const unsigned char* Bs = As + Feed::ABYTES;
         bf16x8 af[2][2], bf[2][TN];
-        auto fload = [&](int ks, int slot) {
-            const int c = ks * 2 + fk;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) af[slot][i] = *reinterpret_cast<const bf16x8*>(As + lds_off_t<BKT>(wr * 64 + i * 32 + frow, c));
-#pragma unroll
-            for (int j = 0; j < TN; ++j) bf[slot][j] = *reinterpret_cast<const bf16x8*>(Bs + lds_off_t<BKT>(wc * 32 * TN + j * 32 + frow, c));
-        };
-        fload(0, 0);
+        frag_load<2, TN, BKT>(As, Bs, wr * 64, wc * 32 * TN, 0, fk, frow, af[0], bf[0]);
 #pragma unroll
         for (int ks = 0; ks < BKT / 16; ++ks) {
             const int cur = ks & 1;
-            if (ks + 1 < BKT / 16) fload(ks + 1, cur ^ 1);
+            if (ks + 1 < BKT / 16) frag_load<2, TN, BKT>(As, Bs, wr * 64, wc * 32 * TN, ks + 1, fk, frow, af[cur ^ 1], bf[cur ^ 1]);
             __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[cur][j], af[cur][i], acc[i][j], 0, 0, 0);
+            mfma_step(af[cur], bf[cur], acc);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -230,12 +181,12 @@ __global__ void __launch_bounds__(NTHREADS) band_ffn_kernel(const BandDev p) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int r = 8 * (wave * 4 + i) + r8;
-        a_off[i] = r * BF_BAND + ((cs ^ ((r >> 1) & 7)) << 3);
+        a_off[i] = r * BF_BAND + ((cs ^ tile_swz<64>(r)) << 3);
     }
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         const int r = 16 * (wave * 3 + i) + (lane >> 2);
-        b_off[i] = r * p.H + (((lane & 3) ^ ((r >> 2) & 3)) << 3);
+        b_off[i] = r * p.H + (((lane & 3) ^ tile_swz<32>(r)) << 3);
     }
     const int nchunk = p.H / 64;
     const int nload = nchunk * 5;
@@ -260,17 +211,8 @@ __global__ void __launch_bounds__(NTHREADS) band_ffn_kernel(const BandDev p) {
     for (int q = 0; q < NSLOT - 1; ++q) issue(q);
 
     f32x16 acc1[3][2], acc2[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc1[i][j][r] = 0.f;
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc2[i][j][r] = 0.f;
-    }
+    acc_zero(acc1);
+    acc_zero(acc2);
     // step q multiplies load q; loads q+1 .. q+6 (already issued) may stay in flight: AHEAD = their DMA pieces per wave
     auto step_begin = [&](int q, auto ahead) -> const unsigned char* {
         wait_vmcnt<decltype(ahead)::value>();
@@ -283,39 +225,28 @@ __global__ void __launch_bounds__(NTHREADS) band_ffn_kernel(const BandDev p) {
     // six MFMAs was as long as the batch)
     auto phase_a = [&](int kc, const unsigned char* Bs) {
         bf16x8 bf[2][2];
-        auto rd = [&](int ks, int slot) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) bf[slot][j] = *reinterpret_cast<const bf16x8*>(Bs + lds_off_t<64>(wc * 64 + j * 32 + frow, ks * 2 + fk));
-        };
-        rd(0, 0);
+        frag_load<2, 64>(Bs, wc * 64, 0, fk, frow, bf[0]);
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-            if (ks + 1 < 4) rd(ks + 1, (ks + 1) & 1);
+            if (ks + 1 < 4) frag_load<2, 64>(Bs, wc * 64, ks + 1, fk, frow, bf[(ks + 1) & 1]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[ks & 1][j], ay[i][kc * 4 + ks], acc1[i][j], 0, 0, 0);
+            for (int i = 0; i < 3; ++i) mfma_row(ay[i][kc * 4 + ks], bf[ks & 1], acc1[i]);      // (A: the register-resident token fragments)
             __builtin_amdgcn_sched_barrier(0);
         }
     };
     auto phase_b = [&](const unsigned char* Bs, int khalf) {
         bf16x8 af[2][3], bf[2][3];
-        auto rd = [&](int ks, int slot) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) af[slot][i] = *reinterpret_cast<const bf16x8*>(Hs + lds_off_t<64>(wr * 96 + i * 32 + frow, (khalf * 2 + ks) * 2 + fk));
-#pragma unroll
-            for (int j = 0; j < 3; ++j) bf[slot][j] = *reinterpret_cast<const bf16x8*>(Bs + lds_off_t<32>(wc * 96 + j * 32 + frow, ks * 2 + fk));
+        auto rd = [&](int ks, int slot) {       // hidden chunk: 64-deep rows, k half khalf; w2 half-slab: 32-deep rows
+            frag_load<3, 64>(Hs, wr * 96, khalf * 2 + ks, fk, frow, af[slot]);
+            frag_load<3, 32>(Bs, wc * 96, ks, fk, frow, bf[slot]);
         };
         rd(0, 0);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             if (ks + 1 < 2) rd(ks + 1, (ks + 1) & 1);
             __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) acc2[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[ks & 1][j], af[ks & 1][i], acc2[i][j], 0, 0, 0);
+            mfma_step(af[ks & 1], bf[ks & 1], acc2);
             __builtin_amdgcn_sched_barrier(0);
         }
     };
@@ -410,12 +341,12 @@ __global__ void __launch_bounds__(NTHREADS) band_ffn96_kernel(const BandDev p) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int r = 16 * (wave * 2 + i) + (lane >> 2);                  // 16 rows x 64 B per piece
-        a_off[i] = r * B96_BAND + (((lane & 3) ^ ((r >> 2) & 3)) << 3);
+        a_off[i] = r * B96_BAND + (((lane & 3) ^ tile_swz<32>(r)) << 3);
     }
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         const int r = 8 * (wave * 3 + i) + (lane >> 3);                   // 8 rows x 128 B per piece
-        b_off[i] = r * p.H + (((lane & 7) ^ ((r >> 1) & 7)) << 3);
+        b_off[i] = r * p.H + (((lane & 7) ^ tile_swz<64>(r)) << 3);
     }
     const int nchunk = p.H / 64;
     const int nload = nchunk * 4;
@@ -439,17 +370,8 @@ __global__ void __launch_bounds__(NTHREADS) band_ffn96_kernel(const BandDev p) {
     for (int q = 0; q < NSLOT - 1; ++q) issue(q);
 
     f32x16 acc1[2][4], acc2[2][3];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc1[i][j][r] = 0.f;
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc2[i][j][r] = 0.f;
-    }
+    acc_zero(acc1);
+    acc_zero(acc2);
     // step q multiplies load q; loads q+1 .. q+6 (already issued) may stay in flight: AHEAD = their DMA pieces per wave
     auto step_begin = [&](int q, auto ahead) -> const unsigned char* {
         wait_vmcnt<decltype(ahead)::value>();
@@ -460,39 +382,24 @@ __global__ void __launch_bounds__(NTHREADS) band_ffn96_kernel(const BandDev p) {
     };
     auto phase_a = [&](int t, const unsigned char* Bs) {
         bf16x8 bf[2][4];
-        auto rd = [&](int ks, int slot) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bf[slot][j] = *reinterpret_cast<const bf16x8*>(Bs + lds_off_t<32>(j * 32 + frow, ks * 2 + fk));
-        };
-        rd(0, 0);
+        frag_load<4, 32>(Bs, 0, 0, fk, frow, bf[0]);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            if (ks + 1 < 2) rd(ks + 1, 1);
+            if (ks + 1 < 2) frag_load<4, 32>(Bs, 0, ks + 1, fk, frow, bf[1]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[ks][j], ay[i][t * 2 + ks], acc1[i][j], 0, 0, 0);
+            for (int i = 0; i < 2; ++i) mfma_row(ay[i][t * 2 + ks], bf[ks], acc1[i]);            // (A: the register-resident token fragments)
             __builtin_amdgcn_sched_barrier(0);
         }
     };
     auto phase_b = [&](const unsigned char* Bs) {
         bf16x8 af[2][2], bf[2][3];
-        auto rd = [&](int ks, int slot) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) af[slot][i] = *reinterpret_cast<const bf16x8*>(Hs + lds_off_t<64>(wave * 64 + i * 32 + frow, ks * 2 + fk));
-#pragma unroll
-            for (int j = 0; j < 3; ++j) bf[slot][j] = *reinterpret_cast<const bf16x8*>(Bs + lds_off_t<64>(j * 32 + frow, ks * 2 + fk));
-        };
-        rd(0, 0);
+        frag_load<2, 3, 64>(Hs, Bs, wave * 64, 0, 0, fk, frow, af[0], bf[0]);
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-            if (ks + 1 < 4) rd(ks + 1, (ks + 1) & 1);
+            if (ks + 1 < 4) frag_load<2, 3, 64>(Hs, Bs, wave * 64, 0, ks + 1, fk, frow, af[(ks + 1) & 1], bf[(ks + 1) & 1]);
             __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) acc2[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[ks & 1][j], af[ks & 1][i], acc2[i][j], 0, 0, 0);
+            mfma_step(af[ks & 1], bf[ks & 1], acc2);
             __builtin_amdgcn_sched_barrier(0);
         }
     };

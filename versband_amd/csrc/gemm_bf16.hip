@@ -10,8 +10,9 @@
 //   GEMM_P8            256 x 256, 8 waves, P16 epilogues (QKV + RoPE, routed SwiGLU): gemm_bf16_p8_kernel         -> launch_p8_product
 //   experiments build: GEMM_P8_VARIANT (other schedules / epilogues of the 8-wave kernel, launch_p8), GEMM_PK / GEMM_PK_F32 (persistent
 //                      kernel, gemm_bf16_pk.hip)
-// The fused Band-MoE kernels built from the same pieces are in band_ffn.hip.
-#include "gemm_dev.h"
+// What the main loops share - tile walk, LDS tile image and swizzle, DMA feed, k-tile offsets, the MFMA step - is gemm_tile.h; a kernel
+// body here is its schedule.  The fused Band-MoE kernels built from the same pieces are in band_ffn.hip.
+#include "gemm_tile.h"
 
 #define P8_MIN_TILES 96     // selection threshold of the 8-wave 256 x 256 kernel (tiles of the launch)
 
@@ -19,9 +20,8 @@
 //
 //  * 128x128x64 block tile, 256 threads = 4 waves (2x2), each wave 64x64 as 2x2
 //    v_mfma_f32_32x32x16_bf16 tiles, fp32 accumulation.
-//  * Both operands are K-contiguous; tiles are register-staged into an XOR-swizzled
-//    LDS image (16-B chunk c of row r lives at chunk c ^ ((r>>1)&7)) so the
-//    ds_read_b128 fragment reads of 16 consecutive rows hit 16 distinct 16-B slots.
+//  * Both operands are K-contiguous; tiles are register-staged into the XOR-swizzled
+//    LDS image of gemm_tile.h (lds_off_t), zero-filled past K and past the last row.
 //  * LDS is double buffered: global loads of tile t+1 are in flight while the MFMAs
 //    of tile t run; one barrier per K tile.
 //  * The MFMA is issued "swapped" (weights as the A operand) so a lane owns one
@@ -39,31 +39,8 @@ __global__ void __launch_bounds__(NTHREADS) gemm_bf16_kernel(const GemmDev p) {
     const int lane = tid & 63, wave = tid >> 6;
     const int wr = wave >> 1, wc = wave & 1;
 
-    // ---- which (group, m-tile) is this block -------------------------------------
-    int g = 0, row0, rows_end, tile_n;
-    {
-        // XCD-aware tile order: block L runs on XCD L%8 (8 private L2s).  All N-tiles of one M-tile are
-        // consecutive blocks of the SAME XCD, so an A tile is fetched into one L2 once instead of once per N-tile.
-        const int L = blockIdx.x, nN = p.n_tiles;
-        const int jx = L >> 3;
-        tile_n = jx % nN;
-        int tmg = (jx / nN) * 8 + (L & 7);
-        if (p.group_off) {
-            bool found = false;
-            for (int gi = 0; gi < p.ngroups; ++gi) {
-                int lo = p.group_off[gi], hi = p.group_off[gi + 1];
-                int nt = (hi - lo + BM - 1) / BM;
-                if (tmg < nt) { g = gi; row0 = lo + tmg * BM; rows_end = hi; found = true; break; }
-                tmg -= nt;
-            }
-            if (!found) return;
-        } else {
-            g = blockIdx.z;              // groups that share the row range (band experts)
-            row0 = tmg * BM; rows_end = p.M;
-            if (row0 >= rows_end) return;
-        }
-    }
-    const int n0 = tile_n * BN;
+    int g, row0, rows_end, n0;
+    if (!gemm_tile_pos<BM, BN, TILE_GROUPS>(p, g, row0, rows_end, n0)) return;
     const int K = p.K;
     const int KT = (K + BK - 1) / BK;
     const int total = KT * p.nseg;
@@ -81,16 +58,11 @@ __global__ void __launch_bounds__(NTHREADS) gemm_bf16_kernel(const GemmDev p) {
         int nrow = n0 + r;
         bval[i] = nrow < p.N;
         bptr[i] = p.B + g * p.b_group_stride + (int64_t)(bval[i] ? nrow : 0) * p.ldb + cch * 8;
-        lds_w[i] = lds_off(r, cch);
+        lds_w[i] = lds_off_t<BK>(r, cch);
     }
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    acc_zero(acc);
 
     uint4 ra[4], rb[4];
     auto gload = [&](int t) {
@@ -123,18 +95,15 @@ __global__ void __launch_bounds__(NTHREADS) gemm_bf16_kernel(const GemmDev p) {
         if (t + 1 < total) gload(t + 1);
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
+            // (this kernel's own fragment read, A and B alternating: through frag_load - A's fragments, then B's - every instance gained
+            //  four s_waitcnt between its MFMAs and 4 VGPRs)
             bf16x8 af[2], bf[2];
-            int c = ks * 2 + fk;
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                af[i] = *reinterpret_cast<const bf16x8*>(&lds[buf][0][lds_off(wr * 64 + i * 32 + frow, c)]);
-                bf[i] = *reinterpret_cast<const bf16x8*>(&lds[buf][1][lds_off(wc * 64 + i * 32 + frow, c)]);
+                af[i] = *reinterpret_cast<const bf16x8*>(&lds[buf][0][lds_off_t<BK>(wr * 64 + i * 32 + frow, ks * 2 + fk)]);
+                bf[i] = *reinterpret_cast<const bf16x8*>(&lds[buf][1][lds_off_t<BK>(wc * 64 + i * 32 + frow, ks * 2 + fk)]);
             }
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[j], af[i], acc[i][j], 0, 0, 0);
+            mfma_step(af, bf, acc);
         }
         if (t + 1 < total) lstore(buf ^ 1);
         __syncthreads();
@@ -143,25 +112,18 @@ __global__ void __launch_bounds__(NTHREADS) gemm_bf16_kernel(const GemmDev p) {
     wave_epilogue<EPI>(p, g, acc, row0 + wr * 64, rows_end, n0 + wc * 64, frow, fk);
 }
 
-// ---- variant 2: tiles DMA'd straight into an LDS ring (global_load_lds, 16 B / lane, no VGPR staging, no ds_write) ----
-// The LDS image must be lane-linear (wave-uniform base + lane*16), so the XOR swizzle is applied to the per-lane
-// SOURCE chunk instead: LDS slot (row, c') receives global chunk c = c' ^ swz(row); the fragment reads use the same
-// involution.  NST stages: tiles t+1 .. t+NST-1 are in flight while tile t is multiplied; the wait is a COUNTED
+// ---- 128 x 128 tiles DMA'd straight into an LDS ring (gemm_tile.h: TileFeed, source-side swizzle) -----------------------------------
+// NST stages: tiles t+1 .. t+NST-1 are in flight while tile t is multiplied; the wait is a COUNTED
 // s_waitcnt vmcnt((NST-2)*loads_per_tile) + a raw s_barrier, so the DMA queue is never drained inside the loop.
 // Needs K % BKT == 0 (no zero fill on this path); out-of-range rows read a clamped valid row and are never stored.
-
-
 // ABL (tuning only): 1 = no tile DMA in the loop, 2 = no MFMA, 3 = no LDS fragment reads
 template <int EPI, int BKT, int NST, int ABL = 0, bool P16 = false>
 __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(BKT * NST == 96 ? 3 : 1, BKT * NST == 96 ? 3 : 8)))
 gemm_bf16_glds_kernel(const GemmDev p) {
     static_assert(!P16 || EPI == EPI_QKV_ROPE || EPI == EPI_SWIGLU, "the P16 column layout is wired for the QKV + RoPE and SwiGLU epilogues");
-    constexpr int CH = BKT / 8;              // 16-B chunks per tile row
-    constexpr int RS = 64 / CH;              // tile rows covered by one wave-wide DMA (1 KB)
-    constexpr int SPW = CH / 2;              // DMA pieces per wave per operand per tile
-    constexpr int LPT = 2 * SPW;             // loads per wave per tile
-    constexpr int OPB = BM * BKT * 2;        // bytes of one operand tile
-    __shared__ __attribute__((aligned(16))) unsigned char lds[NST * 2 * OPB];
+    using Feed = TileFeed<BM, BN, BKT, 4>;
+    constexpr int LPT = Feed::LPT, OPB = Feed::ABYTES;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[NST * Feed::STAGE];
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -170,106 +132,24 @@ gemm_bf16_glds_kernel(const GemmDev p) {
     unsigned long long t_start = 0;
     if constexpr (EPI == EPI_F32) { if (p.trace) t_start = __builtin_amdgcn_s_memtime(); }
 
-    int g = 0, row0, rows_end, tile_n;
-    {
-        const int L = blockIdx.x, nN = p.n_tiles;
-        const int jx = L >> 3;
-        int rt;
-        if (p.ncc > 0) {
-            // wide N (QKV: 18 column tiles = 3.5 MB of weights against a 4 MB L2 per XCD): an XCD walks ALL its row tiles for one
-            // chunk of ncc column tiles before moving to the next chunk, so the live weight set is ncc/nN of the matrix
-            const int per = p.rpx * p.ncc;
-            const int ch = jx / per, rem = jx - ch * per;
-            rt = rem / p.ncc;
-            tile_n = ch * p.ncc + (rem - rt * p.ncc);
-        } else {
-            tile_n = jx % nN;
-            rt = jx / nN;
-        }
-        int tmg = rt * 8 + (L & 7);
-        if (p.grp_rows > 0) {
-            int lt;       // row tile inside the group
-            if (p.grp_xcd) {
-                // per-group B operands (caption-gate scores: one folded key matrix per clip) and a multiple of 8 groups: XCD x = L & 7 serves
-                // the groups x, x + 8, ... - all row tiles of a group on one XCD, its B operand in one L2 (it was fetched by all eight)
-                g = (L & 7) + 8 * (rt / p.grp_tiles);
-                lt = rt % p.grp_tiles;
-            } else {
-                // shared B operand (conv-as-GEMM) or a group count the XCDs do not divide: plain enumeration of (group, row tile)
-                g = tmg / p.grp_tiles;
-                lt = tmg - g * p.grp_tiles;
-            }
-            if (g >= p.ngroups) return;
-            row0 = g * p.grp_rows + lt * BM; rows_end = (g + 1) * p.grp_rows;
-            if (row0 >= rows_end) return;
-        } else if (p.group_off) {
-            bool found = false;
-            for (int gi = 0; gi < p.ngroups; ++gi) {
-                int lo = p.group_off[gi], hi = p.group_off[gi + 1];
-                int nt = (hi - lo + BM - 1) / BM;
-                if (tmg < nt) { g = gi; row0 = lo + tmg * BM; rows_end = hi; found = true; break; }
-                tmg -= nt;
-            }
-            if (!found) return;
-        } else {
-            g = blockIdx.z;
-            row0 = tmg * BM; rows_end = p.M;
-            if (row0 >= rows_end) return;
-        }
-    }
-    const int n0 = tile_n * BN;
+    int g, row0, rows_end, n0;
+    if (!gemm_tile_pos<BM, BN, TILE_UNIFORM_XCD>(p, g, row0, rows_end, n0)) return;
     const int KT = (ABL == 5) ? 0 : p.K / BKT;
     const int total = KT * p.nseg;
     // QKV, P16: a tile of the V third exchanges the operands' roles (see wave_epilogue_vt_p16) - the permutation then belongs to the TOKEN rows
     bool vsec = false;
     if constexpr (P16 && EPI == EPI_QKV_ROPE) vsec = n0 >= 2 * p.D && (p.T & 15) == 0 && (p.Tpad & 7) == 0 && !p.no_vt16;       // (16-byte V^T stores: T and the padded pitch)
 
-    const bf16_t* asrc[SPW]; const bf16_t* bsrc[SPW];
-#pragma unroll
-    for (int i = 0; i < SPW; ++i) {
-        const int s = wave * SPW + i;
-        const int r = RS * s + lane / CH;
-        const int cs = lane % CH;
-        const int c = (BKT == 64) ? (cs ^ ((r >> 1) & 7)) : (cs ^ ((r >> 2) & 3));
-        int slot = row0 + (vsec ? p16_src_row(r) : r);
-        if (slot >= rows_end) slot = row0;
-        int arow = p.a_rows ? p.a_rows[slot] : slot;
-        if constexpr (EPI == EPI_F32_CT) {
-            if (p.conv_ktap > 0) arow = g * p.conv_agrp + p.conv_arow0 + (slot - g * p.grp_rows);      // clip g's padded plane image, row of tap 0
-        }
-        asrc[i] = p.A + (int64_t)arow * p.lda + g * p.a_koff_group + c * 8;
-        int nrow = n0 + ((P16 && !vsec) ? p16_src_row(r) : r);
-        if (nrow >= p.N) nrow = 0;
-        bsrc[i] = p.B + g * p.b_group_stride + (int64_t)nrow * p.ldb + c * 8;
-    }
+    const bf16_t* asrc[Feed::PA]; const bf16_t* bsrc[Feed::PB];
+    gemm_feed_setup<EPI, Feed>(p, g, row0, rows_end, n0, vsec, P16 && !vsec, wave, lane, asrc, bsrc);
     auto issue = [&](int t) {
-        const int st = t % NST;
-        const int seg = t / KT;
-        const int k0 = (t - seg * KT) * BKT;
-        int64_t ao = (seg == 1 ? p.a_plane : 0) + k0;
-        int64_t bo = (seg == 2 ? p.b_plane : 0) + k0;
-        if constexpr (EPI == EPI_F32_CT && BKT == 64) {
-            if (p.conv_ktap > 0) {       // conv mode: k-tile -> (tap, channel chunk); tap j reads the rows j * dil below tap 0's
-                const int kt = t - seg * KT, tap = kt / p.conv_ktap, c0 = (kt - tap * p.conv_ktap) * BKT;
-                ao = (seg == 1 ? p.a_plane : 0) + (int64_t)tap * p.conv_dil * p.lda + c0;
-                bo = (seg == 2 ? p.b_plane : 0) + (int64_t)tap * p.conv_btap + c0;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < SPW; ++i) {
-            const int s = wave * SPW + i;
-            __builtin_amdgcn_global_load_lds((glb_ptr_t)(asrc[i] + ao), (lds_ptr_t)(&lds[(st * 2 + 0) * OPB + s * 1024]), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((glb_ptr_t)(bsrc[i] + bo), (lds_ptr_t)(&lds[(st * 2 + 1) * OPB + s * 1024]), 16, 0, 0);
-        }
+        int64_t ao, bo;
+        gemm_k_offsets<EPI, BKT>(p, t, KT, ao, bo);
+        Feed::issue(asrc, bsrc, wave, lds + (t % NST) * Feed::STAGE, ao, bo, 0, Feed::PA);
     };
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    acc_zero(acc);
 
 #pragma unroll
     for (int t = 0; t < NST - 1; ++t)
@@ -291,16 +171,13 @@ gemm_bf16_glds_kernel(const GemmDev p) {
         // k-step ks (the compiler otherwise reuses one register set and serialises read -> wait -> 4 MFMA per k-step)
         bf16x8 af[2][2], bf[2][2];
         auto fload = [&](int ks, int slot) {
-            const int c = ks * 2 + fk;
+            if constexpr (ABL == 3) {
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                if constexpr (ABL == 3) {
+                for (int i = 0; i < 2; ++i)
 #pragma unroll
                     for (int e = 0; e < 8; ++e) { af[slot][i][e] = (bf16_t)(float)(t + e); bf[slot][i][e] = (bf16_t)(float)(ks + e); }
-                } else {
-                    af[slot][i] = *reinterpret_cast<const bf16x8*>(As + lds_off_t<BKT>(wr * 64 + i * 32 + frow, c));
-                    bf[slot][i] = *reinterpret_cast<const bf16x8*>(Bs + lds_off_t<BKT>(wc * 64 + i * 32 + frow, c));
-                }
+            } else {
+                frag_load<2, 2, BKT>(As, Bs, wr * 64, wc * 64, ks, fk, frow, af[slot], bf[slot]);
             }
         };
         fload(0, 0);
@@ -309,17 +186,16 @@ gemm_bf16_glds_kernel(const GemmDev p) {
             const int cur = ks & 1;
             if (ks + 1 < BKT / 16) fload(ks + 1, cur ^ 1);
             __builtin_amdgcn_sched_barrier(0);
+            if constexpr (ABL == 2) {
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
+                for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    if constexpr (ABL == 2) {
+                    for (int j = 0; j < 2; ++j)
 #pragma unroll
                         for (int e = 0; e < 8; ++e) acc[i][j][e] += (float)af[cur][i][e] * (float)bf[cur][j][e];
-                    } else {
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[cur][j], af[cur][i], acc[i][j], 0, 0, 0);
-                    }
-                }
+            } else {
+                mfma_step(af[cur], bf[cur], acc);
+            }
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -344,16 +220,7 @@ gemm_bf16_glds_kernel(const GemmDev p) {
         else if constexpr (STAGED_EPI(EPI)) staged_epilogue<EPI, 2, 2>(p, g, acc, reinterpret_cast<float*>(lds), row0, rows_end, n0, tid, wr, wc, frow, fk);
         else wave_epilogue<EPI>(p, g, acc, row0 + wr * 64, rows_end, n0 + wc * 64, frow, fk);
     }
-    if constexpr (EPI == EPI_F32) {
-        if (p.trace && tid == 0) {
-            __builtin_amdgcn_s_waitcnt(0);
-            unsigned hwid, xcc;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-            unsigned long long* tr = p.trace + (size_t)blockIdx.x * 4;
-            tr[0] = t_start; tr[1] = t_loop; tr[2] = __builtin_amdgcn_s_memtime(); tr[3] = ((unsigned long long)xcc << 32) | hwid;
-        }
-    }
+    if constexpr (EPI == EPI_F32) gemm_trace_write(p, t_start, t_start, t_loop);       // (no prologue timestamp in this kernel)
 }
 
 // ---- 128 x 192 tiles, two workgroups per CU, gated-residual epilogue in the P16 layout (attention out-proj at >= 8 clips) ----------
@@ -370,62 +237,30 @@ gemm_bf16_glds_kernel(const GemmDev p) {
 //  slowed the un-fused path of the same kernel, 36 -> 55 us.)
 template <int TN>
 __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) gemm_bf16_wide_resid_kernel(const GemmDev p) {
-    constexpr int BKT = 64, NST = 2, CH = 8, RS = 8;
+    constexpr int BKT = 64, NST = 2;
     constexpr int BNP = 64 * TN;
-    constexpr int SPA = 4, SPB = BNP / 32;
-    constexpr int ABYTES = BM * BKT * 2, BBYTES = BNP * BKT * 2, STAGE = ABYTES + BBYTES;
-    __shared__ __attribute__((aligned(16))) unsigned char lds[NST * STAGE];
+    using Feed = TileFeed<BM, BNP, BKT, 4>;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[NST * Feed::STAGE];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 1, wc = wave & 1;
-    const int L = blockIdx.x, nN = p.n_tiles;
-    const int jx = L >> 3;
-    const int tile_n = jx % nN;
-    const int row0 = ((jx / nN) * 8 + (L & 7)) * BM, rows_end = p.M;
-    if (row0 >= rows_end) return;
-    const int n0 = tile_n * BNP;
+    int g, row0, rows_end, n0;
+    if (!gemm_tile_pos<BM, BNP, TILE_UNGROUPED>(p, g, row0, rows_end, n0)) return;
     const int KT = p.K / BKT;
     const int total = KT * p.nseg;
 
-    const bf16_t* asrc[SPA]; const bf16_t* bsrc[SPB];
-#pragma unroll
-    for (int i = 0; i < SPA; ++i) {
-        const int r = RS * (wave * SPA + i) + lane / CH;
-        const int c = (lane % CH) ^ ((r >> 1) & 7);
-        int slot = row0 + r;
-        if (slot >= rows_end) slot = row0;
-        asrc[i] = p.A + (int64_t)slot * p.lda + c * 8;
-    }
-#pragma unroll
-    for (int i = 0; i < SPB; ++i) {
-        const int r = RS * (wave * SPB + i) + lane / CH;
-        const int c = (lane % CH) ^ ((r >> 1) & 7);
-        int nrow = n0 + p16_src_row(r);
-        if (nrow >= p.N) nrow = 0;
-        bsrc[i] = p.B + (int64_t)nrow * p.ldb + c * 8;
-    }
+    // (plain rows of both operands: this kernel is launched without groups or gathered rows, gemm_wide_resid_shape)
+    const bf16_t* asrc[Feed::PA]; const bf16_t* bsrc[Feed::PB];
+    Feed::rows(asrc, p.A, p.lda, row0, rows_end, row0, false, wave, lane, [](int r) { return r; });
+    Feed::rows(bsrc, p.B, p.ldb, n0, p.N, 0, true, wave, lane, [](int r) { return r; });
     auto issue = [&](int t) {
-        const int st = t % NST;
-        const int seg = t / KT;
-        const int k0 = (t - seg * KT) * BKT;
-        const int64_t ao = (seg == 1 ? p.a_plane : 0) + k0;
-        const int64_t bo = (seg == 2 ? p.b_plane : 0) + k0;
-        unsigned char* sa = lds + st * STAGE;
-#pragma unroll
-        for (int i = 0; i < SPA; ++i)
-            __builtin_amdgcn_global_load_lds((glb_ptr_t)(asrc[i] + ao), (lds_ptr_t)(sa + (wave * SPA + i) * 1024), 16, 0, 0);
-#pragma unroll
-        for (int i = 0; i < SPB; ++i)
-            __builtin_amdgcn_global_load_lds((glb_ptr_t)(bsrc[i] + bo), (lds_ptr_t)(sa + ABYTES + (wave * SPB + i) * 1024), 16, 0, 0);
+        int64_t ao, bo;
+        gemm_k_offsets<EPI_RESID_GATE, BKT>(p, t, KT, ao, bo);
+        Feed::issue(asrc, bsrc, wave, lds + (t % NST) * Feed::STAGE, ao, bo);
     };
     f32x16 acc[2][TN];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    acc_zero(acc);
     issue(0);
     const int frow = lane & 31, fk = lane >> 5;
     for (int t = 0; t < total; ++t) {
@@ -433,27 +268,16 @@ __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(2
         wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         if (t + 1 < total) issue(t + 1);
-        const unsigned char* As = lds + st * STAGE;
-        const unsigned char* Bs = As + ABYTES;
+        const unsigned char* As = lds + st * Feed::STAGE;
+        const unsigned char* Bs = As + Feed::ABYTES;
         bf16x8 af[2][2], bf[2][TN];
-        auto fload = [&](int ks, int slot) {
-            const int c = ks * 2 + fk;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) af[slot][i] = *reinterpret_cast<const bf16x8*>(As + lds_off_t<BKT>(wr * 64 + i * 32 + frow, c));
-#pragma unroll
-            for (int j = 0; j < TN; ++j) bf[slot][j] = *reinterpret_cast<const bf16x8*>(Bs + lds_off_t<BKT>(wc * 32 * TN + j * 32 + frow, c));
-        };
-        fload(0, 0);
+        frag_load<2, TN, BKT>(As, Bs, wr * 64, wc * 32 * TN, 0, fk, frow, af[0], bf[0]);
 #pragma unroll
         for (int ks = 0; ks < BKT / 16; ++ks) {
             const int cur = ks & 1;
-            if (ks + 1 < BKT / 16) fload(ks + 1, cur ^ 1);
+            if (ks + 1 < BKT / 16) frag_load<2, TN, BKT>(As, Bs, wr * 64, wc * 32 * TN, ks + 1, fk, frow, af[cur ^ 1], bf[cur ^ 1]);
             __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[cur][j], af[cur][i], acc[i][j], 0, 0, 0);
+            mfma_step(af[cur], bf[cur], acc);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -495,7 +319,7 @@ __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(2
     }
 }
 
-// ---- variant 3: big block tiles, one workgroup per CU --------------------------------------------------------------
+// ---- gemm_bf16_big_kernel: (64 TM) x (64 TN) block tiles, 192 x 192 at one workgroup per CU ---------------------------------------
 // Per-block traces of the 128x128 kernel (tools/gemm_trace.py) show a k-iteration costs ~1500 cycles against 640 cycles
 // of MFMA: every iteration moves 32 KB through the CU's 64 B/clk vector-memory path (512 cycles at best) and waits for
 // the tile issued one iteration earlier, and a launch of M=12032 x N=768 leaves 2.2 tiles per CU (priced as 3).  This
@@ -512,9 +336,8 @@ __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(2
 template <int EPI, int TM, int TN, int NSTB, int ABL = 0>
 __global__ void __launch_bounds__(NTHREADS) gemm_bf16_big_kernel(const GemmDev p) {
     constexpr int BMB = 64 * TM, BNB = 64 * TN;
-    constexpr int PA = BMB / 32, PB = BNB / 32;        // 1-KB DMA pieces (8 tile rows) per wave per tile
-    constexpr int LPT = PA + PB;
-    constexpr int ABYTES = BMB * 128, BBYTES = BNB * 128, STAGE = ABYTES + BBYTES;
+    using Feed = TileFeed<BMB, BNB, 64, 4>;
+    constexpr int LPT = Feed::LPT, ABYTES = Feed::ABYTES, STAGE = Feed::STAGE;
     extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
 
     const int tid = threadIdx.x;
@@ -524,90 +347,21 @@ __global__ void __launch_bounds__(NTHREADS) gemm_bf16_big_kernel(const GemmDev p
     unsigned long long t_start = 0, t_pro = 0, t_loop = 0;
     if constexpr (EPI == EPI_F32) { if (p.trace) t_start = __builtin_amdgcn_s_memtime(); }
 
-    int g = 0, row0, rows_end, tile_n;
-    {
-        const int L = blockIdx.x, nN = p.n_tiles;
-        const int jx = L >> 3;
-        tile_n = jx % nN;
-        int tmg = (jx / nN) * 8 + (L & 7);
-        if (p.grp_rows > 0) {
-            // uniform groups (conv-as-GEMM: one clip per group, shared weights): plain enumeration of (group, row tile)
-            g = tmg / p.grp_tiles;
-            if (g >= p.ngroups) return;
-            row0 = g * p.grp_rows + (tmg - g * p.grp_tiles) * BMB; rows_end = (g + 1) * p.grp_rows;
-            if (row0 >= rows_end) return;
-        } else if (p.group_off) {
-            bool found = false;
-            for (int gi = 0; gi < p.ngroups; ++gi) {
-                int lo = p.group_off[gi], hi = p.group_off[gi + 1];
-                int nt = (hi - lo + BMB - 1) / BMB;
-                if (tmg < nt) { g = gi; row0 = lo + tmg * BMB; rows_end = hi; found = true; break; }
-                tmg -= nt;
-            }
-            if (!found) return;
-        } else {
-            g = blockIdx.z;
-            row0 = tmg * BMB; rows_end = p.M;
-            if (row0 >= rows_end) return;
-        }
-    }
-    const int n0 = tile_n * BNB;
+    int g, row0, rows_end, n0;
+    if (!gemm_tile_pos<BMB, BNB, TILE_UNIFORM>(p, g, row0, rows_end, n0)) return;
     const int KT = p.K / 64;
     const int total = KT * p.nseg;
 
-    const bf16_t* asrc[PA]; const bf16_t* bsrc[PB];
-    {
-        const int r8 = lane >> 3, cs = lane & 7;
-#pragma unroll
-        for (int i = 0; i < PA; ++i) {
-            const int r = 8 * (wave * PA + i) + r8;
-            const int c = cs ^ ((r >> 1) & 7);
-            int slot = row0 + r;
-            if (slot >= rows_end) slot = row0;
-            int arow = p.a_rows ? p.a_rows[slot] : slot;
-            if constexpr (EPI == EPI_F32_CT) {
-                if (p.conv_ktap > 0) arow = g * p.conv_agrp + p.conv_arow0 + (slot - g * p.grp_rows);
-            }
-            asrc[i] = p.A + (int64_t)arow * p.lda + g * p.a_koff_group + c * 8;
-        }
-#pragma unroll
-        for (int i = 0; i < PB; ++i) {
-            const int r = 8 * (wave * PB + i) + r8;
-            const int c = cs ^ ((r >> 1) & 7);
-            int nrow = n0 + r;
-            if (nrow >= p.N) nrow = 0;
-            bsrc[i] = p.B + g * p.b_group_stride + (int64_t)nrow * p.ldb + c * 8;
-        }
-    }
+    const bf16_t* asrc[Feed::PA]; const bf16_t* bsrc[Feed::PB];
+    gemm_feed_setup<EPI, Feed>(p, g, row0, rows_end, n0, false, false, wave, lane, asrc, bsrc);
     auto issue = [&](int t) {
-        const int st = t % NSTB;
-        const int seg = t / KT;
-        const int k0 = (t - seg * KT) * 64;
-        int64_t ao = (seg == 1 ? p.a_plane : 0) + k0;
-        int64_t bo = (seg == 2 ? p.b_plane : 0) + k0;
-        if constexpr (EPI == EPI_F32_CT) {
-            if (p.conv_ktap > 0) {       // conv mode: k-tile -> (tap, channel chunk), see gemm_bf16_glds_kernel
-                const int kt = t - seg * KT, tap = kt / p.conv_ktap, c0 = (kt - tap * p.conv_ktap) * 64;
-                ao = (seg == 1 ? p.a_plane : 0) + (int64_t)tap * p.conv_dil * p.lda + c0;
-                bo = (seg == 2 ? p.b_plane : 0) + (int64_t)tap * p.conv_btap + c0;
-            }
-        }
-        unsigned char* sa = ldsb + st * STAGE;
-#pragma unroll
-        for (int i = 0; i < PA; ++i)
-            __builtin_amdgcn_global_load_lds((glb_ptr_t)(asrc[i] + ao), (lds_ptr_t)(sa + (wave * PA + i) * 1024), 16, 0, 0);
-#pragma unroll
-        for (int i = 0; i < PB; ++i)
-            __builtin_amdgcn_global_load_lds((glb_ptr_t)(bsrc[i] + bo), (lds_ptr_t)(sa + ABYTES + (wave * PB + i) * 1024), 16, 0, 0);
+        int64_t ao, bo;
+        gemm_k_offsets<EPI, 64>(p, t, KT, ao, bo);
+        Feed::issue(asrc, bsrc, wave, ldsb + (t % NSTB) * STAGE, ao, bo);
     };
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    acc_zero(acc);
 
     // Software pipeline across tiles (NSTB = 3 stages, 2 tiles of DMA in flight):
     //   a tile's LAST fragment set (k-step 3) is read into registers during k-step 2, so its stage is dead at the
@@ -623,7 +377,6 @@ __global__ void __launch_bounds__(NTHREADS) gemm_bf16_big_kernel(const GemmDev p
     auto fload = [&](int st, int ks, int slot) {
         const unsigned char* As = ldsb + st * STAGE;
         const unsigned char* Bs = As + ABYTES;
-        const int c = ks * 2 + fk;
         if constexpr (ABL == 3) {
 #pragma unroll
             for (int i = 0; i < TM; ++i)
@@ -635,23 +388,19 @@ __global__ void __launch_bounds__(NTHREADS) gemm_bf16_big_kernel(const GemmDev p
                 for (int e = 0; e < 8; ++e) bf[slot][j][e] = (bf16_t)(float)(ks + e + j);
             return;
         }
-#pragma unroll
-        for (int i = 0; i < TM; ++i) af[slot][i] = *reinterpret_cast<const bf16x8*>(As + lds_off_t<64>(wr * 32 * TM + i * 32 + frow, c));
-#pragma unroll
-        for (int j = 0; j < TN; ++j) bf[slot][j] = *reinterpret_cast<const bf16x8*>(Bs + lds_off_t<64>(wc * 32 * TN + j * 32 + frow, c));
+        frag_load<TM, TN, 64>(As, Bs, wr * 32 * TM, wc * 32 * TN, ks, fk, frow, af[slot], bf[slot]);
     };
     auto mfmas = [&](int slot) {
+        if constexpr (ABL == 2) {
 #pragma unroll
-        for (int i = 0; i < TM; ++i)
+            for (int i = 0; i < TM; ++i)
 #pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                if constexpr (ABL == 2) {
+                for (int j = 0; j < TN; ++j)
 #pragma unroll
                     for (int e = 0; e < 2; ++e) acc[i][j][e] += (float)af[slot][i][e] * (float)bf[slot][j][e];
-                } else {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[slot][j], af[slot][i], acc[i][j], 0, 0, 0);
-                }
-            }
+        } else {
+            mfma_step(af[slot], bf[slot], acc);
+        }
     };
     if (total > 2) wait_vmcnt<2 * LPT>();
     else if (total > 1) wait_vmcnt<LPT>();
@@ -697,20 +446,10 @@ __global__ void __launch_bounds__(NTHREADS) gemm_bf16_big_kernel(const GemmDev p
         else staged_epilogue<EPI, TM, TN>(p, g, acc, reinterpret_cast<float*>(ldsb), row0, rows_end, n0, tid, wr, wc, frow, fk);
     } else
     staged_epilogue<EPI, TM, TN>(p, g, acc, reinterpret_cast<float*>(ldsb), row0, rows_end, n0, tid, wr, wc, frow, fk);
-    if constexpr (EPI == EPI_F32) {
-        if (p.trace && tid == 0) {
-            __builtin_amdgcn_s_waitcnt(0);
-            unsigned hwid, xcc;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-            unsigned long long* tr = p.trace + (size_t)blockIdx.x * 4;
-            tr[0] = t_start; tr[1] = t_loop; tr[2] = __builtin_amdgcn_s_memtime();
-            tr[3] = ((unsigned long long)(t_pro - t_start) << 36) | ((unsigned long long)xcc << 32) | hwid;
-        }
-    }
+    if constexpr (EPI == EPI_F32) gemm_trace_write(p, t_start, t_pro, t_loop);
 }
 
-// ---- variant 4: 256 x 256 tiles, 8 waves.  Round 2 measured it slower inside the DiT (quad-layout epilogues, docs/history.md, round 2) and
+// ---- 256 x 256 tiles, 8 waves (gemm_bf16_p8_kernel).  Round 2 measured it slower inside the DiT (quad-layout epilogues, docs/history.md, round 2) and
 // kept it in the experiments build; with the P16 epilogues of round 3 it wins on the two wide projections (round 4, same box:
 // QKV + RoPE 65.3 -> 60.7 us, whole two-stream run +3.2 %, two clips 56.8 -> 51.8 ms) and the product library instantiates exactly those
 // two forms (software-pipelined schedule, P16 layout; ring shape: launch_p8_product).  The other schedules / ring shapes /
@@ -743,13 +482,11 @@ template <int EPI, int BKT, int NST, int PP, int ABL = 0, int STG = 1>
 __global__ void __launch_bounds__(512) gemm_bf16_p8_kernel(const GemmDev p) {
     constexpr int BMP = 256, BNP = 256;
     constexpr int NSUB = BKT / 32;                 // 32-deep sub-stages per ring stage
-    constexpr int OPB = BMP * BKT * 2;             // bytes of one operand of a stage
-    constexpr int STAGE = 2 * OPB;
-    constexpr int PPW = OPB / 1024 / 8;            // 1-KB DMA pieces per wave per operand per stage
-    constexpr int LPT = 2 * PPW;                   // DMA instructions per wave per stage
-    constexpr int CH = BKT / 8;                    // 16-B chunks per tile row
-    constexpr int RPP = 64 / CH;                   // tile rows per piece
-    static_assert(BKT == 32 || BKT == 64, "BKT");
+    using Feed = TileFeed<BMP, BNP, BKT, 8>;
+    constexpr int OPB = Feed::ABYTES;              // bytes of one operand of a stage
+    constexpr int STAGE = Feed::STAGE;
+    constexpr int PPW = Feed::PA;                  // 1-KB DMA pieces per wave per operand per stage
+    constexpr int LPT = Feed::LPT;                 // DMA instructions per wave per stage
     static_assert(NST >= 2 && (NST - 2) * LPT < 64, "ring depth vs vmcnt range");
     extern __shared__ __attribute__((aligned(16))) unsigned char ldsp[];
 
@@ -757,60 +494,20 @@ __global__ void __launch_bounds__(512) gemm_bf16_p8_kernel(const GemmDev p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2, wc = wave & 3;
 
-    int g = 0, row0, rows_end, tile_n;
-    {
-        const int L = blockIdx.x, nN = p.n_tiles;
-        const int jx = L >> 3;
-        tile_n = jx % nN;
-        int tmg = (jx / nN) * 8 + (L & 7);
-        if (p.group_off) {
-            bool found = false;
-            for (int gi = 0; gi < p.ngroups; ++gi) {
-                int lo = p.group_off[gi], hi = p.group_off[gi + 1];
-                int nt = (hi - lo + BMP - 1) / BMP;
-                if (tmg < nt) { g = gi; row0 = lo + tmg * BMP; rows_end = hi; found = true; break; }
-                tmg -= nt;
-            }
-            if (!found) return;
-        } else {
-            g = blockIdx.z;
-            row0 = tmg * BMP; rows_end = p.M;
-            if (row0 >= rows_end) return;
-        }
-    }
-    const int n0 = tile_n * BNP;
+    int g, row0, rows_end, n0;
+    if (!gemm_tile_pos<BMP, BNP, TILE_GROUPS>(p, g, row0, rows_end, n0)) return;
     const int KT = p.K / BKT;
     const int total = KT * p.nseg;
 
     const bf16_t* asrc[PPW]; const bf16_t* bsrc[PPW];
-    {
-        const int rr = lane / CH, cs = lane % CH;
-#pragma unroll
-        for (int i = 0; i < PPW; ++i) {
-            const int r = RPP * (wave * PPW + i) + rr;
-            const int c = (BKT == 64) ? (cs ^ ((r >> 1) & 7)) : (cs ^ ((r >> 2) & 3));
-            int slot = row0 + r;
-            if (slot >= rows_end) slot = row0;
-            const int arow = p.a_rows ? p.a_rows[slot] : slot;
-            asrc[i] = p.A + (int64_t)arow * p.lda + g * p.a_koff_group + c * 8;
-            int nrow = n0 + (STG == 2 ? p16_src_row(r) : r);       // STG = 2: P16 column layout (16 consecutive output columns per lane)
-            if (nrow >= p.N) nrow = 0;
-            bsrc[i] = p.B + g * p.b_group_stride + (int64_t)nrow * p.ldb + c * 8;
-        }
-    }
+    gemm_feed_setup<EPI, Feed>(p, g, row0, rows_end, n0, false, STG == 2, wave, lane, asrc, bsrc);      // STG = 2: P16 column layout
     // issue state: stage counter, its ring slot and its (segment, k) position - advanced incrementally (scalar adds / selects, no
     // division in the loop); past the last stage the position stays on the last one: dummy reloads into dead slots
     int iss_t = 0, iss_slot = 0, iss_kt = 0, iss_seg = 0;
     auto issue_pieces = [&](int q0, int q1) {           // DMA pieces [q0, q1) of the current issue stage
-        const int64_t ao = (iss_seg == 1 ? p.a_plane : 0) + iss_kt * BKT;
-        const int64_t bo = (iss_seg == 2 ? p.b_plane : 0) + iss_kt * BKT;
-        unsigned char* sa = ldsp + iss_slot * STAGE;
-#pragma unroll
-        for (int i = 0; i < PPW; ++i) {
-            if (i < q0 || i >= q1) continue;
-            __builtin_amdgcn_global_load_lds((glb_ptr_t)(asrc[i] + ao), (lds_ptr_t)(sa + (wave * PPW + i) * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((glb_ptr_t)(bsrc[i] + bo), (lds_ptr_t)(sa + OPB + (wave * PPW + i) * 1024), 16, 0, 0);
-        }
+        int64_t ao, bo;
+        gemm_seg_offsets<BKT>(p, iss_seg, iss_kt, ao, bo);
+        Feed::issue(asrc, bsrc, wave, ldsp + iss_slot * STAGE, ao, bo, q0, q1);
     };
     auto issue_advance = [&]() {
         iss_t += 1;
@@ -823,13 +520,9 @@ __global__ void __launch_bounds__(512) gemm_bf16_p8_kernel(const GemmDev p) {
     auto issue = [&]() { issue_pieces(0, PPW); issue_advance(); };
 
     f32x16 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    acc_zero(acc);
 
+    // (both schedules read a k-step's two B fragments before its four A fragments: the first MFMA pair waits for three reads, not five)
     const int frow = lane & 31, fk = lane >> 5;
     bf16x8 af[2][4], bf[2][2];
     auto fload = [&](int st, int sub) {
@@ -837,11 +530,8 @@ __global__ void __launch_bounds__(512) gemm_bf16_p8_kernel(const GemmDev p) {
         const unsigned char* Bs = As + OPB;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            const int c = (sub * 2 + ks) * 2 + fk;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) bf[ks][j] = *reinterpret_cast<const bf16x8*>(Bs + lds_off_t<BKT>(wc * 64 + j * 32 + frow, c));
-#pragma unroll
-            for (int i = 0; i < 4; ++i) af[ks][i] = *reinterpret_cast<const bf16x8*>(As + lds_off_t<BKT>(wr * 128 + i * 32 + frow, c));
+            frag_load<2, BKT>(Bs, wc * 64, sub * 2 + ks, fk, frow, bf[ks]);
+            frag_load<4, BKT>(As, wr * 128, sub * 2 + ks, fk, frow, af[ks]);
         }
     };
 
@@ -856,11 +546,8 @@ __global__ void __launch_bounds__(512) gemm_bf16_p8_kernel(const GemmDev p) {
             if constexpr (ABL == 2) { if (st_ >= 0) return; }
             const unsigned char* As = ldsp + st_ * STAGE;
             const unsigned char* Bs = As + OPB;
-            const int c = ks * 2 + fk;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) fb[slot][j] = *reinterpret_cast<const bf16x8*>(Bs + lds_off_t<BKT>(wc * 64 + j * 32 + frow, c));
-#pragma unroll
-            for (int i = 0; i < 4; ++i) fa[slot][i] = *reinterpret_cast<const bf16x8*>(As + lds_off_t<BKT>(wr * 128 + i * 32 + frow, c));
+            frag_load<2, BKT>(Bs, wc * 64, ks, fk, frow, fb[slot]);
+            frag_load<4, BKT>(As, wr * 128, ks, fk, frow, fa[slot]);
         };
         auto mfma2 = [&](int slot, int i) {
             if constexpr (ABL == 3) {
@@ -868,8 +555,7 @@ __global__ void __launch_bounds__(512) gemm_bf16_p8_kernel(const GemmDev p) {
                 acc[i][1][0] += (float)fb[slot][1][2] * (float)fa[slot][i][3];
                 return;
             }
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[slot][0], fa[slot][i], acc[i][0], 0, 0, 0);
-            acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[slot][1], fa[slot][i], acc[i][1], 0, 0, 0);
+            mfma_row(fa[slot][i], fb[slot], acc[i]);
         };
         if constexpr (ABL == 2) {
 #pragma unroll
@@ -956,12 +642,7 @@ __global__ void __launch_bounds__(512) gemm_bf16_p8_kernel(const GemmDev p) {
             // ---- M: 16 MFMAs, the partner wave of this SIMD is in its L phase
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[ks][j], af[ks][i], acc[i][j], 0, 0, 0);
+            for (int ks = 0; ks < 2; ++ks) mfma_step(af[ks], bf[ks], acc);
             __builtin_amdgcn_s_setprio(0);
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_barrier();          // Y
@@ -1176,10 +857,17 @@ enum GemmRoute {
 #ifdef VB_EXPERIMENTS
     GEMM_P8_VARIANT, GEMM_PK, GEMM_PK_F32,      // (the persistent kernel sizes its own grid)
 #endif
+    GEMM_ROUTE_COUNT
 };
 // (bm, bn) of each route, in the enum's order (the experiments forms walk the 8-wave kernel's tile)
 struct GemmTile { int bm, bn; };
-static constexpr GemmTile GEMM_TILE[] = {{BM, BN}, {BM, 192}, {192, 192}, {64, 64}, {128, 64}, {256, 256}, {256, 256}, {256, 256}, {256, 256}};
+static constexpr GemmTile GEMM_TILE[] = {
+    {BM, BN}, {BM, 192}, {192, 192}, {64, 64}, {128, 64}, {256, 256},
+#ifdef VB_EXPERIMENTS
+    {256, 256}, {256, 256}, {256, 256},
+#endif
+};
+static_assert(sizeof(GEMM_TILE) / sizeof(GEMM_TILE[0]) == GEMM_ROUTE_COUNT, "one tile per GemmRoute, in the enum's order");
 // tiles a launch makes with bm x bn tiles: row-range groups may each end in a partial row tile, groups sharing the rows multiply the grid
 static int64_t gemm_tiles(const GemmArgs& a, int bm, int bn) {
     return (int64_t)(gemm_row_groups(a) ? cdiv(a.M, bm) + a.ngroups : cdiv(a.M, bm)) * cdiv(a.N, bn) * gemm_grid_z(a);
@@ -1233,7 +921,7 @@ static GemmRoute gemm_route_experiments(const GemmArgs& a, const GemmDev& d, con
                                            : ((d.T & 15) == 0 && (d.Tpad & 7) == 0 && !d.no_vt16 && ((2 * d.D) & 255) == 0 && a.q.np == a.vt.np);
     if (route == GEMM_P8 && tune.gemm_pk > 0 && gemm_grid_z(a) == 1 && pk_ok && (int64_t)a.M * a.lda < (1ll << 31) &&
         (int64_t)(a.ngroups > 0 ? a.ngroups : 1) * a.b_group_stride + (int64_t)a.N * a.ldb < (1ll << 31)) route = GEMM_PK;
-    // 8-wave 256 x 256 kernel (variant 4): taken when the problem makes enough of its tiles to occupy a good part of the chip - it
+    // 8-wave 256 x 256 kernel (gemm_bf16_p8_kernel): taken when the problem makes enough of its tiles to occupy a good part of the chip - it
     // moves half the bytes per flop through the L2 -> LDS feed, so it wins even at ~55 % of the CUs busy (12032 x 768: 141 tiles);
     // small problems (one 20 s clip: 18 tiles) stay on the 128 x 128 kernel.  VB_GEMM_P8 = 0 off / 1..3 force a ring shape.
     const int p8 = tune.gemm_p8;
@@ -1325,6 +1013,7 @@ static void gemm_launch(GemmRoute route, const GemmDev& d, dim3 grid, hipStream_
         case GEMM_SMALL_64: launch_big<EPI, 1, 1, 3>(d, grid, st); break;
         case GEMM_SMALL_128x64: launch_big<EPI, 2, 1, 3>(d, grid, st); break;
         case GEMM_T128: launch_t<EPI>(d, grid, st); break;
+        case GEMM_ROUTE_COUNT: break;
     }
 }
 

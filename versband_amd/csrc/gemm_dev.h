@@ -1,4 +1,5 @@
-// What the bf16 GEMM kernels share (gemm_bf16.hip, band_ffn.hip, gemm_bf16_pk.hip): device-side descriptor, epilogues, LDS tile addressing.
+// What the bf16 GEMM kernels share (gemm_bf16.hip, band_ffn.hip, gemm_bf16_pk.hip): device-side descriptor, P16 column layout, epilogues.
+// The main loops' shared pieces (tile walk, LDS tile image, DMA feed, MFMA step) are in gemm_tile.h.
 #pragma once
 #include <stdlib.h>
 #include <string.h>
@@ -492,15 +493,6 @@ __device__ __forceinline__ void staged_epilogue(const GemmDev& p, int g, f32x16 
         }
         }
     }
-}
-
-__device__ __forceinline__ int lds_off(int row, int c) {   // byte offset inside a [128][64] bf16 tile
-    return row * 128 + ((c ^ ((row >> 1) & 7)) << 4);
-}
-
-template <int BKT> __device__ __forceinline__ int lds_off_t(int row, int c) {
-    if constexpr (BKT == 64) return row * 128 + ((c ^ ((row >> 1) & 7)) << 4);
-    else return row * 64 + ((c ^ ((row >> 2) & 3)) << 4);
 }
 
 // which epilogues of the 128x128 kernel go through LDS (staged_epilogue) instead of storing from the MFMA layout
