@@ -792,11 +792,12 @@ def test_fp32_dma_conv_upsampled_window_is_bit_identical(lib, monkeypatch, T_in,
                                                    (1, 64, 244, 11, 5, 1.0 / 3, 1.0), (1, 64, 128, 3, 5, 1.0 / 3, 0.0),
                                                    (1, 128, 360, 7, 1, 1.0, 0.0), (2, 128, 120, 11, 3, 1.0 / 3, 1.0),
                                                    (2, 32, 1000, 7, 3, 1.0, 0.0), (1, 32, 360, 5, 1, 1.0, 0.0), (2, 64, 372, 3, 1, 1.0, 0.0),
-                                                   (1, 64, 500, 5, 3, 1.0, 0.0)])
+                                                   (1, 64, 500, 5, 3, 1.0, 0.0), (1, 32, 8, 11, 5, 1.0, 0.0)])
 def test_fp32_respair_equals_two_fp32_convolutions(lib, B, C, T, k, dil, alpha, beta):
     """respair_f32_kernel (vocoder/hifigan/modules/hifigan.py:27-64 ResBlock1 pair, intermediate kept in LDS) against the two launches
     of the fp32 convolution kernel it replaces: same accumulation order, same epilogue arithmetic - equal bit for bit (torch.equal
-    treats the two zeros alike), incl. the accumulate-into-the-MRF-sum form (alpha = 1/3, beta = 1) and both clip ends."""
+    treats the two zeros alike), incl. the accumulate-into-the-MRF-sum form (alpha = 1/3, beta = 1) and both clip ends; T = 8 is a clip
+    shorter than the halo: almost every window quad and intermediate position is padding."""
     x = dev(rnd((B, C, T), "px"))
     w1, w2 = rnd((C, C, k), "pw1", 1.0 / (C * k) ** 0.5), rnd((C, C, k), "pw2", 1.0 / (C * k) ** 0.5)
     b1, b2 = dev(rnd((C,), "pb1")), dev(rnd((C,), "pb2"))
@@ -847,11 +848,14 @@ def test_split_respair_matches_float64(lib, B, C, T, k, dil, alpha, beta):
     assert err < 2e-5, describe("respair split-bf16", out, ref)
 
 
-@pytest.mark.parametrize("C", [32, 64])
-@pytest.mark.parametrize("B,T,k,dil,alpha,beta", [(2, 1000, 3, 1, 1.0, 0.0), (1, 472, 11, 5, 1.0 / 3, 1.0), (2, 1000, 7, 3, 1.0, 0.0), (1, 2048, 11, 1, 1.0, 0.0),
-                                                 (1, 228, 11, 5, 1.0, 0.0), (2, 252, 3, 5, 1.0, 0.0), (1, 60, 7, 1, 1.0 / 3, 1.0), (1, 1504, 11, 3, 1.0, 0.0),
-                                                 (1, 736, 3, 3, 1.0, 0.0), (3, 244, 7, 5, 1.0, 0.0), (1, 120, 11, 5, 1.0, 0.0), (1, 116, 11, 1, 1.0, 0.0)])
-def test_fp32_minimal_filtering_pair_matches_float64_and_the_direct_pair(lib, C, B, T, k, dil, alpha, beta):
+_MF_PAIR_CASES = [(2, 1000, 3, 1, 1.0, 0.0), (1, 472, 11, 5, 1.0 / 3, 1.0), (2, 1000, 7, 3, 1.0, 0.0), (1, 2048, 11, 1, 1.0, 0.0),
+                  (1, 228, 11, 5, 1.0, 0.0), (2, 252, 3, 5, 1.0, 0.0), (1, 60, 7, 1, 1.0 / 3, 1.0), (1, 1504, 11, 3, 1.0, 0.0),
+                  (1, 736, 3, 3, 1.0, 0.0), (3, 244, 7, 5, 1.0, 0.0), (1, 120, 11, 5, 1.0, 0.0), (1, 116, 11, 1, 1.0, 0.0)]
+
+
+# every case at 32 and at 64 channels; a clip shorter than the halo (T = 8: almost all padding) at 32
+@pytest.mark.parametrize("B,T,k,dil,alpha,beta,C", [(*c, C) for C in (32, 64) for c in _MF_PAIR_CASES] + [(1, 8, 11, 5, 1.0, 0.0, 32)])
+def test_fp32_minimal_filtering_pair_matches_float64_and_the_direct_pair(lib, B, T, k, dil, alpha, beta, C):
     """respair_f32w_kernel (round 6: the 32-channel ResBlock1 pair with F(2,3) minimal filtering in both convolutions, intermediate in LDS)
     against float64 to fp32 roundoff and against the direct fused pair (< 4e-6 of the output's max); workgroup runs of 256 / 240 intermediate
     positions (d = 1 / 3, 5), both clip ends, T smaller than one run, the accumulate-into-the-MRF-sum form.  It is NOT bit-identical to two
@@ -887,6 +891,31 @@ def test_fp32_minimal_filtering_pair_matches_float64_and_the_direct_pair(lib, C,
                                    L.stream_ptr()), "respair_f32")
         sync()
         assert float((fused - direct).abs().max()) < 4e-6 * float(ref64.abs().max())
+
+
+@pytest.mark.parametrize("B,C,T,k,dil,alpha,beta", [(2, 32, 252, 3, 1, 1.0, 0.0), (1, 64, 244, 11, 5, 1.0 / 3, 1.0), (1, 128, 120, 7, 1, 1.0, 0.0)])
+def test_fp32_pair_staged_and_direct_epilogues_are_bit_identical(lib, monkeypatch, B, C, T, k, dil, alpha, beta):
+    """respair_f32_kernel's two epilogue forms (pair_epilogue, respair_dev.h): the staged 16-byte one (default) and the direct 4-byte one
+    (VB_CONV_DIRECT_EPI=1) do the same arithmetic per element - the same bits.  Runs of 124 outputs whose third workgroup stores one quad;
+    the accumulate form; CH = 4 with less than one run."""
+    x = dev(rnd((B, C, T), "ex"))
+    p1, p2 = dev(pack.pack_conv(rnd((C, C, k), "ew1", 1.0 / (C * k) ** 0.5))), dev(pack.pack_conv(rnd((C, C, k), "ew2", 1.0 / (C * k) ** 0.5)))
+    b1, b2 = dev(rnd((C,), "eb1")), dev(rnd((C,), "eb2"))
+    acc0 = dev(rnd((B, C, T), "eacc"))
+
+    def run():
+        out = acc0.clone()
+        L.check(lib.vb_respair_f32(L.ptr(x), L.ptr(p1), L.ptr(b1), L.ptr(p2), L.ptr(b2), B, C, T, k, dil, 0.1, alpha, beta, L.ptr(out),
+                                   L.stream_ptr()), "respair_f32")
+        sync()
+        return out
+    staged = run()
+    monkeypatch.setenv("VB_CONV_DIRECT_EPI", "1")
+    lib.vb_tune_reload()
+    direct = run()
+    monkeypatch.delenv("VB_CONV_DIRECT_EPI")
+    lib.vb_tune_reload()
+    assert torch.isfinite(staged).all() and torch.equal(staged, direct), f"staged vs direct epilogue differ by {float((staged - direct).abs().max()):.3e}"
 
 
 @pytest.mark.parametrize("C,k,dil", [(32, 7, 3), (32, 11, 5), (64, 3, 1), (64, 7, 3), (64, 11, 5)])

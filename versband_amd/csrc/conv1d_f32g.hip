@@ -8,6 +8,7 @@
 #include "dma_ring.h"
 #include "lds_asm.h"
 #include "ring_window.h"
+#include "ring_step.h"
 
 // ---------------------------------------------------------------------------------------------------------
 // DMA-fed exact-fp32 kernel (round 4).  conv1d_f32_kernel (conv1d_f32.hip) multiplies at 80-93 % of the f32 MFMA rate PER TAP (measured at 8
@@ -20,7 +21,8 @@
 //     and zero padding by the lanes that own the quads (ring_window.h: the feed all four fp32 ring kernels share); GroupNorm + swish inputs
 //     are pre-activated by gn_apply_kernel (the builder emits it in fp32 mode: the old kernel redid norm + swish + expf once per
 //     output-channel tile, 12x on the 1536-channel layers);
-//   * weight tiles [16 ci][CO_TILE] stream through a 4-stage ring, three tiles in flight, counted vmcnt + one raw s_barrier per tap;
+//   * weight tiles [16 ci][CO_TILE] stream through a 4-stage ring, three tiles in flight, counted vmcnt + one raw s_barrier per tap; a
+//     tap's fragments go through the pipeline all four fp32 ring kernels share (ring_step.h);
 //   * the [b][co][t] result leaves through the staged 16-byte epilogue of the split-bf16 kernel (conv_epilogue_staged);
 //   * workgroups are numbered so that one XCD keeps a (time tile, clip) unit for ALL its output-channel tiles: the window is fetched
 //     into one L2, the (small) weights into all of them.
@@ -29,18 +31,24 @@
 // NSW = weight-tile ring stages (4: three tiles in flight; 3: two - 49 KB of LDS with the 96-sample tile, three workgroups per CU)
 // ABL (experiments build, timing only - results are wrong): 1 = no fragment reads, 2 = no DMA, 4 = no barrier, 8 = no MFMAs, 16 = no epilogue
 // NT = taps per phase as a template parameter (0: runtime loop)
+// the kernel's geometry, read by the kernel and by its launcher
+template <int WM, int WN, int TM, int TN, bool UPS, int NSW>
+struct F32gGeo {
+    static constexpr int CO_TILE = WM * TM * 32, T_TILE = WN * TN * 32;
+    static constexpr int XP = (T_TILE + 64 + 63) / 64 * 64;      // window pitch (positions): tile + halo (<= 60) + alignment slack (<= 3)
+    static constexpr int NP = XP / 64;
+    static constexpr int XST = CONV_CK * XP, WT = CONV_CK * CO_TILE;       // floats per window stage / weight tile
+    static constexpr int NWI = CO_TILE / 16;                     // 1-KB DMA pieces per weight tile
+    static constexpr int WPW = NWI >= 4 ? NWI / 4 : 1;           // ... per wave (narrow tiles: the waves repeat each other's pieces)
+    static constexpr int XPW = UPS ? 4 * NP : NP;                // window pieces per wave and chunk (16-B lanes: 4 rows of 64 positions per piece)
+    static constexpr int BYTES = (2 * XST + NSW * WT) * (int)sizeof(float);      // two window stages, NSW weight stages
+    static_assert(NSW == 3 || NSW == 4, "wait_tile counts at most two tiles ahead");
+    static_assert(BYTES >= 4 * 32 * CE_PITCH * sizeof(float), "staging patches must fit in the rings (contiguous)");
+};
 template <int WM, int WN, int TM, int TN, bool UPS, int NSW, int ABL = 0, int NT = 0>
 __global__ void __launch_bounds__(256, 3) conv1d_f32g_kernel(const ConvDev p) {      // three waves per SIMD: <= 168 VGPRs (the unrolled-tap instances of the 128 x 128 tile came out at 171)
-    constexpr int CO_TILE = WM * TM * 32;
-    constexpr int T_TILE = WN * TN * 32;
-    constexpr int XP = (T_TILE + 64 + 63) / 64 * 64;      // window pitch (positions): tile + halo (<= 60) + alignment slack (<= 3)
-    constexpr int NP = XP / 64;
-    constexpr int XST = CONV_CK * XP, WT = CONV_CK * CO_TILE;       // floats per window stage / weight tile
-    constexpr int NWI = CO_TILE / 16;                     // 1-KB DMA pieces per weight tile
-    constexpr int WPW = NWI >= 4 ? NWI / 4 : 1;           // ... per wave (narrow tiles: the waves repeat each other's pieces)
-    constexpr int XPW = UPS ? 4 * NP : NP;                // window pieces per wave and chunk (16-B lanes: 4 rows of 64 positions per piece)
-    static_assert(NSW == 3 || NSW == 4, "wait_tile counts at most two tiles ahead");
-    static_assert((2 * XST + NSW * WT) * sizeof(float) >= 4 * 32 * CE_PITCH * sizeof(float), "staging patches must fit in the rings (contiguous)");
+    using G = F32gGeo<WM, WN, TM, TN, UPS, NSW>;
+    constexpr int CO_TILE = G::CO_TILE, T_TILE = G::T_TILE, XP = G::XP, NP = G::NP, XST = G::XST, WT = G::WT, NWI = G::NWI, WPW = G::WPW, XPW = G::XPW;
     extern __shared__ __attribute__((aligned(16))) float g_lds[];
     float* lx = g_lds;
     float* lw = g_lds + 2 * XST;
@@ -130,64 +138,39 @@ __global__ void __launch_bounds__(256, 3) conv1d_f32g_kernel(const ConvDev p) { 
     for (int i = 0; i < TM; ++i) da[i] = 0.f;
 #pragma unroll
     for (int jn = 0; jn < TN; ++jn) dbv[jn] = 0.f;
-    // one ring step's multiplications: fragments are requested two channel pairs ahead of their MFMAs from inline asm with exact lgkmcnt
-    // waits (lds_asm.h: with LDS-DMA in flight hipcc only ever waits lgkmcnt(0), which exposed one LDS round trip per two pairs); three
-    // register sets so that a request never lands in registers an MFMA in flight still reads
+    // one ring step's multiplications: the fragment pipeline of ring_step.h, TM A fragments and TN B reads per channel pair
     auto multiply = [&](const unsigned xaddr, const unsigned waddr) {
-        float a[3][TM], bb[3][TN];
-        if constexpr (ABL & 1) {
+        auto mfma = [&](const float (&a)[TM], const float (&bb)[TN]) {
 #pragma unroll
-            for (int s3 = 0; s3 < 3; ++s3) {
+            for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int i = 0; i < TM; ++i) a[s3][i] = (float)lane;
-#pragma unroll
-                for (int jn = 0; jn < TN; ++jn) bb[s3][jn] = (float)(lane + s3);
-            }
-        }
-        auto fload = [&](auto kc) {
-            constexpr int KK = decltype(kc)::value, S = KK % 3;
-            if constexpr (ABL & 1) return;
-            static_for<0, TM>([&](auto ic) { constexpr int I = decltype(ic)::value; lds_rd32<(2 * KK * CO_TILE + I * 32) * 4>(a[S][I], waddr); });
-            static_for<0, TN>([&](auto jc) { constexpr int J = decltype(jc)::value; lds_rd32<(2 * KK * XP + J * 32) * 4>(bb[S][J], xaddr); });
+                for (int jn = 0; jn < TN; ++jn) {
+                    if constexpr (ABL & 8) acc[i][jn][0] += a[i] * bb[jn];
+                    else acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], bb[jn], acc[i][jn], 0, 0, 0);
+                }
         };
-        fload(std::integral_constant<int, 0>{});
-        fload(std::integral_constant<int, 1>{});
-        __builtin_amdgcn_sched_barrier(0);
-        // the LAST channel pair of the previous step was held back (operands in registers): its MFMAs are queued here, behind the barrier,
-        // the DMA issue and the first two fragment requests of this step - 256 matrix-pipe cycles that cover the first LDS round trip
-        // (same box: 810 -> 798 us on the 128 x 128 tile; at three workgroups per CU most of it was hidden already).
-        // Same accumulation order (they still precede this step's first pair); the first step queues zeros.
+        ring_step_pairs<CONV_CK / 2, TM, TN, (ABL & 1) != 0>(
+            [](auto) { return std::integral_constant<int, TN>{}; },
+            [&](auto kc, auto ic, float& v) { lds_rd32<(2 * decltype(kc)::value * CO_TILE + decltype(ic)::value * 32) * 4>(v, waddr); },
+            [&](auto kc, auto jc, float& v) { lds_rd32<(2 * decltype(kc)::value * XP + decltype(jc)::value * 32) * 4>(v, xaddr); },
+            [&]() {
+                // the LAST channel pair of the previous step was held back (operands in registers): its MFMAs are queued here, behind the
+                // barrier, the DMA issue and the first two fragment requests of this step - 256 matrix-pipe cycles that cover the first LDS
+                // round trip (same box: 810 -> 798 us on the 128 x 128 tile; at three workgroups per CU most of it was hidden already).
+                // Same accumulation order (they still precede this step's first pair); the first step queues zeros.
+                __builtin_amdgcn_sched_barrier(0);
+                mfma(da, dbv);
+                __builtin_amdgcn_sched_barrier(0);
+            },
+            [&](auto kc, const float (&a)[TM], const float (&bb)[TN]) {
+                if constexpr (decltype(kc)::value + 1 < CONV_CK / 2) mfma(a, bb);
+                else {
 #pragma unroll
-        for (int i = 0; i < TM; ++i)
+                    for (int i = 0; i < TM; ++i) da[i] = a[i];
 #pragma unroll
-            for (int jn = 0; jn < TN; ++jn) {
-                if constexpr (ABL & 8) acc[i][jn][0] += da[i] * dbv[jn];
-                else acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(da[i], dbv[jn], acc[i][jn], 0, 0, 0);
-            }
-        __builtin_amdgcn_sched_barrier(0);
-        static_for<0, CONV_CK / 2>([&](auto kc) {
-            constexpr int KK = decltype(kc)::value, S = KK % 3;
-            if constexpr (KK + 1 < CONV_CK / 2) LDS_WAIT(TM + TN); else LDS_WAIT(0);
-#pragma unroll
-            for (int i = 0; i < TM; ++i) lds_pin(a[S][i]);
-#pragma unroll
-            for (int jn = 0; jn < TN; ++jn) lds_pin(bb[S][jn]);
-            if constexpr (KK + 2 < CONV_CK / 2) fload(std::integral_constant<int, KK + 2>{});
-            if constexpr (KK + 1 < CONV_CK / 2) {
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int jn = 0; jn < TN; ++jn) {
-                        if constexpr (ABL & 8) acc[i][jn][0] += a[S][i] * bb[S][jn];
-                        else acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[S][i], bb[S][jn], acc[i][jn], 0, 0, 0);
-                    }
-            } else {
-#pragma unroll
-                for (int i = 0; i < TM; ++i) da[i] = a[S][i];
-#pragma unroll
-                for (int jn = 0; jn < TN; ++jn) dbv[jn] = bb[S][jn];
-            }
-        });
+                    for (int jn = 0; jn < TN; ++jn) dbv[jn] = bb[jn];
+                }
+            });
     };
     if constexpr (NT > 0) {
         // ---- the tap count is a template parameter (3 / 7 / 11: the generator's ResBlock layers; the launcher checks p.ntaps == NT): the
@@ -283,8 +266,8 @@ __global__ void __launch_bounds__(256, 3) conv1d_f32g_kernel(const ConvDev p) { 
 
 template <int WM, int WN, int TM, int TN, bool UPS, int NSW = 4, int ABL = 0, int NT = 0>
 static void launch_cfg_g(ConvDev& d, int n_count, int B, hipStream_t st) {
-    constexpr int CO_TILE = WM * TM * 32, T_TILE = WN * TN * 32, XP = (T_TILE + 64 + 63) / 64 * 64;
-    constexpr int BYTES = (2 * CONV_CK * XP + NSW * CONV_CK * CO_TILE) * (int)sizeof(float);
+    using G = F32gGeo<WM, WN, TM, TN, UPS, NSW>;
+    constexpr int CO_TILE = G::CO_TILE, T_TILE = G::T_TILE, BYTES = G::BYTES;
     const int grid = conv_xcd_grid(d, n_count, T_TILE, CO_TILE, B);
     static OnceFlags once;
     vb_set_max_lds_once(once, (const void*)conv1d_f32g_kernel<WM, WN, TM, TN, UPS, NSW, ABL, NT>, BYTES);

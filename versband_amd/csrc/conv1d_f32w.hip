@@ -27,7 +27,7 @@
 // 2 d q + r + d of the wave's 2 * VW positions, VW = (32 / d) d (32 for d = 1, 30 for d = 3 / 5: two idle columns).  Tile = 128 co x 4 VW positions,
 // 4 waves as 2 x 2, wave = 64 co x 2 VW positions, accumulators 4 m's x 2 co tiles x 16 = 128 VGPRs (two workgroups per CU).
 // Ring, counted vmcnt, fragment pipeline and XCD numbering: conv1d_f32g_kernel's unrolled-tap form with NT = pseudo-taps; the window feed is
-// ring_window.h's, as there.
+// ring_window.h's, the fragment pipeline ring_step.h's, as there.
 #include <stdlib.h>
 #include <type_traits>
 
@@ -35,6 +35,7 @@
 #include "dma_ring.h"
 #include "lds_asm.h"
 #include "ring_window.h"
+#include "ring_step.h"
 #include "mf_taps.h"
 
 #define MF_PITCH 68          // floats per staged channel row (64 positions + 4)
@@ -49,19 +50,27 @@
 #define MFMA_ACC(c, a, b) asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b))
 #endif
 
-// WN = waves along time (2: tile 128 co x 4 VW positions; 4: 64 co x 8 VW positions - the 64-channel layers)
-template <int K, int OCC, int WN>
-__global__ void __launch_bounds__(256, OCC) conv1d_f32w_kernel(const ConvDev p) {
+// The kernel's geometry, read by the kernel and by its launcher.  WN = waves along time (2: tile 128 co x 4 VW positions; 4: 64 co x 8 VW
+// positions - the 64-channel layers)
+template <int WN>
+struct F32wGeo {
     // ring depth = conv1d_f32g_kernel's: two window stages, three weight stages (49 KB; 60 KB on the 64-channel tile).  (Round 6, measured and not
     // adopted: five weight stages in the two-per-CU build - vmcnt retires in order, so every load's lead, the window's too, is NSW - 1 ring steps -
     // no faster on the layer shapes and 1.5 % slower to equal end to end: 1215 / 1193 against 1199 / 1205 mel-s/s, profiles/r06_mf_ring_depth.txt.)
-    constexpr int TM = 2, WM = 4 / WN, NXS = 2, NSW = 3;
-    constexpr int P = mf_ntaps(K);
-    constexpr int CO_TILE = WM * TM * 32, XP = WN * 64 + 64, NP = XP / 64;
-    constexpr int XST = CONV_CK * XP, WT = CONV_CK * CO_TILE;
-    constexpr int NWI = CO_TILE / 16, WPW = NWI / 4, XPW = NP;
-    static_assert(P >= NSW - 1, "a step issues the tile NSW - 1 ahead: it lies in this chunk or the next one");
+    static constexpr int TM = 2, WM = 4 / WN, NXS = 2, NSW = 3;
+    static constexpr int CO_TILE = WM * TM * 32, XP = WN * 64 + 64, NP = XP / 64;
+    static constexpr int XST = CONV_CK * XP, WT = CONV_CK * CO_TILE;
+    static constexpr int NWI = CO_TILE / 16, WPW = NWI / 4, XPW = NP;
+    static constexpr int BYTES = (NXS * XST + NSW * WT) * (int)sizeof(float);
     static_assert((NXS * XST + NSW * WT) >= 4 * 32 * MF_PITCH, "the staging patches must fit in the rings");
+};
+template <int K, int OCC, int WN>
+__global__ void __launch_bounds__(256, OCC) conv1d_f32w_kernel(const ConvDev p) {
+    using G = F32wGeo<WN>;
+    constexpr int TM = G::TM, WM = G::WM, NXS = G::NXS, NSW = G::NSW, CO_TILE = G::CO_TILE, XP = G::XP, NP = G::NP, XST = G::XST, WT = G::WT;
+    constexpr int WPW = G::WPW, XPW = G::XPW;
+    constexpr int P = mf_ntaps(K);
+    static_assert(P >= NSW - 1, "a step issues the tile NSW - 1 ahead: it lies in this chunk or the next one");
     extern __shared__ __attribute__((aligned(16))) float w_lds[];
     float* lx = w_lds;
     float* lw = w_lds + NXS * XST;
@@ -178,41 +187,28 @@ __global__ void __launch_bounds__(256, OCC) conv1d_f32w_kernel(const ConvDev p) 
                 const unsigned waddr = wa0 + slot * (WT * 4);
                 const unsigned xaddr_a = xa_ch + TP.oa * dil4;
                 const unsigned xaddr_b = xa_ch + TP.ob * dil4;
-                constexpr int NR = TM + (TP.op == 2 ? 1 : 2);
-                float a[3][TM], xa[3], xb[3];
-                auto fload = [&](auto kc) {
-                    constexpr int KK = decltype(kc)::value, S = KK % 3;
-                    static_for<0, TM>([&](auto ic) { constexpr int I = decltype(ic)::value; lds_rd32<(2 * KK * CO_TILE + I * 32) * 4>(a[S][I], waddr); });
-                    lds_rd32<(2 * KK * XP) * 4>(xa[S], xaddr_a);
-                    if constexpr (TP.op != 2) lds_rd32<(2 * KK * XP) * 4>(xb[S], xaddr_b);
-                };
-                fload(std::integral_constant<int, 0>{});
-                fload(std::integral_constant<int, 1>{});
-                __builtin_amdgcn_sched_barrier(0);
+                constexpr int NB = mf_reads(TP);
+                ring_step_pairs<CONV_CK / 2, TM, 2>(
+                    [](auto) { return std::integral_constant<int, NB>{}; },
+                    [&](auto kc, auto ic, float& v) { lds_rd32<(2 * decltype(kc)::value * CO_TILE + decltype(ic)::value * 32) * 4>(v, waddr); },
+                    [&](auto kc, auto jc, float& v) { lds_rd32<(2 * decltype(kc)::value * XP) * 4>(v, decltype(jc)::value ? xaddr_b : xaddr_a); },
+                    [&]() {             // the previous step's held-back pair (conv1d_f32g_kernel)
+                        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int i = 0; i < TM; ++i) MFMA_ACC(acc[PACC][i], da[i], dbv);
-                __builtin_amdgcn_sched_barrier(0);
-                static_for<0, CONV_CK / 2>([&](auto kc) {
-                    constexpr int KK = decltype(kc)::value, S = KK % 3;
-                    if constexpr (KK + 1 < CONV_CK / 2) LDS_WAIT(NR); else LDS_WAIT(0);
+                        for (int i = 0; i < TM; ++i) MFMA_ACC(acc[PACC][i], da[i], dbv);
+                        __builtin_amdgcn_sched_barrier(0);
+                    },
+                    [&](auto kc, const float (&a)[TM], const float (&x)[2]) {
+                        const float bv = mf_operand<TP.op>(x);
+                        if constexpr (decltype(kc)::value + 1 < CONV_CK / 2) {
 #pragma unroll
-                    for (int i = 0; i < TM; ++i) lds_pin(a[S][i]);
-                    lds_pin(xa[S]);
-                    if constexpr (TP.op != 2) lds_pin(xb[S]);
-                    if constexpr (KK + 2 < CONV_CK / 2) fload(std::integral_constant<int, KK + 2>{});
-                    float bv;
-                    if constexpr (TP.op == 0) bv = xa[S] - xb[S];
-                    else if constexpr (TP.op == 1) bv = xa[S] + xb[S];
-                    else bv = xa[S];
-                    if constexpr (KK + 1 < CONV_CK / 2) {
+                            for (int i = 0; i < TM; ++i) MFMA_ACC(acc[TP.acc][i], a[i], bv);
+                        } else {
 #pragma unroll
-                        for (int i = 0; i < TM; ++i) MFMA_ACC(acc[TP.acc][i], a[S][i], bv);
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < TM; ++i) da[i] = a[S][i];
-                        dbv = bv;
-                    }
-                });
+                            for (int i = 0; i < TM; ++i) da[i] = a[i];
+                            dbv = bv;
+                        }
+                    });
             }
             if (++slot == NSW) slot = 0;
             if (++nslot == NSW) nslot = 0;
@@ -298,9 +294,7 @@ __global__ void __launch_bounds__(256, OCC) conv1d_f32w_kernel(const ConvDev p) 
 
 template <int K, int OCC, int WN>
 static void launch_w(ConvDev& d, int B, hipStream_t st) {
-    constexpr int CO_TILE = (4 / WN) * 64, XP = WN * 64 + 64;
-    constexpr int NXS = 2, NSW = 3;      // (the kernel's ring depths)
-    constexpr int BYTES = (NXS * CONV_CK * XP + NSW * CONV_CK * CO_TILE) * (int)sizeof(float);
+    constexpr int CO_TILE = F32wGeo<WN>::CO_TILE, BYTES = F32wGeo<WN>::BYTES;
     const int T_TILE = WN * 2 * ((32 / d.dil) * d.dil);
     const int grid = conv_xcd_grid(d, d.T_out, T_TILE, CO_TILE, B);      // (phases == 1)
 #ifdef VB_EXPERIMENTS

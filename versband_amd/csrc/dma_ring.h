@@ -1,6 +1,6 @@
 // What the kernels that DMA their tiles into LDS rings (global_load_lds + counted vmcnt) share: the compile-time loop, the counted waits,
 // the pointer types of the DMA builtin and the fused pairs' outputs per workgroup and output element.  No inline assembly (that is lds_asm.h); the fp32 conv
-// kernels' window feed, which needs both, is ring_window.h.
+// kernels' window feed and fragment pipeline, which need both, are ring_window.h and ring_step.h.
 #pragma once
 #include <type_traits>
 

@@ -18,4 +18,11 @@ __host__ __device__ constexpr MfTap mf_tap(int K, int j) {
     return r == 0 ? MfTap{0, 0, ob, ob + 1} : (r == 1 ? MfTap{1, 2, ob + 1, ob + 1} : MfTap{3, 0, ob + 2, ob + 1});
 }
 __host__ __device__ constexpr int mf_ntaps(int K) { return 4 * (K / 3) + (K % 3 == 1 ? 2 : (K % 3 == 2 ? 3 : 0)); }
+// the operand of a pseudo-tap from its window reads x = {x[oa], x[ob]} (op 2 reads x[oa] only)
+__host__ __device__ constexpr int mf_reads(MfTap t) { return t.op == 2 ? 1 : 2; }
+template <int OP> __device__ __forceinline__ float mf_operand(const float (&x)[2]) {
+    if constexpr (OP == 0) return x[0] - x[1];
+    else if constexpr (OP == 1) return x[0] + x[1];
+    else return x[0];
+}
 

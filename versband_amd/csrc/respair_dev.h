@@ -1,5 +1,6 @@
-// What the split-bf16 and bf16 ResBlock1 pairs (respair_x3.hip, respair_bf16.hip) share: descriptor, run geometry (outputs per workgroup:
-// pair_run_outputs, dma_ring.h, as the fp32 pairs take it), the launcher's checks, and their epilogue, once:
+// What the fused ResBlock1 pairs share.  All four (respair_x3.hip, respair_bf16.hip, respair_f32.hip, respair_f32w.hip): the run geometry
+// (pair_run) and the host-side fill (pair_fill_common); the bf16 pairs their descriptor and checks, the fp32 pairs theirs; all but the
+// minimal-filtering pair (whose lanes own two outputs) the epilogue, once:
 //   out = pair_out_value(alpha, beta, acc, b2[co], x, out)   for the workgroup's outputs n0 + [0, TT) of all 32*CH channels.
 // The MFMA accumulator gives a lane ONE output sample and 16 channels; moved like that every residual / accumulate-into load and every store
 // is a 4-byte lane access (the direct form, any T).  With 16-byte aligned rows (staged: T % 4 == 0, aligned tensors) each wave passes its
@@ -23,16 +24,31 @@ struct PairDev {
     float slope, alpha, beta;
     int staged;               // 16-B (staged) epilogue: T % 4 == 0 and 16-B aligned tensors
 };
-// One workgroup's run: outputs n0 + [0, TT), intermediate positions m0 + [0, PAIR_T), window samples x0 + [0, xw_used)
-struct PairRun { int h1, h2, TT, n0, m0, x0, xw_used; };
-__device__ __forceinline__ PairRun pair_run(const PairDev& p) {
+// the fp32 pairs (respair_f32.hip; respair_f32w.hip, whose kernel size is a template parameter and whose epilogue is always the staged one)
+struct PairF32Dev {
+    const float* x; float* out; int64_t bstride; int T;
+    int k, dil;
+    const float* w1; const float* w2;      // [k][C ci][C co] fp32 each; respair_f32w: minimal-filtering pseudo-taps [P][C ci][C co] (pack.py:pack_conv_mf)
+    const float* b1; const float* b2;
+    float slope, alpha, beta;
+    int staged;
+#ifdef VB_EXPERIMENTS
+    int x_nt;          // window DMA with the non-temporal policy (VB_CONV_XNT, see conv1d_f32g.hip)
+#endif
+};
+// One workgroup's run of `run` intermediate positions (PAIR_T; 128 in respair_f32, M in respair_f32w): outputs n0 + [0, TT), intermediate
+// positions m0 + [0, run), window samples x0 + [0, xw_used); the DMA-fed windows start on the quad start_al = x0 - aoff
+struct PairRun { int h1, h2, TT, n0, m0, x0, xw_used, start_al, aoff; };
+__device__ __forceinline__ PairRun pair_run(int run, int k, int dil) {
     PairRun r;
-    r.h2 = (p.k - 1) / 2; r.h1 = (p.k - 1) * p.dil / 2;
-    r.TT = pair_run_outputs(PAIR_T, p.k);
+    r.h2 = (k - 1) / 2; r.h1 = (k - 1) * dil / 2;
+    r.TT = pair_run_outputs(run, k);
     r.n0 = blockIdx.x * r.TT;
     r.m0 = r.n0 - r.h2;
     r.x0 = r.m0 - r.h1;
-    r.xw_used = PAIR_T + (p.k - 1) * p.dil;
+    r.xw_used = run + (k - 1) * dil;
+    r.start_al = r.x0 & ~3;
+    r.aoff = r.x0 - r.start_al;
     return r;
 }
 // b1, LeakyReLU, zero outside [0, T) (conv2 pads the ACTIVATED intermediate) and the operand rounding over the conv1 accumulators of channel
@@ -54,21 +70,30 @@ __device__ __forceinline__ void pair_store_intermediate(const f32x16& acc, const
     }
 }
 
-// ---- host side: the argument checks of launch_respair / launch_respair_bf16 (`who` prefixes the messages), the descriptor, the grid and the
-// profiler's flops (two convolutions' worth; the recomputed halo of conv1 is not counted) and activation bytes
-struct PairLaunch { PairDev d; dim3 grid; double flops, act_bytes; };
+// ---- host side, after a launcher's own argument checks (`who` prefixes the message): the x / out check, the descriptor, the grid for runs of
+// `run` intermediate positions and the profiler's flops (two convolutions of `taps` multiplications per output; the recomputed halo of conv1
+// is not counted) and activation bytes
+template <class Dev> struct PairLaunchT { Dev d; dim3 grid; double flops, act_bytes; };
+template <class Args, class Dev>
+static inline int pair_fill_common(const Args& a, const char* who, int run, double taps, PairLaunchT<Dev>& L) {
+    if (a.x == a.out) VB_FAIL(VB_E_INVALID, "%s: x and out must be distinct buffers (neighbouring workgroups re-read the halo)", who);
+    Dev& d = L.d;
+    d.x = a.x; d.out = a.out; d.bstride = (int64_t)a.C * a.T; d.T = a.T; d.k = a.k; d.dil = a.dil;
+    d.w1 = a.w1; d.w2 = a.w2; d.b1 = a.b1; d.b2 = a.b2;
+    d.slope = a.slope; d.alpha = a.alpha; d.beta = a.beta;
+    d.staged = (a.T % 4 == 0 && aligned16(a.x) && aligned16(a.out) && !vb_tune().conv_direct_epi) ? 1 : 0;
+    L.grid = dim3(cdiv(a.T, pair_run_outputs(run, a.k)), 1, a.B);
+    L.flops = 2.0 * 2.0 * a.B * (double)a.C * a.C * taps * (double)a.T;
+    L.act_bytes = 4.0 * a.B * (double)a.C * a.T * (2.0 + (a.beta != 0.f ? 1.0 : 0.0));
+    return VB_OK;
+}
+// the bf16 pairs: the argument checks of launch_respair / launch_respair_bf16
+using PairLaunch = PairLaunchT<PairDev>;
 static inline int pair_fill(const RespairArgs& a, const char* who, PairLaunch& L) {
     if (a.C != 32 && a.C != 64) VB_FAIL(VB_E_INVALID, "%s: C=%d (32 or 64)", who, a.C);
     if (a.k < 1 || (a.k & 1) == 0 || (a.k - 1) * a.dil > CONV_HALO || a.k > 33) VB_FAIL(VB_E_INVALID, "%s: k=%d dil=%d", who, a.k, a.dil);
-    if (a.x == a.out) VB_FAIL(VB_E_INVALID, "%s: x and out must be distinct buffers (neighbouring workgroups re-read the halo)", who);
-    PairDev& d = L.d;
-    d.x = a.x; d.out = a.out; d.bstride = (int64_t)a.C * a.T; d.T = a.T; d.k = a.k; d.dil = a.dil;
-    d.w1 = a.w1; d.w2 = a.w2; d.w_plane = (int64_t)a.k * a.C * a.C; d.b1 = a.b1; d.b2 = a.b2;
-    d.slope = a.slope; d.alpha = a.alpha; d.beta = a.beta;
-    d.staged = (a.T % 4 == 0 && aligned16(a.x) && aligned16(a.out) && !vb_tune().conv_direct_epi) ? 1 : 0;
-    L.grid = dim3(cdiv(a.T, pair_run_outputs(PAIR_T, a.k)), 1, a.B);
-    L.flops = 2.0 * 2.0 * a.B * (double)a.C * a.C * a.k * (double)a.T;
-    L.act_bytes = 4.0 * a.B * (double)a.C * a.T * (2.0 + (a.beta != 0.f ? 1.0 : 0.0));
+    VB_TRY(pair_fill_common(a, who, PAIR_T, a.k, L));
+    L.d.w_plane = (int64_t)a.k * a.C * a.C;
     return VB_OK;
 }
 

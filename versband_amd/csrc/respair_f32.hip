@@ -12,37 +12,39 @@
 //   * conv1: the raw window of x (128 + (k-1) d positions) arrives by DMA (global_load_lds, 16-B lanes) one 16-channel chunk ahead, the
 //     weight tiles [TPS taps][16 ci][C co] of BOTH convolutions stream through one 3- or 4-stage ring (counted vmcnt, one raw s_barrier per
 //     ring step = TPS taps of a chunk: 32 / 16 MFMAs per wave at 32 / 64 channels); fragments by inline-asm ds_read_b32 two channel pairs ahead with exact lgkmcnt
-//     (lds_asm.h); LeakyReLU is applied in place once per chunk by the lanes that DMA'd it (ring_window.h); a wave owns 32 intermediate positions x all channels;
+//     (ring_step.h); LeakyReLU is applied in place once per chunk by the lanes that DMA'd it (ring_window.h); a wave owns 32 intermediate positions x all channels;
 //   * + b1, LeakyReLU, zero outside [0,T) (conv2 pads the ACTIVATED intermediate) -> LDS h[c][m] (aliases the window ring);
-//   * conv2 over h, + b2 + residual x, alpha / beta accumulation into the MRF sum through the staged 16-byte epilogue.
+//   * conv2 over h, + b2 + residual x, alpha / beta accumulation into the MRF sum through the staged 16-byte epilogue (pair_epilogue, respair_dev.h).
 // Same chunk -> tap -> channel-pair accumulation order and the same epilogue arithmetic as conv1d_f32_kernel / conv1d_f32g_kernel:
 // the fused pair equals the two unfused fp32 launches bit for bit (up to the sign of a zero intermediate) - the test compares them.
 #include <stdlib.h>
 #include <type_traits>
 
-#include "kernels.h"
-#include "dma_ring.h"
+#include "respair_dev.h"
 #include "lds_asm.h"
 #include "ring_window.h"
+#include "ring_step.h"
 
 #define PF_T 128            // intermediate positions per workgroup (4 waves x 32)
 #define PF_XP 192           // window pitch: 128 + halo (<= 60) + alignment slack (<= 3)
 #define PF_HP 144           // intermediate pitch: 128 + (k-1 <= 16)
 #define PF_GK 16
-#define PF_EP 36
 
-struct PairF32Dev {
-    const float* x; float* out; int64_t bstride; int T;
-    int k, dil;
-    const float* w1; const float* w2;      // [k][C ci][C co] fp32 each
-    const float* b1; const float* b2;
-    float slope, alpha, beta;
-    int staged;
-#ifdef VB_EXPERIMENTS
-    int x_nt;          // window DMA with the non-temporal policy (VB_CONV_XNT, see conv1d_f32g.hip)
-#endif
+// the kernel's geometry, read by the kernel and by its launcher
+template <int CH, int TPS, int NSW>
+struct PairF32Geo {
+    static constexpr int C = 32 * CH;
+    static constexpr int XST = PF_GK * PF_XP;                 // floats per window stage
+    static constexpr int WT = TPS * PF_GK * C;                // floats per weight tile: [tap][16 ci][C co], contiguous per tap in global memory
+    static constexpr int PPT = C / 16, NWI = TPS * PPT;       // 1-KB DMA pieces per tap / per tile
+    static_assert(NWI % 4 == 0, "every wave issues the same number of pieces");
+    static constexpr int WPW = NWI / 4;
+    static constexpr int NP = PF_XP / 64, XPW = NP;
+    static constexpr int XH = (2 * XST > C * PF_HP) ? 2 * XST : C * PF_HP;     // window ring and intermediate share storage
+    static constexpr int BYTES = (XH + NSW * WT) * (int)sizeof(float);
+    static_assert(NSW == 3 || NSW == 4, "wait_tile counts at most two tiles ahead");
+    static_assert(XH >= PAIR_EPI_FLOATS, "staging patches must fit");
 };
-
 // C = 32*CH channels; a ring step multiplies TPS taps of one 16-channel chunk (at 32 channels a one-tap step is 8 MFMAs = 512 cycles
 // between two barriers, and the step's fixed costs - barrier, DMA issue, the first fragment round trip - were 40 % of it: four taps,
 // 32 MFMAs; at 64 channels one tap = 16 MFMAs keeps the workgroup at 49 KB of LDS, see launch_respair_f32); NSW ring stages
@@ -51,18 +53,8 @@ struct PairF32Dev {
 // K = kernel size as a template parameter (3 / 7 / 11; 0 = runtime): see the unrolled control flow below
 template <int CH, int TPS, int NSW, int ABL = 0, int K = 0>
 __global__ void __launch_bounds__(256) respair_f32_kernel(const PairF32Dev p) {
-    constexpr int C = 32 * CH;
-    constexpr int XST = PF_GK * PF_XP;                 // floats per window stage
-    constexpr int WT = TPS * PF_GK * C;                // floats per weight tile: [tap][16 ci][C co], contiguous per tap in global memory
-    constexpr int PPT = C / 16;                        // 1-KB DMA pieces per tap
-    constexpr int NWI = TPS * PPT;                     // ... per tile
-    static_assert(NWI % 4 == 0, "every wave issues the same number of pieces");
-    constexpr int WPW = NWI / 4;
-    constexpr int NP = PF_XP / 64;
-    constexpr int XPW = NP;
-    constexpr int XH = (2 * XST > C * PF_HP) ? 2 * XST : C * PF_HP;     // window ring and intermediate share storage
-    static_assert(NSW == 3 || NSW == 4, "wait_tile counts at most two tiles ahead");
-    static_assert(XH * sizeof(float) >= 4 * 32 * PF_EP * sizeof(float), "staging patches must fit");
+    using G = PairF32Geo<CH, TPS, NSW>;
+    constexpr int C = G::C, XST = G::XST, WT = G::WT, PPT = G::PPT, WPW = G::WPW, NP = G::NP, XPW = G::XPW, XH = G::XH;
     extern __shared__ __attribute__((aligned(16))) float pf_lds[];
     float* lx = pf_lds;                                // conv1: window ring; then h[c][PF_HP]; then the epilogue patches
     float* lw = pf_lds + XH;
@@ -71,13 +63,8 @@ __global__ void __launch_bounds__(256) respair_f32_kernel(const PairF32Dev p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 5, l31 = lane & 31;
     const int b = blockIdx.z;
-    const int h2 = (p.k - 1) / 2, h1 = (p.k - 1) * p.dil / 2;
-    const int TT = pair_run_outputs(PF_T, p.k);       // outputs per workgroup (dma_ring.h)
-    const int n0 = blockIdx.x * TT;                   // first output sample
-    const int m0 = n0 - h2;                           // first intermediate position
-    const int x0 = m0 - h1;                           // first window sample
-    const int start_al = x0 & ~3;
-    const int aoff = x0 - start_al;
+    const PairRun r = pair_run(PF_T, p.k, p.dil);     // respair_dev.h
+    const int TT = r.TT, n0 = r.n0, m0 = r.m0, start_al = r.start_al, aoff = r.aoff;
     const float* xb = p.x + (int64_t)b * p.bstride;
     float slope = p.slope;
     vgpr_pin(slope);
@@ -153,49 +140,29 @@ __global__ void __launch_bounds__(256) respair_f32_kernel(const PairF32Dev p) {
         if (++slot == NSW) slot = 0;
         if (++nslot == NSW) nslot = 0;
     };
-    // one ring step: up to TPS taps x 8 channel pairs, fragments requested two pairs ahead of their MFMAs (lds_asm.h), three
-    // register sets so that a request never lands in registers an MFMA in flight still reads
+    // one ring step: up to TPS taps x 8 channel pairs through the fragment pipeline of ring_step.h, CH A fragments and one B read per pair
     // (waddr: this lane's byte address in the step's weight tile; b0: ... of the step's first tap in the window / intermediate; bstep: bytes per tap)
     auto body = [&](auto convc, auto ntc, const unsigned waddr, const unsigned b0, const unsigned bstep) {
         constexpr int CONV = decltype(convc)::value, NM = decltype(ntc)::value * 8;       // channel pairs of this step: compile-time,
-        constexpr int PITCH = CONV ? PF_HP : PF_XP;                                          // so every wait count below is an immediate
+        constexpr int PITCH = CONV ? PF_HP : PF_XP;                                          // so every wait count is an immediate
         unsigned baddr[TPS];
 #pragma unroll
         for (int tp = 0; tp < TPS; ++tp) baddr[tp] = b0 + tp * bstep;
-        float fa[3][CH], fb[3];
-        if constexpr (ABL & 1) {
+        ring_step_pairs<NM, CH, 1, (ABL & 1) != 0>(
+            [](auto) { return std::integral_constant<int, 1>{}; },
+            [&](auto mc, auto ic, float& v) {
+                constexpr int M = decltype(mc)::value;
+                lds_rd32<((M / 8 * PF_GK + 2 * (M % 8)) * C + decltype(ic)::value * 32) * 4>(v, waddr);
+            },
+            [&](auto mc, auto, float& v) { constexpr int M = decltype(mc)::value; lds_rd32<2 * (M % 8) * PITCH * 4>(v, baddr[M / 8]); },
+            []() {},
+            [&](auto, const float (&fa)[CH], const float (&fb)[1]) {
 #pragma unroll
-            for (int s3 = 0; s3 < 3; ++s3) {
-#pragma unroll
-                for (int i = 0; i < CH; ++i) fa[s3][i] = (float)lane;
-                fb[s3] = (float)(lane + s3);
-            }
-        }
-        auto fload = [&](auto mc) {
-            constexpr int M = decltype(mc)::value, TP = M / 8, KK = M % 8, S = M % 3;
-            if constexpr (ABL & 1) return;
-            static_for<0, CH>([&](auto ic) {
-                constexpr int I = decltype(ic)::value;
-                lds_rd32<((TP * PF_GK + 2 * KK) * C + I * 32) * 4>(fa[S][I], waddr);
+                for (int i = 0; i < CH; ++i) {
+                    if constexpr (ABL & 8) acc[i][0] += fa[i] * fb[0];
+                    else acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i], fb[0], acc[i], 0, 0, 0);
+                }
             });
-            lds_rd32<2 * KK * PITCH * 4>(fb[S], baddr[TP]);
-        };
-        fload(std::integral_constant<int, 0>{});
-        fload(std::integral_constant<int, 1>{});
-        static_for<0, NM>([&](auto mc) {
-            constexpr int M = decltype(mc)::value, S = M % 3;
-            if constexpr (M + 1 < NM) LDS_WAIT(CH + 1); else LDS_WAIT(0);
-#pragma unroll
-            for (int i = 0; i < CH; ++i) lds_pin(fa[S][i]);
-            lds_pin(fb[S]);
-            if constexpr (M + 2 < NM) fload(std::integral_constant<int, M + 2>{});
-            const float bv = fb[S];
-#pragma unroll
-            for (int i = 0; i < CH; ++i) {
-                if constexpr (ABL & 8) acc[i][0] += fa[S][i] * bv;
-                else acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S][i], bv, acc[i], 0, 0, 0);
-            }
-        });
     };
     auto compute = [&](auto convc) {
         constexpr int CONV = decltype(convc)::value;
@@ -306,71 +273,12 @@ __global__ void __launch_bounds__(256) respair_f32_kernel(const PairF32Dev p) {
         if (sum == 1.2345e-33f) ob[0] = sum;
         return;
     }
-    if (p.staged) {
-        float* patch = lx + wave * (32 * PF_EP);
-        const int rr = lane >> 3, t4 = (lane & 7) * 4;
-        const int nl = 32 * wave + t4;
-        const int n = n0 + nl;
-        const bool nok = nl < TT && n < p.T;
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) patch[(4 * g + 8 * (r >> 2) + (r & 3)) * PF_EP + l31] = acc[i][r];
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            float4 v[4], rv[4], ov[4];
-            float bv[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int co = i * 32 + rr + 8 * q;
-                v[q] = *reinterpret_cast<const float4*>(patch + (rr + 8 * q) * PF_EP + t4);
-                const int64_t oi = (int64_t)co * p.T + (nok ? n : 0);
-                rv[q] = nok ? *reinterpret_cast<const float4*>(xb + oi) : make_float4(0.f, 0.f, 0.f, 0.f);
-                ov[q] = (nok && p.beta != 0.f) ? *reinterpret_cast<const float4*>(ob + oi) : make_float4(0.f, 0.f, 0.f, 0.f);
-                bv[q] = p.b2[co];
-            }
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            if (nok) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int co = i * 32 + rr + 8 * q;
-                    const float a4[4] = {v[q].x, v[q].y, v[q].z, v[q].w}, r4[4] = {rv[q].x, rv[q].y, rv[q].z, rv[q].w};
-                    const float o4[4] = {ov[q].x, ov[q].y, ov[q].z, ov[q].w};
-                    float o[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = pair_out_value(p.alpha, p.beta, a4[e], bv[q], r4[e], o4[e]);
-                    *reinterpret_cast<float4*>(ob + (int64_t)co * p.T + n) = make_float4(o[0], o[1], o[2], o[3]);
-                }
-            }
-        }
-    } else {
-        const int nl = 32 * wave + l31;
-        const int n = n0 + nl;
-        const bool nok = nl < TT && n < p.T;
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-            float rv[16], ov[16], bv[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = i * 32 + 4 * g + 8 * (r >> 2) + (r & 3);
-                rv[r] = nok ? xb[(int64_t)co * p.T + n] : 0.f;
-                ov[r] = (nok && p.beta != 0.f) ? ob[(int64_t)co * p.T + n] : 0.f;
-                bv[r] = p.b2[co];
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = i * 32 + 4 * g + 8 * (r >> 2) + (r & 3);
-                if (!nok) continue;
-                ob[(int64_t)co * p.T + n] = pair_out_value(p.alpha, p.beta, acc[i][r], bv[r], rv[r], ov[r]);
-            }
-        }
-    }
+    pair_epilogue<CH>(acc, lx, p.staged, xb, ob, p.T, n0, TT, p.b2, p.alpha, p.beta);
 }
 
 template <int CH, int TPS, int NSW, int ABL = 0, int K = 0>
 static void launch_pair_f32(const PairF32Dev& d, dim3 grid, hipStream_t st) {
-    constexpr int C = 32 * CH, XST = PF_GK * PF_XP;
-    constexpr int XH = (2 * XST > C * PF_HP) ? 2 * XST : C * PF_HP;
-    constexpr int BYTES = (XH + NSW * TPS * PF_GK * C) * (int)sizeof(float);
+    constexpr int BYTES = PairF32Geo<CH, TPS, NSW>::BYTES;
     static OnceFlags once;
     vb_set_max_lds_once(once, (const void*)respair_f32_kernel<CH, TPS, NSW, ABL, K>, BYTES);
     hipLaunchKernelGGL((respair_f32_kernel<CH, TPS, NSW, ABL, K>), grid, dim3(256), BYTES, st, d);
@@ -383,18 +291,14 @@ bool respair_f32_supported(const RespairF32Args& a) {
 
 int launch_respair_f32(const RespairF32Args& a, hipStream_t st) {
     if (!respair_f32_supported(a)) VB_FAIL(VB_E_INVALID, "respair_f32: C=%d k=%d dil=%d T=%d (C 32/64/128, odd k <= 17, (k-1) dil <= 60, T %% 4 == 0, 16-B aligned)", a.C, a.k, a.dil, a.T);
-    if (a.x == a.out) VB_FAIL(VB_E_INVALID, "respair_f32: x and out must be distinct buffers (neighbouring workgroups re-read the halo)");
-    PairF32Dev d;
-    d.x = a.x; d.out = a.out; d.bstride = (int64_t)a.C * a.T; d.T = a.T; d.k = a.k; d.dil = a.dil;
-    d.w1 = a.w1; d.w2 = a.w2; d.b1 = a.b1; d.b2 = a.b2; d.slope = a.slope; d.alpha = a.alpha; d.beta = a.beta;
-    const int TT = pair_run_outputs(PF_T, a.k);
-    d.staged = (aligned16(a.out) && !vb_tune().conv_direct_epi) ? 1 : 0;
+    PairLaunchT<PairF32Dev> L{};
+    VB_TRY(pair_fill_common(a, "respair_f32", PF_T, a.k, L));      // respair_dev.h
+    PairF32Dev& d = L.d;
+    const dim3 grid = L.grid;
 #ifdef VB_EXPERIMENTS
     d.x_nt = getenv("VB_CONV_XNT") ? 1 : 0;
 #endif
-    dim3 grid(cdiv(a.T, TT), 1, a.B);
-    ProfScope prof(3, 2.0 * 2.0 * a.B * (double)a.C * a.C * a.k * (double)a.T,
-                   4.0 * a.B * (double)a.C * a.T * (2.0 + (a.beta != 0.f ? 1.0 : 0.0)) + 2.0 * 4.0 * a.k * a.C * a.C, st);
+    ProfScope prof(3, L.flops, L.act_bytes + 2.0 * 4.0 * a.k * a.C * a.C, st);
     // 32 channels: 4 taps per ring step, 3 stages (49 KB: three workgroups per CU).  64 channels: ONE tap per step, 3 stages - 49 KB, three
     // workgroups per CU: 16 MFMAs per step and wave instead of 32, but a third wave per SIMD: 2046 -> 1787 us at k = 7, 3181 -> 2799 at k = 11,
     // 994 -> 850 at k = 3 (8 clips; two taps / 4 stages = 70 KB = two per CU was the first shape; four per CU at 32 channels measured

@@ -16,47 +16,51 @@
 // LDS: window ring 2 x [16 ci][320] (both 16-channel chunks of x are requested up front), the intermediate h[32][272] aliases it, weight ring of 3 tiles
 // [TPS pseudo-taps][16 ci][32 co] (TPS = 4: 32 MFMAs per ring step and wave; k = 3 has 4 pseudo-taps in all and runs TPS = 2) = 64 KB, two workgroups
 // per CU.  The whole schedule - 2 convolutions x 2 chunks x ceil(P / TPS) ring steps - is unrolled: every wait count, tap offset and tile index is an
-// immediate.  Ring / fragment pipeline / counted vmcnt as in respair_f32_kernel; window feed: ring_window.h.
+// immediate.  Ring / counted vmcnt as in respair_f32_kernel; window feed: ring_window.h; fragment pipeline: ring_step.h; run
+// geometry and host-side fill: respair_dev.h.
 // C = 64: the waves are 2 (time) x 2 (channel halves) - a wave computes 32 of the 64 output channels of its 64 positions in BOTH convolutions, so the
 // accumulators stay 4 x 16 registers; runs of M = 4 VW = 128 / 120 intermediate positions, window pitch 192, h[64][144] = 37 KB, tiles of TPS = 2 pseudo-taps
 // [2][16][64] = 8 KB: 61 KB, two workgroups per CU; the four 16-channel windows go through the two-stage ring (chunk c + 1 is requested at chunk c's first step).
 #include <stdlib.h>
 #include <type_traits>
 
-#include "kernels.h"
-#include "dma_ring.h"
+#include "respair_dev.h"
 #include "lds_asm.h"
 #include "ring_window.h"
+#include "ring_step.h"
 #include "mf_taps.h"
 
 #define PW_GK 16
 #define PW_EP 68             // staged epilogue patch pitch (64 positions + 4)
 
-struct PairWDev {
-    const float* x; float* out; int64_t bstride; int T;
-    int dil;
-    const float* w1; const float* w2;      // minimal-filtering pseudo-taps [P][32 ci][32 co] fp32 each (pack.py:pack_conv_mf)
-    const float* b1; const float* b2;
-    float slope, alpha, beta;
+// the kernel's geometry, read by the kernel and by its launcher
+template <int TPS, int C>
+struct PairWGeo {
+    static constexpr int NSW = 3;
+    static constexpr int WC = C / 32, WTW = 4 / WC;            // waves along the channels / along time
+    static constexpr int XP = WTW * 64 + 64;                   // window pitch: the run + halo (<= 60) + alignment slack (<= 3)
+    static constexpr int HP = WTW * 64 + 16;                   // intermediate pitch: the run + (k - 1 <= 16)
+    static constexpr int XST = PW_GK * XP;                     // floats per window stage
+    static constexpr int WT = TPS * PW_GK * C;                 // floats per weight tile [TPS][16 ci][C co]
+    static constexpr int PPT = PW_GK * C / 256, NPIECE = WT / 256;      // 1-KB DMA pieces per pseudo-tap / per weight tile
+    static_assert(NPIECE % 4 == 0, "every wave issues the same number of pieces");
+    static constexpr int WPW = NPIECE / 4;
+    static constexpr int NP = XP / 64, XPW = NP;               // window pieces per wave and chunk (16 rows x XP / 256 floats / 4 waves)
+    static constexpr int XH0 = 2 * XST > C * HP ? 2 * XST : C * HP;      // window ring, intermediate and epilogue patches share storage
+    static constexpr int XH = XH0 > 4 * 32 * PW_EP ? XH0 : 4 * 32 * PW_EP;
+    static constexpr int BYTES = (XH + NSW * WT) * (int)sizeof(float);
+    // intermediate positions per workgroup at dilation dil (VW columns in use per wave)
+    __host__ __device__ static constexpr int run(int dil) { return WTW * 2 * ((32 / dil) * dil); }
 };
-
 template <int K, int TPS, int C>
-__global__ void __launch_bounds__(256, 2) respair_f32w_kernel(const PairWDev p) {
-    constexpr int NSW = 3;
-    constexpr int WC = C / 32, WTW = 4 / WC;            // waves along the channels / along time
+__global__ void __launch_bounds__(256, 2) respair_f32w_kernel(const PairF32Dev p) {
+    using G = PairWGeo<TPS, C>;
+    constexpr int NSW = G::NSW, WC = G::WC, WTW = G::WTW, XP = G::XP, HP = G::HP, XST = G::XST, WT = G::WT, PPT = G::PPT, WPW = G::WPW, NP = G::NP, XPW = G::XPW;
+    constexpr int XH = G::XH;
     constexpr int NCH = C / PW_GK;                      // 16-channel chunks per convolution
-    constexpr int XP = WTW * 64 + 64;                   // window pitch: the run + halo (<= 60) + alignment slack (<= 3)
-    constexpr int HP = WTW * 64 + 16;                   // intermediate pitch: the run + (k - 1 <= 16)
     constexpr int P = mf_ntaps(K);
     constexpr int KNS = (P + TPS - 1) / TPS;            // ring steps per 16-channel chunk
     constexpr int NT = 2 * NCH * KNS;                   // conv1 chunks, then conv2 chunks
-    constexpr int XST = PW_GK * XP;                     // floats per window stage
-    constexpr int WT = TPS * PW_GK * C;                 // floats per weight tile [TPS][16 ci][C co]
-    constexpr int NPIECE = WT / 256;                    // 1-KB DMA pieces per weight tile
-    static_assert(NPIECE % 4 == 0, "every wave issues the same number of pieces");
-    constexpr int WPW = NPIECE / 4;
-    constexpr int NP = XP / 64, XPW = NP;               // window pieces per wave and chunk (16 rows x XP / 256 floats / 4 waves)
-    constexpr int XH = (2 * XST > C * HP ? 2 * XST : C * HP) > 4 * 32 * PW_EP ? (2 * XST > C * HP ? 2 * XST : C * HP) : 4 * 32 * PW_EP;
     static_assert(NT >= NSW, "ring");
     extern __shared__ __attribute__((aligned(16))) float pw_lds[];
     float* lx = pw_lds;                                 // window ring; then h[c][HP]; then the epilogue patches
@@ -69,14 +73,8 @@ __global__ void __launch_bounds__(256, 2) respair_f32w_kernel(const PairWDev p) 
     const int b = blockIdx.z;
     const int dil = p.dil;
     const int VW = (32 / dil) * dil;
-    const int M = WTW * 2 * VW;                         // intermediate positions per workgroup
-    const int h2 = (K - 1) / 2, h1 = (K - 1) * dil / 2;
-    const int TT = pair_run_outputs(M, K);               // outputs per workgroup (dma_ring.h)
-    const int n0 = blockIdx.x * TT;
-    const int m0 = n0 - h2;
-    const int x0 = m0 - h1;
-    const int start_al = x0 & ~3;
-    const int aoff = x0 - start_al;
+    const PairRun r = pair_run(G::run(dil), K, dil);     // respair_dev.h
+    const int TT = r.TT, n0 = r.n0, m0 = r.m0, start_al = r.start_al, aoff = r.aoff;
     const float* xb = p.x + (int64_t)b * p.bstride;
     float slope = p.slope;
     vgpr_pin(slope);
@@ -90,7 +88,6 @@ __global__ void __launch_bounds__(256, 2) respair_f32w_kernel(const PairWDev p) 
     auto fix_x = [&](int ch) { win.fix(lx + (ch & 1) * XST, std::true_type{}, slope); };
     // ---- weight DMA: tile t = (conv, chunk, step): pseudo-taps [s TPS, s TPS + TPS) of 16 input channels; a piece = 256 consecutive floats of the
     // pseudo-tap's [16 ci][C co] block
-    constexpr int PPT = PW_GK * C / 256;                // pieces per pseudo-tap
     auto issue_w = [&](auto tc) {
         constexpr int T_ = decltype(tc)::value;
         constexpr int CONV = T_ / (NCH * KNS), CH = (T_ / KNS) % NCH, S = T_ % KNS, SLOT = T_ % NSW;
@@ -169,39 +166,22 @@ __global__ void __launch_bounds__(256, 2) respair_f32w_kernel(const PairWDev p) 
         constexpr int NM = NTAP * 8;
         const unsigned waddr = wa0 + SLOT * (WT * 4);
         const unsigned baddr = CONV ? ha0 + CH * (PW_GK * HP * 4) : xa0 + (CH & 1) * (XST * 4);
-        float fa[3], xa[3], xb2[3];
-        auto fload = [&](auto mc) {
-            constexpr int MM = decltype(mc)::value, TP = MM / 8, KK = MM % 8, SS = MM % 3;
-            constexpr MfTap MT = mf_tap(K, J0 + TP);
-            lds_rd32<((TP * PW_GK + 2 * KK) * C) * 4>(fa[SS], waddr);
-            if constexpr (CONV) {
-                lds_rd32<(2 * KK * HP + MT.oa) * 4>(xa[SS], baddr);
-                if constexpr (MT.op != 2) lds_rd32<(2 * KK * HP + MT.ob) * 4>(xb2[SS], baddr);
-            } else {
-                lds_rd32<(2 * KK * XP) * 4>(xa[SS], baddr + MT.oa * dil4);
-                if constexpr (MT.op != 2) lds_rd32<(2 * KK * XP) * 4>(xb2[SS], baddr + MT.ob * dil4);
-            }
-        };
-        fload(std::integral_constant<int, 0>{});
-        fload(std::integral_constant<int, 1>{});
-        static_for<0, NM>([&](auto mc) {
-            constexpr int MM = decltype(mc)::value, SS = MM % 3;
-            constexpr MfTap MT = mf_tap(K, J0 + MM / 8);
-            if constexpr (MM + 1 < NM) {
-                constexpr MfTap MN = mf_tap(K, J0 + (MM + 1) / 8);
-                LDS_WAIT(MN.op == 2 ? 2 : 3);
-            } else {
-                LDS_WAIT(0);
-            }
-            lds_pin(fa[SS]); lds_pin(xa[SS]);
-            if constexpr (MT.op != 2) lds_pin(xb2[SS]);
-            if constexpr (MM + 2 < NM) fload(std::integral_constant<int, MM + 2>{});
-            float bv;
-            if constexpr (MT.op == 0) bv = xa[SS] - xb2[SS];
-            else if constexpr (MT.op == 1) bv = xa[SS] + xb2[SS];
-            else bv = xa[SS];
-            acc[MT.acc] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[SS], bv, acc[MT.acc], 0, 0, 0);
-        });
+        auto tap = [](auto mc) { return std::integral_constant<int, J0 + decltype(mc)::value / 8>{}; };      // pair m's pseudo-tap
+        ring_step_pairs<NM, 1, 2>(
+            [&](auto mc) { return std::integral_constant<int, mf_reads(mf_tap(K, decltype(tap(mc))::value))>{}; },
+            [&](auto mc, auto, float& v) { constexpr int MM = decltype(mc)::value; lds_rd32<((MM / 8 * PW_GK + 2 * (MM % 8)) * C) * 4>(v, waddr); },
+            [&](auto mc, auto jc, float& v) {
+                constexpr int KK = decltype(mc)::value % 8;
+                constexpr MfTap MT = mf_tap(K, decltype(tap(mc))::value);
+                constexpr int O = decltype(jc)::value ? MT.ob : MT.oa;
+                if constexpr (CONV) lds_rd32<(2 * KK * HP + O) * 4>(v, baddr);
+                else lds_rd32<(2 * KK * XP) * 4>(v, baddr + O * dil4);
+            },
+            []() {},
+            [&](auto mc, const float (&fa)[1], const float (&x)[2]) {
+                constexpr MfTap MT = mf_tap(K, decltype(tap(mc))::value);
+                acc[MT.acc] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[0], mf_operand<MT.op>(x), acc[MT.acc], 0, 0, 0);
+            });
     });
     __syncthreads();                     // h is dead: its storage holds the four wave-private staging patches now
 
@@ -250,15 +230,11 @@ __global__ void __launch_bounds__(256, 2) respair_f32w_kernel(const PairWDev p) 
 }
 
 template <int K, int TPS, int C>
-static void launch_pair_w(const PairWDev& d, int B, hipStream_t st) {
-    constexpr int WTW = 4 / (C / 32), XP = WTW * 64 + 64, HP = WTW * 64 + 16;
-    constexpr int XH = (2 * PW_GK * XP > C * HP ? 2 * PW_GK * XP : C * HP) > 4 * 32 * PW_EP ? (2 * PW_GK * XP > C * HP ? 2 * PW_GK * XP : C * HP) : 4 * 32 * PW_EP;
-    constexpr int BYTES = (XH + 3 * TPS * PW_GK * C) * (int)sizeof(float);
-    const int VW = (32 / d.dil) * d.dil;
-    const int TT = pair_run_outputs(WTW * 2 * VW, K);
+static void launch_pair_w(const PairF32Dev& d, dim3 grid, hipStream_t st) {
+    constexpr int BYTES = PairWGeo<TPS, C>::BYTES;
     static OnceFlags once;
     vb_set_max_lds_once(once, (const void*)respair_f32w_kernel<K, TPS, C>, BYTES);
-    hipLaunchKernelGGL((respair_f32w_kernel<K, TPS, C>), dim3(cdiv(d.T, TT), 1, B), dim3(256), BYTES, st, d);
+    hipLaunchKernelGGL((respair_f32w_kernel<K, TPS, C>), grid, dim3(256), BYTES, st, d);
 }
 
 bool respair_f32w_supported(const RespairF32Args& a) {
@@ -269,21 +245,19 @@ bool respair_f32w_supported(const RespairF32Args& a) {
 // a.w1 / a.w2 are the minimal-filtering pseudo-tap weights of the two convolutions ([P][C][C], pack.py:pack_conv_mf)
 int launch_respair_f32w(const RespairF32Args& a, hipStream_t st) {
     if (!respair_f32w_supported(a)) VB_FAIL(VB_E_INVALID, "respair_f32w: C=%d k=%d dil=%d T=%d (C 32 / 64, k 3/7/11, (k-1) dil <= 60, T %% 4 == 0, 16-B aligned)", a.C, a.k, a.dil, a.T);
-    if (a.x == a.out) VB_FAIL(VB_E_INVALID, "respair_f32w: x and out must be distinct buffers (neighbouring workgroups re-read the halo)");
-    PairWDev d;
-    d.x = a.x; d.out = a.out; d.bstride = (int64_t)a.C * a.T; d.T = a.T; d.dil = a.dil;
-    d.w1 = a.w1; d.w2 = a.w2; d.b1 = a.b1; d.b2 = a.b2; d.slope = a.slope; d.alpha = a.alpha; d.beta = a.beta;
-    // executed flops: pseudo-taps / 2 products per output, two convolutions
-    ProfScope prof(3, 2.0 * 2.0 * a.B * (double)a.C * a.C * (0.5 * mf_ntaps(a.k)) * (double)a.T,
-                   4.0 * a.B * (double)a.C * a.T * (2.0 + (a.beta != 0.f ? 1.0 : 0.0)) + 2.0 * 4.0 * mf_ntaps(a.k) * a.C * a.C, st);
+    // runs of M = 8 VW (C = 32) / 4 VW (C = 64) intermediate positions; executed flops: pseudo-taps / 2 products per output, two convolutions
+    PairLaunchT<PairF32Dev> L{};
+    VB_TRY(pair_fill_common(a, "respair_f32w", a.C == 32 ? PairWGeo<4, 32>::run(a.dil) : PairWGeo<2, 64>::run(a.dil), 0.5 * mf_ntaps(a.k), L));      // respair_dev.h
+    const PairF32Dev& d = L.d;
+    ProfScope prof(3, L.flops, L.act_bytes + 2.0 * 4.0 * mf_ntaps(a.k) * a.C * a.C, st);
     if (a.C == 32) {
-        if (a.k == 3) launch_pair_w<3, 2, 32>(d, a.B, st);
-        else if (a.k == 7) launch_pair_w<7, 4, 32>(d, a.B, st);
-        else launch_pair_w<11, 4, 32>(d, a.B, st);
+        if (a.k == 3) launch_pair_w<3, 2, 32>(d, L.grid, st);
+        else if (a.k == 7) launch_pair_w<7, 4, 32>(d, L.grid, st);
+        else launch_pair_w<11, 4, 32>(d, L.grid, st);
     } else {
-        if (a.k == 3) launch_pair_w<3, 2, 64>(d, a.B, st);
-        else if (a.k == 7) launch_pair_w<7, 2, 64>(d, a.B, st);
-        else launch_pair_w<11, 2, 64>(d, a.B, st);
+        if (a.k == 3) launch_pair_w<3, 2, 64>(d, L.grid, st);
+        else if (a.k == 7) launch_pair_w<7, 2, 64>(d, L.grid, st);
+        else launch_pair_w<11, 2, 64>(d, L.grid, st);
     }
     VB_CHECK_LAUNCH();
     return VB_OK;

@@ -32,7 +32,7 @@ __global__ void __launch_bounds__(256) respair_x3_kernel(const PairDev p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 5, l31 = lane & 31;
     const int b = blockIdx.z;
-    const PairRun r = pair_run(p);
+    const PairRun r = pair_run(PAIR_T, p.k, p.dil);
     const int TT = r.TT, n0 = r.n0, m0 = r.m0, x0 = r.x0, xw_used = r.xw_used;
     const float* xb = p.x + (int64_t)b * p.bstride;
 
