@@ -212,6 +212,35 @@ typedef struct { const float* cfg_scale; const int64_t* clip; } vb_rows;
 int vb_sample_cfg_rows(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
                        const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_rows* rows, const vb_keep* keep,
                        const vb_noise* noise, float* traj, void* ws, void* stream);
+/* The same sampler over JOINT WINDOWS of long clips (build-defined; the MultiDiffusion construction on this sampler).  The B rows are nw
+ * windows of Bc = B / nw clips, x [nw*Bc][C][n] with row = w*Bc + b and n = T the window length; window w covers the clip's tokens
+ * [starts[w], starts[w] + n).  Neighbouring windows overlap in ov = starts[w] + n - starts[w+1] tokens: token n - ov + u of row w*Bc + b
+ * and token u of row (w+1)*Bc + b are the same token of clip b.  After every Euler step both copies take one consensus value, in fp32
+ * and in exactly this arithmetic, for every u in [0, ov), clip b and channel c:
+ *     ia = ((w*Bc + b)*C + c)*n + (n - ov + u)        ib = (((w+1)*Bc + b)*C + c)*n + u
+ *     g  = (float)(u + 1) / (float)(ov + 1)           (the later window's ramp weight (u + 1) / (ov + 1), the one vb_crossfade_windows uses)
+ *     m  = fmaf(g, x[ib] - x[ia], x[ia]);   x[ia] = x[ib] = m
+ * so equal copies come back unchanged bit for bit, and overlapping tokens of neighbouring rows are bit-identical after every step, in
+ * every traj[k] and in the result: the windows are stitched by plain slicing, without a fade.  Every window's self-attention sees at
+ * every step the state its neighbour sees in the overlap.
+ * Order within a step: (1) the Euler + CFG update - fused into FinalLayer or the separate launch - with the known-region blend when
+ * keep is given, (2) the overlap consensus, (3) the traj copy.  A known region that is equal in both windows stays on its path bit for
+ * bit.  The consensus also runs once on entry, after the keep projection and before traj[0]: rows that disagree in their overlaps
+ * start from the consensus, rows cut from one start noise are not changed.  It is one kernel in both update forms, so VB_EULER_LAUNCH
+ * stays bit-identical to the fused form.
+ *   starts  int32 [nw]  HOST array of window starts, ascending; read during the call only.
+ * VB_E_INVALID, with the window named in vb_last_error(), when: nw < 1 or nw > 64; B % nw != 0; starts[0] < 0;
+ * starts[w] < starts[w+1] <= starts[w] + n is violated (descending starts, or a gap); starts[w+2] < starts[w] + n (a token under three
+ * windows - the pairs above would no longer be disjoint).
+ * win == NULL or nw == 1 is exactly vb_sample_cfg_rows (which, like vb_sample_cfg and vb_sample_cfg_keep, forwards here).  The captured
+ * graph includes the consensus launches; its key holds nw and the VALUES of starts, so another plan on the same buffers captures its
+ * own graph and a plain call never replays a windows graph. */
+typedef struct { const int32_t* starts; int nw; } vb_windows;     /* starts: HOST array of nw window starts, ascending */
+int vb_sample_cfg_windows(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
+                          const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_windows* win, const vb_rows* rows,
+                          const vb_keep* keep, const vb_noise* noise, float* traj, void* ws, void* stream);
+/* The overlap consensus alone, on x [nw*Bc][C][n] with B = nw*Bc rows (the unit, like vb_euler_cfg_step): same formula, same checks. */
+int vb_window_blend(float* x, const int32_t* starts, int nw, int B, int C, int n, void* stream);
 /* The step loop of vb_sample_cfg is captured into a hipGraph the second time a call arrives with the same buffers / shape on a
  * capturable (non-default) stream and replayed from then on (noise key via device memory: any seed / clip base replays).
  * Number of instantiated graphs this context holds (0 = every call so far ran eagerly): */

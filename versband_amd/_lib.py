@@ -68,6 +68,10 @@ class Rows(C.Structure):
     _fields_ = [("cfg_scale", c_void_p), ("clip", c_void_p)]
 
 
+class Windows(C.Structure):
+    _fields_ = [("starts", C.POINTER(C.c_int32)), ("nw", c_int)]
+
+
 class MelConfig(C.Structure):
     _fields_ = [("n_fft", c_int), ("hop", c_int), ("n_mels", c_int)]
 
@@ -113,6 +117,9 @@ PROTOTYPES = {
     "vb_sample_cfg": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_float, C.POINTER(Noise), P, P, P]),
     "vb_sample_cfg_keep": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_float, C.POINTER(Keep), C.POINTER(Noise), P, P, P]),
     "vb_sample_cfg_rows": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_float, C.POINTER(Rows), C.POINTER(Keep), C.POINTER(Noise), P, P, P]),
+    "vb_sample_cfg_windows": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_float, C.POINTER(Windows), C.POINTER(Rows), C.POINTER(Keep),
+                                      C.POINTER(Noise), P, P, P]),
+    "vb_window_blend": (c_int, [P, C.POINTER(C.c_int32), c_int, c_int, c_int, c_int, P]),
     "vb_sample_graphs": (c_int, [P]),
     "vb_net_load": (c_int, [P, c_int, C.POINTER(NetOp), c_int, C.POINTER(BufDesc), c_int, c_int, c_int, c_int, c_int]),
     "vb_net_workspace_bytes": (c_size_t, [P, c_int, c_int, c_int]),

@@ -2,6 +2,7 @@
 // host drivers at the end of t5.hip / melnet.hip): the context, the workspace carver, the DiT layouts and the calls that cross files.
 // No device allocation happens on the host side: all scratch is carved out of caller buffers (sizes from *_bytes()).
 #pragma once
+#include <array>
 #include <tuple>
 #include <vector>
 
@@ -22,7 +23,8 @@ struct SampleGraph {
         unsigned tune_gen = 0;            // a captured graph bakes the knob-dependent kernel selection in
         const void* keep_ref = nullptr; const void* keep_x0 = nullptr; const void* keep_mask = nullptr; float sigma_min = 0.f;   // vb_sample_cfg_keep (all null: a plain call)
         const void* rows_scale = nullptr; const void* rows_clip = nullptr;   // vb_sample_cfg_rows: the two POINTERS (cfg_scale is 0 beside rows_scale); their contents are read when the kernels run
-        auto tie() const { return std::tie(x, cond, ws, B, nb, T, L, n_steps, cfg_scale, tune_gen, keep_ref, keep_x0, keep_mask, sigma_min, rows_scale, rows_clip); }
+        int nw = 0; std::array<int, 64> starts{};    // vb_sample_cfg_windows: the plan's VALUES (the kernel argument holds them); nw = 0: no windows
+        auto tie() const { return std::tie(x, cond, ws, B, nb, T, L, n_steps, cfg_scale, tune_gen, keep_ref, keep_x0, keep_mask, sigma_min, rows_scale, rows_clip, nw, starts); }
         bool operator==(const Key& o) const { return tie() == o.tie(); }
     } key;
     int seen = 0;                         // calls with this key so far (the first runs eagerly, the second captures)

@@ -221,6 +221,13 @@ int launch_final_layer_euler(const float* h, const float* shift, const float* sc
 int launch_euler_cfg(const EulerStep& es, const float* v, int B, int64_t per, int T, int has_uncond, float dt_val, hipStream_t st);
 // projection on entry: x <- blend(mask, r(t_0), x) with t_0 = tn_table[0] - dt_table[0]
 int launch_keep_project(float* x, int B, int64_t per, int T, const float* dt_table, const EulerKeep& keep, hipStream_t st);
+// joint windows (vb_sample_cfg_windows): the validated plan, by value in the kernel's argument block (nothing on the device to fill, and
+// a captured graph holds its own copy).  window_plan checks starts (HOST array) for B rows of n tokens: 1 <= nw <= 64, B % nw == 0,
+// starts[0] >= 0, starts[w] < starts[w+1] <= starts[w] + n, starts[w+2] >= starts[w] + n; VB_E_INVALID names the window otherwise.
+struct WindowPlan { int nw = 0; int s[64] = {}; };
+int window_plan(const int32_t* starts, int nw, int B, int n, WindowPlan* out);
+// x [nw*Bc][C][n] (row = w*Bc + b): both copies of every overlapping token <- fmaf(g, x[ib] - x[ia], x[ia]), g = (u + 1) / (ov + 1)
+int launch_window_blend(float* x, const WindowPlan& wp, int Bc, int C, int n, hipStream_t st);
 int launch_sampler_params(int* step, uint64_t seed, int64_t clip_base, int nfe_base, hipStream_t st);   // step[4..9]: noise key of the call
 int launch_step_ctl(int* step, int64_t* t_idx_cur, const int64_t* t_table, int n_steps, int Beff, int reset, hipStream_t st);
 

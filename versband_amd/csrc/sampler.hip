@@ -1,12 +1,17 @@
 // CFG / Euler sampler (cfm1_audio_sampler.py:107-116): the step loop around dit_forward and its hipGraph cache.
+#include <algorithm>
+
 #include "engine.h"
 
 // the launches of one sampler call after its tables are in place: tabulation of the per-step conditioning vectors, then n_steps x
 // [step bookkeeping, one network evaluation of both CFG branches, Euler + guidance update]   (cfm1_audio_sampler.py:107-116)
 // keep != nullptr (vb_sample_cfg_keep): every update also puts the known tokens back on the probability path at the time after the step
 // rows (vb_sample_cfg_rows; either member may be null): clip b is guided by rows.cfg_scale[b] and draws its router noise as clip rows.clip[b]
+// wins != nullptr (vb_sample_cfg_windows): the rows are wins->nw windows of B / nw clips; after every update - in either form, the same
+// launch - the overlapping tokens of neighbouring windows take their consensus value, before the trajectory copy
 static int sample_steps(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps, float cfg_scale,
-                        const vb_rows& rows, const vb_keep* keep, const vb_noise* noise, float* traj, void* ws, hipStream_t st) {
+                        const vb_rows& rows, const vb_keep* keep, const WindowPlan* wins, const vb_noise* noise, float* traj, void* ws,
+                        hipStream_t st) {
     const vb_dit_config& c = ctx->cfg;
     const DitPlan plan = dit_plan(ctx, B, n_branch, T, L);
     WsL s = carve_ws(ws, c, B, n_branch, T, L);
@@ -65,6 +70,7 @@ static int sample_steps(vb_ctx* ctx, float* x, const void* cond, int B, int n_br
         if (fuse) ev.euler = &es;
         VB_TRY(dit_forward(ctx, ev, st));
         if (!fuse) VB_TRY(launch_euler_cfg(es, s.v, B, per, T, n_branch == 2, 0.f, st));
+        if (wins) VB_TRY(launch_window_blend(x, *wins, B / wins->nw, c.in_channels, T, st));
         if (traj) VB_HIP(hipMemcpyAsync(traj + (size_t)(k + 1) * B * per, x, (size_t)B * per * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     return VB_OK;
@@ -101,21 +107,35 @@ int vb_euler_cfg_step(float* x, const float* v, int B, int64_t per_item, float c
 int vb_sample_cfg(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
                   const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_noise* noise, float* traj, void* ws,
                   void* stream) {
-    return vb_sample_cfg_rows(ctx, x, cond, B, n_branch, T, L, n_steps, t_idx_table, dt_table, cfg_scale, nullptr, nullptr, noise, traj, ws, stream);
+    return vb_sample_cfg_windows(ctx, x, cond, B, n_branch, T, L, n_steps, t_idx_table, dt_table, cfg_scale, nullptr, nullptr, nullptr, noise, traj, ws, stream);
 }
 int vb_sample_cfg_keep(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
                        const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_keep* keep, const vb_noise* noise,
                        float* traj, void* ws, void* stream) {
-    return vb_sample_cfg_rows(ctx, x, cond, B, n_branch, T, L, n_steps, t_idx_table, dt_table, cfg_scale, nullptr, keep, noise, traj, ws, stream);
+    return vb_sample_cfg_windows(ctx, x, cond, B, n_branch, T, L, n_steps, t_idx_table, dt_table, cfg_scale, nullptr, nullptr, keep, noise, traj, ws, stream);
 }
 int vb_sample_cfg_rows(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
-                       const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_rows* rows_in, const vb_keep* keep,
+                       const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_rows* rows, const vb_keep* keep,
                        const vb_noise* noise, float* traj, void* ws, void* stream) {
+    return vb_sample_cfg_windows(ctx, x, cond, B, n_branch, T, L, n_steps, t_idx_table, dt_table, cfg_scale, nullptr, rows, keep, noise, traj, ws, stream);
+}
+int vb_window_blend(float* x, const int32_t* starts, int nw, int B, int C, int n, void* stream) {
+    if (!x || C < 1) VB_FAIL(VB_E_INVALID, "window_blend: null x or C < 1");
+    WindowPlan wp;
+    VB_TRY(window_plan(starts, nw, B, n, &wp));
+    return launch_window_blend(x, wp, B / nw, C, n, (hipStream_t)stream);
+}
+int vb_sample_cfg_windows(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
+                          const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_windows* win, const vb_rows* rows_in,
+                          const vb_keep* keep, const vb_noise* noise, float* traj, void* ws, void* stream) {
     const vb_rows rows = rows_in ? *rows_in : vb_rows{nullptr, nullptr};
     if (rows.cfg_scale) cfg_scale = 0.f;          // unused beside the array; one value in the graph key
     if (!ctx || !ctx->dit_loaded) VB_FAIL(VB_E_STATE, "sample_cfg: DiT not loaded");
     if (n_steps < 1 || n_steps > 1024) VB_FAIL(VB_E_INVALID, "sample_cfg: n_steps=%d", n_steps);
     if (keep && (!keep->ref || !keep->x0 || !keep->mask || !keep->t_next)) VB_FAIL(VB_E_INVALID, "sample_cfg_keep: ref, x0, mask and t_next must all be given");
+    WindowPlan wp;
+    if (win) VB_TRY(window_plan(win->starts, win->nw, B, T, &wp));
+    const WindowPlan* wins = win && wp.nw > 1 ? &wp : nullptr;      // (one window: the plain call, and its graph)
     VB_HIP(hipSetDevice(ctx->device));
     RoctxRange rr("vb_sample_cfg");
     hipStream_t st = (hipStream_t)stream;
@@ -131,6 +151,8 @@ int vb_sample_cfg_rows(vb_ctx* ctx, float* x, const void* cond, int B, int n_bra
         VB_HIP(hipMemcpyAsync(s.tn_table, keep->t_next, (size_t)n_steps * sizeof(float), hipMemcpyDefault, st));
         VB_TRY(launch_keep_project(x, B, per, T, s.dt_table, EulerKeep{keep->ref, keep->x0, keep->mask, s.tn_table, keep->sigma_min}, st));
     }
+    // rows that disagree in their overlaps start from the consensus; rows cut from one start noise are not changed by it
+    if (wins) VB_TRY(launch_window_blend(x, wp, B / wp.nw, c.in_channels, T, st));
     if (traj) VB_HIP(hipMemcpyAsync(traj, x, (size_t)B * per * sizeof(float), hipMemcpyDeviceToDevice, st));
     // the noise key travels through device memory (the router reads it behind the step counter): nothing a replayed graph bakes in
     VB_TRY(launch_sampler_params(s.step, noise ? noise->seed : 0, noise ? noise->clip_base : 0, noise ? noise->nfe : 0, st));
@@ -148,10 +170,11 @@ int vb_sample_cfg_rows(vb_ctx* ctx, float* x, const void* cond, int B, int n_bra
         key.tune_gen = vb_tune_generation();
         if (keep) { key.keep_ref = keep->ref; key.keep_x0 = keep->x0; key.keep_mask = keep->mask; key.sigma_min = keep->sigma_min; }
         key.rows_scale = rows.cfg_scale; key.rows_clip = rows.clip;
+        if (wins) { key.nw = wp.nw; std::copy(wp.s, wp.s + 64, key.starts.begin()); }
         SampleGraph* e = graph_entry(ctx, key);
         if (!e->exec && !e->failed && e->seen >= 2) {
             if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                const int rc = sample_steps(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, rows, keep, noise, nullptr, ws, st);
+                const int rc = sample_steps(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, rows, keep, wins, noise, nullptr, ws, st);
                 hipGraph_t gr = nullptr;
                 const hipError_t ee = hipStreamEndCapture(st, &gr);
                 if (rc == VB_OK && ee == hipSuccess && gr && hipGraphInstantiate(&e->exec, gr, nullptr, nullptr, 0) == hipSuccess) {
@@ -171,7 +194,7 @@ int vb_sample_cfg_rows(vb_ctx* ctx, float* x, const void* cond, int B, int n_bra
             return VB_OK;
         }
     }
-    return sample_steps(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, rows, keep, noise, traj, ws, st);
+    return sample_steps(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, rows, keep, wins, noise, traj, ws, st);
 }
 int vb_sample_graphs(vb_ctx* ctx) {
     int n = 0;

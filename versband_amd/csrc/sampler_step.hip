@@ -1,6 +1,8 @@
 // The sampler's own kernels (gfx950), called by sampler.hip: the CFG + Euler update where it is a launch of its own (n_branch == 1,
 // VB_EULER_LAUNCH, vb_euler_cfg_step; the sampler's default path fuses it into FinalLayer, rowlin.hip: final_layer_kernel<NQ, true>),
-// the entry projection of a known region, and the step bookkeeping behind the device-side step counter.
+// the entry projection of a known region, the overlap consensus of joint windows, and the step bookkeeping behind the device-side
+// step counter.
+#include <algorithm>
 #include <type_traits>
 
 #include "kernels.h"
@@ -61,6 +63,59 @@ __global__ void keep_project_kernel(float* x, int64_t n, int64_t per, int T, con
 int launch_keep_project(float* x, int B, int64_t per, int T, const float* dt_table, const EulerKeep& keep, hipStream_t st) {
     int64_t n = (int64_t)B * per;
     hipLaunchKernelGGL(keep_project_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, n, per, T, dt_table, keep);
+    VB_CHECK_LAUNCH();
+    return VB_OK;
+}
+// ---------------------------------------------------------------------------
+// Joint windows (vb_sample_cfg_windows, vb_window_blend): x [nw*Bc][C][n], row = w*Bc + b, holds the windows of Bc long clips.  The
+// last ov = starts[w] + n - starts[w+1] tokens of window w and the first ov of window w + 1 are the same tokens of the clip; after
+// every step both copies take one consensus value, the cross-fade of the two at that token (the later window's ramp weight, the one
+// crossfade_windows_kernel uses):
+//     g = (float)(u + 1) / (float)(ov + 1);   m = fmaf(g, x[ib] - x[ia], x[ia]);   x[ia] = x[ib] = m
+// Equal copies come back unchanged bit for bit (fmaf(g, 0, a) = a).  One thread owns one (ia, ib) pair and no token lies under three
+// windows (window_plan refuses such a plan), so the pairs are disjoint: no race, no dependence on the launch shape.
+// grid: y = the pair of windows (w, w + 1), x over Bc * C * ov of that pair (the widest overlap sizes it)
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) window_blend_kernel(float* x, const WindowPlan wp, int Bc, int C, int n) {
+    const int w = blockIdx.y;
+    const int ov = wp.s[w] + n - wp.s[w + 1];
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (ov <= 0 || i >= (int64_t)Bc * C * ov) return;
+    const int u = (int)(i % ov);
+    const int64_t bc = i / ov;                                   // b * C + c: rows of one window are contiguous
+    const int64_t ia = ((int64_t)w * Bc * C + bc) * n + (n - ov + u);
+    const int64_t ib = ((int64_t)(w + 1) * Bc * C + bc) * n + u;
+    const float g = (float)(u + 1) / (float)(ov + 1);
+    const float a = x[ia];
+    const float m = fmaf(g, x[ib] - a, a);
+    x[ia] = m;
+    x[ib] = m;
+}
+int window_plan(const int32_t* starts, int nw, int B, int n, WindowPlan* out) {
+    if (nw < 1 || nw > 64) VB_FAIL(VB_E_INVALID, "windows: %d windows (1..64)", nw);
+    if (!starts) VB_FAIL(VB_E_INVALID, "windows: starts is null");
+    if (B < 1 || n < 1 || B % nw != 0) VB_FAIL(VB_E_INVALID, "windows: %d rows of %d tokens are not %d windows of whole clips", B, n, nw);
+    if (starts[0] < 0) VB_FAIL(VB_E_INVALID, "windows: window 0 starts at %d", starts[0]);
+    for (int w = 0; w + 1 < nw; ++w) {
+        if (starts[w + 1] <= starts[w] || starts[w + 1] > starts[w] + n)
+            VB_FAIL(VB_E_INVALID, "windows: window %d at %d does not continue window %d at %d (length %d): descending or a gap", w + 1,
+                    starts[w + 1], w, starts[w], n);
+        if (w + 2 < nw && starts[w + 2] < starts[w] + n)
+            VB_FAIL(VB_E_INVALID, "windows: window %d at %d reaches into window %d at %d (length %d): a token under three windows", w + 2,
+                    starts[w + 2], w, starts[w], n);
+    }
+    WindowPlan p;
+    p.nw = nw;
+    for (int w = 0; w < nw; ++w) p.s[w] = starts[w];
+    *out = p;
+    return VB_OK;
+}
+int launch_window_blend(float* x, const WindowPlan& wp, int Bc, int C, int n, hipStream_t st) {
+    int ov_max = 0;
+    for (int w = 0; w + 1 < wp.nw; ++w) ov_max = std::max(ov_max, wp.s[w] + n - wp.s[w + 1]);
+    if (ov_max <= 0) return VB_OK;                               // one window, or windows that only touch
+    const int64_t tot = (int64_t)Bc * C * ov_max;
+    hipLaunchKernelGGL(window_blend_kernel, dim3((unsigned)((tot + 255) / 256), (unsigned)(wp.nw - 1)), dim3(256), 0, st, x, wp, Bc, C, n);
     VB_CHECK_LAUNCH();
     return VB_OK;
 }

@@ -286,15 +286,52 @@ class DiTEngine:
         rs = L.Rows(s_rows.data_ptr() if s_rows is not None else None, c_rows.data_ptr() if c_rows is not None else None)
         return rs, 0.0 if s_rows is not None else float(scale), held + [s_rows, c_rows]
 
+    @staticmethod
+    def _windows_struct(windows, B: int, T: int):
+        """validate the window starts of a joint call - B rows = nw windows (row = w * Bc + b) of T tokens each - and lay them out as
+        vb_windows (a host array, read during the call).  The rules are the library's (include/versband_hip.h), stated here first so that
+        the error names the caller's argument.  Returns (struct, the array to hold)."""
+        if torch.is_tensor(windows):
+            windows = windows.tolist()
+        try:
+            starts = list(windows)
+        except TypeError:
+            raise TypeError(f"windows must be a sequence of window starts, got {type(windows).__name__}") from None
+        if any(isinstance(s, bool) or not isinstance(s, (int, np.integer)) for s in starts):
+            raise TypeError("windows must hold integers (the window starts)")
+        starts = [int(s) for s in starts]
+        nw = len(starts)
+        if not 1 <= nw <= 64:
+            raise ValueError(f"windows: {nw} windows (1..64)")
+        if B % nw:
+            raise ValueError(f"windows: {B} rows are not {nw} windows of whole clips (B % nw != 0)")
+        if starts[0] < 0:
+            raise ValueError(f"windows: window 0 starts at {starts[0]}")
+        for w in range(nw - 1):
+            if starts[w + 1] <= starts[w]:
+                raise ValueError(f"windows: window {w + 1} at {starts[w + 1]} does not come after window {w} at {starts[w]} (descending starts)")
+            if starts[w + 1] > starts[w] + T:
+                raise ValueError(f"windows: a gap between window {w} at {starts[w]} (length {T}) and window {w + 1} at {starts[w + 1]}")
+            if w + 2 < nw and starts[w + 2] < starts[w] + T:
+                raise ValueError(f"windows: window {w + 2} at {starts[w + 2]} reaches into window {w} at {starts[w]} (length {T}): "
+                                 "a token under three windows")
+        arr = (C.c_int32 * nw)(*starts)
+        return L.Windows(arr, nw), arr
+
     def sample_cfg(self, x0: Tensor, cond: dict, t_idx_table: Sequence[int], dt_table: Sequence[float], scale,
-                   noise=None, seed: int = 0, clip_base: int = 0, return_traj: bool = False, keep=None, clip_ids=None):
+                   noise=None, seed: int = 0, clip_base: int = 0, return_traj: bool = False, keep=None, clip_ids=None, windows=None):
         """n Euler steps with classifier-free guidance; x0 [B,C,T] is not modified.
         scale: one number for the batch, or B values (sequence / float32 tensor): row b is guided by scale[b].  clip_ids: B global clip
         indices (sequence / int64 tensor): row b draws its router noise as clip clip_ids[b] instead of clip_base + b (vb_sample_cfg_rows).
         keep = (ref [B,C,T], x0 [B,C,T], mask [B,T] in [0,1], t_next [n], sigma_min) or a dict of those names holds the masked tokens on
-        the probability path t ref + (1 - (1 - sigma_min) t) x0 after every step (vb_sample_cfg_keep; t_next = model.euler_times)."""
+        the probability path t ref + (1 - (1 - sigma_min) t) x0 after every step (vb_sample_cfg_keep; t_next = model.euler_times).
+        windows: a sequence of nw ascending window starts - the B rows are then nw windows (row = w * (B // nw) + b, T tokens each) of
+        B // nw long clips, and after every step the overlapping tokens of neighbouring windows take one consensus value, so they are
+        bit-identical in the result and in every trajectory state (vb_sample_cfg_windows).  Combines with all of the above; scale,
+        clip_ids and keep stay per ROW."""
         dev = self.ctx.device
         B, nb, T, Lc = cond["B"], cond["nb"], cond["T"], cond["L"]
+        wstruct, held_win = self._windows_struct(windows, B, T) if windows is not None else (None, None)
         rs, scale, held_rows = self._rows_struct(scale, clip_ids, B, clip_base)
         self._check_cond(cond)
         xkey = (B, self.cfg.in_channels, T)
@@ -313,7 +350,13 @@ class DiTEngine:
         traj = torch.empty(n + 1, *x.shape, dtype=torch.float32, device=dev) if return_traj else None
         ns, held = self._noise_struct(noise, seed, clip_base, 0)
         ws = self._workspace(B, nb, T, Lc)
-        if rs is not None:
+        if wstruct is not None:
+            ks, held_keep = self._keep_struct(keep, B, T, n) if keep is not None else (None, None)
+            L.check(self.ctx.lib.vb_sample_cfg_windows(self.ctx.handle, L.ptr(x), L.ptr(cond["buf"]), B, nb, T, Lc, n, L.ptr(tt), L.ptr(dd),
+                                                       float(scale), C.byref(wstruct), C.byref(rs) if rs is not None else None,
+                                                       C.byref(ks) if ks is not None else None, C.byref(ns), L.ptr(traj), L.ptr(ws),
+                                                       L.stream_ptr()), "vb_sample_cfg_windows")
+        elif rs is not None:
             ks, held_keep = self._keep_struct(keep, B, T, n) if keep is not None else (None, None)
             L.check(self.ctx.lib.vb_sample_cfg_rows(self.ctx.handle, L.ptr(x), L.ptr(cond["buf"]), B, nb, T, Lc, n, L.ptr(tt), L.ptr(dd),
                                                     float(scale), C.byref(rs), C.byref(ks) if ks is not None else None, C.byref(ns),

@@ -5,10 +5,13 @@ The reference cannot go past max_len = 1500 latent tokens (40 s): its RoPE table
 (SURVEY Q14).  Here a long clip is cut into windows of <= max_len latent tokens that overlap by
 `overlap` tokens; every window is an independent "clip" for the sampler (own slice of the midi/beats
 tracks, same caption, own slice of the start noise), so all windows of all clips run as ONE batch
-through vb_sample_cfg.  Window latents are cross-faded linearly over the overlaps.  The VAE decoder is
+through vb_sample_cfg.  Window latents are cross-faded linearly over the overlaps.
 (sample_long(mode="continue") gives up that batching for coherence: the windows of a clip are sampled in order and each holds its
 overlap with the previous one on the model's probability path - vb_sample_cfg_keep - so the new tokens are generated in agreement with
-the music that is already there, and the windows are stitched without a cross-fade.)  The VAE decoder is
+the music that is already there, and the windows are stitched without a cross-fade.  sample_long(mode="joint") keeps the one batched
+call AND is coherent: after every Euler step the overlapping tokens of neighbouring windows are reconciled to one consensus value -
+vb_sample_cfg_windows - so every window sees in its overlap the state its neighbour sees, the windows agree bit for bit where they
+overlap, and the stitch is plain slicing.)  The VAE decoder is
 applied to the whole latent (it is length-agnostic), the HiFi-GAN - fully convolutional - is run in
 chunks with a halo larger than its receptive field and the chunks are stitched (overlap-discard), which
 reproduces whole-clip vocoding exactly.
@@ -91,10 +94,14 @@ def sample_long(engine, x0: Tensor, t5_cond: Tensor, t5_uncond: Tensor, midi: Te
     """x0 [B,C,T], t5_* [B,L,1024], midi/beats [B,1,2T] -> z [B,C,T] for T beyond the DiT's max_len.
     mode "crossfade" (default): all windows as one batch of independent clips, latents cross-faded over the overlaps.
     mode "continue": windows in order, each with its overlap held on the probability path of the previous window's result (needs
-    t_next = model.euler_times of the same grid as the step tables, and the model's sigma_min); no cross-fade.  return_windows (continue
-    mode only) also returns every window's full result, overlaps included: (z, [z_w [B,C,n]])."""
-    if mode not in ("crossfade", "continue"):
-        raise ValueError(f"sample_long: mode {mode!r} (crossfade | continue)")
+    t_next = model.euler_times of the same grid as the step tables, and the model's sigma_min); no cross-fade.
+    mode "joint": all windows as one batch, like "crossfade", with the overlapping tokens of neighbouring windows reconciled to one
+    consensus value after every step (engine.sample_cfg(windows=...)); the windows agree bit for bit in their overlaps, no cross-fade.
+    (A plan whose shifted last window starts before the end of the window two before it puts a token under three windows and is
+    refused by the engine's validation.)
+    return_windows (continue and joint modes) also returns every window's full result, overlaps included: (z, [z_w [B,C,n]])."""
+    if mode not in ("crossfade", "continue", "joint"):
+        raise ValueError(f"sample_long: mode {mode!r} (crossfade | continue | joint)")
     B, C, T = x0.shape
     window = min(window, engine.cfg.max_len)
     plan = plan_windows(T, window, overlap)
@@ -107,8 +114,8 @@ def sample_long(engine, x0: Tensor, t5_cond: Tensor, t5_uncond: Tensor, midi: Te
         pad = 2 * T - midi.shape[1]
         midi = torch.cat([midi, midi[:, -1:].expand(B, pad)], dim=1)
         beats = torch.cat([beats, beats[:, -1:].expand(B, pad)], dim=1)
-    if return_windows and mode != "continue":
-        raise ValueError("sample_long: return_windows belongs to mode=\"continue\"")
+    if return_windows and mode == "crossfade":
+        raise ValueError("sample_long: return_windows belongs to mode=\"continue\" and mode=\"joint\"")
     if mode == "continue":
         if t_next is None:
             raise ValueError('sample_long(mode="continue") needs t_next (model.euler_times of the step tables\' grid)')
@@ -120,6 +127,17 @@ def sample_long(engine, x0: Tensor, t5_cond: Tensor, t5_uncond: Tensor, midi: Te
     bw = torch.cat([beats[:, 2 * s:2 * (s + n)] for s, _ in plan], dim=0)
     t5 = torch.cat([t5_cond.repeat(nw, 1, 1), t5_uncond.repeat(nw, 1, 1)], dim=0)
     cond = engine.precompute_cond(t5, mw, bw, n, persistent=True)
+    if mode == "joint":
+        if nw == 1:           # T <= window: the plain call
+            zw = engine.sample_cfg(xw, cond, t_idx_table, dt_table, scale, seed=seed, clip_base=clip_base * nw)
+            return (zw, [zw]) if return_windows else zw
+        zw = engine.sample_cfg(xw, cond, t_idx_table, dt_table, scale, seed=seed, clip_base=clip_base * nw, windows=[s for s, _ in plan])
+        parts = [zw[w * B:(w + 1) * B] for w in range(nw)]
+        # every token from exactly one window (plan_continue); the overlaps hold the same bits in both, so there is nothing to fade
+        out = torch.empty(B, C, T, dtype=zw.dtype, device=zw.device)
+        for (s, m, known), p in zip(plan_continue(plan), parts):
+            out[:, :, s + known:s + m] = p[:, :, known:]
+        return (out, parts) if return_windows else out
     zw = engine.sample_cfg(xw, cond, t_idx_table, dt_table, scale, seed=seed, clip_base=clip_base * nw)
     if nw == 1:
         return zw
