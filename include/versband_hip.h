@@ -251,7 +251,8 @@ int vb_sample_graphs(vb_ctx* ctx);
  * HifiGanGenerator.forward (vocoder/hifigan/modules/hifigan.py:126-143) both run as a flat op
  * list over fp32 [B][C][T] buffers; the list is built from the model config by the host side. */
 typedef struct { int channels; int tmul; int square; } vb_buf_desc;   /* square: 1 = [T*tmul]^2 floats, 2 = channels x roundup(T*tmul, 32),
-                                                                         3 = channels x (T*tmul + 448) (transposed planes with halo) */
+                                                                         3 = channels x (T*tmul + 448) floats (two transposed bf16 planes with halo),
+                                                                         4 = half of that (ONE transposed bf16 plane with halo) */
 /* VB_OP_SPLIT_PLANES: x (f32 [B][rows][cols], rows = Co, cols = Ci, -1 = the buffer's time length) -> out = split-bf16
  * planes [2][B][rows][roundup(cols, 32)]; a later VB_OP_CONV with w_buf = that buffer and wfmt = VB_WFMT_BUF_X3 uses them as
  * per-batch weights on the bf16x3 kernel (the VAE decoder's single-head attention) */
@@ -262,7 +263,9 @@ typedef struct { int channels; int tmul; int square; } vb_buf_desc;   /* square:
 /* VB_OP_AA_ACT: BigVGAN anti-aliased Snake / SnakeBeta (vocoder/bigvgan/alias_free_torch/act.py): out = down2(snake(up2(x))), Ci channels,
  * gn_gamma = alpha (exp'ed when log-scale), gn_beta = 1 / (beta + 1e-9), w = the 12-tap Kaiser-sinc filter */
 /* VB_OP_XT_PLANES: x (f32 [B][Ci][T]) -> out = pre-activated (in_act with `stats` / gn_gamma / gn_beta / in_slope), nearest-x2
- * upsampled (upsample2), split-bf16 TRANSPOSED planes with zero halo rows; a VB_OP_CONV with x_planes = 1 reads them by DMA */
+ * upsampled (upsample2), split-bf16 TRANSPOSED planes [2][B][T + 448][Ci] with zero halo rows (out: a buffer of square = 3); a VB_OP_CONV
+ * with x_planes = 1 reads them by DMA.  wfmt = VB_WFMT_BF16: the one-plane form - only the round-to-nearest plane [B][T + 448][Ci], plane 0
+ * of the split form bit for bit (out: a buffer of square = 4) - which a BF16 VB_OP_CONV with x_planes = 1 reads */
 enum { VB_OP_CONV = 0, VB_OP_GN_STATS = 1, VB_OP_SOFTMAX_T = 2, VB_OP_SPLIT_PLANES = 3, VB_OP_RESPAIR = 4, VB_OP_GN_APPLY = 5, VB_OP_AA_ACT = 6,
        VB_OP_XT_PLANES = 7 };
 enum { VB_ACT_NONE = 0, VB_ACT_LRELU = 1, VB_ACT_GN_SWISH = 2, VB_ACT_TANH = 3, VB_ACT_GN = 4 };
@@ -286,12 +289,19 @@ enum { VB_ACT_NONE = 0, VB_ACT_LRELU = 1, VB_ACT_GN_SWISH = 2, VB_ACT_TANH = 3, 
  *   CONV     BF16     w_x3, ci_pad, w (Co = 1 only)  conv1d_bf16_kernel (one plane [phase][tap][Co][ci_pad]); w feeds the one-output-channel kernel
  *   RESPAIR  BF16     w_x3, ci_pad, w2, bias, bias2  respair_bf16_kernel (one plane [k][C][C] each), C = 32 / 64
  *   AA_ACT   NONE     w (the filter)
+ *   XT_PLANES NONE    -                              split planes (two) for an X3 CONV with x_planes = 1
+ *   XT_PLANES BF16    -                              ONE plane for a BF16 CONV with x_planes = 1 (the "bf16xt" op list)
  *   other    NONE     -
  * BF16 is the single-pass bf16 mode: every product is RN_bf16(weight) * RN_bf16(activated input), accumulated in fp32 - outside the 1e-3
  * parity contract by design (see vb_conv1d_bf16).  A BF16 CONV carries w exactly when Co == 1; a BF16 RESPAIR with C outside 32 / 64 is refused.
  * It also refuses an X3 / BF16 op whose ci_pad is not Ci rounded up to 32, MF weights that are not 16-byte aligned, and a RESPAIR without
  * Ci == Co or whose x / out differ in time length (buffer tmul; in_tmul / out_tmul for the I/O ids).  The failing op's index is in
- * vb_last_error().  Conditions that depend on T or on buffer addresses are checked when the op runs. */
+ * vb_last_error().  Input planes must match the reader: XT_PLANES NONE writes a buffer of square = 3 and XT_PLANES BF16 one of square = 4;
+ * a CONV with x_planes = 1 is X3 over a square = 3 buffer or BF16 over a square = 4 buffer - a split buffer into a BF16 conv, a one-plane
+ * buffer into an X3 conv, x_planes with any other format, and a one-plane buffer into a BF16 conv of one output channel (the fp32
+ * one-output-channel kernel reads no planes) are refused.  A BF16 CONV over planes runs as a one-pass GEMM on the DMA-fed 128 x 128 kernel
+ * where the layer qualifies (Co >= 384, Ci % 64 == 0, plain channel-major output) and on conv1d_bf16_kernel's DMA-fed input mode otherwise
+ * (VB_CONV_GEMM_OFF=1: always).  Conditions that depend on T or on buffer addresses are checked when the op runs. */
 enum { VB_WFMT_NONE = 0, VB_WFMT_F32 = 1, VB_WFMT_X3 = 2, VB_WFMT_MF = 3, VB_WFMT_BUF_F32 = 4, VB_WFMT_BUF_X3 = 5, VB_WFMT_BF16 = 6 };
 #define VB_BUF_INPUT (-2)
 #define VB_BUF_OUTPUT (-3)
@@ -435,6 +445,24 @@ int vb_conv1d_bf16(const float* x, const void* w_bf16, int ci_pad, const float* 
                    int pad, int tr_stride, int tr_pad, int tr_k, int T_out, int upsample2, int in_stride, int in_phase, int in_act,
                    float in_slope, const float* gn_mean, const float* gn_rstd, const float* gn_gamma, const float* gn_beta, int gn_groups,
                    const float* res, float alpha, float beta, float* out, void* stream);
+/* The same convolution over a pre-activated plane, the wide-layer route of the "bf16xt" precision (stride 1 only: tr_stride <= 1,
+ * in_stride <= 1): first the planes pre-pass (VB_OP_XT_PLANES, one-plane form) writes RN_bf16(act_in(x)), nearest-x2 upsampled when
+ * upsample2, transposed with zero halo rows into planes_scratch (vb_conv1d_bf16_xt_scratch_bytes bytes, 16-byte aligned); then the
+ * convolution reads that plane by DMA - as a one-pass GEMM (Co >= 384, Ci % 64 == 0, alpha == 1, beta == 0) or on conv1d_bf16_kernel's
+ * DMA-fed input mode (anything else with Co > 64 and Ci % 32 == 0; VB_CONV_GEMM_OFF=1: always).  Same arithmetic definition as
+ * vb_conv1d_bf16: the routes differ by where the activation is applied and by accumulation order only.  Hosts detect the "bf16xt"
+ * precision by the presence of this symbol (vb_abi_version() stays 3). */
+size_t vb_conv1d_bf16_xt_scratch_bytes(int B, int Ci, int T_in, int upsample2);
+int vb_conv1d_bf16_xt(const float* x, const void* w_bf16, int ci_pad, const float* bias, int B, int Ci, int T_in, int Co, int ksize, int dil,
+                      int pad, int tr_stride, int tr_pad, int tr_k, int T_out, int upsample2, int in_stride, int in_phase, int in_act,
+                      float in_slope, const float* gn_mean, const float* gn_rstd, const float* gn_gamma, const float* gn_beta, int gn_groups,
+                      const float* res, float alpha, float beta, float* out, void* planes_scratch, void* stream);
+/* The planes pre-pass alone: x f32 [B][C][T_in] -> planes [nplanes][B][T_eff + 448][C] bf16 (T_eff = 2 T_in when upsample2), 64 zero rows
+ * in front of every clip and 384 behind; nplanes = 2: round-to-nearest value and its rounding residual, 1: the value alone (bit-equal to
+ * plane 0 of the two-plane form).  C % 16 == 0; planes 16-byte aligned, vb_xt_planes_bytes bytes. */
+size_t vb_xt_planes_bytes(int B, int C, int T_in, int upsample2, int nplanes);
+int vb_xt_planes(const float* x, int B, int C, int T_in, int upsample2, int in_act, float in_slope, const float* gn_mean, const float* gn_rstd,
+                 const float* gn_gamma, const float* gn_beta, int gn_groups, int nplanes, void* planes, void* stream);
 /* HiFi-GAN ResBlock1 pair in single-pass bf16, one launch (respair_bf16.hip):
  *   out = beta*out + alpha*(x + b2 + conv2_{k,1}( RN_bf16( lrelu(b1 + conv1_{k,dil}( RN_bf16(lrelu(x)) )) ) ))
  * both convolutions with RN-bf16 weights (w1_bf16 / w2_bf16: one plane [k][C co][C ci] each, pack.py:pack_conv_bf16), exact products, fp32

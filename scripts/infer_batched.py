@@ -34,7 +34,7 @@ from versband_amd.model import normalize_loudness  # noqa: E402
 def parse_args(argv=None):
     """--items_per_batch, --synthetic_frames and --vocoder_precision are taken out of the command line here; every other flag goes through
     test_final.py's own parser (which reads sys.argv and is not ours to change: it sees the remaining arguments for the length of its call).
-    --vocoder_precision is that parser's flag with one more choice, "bf16", the preview mode only this CLI offers."""
+    --vocoder_precision is that parser's flag with two more choices, "bf16" and "bf16xt", the preview modes only this CLI offers."""
     from unittest import mock
     own = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
     own.add_argument("--items_per_batch", type=int, default=1,
@@ -43,9 +43,10 @@ def parse_args(argv=None):
                           "(default 1: that loop's calls).  items x guided scales x n_samples may not exceed 32 rows")
     own.add_argument("--synthetic_frames", type=str, default="1500",
                      help="mel frames of a synthetic item: one integer, or a comma list that cycles over the items (150,150,230)")
-    own.add_argument("--vocoder_precision", type=str, default="fp32mf", choices=["fp32mf", "fp32", "split", "bf16"],
+    own.add_argument("--vocoder_precision", type=str, default="fp32mf", choices=["fp32mf", "fp32", "split", "bf16", "bf16xt"],
                      help="VAE + vocoder arithmetic: test_final.py's fp32mf (default) / fp32 / split, and bf16 = ONE bf16 pass per convolution (bf16 "
-                          "operands, fp32 accumulation): preview quality, outside the 1e-3 parity bound")
+                          "operands, fp32 accumulation): preview quality, outside the 1e-3 parity bound; bf16xt = the same arithmetic with the wide "
+                          "layers' inputs activated once into a bf16 plane and multiplied as DMA-fed GEMMs")
     argv = list(sys.argv[1:] if argv is None else argv)
     if "-h" in argv or "--help" in argv:
         own.print_help()

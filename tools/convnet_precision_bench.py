@@ -14,7 +14,7 @@ from versband_amd.engine import Context, build_hifigan, build_vae_decoder  # noq
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 ROUNDS = int(sys.argv[2]) if len(sys.argv) > 2 else 7
-MODES = ("bf16", "split", "fp32mf")
+MODES = ("bf16", "bf16xt", "split", "fp32mf")
 T_LAT = 752
 ctx = Context("cuda:0")
 vcfg, hcfg = synth.VAEConfig(), synth.HifiGanConfig()
@@ -52,8 +52,12 @@ for r in range(ROUNDS):
 res = {"clips": B, "rounds": ROUNDS}
 for m in MODES:
     res[m] = {"vae_ms": round(statistics.median(v for v, _ in ms[m]), 3), "vocoder_ms": round(statistics.median(h for _, h in ms[m]), 3),
+              "vae_ms_min_max": [round(min(v for v, _ in ms[m]), 3), round(max(v for v, _ in ms[m]), 3)],
+              "vocoder_ms_min_max": [round(min(h for _, h in ms[m]), 3), round(max(h for _, h in ms[m]), 3)],
               "pass_ms": round(statistics.median(v + h for v, h in ms[m]), 3),
               "pass_ms_min_max": [round(min(v + h for v, h in ms[m]), 3), round(max(v + h for v, h in ms[m]), 3)]}
 res["bf16_over_split"] = round(res["bf16"]["pass_ms"] / res["split"]["pass_ms"], 4)
+res["bf16xt_vae_over_bf16_vae"] = round(res["bf16xt"]["vae_ms"] / res["bf16"]["vae_ms"], 4)
+res["bf16xt_vae_over_split_vae"] = round(res["bf16xt"]["vae_ms"] / res["split"]["vae_ms"], 4)
 res["bf16_over_fp32mf"] = round(res["bf16"]["pass_ms"] / res["fp32mf"]["pass_ms"], 4)
 print(json.dumps(res))

@@ -150,6 +150,11 @@ PROTOTYPES = {
     "vb_respair_f32": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, P, P]),
     "vb_conv1d_bf16": (c_int, [P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                c_int, c_float, P, P, P, P, c_int, P, c_float, c_float, P, P]),
+    "vb_conv1d_bf16_xt_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "vb_conv1d_bf16_xt": (c_int, [P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                  c_int, c_float, P, P, P, P, c_int, P, c_float, c_float, P, P, P]),
+    "vb_xt_planes_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "vb_xt_planes": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_float, P, P, P, P, c_int, c_int, P, P]),
     "vb_respair_bf16": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, P, P]),
     "vb_fill_gumbel": (c_int, [P, c_int, c_int, c_int, c_int, c_u64, c_i64, c_int, c_int, c_int, P]),
     "vb_cast_planes": (c_int, [P, c_i64, P, c_int, P]),

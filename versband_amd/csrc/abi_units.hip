@@ -104,6 +104,35 @@ int vb_conv1d_bf16(const float* x, const void* w_bf16, int ci_pad, const float* 
     a.alpha = alpha; a.beta = beta; a.tr_stride = tr_stride; a.tr_pad = tr_pad; a.tr_k = tr_k;
     return launch_conv1d(a, (hipStream_t)stream);
 }
+size_t vb_xt_planes_bytes(int B, int C, int T_in, int upsample2, int nplanes) {
+    if (B < 1 || C < 1 || T_in < 1 || (nplanes != 1 && nplanes != 2)) return 0;
+    return (size_t)nplanes * B * xt_rows(upsample2 ? 2 * T_in : T_in) * C * sizeof(bf16_t);
+}
+int vb_xt_planes(const float* x, int B, int C, int T_in, int upsample2, int in_act, float in_slope, const float* gn_mean, const float* gn_rstd,
+                 const float* gn_gamma, const float* gn_beta, int gn_groups, int nplanes, void* planes, void* stream) {
+    if (!x || !planes || B < 1 || C < 1 || T_in < 1) VB_FAIL(VB_E_INVALID, "xt_planes: null pointer or B/C/T < 1");
+    return launch_xt_planes(x, gn_mean, gn_rstd, gn_gamma, gn_beta, gn_groups, in_act, in_slope, upsample2, B, C, T_in, nplanes, (bf16_t*)planes,
+                            (hipStream_t)stream);
+}
+size_t vb_conv1d_bf16_xt_scratch_bytes(int B, int Ci, int T_in, int upsample2) { return vb_xt_planes_bytes(B, Ci, T_in, upsample2, 1); }
+int vb_conv1d_bf16_xt(const float* x, const void* w_bf16, int ci_pad, const float* bias, int B, int Ci, int T_in, int Co, int ksize, int dil,
+                      int pad, int tr_stride, int tr_pad, int tr_k, int T_out, int upsample2, int in_stride, int in_phase, int in_act,
+                      float in_slope, const float* gn_mean, const float* gn_rstd, const float* gn_gamma, const float* gn_beta, int gn_groups,
+                      const float* res, float alpha, float beta, float* out, void* planes_scratch, void* stream) {
+    if (!x || !w_bf16 || !out || !planes_scratch || B < 1 || T_in < 1 || T_out < 1 || Ci < 1 || Co < 1)
+        VB_FAIL(VB_E_INVALID, "conv1d_bf16_xt: null pointer or B/T/Ci/Co < 1");
+    if (tr_stride > 1 || in_stride > 1) VB_FAIL(VB_E_INVALID, "conv1d_bf16_xt: the planes feed stride-1 convolutions only");
+    hipStream_t st = (hipStream_t)stream;
+    VB_TRY(launch_xt_planes(x, gn_mean, gn_rstd, gn_gamma, gn_beta, gn_groups, in_act, in_slope, upsample2, B, Ci, T_in, 1, (bf16_t*)planes_scratch, st));
+    ConvArgs a;
+    a.wp = (const bf16_t*)w_bf16; a.Ci_pad = ci_pad; a.wp_bf16 = true;
+    a.xt = (const bf16_t*)planes_scratch; a.xt_np = 1;         // (the activation is in the plane: the convolution itself has none)
+    a.x = x; a.x_bstride = (int64_t)Ci * T_in; a.Ci = Ci; a.T_in = T_in; a.bias = bias; a.Co = Co; a.ksize = ksize;
+    a.dil = dil; a.pad = pad; a.upsample2 = upsample2;
+    a.out = out; a.out_bstride = (int64_t)Co * T_out; a.T_out = T_out; a.res = res; a.res_bstride = (int64_t)Co * T_out; a.B = B;
+    a.alpha = alpha; a.beta = beta; a.tr_stride = tr_stride; a.tr_pad = tr_pad; a.tr_k = tr_k;
+    return launch_conv1d(a, st);
+}
 int vb_respair_bf16(const float* x, const void* w1_bf16, const float* b1, const void* w2_bf16, const float* b2, int B, int C, int T, int k,
                     int dil, float slope, float alpha, float beta, float* out, void* stream) {
     if (!x || !w1_bf16 || !b1 || !w2_bf16 || !b2 || !out || B < 1 || T < 1) VB_FAIL(VB_E_INVALID, "respair_bf16: null pointer or B/T < 1");

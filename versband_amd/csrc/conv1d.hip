@@ -18,9 +18,14 @@ static int conv1d_fill(const ConvArgs& a, ConvDev& d, int& n_count) {
     d.out_transposed = a.out_transposed; d.add = a.add; d.add_bstride = a.add_bstride; d.add_bmod = a.add_bmod;
     d.wp = a.wp; d.wp_plane = a.wp_plane; d.Ci_pad = a.Ci_pad; d.wp_bstride = a.wp_bstride;
     d.xt = a.xt; d.xt_Tp = xt_rows(a.upsample2 ? 2 * a.T_in : a.T_in); d.xt_plane = (int64_t)a.B * d.xt_Tp * a.Ci;
-    if (a.wp_bf16 && (!a.wp || a.xt || a.wp_bstride || a.w_mf)) VB_FAIL(VB_E_INVALID, "conv1d: bf16 weights are one shared plane (no XT input, no per-clip or minimal-filtering weights)");
+    if (a.wp_bf16 && (!a.wp || a.wp_bstride || a.w_mf)) VB_FAIL(VB_E_INVALID, "conv1d: bf16 weights are one shared plane (no per-clip or minimal-filtering weights)");
     if (a.xt && (a.Ci % 32 || a.tr_stride > 1 || a.in_stride > 1 || !a.wp || a.x_bmod || a.pad > XT_HEAD))
         VB_FAIL(VB_E_INVALID, "conv1d: XT input needs Ci %% 32 == 0, stride 1, split weights, pad <= %d", XT_HEAD);
+    if (a.xt && a.xt_np != (a.wp_bf16 ? 1 : 2))
+        VB_FAIL(VB_E_INVALID, "conv1d: XT input of %d plane(s): bf16 weights read a one-plane buffer, split weights a two-plane one", a.xt_np);
+    // (the DMA'd windows of the last time tile reach at most 64 + 256 rows past row T_out of the padded image: inside its XT_TAIL zero rows)
+    if (a.xt && a.T_out > (a.upsample2 ? 2 * a.T_in : a.T_in) + XT_HEAD)
+        VB_FAIL(VB_E_INVALID, "conv1d: XT input of %d positions cannot feed %d outputs", a.upsample2 ? 2 * a.T_in : a.T_in, a.T_out);
     d.stage_epi = 0;
     if (a.tr_stride > 1) {
         d.phases = a.tr_stride; d.tr_pad = a.tr_pad; d.ntaps = (a.tr_k + a.tr_stride - 1) / a.tr_stride; d.dil = 1;
@@ -36,8 +41,12 @@ static int conv1d_fill(const ConvArgs& a, ConvDev& d, int& n_count) {
 }
 
 // Wide layers over pre-activated transposed planes ARE GEMMs (rows = clip x time, K = taps x Ci, both operands K-contiguous
-// already): the DMA-fed 128 x 128 GEMM kernel walks K tap by tap (GemmArgs::conv_*), three bf16 passes for the split precision,
-// bias + residual in a channel-major epilogue.  Measured on these shapes (tools/conv_as_gemm_calib.py): 750-840 TFLOP/s of bf16
+// already): the DMA-fed 128 x 128 GEMM kernel walks K tap by tap (GemmArgs::conv_*), three bf16 passes for the split precision, one
+// (nseg = 1: the one activation plane against the one weight plane [tap][Co][Ci_pad], plane 0 of the split packing, so the tap stride is
+// the same) for bf16 weights; bias + residual in a channel-major epilogue.  The tap walk at one segment: gemm_k_offsets takes step t as
+// (seg, kt) = (t / KT, t % KT) with KT = taps * Ci / 64 - seg stays 0, no plane offset is ever added, and the ring's stage index t % NST and
+// its counted waits depend on the step count alone (the prologues of both DMA kernels guard total < ring depth: K = 64 is one step).
+// launch_gemm's conv-mode tile choice does not look at K (gemm_route's last rule): 128 x 128, or 64 x 64 under 200 workgroups, as for split.  Measured on these shapes (tools/conv_as_gemm_calib.py): 750-840 TFLOP/s of bf16
 // MFMA work against ~385 of conv1d_x3_kernel, which stages weights through registers and synchronises per (tap, 32 channels).
 // (B * T_out / Co beyond launch_gemm's reciprocal-divide range fall through to the conv kernels - ADVICE r3)
 static bool conv1d_as_gemm_eligible(const ConvArgs& a, const ConvDev& d) {
@@ -49,7 +58,7 @@ static bool conv1d_as_gemm_eligible(const ConvArgs& a, const ConvDev& d) {
 static int launch_conv1d_as_gemm(const ConvArgs& a, const ConvDev& d, hipStream_t st) {
     GemmArgs g;
     g.A = a.xt; g.a_plane = d.xt_plane; g.lda = a.Ci; g.B = a.wp; g.b_plane = a.wp_plane; g.ldb = a.Ci_pad;
-    g.M = a.B * a.T_out; g.N = a.Co; g.K = d.ntaps * a.Ci; g.nseg = 3; g.ngroups = a.B;
+    g.M = a.B * a.T_out; g.N = a.Co; g.K = d.ntaps * a.Ci; g.nseg = a.wp_bf16 ? 1 : 3; g.ngroups = a.B;
     g.group_rows = a.T_out; g.T = a.T_out; g.epi = EPI_F32_CT; g.bias = a.bias; g.out32 = a.out; g.res32 = a.res;
     g.conv_ci = a.Ci; g.conv_dil = d.dil; g.conv_agrp = d.xt_Tp; g.conv_arow0 = XT_HEAD - a.pad; g.conv_btap = (int64_t)a.Co * a.Ci_pad;
     g.prof_class = 2;
@@ -62,13 +71,13 @@ static bool conv1d_stage_epi_eligible(const ConvArgs& a) {
 }
 // conv1d_co1_kernel: one output channel of an ordinary stride-1 convolution, shared fp32 weights, input transform none / LeakyReLU
 static bool conv1d_co1_eligible(const ConvArgs& a, const ConvDev& d) {
-    return a.Co == 1 && a.w && !a.w_bstride && !a.x_bmod && d.phases == 1 && d.in_stride == 1 && !a.upsample2 && !a.out_transposed &&
+    return a.Co == 1 && a.w && !a.xt && !a.w_bstride && !a.x_bmod && d.phases == 1 && d.in_stride == 1 && !a.upsample2 && !a.out_transposed &&
            (a.in_act == ACT_NONE || a.in_act == ACT_LRELU);
 }
 // conv1d_x3_kernel: split-bf16 weights are there - and per clip where the fp32 ones are
 static bool conv1d_x3_eligible(const ConvArgs& a) { return a.wp && (!a.w_bstride || a.wp_bstride); }
 
-enum ConvRoute { CONV_AS_GEMM, CONV_F32W, CONV_CO1, CONV_BF16, CONV_X3_XT, CONV_X3, CONV_F32G, CONV_F32 };
+enum ConvRoute { CONV_AS_GEMM, CONV_F32W, CONV_CO1, CONV_BF16_XT, CONV_BF16, CONV_X3_XT, CONV_X3, CONV_F32G, CONV_F32 };
 // Which kernel runs: the first candidate, in this order, whose conditions hold and whose A/B knob has not switched it off; the register-staged
 // fp32 kernel takes everything.  Settles d.stage_epi on the way (VB_CONV_DIRECT_EPI=1: the direct epilogue - no minimal filtering then).
 static ConvRoute conv1d_route(const ConvArgs& a, ConvDev& d) {
@@ -77,7 +86,7 @@ static ConvRoute conv1d_route(const ConvArgs& a, ConvDev& d) {
     d.stage_epi = (conv1d_stage_epi_eligible(a) && !tune.conv_direct_epi) ? 1 : 0;
     if (conv1d_f32w_eligible(a, d) && !tune.conv_mf_off) return CONV_F32W;
     if (conv1d_co1_eligible(a, d) && !tune.conv_f32_old) return CONV_CO1;             // (VB_CONV_F32_OLD=1: the MFMA kernels)
-    if (a.wp_bf16) return CONV_BF16;                                                  // one weight plane: no other kernel reads it
+    if (a.wp_bf16) return a.xt ? CONV_BF16_XT : CONV_BF16;                            // one weight plane: no other kernel reads it
     if (conv1d_x3_eligible(a)) return a.xt ? CONV_X3_XT : CONV_X3;
     // exact fp32, DMA-fed; VB_CONV_F32_OLD=1 keeps the register-staged kernel (bit-identical, tests compare the two)
     if (conv1d_f32g_eligible(a, d) && !tune.conv_f32_old) return CONV_F32G;
@@ -99,7 +108,8 @@ int launch_conv1d(const ConvArgs& a, hipStream_t st) {
         case CONV_AS_GEMM: break;      // (left above)
         case CONV_F32W: d.ww = a.w_mf; launch_conv1d_f32w(d, a.B, st); break;
         case CONV_CO1: launch_conv1d_co1(d, a.B, st); break;
-        case CONV_BF16: VB_TRY(launch_conv1d_bf16(d, conv_staged_tile(a.Co, n_count, a.B, d.phases), n_count, a.B, st)); break;
+        case CONV_BF16_XT:
+        case CONV_BF16: VB_TRY(launch_conv1d_bf16(d, conv_staged_tile(a.Co, n_count, a.B, d.phases), n_count, a.B, route == CONV_BF16_XT, st)); break;
         case CONV_X3_XT:
         case CONV_X3: VB_TRY(launch_conv1d_x3(d, conv_staged_tile(a.Co, n_count, a.B, d.phases), n_count, a.B, route == CONV_X3_XT, st)); break;
         case CONV_F32G: launch_conv1d_f32g(d, n_count, a.B, a.upsample2, st); break;

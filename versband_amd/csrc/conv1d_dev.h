@@ -218,5 +218,6 @@ void launch_conv1d_co1(const ConvDev& d, int B, hipStream_t st);
 enum ConvTileId { CONV_TILE_128x128, CONV_TILE_128x64, CONV_TILE_64x128, CONV_TILE_32x256 };
 // conv1d_x3.hip: split-bf16 (hi*hi + lo*hi + hi*lo, fp32-class); xt: the window comes from pre-activated transposed planes (d.xt)
 int launch_conv1d_x3(const ConvDev& d, ConvTileId tile, int n_count, int B, bool xt, hipStream_t st);
-// conv1d_bf16.hip: single-pass bf16 (RN-bf16 weights x RN-bf16 activated input, fp32 accumulation); d.wp = ONE plane [phase][tap][Co][Ci_pad]
-int launch_conv1d_bf16(const ConvDev& d, ConvTileId tile, int n_count, int B, hipStream_t st);
+// conv1d_bf16.hip: single-pass bf16 (RN-bf16 weights x RN-bf16 activated input, fp32 accumulation); d.wp = ONE plane [phase][tap][Co][Ci_pad];
+// xt: the window comes from the ONE pre-activated transposed plane d.xt (xt_planes_kernel<1>)
+int launch_conv1d_bf16(const ConvDev& d, ConvTileId tile, int n_count, int B, bool xt, hipStream_t st);

@@ -7,8 +7,10 @@ static size_t net_ws_bytes(const NetProgram& n, int B, int T, std::vector<size_t
     if (offs) offs->clear();
     for (const vb_buf_desc& d : n.bufs) {
         size_t tl = (size_t)T * d.tmul;
+        // (floats per clip; square 3 = two bf16 planes with halo rows, 4 = one: half as many floats, channels % 16 == 0)
         size_t el = d.square == 1 ? tl * tl : (d.square == 2 ? (size_t)d.channels * ((tl + 31) / 32 * 32)
-                                  : (d.square == 3 ? (size_t)d.channels * (tl + XT_HEAD + XT_TAIL) : (size_t)d.channels * tl));
+                                  : (d.square == 3 ? (size_t)d.channels * (tl + XT_HEAD + XT_TAIL)
+                                  : (d.square == 4 ? ((size_t)d.channels * (tl + XT_HEAD + XT_TAIL) + 1) / 2 : (size_t)d.channels * tl)));
         if (offs) offs->push_back(off);
         off = align_up(off + el * B * sizeof(float));
     }
@@ -53,6 +55,7 @@ int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, v
             if (o.x_planes) {
                 // input written by VB_OP_XT_PLANES: its buffer's time length is the (upsampled) length the planes were made for
                 a.xt = reinterpret_cast<const bf16_t*>(ptr(o.x));
+                a.xt_np = n.bufs[o.x].square == 4 ? 1 : 2;       // (vb_net_load checked the buffer against the weight format)
                 a.T_in = o.upsample2 ? tlen(o.x) / 2 : tlen(o.x);
             }
             a.Ci = o.Ci > 0 ? o.Ci : tlen(o.x);            // dynamic channel counts: the VAE attention contracts over T
@@ -100,7 +103,7 @@ int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, v
         } else if (o.kind == VB_OP_XT_PLANES) {
             const float* stp = o.stats >= 0 ? ptr(o.stats) : nullptr;
             VB_TRY(launch_xt_planes(ptr(o.x), stp, stp ? stp + (size_t)B * o.gn_groups : nullptr, o.gn_gamma, o.gn_beta, o.gn_groups, o.in_act, o.in_slope,
-                                    o.upsample2, B, o.Ci, tlen(o.x), reinterpret_cast<bf16_t*>(ptr(o.out)), st));
+                                    o.upsample2, B, o.Ci, tlen(o.x), o.wfmt == VB_WFMT_BF16 ? 1 : 2, reinterpret_cast<bf16_t*>(ptr(o.out)), st));
         } else if (o.kind == VB_OP_AA_ACT) {
             VB_TRY(launch_aa_act(ptr(o.x), o.gn_gamma, o.gn_beta, o.w, B, o.Ci, tlen(o.x), ptr(o.out), st));
         } else if (o.kind == VB_OP_RESPAIR) {
@@ -152,7 +155,8 @@ static int net_op_fields(int kind, int wfmt, int Co) {
         }
         return -1;
     case VB_OP_AA_ACT: return wfmt == VB_WFMT_NONE ? NW_W : -1;
-    case VB_OP_GN_STATS: case VB_OP_SOFTMAX_T: case VB_OP_SPLIT_PLANES: case VB_OP_GN_APPLY: case VB_OP_XT_PLANES:
+    case VB_OP_XT_PLANES: return wfmt == VB_WFMT_NONE || wfmt == VB_WFMT_BF16 ? 0 : -1;      // (BF16: the one-plane form; no weights either way)
+    case VB_OP_GN_STATS: case VB_OP_SOFTMAX_T: case VB_OP_SPLIT_PLANES: case VB_OP_GN_APPLY:
         return wfmt == VB_WFMT_NONE ? 0 : -1;
     }
     return -1;
@@ -178,10 +182,24 @@ int vb_net_load(vb_ctx* ctx, int which, const vb_net_op* ops, int n_ops, const v
             if (sl.set != ((f & sl.bit) != 0))
                 VB_FAIL(VB_E_INVALID, "net_load: op %d (kind %d, weight format %d): %s is %s", i, o.kind, o.wfmt, sl.name,
                         sl.set ? "set but not read" : "missing");
-        if ((o.wfmt == VB_WFMT_X3 || o.wfmt == VB_WFMT_BF16) && o.ci_pad != (o.Ci + 31) / 32 * 32)
+        if ((f & NW_X3) && o.ci_pad != (o.Ci + 31) / 32 * 32)       // (the ops that read w_x3; a BF16 XT_PLANES has no weights)
             VB_FAIL(VB_E_INVALID, "net_load: op %d: split weights padded to %d input channels, not %d rounded up to 32", i, o.ci_pad, o.Ci);
         if (o.wfmt == VB_WFMT_MF && (!aligned16(o.w_mf) || !aligned16(o.w2)))
             VB_FAIL(VB_E_INVALID, "net_load: op %d: minimal-filtering weights are not 16-byte aligned", i);
+        // DMA-fed input planes: the buffer holds as many planes as the reader's weight format multiplies (square 3 = two, 4 = one)
+        if (o.kind == VB_OP_XT_PLANES) {
+            const int want = o.wfmt == VB_WFMT_BF16 ? 4 : 3;
+            if (o.out < 0 || bufs[o.out].square != want)
+                VB_FAIL(VB_E_INVALID, "net_load: op %d: %s planes are written to a buffer of square = %d", i, want == 4 ? "one-plane (BF16)" : "split", want);
+        }
+        if (o.kind == VB_OP_CONV && o.x_planes) {
+            const int sq = o.x >= 0 ? bufs[o.x].square : 0;
+            if (o.wfmt == VB_WFMT_X3 ? sq != 3 : (o.wfmt == VB_WFMT_BF16 ? sq != 4 : true))
+                VB_FAIL(VB_E_INVALID, "net_load: op %d: x_planes with weight format %d reads a buffer of square = %d (X3: 3, split planes; BF16: 4, one plane)",
+                        i, o.wfmt, sq);
+            if (o.wfmt == VB_WFMT_BF16 && o.Co == 1)
+                VB_FAIL(VB_E_INVALID, "net_load: op %d: one output channel runs the fp32 one-output-channel kernel, which reads no planes", i);
+        }
         if (o.kind == VB_OP_RESPAIR) {
             if (!o.bias || !o.bias2) VB_FAIL(VB_E_INVALID, "net_load: op %d: respair without both biases", i);
             if (o.Ci != o.Co) VB_FAIL(VB_E_INVALID, "net_load: op %d: respair with Ci %d != Co %d", i, o.Ci, o.Co);

@@ -129,8 +129,9 @@ struct ConvArgs {
     int64_t wp_bstride = 0;          // per-batch split weights (bf16 elements inside a plane), VAE attention
     bool wp_bf16 = false;            // wp holds ONE plane (the round-to-nearest bf16 weights): the single-pass bf16 kernel (conv1d_bf16.hip)
     // optional pre-activated transposed split planes of the input (xt_planes_kernel): [2][B][xt_rows(T_in)][Ci]; x / in_act /
-    // GroupNorm fields are then ignored and the window is DMA'd straight into LDS
-    const bf16_t* xt = nullptr;
+    // GroupNorm fields are then ignored and the window is DMA'd straight into LDS.  xt_np = planes the buffer holds: 2 for the split weights,
+    // 1 (the round-to-nearest plane alone, [B][xt_rows(T_in)][Ci]) for wp_bf16
+    const bf16_t* xt = nullptr; int xt_np = 2;
     // optional minimal-filtering weights [P][Ci][Co] fp32 (pack.py:pack_conv_mf): selects conv1d_f32w_kernel (fp32 products, F(2,3)) where it applies
     const float* w_mf = nullptr;
 };
@@ -296,8 +297,9 @@ int launch_gn_apply(const float* x, const float* mean, const float* rstd, const 
 #define XT_HEAD 64
 #define XT_TAIL 384
 static inline int xt_rows(int T_eff) { return T_eff + XT_HEAD + XT_TAIL; }
+// nplanes: 2 = split planes [2][B][xt_rows][C] (hi, lo), 1 = the round-to-nearest plane alone (the single-pass bf16 convolutions)
 int launch_xt_planes(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int groups, int act,
-                     float slope, int upsample2, int B, int C, int T_in, bf16_t* out, hipStream_t st);
+                     float slope, int upsample2, int B, int C, int T_in, int nplanes, bf16_t* out, hipStream_t st);
 int launch_aa_act(const float* x, const float* alpha, const float* inv_beta, const float* filt, int B, int C, int T, float* out, hipStream_t st);
 // f32 [rows][cols] -> split-bf16 planes [2][rows][cpad] (cpad % 4 == 0, columns >= cols zero filled)
 int launch_split_rows(const float* x, int64_t rows, int cols, int cpad, bf16_t* out, int64_t plane, hipStream_t st);

@@ -101,6 +101,9 @@ int launch_gn_apply(const float* x, const float* mean, const float* rstd, const 
 // XT_HEAD zero rows in front and zero rows behind (Tp = T_eff + XT_HEAD + XT_TAIL), so the conv kernel can DMA its input window
 // straight into LDS: the pointwise transform (GroupNorm affine, swish, LeakyReLU), the hi/lo split, the transpose and the zero
 // padding happen ONCE here instead of once per output-channel tile of the convolution (12 tiles on the 1536-channel layers).
+// NPL == 1 (the single-pass bf16 convolutions): only the round-to-nearest plane [B][Tp][C] - plane 0 of the NPL == 2 form bit for bit;
+// the rounding residual is neither computed nor stored.
+template <int NPL>
 __global__ void __launch_bounds__(256) xt_planes_kernel(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta, int groups, int act,
                                                        float slope, int upsample2, int C, int T_in, int Tp, bf16_t* out, int64_t plane) {
@@ -140,21 +143,32 @@ __global__ void __launch_bounds__(256) xt_planes_kernel(const float* __restrict_
             const float v = tile[tr][cg + e];
             const bf16_t h = f2bf(v);
             hi[e >> 3][e & 7] = h;
-            lo[e >> 3][e & 7] = f2bf(v - bf2f(h));
+            if constexpr (NPL == 2) lo[e >> 3][e & 7] = f2bf(v - bf2f(h));
         }
         bf16_t* dst = out + ((int64_t)b * Tp + r) * C + c0 + cg;
         *reinterpret_cast<bf16x8*>(dst) = hi[0];
         *reinterpret_cast<bf16x8*>(dst + 8) = hi[1];
-        *reinterpret_cast<bf16x8*>(dst + plane) = lo[0];
-        *reinterpret_cast<bf16x8*>(dst + plane + 8) = lo[1];
+        if constexpr (NPL == 2) {
+            *reinterpret_cast<bf16x8*>(dst + plane) = lo[0];
+            *reinterpret_cast<bf16x8*>(dst + plane + 8) = lo[1];
+        }
     }
 }
 int launch_xt_planes(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int groups, int act,
-                     float slope, int upsample2, int B, int C, int T_in, bf16_t* out, hipStream_t st) {
+                     float slope, int upsample2, int B, int C, int T_in, int nplanes, bf16_t* out, hipStream_t st) {
     if (C % 16) VB_FAIL(VB_E_INVALID, "xt_planes: C %% 16");
+    if (nplanes != 1 && nplanes != 2) VB_FAIL(VB_E_INVALID, "xt_planes: %d planes (1 or 2)", nplanes);
+    if (!aligned16(out)) VB_FAIL(VB_E_INVALID, "xt_planes: the planes are not 16-byte aligned");
+    if ((act == ACT_GN || act == ACT_GN_SWISH) && (!mean || !rstd || !gamma || !beta || groups < 1 || C % groups))
+        VB_FAIL(VB_E_INVALID, "xt_planes: GroupNorm input without its statistics / affine, or C %% groups");
     const int Tp = xt_rows(upsample2 ? 2 * T_in : T_in);
-    hipLaunchKernelGGL(xt_planes_kernel, dim3(cdiv(Tp, 64), cdiv(C, 64), B), dim3(256), 0, st, x, mean, rstd, gamma, beta, groups, act, slope,
-                       upsample2, C, T_in, Tp, out, (int64_t)B * Tp * C);
+    const dim3 grid(cdiv(Tp, 64), cdiv(C, 64), B);
+    if (nplanes == 1)
+        hipLaunchKernelGGL(xt_planes_kernel<1>, grid, dim3(256), 0, st, x, mean, rstd, gamma, beta, groups, act, slope, upsample2, C, T_in, Tp, out,
+                           (int64_t)0);
+    else
+        hipLaunchKernelGGL(xt_planes_kernel<2>, grid, dim3(256), 0, st, x, mean, rstd, gamma, beta, groups, act, slope, upsample2, C, T_in, Tp, out,
+                           (int64_t)B * Tp * C);
     VB_CHECK_LAUNCH();
     return VB_OK;
 }

@@ -432,14 +432,17 @@ class NetBuilder:
     """Flattens a conv network into the vb_net_op list executed by the C++ runtime."""
 
     def __init__(self, device, precision: str = "split"):
-        assert precision in ("split", "fp32", "fp32mf", "bf16")
+        assert precision in ("split", "fp32", "fp32mf", "bf16", "bf16xt")
         self.device = device
         # "split": bf16x3 MFMA conv kernels (fp32-class); "fp32": the exact-fp32 MFMA kernels; "fp32mf": the fp32 op list in which the
         # layers of mf_conv_eligible and the 32 / 64-channel pairs run F(2,3) minimal filtering (fp32 products, ~1.45x fewer);
         # "bf16": the split op list without the DMA-fed input planes, every static-weight convolution and 32 / 64-channel pair in ONE
-        # bf16 pass (RN-bf16 weights x RN-bf16 activated input, fp32 accumulation: outside the 1e-3 parity contract, DESIGN.md section 2)
+        # bf16 pass (RN-bf16 weights x RN-bf16 activated input, fp32 accumulation: outside the 1e-3 parity contract, DESIGN.md section 2);
+        # "bf16xt": the same arithmetic on the split op list's SHAPE - every wide layer's input is activated, rounded and transposed once
+        # into ONE bf16 plane (VB_OP_XT_PLANES with WFMT_BF16) and the BF16 convolution reads it by DMA (a one-pass GEMM where it qualifies)
         self.precision = precision
-        self.x3_like = precision in ("split", "bf16")      # the op list's shape: fused input transforms, split planes for per-clip weights
+        self.x3_like = precision in ("split", "bf16", "bf16xt")      # the op list's shape: fused input transforms, split planes for per-clip weights
+        self.xt_like = precision in ("split", "bf16xt")              # wide layers read pre-activated transposed planes
         self.ops: List[L.NetOp] = []
         self.bufs: List[Tuple[int, int, int]] = []
         self.free: Dict[Tuple[int, int, int], List[int]] = {}
@@ -480,7 +483,7 @@ class NetBuilder:
         kernel and the direct kernels read)."""
         if w_buf != -1:
             return dict(wfmt=L.WFMT_BUF_X3 if self.x3_like else L.WFMT_BUF_F32)
-        if self.precision == "bf16":
+        if self.precision in ("bf16", "bf16xt"):
             plane, ci_pad = pack.pack_conv_bf16(w.to(self.device))
             self.keep.append(plane)
             f = dict(wfmt=L.WFMT_BF16, w_x3=plane.data_ptr(), ci_pad=ci_pad)
@@ -529,10 +532,10 @@ class NetBuilder:
              acc_scale=1.0, tr_stride=1, tr_pad=0, tr_k=0, groups=32, in_stride=1, in_phase=0, x_is_planes=False):
         tmp = -1
         x_planes = int(bool(x_is_planes))
-        if (self.precision == "split" and not x_planes and w is not None and w_buf == -1 and x >= 0 and Co >= self.XT_MIN_CO and Ci % 32 == 0
+        if (self.xt_like and not x_planes and w is not None and w_buf == -1 and x >= 0 and Co >= self.XT_MIN_CO and Ci % 32 == 0
                 and tr_stride == 1 and in_stride == 1 and pad <= 64 and (k - 1) * dil <= 64 and (k > 1 or in_act != L.ACT_NONE)):
-            # wide layer (>= 3 output-channel tiles): the input is activated, split and transposed ONCE (VB_OP_XT_PLANES) and every
-            # tile of the convolution DMAs its window from there, instead of each tile redoing norm / swish / split while staging
+            # wide layer (>= 3 output-channel tiles): the input is activated, split (bf16xt: rounded) and transposed ONCE (VB_OP_XT_PLANES)
+            # and every tile of the convolution DMAs its window from there, instead of each tile redoing norm / swish / split while staging
             tmp = self.xt_planes(x, Ci, stats, gamma, beta_gn, in_act, in_slope, upsample2, groups)
             x, stats, gamma, beta_gn, in_act, x_planes = tmp, -1, None, None, L.ACT_NONE, 1
         if (not self.x3_like and in_act in (L.ACT_GN_SWISH, L.ACT_GN) and stats >= 0 and w is not None and w_buf == -1 and x >= 0
@@ -555,9 +558,12 @@ class NetBuilder:
     XT_MIN_CO = int(os.environ.get("VB_XT_MIN_CO", "384"))      # (tuning knob; 256 / 128 would pull the wide vocoder stages in)
 
     def xt_planes(self, x: int, channels: int, stats: int, gamma, beta_gn, act: int, slope: float, upsample2: int, groups: int = 32) -> int:
-        """x -> new buffer of pre-activated, split-bf16, transposed planes with zero halo rows (VB_OP_XT_PLANES)."""
-        out = self.buf(channels, self.bufs[x][1] * (2 if upsample2 else 1), 3)
-        self.ops.append(L.NetOp(kind=L.OP_XT_PLANES, x=x, out=out, res=-1, stats=stats, w_buf=-1, gn_gamma=self._t(gamma),
+        """x -> new buffer of pre-activated, split-bf16, transposed planes with zero halo rows (VB_OP_XT_PLANES); bf16xt: the one-plane
+        form (WFMT_BF16, a buffer of square = 4: half the bytes)."""
+        one = self.precision == "bf16xt"
+        out = self.buf(channels, self.bufs[x][1] * (2 if upsample2 else 1), 4 if one else 3)
+        self.ops.append(L.NetOp(kind=L.OP_XT_PLANES, wfmt=L.WFMT_BF16 if one else L.WFMT_NONE, x=x, out=out, res=-1, stats=stats, w_buf=-1,
+                                gn_gamma=self._t(gamma),
                                 gn_beta=self._t(beta_gn), Ci=channels, gn_groups=groups, in_act=act, in_slope=slope, upsample2=upsample2))
         return out
 
@@ -668,7 +674,7 @@ def _vae_block_builders(nb: "NetBuilder", g: Dict[str, Tensor]):
         split = nb.x3_like       # (bf16: the per-clip products stay on the bf16x3 kernel, the q / k / v projections fuse the norm)
         q, k, v = nb.buf(c, tm), nb.buf(c, tm), nb.buf(c, tm)
         gam, bet = g[p + "norm.weight"], g[p + "norm.bias"]
-        xn = nb.xt_planes(x, c, st, gam, bet, L.ACT_GN, 0.0, 0) if (nb.precision == "split" and c >= nb.XT_MIN_CO and c % 32 == 0) else -1
+        xn = nb.xt_planes(x, c, st, gam, bet, L.ACT_GN, 0.0, 0) if (nb.xt_like and c >= nb.XT_MIN_CO and c % 32 == 0) else -1
         for name, dst, tr in (("q", q, 1 if split else 0), ("k", k, 0), ("v", v, 0 if split else 1)):
             w, b = cw(p + name)
             if xn >= 0:
@@ -829,7 +835,7 @@ def build_hifigan(ctx: Context, sd: Dict[str, Tensor], hp: dict, precision: str 
                 al, be = (1.0 / nk, 0.0 if j == 0 else 1.0) if last else (1.0, 0.0)
                 # (fp32 pair kernel: 16-byte window DMA needs T % 4 == 0 - guaranteed for every mel length, chunked runs included, when the
                 #  stage's length multiplier is a multiple of 4; other stages keep the two unfused launches)
-                fuse = (ch in fuse_pairs and (rk - 1) * d <= 64) if precision in ("split", "bf16") else \
+                fuse = (ch in fuse_pairs and (rk - 1) * d <= 64) if precision in ("split", "bf16", "bf16xt") else \
                        (ch in fp32_pairs and (rk - 1) * d <= 60 and rk <= 17 and tm % 4 == 0)
                 if hp["resblock"] == "1" and fuse and rk % 2 == 1:
                     # narrowest, longest stage: both convolutions of the pair in one launch, intermediate kept in LDS

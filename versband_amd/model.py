@@ -121,7 +121,7 @@ class AutoencoderKL:
     enc_state: Dict[str, Tensor] = {}
     enc_net = None
     _device = None
-    _precision = "fp32mf"        # VAE arithmetic: fp32 with minimal filtering (default), "fp32" = direct fp32 kernels, "split" = bf16x3, "bf16" = single-pass bf16 (set by CFM(vocoder_precision=...))
+    _precision = "fp32mf"        # VAE arithmetic: fp32 with minimal filtering (default), "fp32" = direct fp32 kernels, "split" = bf16x3, "bf16" = single-pass bf16, "bf16xt" = the same with the wide layers as one-plane DMA-fed GEMMs (set by CFM(vocoder_precision=...))
 
     def encode(self, x):
         """:49-53  mel [B,80,T_mel] -> DiagonalGaussianDistribution over z [B,embed_dim,T_mel/2] (HIP encoder net)."""
@@ -265,7 +265,7 @@ class CFM:
         self.cond_stage_forward = None
         self.scale_factor = torch.tensor(float(scale_factor))
         self.precision = precision
-        assert vocoder_precision in ("fp32", "split", "fp32mf", "bf16"), vocoder_precision
+        assert vocoder_precision in ("fp32", "split", "fp32mf", "bf16", "bf16xt"), vocoder_precision
         self.vocoder_precision = vocoder_precision
         self.first_stage_model._precision = vocoder_precision
         self.device = torch.device("cpu")
@@ -569,8 +569,9 @@ class HifiGAN:
         """vocoder/hifigan/hifigan.py:7-18.  precision: "fp32mf" (default since round 6) = the reference's fp32 arithmetic on the f32 MFMA with
         F(2,3) minimal filtering on the ResBlock convolutions (fp32 products, fewer of them; same bounds against the reference's outputs as
         "fp32" = the direct fp32 kernels); "split" = bf16x3 (<= 3e-5 of it, faster); "bf16" = one bf16 pass per convolution (RN-bf16 weights
-        x RN-bf16 activations, fp32 accumulation: a preview / draft mode outside the 1e-3 parity contract)"""
-        assert precision in ("fp32", "split", "fp32mf", "bf16"), precision
+        x RN-bf16 activations, fp32 accumulation: a preview / draft mode outside the 1e-3 parity contract); "bf16xt" =
+        the same arithmetic, wide layers reading a pre-activated bf16 plane by DMA (no layer of the default HiFi-GAN is that wide)"""
+        assert precision in ("fp32", "split", "fp32mf", "bf16", "bf16xt"), precision
         self.precision = precision
         base_dir = vocoder_ckpt
         self.config = set_hparams(f"{base_dir}/config.yaml")
@@ -626,7 +627,7 @@ class VocoderBigVGAN:
 
     def __init__(self, ckpt_vocoder, device="cuda", precision="fp32"):
         import yaml
-        assert precision in ("fp32", "split", "fp32mf", "bf16"), precision
+        assert precision in ("fp32", "split", "fp32mf", "bf16", "bf16xt"), precision
         self.precision = precision
         sd = torch.load(os.path.join(ckpt_vocoder, "best_netG.pt"), map_location="cpu")
         self.state = {k: v for k, v in sd["generator"].items() if not k.endswith("filter")}     # the filters are recomputed
