@@ -239,6 +239,31 @@ typedef struct { const int32_t* starts; int nw; } vb_windows;     /* starts: HOS
 int vb_sample_cfg_windows(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
                           const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_windows* win, const vb_rows* rows,
                           const vb_keep* keep, const vb_noise* noise, float* traj, void* ws, void* stream);
+/* The same sampler with PER-STEP GUIDANCE WEIGHTS (build-defined; guidance intervals and guidance ramps): vb_sample_cfg_windows plus a
+ * schedule.  weight is a HOST array of n_steps finite floats in [0, 16], read during the call only; anything else is VB_E_INVALID, with
+ * the step named in vb_last_error(), before anything is launched.  With s the call's scalar scale, or rows->cfg_scale[b] for row b,
+ * step k is one of three kinds:
+ *   weight[k] == 1   today's step: the same launches, arguments and bits as vb_sample_cfg_windows.
+ *   weight[k] == 0   a single-branch step: only the conditional rows [0, B) are evaluated - about half a network evaluation - and the
+ *                    update is x = fmaf(dt, v_c, x), the update of an n_branch == 1 call.  The unconditional rows are neither read nor
+ *                    written in that step.
+ *   otherwise        both branches under the step's effective scale s_k = fmaf(weight[k], s - 1, 1):
+ *                    e = fmaf(s_k, v_c - v_u, v_u), x = fmaf(dt, e, x).  A scalar s is combined on the host; per-row scales are combined
+ *                    per token on the device, in exactly this arithmetic.
+ * The known-region blend (keep) and the overlap consensus (win) follow the update exactly as in any step, in the order stated above.
+ * Router noise is keyed as if every step had two branches: the conditional rows of step k draw from the stream (seed, clip, evaluation
+ * k, branch 0, block, gate) whatever the kind of this or any other step, so a schedule changes no other step's noise and one replayed
+ * graph serves any seed.  Injected noise arrays (noise->g1) keep their two-branch layout; a single-branch step reads its first B*T rows.
+ * guidance == NULL, weight == NULL or all weights == 1 is exactly vb_sample_cfg_windows (which, like the three before it, forwards here):
+ * same launches, same graph.  With n_branch == 1 there is nothing to guide and the schedule is not read, as the scales are not.
+ * Which steps run one branch is baked into the captured graph, and the weights are launch arguments: the graph key holds the VALUES of
+ * weight, so another schedule on the same buffers captures its own graph.  rows->cfg_scale is still read when the kernels run:
+ * rewriting it in place replays the same graph.  The fused and the separate (VB_EULER_LAUNCH) update forms stay bit-identical. */
+typedef struct { const float* weight; } vb_guidance;              /* weight: HOST array of n_steps step weights in [0, 16] */
+int vb_sample_cfg_sched(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
+                        const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_guidance* guidance,
+                        const vb_windows* win, const vb_rows* rows, const vb_keep* keep, const vb_noise* noise, float* traj, void* ws,
+                        void* stream);
 /* The overlap consensus alone, on x [nw*Bc][C][n] with B = nw*Bc rows (the unit, like vb_euler_cfg_step): same formula, same checks. */
 int vb_window_blend(float* x, const int32_t* starts, int nw, int B, int C, int n, void* stream);
 /* The step loop of vb_sample_cfg is captured into a hipGraph the second time a call arrives with the same buffers / shape on a

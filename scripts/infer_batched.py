@@ -47,6 +47,9 @@ def parse_args(argv=None):
                      help="VAE + vocoder arithmetic: test_final.py's fp32mf (default) / fp32 / split, and bf16 = ONE bf16 pass per convolution (bf16 "
                           "operands, fp32 accumulation): preview quality, outside the 1e-3 parity bound; bf16xt = the same arithmetic with the wide "
                           "layers' inputs activated once into a bf16 plane and multiplied as DMA-fed GEMMs")
+    own.add_argument("--guidance_interval", type=parse_interval, default=None, metavar="LO-HI",
+                     help="guide only the steps that start at t in [LO, HI] (0-1 covers every step: today's files); the other steps of a "
+                          "guided call evaluate the conditional branch alone.  The scale-1.0 rows stay the one-branch call they are")
     argv = list(sys.argv[1:] if argv is None else argv)
     if "-h" in argv or "--help" in argv:
         own.print_help()
@@ -56,8 +59,20 @@ def parse_args(argv=None):
         args = loop.parse_args()
     args.items_per_batch, args.synthetic_frames = mine.items_per_batch, parse_frames(mine.synthetic_frames)
     args.vocoder_precision = mine.vocoder_precision
+    args.guidance_interval = mine.guidance_interval
     check_items_per_batch(args.items_per_batch, list(dict.fromkeys(_scales(args))), args.n_samples)
     return args
+
+
+def parse_interval(text):
+    """"LO-HI" -> (lo, hi) with 0 <= lo <= hi <= 1"""
+    try:
+        lo, hi = (float(v) for v in text.split("-"))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--guidance_interval {text!r}: expected LO-HI, two numbers in [0, 1]") from None
+    if not 0.0 <= lo <= hi <= 1.0:
+        raise argparse.ArgumentTypeError(f"--guidance_interval {text!r}: needs 0 <= LO <= HI <= 1")
+    return lo, hi
 
 
 def _scales(args):
@@ -121,9 +136,11 @@ def sample_group(args, sampler, vocoder, group, scales, device):
         uc = _cat_conditioning([conds[p][1] for p, _ in runs]) if call["n_branch"] == 2 else None
         x = torch.cat([starts[p] for p, _ in runs])
         scale = [s for _, s, _ in rows] if call["n_branch"] == 2 else 1.0
+        interval = getattr(args, "guidance_interval", None)
+        gk = {"guidance_interval": interval} if interval is not None and call["n_branch"] == 2 else {}
         z, _ = sampler.sample_cfg(cond=c, unconditional_guidance_scale=scale, unconditional_conditioning=uc, batch_size=len(rows),
                                   shape=[embed_dim, call["length"]], x_latent=x, timesteps=args.ddim_steps + 1, seed=args.seed,
-                                  clip_ids=call["clip_ids"])
+                                  clip_ids=call["clip_ids"], **gk)
         mel = sampler.model.decode_first_stage(z)
         wav = vocoder.spec2wav_batch(mel).cpu().numpy()
         for r, (p, s, k) in enumerate(rows):

@@ -72,6 +72,10 @@ class Windows(C.Structure):
     _fields_ = [("starts", C.POINTER(C.c_int32)), ("nw", c_int)]
 
 
+class Guidance(C.Structure):
+    _fields_ = [("weight", C.POINTER(c_float))]
+
+
 class MelConfig(C.Structure):
     _fields_ = [("n_fft", c_int), ("hop", c_int), ("n_mels", c_int)]
 
@@ -119,6 +123,8 @@ PROTOTYPES = {
     "vb_sample_cfg_rows": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_float, C.POINTER(Rows), C.POINTER(Keep), C.POINTER(Noise), P, P, P]),
     "vb_sample_cfg_windows": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_float, C.POINTER(Windows), C.POINTER(Rows), C.POINTER(Keep),
                                       C.POINTER(Noise), P, P, P]),
+    "vb_sample_cfg_sched": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_float, C.POINTER(Guidance), C.POINTER(Windows), C.POINTER(Rows),
+                                    C.POINTER(Keep), C.POINTER(Noise), P, P, P]),
     "vb_window_blend": (c_int, [P, C.POINTER(C.c_int32), c_int, c_int, c_int, c_int, P]),
     "vb_sample_graphs": (c_int, [P]),
     "vb_net_load": (c_int, [P, c_int, C.POINTER(NetOp), c_int, C.POINTER(BufDesc), c_int, c_int, c_int, c_int, c_int]),

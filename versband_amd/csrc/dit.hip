@@ -155,19 +155,22 @@ static FinalRoute final_route(const vb_dit_config& c, const vb_dit_weights& w, i
     if (w.final_wp && c.in_channels % 4 == 0 && (int64_t)2 * N * c.ffn_hidden >= (int64_t)N * c.hidden) return FINAL_GEMM;
     return FINAL_ROWS;
 }
-DitPlan dit_plan(const vb_ctx* ctx, int B, int nb, int T, int L) {
+DitPlan dit_plan(const vb_ctx* ctx, int B, int nb, int T, int L, int nb_active) {
     const vb_dit_config& c = ctx->cfg;
-    const int Beff = B * nb, N = Beff * T;
+    const int nba = nb_active > 0 ? nb_active : nb;
+    const int Beff = B * nba, N = Beff * T;          // the rows the launches count
     DitPlan p;
     p.w = &ctx->w;
-    p.router_counts = router_counts_eligible(N);
+    // the layout (model, knobs and L alone: the same for every nb_active)
     p.w2_pair = w2_pair_eligible(c);
-    p.band_fused = band_fused_eligible(c, N);
     p.proj_in_split_w = proj_in_split_w_eligible(c, ctx->w);
     p.proj_in_gemm = p.proj_in_split_w && !vb_tune().proj_in_conv;
     p.fold_layout = gate_fold_ok(c, L);
+    // kernels picked from the token count: the active rows
+    p.router_counts = router_counts_eligible(N);
+    p.band_fused = band_fused_eligible(c, N);
     p.score_fused = score_fused_eligible(c, Beff, T, L);
-    p.final_route = final_route(c, ctx->w, nb, N);
+    p.final_route = final_route(c, ctx->w, nba, N);
     return p;
 }
 
@@ -272,27 +275,31 @@ static int dit_precompute(vb_ctx* ctx, const float* t5, const int64_t* midi, con
 }
 
 // ------------------------------------------------------------------------------------------
-// DiT: one evaluation (both CFG branches batched: rows [0,B) cond, [B,2B) uncond)
+// DiT: one evaluation (both CFG branches batched: rows [0,B) cond, [B,2B) uncond; DitEval::nb_active = 1 beside nb = 2: the
+// conditional rows alone, in the two-branch layout)
 // ------------------------------------------------------------------------------------------
 // what the steps of one evaluation share
 struct Eval {
     const vb_dit_config& c; const vb_dit_weights& w; const DitEval& ev; hipStream_t st;
     const DitPlan p; const CondL cd; const WsL s;
-    const int Beff, D, H, E, hd, np, nseg, N, MODW, band; const int64_t ND;
+    const int Beff, D, H, E, hd, np, nseg, N, MODW, band;     // Beff, N: the ACTIVE rows / tokens - what every launch counts
+    const int BeffL, NL;                                      // rows / tokens of the layout (ev.nb): strides, table offsets
+    const int64_t ND;                                         // plane stride of the [N][D] bf16 buffers (layout)
     const int eval0;                                          // block evaluations before this one: block i's router counts into table (eval0 + i) & 1
     const float* mod_all; const float* hl; int hl_ld;        // this evaluation's adaLN modulations and high-level gate logits (conditioning_vectors)
     Planes u, q, k, vt, a, qm, cqa, Hs, y, Hf;
     Eval(vb_ctx* ctx, const DitEval& e, hipStream_t stream)
-        : c(ctx->cfg), w(ctx->w), ev(e), st(stream), p(dit_plan(ctx, e.B, e.nb, e.T, e.L)),
+        : c(ctx->cfg), w(ctx->w), ev(e), st(stream), p(dit_plan(ctx, e.B, e.nb, e.T, e.L, e.nb_active)),
           cd(carve_cond(const_cast<void*>(e.cond), ctx->cfg, e.B, e.nb, e.T, e.L)), s(carve_ws(e.ws, ctx->cfg, e.B, e.nb, e.T, e.L)),
-          Beff(e.B * e.nb), D(c.hidden), H(c.ffn_hidden), E(c.num_experts), hd(D / c.heads), np(c.np), nseg(np == 2 ? 3 : 1), N((int)s.n_tok),
-          MODW(s.MODW), band(D / E), ND((int64_t)N * D), eval0(e.evals_before < 0 ? 0 : e.evals_before),
+          Beff(e.B * (e.nb_active > 0 ? e.nb_active : e.nb)), D(c.hidden), H(c.ffn_hidden), E(c.num_experts), hd(D / c.heads), np(c.np),
+          nseg(np == 2 ? 3 : 1), N(Beff * e.T), MODW(s.MODW), band(D / E), BeffL(e.B * e.nb), NL((int)s.n_tok), ND((int64_t)NL * D),
+          eval0(e.evals_before < 0 ? 0 : e.evals_before),
           mod_all(s.mod_all), hl(s.hl), hl_ld(c.depth * 2),
           u(mkp(s.u, ND, np)), q(mkp(s.q, ND, np)), k(mkp(s.k, ND, np)), vt(mkp(s.vt, s.n_vt, np)), a(mkp(s.a, ND, np)), qm(mkp(s.qm, ND, np)),
-          cqa(mkp(s.cqa, ND, np)), Hs(mkp(s.Hs, (int64_t)2 * N * H, np)), y(mkp(s.y, ND, np)), Hf(mkp(s.Hf, (int64_t)N * E * H, np)) {}
+          cqa(mkp(s.cqa, ND, np)), Hs(mkp(s.Hs, (int64_t)2 * NL * H, np)), y(mkp(s.y, ND, np)), Hf(mkp(s.Hf, (int64_t)NL * E * H, np)) {}
     const float* mod(int i) const { return mod_all + (size_t)i * 6 * D; }      // shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
     float scale() const { return 1.0f / sqrtf((float)hd); }
-    int* counts(int i) const { return bucket_counts(s.perm, N, (eval0 + i) & 1); }
+    int* counts(int i) const { return bucket_counts(s.perm, NL, (eval0 + i) & 1); }      // (where the layout puts them, whatever the active rows)
 };
 
 // timestep embedding + all adaLN modulations + high-level gate logits (depend on (t, caption) only)
@@ -323,7 +330,7 @@ static int embed_latent(const Eval& e) {
         VB_TRY(launch_im2col_latent(e.ev.x, B, c.in_channels, T, 5, 2, PIN_KP, s.pin_a, (int64_t)BT * PIN_KP, e.st));
         GemmArgs g = gemm_operands(s.pin_a, (int64_t)BT * PIN_KP, PIN_KP, e.cd.pin_w, (int64_t)D * PIN_KP, PIN_KP, BT, D, PIN_KP, 3);
         g.epi = EPI_F32; g.bias = w.proj_in_b; g.out32 = s.h; g.ldc32 = D;
-        g.add32 = e.cd.ac; g.dup_rows = e.ev.nb == 2 ? BT : 0; g.prof_class = 2;       // split-precision convolution work: counted with the conv class
+        g.add32 = e.cd.ac; g.dup_rows = e.Beff == 2 * B ? BT : 0; g.prof_class = 2;       // split-precision convolution work: counted with the conv class
         return launch_gemm(g, e.st);
     }
     ConvArgs cv;
@@ -361,7 +368,7 @@ static GateNoise gate_noise(const Eval& e, int i) {
     GateNoise n;
     if (const vb_noise* nz = e.ev.noise; nz && nz->g1) {
         const size_t so = (size_t)e.ev.noise_step * e.c.depth + i;
-        n.g1 = nz->g1 + so * e.N * 2; n.g2 = nz->g2 + so * e.N * e.E; n.g3 = nz->g3 + so * e.N * e.E;
+        n.g1 = nz->g1 + so * e.NL * 2; n.g2 = nz->g2 + so * e.NL * e.E; n.g3 = nz->g3 + so * e.NL * e.E;      // (arrays of the layout; the conditional rows come first)
     }
     return n;
 }
@@ -396,7 +403,7 @@ static int caption_gate_and_route(const Eval& e, int i) {
             // caption gate, folded: scores of every token against its clip's caption keys for all heads in ONE grouped GEMM
             // (q-projection, q-bias and softmax scale live in the per-clip operand), then softmax + value/gate contraction +
             // routing in the router kernel.  Replaces q-projection GEMM + cross-attention launch + 768-wide gate dot.
-            GemmArgs g = gemm_operands(e.u.p, e.ND, D, cd.mf[i], (int64_t)e.Beff * cd.NS * D, D, N, cd.NS, D, e.nseg);
+            GemmArgs g = gemm_operands(e.u.p, e.ND, D, cd.mf[i], (int64_t)e.BeffL * cd.NS * D, D, N, cd.NS, D, e.nseg);
             g.b_group_stride = (int64_t)cd.NS * D; g.ngroups = e.Beff; g.group_off = cd.clip_off; g.group_rows = T;
             g.epi = EPI_F32; g.bias = cd.cb[i]; g.bias_group_stride = cd.NS; g.out32 = s.y32; g.ldc32 = cd.NS;
             VB_TRY(launch_gemm(g, e.st));
@@ -511,8 +518,9 @@ int dit_forward(vb_ctx* ctx, const DitEval& ev, hipStream_t st) {
     const vb_dit_config& c = e.c;
     if (ev.T > c.max_len) VB_FAIL(VB_E_INVALID, "dit_forward: T=%d exceeds the RoPE table (max_len=%d, vocal2music_moe.py:421)", ev.T, c.max_len);
     if (ev.zero_vt) VB_HIP(hipMemsetAsync(e.s.vt, 0, (size_t)e.s.n_vt * e.np * sizeof(bf16_t), st));
+    if (ev.nb_active < 0 || ev.nb_active > ev.nb) VB_FAIL(VB_E_INVALID, "dit_forward: nb_active=%d of nb=%d", ev.nb_active, ev.nb);
     if (e.p.router_counts && ev.evals_before < 0)
-        VB_TRY(launch_fill_f32(reinterpret_cast<float*>(bucket_counts(e.s.perm, e.N, 0)), bucket_counts_ints(e.N), 0.f, st));
+        VB_TRY(launch_fill_f32(reinterpret_cast<float*>(bucket_counts(e.s.perm, e.NL, 0)), bucket_counts_ints(e.NL), 0.f, st));
     VB_TRY(conditioning_vectors(e));
     VB_TRY(embed_latent(e));
     for (int i = 0; i < c.depth; ++i) {

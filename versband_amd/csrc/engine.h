@@ -24,7 +24,8 @@ struct SampleGraph {
         const void* keep_ref = nullptr; const void* keep_x0 = nullptr; const void* keep_mask = nullptr; float sigma_min = 0.f;   // vb_sample_cfg_keep (all null: a plain call)
         const void* rows_scale = nullptr; const void* rows_clip = nullptr;   // vb_sample_cfg_rows: the two POINTERS (cfg_scale is 0 beside rows_scale); their contents are read when the kernels run
         int nw = 0; std::array<int, 64> starts{};    // vb_sample_cfg_windows: the plan's VALUES (the kernel argument holds them); nw = 0: no windows
-        auto tie() const { return std::tie(x, cond, ws, B, nb, T, L, n_steps, cfg_scale, tune_gen, keep_ref, keep_x0, keep_mask, sigma_min, rows_scale, rows_clip, nw, starts); }
+        bool sched = false; std::array<float, 64> weights{};   // vb_sample_cfg_sched: the step weights' VALUES (launch arguments, and which steps run one branch); sched = false: no schedule
+        auto tie() const { return std::tie(x, cond, ws, B, nb, T, L, n_steps, cfg_scale, tune_gen, keep_ref, keep_x0, keep_mask, sigma_min, rows_scale, rows_clip, nw, starts, sched, weights); }
         bool operator==(const Key& o) const { return tie() == o.tie(); }
     } key;
     int seen = 0;                         // calls with this key so far (the first runs eagerly, the second captures)
@@ -108,7 +109,10 @@ WsL carve_ws(void* base, const vb_dit_config& c, int B, int nb, int T, int L);
 
 // Every choice one network evaluation makes, stated once (dit_plan): each member is a function of the loaded model, the knobs and
 // (B, nb, T, L) alone, so precompute, evaluation and sampler cannot disagree, and none depends on anything that varies between the
-// blocks or the steps of a call.
+// blocks of an evaluation.
+// An evaluation over nb_active < nb branches of the nb layout (a single-branch step of vb_sample_cfg_sched): the members that describe
+// the LAYOUT (proj_in_split_w, proj_in_gemm, fold_layout, w2_pair - model and L alone) are those of nb; the members that pick a kernel
+// from the token count (router_counts, band_fused, score_fused, final_route) follow the active rows, i.e. are those of an nb_active call.
 enum FinalRoute {
     FINAL_EULER_FUSED,   // FinalLayer + CFG + Euler update + step advance as one launch: only with DitEval::euler (the sampler);
                          // an evaluation without it takes FINAL_FUSED, whose conditions this route includes
@@ -124,12 +128,15 @@ struct DitPlan {
     // block i takes the folded caption gate: the layout holds its operands and the pack carries the folded weights
     bool gate_fold(int i) const { return fold_layout && w->blocks[i].wqt_s && w->blocks[i].bq_s; }
 };
-DitPlan dit_plan(const vb_ctx* ctx, int B, int nb, int T, int L);
+DitPlan dit_plan(const vb_ctx* ctx, int B, int nb, int T, int L, int nb_active = 0);      // nb_active = 0: nb
 
 // one network evaluation (both CFG branches batched: rows [0,B) cond, [B,2B) uncond); a caller fills what it uses
 struct DitEval {
     const float* x = nullptr; const int64_t* t_idx = nullptr; const void* cond = nullptr; void* ws = nullptr;
     int B = 0, nb = 0, T = 0, L = 0;
+    // branches evaluated (0: all nb).  1 beside nb = 2: the conditional rows [0, B) alone, in the layout of nb - cond, workspace, plane
+    // strides, injected-noise arrays and the tabulated pre_mod rows keep their two-branch offsets; every row and group count follows B
+    int nb_active = 0;
     const vb_noise* noise = nullptr; int noise_step = 0; const int* step_ptr = nullptr;
     const int64_t* clip_rows = nullptr;                         // vb_sample_cfg_rows: device [B] global clip ids of the router noise (null: noise->clip_base + b)
     float* v_out = nullptr; int32_t* route_out = nullptr;

@@ -212,6 +212,9 @@ struct EulerKeep { const float* ref; const float* x0; const float* mask; const f
 struct EulerStep {
     float* x = nullptr; float cfg_scale = 0.f; const float* scale_rows = nullptr; const float* dt_table = nullptr;
     const EulerKeep* keep = nullptr;
+    // vb_sample_cfg_sched, beside scale_rows only: this step's guidance weight w, the row's scale becomes fmaf(w, scale_rows[b] - 1, 1).
+    // 1 = the plain rows instances; anything else takes the *_sched_kernel instances.  (A scalar scale is combined on the host: cfg_scale.)
+    float row_weight = 1.f;
     int k = 0; int* step = nullptr; int64_t* t_idx_cur = nullptr; const int64_t* t_table = nullptr; int n_steps = 0, Beff = 0;
 };
 // FinalLayer + the update + the step advance as one launch (rows = 2 x (B T) token rows, conditional half first; reads es.k, not *es.step)

@@ -156,15 +156,22 @@ struct FinalEulerKeep : FinalEuler { EulerKeep kp; };
 // keep their kernel arguments and compile to the code they had.
 struct FinalEulerRows : FinalEuler { const float* scale_rows; };
 struct FinalEulerKeepRows : FinalEulerKeep { const float* scale_rows; };
-template <bool KEEP, bool ROWS>
-using FinalEulerArgs = std::conditional_t<ROWS, std::conditional_t<KEEP, FinalEulerKeepRows, FinalEulerRows>, std::conditional_t<KEEP, FinalEulerKeep, FinalEuler>>;
-template <int NQ, bool EUL = false, bool KEEP = false, bool ROWS = false>      // D = 256 * NQ
+// SCHED (vb_sample_cfg_sched, per-row scales under a step weight that is neither 0 nor 1): the token's scale becomes
+// fmaf(weight, scale_rows[b] - 1, 1), one more fused multiply-add per output row.  Two more instances (plain / keep) with their own
+// argument blocks: the five forms above keep their kernel arguments and compile to the code they had.
+struct FinalEulerRowsSched : FinalEulerRows { float weight; };
+struct FinalEulerKeepRowsSched : FinalEulerKeepRows { float weight; };
+template <bool KEEP, bool ROWS, bool SCHED = false>
+using FinalEulerArgs = std::conditional_t<SCHED, std::conditional_t<KEEP, FinalEulerKeepRowsSched, FinalEulerRowsSched>,
+                                          std::conditional_t<ROWS, std::conditional_t<KEEP, FinalEulerKeepRows, FinalEulerRows>, std::conditional_t<KEEP, FinalEulerKeep, FinalEuler>>>;
+template <int NQ, bool EUL = false, bool KEEP = false, bool ROWS = false, bool SCHED = false>      // D = 256 * NQ
 __global__ void __launch_bounds__(256) final_layer_kernel(const float* __restrict__ h, const float* __restrict__ shift,
                                                          const float* __restrict__ scale, int mod_ld, const float* __restrict__ W,
                                                          const float* __restrict__ bias, int rows, int T, int C, float eps, float* out,
-                                                         const FinalEulerArgs<KEEP, ROWS> fe) {
+                                                         const FinalEulerArgs<KEEP, ROWS, SCHED> fe) {
     static_assert(EUL || !KEEP, "the known-region blend belongs to the Euler update");
     static_assert(EUL || !ROWS, "the guidance scales belong to the Euler update");
+    static_assert(ROWS || !SCHED, "the step weight belongs to the per-row scales (a scalar scale is combined on the host)");
     constexpr int D = 256 * NQ;
     extern __shared__ __attribute__((aligned(16))) float wl[];      // [C][D]
     for (int id = threadIdx.x * 4; id < C * D; id += 1024) *reinterpret_cast<float4*>(wl + id) = *reinterpret_cast<const float4*>(W + id);
@@ -242,6 +249,7 @@ __global__ void __launch_bounds__(256) final_layer_kernel(const float* __restric
                         const float vc = res[j] + bv, vu = res[2 + j] + bv;
                         float sb = fe.cfg_scale;
                         if constexpr (ROWS) sb = fe.scale_rows[bb[j]];      // (bb[j] < B: rows 0 / 1 of the group are tokens of the conditional half)
+                        if constexpr (SCHED) sb = fmaf(fe.weight, sb - 1.f, 1.f);
                         float* xp = fe.x + ((int64_t)bb[j] * C + lane) * T + tt[j];
                         if constexpr (KEEP) {
                             const int64_t xi = xp - fe.x;
@@ -303,9 +311,23 @@ int launch_final_layer_euler(const float* h, const float* shift, const float* sc
         hipLaunchKernelGGL((final_layer_kernel<NQ, true, KEEP, ROWS>), dim3(grid), dim3(256), sh, st, h, shift, scale, mod_ld, W, bias, rows, T > 0 ? T : 1, C,
                            eps, (float*)nullptr, fe);
     };
+    // per-row scales under a step weight (EulerStep::row_weight != 1): the SCHED instances
+    auto go_sched = [&](auto nq, auto keep) {
+        constexpr int NQ = decltype(nq)::value;
+        constexpr bool KEEP = decltype(keep)::value;
+        FinalEulerArgs<KEEP, true, true> fe;
+        static_cast<FinalEuler&>(fe) = base;
+        if constexpr (KEEP) fe.kp = *es.keep;
+        fe.scale_rows = es.scale_rows; fe.weight = es.row_weight;
+        static OnceFlags attr;
+        vb_set_max_lds_once(attr, reinterpret_cast<const void*>(final_layer_kernel<NQ, true, KEEP, true, true>), 96 * 1024);
+        hipLaunchKernelGGL((final_layer_kernel<NQ, true, KEEP, true, true>), dim3(grid), dim3(256), sh, st, h, shift, scale, mod_ld, W, bias, rows, T > 0 ? T : 1, C,
+                           eps, (float*)nullptr, fe);
+    };
     const std::true_type yes; const std::false_type no;
     auto form = [&](auto nq) {
-        if (es.keep && es.scale_rows) go(nq, yes, yes); else if (es.scale_rows) go(nq, no, yes); else if (es.keep) go(nq, yes, no); else go(nq, no, no);
+        if (es.scale_rows && es.row_weight != 1.f) { if (es.keep) go_sched(nq, yes); else go_sched(nq, no); }
+        else if (es.keep && es.scale_rows) go(nq, yes, yes); else if (es.scale_rows) go(nq, no, yes); else if (es.keep) go(nq, yes, no); else go(nq, no, no);
     };
     if (D == 256) form(std::integral_constant<int, 1>()); else if (D == 512) form(std::integral_constant<int, 2>());
     else if (D == 768) form(std::integral_constant<int, 3>()); else form(std::integral_constant<int, 4>());

@@ -9,9 +9,18 @@
 // rows (vb_sample_cfg_rows; either member may be null): clip b is guided by rows.cfg_scale[b] and draws its router noise as clip rows.clip[b]
 // wins != nullptr (vb_sample_cfg_windows): the rows are wins->nw windows of B / nw clips; after every update - in either form, the same
 // launch - the overlapping tokens of neighbouring windows take their consensus value, before the trajectory copy
+// gw != nullptr (vb_sample_cfg_sched; host array, n_branch == 2 and not all ones): step k is one of three kinds by gw[k] -
+//   1: today's step, launch for launch;
+//   0: a single-branch step - the network runs over the conditional rows alone (DitEval::nb_active = 1), FinalLayer writes their velocity
+//      and the update is the separate launch without an unconditional half, as in an n_branch == 1 call;
+//   else: both branches under the step's effective scale fmaf(gw[k], s - 1, 1): a scalar s is combined here and handed to the existing
+//      instances, per-row scales take the *_sched_kernel instances with gw[k] in their arguments.
+// The kinds are baked into a captured graph (its key holds the weights).  Keep blend, window consensus and trajectory copy do not
+// depend on the kind.
+static_assert(PRE_STEPS <= 64, "the graph key holds the step weights of a graphable call (SampleGraph::Key::weights)");
 static int sample_steps(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps, float cfg_scale,
-                        const vb_rows& rows, const vb_keep* keep, const WindowPlan* wins, const vb_noise* noise, float* traj, void* ws,
-                        hipStream_t st) {
+                        const vb_rows& rows, const vb_keep* keep, const WindowPlan* wins, const float* gw, const vb_noise* noise, float* traj,
+                        void* ws, hipStream_t st) {
     const vb_dit_config& c = ctx->cfg;
     const DitPlan plan = dit_plan(ctx, B, n_branch, T, L);
     WsL s = carve_ws(ws, c, B, n_branch, T, L);
@@ -58,18 +67,35 @@ static int sample_steps(vb_ctx* ctx, float* x, const void* cond, int B, int n_br
     es.x = x; es.cfg_scale = cfg_scale; es.dt_table = s.dt_table; es.keep = keep ? &kp : nullptr;
     es.scale_rows = n_branch == 2 ? rows.cfg_scale : nullptr;      // (one branch: there is nothing to guide, the scales are unused)
     es.step = s.step; es.t_idx_cur = s.t_idx_cur; es.t_table = s.t_table; es.n_steps = n_steps; es.Beff = Beff;
+    bool advanced = false;        // the previous step's update launch advanced the device step counter (the fused form does)
+    bool single_prev = false;
     for (int k = 0; k < n_steps; ++k) {
         RoctxRange rs("euler_step");
-        if (!fuse || k == 0) VB_TRY(launch_step_ctl(s.step, s.t_idx_cur, s.t_table, n_steps, Beff, k == 0, st));
-        es.k = k;
+        const float wk = gw ? gw[k] : 1.f;
+        const bool single = gw && wk == 0.f;
+        const bool fuse_k = fuse && !single;
+        // the router's count tables are in step only while every evaluation counts the same rows (DitPlan::router_counts): a change between
+        // one and two branches starts them afresh
+        if (k > 0 && single != single_prev && plan.router_counts)
+            VB_TRY(launch_fill_f32(reinterpret_cast<float*>(bucket_counts(s.perm, (int)s.n_tok, 0)), bucket_counts_ints((int)s.n_tok), 0.f, st));
+        single_prev = single;
+        if (k == 0 || !advanced) VB_TRY(launch_step_ctl(s.step, s.t_idx_cur, s.t_table, n_steps, Beff, k == 0, st));
+        EulerStep ek = es;
+        ek.k = k;
+        if (single) ek.scale_rows = nullptr;                          // (one branch: nothing to guide, as in an n_branch == 1 call)
+        else if (gw && wk != 1.f) {
+            if (ek.scale_rows) ek.row_weight = wk; else ek.cfg_scale = fmaf(wk, cfg_scale - 1.f, 1.f);
+        }
         DitEval ev;
         ev.x = x; ev.t_idx = s.t_idx_cur; ev.cond = cond; ev.ws = ws; ev.B = B; ev.nb = n_branch; ev.T = T; ev.L = L;
+        if (single) ev.nb_active = 1;
         ev.noise = noise; ev.noise_step = k; ev.step_ptr = s.step; ev.v_out = s.v; ev.clip_rows = rows.clip;
         if (tab) { ev.pre_mod = s.mod_s + (size_t)k * Beff * MODW; ev.pre_hl = s.hl_s + (size_t)k * c.depth * 2; }
         ev.evals_before = k * c.depth;
-        if (fuse) ev.euler = &es;
+        if (fuse_k) ev.euler = &ek;
         VB_TRY(dit_forward(ctx, ev, st));
-        if (!fuse) VB_TRY(launch_euler_cfg(es, s.v, B, per, T, n_branch == 2, 0.f, st));
+        if (!fuse_k) VB_TRY(launch_euler_cfg(ek, s.v, B, per, T, n_branch == 2 && !single, 0.f, st));
+        advanced = fuse_k;
         if (wins) VB_TRY(launch_window_blend(x, *wins, B / wins->nw, c.in_channels, T, st));
         if (traj) VB_HIP(hipMemcpyAsync(traj + (size_t)(k + 1) * B * per, x, (size_t)B * per * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
@@ -107,17 +133,17 @@ int vb_euler_cfg_step(float* x, const float* v, int B, int64_t per_item, float c
 int vb_sample_cfg(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
                   const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_noise* noise, float* traj, void* ws,
                   void* stream) {
-    return vb_sample_cfg_windows(ctx, x, cond, B, n_branch, T, L, n_steps, t_idx_table, dt_table, cfg_scale, nullptr, nullptr, nullptr, noise, traj, ws, stream);
+    return vb_sample_cfg_sched(ctx, x, cond, B, n_branch, T, L, n_steps, t_idx_table, dt_table, cfg_scale, nullptr, nullptr, nullptr, nullptr, noise, traj, ws, stream);
 }
 int vb_sample_cfg_keep(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
                        const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_keep* keep, const vb_noise* noise,
                        float* traj, void* ws, void* stream) {
-    return vb_sample_cfg_windows(ctx, x, cond, B, n_branch, T, L, n_steps, t_idx_table, dt_table, cfg_scale, nullptr, nullptr, keep, noise, traj, ws, stream);
+    return vb_sample_cfg_sched(ctx, x, cond, B, n_branch, T, L, n_steps, t_idx_table, dt_table, cfg_scale, nullptr, nullptr, nullptr, keep, noise, traj, ws, stream);
 }
 int vb_sample_cfg_rows(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
                        const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_rows* rows, const vb_keep* keep,
                        const vb_noise* noise, float* traj, void* ws, void* stream) {
-    return vb_sample_cfg_windows(ctx, x, cond, B, n_branch, T, L, n_steps, t_idx_table, dt_table, cfg_scale, nullptr, rows, keep, noise, traj, ws, stream);
+    return vb_sample_cfg_sched(ctx, x, cond, B, n_branch, T, L, n_steps, t_idx_table, dt_table, cfg_scale, nullptr, nullptr, rows, keep, noise, traj, ws, stream);
 }
 int vb_window_blend(float* x, const int32_t* starts, int nw, int B, int C, int n, void* stream) {
     if (!x || C < 1) VB_FAIL(VB_E_INVALID, "window_blend: null x or C < 1");
@@ -126,13 +152,28 @@ int vb_window_blend(float* x, const int32_t* starts, int nw, int B, int C, int n
     return launch_window_blend(x, wp, B / nw, C, n, (hipStream_t)stream);
 }
 int vb_sample_cfg_windows(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
-                          const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_windows* win, const vb_rows* rows_in,
+                          const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_windows* win, const vb_rows* rows,
                           const vb_keep* keep, const vb_noise* noise, float* traj, void* ws, void* stream) {
+    return vb_sample_cfg_sched(ctx, x, cond, B, n_branch, T, L, n_steps, t_idx_table, dt_table, cfg_scale, nullptr, win, rows, keep, noise, traj, ws, stream);
+}
+int vb_sample_cfg_sched(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
+                        const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_guidance* guidance,
+                        const vb_windows* win, const vb_rows* rows_in, const vb_keep* keep, const vb_noise* noise, float* traj, void* ws,
+                        void* stream) {
     const vb_rows rows = rows_in ? *rows_in : vb_rows{nullptr, nullptr};
     if (rows.cfg_scale) cfg_scale = 0.f;          // unused beside the array; one value in the graph key
     if (!ctx || !ctx->dit_loaded) VB_FAIL(VB_E_STATE, "sample_cfg: DiT not loaded");
     if (n_steps < 1 || n_steps > 1024) VB_FAIL(VB_E_INVALID, "sample_cfg: n_steps=%d", n_steps);
     if (keep && (!keep->ref || !keep->x0 || !keep->mask || !keep->t_next)) VB_FAIL(VB_E_INVALID, "sample_cfg_keep: ref, x0, mask and t_next must all be given");
+    // the schedule (host array): checked before anything is launched; all ones, or one branch (nothing to guide), is the plain call
+    const float* gw = nullptr;
+    if (guidance && guidance->weight && n_branch == 2) {
+        for (int k = 0; k < n_steps; ++k) {
+            const float w = guidance->weight[k];
+            if (!(w >= 0.f && w <= 16.f)) VB_FAIL(VB_E_INVALID, "sample_cfg_sched: weight[%d] = %g is not a finite value in [0, 16]", k, (double)w);
+            if (w != 1.f) gw = guidance->weight;
+        }
+    }
     WindowPlan wp;
     if (win) VB_TRY(window_plan(win->starts, win->nw, B, T, &wp));
     const WindowPlan* wins = win && wp.nw > 1 ? &wp : nullptr;      // (one window: the plain call, and its graph)
@@ -171,10 +212,11 @@ int vb_sample_cfg_windows(vb_ctx* ctx, float* x, const void* cond, int B, int n_
         if (keep) { key.keep_ref = keep->ref; key.keep_x0 = keep->x0; key.keep_mask = keep->mask; key.sigma_min = keep->sigma_min; }
         key.rows_scale = rows.cfg_scale; key.rows_clip = rows.clip;
         if (wins) { key.nw = wp.nw; std::copy(wp.s, wp.s + 64, key.starts.begin()); }
+        if (gw) { key.sched = true; std::copy(gw, gw + n_steps, key.weights.begin()); }      // (graphable: n_steps <= PRE_STEPS = 64)
         SampleGraph* e = graph_entry(ctx, key);
         if (!e->exec && !e->failed && e->seen >= 2) {
             if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                const int rc = sample_steps(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, rows, keep, wins, noise, nullptr, ws, st);
+                const int rc = sample_steps(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, rows, keep, wins, gw, noise, nullptr, ws, st);
                 hipGraph_t gr = nullptr;
                 const hipError_t ee = hipStreamEndCapture(st, &gr);
                 if (rc == VB_OK && ee == hipSuccess && gr && hipGraphInstantiate(&e->exec, gr, nullptr, nullptr, 0) == hipSuccess) {
@@ -194,7 +236,7 @@ int vb_sample_cfg_windows(vb_ctx* ctx, float* x, const void* cond, int B, int n_
             return VB_OK;
         }
     }
-    return sample_steps(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, rows, keep, wins, noise, traj, ws, st);
+    return sample_steps(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, rows, keep, wins, gw, noise, traj, ws, st);
 }
 int vb_sample_graphs(vb_ctx* ctx) {
     int n = 0;

@@ -14,10 +14,12 @@
 // KEEP (vb_sample_cfg_keep): the blend with the known region at t = tn_table[*step]; mask, ref and x0 are read in these instances only.
 // ROWS (vb_sample_cfg_rows): clip b = i / per takes scale_rows[b] instead of cfg_scale.
 // ---------------------------------------------------------------------------
-template <bool KEEP, bool ROWS>
-__global__ void euler_cfg_kernel(float* x, const float* __restrict__ v, int64_t n, int64_t per, int T, float cfg_scale,
-                                 const float* __restrict__ scale_rows, const float* dt_table, const int* step, float dt_val,
-                                 int has_uncond, const EulerKeep kp) {
+// SCHED (vb_sample_cfg_sched, per-row scales under a step weight that is neither 0 nor 1): s = fmaf(weight, scale_rows[b] - 1, 1); a kernel
+// of its own (euler_cfg_sched_kernel) with the weight as one more argument, so the four instances of euler_cfg_kernel keep theirs.
+template <bool KEEP, bool ROWS, bool SCHED>
+__device__ __forceinline__ void euler_cfg_body(float* x, const float* __restrict__ v, int64_t n, int64_t per, int T, float cfg_scale,
+                                               const float* __restrict__ scale_rows, const float* dt_table, const int* step, float dt_val,
+                                               int has_uncond, const EulerKeep& kp, float weight) {
     const int k = step ? *step : 0;
     const float dt = dt_table ? dt_table[k] : dt_val;
     KeepAt ka{};
@@ -30,12 +32,25 @@ __global__ void euler_cfg_kernel(float* x, const float* __restrict__ v, int64_t 
     if (has_uncond) {
         vu = v[n + i];
         if constexpr (ROWS) s = scale_rows[b];
+        if constexpr (SCHED) s = fmaf(weight, s - 1.f, 1.f);
     }
     if constexpr (KEEP) {
         ka.m = kp.mask[b * T + (i - b * per) % T];
         ka.sigma_min = kp.sigma_min; ka.ref = kp.ref[i]; ka.x0 = kp.x0[i];
     }
     x[i] = euler_cfg_update<KEEP>(x[i], vc, vu, has_uncond != 0, s, dt, ka);
+}
+template <bool KEEP, bool ROWS>
+__global__ void euler_cfg_kernel(float* x, const float* __restrict__ v, int64_t n, int64_t per, int T, float cfg_scale,
+                                 const float* __restrict__ scale_rows, const float* dt_table, const int* step, float dt_val,
+                                 int has_uncond, const EulerKeep kp) {
+    euler_cfg_body<KEEP, ROWS, false>(x, v, n, per, T, cfg_scale, scale_rows, dt_table, step, dt_val, has_uncond, kp, 1.f);
+}
+template <bool KEEP>
+__global__ void euler_cfg_sched_kernel(float* x, const float* __restrict__ v, int64_t n, int64_t per, int T,
+                                       const float* __restrict__ scale_rows, const float* dt_table, const int* step, float dt_val,
+                                       int has_uncond, const EulerKeep kp, float weight) {
+    euler_cfg_body<KEEP, true, true>(x, v, n, per, T, 0.f, scale_rows, dt_table, step, dt_val, has_uncond, kp, weight);
 }
 int launch_euler_cfg(const EulerStep& es, const float* v, int B, int64_t per, int T, int has_uncond, float dt_val, hipStream_t st) {
     if (es.keep && (!es.dt_table || !es.step || T < 1)) VB_FAIL(VB_E_INVALID, "euler_cfg: a known region needs the step tables and T");
@@ -45,8 +60,13 @@ int launch_euler_cfg(const EulerStep& es, const float* v, int B, int64_t per, in
                            es.x, v, n, per, T, es.cfg_scale, es.scale_rows, es.dt_table, (const int*)es.step, dt_val, has_uncond,
                            es.keep ? *es.keep : EulerKeep{});
     };
+    auto go_sched = [&](auto keep) {
+        hipLaunchKernelGGL((euler_cfg_sched_kernel<decltype(keep)::value>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, es.x, v, n, per, T,
+                           es.scale_rows, es.dt_table, (const int*)es.step, dt_val, has_uncond, es.keep ? *es.keep : EulerKeep{}, es.row_weight);
+    };
     const std::true_type yes; const std::false_type no;
-    if (es.keep && es.scale_rows) go(yes, yes); else if (es.keep) go(yes, no); else if (es.scale_rows) go(no, yes); else go(no, no);
+    if (es.scale_rows && has_uncond && es.row_weight != 1.f) { if (es.keep) go_sched(yes); else go_sched(no); }
+    else if (es.keep && es.scale_rows) go(yes, yes); else if (es.keep) go(yes, no); else if (es.scale_rows) go(no, yes); else go(no, no);
     VB_CHECK_LAUNCH();
     return VB_OK;
 }

@@ -318,8 +318,33 @@ class DiTEngine:
         arr = (C.c_int32 * nw)(*starts)
         return L.Windows(arr, nw), arr
 
+    @staticmethod
+    def _guidance_struct(guidance, n: int):
+        """validate per-step guidance weights - n finite numbers in [0, 16], the library's rules (include/versband_hip.h), stated here
+        first so that the error names the caller's argument - and lay them out as vb_guidance (a host array, read during the call).
+        All ones is the plain call.  Returns (struct or None, the array to hold)."""
+        if torch.is_tensor(guidance):
+            guidance = guidance.tolist()
+        try:
+            vals = list(guidance)
+        except TypeError:
+            raise TypeError(f"guidance must be a sequence of {n} step weights, got {type(guidance).__name__}") from None
+        if any(isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) for v in vals):
+            raise TypeError("guidance must hold numbers (one weight per step)")
+        if len(vals) != n:
+            raise ValueError(f"guidance has {len(vals)} entries for {n} steps")
+        vals = [float(np.float32(v)) for v in vals]
+        for k, v in enumerate(vals):
+            if not (np.isfinite(v) and 0.0 <= v <= 16.0):
+                raise ValueError(f"guidance[{k}] = {v} is not a finite value in [0, 16]")
+        if all(v == 1.0 for v in vals):
+            return None, None
+        arr = (C.c_float * n)(*vals)
+        return L.Guidance(arr), arr
+
     def sample_cfg(self, x0: Tensor, cond: dict, t_idx_table: Sequence[int], dt_table: Sequence[float], scale,
-                   noise=None, seed: int = 0, clip_base: int = 0, return_traj: bool = False, keep=None, clip_ids=None, windows=None):
+                   noise=None, seed: int = 0, clip_base: int = 0, return_traj: bool = False, keep=None, clip_ids=None, windows=None,
+                   guidance=None):
         """n Euler steps with classifier-free guidance; x0 [B,C,T] is not modified.
         scale: one number for the batch, or B values (sequence / float32 tensor): row b is guided by scale[b].  clip_ids: B global clip
         indices (sequence / int64 tensor): row b draws its router noise as clip clip_ids[b] instead of clip_base + b (vb_sample_cfg_rows).
@@ -328,7 +353,11 @@ class DiTEngine:
         windows: a sequence of nw ascending window starts - the B rows are then nw windows (row = w * (B // nw) + b, T tokens each) of
         B // nw long clips, and after every step the overlapping tokens of neighbouring windows take one consensus value, so they are
         bit-identical in the result and in every trajectory state (vb_sample_cfg_windows).  Combines with all of the above; scale,
-        clip_ids and keep stay per ROW."""
+        clip_ids and keep stay per ROW.
+        guidance: one weight in [0, 16] per step (vb_sample_cfg_sched) - step k runs under the effective scale 1 + guidance[k] * (scale - 1):
+        1 is the plain step, 0 evaluates the conditional branch alone (about half the step's network time), anything between or
+        beyond scales the guidance.  All ones or None is the plain call; with one branch (nb = 1) the weights are checked and unused.
+        Combines with all of the above."""
         dev = self.ctx.device
         B, nb, T, Lc = cond["B"], cond["nb"], cond["T"], cond["L"]
         wstruct, held_win = self._windows_struct(windows, B, T) if windows is not None else (None, None)
@@ -350,7 +379,14 @@ class DiTEngine:
         traj = torch.empty(n + 1, *x.shape, dtype=torch.float32, device=dev) if return_traj else None
         ns, held = self._noise_struct(noise, seed, clip_base, 0)
         ws = self._workspace(B, nb, T, Lc)
-        if wstruct is not None:
+        gs, held_guid = self._guidance_struct(guidance, n) if guidance is not None else (None, None)
+        if gs is not None:
+            ks, held_keep = self._keep_struct(keep, B, T, n) if keep is not None else (None, None)
+            L.check(self.ctx.lib.vb_sample_cfg_sched(self.ctx.handle, L.ptr(x), L.ptr(cond["buf"]), B, nb, T, Lc, n, L.ptr(tt), L.ptr(dd),
+                                                     float(scale), C.byref(gs), C.byref(wstruct) if wstruct is not None else None,
+                                                     C.byref(rs) if rs is not None else None, C.byref(ks) if ks is not None else None,
+                                                     C.byref(ns), L.ptr(traj), L.ptr(ws), L.stream_ptr()), "vb_sample_cfg_sched")
+        elif wstruct is not None:
             ks, held_keep = self._keep_struct(keep, B, T, n) if keep is not None else (None, None)
             L.check(self.ctx.lib.vb_sample_cfg_windows(self.ctx.handle, L.ptr(x), L.ptr(cond["buf"]), B, nb, T, Lc, n, L.ptr(tt), L.ptr(dd),
                                                        float(scale), C.byref(wstruct), C.byref(rs) if rs is not None else None,

@@ -90,7 +90,7 @@ def plan_continue(plan: Sequence[Tuple[int, int]]) -> List[Tuple[int, int, int]]
 
 def sample_long(engine, x0: Tensor, t5_cond: Tensor, t5_uncond: Tensor, midi: Tensor, beats: Tensor, t_idx_table, dt_table,
                 scale: float, window: int = 1500, overlap: int = 128, seed: int = 0, clip_base: int = 0, mode: str = "crossfade",
-                t_next=None, sigma_min: float = 1e-4, return_windows: bool = False):
+                t_next=None, sigma_min: float = 1e-4, return_windows: bool = False, guidance=None):
     """x0 [B,C,T], t5_* [B,L,1024], midi/beats [B,1,2T] -> z [B,C,T] for T beyond the DiT's max_len.
     mode "crossfade" (default): all windows as one batch of independent clips, latents cross-faded over the overlaps.
     mode "continue": windows in order, each with its overlap held on the probability path of the previous window's result (needs
@@ -99,9 +99,11 @@ def sample_long(engine, x0: Tensor, t5_cond: Tensor, t5_uncond: Tensor, midi: Te
     consensus value after every step (engine.sample_cfg(windows=...)); the windows agree bit for bit in their overlaps, no cross-fade.
     (A plan whose shifted last window starts before the end of the window two before it puts a token under three windows and is
     refused by the engine's validation.)
+    guidance: per-step guidance weights, handed to every sampler call of the mode (engine.sample_cfg(guidance=...)).
     return_windows (continue and joint modes) also returns every window's full result, overlaps included: (z, [z_w [B,C,n]])."""
     if mode not in ("crossfade", "continue", "joint"):
         raise ValueError(f"sample_long: mode {mode!r} (crossfade | continue | joint)")
+    gk = {} if guidance is None else {"guidance": guidance}        # (None: the calls are the ones they were)
     B, C, T = x0.shape
     window = min(window, engine.cfg.max_len)
     plan = plan_windows(T, window, overlap)
@@ -120,7 +122,7 @@ def sample_long(engine, x0: Tensor, t5_cond: Tensor, t5_uncond: Tensor, midi: Te
         if t_next is None:
             raise ValueError('sample_long(mode="continue") needs t_next (model.euler_times of the step tables\' grid)')
         return _sample_continue(engine, x0, t5_cond, t5_uncond, midi, beats, t_idx_table, dt_table, scale, plan, seed, clip_base, t_next,
-                                sigma_min, return_windows)
+                                sigma_min, return_windows, guidance)
     # windows become extra batch rows: row = w * B + b
     xw = torch.cat([x0[:, :, s:s + n] for s, _ in plan], dim=0)
     mw = torch.cat([midi[:, 2 * s:2 * (s + n)] for s, _ in plan], dim=0)
@@ -129,16 +131,16 @@ def sample_long(engine, x0: Tensor, t5_cond: Tensor, t5_uncond: Tensor, midi: Te
     cond = engine.precompute_cond(t5, mw, bw, n, persistent=True)
     if mode == "joint":
         if nw == 1:           # T <= window: the plain call
-            zw = engine.sample_cfg(xw, cond, t_idx_table, dt_table, scale, seed=seed, clip_base=clip_base * nw)
+            zw = engine.sample_cfg(xw, cond, t_idx_table, dt_table, scale, seed=seed, clip_base=clip_base * nw, **gk)
             return (zw, [zw]) if return_windows else zw
-        zw = engine.sample_cfg(xw, cond, t_idx_table, dt_table, scale, seed=seed, clip_base=clip_base * nw, windows=[s for s, _ in plan])
+        zw = engine.sample_cfg(xw, cond, t_idx_table, dt_table, scale, seed=seed, clip_base=clip_base * nw, windows=[s for s, _ in plan], **gk)
         parts = [zw[w * B:(w + 1) * B] for w in range(nw)]
         # every token from exactly one window (plan_continue); the overlaps hold the same bits in both, so there is nothing to fade
         out = torch.empty(B, C, T, dtype=zw.dtype, device=zw.device)
         for (s, m, known), p in zip(plan_continue(plan), parts):
             out[:, :, s + known:s + m] = p[:, :, known:]
         return (out, parts) if return_windows else out
-    zw = engine.sample_cfg(xw, cond, t_idx_table, dt_table, scale, seed=seed, clip_base=clip_base * nw)
+    zw = engine.sample_cfg(xw, cond, t_idx_table, dt_table, scale, seed=seed, clip_base=clip_base * nw, **gk)
     if nw == 1:
         return zw
     if zw.is_cuda and all(m == n for _, m in plan):
@@ -148,9 +150,10 @@ def sample_long(engine, x0: Tensor, t5_cond: Tensor, t5_uncond: Tensor, midi: Te
 
 
 def _sample_continue(engine, x0, t5_cond, t5_uncond, midi, beats, t_idx_table, dt_table, scale, plan, seed, clip_base, t_next, sigma_min,
-                     return_windows=False):
+                     return_windows=False, guidance=None):
     """mode="continue" of sample_long: one sampler call of B rows per window.  Window w's noise key is the one it has as rows
     [w*B, (w+1)*B) of the cross-fade batch, so window 0 equals today's window 0."""
+    gk = {} if guidance is None else {"guidance": guidance}
     B, C, T = x0.shape
     nw = len(plan)
     dev = engine.ctx.device
@@ -172,7 +175,7 @@ def _sample_continue(engine, x0, t5_cond, t5_uncond, midi, beats, t_idx_table, d
             mask.zero_()
             mask[:, :known] = 1.0
             keep = (ref, xn, mask, t_next, sigma_min)
-        zw = engine.sample_cfg(xw, cond, t_idx_table, dt_table, scale, seed=seed, clip_base=clip_base * nw + w * B, keep=keep)
+        zw = engine.sample_cfg(xw, cond, t_idx_table, dt_table, scale, seed=seed, clip_base=clip_base * nw + w * B, keep=keep, **gk)
         out[:, :, s + known:s + n] = zw[:, :, known:]
         if return_windows:
             parts.append(zw)

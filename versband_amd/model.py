@@ -427,6 +427,47 @@ def euler_times(timesteps: int, t_start: Optional[int] = None) -> List[float]:
     return out
 
 
+def guidance_interval_weights(timesteps: int, lo: float, hi: float, t_start: Optional[int] = None) -> List[float]:
+    """per-step guidance weights of a guidance interval on the grid of euler_tables(timesteps, t_start): 1.0 where the step's start time
+    t_span[k] lies in [lo, hi] (both ends included, compared in float32 like the grid), 0.0 elsewhere - the step is then a plain
+    conditional one (DiTEngine.sample_cfg(guidance=...))."""
+    lo, hi = float(lo), float(hi)
+    if not (np.isfinite(lo) and np.isfinite(hi)) or lo > hi:
+        raise ValueError(f"guidance interval [{lo}, {hi}]: two finite values lo <= hi")
+    t_span = torch.linspace(0, 1, timesteps)
+    if t_start is not None:
+        t_span = t_span[t_start:]
+    lo32, hi32 = np.float32(lo), np.float32(hi)
+    return [1.0 if lo32 <= np.float32(t) <= hi32 else 0.0 for t in t_span[:-1].tolist()]
+
+
+def guidance_arg(guidance_weights, guidance_interval, timesteps: int, t_start: Optional[int] = None):
+    """the guidance arguments of CFMSampler.sample_cfg -> the `guidance` list of DiTEngine.sample_cfg, or None for the plain call (neither
+    given, or every weight 1).  At most one of the two; the weights are n finite numbers in [0, 16], the interval is (lo, hi)."""
+    if guidance_weights is not None and guidance_interval is not None:
+        raise ValueError("guidance_weights and guidance_interval do not go together: give at most one")
+    if guidance_interval is not None:
+        try:
+            lo, hi = guidance_interval
+        except (TypeError, ValueError):
+            raise ValueError("guidance_interval must be (lo, hi)") from None
+        w = guidance_interval_weights(timesteps, lo, hi, t_start)
+    elif guidance_weights is not None:
+        n = len(euler_tables(timesteps, t_start)[0])
+        w = guidance_weights.tolist() if torch.is_tensor(guidance_weights) else list(guidance_weights)
+        if any(isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) for v in w):
+            raise TypeError("guidance_weights must hold numbers (one weight per step)")
+        if len(w) != n:
+            raise ValueError(f"guidance_weights has {len(w)} entries for {n} steps")
+        w = [float(v) for v in w]
+        for k, v in enumerate(w):
+            if not (np.isfinite(v) and 0.0 <= v <= 16.0):
+                raise ValueError(f"guidance_weights[{k}] = {v} is not a finite value in [0, 16]")
+    else:
+        return None
+    return None if all(v == 1.0 for v in w) else w
+
+
 def keep_block(x_known, keep_mask, keep_noise, x_latent, t_start, shape, timesteps, sigma_min):
     """the known-region arguments of CFMSampler.sample_cfg -> the (ref, x0, mask, t_next, sigma_min) block of DiTEngine.sample_cfg, or None
     when no region is given.  x_known is in the sampler's latent scale; keep_mask [B,T] or [T]; keep_noise is the start noise of the
@@ -488,7 +529,7 @@ class CFMSampler(object):
     @torch.no_grad()
     def sample_cfg(self, cond, unconditional_guidance_scale, unconditional_conditioning, batch_size=16, timesteps=None, shape=None,
                    x_latent=None, t_start=None, gumbel_noise=None, seed=None, clip_base=0, x_known=None, keep_mask=None, keep_noise=None,
-                   clip_ids=None, **kwargs):
+                   clip_ids=None, *, guidance_weights=None, guidance_interval=None, **kwargs):
         """:87-116.  Extra kwargs (S=, x_T=, verbose=) are tolerated and ignored like the reference does
         (SURVEY Q1/Q2).  gumbel_noise/seed/clip_base are additions: injected router noise for parity, or the
         (seed, global clip index) that keys the on-device counter-based draws.
@@ -497,10 +538,14 @@ class CFMSampler(object):
         x_known + sigma_min * keep_noise; the others are generated in agreement with them.  keep_noise defaults to the start noise
         when t_start is None and is required with t_start.
         unconditional_guidance_scale may hold one value per row (sequence / float32 tensor) and clip_ids one global clip index per row
-        (addition; DiTEngine.sample_cfg): rows of different scales or non-contiguous clips then share the call."""
+        (addition; DiTEngine.sample_cfg): rows of different scales or non-contiguous clips then share the call.
+        guidance_weights (one weight in [0, 16] per step) or guidance_interval = (lo, hi) (addition, keyword-only, at most one of them):
+        step k runs under the effective scale 1 + w_k (scale - 1); the interval is w_k = 1 where the step starts at t in [lo, hi] and 0
+        elsewhere, and a step of weight 0 evaluates the conditional branch alone."""
         shape = self._shape(shape, batch_size)
         timesteps = 25 if timesteps is None else timesteps
         idx, dts = euler_tables(timesteps, t_start)
+        guidance = guidance_arg(guidance_weights, guidance_interval, timesteps, t_start)
         dev = self.model.device
         x0 = torch.randn(shape, device=dev) if x_latent is None else x_latent
         keep = keep_block(x_known, keep_mask, keep_noise, x0, t_start, shape, timesteps, self.model.sigma_min)
@@ -512,7 +557,8 @@ class CFMSampler(object):
         if isinstance(scale, (int, float, np.integer, np.floating)) and not isinstance(scale, bool):
             scale = float(scale)
         x, traj = self.model.dit_engine().sample_cfg(x0, pc, idx, dts, scale, noise=gumbel_noise,
-                                                     seed=seed, clip_base=clip_base, return_traj=True, keep=keep, clip_ids=clip_ids)
+                                                     seed=seed, clip_base=clip_base, return_traj=True, keep=keep, clip_ids=clip_ids,
+                                                     **({} if guidance is None else {"guidance": guidance}))
         return traj[-1], traj
 
     @torch.no_grad()
