@@ -2,6 +2,7 @@
 // host drivers at the end of t5.hip / melnet.hip): the context, the workspace carver, the DiT layouts and the calls that cross files.
 // No device allocation happens on the host side: all scratch is carved out of caller buffers (sizes from *_bytes()).
 #pragma once
+#include <algorithm>
 #include <array>
 #include <tuple>
 #include <vector>
@@ -15,7 +16,8 @@ struct NetProgram {
     int in_ch = 0, out_ch = 0, in_tmul = 1, out_tmul = 1;
     bool loaded = false;
 };
-// one captured + instantiated step loop of vb_sample_cfg (hipGraph), keyed by everything the launches bake in
+// one captured + instantiated step loop of vb_sample_cfg (hipGraph), keyed by everything the launches bake in (the key of a call is
+// made in one place: sample_key, beside SampleCall)
 struct SampleGraph {
     struct Key {
         const void* x = nullptr; const void* cond = nullptr; const void* ws = nullptr;
@@ -146,6 +148,35 @@ struct DitEval {
     const EulerStep* euler = nullptr;                           // sampler only: FinalLayer does this step's update in the same launch (x in place, v_out not written)
 };
 int dit_forward(vb_ctx* ctx, const DitEval& ev, hipStream_t st);
+
+// ---- sampler.hip: one sampler call ------------------------------------------------------------
+// One call of vb_sample_cfg_sched (the older entry points forward to it), validated and normalised where it is made
+// (sampler.hip:sample_call): the step loop launches from it and the graph cache keys on it, so an option is one member here.
+// THE RULE: anything a launch of the step loop bakes in is in the key (sample_key, below), by ADDRESS where the kernels read through the
+// pointer when they run, by VALUE where the launch argument - or the choice of launch - holds the value itself (SampleGraph::Key says which).
+struct SampleCall {
+    float* x = nullptr; const void* cond = nullptr; void* ws = nullptr;
+    int B = 0, nb = 0, T = 0, L = 0, n_steps = 0;
+    float cfg_scale = 0.f;                  // 0 beside rows.cfg_scale, which replaces it
+    vb_rows rows{nullptr, nullptr};         // either may be null: clip b is guided by rows.cfg_scale[b] (unused with nb == 1) and draws its router noise as clip rows.clip[b]
+    const vb_keep* keep = nullptr;          // every update also puts the known tokens back on the probability path at the time after the step (t_next: a workspace table, like dt)
+    // windows: more than one (one is the plain call) - the rows are wp.nw windows of B / nw clips; after every update, in either form, the
+    // overlapping tokens of neighbouring windows take their consensus value, before the trajectory copy
+    WindowPlan wp; bool windows = false;
+    const float* gw = nullptr;              // host [n_steps] step weights (sample_steps has the kinds of step); null unless nb == 2 and some weight differs from 1
+    const vb_noise* noise = nullptr;        // NOT keyed: the noise key travels through device memory, injected arrays keep a call eager
+};
+static_assert(PRE_STEPS <= 64, "the graph key holds the step weights of a graphable call (SampleGraph::Key::weights)");
+inline SampleGraph::Key sample_key(const SampleCall& sc) {
+    SampleGraph::Key key;
+    key.x = sc.x; key.cond = sc.cond; key.ws = sc.ws; key.B = sc.B; key.nb = sc.nb; key.T = sc.T; key.L = sc.L; key.n_steps = sc.n_steps; key.cfg_scale = sc.cfg_scale;
+    key.tune_gen = vb_tune_generation();
+    if (sc.keep) { key.keep_ref = sc.keep->ref; key.keep_x0 = sc.keep->x0; key.keep_mask = sc.keep->mask; key.sigma_min = sc.keep->sigma_min; }
+    key.rows_scale = sc.rows.cfg_scale; key.rows_clip = sc.rows.clip;
+    if (sc.windows) { key.nw = sc.wp.nw; std::copy(sc.wp.s, sc.wp.s + 64, key.starts.begin()); }
+    if (sc.gw) { key.sched = true; std::copy(sc.gw, sc.gw + sc.n_steps, key.weights.begin()); }      // (a keyed call is graphable: n_steps <= PRE_STEPS = 64)
+    return key;
+}
 
 // ---- convnet.hip ----------------------------------------------------------------------------
 int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, void* ws, hipStream_t st);

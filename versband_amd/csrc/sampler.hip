@@ -1,29 +1,22 @@
 // CFG / Euler sampler (cfm1_audio_sampler.py:107-116): the step loop around dit_forward and its hipGraph cache.
-#include <algorithm>
-
 #include "engine.h"
 
 // the launches of one sampler call after its tables are in place: tabulation of the per-step conditioning vectors, then n_steps x
 // [step bookkeeping, one network evaluation of both CFG branches, Euler + guidance update]   (cfm1_audio_sampler.py:107-116)
-// keep != nullptr (vb_sample_cfg_keep): every update also puts the known tokens back on the probability path at the time after the step
-// rows (vb_sample_cfg_rows; either member may be null): clip b is guided by rows.cfg_scale[b] and draws its router noise as clip rows.clip[b]
-// wins != nullptr (vb_sample_cfg_windows): the rows are wins->nw windows of B / nw clips; after every update - in either form, the same
-// launch - the overlapping tokens of neighbouring windows take their consensus value, before the trajectory copy
-// gw != nullptr (vb_sample_cfg_sched; host array, n_branch == 2 and not all ones): step k is one of three kinds by gw[k] -
-//   1: today's step, launch for launch;
+// engine.h:SampleCall says what each member of the call adds to a step.  With step weights (sc.gw) step k is one of three kinds by gw[k] -
+//   1: the plain step, launch for launch;
 //   0: a single-branch step - the network runs over the conditional rows alone (DitEval::nb_active = 1), FinalLayer writes their velocity
-//      and the update is the separate launch without an unconditional half, as in an n_branch == 1 call;
+//      and the update is the separate launch without an unconditional half, as in an nb == 1 call;
 //   else: both branches under the step's effective scale fmaf(gw[k], s - 1, 1): a scalar s is combined here and handed to the existing
 //      instances, per-row scales take the *_sched_kernel instances with gw[k] in their arguments.
 // The kinds are baked into a captured graph (its key holds the weights).  Keep blend, window consensus and trajectory copy do not
 // depend on the kind.
-static_assert(PRE_STEPS <= 64, "the graph key holds the step weights of a graphable call (SampleGraph::Key::weights)");
-static int sample_steps(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps, float cfg_scale,
-                        const vb_rows& rows, const vb_keep* keep, const WindowPlan* wins, const float* gw, const vb_noise* noise, float* traj,
-                        void* ws, hipStream_t st) {
+static EulerKeep euler_keep(const vb_keep& k, const WsL& s) { return EulerKeep{k.ref, k.x0, k.mask, s.tn_table, k.sigma_min}; }
+static int sample_steps(vb_ctx* ctx, const SampleCall& sc, float* traj, hipStream_t st) {
     const vb_dit_config& c = ctx->cfg;
+    const int B = sc.B, n_branch = sc.nb, T = sc.T, L = sc.L, n_steps = sc.n_steps;
     const DitPlan plan = dit_plan(ctx, B, n_branch, T, L);
-    WsL s = carve_ws(ws, c, B, n_branch, T, L);
+    WsL s = carve_ws(sc.ws, c, B, n_branch, T, L);
     const int Beff = B * n_branch;
     const int64_t per = (int64_t)c.in_channels * T;
     // (a kernel, not hipMemsetAsync: the captured step loop then consists of kernel nodes only)
@@ -34,7 +27,7 @@ static int sample_steps(vb_ctx* ctx, float* x, const void* cond, int B, int n_br
     const int D = c.hidden, MODW = s.MODW;
     if (tab) {
         const vb_dit_weights& w = ctx->w;
-        CondL cd = carve_cond(const_cast<void*>(cond), c, B, n_branch, T, L);
+        CondL cd = carve_cond(const_cast<void*>(sc.cond), c, B, n_branch, T, L);
         VB_TRY(launch_gemv_rows_idx(w.t_freq_table, 256, s.t_table, nullptr, 0, 1, w.t_mlp0_w, w.t_mlp0_b, n_steps, D, 256, 0, s.temb0_s, D, st, T_FREQ_ROWS));
         VB_TRY(launch_gemv_rows(s.temb0_s, D, nullptr, 0, 1, w.t_mlp2_w, w.t_mlp2_b, n_steps, D, D, 1, s.temb_s, D, st));
         VB_TRY(launch_iota_div(s.row_step, n_steps * Beff, Beff, st));
@@ -61,18 +54,17 @@ static int sample_steps(vb_ctx* ctx, float* x, const void* cond, int B, int n_br
     // (the device step counter s.step ends a call at n_steps with the fused Euler launch and at n_steps - 1 with the separate launches; nothing
     //  reads it after the call, launch_step_ctl resets it at k == 0)
     const bool fuse = plan.final_route == FINAL_EULER_FUSED;
-    EulerKeep kp{};
-    if (keep) kp = EulerKeep{keep->ref, keep->x0, keep->mask, s.tn_table, keep->sigma_min};
+    const EulerKeep kp = sc.keep ? euler_keep(*sc.keep, s) : EulerKeep{};
     EulerStep es;
-    es.x = x; es.cfg_scale = cfg_scale; es.dt_table = s.dt_table; es.keep = keep ? &kp : nullptr;
-    es.scale_rows = n_branch == 2 ? rows.cfg_scale : nullptr;      // (one branch: there is nothing to guide, the scales are unused)
+    es.x = sc.x; es.cfg_scale = sc.cfg_scale; es.dt_table = s.dt_table; es.keep = sc.keep ? &kp : nullptr;
+    es.scale_rows = n_branch == 2 ? sc.rows.cfg_scale : nullptr;      // (one branch: there is nothing to guide, the scales are unused)
     es.step = s.step; es.t_idx_cur = s.t_idx_cur; es.t_table = s.t_table; es.n_steps = n_steps; es.Beff = Beff;
     bool advanced = false;        // the previous step's update launch advanced the device step counter (the fused form does)
     bool single_prev = false;
     for (int k = 0; k < n_steps; ++k) {
         RoctxRange rs("euler_step");
-        const float wk = gw ? gw[k] : 1.f;
-        const bool single = gw && wk == 0.f;
+        const float wk = sc.gw ? sc.gw[k] : 1.f;
+        const bool single = sc.gw && wk == 0.f;
         const bool fuse_k = fuse && !single;
         // the router's count tables are in step only while every evaluation counts the same rows (DitPlan::router_counts): a change between
         // one and two branches starts them afresh
@@ -83,21 +75,21 @@ static int sample_steps(vb_ctx* ctx, float* x, const void* cond, int B, int n_br
         EulerStep ek = es;
         ek.k = k;
         if (single) ek.scale_rows = nullptr;                          // (one branch: nothing to guide, as in an n_branch == 1 call)
-        else if (gw && wk != 1.f) {
-            if (ek.scale_rows) ek.row_weight = wk; else ek.cfg_scale = fmaf(wk, cfg_scale - 1.f, 1.f);
+        else if (sc.gw && wk != 1.f) {
+            if (ek.scale_rows) ek.row_weight = wk; else ek.cfg_scale = fmaf(wk, sc.cfg_scale - 1.f, 1.f);
         }
         DitEval ev;
-        ev.x = x; ev.t_idx = s.t_idx_cur; ev.cond = cond; ev.ws = ws; ev.B = B; ev.nb = n_branch; ev.T = T; ev.L = L;
+        ev.x = sc.x; ev.t_idx = s.t_idx_cur; ev.cond = sc.cond; ev.ws = sc.ws; ev.B = B; ev.nb = n_branch; ev.T = T; ev.L = L;
         if (single) ev.nb_active = 1;
-        ev.noise = noise; ev.noise_step = k; ev.step_ptr = s.step; ev.v_out = s.v; ev.clip_rows = rows.clip;
+        ev.noise = sc.noise; ev.noise_step = k; ev.step_ptr = s.step; ev.v_out = s.v; ev.clip_rows = sc.rows.clip;
         if (tab) { ev.pre_mod = s.mod_s + (size_t)k * Beff * MODW; ev.pre_hl = s.hl_s + (size_t)k * c.depth * 2; }
         ev.evals_before = k * c.depth;
         if (fuse_k) ev.euler = &ek;
         VB_TRY(dit_forward(ctx, ev, st));
         if (!fuse_k) VB_TRY(launch_euler_cfg(ek, s.v, B, per, T, n_branch == 2 && !single, 0.f, st));
         advanced = fuse_k;
-        if (wins) VB_TRY(launch_window_blend(x, *wins, B / wins->nw, c.in_channels, T, st));
-        if (traj) VB_HIP(hipMemcpyAsync(traj + (size_t)(k + 1) * B * per, x, (size_t)B * per * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (sc.windows) VB_TRY(launch_window_blend(sc.x, sc.wp, B / sc.wp.nw, c.in_channels, T, st));
+        if (traj) VB_HIP(hipMemcpyAsync(traj + (size_t)(k + 1) * B * per, sc.x, (size_t)B * per * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     return VB_OK;
 }
@@ -121,6 +113,80 @@ static SampleGraph* graph_entry(vb_ctx* ctx, const SampleGraph::Key& key) {
     e->last_use = ++ctx->graph_clock;
     e->seen += 1;
     return e;
+}
+
+// ---- vb_sample_cfg_sched as its steps: sample_call, sample_prologue, sample_graph | sample_steps -------------------------------
+// check the ABI arguments before anything is launched and state the call once.  Every normalisation happens here: per-row scales zero
+// the scalar one, a schedule of all ones or beside one branch (nothing to guide) is the plain call, and so is one window.
+static int sample_call(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps, float cfg_scale,
+                       const vb_guidance* guidance, const vb_windows* win, const vb_rows* rows, const vb_keep* keep, const vb_noise* noise,
+                       void* ws, SampleCall& sc) {
+    sc.x = x; sc.cond = cond; sc.ws = ws; sc.B = B; sc.nb = n_branch; sc.T = T; sc.L = L; sc.n_steps = n_steps; sc.keep = keep; sc.noise = noise;
+    if (rows) sc.rows = *rows;
+    sc.cfg_scale = sc.rows.cfg_scale ? 0.f : cfg_scale;          // unused beside the array; one value in the graph key
+    if (!ctx || !ctx->dit_loaded) VB_FAIL(VB_E_STATE, "sample_cfg: DiT not loaded");
+    if (n_steps < 1 || n_steps > 1024) VB_FAIL(VB_E_INVALID, "sample_cfg: n_steps=%d", n_steps);
+    if (keep && (!keep->ref || !keep->x0 || !keep->mask || !keep->t_next)) VB_FAIL(VB_E_INVALID, "sample_cfg_keep: ref, x0, mask and t_next must all be given");
+    if (guidance && guidance->weight && n_branch == 2) {          // (host array)
+        for (int k = 0; k < n_steps; ++k) {
+            const float w = guidance->weight[k];
+            if (!(w >= 0.f && w <= 16.f)) VB_FAIL(VB_E_INVALID, "sample_cfg_sched: weight[%d] = %g is not a finite value in [0, 16]", k, (double)w);
+            if (w != 1.f) sc.gw = guidance->weight;
+        }
+    }
+    if (win) VB_TRY(window_plan(win->starts, win->nw, B, T, &sc.wp));
+    sc.windows = win && sc.wp.nw > 1;
+    return VB_OK;
+}
+
+// what runs in front of the step loop, outside a captured graph: the step tables' way into the workspace, the state the first
+// evaluation sees (and traj[0] holds), the noise key
+static int sample_prologue(vb_ctx* ctx, const SampleCall& sc, const int64_t* t_idx_table, const float* dt_table, float* traj, hipStream_t st) {
+    const vb_dit_config& c = ctx->cfg;
+    WsL s = carve_ws(sc.ws, c, sc.B, sc.nb, sc.T, sc.L);
+    const int64_t per = (int64_t)c.in_channels * sc.T;
+    // (tables may live on the host or on the device; a host caller must keep them alive until the stream has consumed them)
+    VB_HIP(hipMemcpyAsync(s.t_table, t_idx_table, (size_t)sc.n_steps * sizeof(int64_t), hipMemcpyDefault, st));
+    VB_HIP(hipMemcpyAsync(s.dt_table, dt_table, (size_t)sc.n_steps * sizeof(float), hipMemcpyDefault, st));
+    if (sc.keep) {
+        // the times travel like the step sizes do (a device table read behind the step counter); the entry projection runs here, outside
+        // the captured loop, so that traj[0] is the state the first evaluation sees
+        VB_HIP(hipMemcpyAsync(s.tn_table, sc.keep->t_next, (size_t)sc.n_steps * sizeof(float), hipMemcpyDefault, st));
+        VB_TRY(launch_keep_project(sc.x, sc.B, per, sc.T, s.dt_table, euler_keep(*sc.keep, s), st));
+    }
+    // rows that disagree in their overlaps start from the consensus; rows cut from one start noise are not changed by it
+    if (sc.windows) VB_TRY(launch_window_blend(sc.x, sc.wp, sc.B / sc.wp.nw, c.in_channels, sc.T, st));
+    if (traj) VB_HIP(hipMemcpyAsync(traj, sc.x, (size_t)sc.B * per * sizeof(float), hipMemcpyDeviceToDevice, st));
+    // the noise key travels through device memory (the router reads it behind the step counter): nothing a replayed graph bakes in
+    const vb_noise* noise = sc.noise;
+    return launch_sampler_params(s.step, noise ? noise->seed : 0, noise ? noise->clip_base : 0, noise ? noise->nfe : 0, st);
+}
+
+// ---- the step loop as ONE hipGraph (cfm1_audio_sampler.py:107-116 is ~3000 dependent launches at 50 steps): a call whose
+// buffers and shape were seen before replays the captured, instantiated graph - one host call instead of thousands, which is
+// what bounds small batches and several concurrent streams (the HIP runtime serialises launches of different host threads).
+// Returns the call's graph, captured now if its key arrives for the second time; nullptr (run eagerly) when the key is new (its first
+// call also warms every kernel's one-time attributes outside a capture) or capture was refused once.
+static hipGraphExec_t sample_graph(vb_ctx* ctx, const SampleCall& sc, hipStream_t st) {
+    SampleGraph* e = graph_entry(ctx, sample_key(sc));
+    if (!e->exec && !e->failed && e->seen >= 2) {
+        if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+            const int rc = sample_steps(ctx, sc, nullptr, st);
+            hipGraph_t gr = nullptr;
+            const hipError_t ee = hipStreamEndCapture(st, &gr);
+            if (rc == VB_OK && ee == hipSuccess && gr && hipGraphInstantiate(&e->exec, gr, nullptr, nullptr, 0) == hipSuccess) {
+                e->graph = gr;
+            } else {
+                if (gr) (void)hipGraphDestroy(gr);
+                e->exec = nullptr; e->failed = true;
+                (void)hipGetLastError();
+            }
+        } else {
+            e->failed = true;
+            (void)hipGetLastError();
+        }
+    }
+    return e->exec;
 }
 
 extern "C" {
@@ -158,85 +224,22 @@ int vb_sample_cfg_windows(vb_ctx* ctx, float* x, const void* cond, int B, int n_
 }
 int vb_sample_cfg_sched(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
                         const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_guidance* guidance,
-                        const vb_windows* win, const vb_rows* rows_in, const vb_keep* keep, const vb_noise* noise, float* traj, void* ws,
+                        const vb_windows* win, const vb_rows* rows, const vb_keep* keep, const vb_noise* noise, float* traj, void* ws,
                         void* stream) {
-    const vb_rows rows = rows_in ? *rows_in : vb_rows{nullptr, nullptr};
-    if (rows.cfg_scale) cfg_scale = 0.f;          // unused beside the array; one value in the graph key
-    if (!ctx || !ctx->dit_loaded) VB_FAIL(VB_E_STATE, "sample_cfg: DiT not loaded");
-    if (n_steps < 1 || n_steps > 1024) VB_FAIL(VB_E_INVALID, "sample_cfg: n_steps=%d", n_steps);
-    if (keep && (!keep->ref || !keep->x0 || !keep->mask || !keep->t_next)) VB_FAIL(VB_E_INVALID, "sample_cfg_keep: ref, x0, mask and t_next must all be given");
-    // the schedule (host array): checked before anything is launched; all ones, or one branch (nothing to guide), is the plain call
-    const float* gw = nullptr;
-    if (guidance && guidance->weight && n_branch == 2) {
-        for (int k = 0; k < n_steps; ++k) {
-            const float w = guidance->weight[k];
-            if (!(w >= 0.f && w <= 16.f)) VB_FAIL(VB_E_INVALID, "sample_cfg_sched: weight[%d] = %g is not a finite value in [0, 16]", k, (double)w);
-            if (w != 1.f) gw = guidance->weight;
-        }
-    }
-    WindowPlan wp;
-    if (win) VB_TRY(window_plan(win->starts, win->nw, B, T, &wp));
-    const WindowPlan* wins = win && wp.nw > 1 ? &wp : nullptr;      // (one window: the plain call, and its graph)
+    SampleCall sc;
+    VB_TRY(sample_call(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, guidance, win, rows, keep, noise, ws, sc));
     VB_HIP(hipSetDevice(ctx->device));
     RoctxRange rr("vb_sample_cfg");
     hipStream_t st = (hipStream_t)stream;
-    const vb_dit_config& c = ctx->cfg;
-    WsL s = carve_ws(ws, c, B, n_branch, T, L);
-    const int64_t per = (int64_t)c.in_channels * T;
-    // (tables may live on the host or on the device; a host caller must keep them alive until the stream has consumed them)
-    VB_HIP(hipMemcpyAsync(s.t_table, t_idx_table, (size_t)n_steps * sizeof(int64_t), hipMemcpyDefault, st));
-    VB_HIP(hipMemcpyAsync(s.dt_table, dt_table, (size_t)n_steps * sizeof(float), hipMemcpyDefault, st));
-    if (keep) {
-        // the times travel like the step sizes do (a device table read behind the step counter); the entry projection runs here, outside
-        // the captured loop, so that traj[0] is the state the first evaluation sees
-        VB_HIP(hipMemcpyAsync(s.tn_table, keep->t_next, (size_t)n_steps * sizeof(float), hipMemcpyDefault, st));
-        VB_TRY(launch_keep_project(x, B, per, T, s.dt_table, EulerKeep{keep->ref, keep->x0, keep->mask, s.tn_table, keep->sigma_min}, st));
-    }
-    // rows that disagree in their overlaps start from the consensus; rows cut from one start noise are not changed by it
-    if (wins) VB_TRY(launch_window_blend(x, wp, B / wp.nw, c.in_channels, T, st));
-    if (traj) VB_HIP(hipMemcpyAsync(traj, x, (size_t)B * per * sizeof(float), hipMemcpyDeviceToDevice, st));
-    // the noise key travels through device memory (the router reads it behind the step counter): nothing a replayed graph bakes in
-    VB_TRY(launch_sampler_params(s.step, noise ? noise->seed : 0, noise ? noise->clip_base : 0, noise ? noise->nfe : 0, st));
-
-    // ---- the step loop as ONE hipGraph (cfm1_audio_sampler.py:107-116 is ~3000 dependent launches at 50 steps): a call whose
-    // buffers and shape were seen before replays the captured, instantiated graph - one host call instead of thousands, which is
-    // what bounds small batches and several concurrent streams (the HIP runtime serialises launches of different host threads).
+    VB_TRY(sample_prologue(ctx, sc, t_idx_table, dt_table, traj, st));
     // Eager when: a trajectory or injected noise arrays are requested (parity path), the per-launch HIP-event profiler is on, the
-    // stream cannot capture (legacy default stream), VB_NO_GRAPH is set, or the key is new (its first call also warms every
-    // kernel's one-time attributes outside a capture).
+    // stream cannot capture (legacy default stream), VB_NO_GRAPH is set, or sample_graph has no graph for the call.
     const bool graphable = !vb_tune().no_graph && !prof_enabled() && !traj && !(noise && noise->g1) && n_steps <= PRE_STEPS && st != nullptr;
-    if (graphable) {
-        SampleGraph::Key key;
-        key.x = x; key.cond = cond; key.ws = ws; key.B = B; key.nb = n_branch; key.T = T; key.L = L; key.n_steps = n_steps; key.cfg_scale = cfg_scale;
-        key.tune_gen = vb_tune_generation();
-        if (keep) { key.keep_ref = keep->ref; key.keep_x0 = keep->x0; key.keep_mask = keep->mask; key.sigma_min = keep->sigma_min; }
-        key.rows_scale = rows.cfg_scale; key.rows_clip = rows.clip;
-        if (wins) { key.nw = wp.nw; std::copy(wp.s, wp.s + 64, key.starts.begin()); }
-        if (gw) { key.sched = true; std::copy(gw, gw + n_steps, key.weights.begin()); }      // (graphable: n_steps <= PRE_STEPS = 64)
-        SampleGraph* e = graph_entry(ctx, key);
-        if (!e->exec && !e->failed && e->seen >= 2) {
-            if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                const int rc = sample_steps(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, rows, keep, wins, gw, noise, nullptr, ws, st);
-                hipGraph_t gr = nullptr;
-                const hipError_t ee = hipStreamEndCapture(st, &gr);
-                if (rc == VB_OK && ee == hipSuccess && gr && hipGraphInstantiate(&e->exec, gr, nullptr, nullptr, 0) == hipSuccess) {
-                    e->graph = gr;
-                } else {
-                    if (gr) (void)hipGraphDestroy(gr);
-                    e->exec = nullptr; e->failed = true;
-                    (void)hipGetLastError();
-                }
-            } else {
-                e->failed = true;
-                (void)hipGetLastError();
-            }
-        }
-        if (e->exec) {
-            VB_HIP(hipGraphLaunch(e->exec, st));
-            return VB_OK;
-        }
+    if (hipGraphExec_t exec = graphable ? sample_graph(ctx, sc, st) : nullptr) {
+        VB_HIP(hipGraphLaunch(exec, st));
+        return VB_OK;
     }
-    return sample_steps(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, rows, keep, wins, gw, noise, traj, ws, st);
+    return sample_steps(ctx, sc, traj, st);
 }
 int vb_sample_graphs(vb_ctx* ctx) {
     int n = 0;

@@ -51,6 +51,21 @@ class Context:
 # ---------------------------------------------------------------------------
 
 
+def _ref(struct):
+    """an optional ABI struct by reference (None -> NULL), as L.ptr does for tensors"""
+    return C.byref(struct) if struct is not None else None
+
+
+def _device_tables(tables: dict, key: tuple, make) -> tuple:
+    """the device copies of one set of step tables ((t_idx, dt) or (t_next,)), made once per distinct key: step tables live on the
+    device, so nothing on the host has to outlive the async launch.  The cache is emptied rather than grown past 16 entries."""
+    if key not in tables:
+        if len(tables) > 16:
+            tables.clear()
+        tables[key] = make()
+    return tables[key]
+
+
 class DiTEngine:
     """TxtFlagLargeImprovedDiTV2 (vocal2music_moe.py:477-520) + CFMSampler hot loop on the GPU.
 
@@ -108,7 +123,7 @@ class DiTEngine:
     def precompute_cond(self, t5: Tensor, midi: Tensor, beats: Tensor, T: int, persistent: bool = False) -> dict:
         """t5 [nb*B, L, ori] (cond rows then uncond rows), midi/beats [B,1,T_mel] or [B,T_mel] int64.
         persistent=True writes into an engine-owned buffer that the NEXT persistent precompute of the same shape overwrites (a
-        serving loop: precompute -> sample -> discard): stable device addresses are what lets vb_sample_cfg replay its captured
+        serving loop: precompute -> sample -> discard): stable device addresses are what lets sample_cfg replay its captured
         hipGraph.  A stale handle is refused loudly (generation check) instead of sampling from overwritten conditioning."""
         dev = self.ctx.device
         t5 = t5.to(dev, torch.float32).contiguous()
@@ -218,12 +233,7 @@ class DiTEngine:
         if len(t_next) != n:
             raise ValueError(f"keep: t_next has {len(t_next)} entries for {n} steps")
         ref, x0k, mask = [t.to(dev).contiguous() for t in (ref, x0k, mask)]
-        tkey = ("t_next", tuple(t_next))
-        if tkey not in self._tables:
-            if len(self._tables) > 16:
-                self._tables.clear()
-            self._tables[tkey] = (torch.tensor(t_next, dtype=torch.float32, device=dev),)
-        tn = self._tables[tkey][0]
+        tn, = _device_tables(self._tables, ("t_next", tuple(t_next)), lambda: (torch.tensor(t_next, dtype=torch.float32, device=dev),))
         ks = L.Keep(ref.data_ptr(), x0k.data_ptr(), mask.data_ptr(), tn.data_ptr(), float(sigma_min))
         return ks, (ref, x0k, mask, tn)
 
@@ -347,14 +357,14 @@ class DiTEngine:
                    guidance=None):
         """n Euler steps with classifier-free guidance; x0 [B,C,T] is not modified.
         scale: one number for the batch, or B values (sequence / float32 tensor): row b is guided by scale[b].  clip_ids: B global clip
-        indices (sequence / int64 tensor): row b draws its router noise as clip clip_ids[b] instead of clip_base + b (vb_sample_cfg_rows).
+        indices (sequence / int64 tensor): row b draws its router noise as clip clip_ids[b] instead of clip_base + b (vb_rows).
         keep = (ref [B,C,T], x0 [B,C,T], mask [B,T] in [0,1], t_next [n], sigma_min) or a dict of those names holds the masked tokens on
-        the probability path t ref + (1 - (1 - sigma_min) t) x0 after every step (vb_sample_cfg_keep; t_next = model.euler_times).
+        the probability path t ref + (1 - (1 - sigma_min) t) x0 after every step (vb_keep; t_next = model.euler_times).
         windows: a sequence of nw ascending window starts - the B rows are then nw windows (row = w * (B // nw) + b, T tokens each) of
         B // nw long clips, and after every step the overlapping tokens of neighbouring windows take one consensus value, so they are
-        bit-identical in the result and in every trajectory state (vb_sample_cfg_windows).  Combines with all of the above; scale,
+        bit-identical in the result and in every trajectory state (vb_windows).  Combines with all of the above; scale,
         clip_ids and keep stay per ROW.
-        guidance: one weight in [0, 16] per step (vb_sample_cfg_sched) - step k runs under the effective scale 1 + guidance[k] * (scale - 1):
+        guidance: one weight in [0, 16] per step (vb_guidance) - step k runs under the effective scale 1 + guidance[k] * (scale - 1):
         1 is the plain step, 0 evaluates the conditional branch alone (about half the step's network time), anything between or
         beyond scales the guidance.  All ones or None is the plain call; with one branch (nb = 1) the weights are checked and unused.
         Combines with all of the above."""
@@ -371,40 +381,17 @@ class DiTEngine:
         x.copy_(x0.to(dev, torch.float32))
         n = len(t_idx_table)
         tkey = (tuple(int(v) for v in t_idx_table), tuple(float(v) for v in dt_table))
-        if tkey not in self._tables:            # step tables live on the device: nothing on the host has to outlive the async launch
-            if len(self._tables) > 16:
-                self._tables.clear()
-            self._tables[tkey] = (torch.tensor(tkey[0], dtype=torch.int64, device=dev), torch.tensor(tkey[1], dtype=torch.float32, device=dev))
-        tt, dd = self._tables[tkey]
-        traj = torch.empty(n + 1, *x.shape, dtype=torch.float32, device=dev) if return_traj else None
-        ns, held = self._noise_struct(noise, seed, clip_base, 0)
-        ws = self._workspace(B, nb, T, Lc)
+        tt, dd = _device_tables(self._tables, tkey, lambda: (torch.tensor(tkey[0], dtype=torch.int64, device=dev),
+                                                             torch.tensor(tkey[1], dtype=torch.float32, device=dev)))
         gs, held_guid = self._guidance_struct(guidance, n) if guidance is not None else (None, None)
-        if gs is not None:
-            ks, held_keep = self._keep_struct(keep, B, T, n) if keep is not None else (None, None)
-            L.check(self.ctx.lib.vb_sample_cfg_sched(self.ctx.handle, L.ptr(x), L.ptr(cond["buf"]), B, nb, T, Lc, n, L.ptr(tt), L.ptr(dd),
-                                                     float(scale), C.byref(gs), C.byref(wstruct) if wstruct is not None else None,
-                                                     C.byref(rs) if rs is not None else None, C.byref(ks) if ks is not None else None,
-                                                     C.byref(ns), L.ptr(traj), L.ptr(ws), L.stream_ptr()), "vb_sample_cfg_sched")
-        elif wstruct is not None:
-            ks, held_keep = self._keep_struct(keep, B, T, n) if keep is not None else (None, None)
-            L.check(self.ctx.lib.vb_sample_cfg_windows(self.ctx.handle, L.ptr(x), L.ptr(cond["buf"]), B, nb, T, Lc, n, L.ptr(tt), L.ptr(dd),
-                                                       float(scale), C.byref(wstruct), C.byref(rs) if rs is not None else None,
-                                                       C.byref(ks) if ks is not None else None, C.byref(ns), L.ptr(traj), L.ptr(ws),
-                                                       L.stream_ptr()), "vb_sample_cfg_windows")
-        elif rs is not None:
-            ks, held_keep = self._keep_struct(keep, B, T, n) if keep is not None else (None, None)
-            L.check(self.ctx.lib.vb_sample_cfg_rows(self.ctx.handle, L.ptr(x), L.ptr(cond["buf"]), B, nb, T, Lc, n, L.ptr(tt), L.ptr(dd),
-                                                    float(scale), C.byref(rs), C.byref(ks) if ks is not None else None, C.byref(ns),
-                                                    L.ptr(traj), L.ptr(ws), L.stream_ptr()), "vb_sample_cfg_rows")
-        elif keep is None:
-            L.check(self.ctx.lib.vb_sample_cfg(self.ctx.handle, L.ptr(x), L.ptr(cond["buf"]), B, nb, T, Lc, n, L.ptr(tt), L.ptr(dd), float(scale),
-                                               C.byref(ns), L.ptr(traj), L.ptr(ws), L.stream_ptr()), "vb_sample_cfg")
-        else:
-            ks, held_keep = self._keep_struct(keep, B, T, n)
-            L.check(self.ctx.lib.vb_sample_cfg_keep(self.ctx.handle, L.ptr(x), L.ptr(cond["buf"]), B, nb, T, Lc, n, L.ptr(tt), L.ptr(dd),
-                                                    float(scale), C.byref(ks), C.byref(ns), L.ptr(traj), L.ptr(ws), L.stream_ptr()),
-                    "vb_sample_cfg_keep")
+        ks, held_keep = self._keep_struct(keep, B, T, n) if keep is not None else (None, None)
+        ns, held = self._noise_struct(noise, seed, clip_base, 0)
+        traj = torch.empty(n + 1, *x.shape, dtype=torch.float32, device=dev) if return_traj else None
+        ws = self._workspace(B, nb, T, Lc)
+        # always the most general entry point: an absent option is a null pointer, which is all the older entry points pass in its place
+        L.check(self.ctx.lib.vb_sample_cfg_sched(self.ctx.handle, L.ptr(x), L.ptr(cond["buf"]), B, nb, T, Lc, n, L.ptr(tt), L.ptr(dd),
+                                                 float(scale), _ref(gs), _ref(wstruct), _ref(rs), _ref(ks), _ref(ns), L.ptr(traj),
+                                                 L.ptr(ws), L.stream_ptr()), "vb_sample_cfg_sched")
         x = x.clone()
         return (x, traj) if return_traj else x
 
