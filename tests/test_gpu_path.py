@@ -465,11 +465,18 @@ def test_eight_wave_gemm_matches_four_wave_kernels(engines, monkeypatch):
             assert torch.equal(outs[0][0], outs[k][0]), describe(f"8-wave vs 4-wave GEMM ({prec}, form {k})", outs[k][0], outs[0][0])
 
 
-@pytest.mark.parametrize("E,B,T", [(4, 2, 752), (8, 3, 752), (8, 4, 700)])
+@pytest.mark.parametrize("E,B,T", [(4, 2, 752), (4, 4, 752), (4, 5, 700), (8, 3, 752), (8, 4, 700)])
 def test_fused_band_experts_match_two_gemm_path(ctx, sds, engines, monkeypatch, E, B, T):
     """bf16 production mode runs the band experts as ONE launch (w1/w3 -> SwiGLU -> w2, hidden kept in LDS; 192-channel bands at
     4 experts, 96-channel bands at 8); it walks K in the same order as the two grouped GEMMs and uses their epilogue arithmetic, so
-    the results must be bit-identical (T = 700: the last 256-token tile of the batch is ragged)."""
+    the results must be bit-identical.
+    The fused kernel runs where cdiv(N, tile rows) * E >= 128 (band_fused_eligible in dit.hip; N = 2 B T token rows, 192 rows per tile
+    at E = 4, 256 at E = 8):
+      (4, 2, 752)  N = 3008: 16 tiles x 4 = 64 - NOT fused, both runs take the two-GEMM path (kept: the small-batch rule itself)
+      (4, 4, 752)  N = 6016: 32 x 4 = 128 - fused, 192-channel kernel, the last tile has 64 rows
+      (4, 5, 700)  N = 7000: 37 x 4 = 148 - fused, the last tile has 88 rows, four blocks of the grid return early
+      (8, 3, 752)  N = 4512: 18 x 8 = 144 - fused, 96-channel kernel, the last tile has 160 rows
+      (8, 4, 700)  N = 5600: 22 x 8 = 176 - fused, the last 256-row tile has 224 rows"""
     from versband_amd.engine import DiTEngine
     eng = engines[(4, "bf16")] if E == 4 else DiTEngine(ctx, synth.DiTConfig(num_experts=8), sds[8], precision="bf16")
     Lc = 80

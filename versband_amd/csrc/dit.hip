@@ -132,7 +132,7 @@ static bool w2_pair_eligible(const vb_dit_config& c) {
 static bool band_fused_eligible(const vb_dit_config& c, int N) {
     const int E = c.num_experts, band = c.hidden / E;
     return c.np == 1 && (band == 192 || band == 96) && c.ffn_hidden % 64 == 0 && E <= 8 && 8 % E == 0 && !vb_tune().band_unfused &&
-           (int64_t)cdiv(N, band == 192 ? 192 : 256) * E >= 128;
+           (int64_t)cdiv(N, band_ffn_tile_rows(band)) * E >= 128;
 }
 // proj_in reads the split-plane weights (as a GEMM operand, or in the conv kernel under VB_PROJ_IN_CONV)
 static bool proj_in_split_w_eligible(const vb_dit_config& c, const vb_dit_weights& w) { return w.proj_in_w3 && c.in_channels <= 32; }

@@ -261,26 +261,8 @@ __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(2
     };
     f32x16 acc[2][TN];
     acc_zero(acc);
-    issue(0);
     const int frow = lane & 31, fk = lane >> 5;
-    for (int t = 0; t < total; ++t) {
-        const int st = t % NST;
-        wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        if (t + 1 < total) issue(t + 1);
-        const unsigned char* As = lds + st * Feed::STAGE;
-        const unsigned char* Bs = As + Feed::ABYTES;
-        bf16x8 af[2][2], bf[2][TN];
-        frag_load<2, TN, BKT>(As, Bs, wr * 64, wc * 32 * TN, 0, fk, frow, af[0], bf[0]);
-#pragma unroll
-        for (int ks = 0; ks < BKT / 16; ++ks) {
-            const int cur = ks & 1;
-            if (ks + 1 < BKT / 16) frag_load<2, TN, BKT>(As, Bs, wr * 64, wc * 32 * TN, ks + 1, fk, frow, af[cur ^ 1], bf[cur ^ 1]);
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_step(af[cur], bf[cur], acc);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
+    gemm_walk_2stage<Feed>(lds, total, issue, wr * 64, wc * 32 * TN, fk, frow, acc);
     // epilogue (EPI_RESID_GATE): out32[m][n..n+15] = fmaf(gate[clip(m)][n..], v, out32[m][n..]); loads of a row slab first, then the stores
     // (round 3, measured and dropped: both row slabs' residual values requested together - 248 VGPRs, 38.4 against 36.6 us)
     {

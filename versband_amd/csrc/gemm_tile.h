@@ -1,6 +1,7 @@
 // What the bf16 GEMM kernels' main loops share (gemm_bf16.hip, band_ffn.hip), each piece defined once: which tile a workgroup owns, the LDS
 // tile image and its swizzle, the tile DMA feed, the operand offsets of a k-tile, and the 16-deep MFMA step.  What differs between the
-// kernels - where the counted waits, the barriers, the fragment prefetch and the refill sit - stays in the kernels.
+// kernels - where the counted waits, the barriers, the fragment prefetch and the refill sit - stays in the kernels; the one schedule with two
+// users, the two-stage K walk of the 128 x 64 TN kernels, is here too (gemm_walk_2stage).
 // Everything here is forced inline over caller-owned arrays of compile-time extent (a runtime-indexed register array would become scratch),
 // and `wave` is the caller's readfirstlane value, so stage bases and piece offsets stay scalar.
 #pragma once
@@ -206,6 +207,34 @@ template <int TN> __device__ __forceinline__ void mfma_row(const bf16x8& a, cons
 template <int TM, int TN> __device__ __forceinline__ void mfma_step(const bf16x8 (&af)[TM], const bf16x8 (&bf)[TN], f32x16 (&acc)[TM][TN]) {
 #pragma unroll
     for (int i = 0; i < TM; ++i) mfma_row<TN>(af[i], bf, acc[i]);
+}
+
+// ---- the K walk of the two-stage 128 x 64 TN kernels (moe_w2_pair_kernel, gemm_bf16_wide_resid_kernel) ---------------------------------------
+// issue(t) DMAs k-tile t into stage t % 2 of `lds`.  With one tile ahead the wait is a full drain: tile t landed, barrier (everyone finished
+// reading stage (t - 1) % 2), refill that stage with tile t + 1, then the k-steps - the fragments of k-step ks + 1 are read in front of the
+// MFMAs of k-step ks, between sched_barriers.  row_a / row_b: the wave's first row of the A / B tile.
+template <class Feed, int TN, class Issue>
+__device__ __forceinline__ void gemm_walk_2stage(const unsigned char* lds, int total, Issue issue, int row_a, int row_b, int fk, int frow,
+                                                 f32x16 (&acc)[2][TN]) {
+    constexpr int BKT = Feed::CH * 8;
+    issue(0);
+    for (int t = 0; t < total; ++t) {
+        wait_vmcnt<0>();
+        __builtin_amdgcn_s_barrier();
+        if (t + 1 < total) issue(t + 1);
+        const unsigned char* As = lds + (t % 2) * Feed::STAGE;
+        const unsigned char* Bs = As + Feed::ABYTES;
+        bf16x8 af[2][2], bf[2][TN];
+        frag_load<2, TN, BKT>(As, Bs, row_a, row_b, 0, fk, frow, af[0], bf[0]);
+#pragma unroll
+        for (int ks = 0; ks < BKT / 16; ++ks) {
+            const int cur = ks & 1;
+            if (ks + 1 < BKT / 16) frag_load<2, TN, BKT>(As, Bs, row_a, row_b, ks + 1, fk, frow, af[cur ^ 1], bf[cur ^ 1]);
+            __builtin_amdgcn_sched_barrier(0);
+            mfma_step(af[cur], bf[cur], acc);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
 }
 
 // ---- per-block trace record (tuning only, vbdbg_gemm_trace): {t_start, t_loop_end, t_end, prologue cycles << 36 | XCC id << 32 | HW id} --------

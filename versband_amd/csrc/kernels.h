@@ -79,6 +79,7 @@ struct BandFfnArgs {
     float* out32 = nullptr; int ldc32 = 0; const float* gate = nullptr; int gate_ld = 0; int T = 1;
 };
 int launch_band_ffn(const BandFfnArgs& a, hipStream_t st);
+int band_ffn_tile_rows(int band);                    // tokens per workgroup of the fused kernel (band = 192 or 96)
 
 // ---------------------------------------------------------------------------
 // flash attention over bf16 planes (head_dim 96): out = softmax(q k^T s) v  [+ w_h * softmax(q ky^T s) vy]
