@@ -330,7 +330,11 @@ def test_router_top1_bit_exact(lib, E):
     assert torch.equal(idx.cpu().long(), ref), f"{int((idx.cpu().long() != ref).sum())} of {N} routing indices differ"
 
 
-@pytest.mark.parametrize("N,E", [(1, 4), (1000, 4), (1504, 4), (4096, 4), (4097, 4), (12032, 4), (3000, 8), (6016, 8)])
+@pytest.mark.parametrize("N,E", [(1, 4), (1000, 4), (1504, 4), (4096, 4), (4097, 4), (12032, 4), (3000, 8), (6016, 8),
+                                 (4100, 3),         # two kernels, G = 6 does not divide the 256 threads; the last caption group is empty
+                                 (4100, 16),        # two kernels at the table's limit, G = 32
+                                 (300, 16),         # one workgroup at G = 32
+                                 (4353, 8)])        # 17 full blocks and a last block of one token
 def test_route_bucket(lib, N, E):
     ic = torch.from_numpy(prng.randint(3, N, 0, E)).int()
     ia = torch.from_numpy(prng.randint(4, N, 0, E)).int()
@@ -350,7 +354,10 @@ def test_route_bucket(lib, N, E):
         assert torch.equal(sel, want), f"group {g}: stable order violated"      # stable: tokens in ascending order
 
 
-@pytest.mark.parametrize("N,E", [(5000, 4), (12032, 4), (6016, 2), (777, 3), (1504, 4), (4096, 4), (1, 2)])
+@pytest.mark.parametrize("N,E", [(5000, 4), (12032, 4), (6016, 2), (777, 3), (1504, 4), (4096, 4), (1, 2),
+                                 (4100, 3),         # two kernels, G = 9
+                                 (4097, 4),         # first size of the two-kernel form, last block of one token
+                                 (4353, 2)])        # G = 4
 def test_route_bucket_pairs(lib, N, E):
     """pair mode: one rank per token by (caption, acoustic) expert pair; caption slots = pair slots (caption-major), acoustic slots =
     the same buckets acoustic-major; group_off / perm stay a valid bucketing by expert, tokens ascending inside a PAIR bucket"""
@@ -377,6 +384,13 @@ def test_route_bucket_pairs(lib, N, E):
     # acoustic half: acoustic-major order of the same pair buckets
     a_of_slot = ia.long()[perm[N:]]
     assert bool((a_of_slot[1:] >= a_of_slot[:-1]).all())
+    # ... each bucket with the rank it has in the caption half: tokens ascending inside a pair bucket there too
+    cnt_am = torch.bincount(ia.long() * E + ic.long(), minlength=E * E)
+    aoff = N + torch.cat([torch.zeros(1, dtype=torch.long), cnt_am.cumsum(0)])
+    for a in range(E):
+        for c in range(E):
+            got = perm[aoff[a * E + c]:aoff[a * E + c + 1]]
+            assert torch.equal(got, (pair == c * E + a).nonzero().squeeze(1)), f"acoustic-major pair bucket ({c}, {a})"
 
 
 @pytest.mark.parametrize("npl", [1, 2])

@@ -372,16 +372,23 @@ static GateNoise gate_noise(const Eval& e, int i) {
     }
     return n;
 }
+// the router's argument block for block i, as far as launch_router and the fused score + router kernel share it
+static RouterDev router_args(const Eval& e, int i) {
+    const vb_dit_block_weights& bw = e.w.blocks[i]; const WsL& s = e.s; const vb_noise* noise = e.ev.noise;
+    const GateNoise gn = gate_noise(e, i);
+    RouterDev r;
+    r.bg = bw.bcg; r.la = e.cd.la[i]; r.la_rows = e.ev.B * e.ev.T; r.hl = e.hl + i * 2; r.hl_ld = e.hl_ld;
+    r.g1 = gn.g1; r.g2 = gn.g2; r.g3 = gn.g3; r.T = e.ev.T; r.E = e.E; r.B = e.ev.B; r.ic = s.ic; r.ia = s.ia; r.mc = s.mc; r.ma = s.ma;
+    r.seed = noise ? noise->seed : 0; r.clip_base = noise ? noise->clip_base : 0; r.nfe_base = noise ? noise->nfe : 0;
+    r.step = e.ev.step_ptr; r.block = i; r.NS = e.cd.NS; r.Hh = e.c.heads; r.clip_rows = e.ev.clip_rows;
+    return r;
+}
 #ifdef VB_EXPERIMENTS
 static int score_router_fused(const Eval& e, int i) {
-    const vb_dit_block_weights& bw = e.w.blocks[i]; const WsL& s = e.s; const CondL& cd = e.cd; const vb_noise* noise = e.ev.noise;
-    const GateNoise gn = gate_noise(e, i);
+    const CondL& cd = e.cd;
     ScoreRouterArgs sr;
-    sr.A = e.u.p; sr.lda = e.D; sr.Bm = cd.mf[i]; sr.ldb = e.D; sr.bias = cd.cb[i]; sr.vw = cd.vw[i]; sr.bg = bw.bcg; sr.la = cd.la[i];
-    sr.la_rows = e.ev.B * e.ev.T; sr.hl = e.hl + i * 2; sr.hl_ld = e.hl_ld; sr.g1 = gn.g1; sr.g2 = gn.g2; sr.g3 = gn.g3; sr.Beff = e.Beff; sr.B = e.ev.B; sr.T = e.ev.T;
-    sr.K = e.D; sr.NS = cd.NS; sr.Hh = e.c.heads; sr.E = e.E; sr.ic = s.ic; sr.ia = s.ia; sr.mc = s.mc; sr.ma = s.ma;
-    sr.seed = noise ? noise->seed : 0; sr.clip_base = noise ? noise->clip_base : 0; sr.nfe_base = noise ? noise->nfe : 0;
-    sr.step = e.ev.step_ptr; sr.block = i; sr.clip_rows = e.ev.clip_rows;
+    sr.A = e.u.p; sr.lda = e.D; sr.Bm = cd.mf[i]; sr.ldb = e.D; sr.bias = cd.cb[i]; sr.K = e.D; sr.Beff = e.Beff;
+    sr.r = router_args(e, i); sr.r.Wg = cd.vw[i];
     return launch_score_router(sr, e.st);
 }
 #endif
@@ -389,8 +396,7 @@ static int score_router_fused(const Eval& e, int i) {
 // and the expert buckets of launch_bucket
 static int caption_gate_and_route(const Eval& e, int i) {
     const vb_dit_config& c = e.c; const vb_dit_block_weights& bw = e.w.blocks[i]; const WsL& s = e.s; const CondL& cd = e.cd;
-    const int B = e.ev.B, T = e.ev.T, D = e.D, N = e.N, E = e.E, np = e.np;
-    const vb_noise* noise = e.ev.noise;
+    const int T = e.ev.T, D = e.D, N = e.N, E = e.E, np = e.np;
     const float* mod = e.mod(i);
     VB_TRY(launch_rmsnorm_mod(s.h, bw.ffn_norm_w, mod + 3 * D, mod + 4 * D, e.MODW, N, D, T, c.norm_eps, e.u, e.st));
     const bool fold = e.p.gate_fold(i), fused_router = fold && e.p.score_fused;
@@ -419,12 +425,8 @@ static int caption_gate_and_route(const Eval& e, int i) {
         }
         // (MoE.cross_attention.out_proj is folded into the caption gate at pack time: lc = cqa . (Wcg Wo)^T + (Wcg bo + bcg),
         //  so the [N,768]x[768,768] out_proj GEMM never runs - its only consumer is the 768->E gate, vocal2music_moe.py:119-141)
-        const GateNoise gn = gate_noise(e, i);
-        RouterDev r;
-        r.cq = e.cqa; r.Wg = fold ? cd.vw[i] : bw.wcg; r.bg = bw.bcg; r.la = cd.la[i]; r.la_rows = B * T; r.hl = e.hl + i * 2; r.hl_ld = e.hl_ld;
-        r.g1 = gn.g1; r.g2 = gn.g2; r.g3 = gn.g3; r.N = N; r.T = T; r.D = D; r.E = E; r.ic = s.ic; r.ia = s.ia; r.mc = s.mc; r.ma = s.ma; r.B = B;
-        r.seed = noise ? noise->seed : 0; r.clip_base = noise ? noise->clip_base : 0; r.nfe_base = noise ? noise->nfe : 0;
-        r.step = e.ev.step_ptr; r.block = i; r.sc = fold ? s.y32 : nullptr; r.NS = cd.NS; r.Hh = c.heads; r.clip_rows = e.ev.clip_rows;
+        RouterDev r = router_args(e, i);
+        r.cq = e.cqa; r.Wg = fold ? cd.vw[i] : bw.wcg; r.N = N; r.D = D; r.sc = fold ? s.y32 : nullptr;
         r.cnt = e.p.router_counts ? e.counts(i) : nullptr; r.cnt_G = e.p.w2_pair ? E * E : 2 * E; r.cnt_pairs = e.p.w2_pair ? 1 : 0;
         VB_TRY(launch_router(r, e.st));
     }

@@ -239,7 +239,8 @@ int launch_step_ctl(int* step, int64_t* t_idx_cur, const int64_t* t_table, int n
 // ---------------------------------------------------------------------------
 // routing.hip: Band-MoE router and bucketing (+ the fused score + router kernel, score_router.hip)
 // ---------------------------------------------------------------------------
-// Band-MoE router: call arguments and the kernel's argument block in one (the device side is router_dev.h).
+// Band-MoE router: call arguments and the kernel's argument block in one (the device side is router_dev.h).  Both users - launch_router and the
+// fused score + router kernel - get it from ONE fill (dit.hip: router_args), so a per-row option is threaded through once.
 // SC = true: "folded" caption gate.  The token features are not materialised at all: `sc` holds the token's attention
 // SCORES against its clip's caption keys for all heads ([N][NS], NS = L * Hh, column = key * Hh + head; scale, q-projection
 // and q-bias already inside - one grouped GEMM against per-clip folded keys), `Wg` holds per clip VW[key*Hh+head][e] =
@@ -260,17 +261,14 @@ struct RouterDev {
 int launch_router(const RouterDev& a, hipStream_t st);
 // fused caption-gate scores + router (score_router.hip): bf16 token features x per-clip folded keys -> routing decisions, the
 // [N][NS] score matrix stays in LDS.  Bit-identical to launch_gemm(EPI_F32 scores) + launch_router(sc = scores).
+// The GEMM side, and the router's own argument block for everything else: the caller fills r as for launch_router with Wg = the per-clip
+// VW [Beff][NS][E]; launch_score_router owns r.N (= Beff * T), r.D (= K), r.sc, r.lc_out and r.cnt (all null: nothing is read back or counted).
 struct ScoreRouterArgs {
     const bf16_t* A = nullptr; int lda = 0;          // token features [Beff*T][lda] bf16
     const bf16_t* Bm = nullptr; int ldb = 0;         // folded keys [Beff][NS][ldb] bf16
     const float* bias = nullptr;                     // [Beff][NS]
-    const float* vw = nullptr;                       // [Beff][NS][E]
-    const float* bg = nullptr; const float* la = nullptr; int la_rows = 0; const float* hl = nullptr; int hl_ld = 0;
-    const float* g1 = nullptr; const float* g2 = nullptr; const float* g3 = nullptr;
-    int Beff = 0, B = 0, T = 0, K = 0, NS = 0, Hh = 1, E = 0;
-    int* ic = nullptr; int* ia = nullptr; float* mc = nullptr; float* ma = nullptr;
-    uint64_t seed = 0; int64_t clip_base = 0; int nfe_base = 0; const int* step = nullptr; int block = 0;
-    const int64_t* clip_rows = nullptr;              // as RouterDev::clip_rows
+    int K = 0, Beff = 0;
+    RouterDev r;
 };
 bool score_router_supported(int NS, int K, int E, int Hh);
 int launch_score_router(const ScoreRouterArgs& a, hipStream_t st);

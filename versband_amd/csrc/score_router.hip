@@ -11,14 +11,10 @@
 //   * epilogue: scores + per-clip bias go to LDS 32 rows at a time (the ring is free after the loop), and every wave runs
 //     router_tokens() - the router kernel's own code - on 8 of those rows, reading the score rows from LDS instead of HBM.
 // Grid: clips x ceil(T / 64) workgroups, the tiles of a clip on one XCD (its 983 KB of folded keys stay in that L2).
-#include <type_traits>
-
-#include "kernels.h"
-#include "dma_ring.h"
+// The tile image, the DMA feed, the fragment reads and the MFMA step are gemm_tile.h's (BKT = 32, A = 64 token rows, B = NS key rows); the
+// schedule - ring depth, counted waits, barrier - and the epilogue are this kernel's own.
+#include "gemm_tile.h"
 #include "router_dev.h"
-
-// byte offset of 16-B chunk c of tile row `row` in a BK = 32 operand image (64 B per row; chunk XOR-swizzled by the row)
-__device__ __forceinline__ int sr_off(int row, int c) { return row * 64 + ((c ^ ((row >> 2) & 3)) << 4); }
 
 #define SR_BM 64
 #define SR_NST 3
@@ -37,10 +33,8 @@ extern "C" void vbdbg_sr_trace(void* buf) { g_sr_trace = static_cast<unsigned lo
 template <int NJ, int PP>
 __global__ void __launch_bounds__(256) score_router_kernel(const ScoreRouterDev p) {
     constexpr int NS = NJ * 128;
-    constexpr int ROWS = SR_BM + NS;                  // tile rows of one stage: 64 token rows, then NS key rows
-    constexpr int STAGE = ROWS * 64;                  // bytes (32 bf16 per row)
-    constexpr int PPW = ROWS / 16 / 4;                // 1-KB DMA pieces (16 rows) per wave per stage
-    static_assert(ROWS % 64 == 0, "pieces must divide over 4 waves");
+    using Feed = TileFeed<SR_BM, NS, 32, 4>;          // a stage: 64 token rows, then NS key rows of 64 B; 1 + 2 NJ 1-KB DMA pieces per wave
+    constexpr int STAGE = Feed::STAGE;
     constexpr int PITCH = NS + 4;                     // floats per staged score row
     static_assert(32 * PITCH * 4 <= SR_NST * STAGE, "score staging must fit in the ring");
     extern __shared__ __attribute__((aligned(16))) unsigned char sr_lds[];
@@ -57,37 +51,14 @@ __global__ void __launch_bounds__(256) score_router_kernel(const ScoreRouterDev 
 
     unsigned long long tq0 = 0, tq1 = 0;
     if (p.trace) tq0 = __builtin_amdgcn_s_memtime();
-    const bf16_t* src[PPW];
-#pragma unroll
-    for (int i = 0; i < PPW; ++i) {
-        const int s = wave * PPW + i;
-        const int r = 16 * s + (lane >> 2);           // stage row
-        const int cs = lane & 3;
-        if (r < SR_BM) {
-            const int c = cs ^ ((r >> 2) & 3);
-            int slot = row0 + r;
-            if (slot >= rows_end) slot = row0;
-            src[i] = p.A + (int64_t)slot * p.lda + c * 8;
-        } else {
-            const int n = r - SR_BM;
-            const int c = cs ^ ((n >> 2) & 3);
-            src[i] = p.Bm + (int64_t)clip * p.b_clip_stride + (int64_t)n * p.ldb + c * 8;
-        }
-    }
-    auto issue = [&](int t) {
-        unsigned char* dst = sr_lds + (t % SR_NST) * STAGE + wave * PPW * 1024;
-        const int k0 = t * 32;
-#pragma unroll
-        for (int i = 0; i < PPW; ++i) __builtin_amdgcn_global_load_lds((glb_ptr_t)(src[i] + k0), (lds_ptr_t)(dst + i * 1024), 16, 0, 0);
-    };
+    const bf16_t* asrc[Feed::PA];
+    const bf16_t* bsrc[Feed::PB];
+    Feed::rows(asrc, p.A, p.lda, row0, rows_end, row0, false, wave, lane, [](int row) { return row; });
+    Feed::rows(bsrc, p.Bm + (int64_t)clip * p.b_clip_stride, p.ldb, 0, NS, 0, false, wave, lane, [](int row) { return row; });
+    auto issue = [&](int t) { Feed::issue(asrc, bsrc, wave, sr_lds + (t % SR_NST) * STAGE, t * 32, t * 32); };
 
     f32x16 acc[2][NJ];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    acc_zero(acc);
 
     const int KT = p.K / 32;
 #pragma unroll
@@ -95,29 +66,19 @@ __global__ void __launch_bounds__(256) score_router_kernel(const ScoreRouterDev 
         if (t < KT) issue(t);
     const int frow = lane & 31, fk = lane >> 5;
     for (int t = 0; t < KT; ++t) {
-        if (t + 1 < KT) wait_vmcnt<PPW>();         // tile t landed, tile t + 1 may stay in flight
+        if (t + 1 < KT) wait_vmcnt<Feed::LPT>();   // tile t landed, tile t + 1 may stay in flight
         else wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();                 // ... everywhere; everyone is done reading stage (t - 1) % NST
         if (t + SR_NST - 1 < KT) issue(t + SR_NST - 1);
         const unsigned char* As = sr_lds + (t % SR_NST) * STAGE;
-        const unsigned char* Bs = As + SR_BM * 64;
+        const unsigned char* Bs = As + Feed::ABYTES;
         bf16x8 af[2][2], bf[2][NJ];
-        auto fload = [&](int ks, int slot) {
-            const int c = ks * 2 + fk;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) af[slot][i] = *reinterpret_cast<const bf16x8*>(As + sr_off(i * 32 + frow, c));
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) bf[slot][j] = *reinterpret_cast<const bf16x8*>(Bs + sr_off(wave * 32 * NJ + j * 32 + frow, c));
-        };
-        fload(0, 0);
+        frag_load<2, NJ, 32>(As, Bs, 0, wave * 32 * NJ, 0, fk, frow, af[0], bf[0]);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            if (ks + 1 < 2) fload(ks + 1, (ks + 1) & 1);
+            if (ks + 1 < 2) frag_load<2, NJ, 32>(As, Bs, 0, wave * 32 * NJ, ks + 1, fk, frow, af[(ks + 1) & 1], bf[(ks + 1) & 1]);
             __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[ks & 1][j], af[ks & 1][i], acc[i][j], 0, 0, 0);
+            mfma_step(af[ks & 1], bf[ks & 1], acc);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -172,27 +133,25 @@ static void launch_sr(const ScoreRouterDev& d, dim3 grid, hipStream_t st) {
 }
 
 int launch_score_router(const ScoreRouterArgs& a, hipStream_t st) {
-    if (!score_router_supported(a.NS, a.K, a.E, a.Hh)) VB_FAIL(VB_E_INVALID, "score_router: NS=%d K=%d E=%d heads=%d unsupported", a.NS, a.K, a.E, a.Hh);
-    if (a.lda % 8 || a.ldb % 8 || a.T < 1 || a.Beff < 1) VB_FAIL(VB_E_INVALID, "score_router: lda/ldb must be multiples of 8, T and clips positive");
+    const int NS = a.r.NS, T = a.r.T;
+    if (!score_router_supported(NS, a.K, a.r.E, a.r.Hh)) VB_FAIL(VB_E_INVALID, "score_router: NS=%d K=%d E=%d heads=%d unsupported", NS, a.K, a.r.E, a.r.Hh);
+    if (a.lda % 8 || a.ldb % 8 || T < 1 || a.Beff < 1) VB_FAIL(VB_E_INVALID, "score_router: lda/ldb must be multiples of 8, T and clips positive");
     ScoreRouterDev d;
-    d.A = a.A; d.lda = a.lda; d.Bm = a.Bm; d.b_clip_stride = (int64_t)a.NS * a.ldb; d.ldb = a.ldb; d.bias = a.bias; d.bias_clip_stride = a.NS;
-    d.K = a.K; d.Beff = a.Beff; d.tiles_per_clip = cdiv(a.T, SR_BM); d.trace = g_sr_trace;
-    RouterDev& r = d.r;
-    r.cq = Planes{nullptr, 0, 1}; r.Wg = a.vw; r.bg = a.bg; r.la = a.la; r.la_rows = a.la_rows; r.hl = a.hl; r.hl_ld = a.hl_ld;
-    r.g1 = a.g1; r.g2 = a.g2; r.g3 = a.g3; r.N = a.Beff * a.T; r.T = a.T; r.D = a.K; r.E = a.E; r.ic = a.ic; r.ia = a.ia; r.mc = a.mc; r.ma = a.ma;
-    r.lc_out = nullptr; r.B = a.B > 0 ? a.B : 1; r.seed = a.seed; r.clip_base = a.clip_base; r.nfe_base = a.nfe_base; r.step = a.step;
-    r.block = a.block; r.sc = nullptr; r.NS = a.NS; r.Hh = a.Hh; r.cnt = nullptr; r.cnt_G = 0; r.cnt_pairs = 0; r.clip_rows = a.clip_rows;
-    const double n_tok = (double)a.Beff * a.T;
-    ProfScope prof(0, 2.0 * n_tok * a.NS * a.K, 2.0 * (n_tok * a.K + (double)a.Beff * a.NS * a.K) + 16.0 * n_tok, st);
+    d.A = a.A; d.lda = a.lda; d.Bm = a.Bm; d.b_clip_stride = (int64_t)NS * a.ldb; d.ldb = a.ldb; d.bias = a.bias; d.bias_clip_stride = NS;
+    d.K = a.K; d.Beff = a.Beff; d.tiles_per_clip = cdiv(T, SR_BM); d.trace = g_sr_trace;
+    d.r = a.r;
+    d.r.N = a.Beff * T; d.r.D = a.K; d.r.sc = nullptr; d.r.lc_out = nullptr; d.r.cnt = nullptr; if (d.r.B <= 0) d.r.B = 1;
+    const double n_tok = (double)a.Beff * T;
+    ProfScope prof(0, 2.0 * n_tok * NS * a.K, 2.0 * (n_tok * a.K + (double)a.Beff * NS * a.K) + 16.0 * n_tok, st);
     const dim3 grid(d.tiles_per_clip * ((a.Beff + 7) / 8 * 8));
-    const int nj = a.NS / 128;
-    const bool pp4 = 2 * a.E + 2 <= 16;
+    const int nj = NS / 128;
+    const bool pp4 = 2 * a.r.E + 2 <= 16;
 #define VB_SR_CASE(NJ) case NJ: if (pp4) launch_sr<NJ, 4>(d, grid, st); else launch_sr<NJ, 2>(d, grid, st); break;
     switch (nj) {
         VB_SR_CASE(4)
         VB_SR_CASE(5)
         VB_SR_CASE(6)
-        default: VB_FAIL(VB_E_INVALID, "score_router: NS=%d", a.NS);
+        default: VB_FAIL(VB_E_INVALID, "score_router: NS=%d", NS);
     }
 #undef VB_SR_CASE
     VB_CHECK_LAUNCH();
