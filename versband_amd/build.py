@@ -19,7 +19,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libversband_hip.so")
-SOURCES = ["gemm_bf16.hip", "band_ffn.hip", "attention.hip", "conv1d.hip", "conv1d_f32.hip", "conv1d_x3.hip", "conv1d_f32g.hip", "conv1d_f32w.hip", "conv1d_bf16.hip", "respair_x3.hip", "respair_bf16.hip", "respair_f32.hip", "respair_f32w.hip", "t5.hip", "melnet.hip", "elementwise.hip", "sampler_step.hip", "routing.hip", "net_glue.hip", "rowlin.hip",
+SOURCES = ["gemm_bf16.hip", "band_ffn.hip", "attention.hip", "conv1d.hip", "conv1d_f32.hip", "conv1d_x3.hip", "conv1d_f32g.hip", "conv1d_f32w.hip", "conv1d_bf16.hip", "respair_x3.hip", "respair_bf16.hip", "respair_f32.hip", "respair_f32w.hip", "t5.hip", "melnet.hip", "elementwise.hip", "sampler_step.hip", "routing.hip", "gate_route.hip", "net_glue.hip", "rowlin.hip",
            "runtime.hip", "dit.hip", "sampler.hip", "convnet.hip", "abi_units.hip"]
 EXPERIMENT_SOURCES = ["score_router.hip", "gemm_bf16_pk.hip"]
 EXPERIMENTS = bool(os.environ.get("VB_BUILD_EXPERIMENTS"))

@@ -147,6 +147,23 @@ static bool score_fused_eligible(const vb_dit_config& c, int Beff, int T, int L)
     return false;
 #endif
 }
+// the product form of that fusion (gate_route.hip): softmax and value/gate contraction lane-local in the MFMA's accumulator layout, no score
+// matrix in memory, bit-identical to the two launches - so the choice may follow the token count.  bf16 mode, fold layout, 80 keys x 8 heads,
+// 4 experts, hidden 768; everything else keeps score GEMM + router.  VB_GATE_ROUTE=0: the two launches (tests, A/B); =1: fused at every count.
+// MEASURED (8 clips x 2 branches, one stream, same box, parent / head alternating): 40.3 / 40.1 us per launch against 25.7 + 17.8 and
+// 25.9 + 17.9 us of score GEMM + router - 3.4 us (8 %) less, the parent's own spread being 0.3 us; well short of the 20-28 us the kernel was
+// sized for, and too little to show in the whole benchmark (profiles/r16_gate_route_ab.txt).  Fetches 34 MB (tokens + folded keys), writes
+// 0.4 MB where the two launches wrote 31.5 MB and read them back (docs/history.md).  The launch is one round of one workgroup per CU and
+// takes its ~40 us at any batch, while the two launches shrink with the token count: at one clip x 2 branches (24 tiles) the whole
+// benchmark ran 45.0 against 41.4 ms per step with it, ~18 us per block evaluation MORE.  Measured to win: 192 tiles (per launch, above) and
+// 96 tiles (4 clips x 2 branches per stream, the default command: median 1242.9 against the parent's 1227.7-1240.5 mel-s/s); 48 tiles
+// were not measured and stay with the two launches.
+constexpr int GATE_ROUTE_MIN_TILES = 96;     // 64-token tiles (= workgroups) from which the one launch is taken
+static bool gate_route_eligible(const vb_dit_config& c, int Beff, int T, int L) {
+    if (c.np != 1 || !gate_fold_ok(c, L) || !gate_route_supported(L * c.heads, c.hidden, c.num_experts, c.heads)) return false;
+    const int knob = vb_tune().gate_route;
+    return knob >= 0 ? knob != 0 : (int64_t)Beff * cdiv(T, 64) >= GATE_ROUTE_MIN_TILES;
+}
 // FinalLayer form.  FINAL_EULER_FUSED is what the sampler's evaluations take (both CFG branches in the batch, VB_EULER_LAUNCH off); VB_FINAL_GEMM=1
 // selects the split-planes kernel + MFMA GEMM the fused kernel replaced (tests compare them)
 static FinalRoute final_route(const vb_dit_config& c, const vb_dit_weights& w, int nb, int N) {
@@ -170,6 +187,7 @@ DitPlan dit_plan(const vb_ctx* ctx, int B, int nb, int T, int L, int nb_active) 
     p.router_counts = router_counts_eligible(N);
     p.band_fused = band_fused_eligible(c, N);
     p.score_fused = score_fused_eligible(c, Beff, T, L);
+    p.gate_route = !p.score_fused && gate_route_eligible(c, Beff, T, L);
     p.final_route = final_route(c, ctx->w, nba, N);
     return p;
 }
@@ -383,15 +401,15 @@ static RouterDev router_args(const Eval& e, int i) {
     r.step = e.ev.step_ptr; r.block = i; r.NS = e.cd.NS; r.Hh = e.c.heads; r.clip_rows = e.ev.clip_rows;
     return r;
 }
-#ifdef VB_EXPERIMENTS
-static int score_router_fused(const Eval& e, int i) {
+// the one-launch forms' arguments: the GEMM side + the router's block (with the count table: launch_score_router ignores it)
+static ScoreRouterArgs score_router_args(const Eval& e, int i) {
     const CondL& cd = e.cd;
     ScoreRouterArgs sr;
     sr.A = e.u.p; sr.lda = e.D; sr.Bm = cd.mf[i]; sr.ldb = e.D; sr.bias = cd.cb[i]; sr.K = e.D; sr.Beff = e.Beff;
     sr.r = router_args(e, i); sr.r.Wg = cd.vw[i];
-    return launch_score_router(sr, e.st);
+    sr.r.cnt = e.p.router_counts ? e.counts(i) : nullptr; sr.r.cnt_G = e.p.w2_pair ? e.E * e.E : 2 * e.E; sr.r.cnt_pairs = e.p.w2_pair ? 1 : 0;
+    return sr;
 }
-#endif
 // Band-MoE gates (vocal2music_moe.py:117-151): modulated RMSNorm of h -> u, caption-gate logits, routing decisions (s.ic / s.ia / s.mc / s.ma)
 // and the expert buckets of launch_bucket
 static int caption_gate_and_route(const Eval& e, int i) {
@@ -402,8 +420,10 @@ static int caption_gate_and_route(const Eval& e, int i) {
     const bool fold = e.p.gate_fold(i), fused_router = fold && e.p.score_fused;
     if (fused_router) {
 #ifdef VB_EXPERIMENTS
-        VB_TRY(score_router_fused(e, i));
+        VB_TRY(launch_score_router(score_router_args(e, i), e.st));
 #endif
+    } else if (fold && e.p.gate_route) {
+        VB_TRY(launch_gate_route(score_router_args(e, i), e.st));
     } else {
         if (fold) {
             // caption gate, folded: scores of every token against its clip's caption keys for all heads in ONE grouped GEMM

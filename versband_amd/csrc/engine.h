@@ -114,7 +114,7 @@ WsL carve_ws(void* base, const vb_dit_config& c, int B, int nb, int T, int L);
 // blocks of an evaluation.
 // An evaluation over nb_active < nb branches of the nb layout (a single-branch step of vb_sample_cfg_sched): the members that describe
 // the LAYOUT (proj_in_split_w, proj_in_gemm, fold_layout, w2_pair - model and L alone) are those of nb; the members that pick a kernel
-// from the token count (router_counts, band_fused, score_fused, final_route) follow the active rows, i.e. are those of an nb_active call.
+// from the token count (router_counts, band_fused, score_fused, gate_route, final_route) follow the active rows, i.e. are those of an nb_active call.
 enum FinalRoute {
     FINAL_EULER_FUSED,   // FinalLayer + CFG + Euler update + step advance as one launch: only with DitEval::euler (the sampler);
                          // an evaluation without it takes FINAL_FUSED, whose conditions this route includes
@@ -125,7 +125,7 @@ enum FinalRoute {
 struct DitPlan {
     const vb_dit_weights* w = nullptr;
     bool router_counts = false, w2_pair = false, band_fused = false, proj_in_split_w = false, proj_in_gemm = false;
-    bool fold_layout = false, score_fused = false;
+    bool fold_layout = false, score_fused = false, gate_route = false;
     FinalRoute final_route = FINAL_ROWS;
     // block i takes the folded caption gate: the layout holds its operands and the pack carries the folded weights
     bool gate_fold(int i) const { return fold_layout && w->blocks[i].wqt_s && w->blocks[i].bq_s; }

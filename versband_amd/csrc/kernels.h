@@ -272,6 +272,10 @@ struct ScoreRouterArgs {
 };
 bool score_router_supported(int NS, int K, int E, int Hh);
 int launch_score_router(const ScoreRouterArgs& a, hipStream_t st);
+// the product form of the same fusion (gate_route.hip: softmax and contraction lane-local in the MFMA's accumulator layout; NS = 640, K = 768,
+// E = 4, 8 heads).  Same arguments, same bits; unlike launch_score_router it keeps r.cnt / cnt_G / cnt_pairs: it counts as launch_router does.
+bool gate_route_supported(int NS, int K, int E, int Hh);
+int launch_gate_route(const ScoreRouterArgs& a, hipStream_t st);
 // (pair_off / pair_pa non-null, E*E <= 16: rank by (caption, acoustic) expert PAIR; both expert-group orders derive from it - see
 //  bucket_place_kernel.  pair_off [E*E + 1], pair_pa [N] = acoustic slot of the token in pair / caption slot p)
 // counts_ready (round 5): the per-256-token-block group counts were already accumulated by the router (RouterDev::cnt) - the count launch is

@@ -38,6 +38,7 @@ static void tune_load() {
     t.conv_gemm_off = getenv("VB_CONV_GEMM_OFF") != nullptr;
     t.final_gemm = getenv("VB_FINAL_GEMM") != nullptr;
     t.router_generic = getenv("VB_ROUTER_GENERIC") != nullptr;
+    t.gate_route = env_int("VB_GATE_ROUTE", -1);      // 0: score GEMM + router launches, 1: the one-launch caption gate at every token count
     t.band_epi_old = getenv("VB_BAND_EPI_OLD") != nullptr;
     t.conv_f32_old = getenv("VB_CONV_F32_OLD") != nullptr;
     t.gemm_p8_off = getenv("VB_GEMM_P8_OFF") != nullptr;
