@@ -196,7 +196,7 @@ int vb_sample_cfg_keep(vb_ctx* ctx, float* x, const void* cond, int B, int n_bra
                        const vb_noise* noise, float* traj, void* ws, void* stream);
 /* The same sampler with PER-ROW guidance scale and noise key: rows that differ in guidance scale (the scales of one item) or whose global
  * clip indices are not contiguous (items sharded rank::world, same-length items picked out of a manifest) share one call.  All rows of a
- * call still share T and L.
+ * call still share L, and T unless row lengths are given (vb_lens, below).
  *   cfg_scale  f32 [B]    (device) row b is guided by cfg_scale[b]: e = fmaf(cfg_scale[b], v_c - v_u, v_u), the fused multiply-add
  *                         evaluation of v_u + cfg_scale[b] * (v_c - v_u), in EVERY update form - fused into FinalLayer, with a known region,
  *                         the separate launch (VB_EULER_LAUNCH): all are the same two fused multiply-adds, the arithmetic of the scalar
@@ -264,6 +264,40 @@ int vb_sample_cfg_sched(vb_ctx* ctx, float* x, const void* cond, int B, int n_br
                         const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_guidance* guidance,
                         const vb_windows* win, const vb_rows* rows, const vb_keep* keep, const vb_noise* noise, float* traj, void* ws,
                         void* stream);
+/* ROW LENGTHS (build-defined; the reference pads and attends over everything in training and runs batch 1 at inference): clips of
+ * different lengths as rows of one call.  T is the padded row length of the call and len[b] <= T row b's own length; its tokens are
+ * [0, len[b]), the rest of the row is padding.  THE CONTRACT: row b of a call with lengths is the call on that clip alone - on its valid
+ * tokens, x, every traj[k], v_out and route_out equal what the same entry point computes for B = 1, T = len[b] (precompute with
+ * T_mel = 2 len[b]) on the row's first len[b] tokens, with the same blocks sliced and the row's noise key (rows->clip[b], or
+ * noise->clip_base + b).  Only three places of a network evaluation look past a token's own row, and each has one mechanism:
+ *   self-attention   row b attends over its first len[b] keys (a device table of the lengths in the workspace; both branches read
+ *                    len[b % B]); query rows from len[b] on are padding.  Cross-attention over the L caption keys is unchanged.
+ *   proj_in          the k = 5 taps at t >= len[b] read as zero, on every route (x itself is not modified).
+ *   acoustic stem    (precompute) the midi / beats embeddings are zero from mel position 2 len[b] on, so the k = 5 convolutions see the zero
+ *                    padding of the clip alone; a call with lengths requires T_mel == 2 T (the +-2 crop / repeat tolerance of
+ *                    vocal2music_moe.py:397 stays for calls without lengths).
+ * Everything else is token-local and runs over the padding tokens too (wasted work of at most the padding share, never wrong).
+ * Padding: the padding of midi / beats / x is never read into a valid token - it may hold anything, NaN included.  The padding tokens
+ * of x, traj, v_out and route_out are written and UNSPECIFIED, but finite when the caller's padding of x was finite (the update kernels
+ * are the ones of a plain call and run over every token); a host that wants a defined tensor clears them (the Python host does).
+ *   len  int32 [B]  HOST array of row lengths, 1 <= len[b] <= T; read during the call only.
+ * VB_E_INVALID, with the row named in vb_last_error(), before anything is launched and with x unchanged, when: len[b] < 1; len[b] > T;
+ * B > 64; T_mel != 2 T (precompute); win with nw > 1 beside lengths (joint windows are equal-length by construction).
+ * lens == NULL, len == NULL or all len[b] == T is exactly the entry point without lengths (vb_sample_cfg_sched, which like the four before
+ * it forwards here; vb_dit_forward; vb_dit_precompute_cond - both forward to their _lens forms): same launches, same graph key, same bits.
+ * keep, rows and guidance compose unchanged (all are token-local); single-branch steps read the same table.  The lengths reach the
+ * device through a launch argument at the head of the step loop, which a captured graph holds: the graph key holds the VALUES of len,
+ * so another set of lengths on the same buffers captures its own graph and a plain call never replays a lengths graph.  Hosts detect
+ * the feature by the presence of these symbols (vb_abi_version() stays 3).  The VAE and vocoder entry points take equal-length rows only. */
+typedef struct { const int32_t* len; } vb_lens;                   /* len: HOST array of B row lengths, 1 <= len[b] <= T */
+int vb_dit_precompute_cond_lens(vb_ctx* ctx, const float* t5, const int64_t* midi, const int64_t* beats, int B, int n_branch, int T,
+                                int T_mel, int L, const vb_lens* lens, void* cond, void* ws, void* stream);
+int vb_dit_forward_lens(vb_ctx* ctx, const float* x, const int64_t* t_idx, const void* cond, const vb_noise* noise, int B, int n_branch,
+                        int T, int L, const vb_lens* lens, float* v_out, int32_t* route_out, void* ws, void* stream);
+int vb_sample_cfg_lens(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
+                       const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_lens* lens, const vb_guidance* guidance,
+                       const vb_windows* win, const vb_rows* rows, const vb_keep* keep, const vb_noise* noise, float* traj, void* ws,
+                       void* stream);
 /* The overlap consensus alone, on x [nw*Bc][C][n] with B = nw*Bc rows (the unit, like vb_euler_cfg_step): same formula, same checks. */
 int vb_window_blend(float* x, const int32_t* starts, int nw, int B, int C, int n, void* stream);
 /* The step loop of vb_sample_cfg is captured into a hipGraph the second time a call arrives with the same buffers / shape on a
@@ -438,6 +472,11 @@ int vb_grouped_swiglu(const void* u, const int32_t* perm, const int32_t* group_o
 /* fused self (+cross) attention, head_dim 96 (Attention.forward, flag_large_dit_moe.py:381-402) */
 int vb_attention(const void* q, const void* k, const void* vt, const void* ky, const void* vyt, const float* cross_w, int B, int T,
                  int Tpad, int L, int Lpad, int H, int hd, int np, void* out, void* stream);
+/* the same with row lengths (the unit of vb_lens): key_len = DEVICE int32 [B], row b's self pass attends over its first key_len[b] keys (K
+ * and V^T keep their strides T / Tpad; V^T must be finite up to the end of the last 64-key tile it touches) and its first key_len[b]
+ * output rows equal vb_attention on those tokens alone, bit for bit; the output rows from key_len[b] on are finite.  NULL: vb_attention. */
+int vb_attention_lens(const void* q, const void* k, const void* vt, const void* ky, const void* vyt, const float* cross_w, int B, int T,
+                      int Tpad, int L, int Lpad, int H, int hd, int np, const int32_t* key_len, void* out, void* stream);
 /* fp32 Conv1d / ConvTranspose1d on [B][C][T] (weights packed [phase][tap][Ci][Co]); w_x3 != NULL runs the
  * split-bf16 (bf16x3) MFMA kernel on weights packed [2][phase][tap][Co][ci_pad] instead of the exact-f32 MFMA kernel */
 int vb_conv1d_f32(const float* x, const float* w, const float* bias, int B, int Ci, int T_in, int Co, int ksize, int dil, int pad,

@@ -7,7 +7,10 @@ versband_amd.harness.plan_row_batches), and the batch is decoded and vocoded on 
 those of scripts/test_final.py.  The work goes group by group: a group's items are loaded, sampled, written and dropped before the next
 group is formed, so memory does not grow with the manifest and a crash loses one group.  `--items_per_batch 1` (the default) makes the
 calls of test_final.py's loop, one per (item, scale).  `--synthetic_frames` additionally accepts a comma list that cycles over the
-synthetic items; every other flag is test_final.py's and is parsed by its parser.
+synthetic items; every other flag is test_final.py's and is parsed by its parser.  `--length_slack N` lets consecutive items whose latent
+lengths differ by at most N tokens share a call too: the group is padded to its longest member and sampled with per-row lengths
+(vb_sample_cfg_lens - a row is the call on that clip alone), then every row is cut to its own length and rows of equal length are
+decoded and vocoded together.
 """
 from __future__ import annotations
 
@@ -27,7 +30,7 @@ for p in (ROOT, HERE):
 import test_final as loop  # noqa: E402
 from versband_amd import dist as vdist  # noqa: E402
 from versband_amd.harness import (MEL_DOWNSAMPLE, InferDataset, check_items_per_batch, parse_frames,  # noqa: E402
-                                  plan_row_batches, save_rows_to_tsv, stream_groups, write_wav_pcm16)
+                                  plan_row_batches, save_rows_to_tsv, stream_length_groups, write_wav_pcm16)
 from versband_amd.model import normalize_loudness  # noqa: E402
 
 
@@ -41,6 +44,10 @@ def parse_args(argv=None):
                      help="consecutive items of equal length that share ONE sampler call per group - all their guided scales and samples as "
                           "rows of one batch, decoded and vocoded on the device; the files are byte-identical to the per-item loop's "
                           "(default 1: that loop's calls).  items x guided scales x n_samples may not exceed 32 rows")
+    own.add_argument("--length_slack", type=int, default=0,
+                     help="latent tokens by which the items of one group may differ in length (default 0: equal lengths only, today's "
+                          "grouping): consecutive items join a group while its longest member is at most this much longer than every "
+                          "member; the group is sampled as one call padded to the longest, each row being the call on that clip alone")
     own.add_argument("--synthetic_frames", type=str, default="1500",
                      help="mel frames of a synthetic item: one integer, or a comma list that cycles over the items (150,150,230)")
     own.add_argument("--vocoder_precision", type=str, default="fp32mf", choices=["fp32mf", "fp32", "split", "bf16", "bf16xt"],
@@ -60,6 +67,9 @@ def parse_args(argv=None):
     args.items_per_batch, args.synthetic_frames = mine.items_per_batch, parse_frames(mine.synthetic_frames)
     args.vocoder_precision = mine.vocoder_precision
     args.guidance_interval = mine.guidance_interval
+    if mine.length_slack < 0:
+        own.error(f"--length_slack must be at least 0, got {mine.length_slack}")
+    args.length_slack = mine.length_slack
     check_items_per_batch(args.items_per_batch, list(dict.fromkeys(_scales(args))), args.n_samples)
     return args
 
@@ -109,15 +119,19 @@ def _item_conditioning(sampler, item, n, device, guided):
     return c, uc
 
 
-def _cat_conditioning(parts):
-    """row-wise concatenation of learned conditionings (caption embeddings, index tracks, names)"""
+def _cat_conditioning(parts, frames=None):
+    """row-wise concatenation of learned conditionings (caption embeddings, index tracks, names); frames: the tracks of shorter items are
+    zero-padded to that many mel frames first (a call with row lengths never reads the padding)"""
+    def track(t):
+        return t if frames is None or t.shape[-1] == frames else torch.nn.functional.pad(t, (0, frames - t.shape[-1]))
     return {"caption": torch.cat([c["caption"] for c in parts]),
-            "acoustic": {k: torch.cat([c["acoustic"][k] for c in parts]) for k in ("acoustic", "midi", "beats")},
+            "acoustic": {k: torch.cat([track(c["acoustic"][k]) for c in parts]) for k in ("acoustic", "midi", "beats")},
             "name": [nm for c in parts for nm in c["name"]]}
 
 
 def sample_group(args, sampler, vocoder, group, scales, device):
-    """the sampler calls of harness.plan_row_batches for ONE group of same-length items: group = [(global index, item)].  A row is what
+    """the sampler calls of harness.plan_row_batches for ONE group of items (of equal length, or within --length_slack of each other:
+    the call then carries the row lengths and its rows are cut to them before decoding): group = [(global index, item)].  A row is what
     test_final.py computes for (item, scale, sample): the item's conditioning and start noise (the same for every scale of an item), its
     own guidance scale and its global clip index gi * n_samples + k as noise key - so the rows, and after the batched decode and vocoder
     the files, equal the loop's.  Returns {(position in the group, scale): [(mel [80,T], wav numpy)] per sample}."""
@@ -129,22 +143,29 @@ def sample_group(args, sampler, vocoder, group, scales, device):
     conds = [_item_conditioning(sampler, it, n, device, has_guided) for it in items]
     starts = [torch.randn(n, embed_dim, lengths[p], generator=torch.Generator().manual_seed(args.seed + gi)).to(device) for p, gi in enumerate(indices)]
     generated = {}
-    for call in plan_row_batches(lengths, list(dict.fromkeys(scales)), n, args.items_per_batch, indices):
+    for call in plan_row_batches(lengths, list(dict.fromkeys(scales)), n, args.items_per_batch, indices, getattr(args, "length_slack", 0)):
         rows = call["rows"]
         runs = [(p, s) for p, s, k in rows if k == 0]                          # rows come as runs of n samples of one (item, scale)
-        c = _cat_conditioning([conds[p][0] for p, _ in runs])
-        uc = _cat_conditioning([conds[p][1] for p, _ in runs]) if call["n_branch"] == 2 else None
-        x = torch.cat([starts[p] for p, _ in runs])
+        row_lengths = call.get("row_lengths")                                  # None: one length, today's call
+        frames = call["length"] * MEL_DOWNSAMPLE if row_lengths else None
+        c = _cat_conditioning([conds[p][0] for p, _ in runs], frames)
+        uc = _cat_conditioning([conds[p][1] for p, _ in runs], frames) if call["n_branch"] == 2 else None
+        x = torch.cat([torch.nn.functional.pad(starts[p], (0, call["length"] - lengths[p])) if row_lengths else starts[p] for p, _ in runs])
         scale = [s for _, s, _ in rows] if call["n_branch"] == 2 else 1.0
         interval = getattr(args, "guidance_interval", None)
         gk = {"guidance_interval": interval} if interval is not None and call["n_branch"] == 2 else {}
         z, _ = sampler.sample_cfg(cond=c, unconditional_guidance_scale=scale, unconditional_conditioning=uc, batch_size=len(rows),
                                   shape=[embed_dim, call["length"]], x_latent=x, timesteps=args.ddim_steps + 1, seed=args.seed,
-                                  clip_ids=call["clip_ids"], **gk)
-        mel = sampler.model.decode_first_stage(z)
-        wav = vocoder.spec2wav_batch(mel).cpu().numpy()
+                                  clip_ids=call["clip_ids"], **gk, **({"lengths": row_lengths} if row_lengths else {}))
+        # the VAE and the vocoder take rows of one length: rows of equal length go through them together
+        done = {}
+        for length in dict.fromkeys(row_lengths or [call["length"]]):
+            idx = [r for r in range(len(rows)) if not row_lengths or row_lengths[r] == length]
+            mel = sampler.model.decode_first_stage(z[idx][:, :, :length].contiguous() if row_lengths else z)
+            wav = vocoder.spec2wav_batch(mel).cpu().numpy()
+            done.update({r: (mel[j], wav[j]) for j, r in enumerate(idx)})
         for r, (p, s, k) in enumerate(rows):
-            generated.setdefault((p, s), []).append((mel[r], wav[r]))
+            generated.setdefault((p, s), []).append(done[r])
     return generated
 
 
@@ -200,7 +221,7 @@ def gen_song(rank, args):
     rows, mel_rows = [], []
     item_idx = 0
     loaded = ((gi, dataset[gi]) for gi in indices)                  # lazily, in shard order: an item is read when its group is formed
-    for group in stream_groups(loaded, lambda e: int(e[1]["acoustic"].shape[1] / MEL_DOWNSAMPLE), args.items_per_batch):
+    for group in stream_length_groups(loaded, lambda e: int(e[1]["acoustic"].shape[1] / MEL_DOWNSAMPLE), args.items_per_batch, args.length_slack):
         generated = sample_group(args, sampler, vocoder, group, scales, device)
         for p, (gi, item) in enumerate(group):
             write_item(args, rank, item_idx, item, scales, {s: generated[(p, s)] for s in scales}, rows, mel_rows, mel_net)

@@ -76,6 +76,10 @@ class Guidance(C.Structure):
     _fields_ = [("weight", C.POINTER(c_float))]
 
 
+class Lens(C.Structure):
+    _fields_ = [("len", C.POINTER(C.c_int32))]
+
+
 class MelConfig(C.Structure):
     _fields_ = [("n_fft", c_int), ("hop", c_int), ("n_mels", c_int)]
 
@@ -125,6 +129,11 @@ PROTOTYPES = {
                                       C.POINTER(Noise), P, P, P]),
     "vb_sample_cfg_sched": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_float, C.POINTER(Guidance), C.POINTER(Windows), C.POINTER(Rows),
                                     C.POINTER(Keep), C.POINTER(Noise), P, P, P]),
+    "vb_dit_precompute_cond_lens": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, C.POINTER(Lens), P, P, P]),
+    "vb_dit_forward_lens": (c_int, [P, P, P, P, C.POINTER(Noise), c_int, c_int, c_int, c_int, C.POINTER(Lens), P, P, P, P]),
+    "vb_sample_cfg_lens": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_float, C.POINTER(Lens), C.POINTER(Guidance), C.POINTER(Windows),
+                                   C.POINTER(Rows), C.POINTER(Keep), C.POINTER(Noise), P, P, P]),
+    "vb_attention_lens": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     "vb_window_blend": (c_int, [P, C.POINTER(C.c_int32), c_int, c_int, c_int, c_int, P]),
     "vb_sample_graphs": (c_int, [P]),
     "vb_net_load": (c_int, [P, c_int, C.POINTER(NetOp), c_int, C.POINTER(BufDesc), c_int, c_int, c_int, c_int, c_int]),

@@ -40,12 +40,18 @@ int vb_grouped_swiglu(const void* u, const int32_t* perm, const int32_t* group_o
 }
 int vb_attention(const void* q, const void* k, const void* vt, const void* ky, const void* vyt, const float* cross_w, int B, int T,
                  int Tpad, int L, int Lpad, int H, int hd, int np, void* out, void* stream) {
+    return vb_attention_lens(q, k, vt, ky, vyt, cross_w, B, T, Tpad, L, Lpad, H, hd, np, nullptr, out, stream);
+}
+int vb_attention_lens(const void* q, const void* k, const void* vt, const void* ky, const void* vyt, const float* cross_w, int B, int T,
+                      int Tpad, int L, int Lpad, int H, int hd, int np, const int32_t* key_len, void* out, void* stream) {
+    if (key_len && !k) VB_FAIL(VB_E_INVALID, "attention_lens: key_len without self-attention keys");
     AttnArgs a;
     const int64_t ND = (int64_t)B * T * H * hd;
     a.q = wpl(q, ND, np); a.k = wpl(k, ND, np); a.vt = wpl(vt, (int64_t)B * H * hd * Tpad, np);
     a.ky = wpl(ky, (int64_t)B * L * H * hd, np); a.vyt = wpl(vyt, (int64_t)B * H * hd * Lpad, np);
     a.cross_w = cross_w; a.out = wpl(out, ND, np); a.B = B; a.T = T; a.Tpad = Tpad; a.L = L; a.Lpad = Lpad; a.H = H; a.hd = hd;
     a.has_self = k != nullptr; a.has_cross = ky != nullptr; a.kv_batch_mod = 0; a.scale = 1.0f / sqrtf((float)hd);
+    a.key_len = key_len; a.key_len_mod = B;
     return launch_attention(a, (hipStream_t)stream);
 }
 int vb_conv1d_f32(const float* x, const float* w, const float* bias, int B, int Ci, int T_in, int Co, int ksize, int dil, int pad,

@@ -1,6 +1,6 @@
 // Flash attention for the DiT blocks (gfx950, head_dim 96, bf16 planes, fp32 softmax).
 //
-//   out = softmax(q k^T * s) v            (self, T keys)
+//   out = softmax(q k^T * s) v            (self, T keys - or, with row lengths, the first key_len[b] keys of row b)
 //       + w[h] * softmax(q ky^T * s) vy   (cross, L keys; two SEPARATE softmaxes,
 //                                           flag_large_dit_moe.py:381-402)
 //
@@ -13,6 +13,12 @@
 // V^T (stored d-major by the QKV GEMM epilogue) with two 8-byte LDS reads - no
 // cross-lane shuffle of P at all.
 // SPLIT = bf16x3 parity mode (hi*hi + lo*hi + hi*lo for both Q K^T and P V).
+// Row lengths (AttnDev::key_len, rows of different clips padded to T): row b's self pass walks ceil(len / 64) key tiles and masks the keys
+// >= len of the last one the way keys >= T are masked - the key count and K's row stride (T) are separate arguments of kv_pass.  Query rows
+// >= len are padding: inside a workgroup that still holds valid rows they are computed as copies of row len - 1, exactly what the rows >= T of
+// the clip alone are (the deferred rescale decides per wave, so a wave must see the same 32 queries as alone), and written - finite; a
+// workgroup of padding rows alone writes zeros and leaves before any K/V load.  A masked key has p = 0 but its V column still enters the
+// MFMA: V^T up to the tile's end must be finite (the finiteness invariant).
 // (Round 3, measured and dropped: the cross keys visited twice - statistics pass in front of the self pass, accumulate pass behind
 //  it - removes the 48-KB stash (LDS 74 -> 26 KB), but at two waves per SIMD the kernel runs 64.4 us against 61.7 with the stash, and
 //  three waves per SIMD need <= 168 registers where the kernel holds 254 (o 48 + s 32 + q 24 + K/V prefetch 24 + fragments): forced,
@@ -42,6 +48,7 @@ struct AttnDev {
     bf16_t* out; int64_t out_plane; int out_np;
     int B, T, Tpad, L, Lpad, H, D;
     int has_self, has_cross, kv_batch_mod, nq;
+    const int* key_len; int key_len_mod;      // null: every row has T keys
     float scale_log2e, defer_thr;
 };
 
@@ -62,7 +69,21 @@ __global__ void __launch_bounds__(256) attn_kernel(const AttnDev p) {
     const int b = bh / p.H, h = bh - b * p.H;
     const int q0 = (jx % p.nq) * 128 + wave * 32;
     const int qrow = q0 + ql;
-    const int qrow_c = qrow < p.T ? qrow : p.T - 1;
+    const int klen = p.key_len ? p.key_len[b % p.key_len_mod] : p.T;      // this row's tokens (wave-uniform)
+    if (p.key_len && (jx % p.nq) * 128 >= klen) {
+        // 128 padding rows: zeros (a later launch reads them), no K/V traffic
+        if (qrow < p.T) {
+            const int64_t base = ((int64_t)b * p.T + qrow) * p.D + h * HD + g * 48;
+            const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+                *reinterpret_cast<bf16x8*>(p.out + base + i * 8) = z;
+                if (p.out_np == 2) *reinterpret_cast<bf16x8*>(p.out + p.out_plane + base + i * 8) = z;
+            }
+        }
+        return;
+    }
+    const int qrow_c = qrow < klen ? qrow : klen - 1;
 
     // ---- Q fragments (B operand): Q[q = ql][d = ks*16 + g*8 .. +8]
     bf16x8 qf[6], qlf[6];
@@ -82,7 +103,8 @@ __global__ void __launch_bounds__(256) attn_kernel(const AttnDev p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
 
-    auto kv_pass = [&](const bf16_t* Kg, int64_t kplane, const bf16_t* Vg, int64_t vplane, int nkeys, int vpad, int kb_batch,
+    // nkeys: keys attended over; krows: K rows per batch row (the stride; >= nkeys)
+    auto kv_pass = [&](const bf16_t* Kg, int64_t kplane, const bf16_t* Vg, int64_t vplane, int nkeys, int krows, int vpad, int kb_batch,
                        f32x16 (&acc)[3], float& l_out) __attribute__((always_inline)) {
         float m_run = -1e30f, l_run = 0.f;
         const int ntiles = (nkeys + KT - 1) / KT;
@@ -96,7 +118,7 @@ __global__ void __launch_bounds__(256) attn_kernel(const AttnDev p) {
                 const int id = tid + i * 256;
                 const int key = id / 12, c = id - key * 12;
                 const bool ok = (key0 + key) < nkeys;
-                const bf16_t* src = Kg + ((int64_t)kb_batch * nkeys + (ok ? key0 + key : 0)) * p.D + h * HD + c * 8;
+                const bf16_t* src = Kg + ((int64_t)kb_batch * krows + (ok ? key0 + key : 0)) * p.D + h * HD + c * 8;
                 kr[i] = ok ? *reinterpret_cast<const uint4*>(src + pl * kplane) : make_uint4(0, 0, 0, 0);
                 const int d = id >> 3, c2 = id & 7;
                 // (LDS row d of the V^T tile holds V^T row pi(d): the O accumulator then carries 16 CONSECUTIVE head-dim columns per
@@ -257,7 +279,7 @@ __global__ void __launch_bounds__(256) attn_kernel(const AttnDev p) {
     if (p.has_cross) {
         float lc;
         const int kb_batch = p.kv_batch_mod > 0 ? (b % p.kv_batch_mod) : b;
-        kv_pass(p.ky, p.ky_plane, p.vyt, p.vyt_plane, p.L, p.Lpad, kb_batch, o, lc);
+        kv_pass(p.ky, p.ky_plane, p.vyt, p.vyt_plane, p.L, p.L, p.Lpad, kb_batch, o, lc);
         const float w = (p.cross_w ? p.cross_w[h] : 1.f) / lc;
 #pragma unroll
         for (int i = 0; i < 3; ++i)
@@ -271,7 +293,7 @@ __global__ void __launch_bounds__(256) attn_kernel(const AttnDev p) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) { stash[wave][i * 16 + r][lane] = o[i][r]; o[i][r] = 0.f; }
         }
-        kv_pass(p.k, p.k_plane, p.vt, p.vt_plane, p.T, p.Tpad, b, o, res_l);
+        kv_pass(p.k, p.k_plane, p.vt, p.vt_plane, klen, p.T, p.Tpad, b, o, res_l);
         const float inv = 1.f / res_l;
 #pragma unroll
         for (int i = 0; i < 3; ++i)
@@ -304,12 +326,14 @@ int launch_attention(const AttnArgs& a, hipStream_t st) {
     if (a.has_self && (a.Tpad % KT || a.Tpad < a.T)) VB_FAIL(VB_E_INVALID, "attention: Tpad=%d must be a multiple of %d >= T", a.Tpad, KT);
     if (a.has_cross && (a.Lpad % KT || a.Lpad < a.L)) VB_FAIL(VB_E_INVALID, "attention: Lpad=%d must be a multiple of %d >= L", a.Lpad, KT);
     if (!a.has_self && !a.has_cross) VB_FAIL(VB_E_INVALID, "attention: nothing to do");
+    if (a.key_len && (!a.has_self || a.key_len_mod < 1)) VB_FAIL(VB_E_INVALID, "attention: row lengths belong to the self pass (key_len_mod=%d)", a.key_len_mod);
     AttnDev d;
     d.q = a.q.p; d.q_plane = a.q.plane; d.k = a.k.p; d.k_plane = a.k.plane; d.vt = a.vt.p; d.vt_plane = a.vt.plane;
     d.ky = a.ky.p; d.ky_plane = a.ky.plane; d.vyt = a.vyt.p; d.vyt_plane = a.vyt.plane; d.cross_w = a.cross_w;
     d.out = a.out.p; d.out_plane = a.out.plane; d.out_np = a.out.np;
     d.B = a.B; d.T = a.T; d.Tpad = a.Tpad; d.L = a.L; d.Lpad = a.Lpad; d.H = a.H; d.D = a.H * a.hd;
     d.has_self = a.has_self; d.has_cross = a.has_cross; d.kv_batch_mod = a.kv_batch_mod;
+    d.key_len = a.key_len; d.key_len_mod = a.key_len_mod;
     d.scale_log2e = a.scale * 1.4426950408889634f;
     d.defer_thr = vb_tune().attn_defer_thr;
     const double ae = (double)a.B * a.H * a.hd * 2.0 * a.q.np;      // bytes per token (or key) row of one q/k/v/out tensor

@@ -105,6 +105,7 @@ WsL carve_ws(void* base, const vb_dit_config& c, int B, int nb, int T, int L) {
     o.row_step = cv.take<int64_t>((size_t)PRE_STEPS * Beff);
     o.modA = cv.take<bf16_t>((size_t)2 * PRE_STEPS * Beff * c.hidden);
     o.tn_table = cv.take<float>(1024);
+    o.len_table = cv.take<int>(64);
     o.total = cv.off;
     return o;
 }
@@ -196,12 +197,14 @@ DitPlan dit_plan(const vb_ctx* ctx, int B, int nb, int T, int L, int nb_active) 
 // DiT: conditioning precompute
 // ------------------------------------------------------------------------------------------
 // acoustic stem (vocal2music_moe.py:388-393) -> cd.ac
+// lens (device [B], null: none): the embeddings are zero from mel position 2 * len[b] on, so the k5p2 convolutions see the zero padding of
+// the clip alone; the pool and the 1x1 projection are position-local
 static int precompute_acoustic(const vb_dit_config& c, const vb_dit_weights& w, const int64_t* midi, const int64_t* beats, int B, int T, int T_mel,
-                               const CondL& cd, const WsL& s, hipStream_t st) {
+                               const int* lens, const CondL& cd, const WsL& s, hipStream_t st) {
     const int D = c.hidden, T_ac = T_mel / 2;
     ConvArgs cv;
     for (int which = 0; which < 2; ++which) {
-        VB_TRY(launch_embed_t(which ? beats : midi, which ? w.beats_emb : w.midi_emb, B, T_mel, D, which ? 3 : 130, s.tA, st));   // Embedding(3) / Embedding(130), vocal2music_moe.py:337-350
+        VB_TRY(launch_embed_t(which ? beats : midi, which ? w.beats_emb : w.midi_emb, B, T_mel, D, which ? 3 : 130, s.tA, st, lens, 2));   // Embedding(3) / Embedding(130), vocal2music_moe.py:337-350
         cv = ConvArgs();
         cv.x = s.tA; cv.x_bstride = (int64_t)D * T_mel; cv.Ci = D; cv.T_in = T_mel;
         cv.w = which ? w.beats_conv_w : w.midi_conv_w; cv.bias = which ? w.beats_conv_b : w.midi_conv_b;
@@ -240,7 +243,7 @@ static int precompute_caption(const vb_dit_config& c, const vb_dit_weights& w, c
     return launch_gemv_rows(s.pooled_ln, D, nullptr, 0, 1, w.cap_lin_w, w.cap_lin_b, Beff, D, D, 0, cd.cemb, D, st);
 }
 static int dit_precompute(vb_ctx* ctx, const float* t5, const int64_t* midi, const int64_t* beats, int B, int nb, int T, int T_mel,
-                          int L, void* cond, void* ws, hipStream_t st) {
+                          int L, const LensPlan& lp, void* cond, void* ws, hipStream_t st) {
     const vb_dit_config& c = ctx->cfg;
     const vb_dit_weights& w = ctx->w;
     if (T_mel > 2 * T + 8) VB_FAIL(VB_E_INVALID, "precompute: T_mel=%d too long for T=%d", T_mel, T);
@@ -252,7 +255,8 @@ static int dit_precompute(vb_ctx* ctx, const float* t5, const int64_t* midi, con
     WsL s = carve_ws(ws, c, B, nb, T, L);
     const int Beff = B * nb, D = c.hidden, E = c.num_experts, hd = D / c.heads, np = c.np;
     const int64_t NL = (int64_t)Beff * L;
-    VB_TRY(precompute_acoustic(c, w, midi, beats, B, T, T_mel, cd, s, st));
+    if (lp.B) VB_TRY(launch_lens_table(lp, s.len_table, st));
+    VB_TRY(precompute_acoustic(c, w, midi, beats, B, T, T_mel, lp.B ? s.len_table : nullptr, cd, s, st));
     VB_TRY(precompute_caption(c, w, t5, Beff, L, cd, s, st));
 
     // ---- per block: context K/V for Attention and MoE.cross_attention, acoustic gate logits
@@ -345,14 +349,21 @@ static int embed_latent(const Eval& e) {
     const int B = e.ev.B, T = e.ev.T, D = e.D;
     if (e.p.proj_in_gemm) {
         const int BT = B * T;
-        VB_TRY(launch_im2col_latent(e.ev.x, B, c.in_channels, T, 5, 2, PIN_KP, s.pin_a, (int64_t)BT * PIN_KP, e.st));
+        VB_TRY(launch_im2col_latent(e.ev.x, B, c.in_channels, T, 5, 2, PIN_KP, s.pin_a, (int64_t)BT * PIN_KP, e.st, e.ev.lens));
         GemmArgs g = gemm_operands(s.pin_a, (int64_t)BT * PIN_KP, PIN_KP, e.cd.pin_w, (int64_t)D * PIN_KP, PIN_KP, BT, D, PIN_KP, 3);
         g.epi = EPI_F32; g.bias = w.proj_in_b; g.out32 = s.h; g.ldc32 = D;
         g.add32 = e.cd.ac; g.dup_rows = e.Beff == 2 * B ? BT : 0; g.prof_class = 2;       // split-precision convolution work: counted with the conv class
         return launch_gemm(g, e.st);
     }
+    // a general convolution kernel: with row lengths it reads a masked copy of x (in the im2col buffer, which this route leaves free)
+    const float* x = e.ev.x;
+    if (e.ev.lens) {
+        float* xm = reinterpret_cast<float*>(s.pin_a);
+        VB_TRY(launch_mask_latent(x, B, c.in_channels, T, e.ev.lens, xm, e.st));
+        x = xm;
+    }
     ConvArgs cv;
-    cv.x = e.ev.x; cv.x_bstride = (int64_t)c.in_channels * T; cv.Ci = c.in_channels; cv.T_in = T; cv.x_bmod = B;
+    cv.x = x; cv.x_bstride = (int64_t)c.in_channels * T; cv.Ci = c.in_channels; cv.T_in = T; cv.x_bmod = B;
     cv.w = w.proj_in_w; cv.bias = w.proj_in_b; cv.Co = D; cv.ksize = 5; cv.pad = 2;
     if (e.p.proj_in_split_w) { cv.wp = (const bf16_t*)w.proj_in_w3; cv.Ci_pad = 32; cv.wp_plane = (int64_t)5 * D * 32; }
     cv.out = s.h; cv.out_bstride = (int64_t)T * D; cv.T_out = T; cv.out_transposed = 1;
@@ -374,6 +385,7 @@ static int attention_half(const Eval& e, int i) {
     at.q = e.q; at.k = e.k; at.vt = e.vt; at.ky = mkp(cd.ky[i], cd.n_k, np); at.vyt = mkp(cd.vyt[i], cd.n_vt, np);
     at.cross_w = bw.cross_w; at.out = e.a; at.B = e.Beff; at.T = T; at.Tpad = s.Tpad; at.L = e.ev.L; at.Lpad = cd.Lpad; at.H = c.heads;
     at.hd = e.hd; at.has_self = 1; at.has_cross = 1; at.kv_batch_mod = 0; at.scale = e.scale();
+    at.key_len = e.ev.lens; at.key_len_mod = e.ev.B;
     VB_TRY(launch_attention(at, e.st));
     g = gemm_operands(e.a.p, e.ND, D, bw.wo, (int64_t)D * D, D, N, D, D, e.nseg);
     g.epi = EPI_RESID_GATE; g.out32 = s.h; g.ldc32 = D; g.gate = mod + 2 * D; g.gate_ld = MODW; g.T = T;
@@ -582,19 +594,39 @@ size_t vb_dit_workspace_bytes(const vb_dit_config* cfg, int B, int n_branch, int
 }
 int vb_dit_precompute_cond(vb_ctx* ctx, const float* t5, const int64_t* midi, const int64_t* beats, int B, int n_branch, int T,
                            int T_mel, int L, void* cond, void* ws, void* stream) {
+    return vb_dit_precompute_cond_lens(ctx, t5, midi, beats, B, n_branch, T, T_mel, L, nullptr, cond, ws, stream);
+}
+int vb_dit_precompute_cond_lens(vb_ctx* ctx, const float* t5, const int64_t* midi, const int64_t* beats, int B, int n_branch, int T,
+                                int T_mel, int L, const vb_lens* lens, void* cond, void* ws, void* stream) {
     if (!ctx || !ctx->dit_loaded) VB_FAIL(VB_E_STATE, "precompute_cond: DiT not loaded");
     if (n_branch < 1 || n_branch > 2 || B < 1) VB_FAIL(VB_E_INVALID, "precompute_cond: B=%d n_branch=%d", B, n_branch);
+    LensPlan lp;
+    if (lens && lens->len) VB_TRY(lens_plan(lens->len, B, T, &lp));
+    if (lp.B && T_mel != 2 * T)
+        VB_FAIL(VB_E_INVALID, "precompute_cond_lens: T_mel=%d is not 2 * T = %d, which row lengths need (row %d has length %d)", T_mel, 2 * T,
+                lp.first_short(T), lp.len[lp.first_short(T)]);
     VB_HIP(hipSetDevice(ctx->device));
     RoctxRange rr("vb_dit_precompute_cond");
-    return dit_precompute(ctx, t5, midi, beats, B, n_branch, T, T_mel, L, cond, ws, (hipStream_t)stream);
+    return dit_precompute(ctx, t5, midi, beats, B, n_branch, T, T_mel, L, lp, cond, ws, (hipStream_t)stream);
 }
 int vb_dit_forward(vb_ctx* ctx, const float* x, const int64_t* t_idx, const void* cond, const vb_noise* noise, int B, int n_branch,
                    int T, int L, float* v_out, int32_t* route_out, void* ws, void* stream) {
+    return vb_dit_forward_lens(ctx, x, t_idx, cond, noise, B, n_branch, T, L, nullptr, v_out, route_out, ws, stream);
+}
+int vb_dit_forward_lens(vb_ctx* ctx, const float* x, const int64_t* t_idx, const void* cond, const vb_noise* noise, int B, int n_branch,
+                        int T, int L, const vb_lens* lens, float* v_out, int32_t* route_out, void* ws, void* stream) {
     if (!ctx || !ctx->dit_loaded) VB_FAIL(VB_E_STATE, "dit_forward: DiT not loaded");
+    LensPlan lp;
+    if (lens && lens->len) VB_TRY(lens_plan(lens->len, B, T, &lp));
     VB_HIP(hipSetDevice(ctx->device));        // the calling host thread may be new (one thread per stream): bind it to the context's GPU
     DitEval ev;
     ev.x = x; ev.t_idx = t_idx; ev.cond = cond; ev.ws = ws; ev.B = B; ev.nb = n_branch; ev.T = T; ev.L = L;
     ev.noise = noise; ev.v_out = v_out; ev.route_out = route_out; ev.zero_vt = true;
+    if (lp.B) {
+        int* table = carve_ws(ws, ctx->cfg, B, n_branch, T, L).len_table;
+        VB_TRY(launch_lens_table(lp, table, (hipStream_t)stream));
+        ev.lens = table;
+    }
     return dit_forward(ctx, ev, (hipStream_t)stream);
 }
 

@@ -222,14 +222,18 @@ int launch_mean_rows(const float* x, int B, int L, int D, float* out, hipStream_
 // ---------------------------------------------------------------------------
 // stem helpers (vocal2music_moe.py:388-393)
 // ---------------------------------------------------------------------------
-// out[b][d][t] = table[idx[b][t]][d]
-__global__ void embed_t_kernel(const int64_t* __restrict__ idx, const float* __restrict__ table, int B, int T, int D, int vocab, float* out) {
+// out[b][d][t] = table[idx[b][t]][d]; with row lengths (len: device [B], counted in units of len_mul positions) 0 for t >= len_mul * len[b],
+// and idx is not read there: the k5p2 convolutions behind it then see the zero padding of the clip alone
+__global__ void embed_t_kernel(const int64_t* __restrict__ idx, const float* __restrict__ table, int B, int T, int D, int vocab, float* out,
+                               const int* __restrict__ len, int len_mul) {
     __shared__ float tile[64][65];
     const int b = blockIdx.z, t0 = blockIdx.x * 64, d0 = blockIdx.y * 64;
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;   // 256 threads: 64 x 4
+    const int tend = len ? len_mul * len[b] : T;
     for (int i = ty; i < 64; i += 4) {
         int t = t0 + i;
-        if (t < T && d0 + tx < D) {
+        if (t >= tend) tile[i][tx] = 0.f;
+        else if (t < T && d0 + tx < D) {
             //  the host range-checks index tensors once per identity; the read itself is clamped so that a buffer refilled behind
             // that cache (raw pointer writes, DLPack aliases) can never index outside the table
             int64_t ix = idx[(int64_t)b * T + t];
@@ -243,8 +247,8 @@ __global__ void embed_t_kernel(const int64_t* __restrict__ idx, const float* __r
         if (d < D && t < T) out[((int64_t)b * D + d) * T + t] = tile[tx][i];
     }
 }
-int launch_embed_t(const int64_t* idx, const float* table, int B, int T, int D, int vocab, float* out, hipStream_t st) {
-    hipLaunchKernelGGL(embed_t_kernel, dim3(cdiv(T, 64), cdiv(D, 64), B), dim3(256), 0, st, idx, table, B, T, D, vocab, out);
+int launch_embed_t(const int64_t* idx, const float* table, int B, int T, int D, int vocab, float* out, hipStream_t st, const int* len, int len_mul) {
+    hipLaunchKernelGGL(embed_t_kernel, dim3(cdiv(T, 64), cdiv(D, 64), B), dim3(256), 0, st, idx, table, B, T, D, vocab, out, len, len_mul);
     VB_CHECK_LAUNCH();
     return VB_OK;
 }
@@ -289,10 +293,11 @@ int launch_transpose_bct_btc(const float* in, int B, int C, int T_in, int T_out,
 // ---------------------------------------------------------------------------
 // proj_in (Conv1d C -> D, k taps; vocal2music_moe.py:395) as a GEMM: the latent window of every token as one K-contiguous row
 //   A[plane][m = b*T + t][k = tap*32 + ci] = split-bf16( x[b][ci][t + tap - pad] )   (zero outside the clip, for ci >= C and for k >= taps*32)
+// With row lengths (len: device [B]) the clip of row b ends at len[b]: taps at or beyond it are zero and x is not read there.
 // and the split conv weights [2][taps][D][32] re-laid as B[plane][D][KP].  One thread = one 16-byte group of 8 consecutive k.
 // ---------------------------------------------------------------------------
 __global__ void im2col_latent_kernel(const float* __restrict__ x, int B, int C, int T, int taps, int pad, int KP, bf16_t* __restrict__ out,
-                                     int64_t plane) {
+                                     int64_t plane, const int* __restrict__ len) {
     const int gpr = KP >> 3;
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (int64_t)B * T * gpr) return;
@@ -300,21 +305,45 @@ __global__ void im2col_latent_kernel(const float* __restrict__ x, int B, int C, 
     const int b = m / T, t = m - b * T;
     const int k0 = gi * 8, tap = k0 >> 5, ci0 = k0 & 31;
     const int ts = t + tap - pad;
+    const int tend = len ? len[b] : T;
     bf16x8 hi, lo;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const int ci = ci0 + e;
-        const float v = (tap < taps && ci < C && ts >= 0 && ts < T) ? x[((int64_t)b * C + ci) * T + ts] : 0.f;
+        const float v = (tap < taps && ci < C && ts >= 0 && ts < tend) ? x[((int64_t)b * C + ci) * T + ts] : 0.f;
         hi[e] = f2bf(v);
         lo[e] = f2bf(v - bf2f(hi[e]));
     }
     *reinterpret_cast<bf16x8*>(out + (int64_t)m * KP + k0) = hi;
     *reinterpret_cast<bf16x8*>(out + plane + (int64_t)m * KP + k0) = lo;
 }
-int launch_im2col_latent(const float* x, int B, int C, int T, int taps, int pad, int KP, bf16_t* out, int64_t plane, hipStream_t st) {
+int launch_im2col_latent(const float* x, int B, int C, int T, int taps, int pad, int KP, bf16_t* out, int64_t plane, hipStream_t st, const int* len) {
     if (KP % 8 || C > 32 || taps * 32 > KP) VB_FAIL(VB_E_INVALID, "im2col_latent: C=%d taps=%d KP=%d", C, taps, KP);
     const int64_t n = (int64_t)B * T * (KP / 8);
-    hipLaunchKernelGGL(im2col_latent_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, x, B, C, T, taps, pad, KP, out, plane);
+    hipLaunchKernelGGL(im2col_latent_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, x, B, C, T, taps, pad, KP, out, plane, len);
+    VB_CHECK_LAUNCH();
+    return VB_OK;
+}
+// the same mask for the proj_in routes that are a general convolution kernel: out[b][c][t] = t < len[b] ? x[b][c][t] : 0 (a select: x's
+// padding, NaN included, is not read into the copy)
+__global__ void mask_latent_kernel(const float* __restrict__ x, int B, int C, int T, const int* __restrict__ len, float* __restrict__ out) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (int64_t)B * C * T) return;
+    const int t = (int)(idx % T), b = (int)(idx / ((int64_t)C * T));
+    out[idx] = t < len[b] ? x[idx] : 0.f;
+}
+int launch_mask_latent(const float* x, int B, int C, int T, const int* len, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(mask_latent_kernel, dim3(cdiv((int64_t)B * C * T, 256)), dim3(256), 0, st, x, B, C, T, len, out);
+    VB_CHECK_LAUNCH();
+    return VB_OK;
+}
+// the row lengths of a call, by value in the argument block (nothing of the caller's host array outlives the call, and a captured graph
+// holds its own copy), into the workspace table the kernels above and the attention read
+__global__ void lens_table_kernel(const LensPlan lp, int* __restrict__ out) {
+    if ((int)threadIdx.x < lp.B) out[threadIdx.x] = lp.len[threadIdx.x];
+}
+int launch_lens_table(const LensPlan& lp, int* out, hipStream_t st) {
+    hipLaunchKernelGGL(lens_table_kernel, dim3(1), dim3(64), 0, st, lp, out);
     VB_CHECK_LAUNCH();
     return VB_OK;
 }

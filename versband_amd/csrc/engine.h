@@ -26,8 +26,9 @@ struct SampleGraph {
         const void* keep_ref = nullptr; const void* keep_x0 = nullptr; const void* keep_mask = nullptr; float sigma_min = 0.f;   // vb_sample_cfg_keep (all null: a plain call)
         const void* rows_scale = nullptr; const void* rows_clip = nullptr;   // vb_sample_cfg_rows: the two POINTERS (cfg_scale is 0 beside rows_scale); their contents are read when the kernels run
         int nw = 0; std::array<int, 64> starts{};    // vb_sample_cfg_windows: the plan's VALUES (the kernel argument holds them); nw = 0: no windows
+        int nlens = 0; std::array<int, 64> lens{};   // vb_sample_cfg_lens: the row lengths' VALUES (the table fill at the head of the step loop holds them); nlens = 0: no lengths
         bool sched = false; std::array<float, 64> weights{};   // vb_sample_cfg_sched: the step weights' VALUES (launch arguments, and which steps run one branch); sched = false: no schedule
-        auto tie() const { return std::tie(x, cond, ws, B, nb, T, L, n_steps, cfg_scale, tune_gen, keep_ref, keep_x0, keep_mask, sigma_min, rows_scale, rows_clip, nw, starts, sched, weights); }
+        auto tie() const { return std::tie(x, cond, ws, B, nb, T, L, n_steps, cfg_scale, tune_gen, keep_ref, keep_x0, keep_mask, sigma_min, rows_scale, rows_clip, nw, starts, nlens, lens, sched, weights); }
         bool operator==(const Key& o) const { return tie() == o.tie(); }
     } key;
     int seen = 0;                         // calls with this key so far (the first runs eagerly, the second captures)
@@ -95,6 +96,7 @@ struct CondL {
 struct WsL {
     int* step; int64_t* t_idx_cur; int64_t* t_table; float* dt_table;
     float* tn_table;                                                // vb_sample_cfg_keep: t after every step (carved last: no other offset moves)
+    int* len_table;                                                 // vb_lens: the row lengths [B <= 64] (carved after it, by the same rule)
     float *temb0, *temb, *mod_all, *hl, *h, *cq32, *mc, *ma, *y32, *g1, *g2, *g3, *v;
     bf16_t* modA;                                                   // A operand (planes) of the adaLN tabulation GEMM
     float *temb0_s, *temb_s, *hl_s, *mod_s; int64_t* row_step;     // per-sample tables of the conditioning vectors of every step
@@ -143,6 +145,9 @@ struct DitEval {
     const int64_t* clip_rows = nullptr;                         // vb_sample_cfg_rows: device [B] global clip ids of the router noise (null: noise->clip_base + b)
     float* v_out = nullptr; int32_t* route_out = nullptr;
     bool zero_vt = false;                                       // clear the padded V^T planes first (a stand-alone call)
+    // vb_lens: device [B] row lengths (null: every row has T tokens).  The three places that look across a clip's end read it: proj_in's
+    // taps, the self-attention's keys, and - in precompute - the acoustic stem.  Both branches read len[b % B].
+    const int* lens = nullptr;
     const float* pre_mod = nullptr; const float* pre_hl = nullptr;   // this step's rows of the sampler's tabulated conditioning vectors
     int evals_before = -1;                                      // block evaluations already done in this call (< 0: stand-alone, see DitPlan::router_counts)
     const EulerStep* euler = nullptr;                           // sampler only: FinalLayer does this step's update in the same launch (x in place, v_out not written)
@@ -150,7 +155,7 @@ struct DitEval {
 int dit_forward(vb_ctx* ctx, const DitEval& ev, hipStream_t st);
 
 // ---- sampler.hip: one sampler call ------------------------------------------------------------
-// One call of vb_sample_cfg_sched (the older entry points forward to it), validated and normalised where it is made
+// One call of vb_sample_cfg_lens (the older entry points forward to it), validated and normalised where it is made
 // (sampler.hip:sample_call): the step loop launches from it and the graph cache keys on it, so an option is one member here.
 // THE RULE: anything a launch of the step loop bakes in is in the key (sample_key, below), by ADDRESS where the kernels read through the
 // pointer when they run, by VALUE where the launch argument - or the choice of launch - holds the value itself (SampleGraph::Key says which).
@@ -163,6 +168,7 @@ struct SampleCall {
     // windows: more than one (one is the plain call) - the rows are wp.nw windows of B / nw clips; after every update, in either form, the
     // overlapping tokens of neighbouring windows take their consensus value, before the trajectory copy
     WindowPlan wp; bool windows = false;
+    LensPlan lens;                          // row lengths: lens.B == B when some row is shorter than T, else 0 (the plain call); the step loop starts by writing them to the workspace table
     const float* gw = nullptr;              // host [n_steps] step weights (sample_steps has the kinds of step); null unless nb == 2 and some weight differs from 1
     const vb_noise* noise = nullptr;        // NOT keyed: the noise key travels through device memory, injected arrays keep a call eager
 };
@@ -174,6 +180,7 @@ inline SampleGraph::Key sample_key(const SampleCall& sc) {
     if (sc.keep) { key.keep_ref = sc.keep->ref; key.keep_x0 = sc.keep->x0; key.keep_mask = sc.keep->mask; key.sigma_min = sc.keep->sigma_min; }
     key.rows_scale = sc.rows.cfg_scale; key.rows_clip = sc.rows.clip;
     if (sc.windows) { key.nw = sc.wp.nw; std::copy(sc.wp.s, sc.wp.s + 64, key.starts.begin()); }
+    if (sc.lens.B) { key.nlens = sc.lens.B; std::copy(sc.lens.len, sc.lens.len + 64, key.lens.begin()); }
     if (sc.gw) { key.sched = true; std::copy(sc.gw, sc.gw + sc.n_steps, key.weights.begin()); }      // (a keyed call is graphable: n_steps <= PRE_STEPS = 64)
     return key;
 }

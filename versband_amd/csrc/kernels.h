@@ -96,6 +96,9 @@ struct AttnArgs {
     int has_self, has_cross;
     int kv_batch_mod;    // cross K/V batch index = b % kv_batch_mod (0: = b)
     float scale;
+    // row lengths (vb_lens), self pass only: device [key_len_mod] - batch row b attends over its first key_len[b % key_len_mod] keys and its
+    // query rows from there on are padding (null: T keys, no padding)
+    const int* key_len = nullptr; int key_len_mod = 1;
 };
 int launch_attention(const AttnArgs& a, hipStream_t st);
 
@@ -170,11 +173,24 @@ int launch_cast_planes(const float* x, int64_t n, Planes out, hipStream_t st);
 int launch_planes_to_f32(Planes in, int64_t n, float* out, hipStream_t st);
 int launch_fill_f32(float* p, int64_t n, float v, hipStream_t st);
 int launch_mean_rows(const float* x, int B, int L, int D, float* out, hipStream_t st);
-int launch_embed_t(const int64_t* idx, const float* table, int B, int T, int D, int vocab, float* out, hipStream_t st);   // (indices clamped to [0, vocab))
+// (indices clamped to [0, vocab); len: device [B] row lengths in units of len_mul positions - out is 0 from len_mul * len[b] on)
+int launch_embed_t(const int64_t* idx, const float* table, int B, int T, int D, int vocab, float* out, hipStream_t st, const int* len = nullptr, int len_mul = 1);
 int launch_pool_add(const float* a, const float* b, int B, int C, int T_in, float* out, hipStream_t st);
 int launch_transpose_bct_btc(const float* in, int B, int C, int T_in, int T_out, float* out, hipStream_t st);
 // proj_in as a GEMM: latent windows as K-contiguous split planes, conv weights re-laid as a GEMM operand
-int launch_im2col_latent(const float* x, int B, int C, int T, int taps, int pad, int KP, bf16_t* out, int64_t plane, hipStream_t st);
+// (len: device [B] row lengths - the clip of row b ends at len[b], taps beyond it are zero; null: T)
+int launch_im2col_latent(const float* x, int B, int C, int T, int taps, int pad, int KP, bf16_t* out, int64_t plane, hipStream_t st, const int* len = nullptr);
+// row lengths of a call (vb_lens): out[b][c][t] = t < len[b] ? x[b][c][t] : 0, what a general convolution kernel reads in place of x
+int launch_mask_latent(const float* x, int B, int C, int T, const int* len, float* out, hipStream_t st);
+// the validated lengths of a call, by value in the kernel's argument block like WindowPlan, and their way into the workspace table.
+// lens_plan checks len (HOST array) for B rows of T tokens: B <= 64, 1 <= len[b] <= T; VB_E_INVALID names the row otherwise.  B = 0 in
+// the plan: every row is full, the call is the plain one.
+struct LensPlan {
+    int B = 0; int len[64] = {};
+    int first_short(int T) const { for (int b = 0; b < B; ++b) if (len[b] < T) return b; return 0; }      // (for messages)
+};
+int lens_plan(const int32_t* len, int B, int T, LensPlan* out);
+int launch_lens_table(const LensPlan& lp, int* out, hipStream_t st);
 int launch_conv_w_to_gemm(const bf16_t* w3, int64_t w3_plane, int taps, int D, int KP, bf16_t* out, hipStream_t st);
 int launch_rows_dot(const float* x, const float* W, const float* bias, int N, int D, int E, float* out, hipStream_t st);
 // LayerNorm (no affine, eps) + adaLN modulate -> split-bf16 planes (FinalLayer input, vocal2music_moe.py:287-291)

@@ -19,6 +19,8 @@ static int sample_steps(vb_ctx* ctx, const SampleCall& sc, float* traj, hipStrea
     WsL s = carve_ws(sc.ws, c, B, n_branch, T, L);
     const int Beff = B * n_branch;
     const int64_t per = (int64_t)c.in_channels * T;
+    // row lengths: the values travel in the launch's argument block (a captured graph holds them; its key does too)
+    if (sc.lens.B) VB_TRY(launch_lens_table(sc.lens, s.len_table, st));
     // (a kernel, not hipMemsetAsync: the captured step loop then consists of kernel nodes only)
     VB_TRY(launch_fill_f32(reinterpret_cast<float*>(s.vt), (int64_t)s.n_vt * c.np / 2, 0.f, st));
     // The timestep embedding, every block's adaLN modulation and the high-level gate logits depend on (t_k, caption)
@@ -82,6 +84,7 @@ static int sample_steps(vb_ctx* ctx, const SampleCall& sc, float* traj, hipStrea
         ev.x = sc.x; ev.t_idx = s.t_idx_cur; ev.cond = sc.cond; ev.ws = sc.ws; ev.B = B; ev.nb = n_branch; ev.T = T; ev.L = L;
         if (single) ev.nb_active = 1;
         ev.noise = sc.noise; ev.noise_step = k; ev.step_ptr = s.step; ev.v_out = s.v; ev.clip_rows = sc.rows.clip;
+        if (sc.lens.B) ev.lens = s.len_table;
         if (tab) { ev.pre_mod = s.mod_s + (size_t)k * Beff * MODW; ev.pre_hl = s.hl_s + (size_t)k * c.depth * 2; }
         ev.evals_before = k * c.depth;
         if (fuse_k) ev.euler = &ek;
@@ -115,11 +118,12 @@ static SampleGraph* graph_entry(vb_ctx* ctx, const SampleGraph::Key& key) {
     return e;
 }
 
-// ---- vb_sample_cfg_sched as its steps: sample_call, sample_prologue, sample_graph | sample_steps -------------------------------
+// ---- vb_sample_cfg_lens as its steps: sample_call, sample_prologue, sample_graph | sample_steps -------------------------------
 // check the ABI arguments before anything is launched and state the call once.  Every normalisation happens here: per-row scales zero
-// the scalar one, a schedule of all ones or beside one branch (nothing to guide) is the plain call, and so is one window.
+// the scalar one, a schedule of all ones or beside one branch (nothing to guide) is the plain call, and so are one window and row
+// lengths that all equal T (lens_plan).
 static int sample_call(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps, float cfg_scale,
-                       const vb_guidance* guidance, const vb_windows* win, const vb_rows* rows, const vb_keep* keep, const vb_noise* noise,
+                       const vb_lens* lens, const vb_guidance* guidance, const vb_windows* win, const vb_rows* rows, const vb_keep* keep, const vb_noise* noise,
                        void* ws, SampleCall& sc) {
     sc.x = x; sc.cond = cond; sc.ws = ws; sc.B = B; sc.nb = n_branch; sc.T = T; sc.L = L; sc.n_steps = n_steps; sc.keep = keep; sc.noise = noise;
     if (rows) sc.rows = *rows;
@@ -136,6 +140,12 @@ static int sample_call(vb_ctx* ctx, float* x, const void* cond, int B, int n_bra
     }
     if (win) VB_TRY(window_plan(win->starts, win->nw, B, T, &sc.wp));
     sc.windows = win && sc.wp.nw > 1;
+    if (lens && lens->len) {
+        VB_TRY(lens_plan(lens->len, B, T, &sc.lens));
+        if (sc.lens.B && sc.windows)
+            VB_FAIL(VB_E_INVALID, "sample_cfg_lens: row %d has length %d of %d beside %d joint windows, which are equal-length by construction",
+                    sc.lens.first_short(T), sc.lens.len[sc.lens.first_short(T)], T, sc.wp.nw);
+    }
     return VB_OK;
 }
 
@@ -226,8 +236,14 @@ int vb_sample_cfg_sched(vb_ctx* ctx, float* x, const void* cond, int B, int n_br
                         const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_guidance* guidance,
                         const vb_windows* win, const vb_rows* rows, const vb_keep* keep, const vb_noise* noise, float* traj, void* ws,
                         void* stream) {
+    return vb_sample_cfg_lens(ctx, x, cond, B, n_branch, T, L, n_steps, t_idx_table, dt_table, cfg_scale, nullptr, guidance, win, rows, keep, noise, traj, ws, stream);
+}
+int vb_sample_cfg_lens(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
+                       const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_lens* lens, const vb_guidance* guidance,
+                       const vb_windows* win, const vb_rows* rows, const vb_keep* keep, const vb_noise* noise, float* traj, void* ws,
+                       void* stream) {
     SampleCall sc;
-    VB_TRY(sample_call(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, guidance, win, rows, keep, noise, ws, sc));
+    VB_TRY(sample_call(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, lens, guidance, win, rows, keep, noise, ws, sc));
     VB_HIP(hipSetDevice(ctx->device));
     RoctxRange rr("vb_sample_cfg");
     hipStream_t st = (hipStream_t)stream;

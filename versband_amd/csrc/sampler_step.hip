@@ -130,6 +130,21 @@ int window_plan(const int32_t* starts, int nw, int B, int n, WindowPlan* out) {
     *out = p;
     return VB_OK;
 }
+// row lengths of a call (vb_lens; HOST array): checked before anything is launched.  Lengths that all equal T are the plain call (B = 0).
+int lens_plan(const int32_t* len, int B, int T, LensPlan* out) {
+    if (!len) VB_FAIL(VB_E_INVALID, "lens: len is null");
+    if (B < 1 || B > 64) VB_FAIL(VB_E_INVALID, "lens: %d rows (1..64); row %d has no slot in the table", B, B < 1 ? 0 : 64);
+    LensPlan p;
+    bool full = true;
+    for (int b = 0; b < B; ++b) {
+        if (len[b] < 1 || len[b] > T) VB_FAIL(VB_E_INVALID, "lens: row %d has length %d (1..T = %d)", b, len[b], T);
+        p.len[b] = len[b];
+        full = full && len[b] == T;
+    }
+    p.B = full ? 0 : B;
+    *out = p;
+    return VB_OK;
+}
 int launch_window_blend(float* x, const WindowPlan& wp, int Bc, int C, int n, hipStream_t st) {
     int ov_max = 0;
     for (int w = 0; w + 1 < wp.nw; ++w) ov_max = std::max(ov_max, wp.s[w] + n - wp.s[w + 1]);

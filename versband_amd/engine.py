@@ -120,8 +120,10 @@ class DiTEngine:
         return self._ws
 
     # -- API ---------------------------------------------------------------
-    def precompute_cond(self, t5: Tensor, midi: Tensor, beats: Tensor, T: int, persistent: bool = False) -> dict:
+    def precompute_cond(self, t5: Tensor, midi: Tensor, beats: Tensor, T: int, persistent: bool = False, lengths=None) -> dict:
         """t5 [nb*B, L, ori] (cond rows then uncond rows), midi/beats [B,1,T_mel] or [B,T_mel] int64.
+        lengths: B row lengths in latent tokens (vb_lens) - row b's conditioning is that of the clip alone, midi / beats beyond
+        2 * lengths[b] are not read; needs T_mel == 2 T.  The handle remembers them: sample_cfg / forward must be given the same.
         persistent=True writes into an engine-owned buffer that the NEXT persistent precompute of the same shape overwrites (a
         serving loop: precompute -> sample -> discard): stable device addresses are what lets sample_cfg replay its captured
         hipGraph.  A stale handle is refused loudly (generation check) instead of sampling from overwritten conditioning."""
@@ -166,9 +168,10 @@ class DiTEngine:
         else:
             cond = torch.empty(n, dtype=torch.uint8, device=dev)
         ws = self._workspace(B, nb, T, Lc)
-        L.check(self.ctx.lib.vb_dit_precompute_cond(self.ctx.handle, L.ptr(t5), L.ptr(midi), L.ptr(beats), B, nb, T, T_mel, Lc,
-                                                    L.ptr(cond), L.ptr(ws), L.stream_ptr()), "vb_dit_precompute_cond")
-        return {"buf": cond, "B": B, "nb": nb, "T": T, "L": Lc, "gen": gen}
+        ls, held_lens, lens = DiTEngine._lens_struct(lengths, B, T, T_mel=T_mel)
+        L.check(self.ctx.lib.vb_dit_precompute_cond_lens(self.ctx.handle, L.ptr(t5), L.ptr(midi), L.ptr(beats), B, nb, T, T_mel, Lc,
+                                                         _ref(ls), L.ptr(cond), L.ptr(ws), L.stream_ptr()), "vb_dit_precompute_cond_lens")
+        return {"buf": cond, "B": B, "nb": nb, "T": T, "L": Lc, "gen": gen, "lengths": lens}
 
     def _check_cond(self, cond: dict):
         if cond.get("gen") is not None:
@@ -188,9 +191,10 @@ class DiTEngine:
         return ns, keep
 
     def forward(self, x: Tensor, t_idx: Tensor, cond: dict, noise=None, seed: int = 0, clip_base: int = 0, nfe: int = 0,
-                return_routes: bool = False):
+                return_routes: bool = False, lengths=None):
         """x [B,C,T] f32, t_idx int64 [nb*B]; noise = (g1 [depth,rows,2], g2 [depth,rows,E], g3 [depth,rows,E]) Gumbel
-        draws or None -> v [nb*B, C, T] (+ routes int32 [depth,2,rows])."""
+        draws or None -> v [nb*B, C, T] (+ routes int32 [depth,2,rows]).  lengths: the row lengths the conditioning was made with
+        (vb_lens); v and the routes of padding tokens are unspecified."""
         dev = self.ctx.device
         B, nb, T, Lc = cond["B"], cond["nb"], cond["T"], cond["L"]
         self._check_cond(cond)
@@ -201,8 +205,9 @@ class DiTEngine:
         routes = torch.empty(self.cfg.depth, 2, nb * B * T, dtype=torch.int32, device=dev) if return_routes else None
         ns, keep = self._noise_struct(noise, seed, clip_base, nfe)
         ws = self._workspace(B, nb, T, Lc)
-        L.check(self.ctx.lib.vb_dit_forward(self.ctx.handle, L.ptr(x), L.ptr(t_idx), L.ptr(cond["buf"]), C.byref(ns), B, nb, T, Lc,
-                                            L.ptr(v), L.ptr(routes), L.ptr(ws), L.stream_ptr()), "vb_dit_forward")
+        ls, held_lens, _ = DiTEngine._lens_struct(lengths, B, T, cond=cond)
+        L.check(self.ctx.lib.vb_dit_forward_lens(self.ctx.handle, L.ptr(x), L.ptr(t_idx), L.ptr(cond["buf"]), C.byref(ns), B, nb, T, Lc,
+                                                 _ref(ls), L.ptr(v), L.ptr(routes), L.ptr(ws), L.stream_ptr()), "vb_dit_forward_lens")
         return (v, routes) if return_routes else v
 
     def _keep_struct(self, keep, B: int, T: int, n: int):
@@ -329,6 +334,43 @@ class DiTEngine:
         return L.Windows(arr, nw), arr
 
     @staticmethod
+    def _lens_struct(lengths, B: int, T: int, windows=None, T_mel: Optional[int] = None, cond: Optional[dict] = None):
+        """validate the row lengths of a call - B integers in [1, T], the library's rules (include/versband_hip.h), stated here first so
+        that the error names the caller's argument - and lay them out as vb_lens (a host array, read during the call).  All equal to T
+        or None is the plain call.  cond: the conditioning handle the call samples from, which must have been made with the same
+        lengths.  Returns (struct or None, the array to hold, the lengths as a tuple or None)."""
+        lens = None
+        if lengths is not None:
+            if torch.is_tensor(lengths):
+                lengths = lengths.tolist()
+            try:
+                vals = list(lengths)
+            except TypeError:
+                raise TypeError(f"lengths must be a sequence of {B} row lengths, got {type(lengths).__name__}") from None
+            if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in vals):
+                raise TypeError("lengths must hold integers (latent tokens per row)")
+            if len(vals) != B:
+                raise ValueError(f"lengths has {len(vals)} entries for {B} rows")
+            if B > 64:
+                raise ValueError(f"lengths: {B} rows (at most 64)")
+            vals = [int(v) for v in vals]
+            for b, v in enumerate(vals):
+                if not 1 <= v <= T:
+                    raise ValueError(f"lengths[{b}] = {v} is not in [1, T = {T}]")
+            if any(v != T for v in vals):
+                lens = tuple(vals)
+        if cond is not None and cond.get("lengths") != lens:
+            raise ValueError(f"lengths {lens} differ from the lengths the conditioning was made with ({cond.get('lengths')})")
+        if lens is None:
+            return None, None, None
+        if windows is not None and len(list(windows)) > 1:
+            raise ValueError("lengths and joint windows do not go together: windows are equal-length by construction")
+        if T_mel is not None and T_mel != 2 * T:
+            raise ValueError(f"lengths need midi / beats of exactly 2 * T = {2 * T} frames, got {T_mel}")
+        arr = (C.c_int32 * B)(*lens)
+        return L.Lens(arr), arr, lens
+
+    @staticmethod
     def _guidance_struct(guidance, n: int):
         """validate per-step guidance weights - n finite numbers in [0, 16], the library's rules (include/versband_hip.h), stated here
         first so that the error names the caller's argument - and lay them out as vb_guidance (a host array, read during the call).
@@ -354,7 +396,7 @@ class DiTEngine:
 
     def sample_cfg(self, x0: Tensor, cond: dict, t_idx_table: Sequence[int], dt_table: Sequence[float], scale,
                    noise=None, seed: int = 0, clip_base: int = 0, return_traj: bool = False, keep=None, clip_ids=None, windows=None,
-                   guidance=None):
+                   guidance=None, lengths=None):
         """n Euler steps with classifier-free guidance; x0 [B,C,T] is not modified.
         scale: one number for the batch, or B values (sequence / float32 tensor): row b is guided by scale[b].  clip_ids: B global clip
         indices (sequence / int64 tensor): row b draws its router noise as clip clip_ids[b] instead of clip_base + b (vb_rows).
@@ -367,9 +409,14 @@ class DiTEngine:
         guidance: one weight in [0, 16] per step (vb_guidance) - step k runs under the effective scale 1 + guidance[k] * (scale - 1):
         1 is the plain step, 0 evaluates the conditional branch alone (about half the step's network time), anything between or
         beyond scales the guidance.  All ones or None is the plain call; with one branch (nb = 1) the weights are checked and unused.
-        Combines with all of the above."""
+        Combines with all of the above.
+        lengths: B row lengths in latent tokens (vb_lens), the ones the conditioning was made with - clips of different lengths as rows of
+        one call, padded to T: row b's first lengths[b] tokens are the call on that clip alone, the rest of x0's row is never read into
+        them.  The padding of the returned latent (and trajectory) is zero-filled.  Combines with scale, clip_ids, keep and guidance
+        (all per row or per step); not with more than one window."""
         dev = self.ctx.device
         B, nb, T, Lc = cond["B"], cond["nb"], cond["T"], cond["L"]
+        ls, held_lens, lens = DiTEngine._lens_struct(lengths, B, T, windows=windows, cond=cond)
         wstruct, held_win = self._windows_struct(windows, B, T) if windows is not None else (None, None)
         rs, scale, held_rows = self._rows_struct(scale, clip_ids, B, clip_base)
         self._check_cond(cond)
@@ -389,10 +436,15 @@ class DiTEngine:
         traj = torch.empty(n + 1, *x.shape, dtype=torch.float32, device=dev) if return_traj else None
         ws = self._workspace(B, nb, T, Lc)
         # always the most general entry point: an absent option is a null pointer, which is all the older entry points pass in its place
-        L.check(self.ctx.lib.vb_sample_cfg_sched(self.ctx.handle, L.ptr(x), L.ptr(cond["buf"]), B, nb, T, Lc, n, L.ptr(tt), L.ptr(dd),
-                                                 float(scale), _ref(gs), _ref(wstruct), _ref(rs), _ref(ks), _ref(ns), L.ptr(traj),
-                                                 L.ptr(ws), L.stream_ptr()), "vb_sample_cfg_sched")
+        L.check(self.ctx.lib.vb_sample_cfg_lens(self.ctx.handle, L.ptr(x), L.ptr(cond["buf"]), B, nb, T, Lc, n, L.ptr(tt), L.ptr(dd),
+                                                float(scale), _ref(ls), _ref(gs), _ref(wstruct), _ref(rs), _ref(ks), _ref(ns), L.ptr(traj),
+                                                L.ptr(ws), L.stream_ptr()), "vb_sample_cfg_lens")
         x = x.clone()
+        if lens is not None:            # the padding tokens are unspecified (vb_lens): the caller gets a defined tensor
+            for b, n_b in enumerate(lens):
+                x[b, :, n_b:] = 0
+                if traj is not None:
+                    traj[:, b, :, n_b:] = 0
         return (x, traj) if return_traj else x
 
     def graphs(self) -> int:

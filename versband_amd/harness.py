@@ -162,7 +162,26 @@ def stream_groups(items, length_of, items_per_batch: int):
         yield group
 
 
-def plan_row_batches(lengths, scales, n_samples: int, items_per_batch: int, indices=None) -> List[dict]:
+def stream_length_groups(items, length_of, items_per_batch: int, length_slack: int = 0):
+    """stream_groups with a length slack (--length_slack, latent tokens): a consecutive item joins the group while, with it, the longest
+    member is at most length_slack tokens longer than EVERY member (max - min <= length_slack) and the group holds fewer than
+    items_per_batch items.  Order is preserved; length_slack = 0 is stream_groups, group for group.  A group of mixed lengths is sampled
+    as one call padded to its longest member (DiTEngine.sample_cfg(lengths=...))."""
+    if length_slack < 0:
+        raise ValueError(f"--length_slack must be at least 0, got {length_slack}")
+    group, lo, hi = [], 0, 0
+    for it in items:
+        n = length_of(it)
+        if group and (len(group) >= items_per_batch or max(hi, n) - min(lo, n) > length_slack):
+            yield group
+            group = []
+        lo, hi = (min(lo, n), max(hi, n)) if group else (n, n)
+        group.append(it)
+    if group:
+        yield group
+
+
+def plan_row_batches(lengths, scales, n_samples: int, items_per_batch: int, indices=None, length_slack: int = 0) -> List[dict]:
     """The sampler calls of the inference loop as a list of
         {"n_branch": 1 | 2, "length": latent length, "items": [positions], "rows": [(position, scale, sample)], "clip_ids": [...]}
     lengths[p] is the latent length of the p-th item of this rank's shard, indices[p] its global index (default p); the global clip of a
@@ -170,7 +189,10 @@ def plan_row_batches(lengths, scales, n_samples: int, items_per_batch: int, indi
     Consecutive items (shard order) of equal length form a group of up to items_per_batch items.  Per group there is ONE guided call
     (n_branch = 2; rows = items x scales != 1.0 x samples, item-major, scales in the order given) and, where the scales hold 1.0, one
     unguided call (n_branch = 1; rows = items x samples).  items_per_batch = 1 is the per-item loop as it always ran: one call per
-    (item, scale) in the order of `scales`, rows = the item's samples."""
+    (item, scale) in the order of `scales`, rows = the item's samples.
+    length_slack > 0 groups by stream_length_groups instead; a call over items of different lengths has "length" = its longest item's
+    and one more key, "row_lengths": the latent length of every row (the `lengths` of the sampler call).  Calls over equal lengths are
+    the dicts they always were."""
     check_items_per_batch(items_per_batch, scales, n_samples)
     lengths = [int(v) for v in lengths]
     indices = list(range(len(lengths))) if indices is None else [int(v) for v in indices]
@@ -179,8 +201,11 @@ def plan_row_batches(lengths, scales, n_samples: int, items_per_batch: int, indi
 
     def call(nb, items, row_scales):
         rows = [(p, s, k) for p in items for s in row_scales for k in range(n_samples)]
-        return {"n_branch": nb, "length": lengths[items[0]], "items": list(items), "rows": rows,
-                "clip_ids": [indices[p] * n_samples + k for p, _, k in rows]}
+        out = {"n_branch": nb, "length": max(lengths[p] for p in items), "items": list(items), "rows": rows,
+               "clip_ids": [indices[p] * n_samples + k for p, _, k in rows]}
+        if any(lengths[p] != out["length"] for p in items):
+            out["row_lengths"] = [lengths[p] for p, _, _ in rows]
+        return out
 
     calls = []
     if items_per_batch == 1:
@@ -188,7 +213,7 @@ def plan_row_batches(lengths, scales, n_samples: int, items_per_batch: int, indi
             calls += [call(1 if s == 1.0 else 2, [p], [s]) for s in scales]
         return calls
     guided = [s for s in scales if s != 1.0]
-    for items in stream_groups(range(len(lengths)), lengths.__getitem__, items_per_batch):
+    for items in stream_length_groups(range(len(lengths)), lengths.__getitem__, items_per_batch, length_slack):
         if guided:
             calls.append(call(2, items, guided))
         if len(guided) < len(scales):

@@ -342,16 +342,16 @@ class CFM:
             return self.cond_stage_model.encode(c)
         return self.cond_stage_model(c)
 
-    def _precompute(self, conds: List[dict], T: int):
+    def _precompute(self, conds: List[dict], T: int, lengths=None):
         def sig(t):       # identity AND content version of a tensor: an in-place edit or a swapped tensor invalidates the entry
             return (t.data_ptr(), t._version, tuple(t.shape)) if torch.is_tensor(t) else id(t)
-        key = tuple((id(c), sig(c["caption"]), sig(c["acoustic"].get("midi")), sig(c["acoustic"].get("beats"))) for c in conds) + (T,)
+        key = tuple((id(c), sig(c["caption"]), sig(c["acoustic"].get("midi")), sig(c["acoustic"].get("beats"))) for c in conds) + (T, None if lengths is None else tuple(int(v) for v in lengths))
         hit = self._cond_cache.get(key)
         if hit is not None:
             return hit[0]
         ac = conds[0]["acoustic"]
         t5 = torch.cat([c["caption"].float().to(self.device) for c in conds], dim=0)
-        pc = self.dit_engine().precompute_cond(t5, ac["midi"], ac["beats"], T)
+        pc = self.dit_engine().precompute_cond(t5, ac["midi"], ac["beats"], T, **({} if lengths is None else {"lengths": lengths}))
         self._cond_cache = {key: (pc, conds)}     # single entry: holds the cond dicts alive so ids stay unique
         return pc
 
@@ -529,7 +529,7 @@ class CFMSampler(object):
     @torch.no_grad()
     def sample_cfg(self, cond, unconditional_guidance_scale, unconditional_conditioning, batch_size=16, timesteps=None, shape=None,
                    x_latent=None, t_start=None, gumbel_noise=None, seed=None, clip_base=0, x_known=None, keep_mask=None, keep_noise=None,
-                   clip_ids=None, *, guidance_weights=None, guidance_interval=None, **kwargs):
+                   clip_ids=None, *, guidance_weights=None, guidance_interval=None, lengths=None, **kwargs):
         """:87-116.  Extra kwargs (S=, x_T=, verbose=) are tolerated and ignored like the reference does
         (SURVEY Q1/Q2).  gumbel_noise/seed/clip_base are additions: injected router noise for parity, or the
         (seed, global clip index) that keys the on-device counter-based draws.
@@ -541,7 +541,10 @@ class CFMSampler(object):
         (addition; DiTEngine.sample_cfg): rows of different scales or non-contiguous clips then share the call.
         guidance_weights (one weight in [0, 16] per step) or guidance_interval = (lo, hi) (addition, keyword-only, at most one of them):
         step k runs under the effective scale 1 + w_k (scale - 1); the interval is w_k = 1 where the step starts at t in [lo, hi] and 0
-        elsewhere, and a step of weight 0 evaluates the conditional branch alone."""
+        elsewhere, and a step of weight 0 evaluates the conditional branch alone.
+        lengths (addition, keyword-only; DiTEngine.sample_cfg): one length in latent tokens per row - clips of different lengths padded
+        to shape[-1] share the call, row b's first lengths[b] tokens are the call on that clip alone (midi / beats hold 2 * shape[-1]
+        frames per row, those beyond 2 * lengths[b] are not read), the padding of the result is zero."""
         shape = self._shape(shape, batch_size)
         timesteps = 25 if timesteps is None else timesteps
         idx, dts = euler_tables(timesteps, t_start)
@@ -550,7 +553,7 @@ class CFMSampler(object):
         x0 = torch.randn(shape, device=dev) if x_latent is None else x_latent
         keep = keep_block(x_known, keep_mask, keep_noise, x0, t_start, shape, timesteps, self.model.sigma_min)
         conds = [cond] if unconditional_conditioning is None else [cond, unconditional_conditioning]
-        pc = self.model._precompute(conds, shape[-1])
+        pc = self.model._precompute(conds, shape[-1], **({} if lengths is None else {"lengths": lengths}))
         if seed is None:
             seed = int(torch.initial_seed()) & 0xFFFFFFFF
         scale = unconditional_guidance_scale
@@ -558,13 +561,14 @@ class CFMSampler(object):
             scale = float(scale)
         x, traj = self.model.dit_engine().sample_cfg(x0, pc, idx, dts, scale, noise=gumbel_noise,
                                                      seed=seed, clip_base=clip_base, return_traj=True, keep=keep, clip_ids=clip_ids,
-                                                     **({} if guidance is None else {"guidance": guidance}))
+                                                     **({} if guidance is None else {"guidance": guidance}),
+                                                     **({} if lengths is None else {"lengths": lengths}))
         return traj[-1], traj
 
     @torch.no_grad()
     def sample(self, cond, batch_size=16, timesteps=None, shape=None, x_latent=None, t_start=None, x_known=None, keep_mask=None,
                keep_noise=None, clip_ids=None, **kwargs):
-        """:49-80 (no guidance)."""
+        """:49-80 (no guidance).  (lengths= travels in kwargs, as in sample_cfg.)"""
         return self.sample_cfg(cond, 1.0, None, batch_size=batch_size, timesteps=timesteps, shape=shape, x_latent=x_latent,
                                t_start=t_start, x_known=x_known, keep_mask=keep_mask, keep_noise=keep_noise, clip_ids=clip_ids, **kwargs)
 
