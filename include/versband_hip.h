@@ -469,6 +469,34 @@ int vb_gemm_bf16(const void* A, const void* Bw, const float* bias, int M, int N,
  *   out f32 [Ntok][D] = row_scale[tok] * FFN_g(u[tok]) written at perm order; hidden scratch planes [Nslots][H] */
 int vb_grouped_swiglu(const void* u, const int32_t* perm, const int32_t* group_off, int G, int n_slots, const void* w13,
                       const void* w2, const float* row_scale, int D, int H, int np, void* hidden, float* out, void* stream);
+/* The MoE block's fused kernels, each alone (bf16 mode only; no eligibility rule and no token-count threshold of the engine applies):
+ * band-expert FFN in one launch (vocal2music_moe.py:171-178): expert e reads band e of y and updates band e of out32 in place,
+ *   out32[m][e*band + n] += gate[m / T][e*band + n] * ( W2_e . (silu(W1_e y_e[m]) * (W3_e y_e[m])) )[n]
+ *   y bf16 [M][ldy]; w13 bf16 [E][2H][band], w1 / w3 rows interleaved; w2 bf16 [E][band][H]; gate f32 [ceil(M / T)][gate_ld];
+ *   out32 f32 [M][ldc32].  band = 192 or 96, H % 64 == 0, E divides 8. */
+int vb_band_ffn(const void* y, int ldy, const void* w13, const void* w2, int M, int H, int E, int band, const float* gate, int gate_ld, int T,
+                float* out32, int ldc32, void* stream);
+/* routed experts in the pair form (vocal2music_moe.py:152-167), the two launches of the engine: the grouped SwiGLU over the 2E expert groups
+ * of group_off with the gate weights folded into the hidden rows (slot < N: mc[token], otherwise ma[token]; token = perm[slot]) ->
+ * hidden bf16 [2N][H]; then the pair-bucketed second product -> out bf16 [N][D] = Hs[p] W2[c]^T + Hs[pair_pa[p]] W2[E + a]^T at row perm[p].
+ *   u bf16 [N][D]; perm / group_off / pair_off / pair_pa from vb_route_bucket_pairs; w13 bf16 [2E][2H][D] interleaved; w2 bf16 [2E][D][H];
+ *   mc, ma f32 [N].  H % 64 == 0, D % 16 == 0, E*E <= 16. */
+int vb_routed_ffn_pair(const void* u, const int32_t* perm, const int32_t* group_off, const int32_t* pair_off, const int32_t* pair_pa, const void* w13,
+                       const void* w2, const float* mc, const float* ma, int N, int D, int H, int E, void* hidden, void* out, void* stream);
+/* folded caption gate + router (vocal2music_moe.py:117-151) on the caller's operands, N = Beff * T token rows, row = (branch * B + b) * T + t:
+ *   x bf16 [N][K] token features; keys bf16 [Beff][NS][K] folded keys; score_bias f32 [Beff][NS]; vw f32 [Beff][NS][E]; bg f32 [E];
+ *   score column = key * Hh + head; logit_e = sum over heads and keys of softmax_keys(x . keys^T + score_bias) * vw[..][e]  (+ bg[e])
+ *   la f32 [la_rows][E] acoustic logits, row n % la_rows; hl f32 [Beff][hl_ld], columns 0 / 1 = the high-level gate's logits of row n / T;
+ *   g1 [N][2], g2 [N][E], g3 [N][E] injected Gumbel noise, or all null: drawn on the device from (seed, clip_base + b, nfe, branch, block)
+ *   ic = argmax(logit + bg + g2), ia = argmax(la + g3) (first maximum), (mc, ma) = softmax(hl + g1); lc_out (form 0, optional) f32 [N][E] =
+ *   logit + bg; cnt (optional, zero on entry) int32 [ceil(N / 256)][cnt_G]: tokens per 256-token block and expert pair ic * E + ia
+ *   (cnt_pairs = 1, cnt_G = E*E) or per expert group ic / E + ia (cnt_pairs = 0, cnt_G = 2E).
+ * form 0: grouped score GEMM into scores (scratch f32 [N][NS]; clip_off scratch int32 [Beff + 1]) + the router launch;
+ * form 1: the one-launch kernel (NS = 640, K = 768, E = 4, Hh = 8; VB_E_INVALID otherwise; lc_out must be null). */
+int vb_caption_gate(const void* x, const void* keys, const float* score_bias, const float* vw, const float* bg, const float* la, int la_rows,
+                    const float* hl, int hl_ld, const float* g1, const float* g2, const float* g3, uint64_t seed, int64_t clip_base, int nfe,
+                    int block, int Beff, int B, int T, int K, int NS, int Hh, int E, int form, float* scores, int32_t* clip_off, int32_t* ic,
+                    int32_t* ia, float* mc, float* ma, float* lc_out, int32_t* cnt, int cnt_G, int cnt_pairs, void* stream);
 /* fused self (+cross) attention, head_dim 96 (Attention.forward, flag_large_dit_moe.py:381-402) */
 int vb_attention(const void* q, const void* k, const void* vt, const void* ky, const void* vyt, const float* cross_w, int B, int T,
                  int Tpad, int L, int Lpad, int H, int hd, int np, void* out, void* stream);

@@ -157,6 +157,10 @@ PROTOTYPES = {
     "vb_route_bucket_pairs": (c_int, [P, P, c_int, c_int, P, P, P, P, P]),
     "vb_gemm_bf16": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P]),
     "vb_grouped_swiglu": (c_int, [P, P, P, c_int, c_int, P, P, P, c_int, c_int, c_int, P, P, P]),
+    "vb_band_ffn": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, P, c_int, P]),
+    "vb_routed_ffn_pair": (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P]),
+    "vb_caption_gate": (c_int, [P, P, P, P, P, P, c_int, P, c_int, P, P, P, c_u64, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                c_int, c_int, c_int, P, P, P, P, P, P, P, P, c_int, c_int, P]),
     "vb_attention": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
     "vb_conv1d_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                               c_float, P, P, P, c_int, P]),

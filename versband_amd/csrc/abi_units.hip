@@ -38,6 +38,63 @@ int vb_grouped_swiglu(const void* u, const int32_t* perm, const int32_t* group_o
     g.epi = EPI_SCATTER_F32; g.out32 = out; g.ldc32 = D; g.rows_out = perm; g.row_scale = row_scale;
     return launch_gemm(g, st);
 }
+int vb_band_ffn(const void* y, int ldy, const void* w13, const void* w2, int M, int H, int E, int band, const float* gate, int gate_ld, int T,
+                float* out32, int ldc32, void* stream) {
+    if (!y || !w13 || !w2 || !gate || !out32 || M < 1 || H < 1 || E < 1 || band < 1 || T < 1) VB_FAIL(VB_E_INVALID, "band_ffn: null pointer or M/H/E/band/T < 1");
+    if (ldy < E * band || ldc32 < E * band || gate_ld < E * band || ldy % 8 || ldc32 % 4 || gate_ld % 4)
+        VB_FAIL(VB_E_INVALID, "band_ffn: ldy/ldc32/gate_ld must hold E*band columns (ldy %% 8, ldc32 %% 4, gate_ld %% 4 == 0)");
+    BandFfnArgs bf;
+    bf.y = (const bf16_t*)y; bf.ldy = ldy; bf.w13 = (const bf16_t*)w13; bf.w2 = (const bf16_t*)w2; bf.M = M; bf.H = H; bf.E = E;
+    bf.band = band; bf.out32 = out32; bf.ldc32 = ldc32; bf.gate = gate; bf.gate_ld = gate_ld; bf.T = T;
+    return launch_band_ffn(bf, (hipStream_t)stream);
+}
+int vb_routed_ffn_pair(const void* u, const int32_t* perm, const int32_t* group_off, const int32_t* pair_off, const int32_t* pair_pa, const void* w13,
+                       const void* w2, const float* mc, const float* ma, int N, int D, int H, int E, void* hidden, void* out, void* stream) {
+    if (!u || !perm || !group_off || !pair_off || !pair_pa || !w13 || !w2 || !mc || !ma || !hidden || !out || N < 1 || D < 1 || H < 1 || E < 1)
+        VB_FAIL(VB_E_INVALID, "routed_ffn_pair: null pointer or N/D/H/E < 1");
+    hipStream_t st = (hipStream_t)stream;
+    GemmArgs g = gemm_operands(u, (int64_t)N * D, D, w13, (int64_t)2 * E * 2 * H * D, D, 2 * N, 2 * H, D, 1);
+    g.a_rows = perm; g.b_group_stride = (int64_t)2 * H * D; g.ngroups = 2 * E; g.group_off = group_off;
+    g.epi = EPI_SWIGLU; g.out = mkp((bf16_t*)hidden, (int64_t)2 * N * H, 1); g.ldc = H;
+    g.row_scale = mc; g.row_scale2 = ma; g.scale_split = N;
+    VB_TRY(launch_gemm(g, st));
+    MoeW2PairArgs pw;
+    pw.Hs = (const bf16_t*)hidden; pw.W2 = (const bf16_t*)w2; pw.pair_off = pair_off; pw.perm = perm; pw.pair_pa = pair_pa;
+    pw.out = (bf16_t*)out; pw.N = N; pw.D = D; pw.H = H; pw.E = E;
+    return launch_moe_w2_pair(pw, st);
+}
+int vb_caption_gate(const void* x, const void* keys, const float* score_bias, const float* vw, const float* bg, const float* la, int la_rows,
+                    const float* hl, int hl_ld, const float* g1, const float* g2, const float* g3, uint64_t seed, int64_t clip_base, int nfe,
+                    int block, int Beff, int B, int T, int K, int NS, int Hh, int E, int form, float* scores, int32_t* clip_off, int32_t* ic,
+                    int32_t* ia, float* mc, float* ma, float* lc_out, int32_t* cnt, int cnt_G, int cnt_pairs, void* stream) {
+    if (!x || !keys || !score_bias || !vw || !bg || !la || !hl || !ic || !ia || !mc || !ma || Beff < 1 || B < 1 || T < 1 || K < 1 || NS < 1 ||
+        Hh < 1 || E < 1 || la_rows < 1 || hl_ld < 2)
+        VB_FAIL(VB_E_INVALID, "caption_gate: null pointer or a size < 1");
+    if ((g1 || g2 || g3) && !(g1 && g2 && g3)) VB_FAIL(VB_E_INVALID, "caption_gate: injected noise needs g1, g2 and g3");
+    if (cnt && cnt_G != (cnt_pairs ? E * E : 2 * E)) VB_FAIL(VB_E_INVALID, "caption_gate: cnt_G=%d does not match E=%d pairs=%d", cnt_G, E, cnt_pairs);
+    hipStream_t st = (hipStream_t)stream;
+    const int N = Beff * T;
+    ScoreRouterArgs sr;
+    sr.A = (const bf16_t*)x; sr.lda = K; sr.Bm = (const bf16_t*)keys; sr.ldb = K; sr.bias = score_bias; sr.K = K; sr.Beff = Beff;
+    RouterDev& r = sr.r;
+    r.Wg = vw; r.bg = bg; r.la = la; r.la_rows = la_rows; r.hl = hl; r.hl_ld = hl_ld; r.g1 = g1; r.g2 = g2; r.g3 = g3; r.T = T; r.E = E; r.B = B;
+    r.ic = ic; r.ia = ia; r.mc = mc; r.ma = ma; r.seed = seed; r.clip_base = clip_base; r.nfe_base = nfe; r.block = block; r.NS = NS; r.Hh = Hh;
+    r.cnt = cnt; r.cnt_G = cnt_G; r.cnt_pairs = cnt_pairs;
+    if (form == 1) {
+        if (!gate_route_supported(NS, K, E, Hh)) VB_FAIL(VB_E_INVALID, "caption_gate: form 1 does not support NS=%d K=%d E=%d heads=%d", NS, K, E, Hh);
+        if (lc_out) VB_FAIL(VB_E_INVALID, "caption_gate: form 1 writes no logits");
+        return launch_gate_route(sr, st);
+    }
+    if (form != 0) VB_FAIL(VB_E_INVALID, "caption_gate: form %d", form);
+    if (!scores || !clip_off) VB_FAIL(VB_E_INVALID, "caption_gate: form 0 needs the [N][NS] score scratch and the [Beff + 1] clip offsets");
+    VB_TRY(launch_iota_mul(clip_off, Beff + 1, T, st));
+    GemmArgs g = gemm_operands(x, (int64_t)N * K, K, keys, (int64_t)Beff * NS * K, K, N, NS, K, 1);
+    g.b_group_stride = (int64_t)NS * K; g.ngroups = Beff; g.group_off = clip_off; g.group_rows = T;
+    g.epi = EPI_F32; g.bias = score_bias; g.bias_group_stride = NS; g.out32 = scores; g.ldc32 = NS;
+    VB_TRY(launch_gemm(g, st));
+    r.N = N; r.D = K; r.sc = scores; r.lc_out = lc_out;
+    return launch_router(r, st);
+}
 int vb_attention(const void* q, const void* k, const void* vt, const void* ky, const void* vyt, const float* cross_w, int B, int T,
                  int Tpad, int L, int Lpad, int H, int hd, int np, void* out, void* stream) {
     return vb_attention_lens(q, k, vt, ky, vyt, cross_w, B, T, Tpad, L, Lpad, H, hd, np, nullptr, out, stream);

@@ -86,7 +86,9 @@ int launch_moe_w2_pair(const MoeW2PairArgs& a, hipStream_t st) {
     const int mt = cdiv(a.N, BM) + a.E * a.E;                    // upper bound of the row tiles over all pair groups
     ProfScope prof(0, 2.0 * a.N * a.D * 2.0 * a.H, 2.0 * a.N * a.H * 2.0 + 2.0 * a.E * a.D * a.H * 2.0 + (double)a.N * a.D * 2.0, st);
     // 128 x 192 tiles when 128 x 128 would need a second round of the 512 workgroup slots (two per CU) and 192-wide tiles do not
-    const int wide = vb_tune().w2_pair == 3 || (vb_tune().w2_pair == 1 && a.D % 192 == 0 && mt * cdiv(a.D, 128) > 512 && mt * (a.D / 192) <= 512);
+    // (192-wide tiles only where they cover D: n_tiles = D / 192 leaves the columns past the last whole tile uncomputed, so VB_W2_PAIR=3
+    //  at D % 192 != 0 falls back to the 128-wide tiles, whose last tile is ragged)
+    const int wide = a.D % 192 == 0 && (vb_tune().w2_pair == 3 || (vb_tune().w2_pair == 1 && mt * cdiv(a.D, 128) > 512 && mt * (a.D / 192) <= 512));
     if (wide) {
         d.n_tiles = a.D / 192;
         hipLaunchKernelGGL(moe_w2_pair_kernel<3>, dim3(d.n_tiles * ((mt + 7) / 8 * 8)), dim3(NTHREADS), 0, st, d);
