@@ -1,5 +1,7 @@
 // Internal launch API shared by the engines and the C-ABI wrappers.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 // ---------------------------------------------------------------------------
@@ -230,10 +232,37 @@ struct EulerStep {
     float* x = nullptr; float cfg_scale = 0.f; const float* scale_rows = nullptr; const float* dt_table = nullptr;
     const EulerKeep* keep = nullptr;
     // vb_sample_cfg_sched, beside scale_rows only: this step's guidance weight w, the row's scale becomes fmaf(w, scale_rows[b] - 1, 1).
-    // 1 = the plain rows instances; anything else takes the *_sched_kernel instances.  (A scalar scale is combined on the host: cfg_scale.)
+    // 1 = the ROWS form; anything else is the SCHED form (euler_form).  (A scalar scale is combined on the host: cfg_scale.)
     float row_weight = 1.f;
     int k = 0; int* step = nullptr; int64_t* t_idx_cur = nullptr; const int64_t* t_table = nullptr; int n_steps = 0, Beff = 0;
 };
+// The update's kernel-argument block, the same for both launches and every form: all that any form reads.  The kernels' template flags
+// <KEEP, ROWS, SCHED> select the code, so an instance reads the fields of its form only (kp: KEEP; scale_rows: ROWS, cfg_scale otherwise;
+// weight: SCHED) and the others cost kernel-argument bytes.  dt_val is the stand-alone launch's step size where dt_table is null
+// (vb_euler_cfg_step); the fields from k on are the fused launch's step advance.  Value-initialised: what the FinalLayer without an
+// update is given.
+struct EulerDev {
+    float* x; float cfg_scale; const float* dt_table; int k; int* step; int64_t* t_idx_cur; const int64_t* t_table; int n_steps, Beff;
+    EulerKeep kp; const float* scale_rows; float weight, dt_val;
+};
+inline EulerDev euler_dev(const EulerStep& es, float dt_val = 0.f) {
+    return {es.x, es.cfg_scale, es.dt_table, es.k, es.step, es.t_idx_cur, es.t_table, es.n_steps, es.Beff,
+            es.keep ? *es.keep : EulerKeep{}, es.scale_rows, es.row_weight, dt_val};
+}
+// The form of one update, decided once for both launches: KEEP with a known region, ROWS with per-row scales, SCHED when those scales
+// stand under a step weight other than 1 - and there is an unconditional half to guide against (the fused launch always has one).
+struct EulerForm { bool keep, rows, sched; };
+inline EulerForm euler_form(const EulerStep& es, bool has_uncond) {
+    const bool rows = es.scale_rows != nullptr;
+    return {es.keep != nullptr, rows, rows && has_uncond && es.row_weight != 1.f};
+}
+// go(KEEP, ROWS, SCHED) with the form as std::bool_constants: the six legal forms (SCHED implies ROWS), each one kernel instance
+template <class Go>
+void euler_dispatch(EulerForm f, Go&& go) {
+    const std::true_type yes; const std::false_type no;
+    if (f.keep) { if (f.sched) go(yes, yes, yes); else if (f.rows) go(yes, yes, no); else go(yes, no, no); }
+    else { if (f.sched) go(no, yes, yes); else if (f.rows) go(no, yes, no); else go(no, no, no); }
+}
 // FinalLayer + the update + the step advance as one launch (rows = 2 x (B T) token rows, conditional half first; reads es.k, not *es.step)
 int launch_final_layer_euler(const float* h, const float* shift, const float* scale, int mod_ld, const float* W, const float* bias,
                              int rows, int D, int T, int C, float eps, const EulerStep& es, hipStream_t st);

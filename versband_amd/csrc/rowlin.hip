@@ -146,29 +146,18 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
 // both branches' velocities of its tokens and updates x [B][C][T] in place through common.h:euler_cfg_update, the two fused
 // multiply-adds of the stand-alone update (sampler_step.hip); the velocity tensor is never written.  Block 0 also advances the sampler's device-side step counter and the timestep
 // indices for the NEXT step (step_advance_kernel's work): nothing in this launch reads them.  Saves two launches per Euler step.
-struct FinalEuler { float* x; float cfg_scale; const float* dt_table; int k; int* step; int64_t* t_idx_cur; const int64_t* t_table; int n_steps, Beff; };
+// The forms of the update are template flags over ONE argument block (kernels.h: EulerDev), of which an instance reads its form's fields:
 // KEEP (vb_sample_cfg_keep): the updated value is blended with the known region's point on the probability path at t = tn_table[k]
-// (common.h:keep_path / keep_blend; three more loads per output element) - a third instance with its own argument block, so the other
-// two keep their kernel arguments and compile to the code they had.
-struct FinalEulerKeep : FinalEuler { EulerKeep kp; };
+// (common.h:keep_path / keep_blend; three more loads per output element).
 // ROWS (vb_sample_cfg_rows): one guidance scale per clip, scale_rows[b] read per TOKEN - a wave's two tokens belong to different clips
-// when T is odd; one more 4-byte load per output row.  Two more instances (plain / keep) with their own argument blocks: the three above
-// keep their kernel arguments and compile to the code they had.
-struct FinalEulerRows : FinalEuler { const float* scale_rows; };
-struct FinalEulerKeepRows : FinalEulerKeep { const float* scale_rows; };
+// when T is odd; one more 4-byte load per output row.
 // SCHED (vb_sample_cfg_sched, per-row scales under a step weight that is neither 0 nor 1): the token's scale becomes
-// fmaf(weight, scale_rows[b] - 1, 1), one more fused multiply-add per output row.  Two more instances (plain / keep) with their own
-// argument blocks: the five forms above keep their kernel arguments and compile to the code they had.
-struct FinalEulerRowsSched : FinalEulerRows { float weight; };
-struct FinalEulerKeepRowsSched : FinalEulerKeepRows { float weight; };
-template <bool KEEP, bool ROWS, bool SCHED = false>
-using FinalEulerArgs = std::conditional_t<SCHED, std::conditional_t<KEEP, FinalEulerKeepRowsSched, FinalEulerRowsSched>,
-                                          std::conditional_t<ROWS, std::conditional_t<KEEP, FinalEulerKeepRows, FinalEulerRows>, std::conditional_t<KEEP, FinalEulerKeep, FinalEuler>>>;
+// fmaf(weight, scale_rows[b] - 1, 1), one more fused multiply-add per output row.
 template <int NQ, bool EUL = false, bool KEEP = false, bool ROWS = false, bool SCHED = false>      // D = 256 * NQ
 __global__ void __launch_bounds__(256) final_layer_kernel(const float* __restrict__ h, const float* __restrict__ shift,
                                                          const float* __restrict__ scale, int mod_ld, const float* __restrict__ W,
                                                          const float* __restrict__ bias, int rows, int T, int C, float eps, float* out,
-                                                         const FinalEulerArgs<KEEP, ROWS, SCHED> fe) {
+                                                         const EulerDev fe) {
     static_assert(EUL || !KEEP, "the known-region blend belongs to the Euler update");
     static_assert(EUL || !ROWS, "the guidance scales belong to the Euler update");
     static_assert(ROWS || !SCHED, "the step weight belongs to the per-row scales (a scalar scale is combined on the host)");
@@ -275,62 +264,42 @@ __global__ void __launch_bounds__(256) final_layer_kernel(const float* __restric
     }
 }
 bool final_layer_fused_ok(int D, int C) { return (D == 256 || D == 512 || D == 768 || D == 1024) && C <= 64 && (size_t)C * D * 4 <= 96 * 1024; }
+// go(NQ) with NQ = D / 256 as a std::integral_constant (final_layer_fused_ok: D is 256, 512, 768 or 1024)
+template <class Go>
+static void final_layer_nq(int D, Go&& go) {
+    if (D == 256) go(std::integral_constant<int, 1>()); else if (D == 512) go(std::integral_constant<int, 2>());
+    else if (D == 768) go(std::integral_constant<int, 3>()); else go(std::integral_constant<int, 4>());
+}
 int launch_final_layer_fused(const float* h, const float* shift, const float* scale, int mod_ld, const float* W, const float* bias,
                              int rows, int D, int T, int C, float eps, float* out, hipStream_t st) {
     if (!final_layer_fused_ok(D, C)) VB_FAIL(VB_E_INVALID, "final_layer_fused: D=%d C=%d unsupported", D, C);
     const size_t sh = (size_t)C * D * sizeof(float);
     const int grid = min(cdiv(rows, 16), 512);
-    static OnceFlags attr[4];
-    auto go = [&](auto nq) {
+    final_layer_nq(D, [&](auto nq) {
         constexpr int NQ = decltype(nq)::value;
-        vb_set_max_lds_once(attr[NQ - 1], reinterpret_cast<const void*>(final_layer_kernel<NQ>), 96 * 1024);
-        hipLaunchKernelGGL(final_layer_kernel<NQ>, dim3(grid), dim3(256), sh, st, h, shift, scale, mod_ld, W, bias, rows, T > 0 ? T : 1, C, eps, out, FinalEuler{});
-    };
-    if (D == 256) go(std::integral_constant<int, 1>()); else if (D == 512) go(std::integral_constant<int, 2>());
-    else if (D == 768) go(std::integral_constant<int, 3>()); else go(std::integral_constant<int, 4>());
+        static OnceFlags attr;      // (one per instance: the lambda's body is instantiated per NQ)
+        vb_set_max_lds_once(attr, reinterpret_cast<const void*>(final_layer_kernel<NQ>), 96 * 1024);
+        hipLaunchKernelGGL(final_layer_kernel<NQ>, dim3(grid), dim3(256), sh, st, h, shift, scale, mod_ld, W, bias, rows, T > 0 ? T : 1, C, eps, out, EulerDev{});
+    });
     VB_CHECK_LAUNCH();
     return VB_OK;
 }
-// FinalLayer + CFG + Euler update + step advance in one launch (see FinalEuler): rows = 2 x (B T) token rows, conditional half first
+// FinalLayer + CFG + Euler update + step advance in one launch (see EUL above): rows = 2 x (B T) token rows, conditional half first
 int launch_final_layer_euler(const float* h, const float* shift, const float* scale, int mod_ld, const float* W, const float* bias,
                              int rows, int D, int T, int C, float eps, const EulerStep& es, hipStream_t st) {
     if (!final_layer_fused_ok(D, C) || (rows & 1) || !es.x || !es.dt_table) VB_FAIL(VB_E_INVALID, "final_layer_euler: D=%d C=%d rows=%d unsupported", D, C, rows);
     const size_t sh = (size_t)C * D * sizeof(float);
     const int grid = min(cdiv(rows / 2, 8), 512);
-    const FinalEuler base{es.x, es.cfg_scale, es.dt_table, es.k, es.step, es.t_idx_cur, es.t_table, es.n_steps, es.Beff};
-    // one instance (NQ, KEEP, ROWS): its own argument block, its LDS attribute set once, its launch
-    auto go = [&](auto nq, auto keep, auto by_rows) {
-        constexpr int NQ = decltype(nq)::value;
-        constexpr bool KEEP = decltype(keep)::value, ROWS = decltype(by_rows)::value;
-        FinalEulerArgs<KEEP, ROWS> fe;
-        static_cast<FinalEuler&>(fe) = base;
-        if constexpr (KEEP) fe.kp = *es.keep;
-        if constexpr (ROWS) fe.scale_rows = es.scale_rows;
-        static OnceFlags attr;
-        vb_set_max_lds_once(attr, reinterpret_cast<const void*>(final_layer_kernel<NQ, true, KEEP, ROWS>), 96 * 1024);
-        hipLaunchKernelGGL((final_layer_kernel<NQ, true, KEEP, ROWS>), dim3(grid), dim3(256), sh, st, h, shift, scale, mod_ld, W, bias, rows, T > 0 ? T : 1, C,
-                           eps, (float*)nullptr, fe);
-    };
-    // per-row scales under a step weight (EulerStep::row_weight != 1): the SCHED instances
-    auto go_sched = [&](auto nq, auto keep) {
-        constexpr int NQ = decltype(nq)::value;
-        constexpr bool KEEP = decltype(keep)::value;
-        FinalEulerArgs<KEEP, true, true> fe;
-        static_cast<FinalEuler&>(fe) = base;
-        if constexpr (KEEP) fe.kp = *es.keep;
-        fe.scale_rows = es.scale_rows; fe.weight = es.row_weight;
-        static OnceFlags attr;
-        vb_set_max_lds_once(attr, reinterpret_cast<const void*>(final_layer_kernel<NQ, true, KEEP, true, true>), 96 * 1024);
-        hipLaunchKernelGGL((final_layer_kernel<NQ, true, KEEP, true, true>), dim3(grid), dim3(256), sh, st, h, shift, scale, mod_ld, W, bias, rows, T > 0 ? T : 1, C,
-                           eps, (float*)nullptr, fe);
-    };
-    const std::true_type yes; const std::false_type no;
-    auto form = [&](auto nq) {
-        if (es.scale_rows && es.row_weight != 1.f) { if (es.keep) go_sched(nq, yes); else go_sched(nq, no); }
-        else if (es.keep && es.scale_rows) go(nq, yes, yes); else if (es.scale_rows) go(nq, no, yes); else if (es.keep) go(nq, yes, no); else go(nq, no, no);
-    };
-    if (D == 256) form(std::integral_constant<int, 1>()); else if (D == 512) form(std::integral_constant<int, 2>());
-    else if (D == 768) form(std::integral_constant<int, 3>()); else form(std::integral_constant<int, 4>());
+    const EulerDev fe = euler_dev(es);
+    // one instance (NQ, KEEP, ROWS, SCHED): its LDS attribute set once, its launch
+    final_layer_nq(D, [&](auto nq) {
+        euler_dispatch(euler_form(es, true), [&](auto keep, auto by_rows, auto sched) {
+            constexpr auto kernel = final_layer_kernel<decltype(nq)::value, true, decltype(keep)::value, decltype(by_rows)::value, decltype(sched)::value>;
+            static OnceFlags attr;
+            vb_set_max_lds_once(attr, reinterpret_cast<const void*>(kernel), 96 * 1024);
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), sh, st, h, shift, scale, mod_ld, W, bias, rows, T > 0 ? T : 1, C, eps, (float*)nullptr, fe);
+        });
+    });
     VB_CHECK_LAUNCH();
     return VB_OK;
 }

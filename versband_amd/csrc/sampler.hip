@@ -8,7 +8,7 @@
 //   0: a single-branch step - the network runs over the conditional rows alone (DitEval::nb_active = 1), FinalLayer writes their velocity
 //      and the update is the separate launch without an unconditional half, as in an nb == 1 call;
 //   else: both branches under the step's effective scale fmaf(gw[k], s - 1, 1): a scalar s is combined here and handed to the existing
-//      instances, per-row scales take the *_sched_kernel instances with gw[k] in their arguments.
+//      instances, per-row scales take the SCHED instances of the update (kernels.h: euler_form) with gw[k] in their arguments.
 // The kinds are baked into a captured graph (its key holds the weights).  Keep blend, window consensus and trajectory copy do not
 // depend on the kind.
 static EulerKeep euler_keep(const vb_keep& k, const WsL& s) { return EulerKeep{k.ref, k.x0, k.mask, s.tn_table, k.sigma_min}; }

@@ -10,63 +10,42 @@
 // ---------------------------------------------------------------------------
 // CFG + Euler:  x[b] += dt * (v_u + s*(v_c - v_u))     (cfm1_audio.py:160 + fixed-step Euler)
 // v holds the cond rows [0,B) then the uncond rows [B,2B); the arithmetic is common.h:euler_cfg_update, as in the fused launch.
+// One kernel over one argument block (kernels.h: EulerDev; this launch reads the device's *step, not the host's k), its forms as flags:
 // dt = dt_table[*step], or dt_val when there is no table (vb_euler_cfg_step).
 // KEEP (vb_sample_cfg_keep): the blend with the known region at t = tn_table[*step]; mask, ref and x0 are read in these instances only.
 // ROWS (vb_sample_cfg_rows): clip b = i / per takes scale_rows[b] instead of cfg_scale.
+// SCHED (vb_sample_cfg_sched, per-row scales under a step weight that is neither 0 nor 1): s = fmaf(weight, scale_rows[b] - 1, 1).
 // ---------------------------------------------------------------------------
-// SCHED (vb_sample_cfg_sched, per-row scales under a step weight that is neither 0 nor 1): s = fmaf(weight, scale_rows[b] - 1, 1); a kernel
-// of its own (euler_cfg_sched_kernel) with the weight as one more argument, so the four instances of euler_cfg_kernel keep theirs.
 template <bool KEEP, bool ROWS, bool SCHED>
-__device__ __forceinline__ void euler_cfg_body(float* x, const float* __restrict__ v, int64_t n, int64_t per, int T, float cfg_scale,
-                                               const float* __restrict__ scale_rows, const float* dt_table, const int* step, float dt_val,
-                                               int has_uncond, const EulerKeep& kp, float weight) {
-    const int k = step ? *step : 0;
-    const float dt = dt_table ? dt_table[k] : dt_val;
+__global__ void euler_cfg_kernel(const float* __restrict__ v, int64_t n, int64_t per, int T, int has_uncond, const EulerDev ed) {
+    static_assert(ROWS || !SCHED, "the step weight belongs to the per-row scales (a scalar scale is combined on the host)");
+    const int k = ed.step ? *ed.step : 0;
+    const float dt = ed.dt_table ? ed.dt_table[k] : ed.dt_val;
     KeepAt ka{};
-    if constexpr (KEEP) ka.tn = kp.tn_table[k];
+    if constexpr (KEEP) ka.tn = ed.kp.tn_table[k];
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int64_t b = (KEEP || ROWS) ? i / per : 0;
     const float vc = v[i];
-    float vu = 0.f, s = cfg_scale;
+    float vu = 0.f, s = ed.cfg_scale;
     if (has_uncond) {
         vu = v[n + i];
-        if constexpr (ROWS) s = scale_rows[b];
-        if constexpr (SCHED) s = fmaf(weight, s - 1.f, 1.f);
+        if constexpr (ROWS) s = ed.scale_rows[b];
+        if constexpr (SCHED) s = fmaf(ed.weight, s - 1.f, 1.f);
     }
     if constexpr (KEEP) {
-        ka.m = kp.mask[b * T + (i - b * per) % T];
-        ka.sigma_min = kp.sigma_min; ka.ref = kp.ref[i]; ka.x0 = kp.x0[i];
+        ka.m = ed.kp.mask[b * T + (i - b * per) % T];
+        ka.sigma_min = ed.kp.sigma_min; ka.ref = ed.kp.ref[i]; ka.x0 = ed.kp.x0[i];
     }
-    x[i] = euler_cfg_update<KEEP>(x[i], vc, vu, has_uncond != 0, s, dt, ka);
-}
-template <bool KEEP, bool ROWS>
-__global__ void euler_cfg_kernel(float* x, const float* __restrict__ v, int64_t n, int64_t per, int T, float cfg_scale,
-                                 const float* __restrict__ scale_rows, const float* dt_table, const int* step, float dt_val,
-                                 int has_uncond, const EulerKeep kp) {
-    euler_cfg_body<KEEP, ROWS, false>(x, v, n, per, T, cfg_scale, scale_rows, dt_table, step, dt_val, has_uncond, kp, 1.f);
-}
-template <bool KEEP>
-__global__ void euler_cfg_sched_kernel(float* x, const float* __restrict__ v, int64_t n, int64_t per, int T,
-                                       const float* __restrict__ scale_rows, const float* dt_table, const int* step, float dt_val,
-                                       int has_uncond, const EulerKeep kp, float weight) {
-    euler_cfg_body<KEEP, true, true>(x, v, n, per, T, 0.f, scale_rows, dt_table, step, dt_val, has_uncond, kp, weight);
+    ed.x[i] = euler_cfg_update<KEEP>(ed.x[i], vc, vu, has_uncond != 0, s, dt, ka);
 }
 int launch_euler_cfg(const EulerStep& es, const float* v, int B, int64_t per, int T, int has_uncond, float dt_val, hipStream_t st) {
     if (es.keep && (!es.dt_table || !es.step || T < 1)) VB_FAIL(VB_E_INVALID, "euler_cfg: a known region needs the step tables and T");
     const int64_t n = (int64_t)B * per;
-    auto go = [&](auto keep, auto rows) {
-        hipLaunchKernelGGL((euler_cfg_kernel<decltype(keep)::value, decltype(rows)::value>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                           es.x, v, n, per, T, es.cfg_scale, es.scale_rows, es.dt_table, (const int*)es.step, dt_val, has_uncond,
-                           es.keep ? *es.keep : EulerKeep{});
-    };
-    auto go_sched = [&](auto keep) {
-        hipLaunchKernelGGL((euler_cfg_sched_kernel<decltype(keep)::value>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, es.x, v, n, per, T,
-                           es.scale_rows, es.dt_table, (const int*)es.step, dt_val, has_uncond, es.keep ? *es.keep : EulerKeep{}, es.row_weight);
-    };
-    const std::true_type yes; const std::false_type no;
-    if (es.scale_rows && has_uncond && es.row_weight != 1.f) { if (es.keep) go_sched(yes); else go_sched(no); }
-    else if (es.keep && es.scale_rows) go(yes, yes); else if (es.keep) go(yes, no); else if (es.scale_rows) go(no, yes); else go(no, no);
+    euler_dispatch(euler_form(es, has_uncond != 0), [&](auto keep, auto rows, auto sched) {
+        hipLaunchKernelGGL((euler_cfg_kernel<decltype(keep)::value, decltype(rows)::value, decltype(sched)::value>), dim3((unsigned)((n + 255) / 256)),
+                           dim3(256), 0, st, v, n, per, T, has_uncond, euler_dev(es, dt_val));
+    });
     VB_CHECK_LAUNCH();
     return VB_OK;
 }

@@ -66,6 +66,36 @@ def _device_tables(tables: dict, key: tuple, make) -> tuple:
     return tables[key]
 
 
+_KINDS = {"integers": (int, np.integer), "numbers": (int, float, np.integer, np.floating)}
+
+
+def _checked_list(name: str, v, kind: Optional[str], count: Optional[Tuple[int, str]], what: str, gloss: str = "",
+                  count_first: bool = False) -> list:
+    """one of the sampler options' sequences - a tensor or any iterable - as a checked Python list.  kind: "integers" / "numbers" (a bool
+    is neither; None: the elements are the caller's to convert); count: (n, noun) - n entries, one per "rows" / "steps" (None: any
+    number); what / gloss: the caller's wording of the two TypeErrors, "{name} must be {what}, got ..." and "{name} must hold
+    {kind}{gloss}".  A wrong element is reported before a wrong count, or after it (count_first)."""
+    if torch.is_tensor(v):
+        v = v.tolist()
+    try:
+        vals = list(v)
+    except TypeError:
+        raise TypeError(f"{name} must be {what}, got {type(v).__name__}") from None
+    bad_count = count is not None and len(vals) != count[0]
+    bad_kind = kind is not None and any(isinstance(s, bool) or not isinstance(s, _KINDS[kind]) for s in vals)
+    if bad_kind and not (count_first and bad_count):
+        raise TypeError(f"{name} must hold {kind}{gloss}")
+    if bad_count:
+        raise ValueError(f"{name} has {len(vals)} entries for {count[0]} {count[1]}")
+    return vals
+
+
+def _check_device(name: str, t: Tensor, dev):
+    """a tensor handed to the engine lives on the host (it is then copied) or on the engine's device"""
+    if t.device.type != "cpu" and t.device != dev:
+        raise ValueError(f"{name} lives on {t.device}, the engine on {dev}")
+
+
 class DiTEngine:
     """TxtFlagLargeImprovedDiTV2 (vocal2music_moe.py:477-520) + CFMSampler hot loop on the GPU.
 
@@ -230,13 +260,10 @@ class DiTEngine:
                 raise ValueError(f"keep: {name} has shape {tuple(t.shape)}, expected {want}")
             if t.dtype != torch.float32:
                 raise TypeError(f"keep: {name} must be float32, got {t.dtype}")
-            if t.device.type != "cpu" and t.device != dev:
-                raise ValueError(f"keep: {name} lives on {t.device}, the engine on {dev}")
+            _check_device(f"keep: {name}", t, dev)
         if mask.numel() and (float(mask.min()) < 0.0 or float(mask.max()) > 1.0 or bool(torch.isnan(mask).any())):
             raise ValueError("keep: mask values must lie in [0, 1]")
-        t_next = [float(v) for v in (t_next.tolist() if torch.is_tensor(t_next) else t_next)]
-        if len(t_next) != n:
-            raise ValueError(f"keep: t_next has {len(t_next)} entries for {n} steps")
+        t_next = [float(v) for v in _checked_list("keep: t_next", t_next, None, (n, "steps"), f"a sequence of {n} times")]
         ref, x0k, mask = [t.to(dev).contiguous() for t in (ref, x0k, mask)]
         tn, = _device_tables(self._tables, ("t_next", tuple(t_next)), lambda: (torch.tensor(t_next, dtype=torch.float32, device=dev),))
         ks = L.Keep(ref.data_ptr(), x0k.data_ptr(), mask.data_ptr(), tn.data_ptr(), float(sigma_min))
@@ -257,8 +284,7 @@ class DiTEngine:
                     raise TypeError(f"{name} must be {str(dtype).replace('torch.', '')}, got {str(v.dtype).replace('torch.', '')}")
                 if v.dim() != 1 or v.numel() != B:
                     raise ValueError(f"{name} has shape {tuple(v.shape)}, expected ({B},)")
-                if v.device.type != "cpu" and v.device != dev:
-                    raise ValueError(f"{name} lives on {v.device}, the engine on {dev}")
+                _check_device(name, v, dev)
                 if v.device == dev and v.is_contiguous():       # (not read here: no device-to-host sync on the replay path)
                     held.append(v)
                     return v
@@ -266,22 +292,14 @@ class DiTEngine:
                     raise ValueError(f"{name} must be finite")
                 vals = v
             else:
-                try:
-                    vals = list(v)
-                except TypeError:
-                    what = "a number, a sequence or a float32 tensor" if kind == "scale" else "a sequence or an int64 tensor"
-                    raise TypeError(f"{name} must be {what} of {B} values, got {type(v).__name__}") from None
-                if len(vals) != B:
-                    raise ValueError(f"{name} has {len(vals)} entries for {B} rows")
+                what = "a number, a sequence or a float32 tensor" if kind == "scale" else "a sequence or an int64 tensor"
+                vals = _checked_list(name, v, "numbers" if kind == "scale" else "integers", (B, "rows"), f"{what} of {B} values",
+                                     count_first=True)
                 if kind == "scale":
-                    if any(isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)) for s in vals):
-                        raise TypeError(f"{name} must hold numbers")
                     if not all(np.isfinite(float(s)) for s in vals):
                         raise ValueError(f"{name} must be finite")
                     vals = torch.tensor([float(s) for s in vals], dtype=torch.float32)
                 else:
-                    if any(isinstance(s, bool) or not isinstance(s, (int, np.integer)) for s in vals):
-                        raise TypeError(f"{name} must hold integers")
                     vals = torch.tensor([int(s) for s in vals], dtype=torch.int64)
             key = (B, kind)
             if key not in self._rowbuf:
@@ -306,15 +324,7 @@ class DiTEngine:
         """validate the window starts of a joint call - B rows = nw windows (row = w * Bc + b) of T tokens each - and lay them out as
         vb_windows (a host array, read during the call).  The rules are the library's (include/versband_hip.h), stated here first so that
         the error names the caller's argument.  Returns (struct, the array to hold)."""
-        if torch.is_tensor(windows):
-            windows = windows.tolist()
-        try:
-            starts = list(windows)
-        except TypeError:
-            raise TypeError(f"windows must be a sequence of window starts, got {type(windows).__name__}") from None
-        if any(isinstance(s, bool) or not isinstance(s, (int, np.integer)) for s in starts):
-            raise TypeError("windows must hold integers (the window starts)")
-        starts = [int(s) for s in starts]
+        starts = [int(s) for s in _checked_list("windows", windows, "integers", None, "a sequence of window starts", " (the window starts)")]
         nw = len(starts)
         if not 1 <= nw <= 64:
             raise ValueError(f"windows: {nw} windows (1..64)")
@@ -341,19 +351,10 @@ class DiTEngine:
         lengths.  Returns (struct or None, the array to hold, the lengths as a tuple or None)."""
         lens = None
         if lengths is not None:
-            if torch.is_tensor(lengths):
-                lengths = lengths.tolist()
-            try:
-                vals = list(lengths)
-            except TypeError:
-                raise TypeError(f"lengths must be a sequence of {B} row lengths, got {type(lengths).__name__}") from None
-            if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in vals):
-                raise TypeError("lengths must hold integers (latent tokens per row)")
-            if len(vals) != B:
-                raise ValueError(f"lengths has {len(vals)} entries for {B} rows")
+            vals = [int(v) for v in _checked_list("lengths", lengths, "integers", (B, "rows"), f"a sequence of {B} row lengths",
+                                                  " (latent tokens per row)")]
             if B > 64:
                 raise ValueError(f"lengths: {B} rows (at most 64)")
-            vals = [int(v) for v in vals]
             for b, v in enumerate(vals):
                 if not 1 <= v <= T:
                     raise ValueError(f"lengths[{b}] = {v} is not in [1, T = {T}]")
@@ -375,17 +376,8 @@ class DiTEngine:
         """validate per-step guidance weights - n finite numbers in [0, 16], the library's rules (include/versband_hip.h), stated here
         first so that the error names the caller's argument - and lay them out as vb_guidance (a host array, read during the call).
         All ones is the plain call.  Returns (struct or None, the array to hold)."""
-        if torch.is_tensor(guidance):
-            guidance = guidance.tolist()
-        try:
-            vals = list(guidance)
-        except TypeError:
-            raise TypeError(f"guidance must be a sequence of {n} step weights, got {type(guidance).__name__}") from None
-        if any(isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) for v in vals):
-            raise TypeError("guidance must hold numbers (one weight per step)")
-        if len(vals) != n:
-            raise ValueError(f"guidance has {len(vals)} entries for {n} steps")
-        vals = [float(np.float32(v)) for v in vals]
+        vals = [float(np.float32(v)) for v in _checked_list("guidance", guidance, "numbers", (n, "steps"), f"a sequence of {n} step weights",
+                                                            " (one weight per step)")]
         for k, v in enumerate(vals):
             if not (np.isfinite(v) and 0.0 <= v <= 16.0):
                 raise ValueError(f"guidance[{k}] = {v} is not a finite value in [0, 16]")
