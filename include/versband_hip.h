@@ -288,7 +288,8 @@ int vb_sample_cfg_sched(vb_ctx* ctx, float* x, const void* cond, int B, int n_br
  * keep, rows and guidance compose unchanged (all are token-local); single-branch steps read the same table.  The lengths reach the
  * device through a launch argument at the head of the step loop, which a captured graph holds: the graph key holds the VALUES of len,
  * so another set of lengths on the same buffers captures its own graph and a plain call never replays a lengths graph.  Hosts detect
- * the feature by the presence of these symbols (vb_abi_version() stays 3).  The VAE and vocoder entry points take equal-length rows only. */
+ * the feature by the presence of these symbols (vb_abi_version() stays 3).  The VAE entry points, BigVGAN and the chunked vocoder take equal-length rows only; the HiFi-GAN
+ * takes row lengths through vb_hifigan_forward_lens (below). */
 typedef struct { const int32_t* len; } vb_lens;                   /* len: HOST array of B row lengths, 1 <= len[b] <= T */
 int vb_dit_precompute_cond_lens(vb_ctx* ctx, const float* t5, const int64_t* midi, const int64_t* beats, int B, int n_branch, int T,
                                 int T_mel, int L, const vb_lens* lens, void* cond, void* ws, void* stream);
@@ -391,6 +392,32 @@ int vb_vae_decode(vb_ctx* ctx, const float* z, int B, int T, float* mel, void* w
 int vb_vae_encode(vb_ctx* ctx, const float* mel, int B, int T, float* moments, void* ws, void* stream);
 /* HifiGAN.spec2wav (vocoder/hifigan/hifigan.py:20-30): mel [B][80][T] -> wav [B][T*hop] */
 int vb_hifigan_forward(vb_ctx* ctx, const float* mel, int B, int T, float* wav, void* ws, void* stream);
+/* HiFi-GAN with ROW LENGTHS (build-defined): mels of different lengths as rows of one call.  mel [B][in_ch][T], T the padded length;
+ * lens->len the HOST array of B mel-frame lengths, 1 <= len[b] <= T, checked like the sampler's (B <= 64; VB_E_INVALID names the row,
+ * nothing is launched and wav is unchanged).  wav [B][out_ch][T*hop]: row b holds len[b]*hop samples followed by exact zeros.  The
+ * caller's mel padding, samples [len[b], T) of a row, is never read into a valid sample; it may hold NaN.
+ * lens == NULL, len == NULL or every row full is vb_hifigan_forward on the same buffers: same launches, same bits.
+ * How it works.  Every input activation of the generator is a LeakyReLU or none (f(0) = 0), every convolution zero-pads, and every op
+ * computes a clip from that clip alone.  So when row b's tail is zero in every activation buffer a convolution reads, its valid samples get
+ * exactly the operands the zero fill of the clip-alone call supplies: the mel is copied into the workspace with its tails zeroed, and after
+ * every op that writes an activation buffer (the output included) one small launch zeroes out[b, :, len[b]*tmul : T*tmul] - its grid covers
+ * the tails only.  The fused ResBlock1 pairs keep their intermediate in LDS and pad the ACTIVATED intermediate with zeros outside [0, T):
+ * with lengths that bound is the row's own length (a device table of the lengths in the workspace), at that one place of each kernel.
+ * THE ROUTE RULE.  Kernel routes depend on a stage's length T*tmul only through (T*tmul) % 4 - minimal-filtering eligibility, staged
+ * (16-byte) epilogues, quad window rows, the fp32 pairs - and through 16-byte alignment of the row bases, which follows from it.  (T and B
+ * also enter the TILE choice of the conv and GEMM kernels; every tile of a kernel accumulates in the same order, so tiles never change a
+ * bit.)  This call picks routes from the padded T, the call on the clip alone from len[b].  Hence:
+ *   len[b] == T (mod 4)   row b's first len[b]*hop samples equal vb_hifigan_forward on that clip alone BIT FOR BIT;
+ *   otherwise             the two agree to fp32 roundoff (an op may run the direct kernel in one call and the F(2,3) kernel in the other).
+ * A host that wants bit-exact rows groups its clips by length mod 4 (harness.plan_vocoder_calls).
+ * Refused with VB_E_INVALID before anything is launched, naming the op and why: a vocoder program with an op other than VB_OP_CONV /
+ * VB_OP_RESPAIR / VB_OP_XT_PLANES (BigVGAN's VB_OP_AA_ACT: its anti-aliasing filters replicate-pad at the row end), an input activation
+ * other than none / LeakyReLU, GroupNorm statistics, dynamic channel counts, w_buf weights, a transposed output.  The VAE nets and
+ * vb_hifigan_forward_chunked take no lengths.
+ * ws: vb_hifigan_lens_workspace_bytes(ctx, B, T) bytes = vb_net_workspace_bytes + the masked mel + the length table.  Hosts detect the
+ * feature by the presence of these symbols (vb_abi_version() stays 3). */
+size_t vb_hifigan_lens_workspace_bytes(vb_ctx* ctx, int B, int T);
+int vb_hifigan_forward_lens(vb_ctx* ctx, const float* mel, int B, int T, const vb_lens* lens, float* wav, void* ws, void* stream);
 
 /* Long-form generation (BASELINE configs[4]; build-defined, the reference stops at max_len = 1500 latent tokens: vocal2music_moe.py:421).
  * vb_crossfade_windows: window results parts [nw*B][C][n] (row = w*B + b; windows of equal length n starting at starts[w], a HOST array,

@@ -9,8 +9,9 @@ group is formed, so memory does not grow with the manifest and a crash loses one
 calls of test_final.py's loop, one per (item, scale).  `--synthetic_frames` additionally accepts a comma list that cycles over the
 synthetic items; every other flag is test_final.py's and is parsed by its parser.  `--length_slack N` lets consecutive items whose latent
 lengths differ by at most N tokens share a call too: the group is padded to its longest member and sampled with per-row lengths
-(vb_sample_cfg_lens - a row is the call on that clip alone), then every row is cut to its own length and rows of equal length are
-decoded and vocoded together.
+(vb_sample_cfg_lens - a row is the call on that clip alone), then every row is cut to its own length, rows of equal length are
+decoded together, and the decoded mels are vocoded with per-row lengths (vb_hifigan_forward_lens) in one call per residue of the mel
+length mod 4 - two at most - where a row again is the call on that clip alone.
 """
 from __future__ import annotations
 
@@ -30,7 +31,7 @@ for p in (ROOT, HERE):
 import test_final as loop  # noqa: E402
 from versband_amd import dist as vdist  # noqa: E402
 from versband_amd.harness import (MEL_DOWNSAMPLE, InferDataset, check_items_per_batch, parse_frames,  # noqa: E402
-                                  plan_row_batches, save_rows_to_tsv, stream_length_groups, write_wav_pcm16)
+                                  plan_row_batches, plan_vocoder_calls, save_rows_to_tsv, stream_length_groups, write_wav_pcm16)
 from versband_amd.model import normalize_loudness  # noqa: E402
 
 
@@ -131,7 +132,7 @@ def _cat_conditioning(parts, frames=None):
 
 def sample_group(args, sampler, vocoder, group, scales, device):
     """the sampler calls of harness.plan_row_batches for ONE group of items (of equal length, or within --length_slack of each other:
-    the call then carries the row lengths and its rows are cut to them before decoding): group = [(global index, item)].  A row is what
+    the call then carries the row lengths, its rows are cut to them before decoding, and the vocoder call carries them again): group = [(global index, item)].  A row is what
     test_final.py computes for (item, scale, sample): the item's conditioning and start noise (the same for every scale of an item), its
     own guidance scale and its global clip index gi * n_samples + k as noise key - so the rows, and after the batched decode and vocoder
     the files, equal the loop's.  Returns {(position in the group, scale): [(mel [80,T], wav numpy)] per sample}."""
@@ -157,13 +158,25 @@ def sample_group(args, sampler, vocoder, group, scales, device):
         z, _ = sampler.sample_cfg(cond=c, unconditional_guidance_scale=scale, unconditional_conditioning=uc, batch_size=len(rows),
                                   shape=[embed_dim, call["length"]], x_latent=x, timesteps=args.ddim_steps + 1, seed=args.seed,
                                   clip_ids=call["clip_ids"], **gk, **({"lengths": row_lengths} if row_lengths else {}))
-        # the VAE and the vocoder take rows of one length: rows of equal length go through them together
         done = {}
-        for length in dict.fromkeys(row_lengths or [call["length"]]):
-            idx = [r for r in range(len(rows)) if not row_lengths or row_lengths[r] == length]
-            mel = sampler.model.decode_first_stage(z[idx][:, :, :length].contiguous() if row_lengths else z)
+        if not row_lengths:
+            mel = sampler.model.decode_first_stage(z)
             wav = vocoder.spec2wav_batch(mel).cpu().numpy()
-            done.update({r: (mel[j], wav[j]) for j, r in enumerate(idx)})
+            done.update({r: (mel[r], wav[r]) for r in range(len(rows))})
+        else:
+            # the VAE takes rows of one length: rows of equal length are decoded together.  The vocoder takes row lengths: the decoded
+            # mels are padded to the longest of their group (harness.plan_vocoder_calls: lengths that agree mod 4, where a row equals
+            # the call on that clip alone bit for bit), vocoded in one call and cut to their own lengths
+            mels = {}
+            for length in dict.fromkeys(row_lengths):
+                idx = [r for r in range(len(rows)) if row_lengths[r] == length]
+                mel = sampler.model.decode_first_stage(z[idx][:, :, :length].contiguous())
+                mels.update({r: mel[j] for j, r in enumerate(idx)})
+            for vc in plan_vocoder_calls([mels[r].shape[-1] for r in range(len(rows))]):
+                batch = torch.stack([torch.nn.functional.pad(mels[r], (0, vc["length"] - mels[r].shape[-1])) for r in vc["rows"]])
+                wav = vocoder.spec2wav_batch(batch, **({"lengths": vc["lengths"]} if vc["lengths"] else {})).cpu().numpy()
+                hop = wav.shape[-1] // vc["length"]
+                done.update({r: (mels[r], wav[j, :mels[r].shape[-1] * hop]) for j, r in enumerate(vc["rows"])})
         for r, (p, s, k) in enumerate(rows):
             generated.setdefault((p, s), []).append(done[r])
     return generated

@@ -144,6 +144,8 @@ PROTOTYPES = {
     "vb_t5_workspace_bytes": (C.c_size_t, [C.POINTER(T5Config), c_int, c_int]),
     "vb_t5_encode": (c_int, [P, P, c_int, c_int, P, P, P]),
     "vb_hifigan_forward": (c_int, [P, P, c_int, c_int, P, P, P]),
+    "vb_hifigan_lens_workspace_bytes": (c_size_t, [P, c_int, c_int]),
+    "vb_hifigan_forward_lens": (c_int, [P, P, c_int, c_int, C.POINTER(Lens), P, P, P]),
     "vb_crossfade_windows": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
     "vb_hifigan_forward_chunked": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P, P, P]),
     "vb_melnet_load": (c_int, [P, C.POINTER(MelConfig), P, P]),

@@ -16,7 +16,9 @@ static size_t net_ws_bytes(const NetProgram& n, int B, int T, std::vector<size_t
     }
     return off;
 }
-int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, void* ws, hipStream_t st) {
+// nl (vb_hifigan_forward_lens, after net_lens_check): `in` is the masked copy of the input, every op that writes an activation buffer is
+// followed by launch_tail_zero on it, and the fused pairs end row b's intermediate at its own length.  Null: the plain run, nothing added.
+int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, void* ws, hipStream_t st, const NetLens* nl) {
     NetProgram& n = ctx->nets[which];
     if (!n.loaded) VB_FAIL(VB_E_STATE, "net %d not loaded", which);
     VB_HIP(hipSetDevice(ctx->device));
@@ -38,6 +40,7 @@ int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, v
         if (id == VB_BUF_OUTPUT) return n.out_ch;
         return n.bufs[id].channels;
     };
+    auto tmul = [&](int id) -> int { return id == VB_BUF_INPUT ? n.in_tmul : (id == VB_BUF_OUTPUT ? n.out_tmul : n.bufs[id].tmul); };
     auto bstride = [&](int id) -> int64_t {
         if (id >= 0 && n.bufs[id].square == 1) return (int64_t)tlen(id) * tlen(id);
         return (int64_t)chans(id) * tlen(id);
@@ -112,6 +115,7 @@ int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, v
                 r.x = ptr(o.x); r.out = ptr(o.out); r.B = B; r.C = o.Ci; r.T = tlen(o.x); r.k = o.ksize; r.dil = o.dil;
                 r.w1 = (const bf16_t*)o.w_x3; r.w2 = (const bf16_t*)o.w2; r.b1 = o.bias; r.b2 = o.bias2;
                 r.slope = o.in_slope; r.alpha = o.alpha; r.beta = o.beta;
+                if (nl) { r.row_len = nl->table; r.len_mul = tmul(o.x); }
                 if (o.wfmt == VB_WFMT_BF16) VB_TRY(launch_respair_bf16(r, st));
                 else VB_TRY(launch_respair(r, st));
             } else {
@@ -119,6 +123,7 @@ int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, v
                 r.x = ptr(o.x); r.out = ptr(o.out); r.B = B; r.C = o.Ci; r.T = tlen(o.x); r.k = o.ksize; r.dil = o.dil;
                 r.w1 = o.wfmt == VB_WFMT_MF ? o.w_mf : o.w; r.w2 = (const float*)o.w2; r.b1 = o.bias; r.b2 = o.bias2;
                 r.slope = o.in_slope; r.alpha = o.alpha; r.beta = o.beta;
+                if (nl) { r.row_len = nl->table; r.len_mul = tmul(o.x); }
                 if (o.wfmt == VB_WFMT_MF) VB_TRY(launch_respair_f32w(r, st));
                 else VB_TRY(launch_respair_f32(r, st));
             }
@@ -129,6 +134,32 @@ int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, v
         } else {
             VB_FAIL(VB_E_INVALID, "net op %zu: bad kind %d", oi, o.kind);
         }
+        // (the planes of VB_OP_XT_PLANES need no pass: they are made from a buffer whose tails are zero, and act(0) = 0 rounds to zero rows)
+        if (nl && o.kind != VB_OP_XT_PLANES) VB_TRY(launch_tail_zero(ptr(o.out), nl->lp, nl->table, B, chans(o.out), T, tmul(o.out), st));
+    }
+    return VB_OK;
+}
+// What a program must be for row lengths to work by zero tails alone (include/versband_hip.h, vb_hifigan_forward_lens): every op computes
+// a sample from a zero-padded window of its own row, through an input activation with f(0) = 0, into a plain [B][C][T] buffer.
+static int net_lens_check(const NetProgram& n) {
+    static const char* const kinds[] = {"VB_OP_CONV", "VB_OP_GN_STATS", "VB_OP_SOFTMAX_T", "VB_OP_SPLIT_PLANES", "VB_OP_RESPAIR", "VB_OP_GN_APPLY",
+                                        "VB_OP_AA_ACT", "VB_OP_XT_PLANES"};
+    for (size_t oi = 0; oi < n.ops.size(); ++oi) {
+        const vb_net_op& o = n.ops[oi];
+        const char* kn = o.kind >= 0 && o.kind <= VB_OP_XT_PLANES ? kinds[o.kind] : "unknown kind";
+        if (o.kind == VB_OP_AA_ACT)
+            VB_FAIL(VB_E_INVALID, "hifigan_forward_lens: op %zu (%s): its anti-aliasing filters replicate-pad at the row end, which a zero tail cannot stand in for", oi, kn);
+        if (o.kind != VB_OP_CONV && o.kind != VB_OP_RESPAIR && o.kind != VB_OP_XT_PLANES)
+            VB_FAIL(VB_E_INVALID, "hifigan_forward_lens: op %zu (%s): only VB_OP_CONV, VB_OP_RESPAIR and VB_OP_XT_PLANES take row lengths", oi, kn);
+        if (o.in_act != ACT_NONE && o.in_act != ACT_LRELU)
+            VB_FAIL(VB_E_INVALID, "hifigan_forward_lens: op %zu (%s): input activation %d does not map 0 to 0 (none / LeakyReLU only)", oi, kn, o.in_act);
+        if (o.stats != -1) VB_FAIL(VB_E_INVALID, "hifigan_forward_lens: op %zu (%s): GroupNorm statistics run over the whole row", oi, kn);
+        if (o.Ci <= 0 || (o.kind != VB_OP_XT_PLANES && o.Co <= 0))
+            VB_FAIL(VB_E_INVALID, "hifigan_forward_lens: op %zu (%s): a dynamic channel count (Ci = %d, Co = %d) contracts over the row length", oi, kn, o.Ci, o.Co);
+        if (o.w_buf != -1) VB_FAIL(VB_E_INVALID, "hifigan_forward_lens: op %zu (%s): w_buf weights are made from whole rows", oi, kn);
+        if (o.out_transposed) VB_FAIL(VB_E_INVALID, "hifigan_forward_lens: op %zu (%s): a transposed output is not a [B][C][T] buffer", oi, kn);
+        if (o.kind != VB_OP_XT_PLANES && o.out >= 0 && n.bufs[o.out].square != 0)
+            VB_FAIL(VB_E_INVALID, "hifigan_forward_lens: op %zu (%s): writes a buffer of square = %d, not [B][C][T]", oi, kn, n.bufs[o.out].square);
     }
     return VB_OK;
 }
@@ -232,6 +263,32 @@ int vb_hifigan_forward(vb_ctx* ctx, const float* mel, int B, int T, float* wav, 
     if (!ctx) VB_FAIL(VB_E_INVALID, "hifigan_forward: null ctx");
     RoctxRange rr("vb_hifigan_forward");
     return net_run(ctx, VB_NET_VOCODER, mel, B, T, wav, ws, (hipStream_t)stream);
+}
+size_t vb_hifigan_lens_workspace_bytes(vb_ctx* ctx, int B, int T) {
+    if (!ctx || !ctx->nets[VB_NET_VOCODER].loaded || B < 1 || T < 1) return 0;
+    const NetProgram& n = ctx->nets[VB_NET_VOCODER];
+    // the net's workspace, the masked input, the table of row lengths
+    return net_ws_bytes(n, B, T, nullptr) + align_up((size_t)B * n.in_ch * T * n.in_tmul * sizeof(float)) + align_up(64 * sizeof(int));
+}
+int vb_hifigan_forward_lens(vb_ctx* ctx, const float* mel, int B, int T, const vb_lens* lens, float* wav, void* ws, void* stream) {
+    if (!ctx) VB_FAIL(VB_E_INVALID, "hifigan_forward_lens: null ctx");
+    NetLens nl;
+    if (lens && lens->len) VB_TRY(lens_plan(lens->len, B, T, &nl.lp));
+    RoctxRange rr("vb_hifigan_forward_lens");
+    hipStream_t st = (hipStream_t)stream;
+    if (!nl.lp.B) return net_run(ctx, VB_NET_VOCODER, mel, B, T, wav, ws, st);       // no lengths, or every row full: vb_hifigan_forward
+    NetProgram& n = ctx->nets[VB_NET_VOCODER];
+    if (!n.loaded) VB_FAIL(VB_E_STATE, "hifigan_forward_lens: no vocoder loaded");
+    VB_TRY(net_lens_check(n));
+    if (n.in_tmul != 1) VB_FAIL(VB_E_INVALID, "hifigan_forward_lens: the vocoder's input runs at %d samples per frame (1)", n.in_tmul);
+    VB_HIP(hipSetDevice(ctx->device));
+    char* p = static_cast<char*>(ws) + net_ws_bytes(n, B, T, nullptr);
+    float* masked = reinterpret_cast<float*>(p);
+    int* table = reinterpret_cast<int*>(p + align_up((size_t)B * n.in_ch * T * n.in_tmul * sizeof(float)));
+    VB_TRY(launch_lens_table(nl.lp, table, st));
+    nl.table = table;
+    VB_TRY(launch_mask_latent(mel, B, n.in_ch, T, table, masked, st));                 // (a select: the caller's padding, NaN included, is not read)
+    return net_run(ctx, VB_NET_VOCODER, masked, B, T, wav, ws, st, &nl);
 }
 int vb_crossfade_windows(const float* parts, const int32_t* starts, int nw, int B, int C, int n, int T, float* out, void* stream) {
     if (!parts || !starts || !out || nw < 1 || B < 1 || C < 1 || n < 1 || T < 1) VB_FAIL(VB_E_INVALID, "crossfade_windows: null pointer or nw/B/C/n/T < 1");

@@ -347,6 +347,37 @@ int launch_lens_table(const LensPlan& lp, int* out, hipStream_t st) {
     VB_CHECK_LAUNCH();
     return VB_OK;
 }
+// row lengths in a conv net: the tails out[b][c][len[b] * tmul .. Tp) of an activation buffer [B][C][Tp] back to zero after the op that wrote
+// it, so that the next convolution reads behind row b's end what the clip-alone call's zero padding supplies.  grid = (pieces of the
+// longest tail, C, B): a workgroup of a full row, or behind a shorter tail's end, leaves at once.  VEC: Tp, every short row's tail start and
+// the base are 16-byte multiples (the host checked) - one float4 per lane; otherwise one float.
+template <bool VEC>
+__global__ void __launch_bounds__(256) tail_zero_kernel(float* __restrict__ out, const int* __restrict__ len, int C, int Tp, int tmul) {
+    const int b = blockIdx.z, c = blockIdx.y;
+    const int start = len[b] * tmul;
+    const int i = (blockIdx.x * 256 + threadIdx.x) * (VEC ? 4 : 1);
+    if (start + i >= Tp) return;
+    float* p = out + ((int64_t)b * C + c) * Tp + start + i;
+    if constexpr (VEC) *reinterpret_cast<float4*>(p) = make_float4(0.f, 0.f, 0.f, 0.f);
+    else *p = 0.f;
+}
+int launch_tail_zero(float* out, const LensPlan& lp, const int* len, int B, int C, int T, int tmul, hipStream_t st) {
+    if (lp.B != B || C < 1 || C > 65535 || tmul < 1) VB_FAIL(VB_E_INVALID, "tail_zero: %d lengths for B=%d, C=%d, tmul=%d", lp.B, B, C, tmul);
+    const int Tp = T * tmul;
+    int tail = 0;
+    bool vec = Tp % 4 == 0 && aligned16(out);
+    for (int b = 0; b < B; ++b) {
+        if (lp.len[b] >= T) continue;
+        if ((T - lp.len[b]) * tmul > tail) tail = (T - lp.len[b]) * tmul;
+        vec = vec && (lp.len[b] * tmul) % 4 == 0;
+    }
+    if (tail == 0) return VB_OK;
+    const dim3 grid(cdiv(tail, vec ? 1024 : 256), C, B);
+    if (vec) hipLaunchKernelGGL(tail_zero_kernel<true>, grid, dim3(256), 0, st, out, len, C, Tp, tmul);
+    else hipLaunchKernelGGL(tail_zero_kernel<false>, grid, dim3(256), 0, st, out, len, C, Tp, tmul);
+    VB_CHECK_LAUNCH();
+    return VB_OK;
+}
 __global__ void conv_w_to_gemm_kernel(const bf16_t* __restrict__ w3, int64_t w3_plane, int taps, int D, int KP, bf16_t* __restrict__ out) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;      // (plane, co, k)
     if (idx >= (int64_t)2 * D * KP) return;

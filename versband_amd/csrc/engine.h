@@ -186,4 +186,6 @@ inline SampleGraph::Key sample_key(const SampleCall& sc) {
 }
 
 // ---- convnet.hip ----------------------------------------------------------------------------
-int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, void* ws, hipStream_t st);
+// row lengths of a conv-net run (vb_hifigan_forward_lens): the validated plan and its device table in the workspace
+struct NetLens { LensPlan lp; const int* table = nullptr; };
+int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, void* ws, hipStream_t st, const NetLens* nl = nullptr);

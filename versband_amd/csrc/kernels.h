@@ -148,6 +148,7 @@ struct RespairArgs {
     const bf16_t* w1 = nullptr; const bf16_t* w2 = nullptr;     // split planes [2][k][C][C]
     const float* b1 = nullptr; const float* b2 = nullptr;
     float slope = 0.1f, alpha = 1.f, beta = 0.f;
+    const int* row_len = nullptr; int len_mul = 1;     // row lengths (device [B], in units of len_mul samples): the intermediate is zero from row_len[b] * len_mul on; null = T
 };
 int launch_respair(const RespairArgs& a, hipStream_t st);
 // the same pair in single-pass bf16 (respair_bf16.hip; same window rules and checks, respair_dev.h): w1 / w2 = ONE plane [k][C][C] each, the intermediate rounded to bf16 once; C = 32 / 64
@@ -157,6 +158,7 @@ struct RespairF32Args {
     const float* x = nullptr; float* out = nullptr; int B = 1, C = 0, T = 0, k = 3, dil = 1;
     const float* w1 = nullptr; const float* w2 = nullptr; const float* b1 = nullptr; const float* b2 = nullptr;
     float slope = 0.1f, alpha = 1.f, beta = 0.f;
+    const int* row_len = nullptr; int len_mul = 1;     // as RespairArgs
 };
 bool respair_f32_supported(const RespairF32Args& a);
 int launch_respair_f32(const RespairF32Args& a, hipStream_t st);
@@ -193,6 +195,10 @@ struct LensPlan {
 };
 int lens_plan(const int32_t* len, int B, int T, LensPlan* out);
 int launch_lens_table(const LensPlan& lp, int* out, hipStream_t st);
+// row lengths in a conv net (vb_hifigan_forward_lens): out[b][c][len[b] * tmul .. T * tmul) = 0 for every row shorter than T, in one launch
+// whose grid covers only the tails (rows x channels x the longest tail); 16-byte stores when the row pitch, every short row's tail start and
+// the base allow, 4-byte stores otherwise.  len: the device table of lp's lengths.  Nothing is launched when no row is short.
+int launch_tail_zero(float* out, const LensPlan& lp, const int* len, int B, int C, int T, int tmul, hipStream_t st);
 int launch_conv_w_to_gemm(const bf16_t* w3, int64_t w3_plane, int taps, int D, int KP, bf16_t* out, hipStream_t st);
 int launch_rows_dot(const float* x, const float* W, const float* bias, int N, int D, int E, float* out, hipStream_t st);
 // LayerNorm (no affine, eps) + adaLN modulate -> split-bf16 planes (FinalLayer input, vocal2music_moe.py:287-291)

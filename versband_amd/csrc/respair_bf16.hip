@@ -129,9 +129,10 @@ __global__ void __launch_bounds__(256, 4 / CH) respair_bf16_kernel(const PairDev
     taps(p.w1, p.dil);
     {   // + b1, LeakyReLU, zero outside [0,T), bf16, to hT[t][c] (xT's storage: conv1's last barrier is behind every wave)
         const int m = m0 + 32 * wave + l31;
+        const int Tv = pair_valid_len(p, b);
 #pragma unroll
         for (int i = 0; i < CH; ++i)
-            pair_store_intermediate<1>(acc[i], p.b1 + i * 32, p.slope, m >= 0 && m < p.T, &xh[(32 * wave + l31) * P + i * 32], 0);
+            pair_store_intermediate<1>(acc[i], p.b1 + i * 32, p.slope, m >= 0 && m < Tv, &xh[(32 * wave + l31) * P + i * 32], 0);
     }
     // ---- conv2 (dil 1) over the intermediate -> outputs n0 + [0,TT).  Rows 128 .. 127 + (k-1) of xh are read as well (stale window
     // values, inside the array): they only reach the output columns nl >= TT, which the epilogue drops.

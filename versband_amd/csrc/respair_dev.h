@@ -23,6 +23,7 @@ struct PairDev {
     const float* b1; const float* b2;
     float slope, alpha, beta;
     int staged;               // 16-B (staged) epilogue: T % 4 == 0 and 16-B aligned tensors
+    const int* row_len; int len_mul;      // row lengths (vb_hifigan_forward_lens): device [B], row b's clip ends at row_len[b] * len_mul; null = T (pair_valid_len)
 };
 // the fp32 pairs (respair_f32.hip; respair_f32w.hip, whose kernel size is a template parameter and whose epilogue is always the staged one)
 struct PairF32Dev {
@@ -32,6 +33,7 @@ struct PairF32Dev {
     const float* b1; const float* b2;
     float slope, alpha, beta;
     int staged;
+    const int* row_len; int len_mul;      // as PairDev
 #ifdef VB_EXPERIMENTS
     int x_nt;          // window DMA with the non-temporal policy (VB_CONV_XNT, see conv1d_f32g.hip)
 #endif
@@ -51,6 +53,11 @@ __device__ __forceinline__ PairRun pair_run(int run, int k, int dil) {
     r.aoff = r.x0 - r.start_al;
     return r;
 }
+// Where conv2's zero padding of the ACTIVATED intermediate starts for row b: the row's own length when the call carries row lengths - the
+// clip alone ends there, and the tail of x behind it is zero like the clip-alone call's padding - else T.  The ONE place of a pair kernel
+// that reads it is the intermediate mask; window loads and epilogues keep p.T, the row pitch and padded length.
+template <class Dev>
+__device__ __forceinline__ int pair_valid_len(const Dev& p, int b) { return p.row_len ? p.row_len[b] * p.len_mul : p.T; }
 // b1, LeakyReLU, zero outside [0, T) (conv2 pads the ACTIVATED intermediate) and the operand rounding over the conv1 accumulators of channel
 // chunk i: this lane's intermediate position (row of hT, `pitch` bf16 each) and 4 x 4 channels from c0 on, NPL planes `plane` apart
 template <int NPL>
@@ -81,6 +88,7 @@ static inline int pair_fill_common(const Args& a, const char* who, int run, doub
     d.x = a.x; d.out = a.out; d.bstride = (int64_t)a.C * a.T; d.T = a.T; d.k = a.k; d.dil = a.dil;
     d.w1 = a.w1; d.w2 = a.w2; d.b1 = a.b1; d.b2 = a.b2;
     d.slope = a.slope; d.alpha = a.alpha; d.beta = a.beta;
+    d.row_len = a.row_len; d.len_mul = a.len_mul;
     d.staged = (a.T % 4 == 0 && aligned16(a.x) && aligned16(a.out) && !vb_tune().conv_direct_epi) ? 1 : 0;
     L.grid = dim3(cdiv(a.T, pair_run_outputs(run, a.k)), 1, a.B);
     L.flops = 2.0 * 2.0 * a.B * (double)a.C * a.C * taps * (double)a.T;

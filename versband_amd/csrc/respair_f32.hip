@@ -178,7 +178,7 @@ __global__ void __launch_bounds__(256) respair_f32_kernel(const PairF32Dev p) {
     // the barrier of the first conv2 tile's step); a second barrier publishes it
     auto middle = [&]() {
         const int m = m0 + 32 * wave + l31;
-        const bool inr = m >= 0 && m < p.T;
+        const bool inr = m >= 0 && m < pair_valid_len(p, b);
 #pragma unroll
         for (int i = 0; i < CH; ++i)
 #pragma unroll

@@ -126,7 +126,8 @@ __global__ void __launch_bounds__(256, 2) respair_f32w_kernel(const PairF32Dev p
 #pragma clang fp contract(off)
         const int mrel = wt * 2 * VW + bpos;
         const int ma = m0 + mrel;
-        const bool ok0 = l31 < VW && ma >= 0 && ma < p.T, ok1 = l31 < VW && ma + dil >= 0 && ma + dil < p.T;
+        const int Tv = pair_valid_len(p, b);
+        const bool ok0 = l31 < VW && ma >= 0 && ma < Tv, ok1 = l31 < VW && ma + dil >= 0 && ma + dil < Tv;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int c = wc * 32 + 8 * (r >> 2) + 4 * g + (r & 3);

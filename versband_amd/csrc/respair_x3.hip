@@ -145,9 +145,10 @@ __global__ void __launch_bounds__(256) respair_x3_kernel(const PairDev p) {
     fold_acc();
     {   // + b1, LeakyReLU, zero outside [0,T), split, to hT[chunk][plane][t][c]
         const int m = m0 + 32 * wave + l31;
+        const int Tv = pair_valid_len(p, b);
 #pragma unroll
         for (int i = 0; i < CH; ++i)
-            pair_store_intermediate<2>(acc[i], p.b1 + i * 32, p.slope, m >= 0 && m < p.T, &hT[i][0][(32 * wave + l31) * RP_P], PAIR_T * RP_P);
+            pair_store_intermediate<2>(acc[i], p.b1 + i * 32, p.slope, m >= 0 && m < Tv, &hT[i][0][(32 * wave + l31) * RP_P], PAIR_T * RP_P);
     }
     // ---- conv2 (dil 1) over the intermediate -> outputs n0 + [0,TT)
     zero_acc();

@@ -344,15 +344,15 @@ class DiTEngine:
         return L.Windows(arr, nw), arr
 
     @staticmethod
-    def _lens_struct(lengths, B: int, T: int, windows=None, T_mel: Optional[int] = None, cond: Optional[dict] = None):
+    def _lens_struct(lengths, B: int, T: int, windows=None, T_mel: Optional[int] = None, cond: Optional[dict] = None,
+                     gloss: str = " (latent tokens per row)"):
         """validate the row lengths of a call - B integers in [1, T], the library's rules (include/versband_hip.h), stated here first so
         that the error names the caller's argument - and lay them out as vb_lens (a host array, read during the call).  All equal to T
         or None is the plain call.  cond: the conditioning handle the call samples from, which must have been made with the same
         lengths.  Returns (struct or None, the array to hold, the lengths as a tuple or None)."""
         lens = None
         if lengths is not None:
-            vals = [int(v) for v in _checked_list("lengths", lengths, "integers", (B, "rows"), f"a sequence of {B} row lengths",
-                                                  " (latent tokens per row)")]
+            vals = [int(v) for v in _checked_list("lengths", lengths, "integers", (B, "rows"), f"a sequence of {B} row lengths", gloss)]
             if B > 64:
                 raise ValueError(f"lengths: {B} rows (at most 64)")
             for b, v in enumerate(vals):
@@ -653,6 +653,8 @@ class ConvNet:
                 "vb_net_load")
         self._ws = None
         self._ws_key = None
+        self._lens_ws = None
+        self._lens_ws_key = None
 
     def _workspace(self, B, T):
         if self._ws_key != (B, T):
@@ -661,18 +663,41 @@ class ConvNet:
             self._ws_key = (B, T)
         return self._ws
 
-    def run(self, x: Tensor) -> Tensor:
+    NET_NAMES = {L.NET_VAE: "VAE decoder", L.NET_VOCODER: "vocoder", L.NET_VAE_ENCODER: "VAE encoder"}
+
+    def run(self, x: Tensor, lengths=None) -> Tensor:
+        """lengths (vocoder only; vb_hifigan_forward_lens): one length in input frames per row - mels of different lengths padded to
+        x.shape[-1] share the call.  Row b's first lengths[b] * out_tmul samples are the call on that clip alone (bit for bit when
+        lengths[b] and x.shape[-1] agree mod 4, to fp32 roundoff otherwise: harness.plan_vocoder_calls groups rows accordingly), the rest
+        of the row is zero, and the padding of x is never read.  None, or every row full, is the plain call."""
         x = x.to(self.ctx.device, torch.float32).contiguous()
         B, Cin, Tin = x.shape
         assert Cin == self.in_ch, (Cin, self.in_ch)
         if Tin % self.in_tmul:
             raise ValueError(f"input length {Tin} is not a multiple of {self.in_tmul}")
         T = Tin // self.in_tmul
+        if lengths is not None:
+            if self.which != L.NET_VOCODER:
+                raise ValueError(f"lengths: the {self.NET_NAMES[self.which]} takes equal-length rows only (row lengths reach the vocoder net alone)")
+            lens, hold, _ = DiTEngine._lens_struct(lengths, B, T, gloss=" (input frames per row)")
+            if lens is not None:
+                return self._run_lens(x, B, T, lens, hold)
         out = torch.empty(B, self.out_ch, T * self.out_tmul, dtype=torch.float32, device=self.ctx.device)
         ws = self._workspace(B, T)
         fn = {L.NET_VAE: self.ctx.lib.vb_vae_decode, L.NET_VOCODER: self.ctx.lib.vb_hifigan_forward,
               L.NET_VAE_ENCODER: self.ctx.lib.vb_vae_encode}[self.which]
         L.check(fn(self.ctx.handle, L.ptr(x), B, T, L.ptr(out), L.ptr(ws), L.stream_ptr()), "conv net run")
+        return out
+
+    def _run_lens(self, x: Tensor, B: int, T: int, lens, hold) -> Tensor:
+        out = torch.empty(B, self.out_ch, T * self.out_tmul, dtype=torch.float32, device=self.ctx.device)
+        if self._lens_ws_key != (B, T):
+            n = self.ctx.lib.vb_hifigan_lens_workspace_bytes(self.ctx.handle, B, T)
+            self._lens_ws = torch.empty(max(n, 256), dtype=torch.uint8, device=self.ctx.device)
+            self._lens_ws_key = (B, T)
+        L.check(self.ctx.lib.vb_hifigan_forward_lens(self.ctx.handle, L.ptr(x), B, T, C.byref(lens), L.ptr(out), L.ptr(self._lens_ws), L.stream_ptr()),
+                "vb_hifigan_forward_lens")
+        del hold                         # (the host array of the lengths: read during the call only)
         return out
 
 

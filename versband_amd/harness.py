@@ -221,6 +221,28 @@ def plan_row_batches(lengths, scales, n_samples: int, items_per_batch: int, indi
     return calls
 
 
+def plan_vocoder_calls(row_lengths_mel) -> List[dict]:
+    """The vocoder calls for rows of the given mel lengths (frames), as a list of
+        {"rows": [row indices, ascending], "length": the padded length = the longest member, "lengths": [mel length per member] | None}
+    Rows whose lengths share a residue mod 4 form one call (HifiGAN.spec2wav_batch(..., lengths=)): the vocoder's kernel routes depend on
+    a length only through that residue, so inside such a group every row equals the call on that clip alone bit for bit
+    (include/versband_hip.h, vb_hifigan_forward_lens).  At most 4 calls, in the order in which their residues first appear; latent
+    lengths make even mel lengths, hence at most 2.  "lengths" is None where the members are all equally long: the plain call."""
+    lens = [int(v) for v in row_lengths_mel]
+    for r, v in enumerate(lens):
+        if v < 1:
+            raise ValueError(f"plan_vocoder_calls: row {r} has length {v} (at least 1)")
+    groups: Dict[int, List[int]] = {}
+    for r, v in enumerate(lens):
+        groups.setdefault(v % 4, []).append(r)
+    calls = []
+    for rows in groups.values():
+        member = [lens[r] for r in rows]
+        longest = max(member)
+        calls.append({"rows": rows, "length": longest, "lengths": member if any(v != longest for v in member) else None})
+    return calls
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # caption text (the "Musical: ..." half of the prompt)
 # ------------------------------------------------------------------------------------------------------------------

@@ -656,9 +656,11 @@ class HifiGAN:
         c = c.transpose(2, 1).contiguous()
         return self.net().run(c).view(-1).cpu().numpy()
 
-    def spec2wav_batch(self, mel_bct: Tensor) -> Tensor:
-        """device-resident batched path: mel [B,80,T] -> wav [B, T*hop] (no host round trip)."""
-        return self.net().run(mel_bct).squeeze(1)
+    def spec2wav_batch(self, mel_bct: Tensor, lengths=None) -> Tensor:
+        """device-resident batched path: mel [B,80,T] -> wav [B, T*hop] (no host round trip).
+        lengths (addition; ConvNet.run): one length in mel frames per row - mels of different lengths padded to T share the call, row b
+        holds lengths[b] * hop samples of the clip alone followed by zeros, the mel padding is never read."""
+        return self.net().run(mel_bct, **({} if lengths is None else {"lengths": lengths})).squeeze(1)
 
     def __call__(self, mel):
         return self.spec2wav(mel)
