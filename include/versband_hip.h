@@ -524,6 +524,14 @@ int vb_caption_gate(const void* x, const void* keys, const float* score_bias, co
                     const float* hl, int hl_ld, const float* g1, const float* g2, const float* g3, uint64_t seed, int64_t clip_base, int nfe,
                     int block, int Beff, int B, int T, int K, int NS, int Hh, int E, int form, float* scores, int32_t* clip_off, int32_t* ic,
                     int32_t* ia, float* mc, float* ma, float* lc_out, int32_t* cnt, int cnt_G, int cnt_pairs, void* stream);
+/* the launch that produces attention's inputs, alone: the QKV projection with the RoPE / V-transpose epilogue, as one DiT block runs it
+ * (Attention.forward, flag_large_dit_moe.py:381-402).  D = H * hd, row m = b * T + t:
+ *   u planes [B*T][D]; wqkv planes [3D][D] (rows: q, k, v thirds); rope_cos / rope_sin f32 [>= T][hd / 2];
+ *   q, k planes [B*T][D]: the pair (2j, 2j+1) of every head rotated by (cos, sin)[t][j]; vt planes [B][H][hd][Tpad] = V transposed per head.
+ * Only the columns < T of vt are written: the caller owns the pad columns [T, Tpad) (vb_attention needs them finite).  No tile route or
+ * store form is chosen here - launch_gemm's own rules and the VB_GEMM_TILE / VB_QKV_* / VB_GEMM_P8_OFF switches apply as in the engine. */
+int vb_qkv_rope(const void* u, const void* wqkv, const float* rope_cos, const float* rope_sin, int B, int T, int Tpad, int H, int hd, int np,
+                void* q, void* k, void* vt, void* stream);
 /* fused self (+cross) attention, head_dim 96 (Attention.forward, flag_large_dit_moe.py:381-402) */
 int vb_attention(const void* q, const void* k, const void* vt, const void* ky, const void* vyt, const float* cross_w, int B, int T,
                  int Tpad, int L, int Lpad, int H, int hd, int np, void* out, void* stream);

@@ -163,6 +163,7 @@ PROTOTYPES = {
     "vb_routed_ffn_pair": (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P]),
     "vb_caption_gate": (c_int, [P, P, P, P, P, P, c_int, P, c_int, P, P, P, c_u64, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                 c_int, c_int, c_int, P, P, P, P, P, P, P, P, c_int, c_int, P]),
+    "vb_qkv_rope": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
     "vb_attention": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
     "vb_conv1d_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                               c_float, P, P, P, c_int, P]),

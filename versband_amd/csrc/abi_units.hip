@@ -95,6 +95,17 @@ int vb_caption_gate(const void* x, const void* keys, const float* score_bias, co
     r.N = N; r.D = K; r.sc = scores; r.lc_out = lc_out;
     return launch_router(r, st);
 }
+int vb_qkv_rope(const void* u, const void* wqkv, const float* rope_cos, const float* rope_sin, int B, int T, int Tpad, int H, int hd, int np,
+                void* q, void* k, void* vt, void* stream) {
+    if (!u || !wqkv || !rope_cos || !rope_sin || !q || !k || !vt || B < 1 || T < 1 || H < 1 || hd < 2 || Tpad < T || (np != 1 && np != 2))
+        VB_FAIL(VB_E_INVALID, "qkv_rope: null pointer, B/T/H < 1, hd < 2, Tpad < T or np not 1 / 2");
+    const int D = H * hd, N = B * T;
+    const int64_t ND = (int64_t)N * D;
+    GemmArgs g = gemm_operands(u, ND, D, wqkv, (int64_t)3 * D * D, D, N, 3 * D, D, np == 2 ? 3 : 1);
+    g.epi = EPI_QKV_ROPE; g.q = mkp((bf16_t*)q, ND, np); g.k = mkp((bf16_t*)k, ND, np); g.vt = mkp((bf16_t*)vt, (int64_t)B * D * Tpad, np);
+    g.rope_cos = rope_cos; g.rope_sin = rope_sin; g.H = H; g.hd = hd; g.Tpad = Tpad; g.D = D; g.T = T;
+    return launch_gemm(g, (hipStream_t)stream);
+}
 int vb_attention(const void* q, const void* k, const void* vt, const void* ky, const void* vyt, const float* cross_w, int B, int T,
                  int Tpad, int L, int Lpad, int H, int hd, int np, void* out, void* stream) {
     return vb_attention_lens(q, k, vt, ky, vyt, cross_w, B, T, Tpad, L, Lpad, H, hd, np, nullptr, out, stream);
