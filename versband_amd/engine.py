@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -88,6 +88,35 @@ def _checked_list(name: str, v, kind: Optional[str], count: Optional[Tuple[int, 
     if bad_count:
         raise ValueError(f"{name} has {len(vals)} entries for {count[0]} {count[1]}")
     return vals
+
+
+def _lens_struct(lengths, B: int, T: int, windows=None, T_mel: Optional[int] = None, cond: Optional[dict] = None,
+                 gloss: str = " (latent tokens per row)"):
+    """validate the row lengths of a call - B integers in [1, T], the library's rules (include/versband_hip.h), stated here first so
+    that the error names the caller's argument - and lay them out as vb_lens (a host array, read during the call).  All equal to T
+    or None is the plain call.  cond: the conditioning handle the call samples from, which must have been made with the same
+    lengths.  Returns (struct or None, the array to hold, the lengths as a tuple or None).  Serves the sampler's rows
+    (latent tokens) and the vocoder's (ConvNet.run: input frames)."""
+    lens = None
+    if lengths is not None:
+        vals = [int(v) for v in _checked_list("lengths", lengths, "integers", (B, "rows"), f"a sequence of {B} row lengths", gloss)]
+        if B > 64:
+            raise ValueError(f"lengths: {B} rows (at most 64)")
+        for b, v in enumerate(vals):
+            if not 1 <= v <= T:
+                raise ValueError(f"lengths[{b}] = {v} is not in [1, T = {T}]")
+        if any(v != T for v in vals):
+            lens = tuple(vals)
+    if cond is not None and cond.get("lengths") != lens:
+        raise ValueError(f"lengths {lens} differ from the lengths the conditioning was made with ({cond.get('lengths')})")
+    if lens is None:
+        return None, None, None
+    if windows is not None and len(list(windows)) > 1:
+        raise ValueError("lengths and joint windows do not go together: windows are equal-length by construction")
+    if T_mel is not None and T_mel != 2 * T:
+        raise ValueError(f"lengths need midi / beats of exactly 2 * T = {2 * T} frames, got {T_mel}")
+    arr = (C.c_int32 * B)(*lens)
+    return L.Lens(arr), arr, lens
 
 
 def _check_device(name: str, t: Tensor, dev):
@@ -343,33 +372,7 @@ class DiTEngine:
         arr = (C.c_int32 * nw)(*starts)
         return L.Windows(arr, nw), arr
 
-    @staticmethod
-    def _lens_struct(lengths, B: int, T: int, windows=None, T_mel: Optional[int] = None, cond: Optional[dict] = None,
-                     gloss: str = " (latent tokens per row)"):
-        """validate the row lengths of a call - B integers in [1, T], the library's rules (include/versband_hip.h), stated here first so
-        that the error names the caller's argument - and lay them out as vb_lens (a host array, read during the call).  All equal to T
-        or None is the plain call.  cond: the conditioning handle the call samples from, which must have been made with the same
-        lengths.  Returns (struct or None, the array to hold, the lengths as a tuple or None)."""
-        lens = None
-        if lengths is not None:
-            vals = [int(v) for v in _checked_list("lengths", lengths, "integers", (B, "rows"), f"a sequence of {B} row lengths", gloss)]
-            if B > 64:
-                raise ValueError(f"lengths: {B} rows (at most 64)")
-            for b, v in enumerate(vals):
-                if not 1 <= v <= T:
-                    raise ValueError(f"lengths[{b}] = {v} is not in [1, T = {T}]")
-            if any(v != T for v in vals):
-                lens = tuple(vals)
-        if cond is not None and cond.get("lengths") != lens:
-            raise ValueError(f"lengths {lens} differ from the lengths the conditioning was made with ({cond.get('lengths')})")
-        if lens is None:
-            return None, None, None
-        if windows is not None and len(list(windows)) > 1:
-            raise ValueError("lengths and joint windows do not go together: windows are equal-length by construction")
-        if T_mel is not None and T_mel != 2 * T:
-            raise ValueError(f"lengths need midi / beats of exactly 2 * T = {2 * T} frames, got {T_mel}")
-        arr = (C.c_int32 * B)(*lens)
-        return L.Lens(arr), arr, lens
+    _lens_struct = staticmethod(_lens_struct)       # (the name the call sites and the tests use)
 
     @staticmethod
     def _guidance_struct(guidance, n: int):
@@ -495,25 +498,85 @@ def mf_conv_eligible(w: Tensor, Ci: int, Co: int, k: int, dil: int, in_act: int,
             tuple(w.shape) == (k, Ci, Co))
 
 
+class _Precision(NamedTuple):
+    """one row of NET_PRECISIONS: everything NetBuilder and the builders decide by a precision's name"""
+    x3_like: bool               # the op list's shape: fused input transforms, per-clip weights as split planes
+    xt_like: bool               # wide layers read pre-activated transposed planes (VB_OP_XT_PLANES)
+    wfmt: int                   # static weights: their format (a layer has to qualify for WFMT_MF, mf_conv_eligible, or stays WFMT_F32),
+    pack: Optional[Callable]    # its packer, (w, device) -> (the tensor to keep, ci_pad or None) - None: plain fp32, w itself -
+    slot: str                   # and the vb_net_op field the packed weights travel in, which respair copies to w2
+    keeps_fp32: bool            # an op that asks for the fp32 copy beside its packed weights gets it (False: only an op that reads w,
+                                # one output channel)
+    buf_wfmt: int               # per-batch weights in a buffer: their format
+    xt_planes: int              # planes xt_planes writes: split-bf16 hi / lo, or ONE RN-bf16 plane (WFMT_BF16, half the bytes)
+    fp32_pairs: Optional[str]   # HiFi-GAN pair fusion: None = the window-staged rule (build_hifigan's fuse_pairs, reach <= 64); a string =
+                                # the fp32 DMA rule, for the channel counts of VB_FP32_PAIRS, this string by default
+
+
+def _pack_x3(w: Tensor, device):
+    return pack.pack_conv_x3(w.to(device))
+
+
+def _pack_bf16(w: Tensor, device):
+    return pack.pack_conv_bf16(w.to(device))
+
+
+def _pack_mf(w: Tensor, device):
+    return pack.pack_conv_mf(w.permute(2, 1, 0)).to(device, torch.float32).contiguous(), None      # (w arrives packed [k][Ci][Co])
+
+
+# The conv-net precisions; a new one is a new row.
+# "split": bf16x3 MFMA conv kernels (fp32-class); "fp32": the exact-fp32 MFMA kernels; "fp32mf": the fp32 op list in which the
+# layers of mf_conv_eligible and the 32 / 64-channel pairs run F(2,3) minimal filtering (fp32 products, ~1.45x fewer);
+# "bf16": the split op list without the DMA-fed input planes, every static-weight convolution and 32 / 64-channel pair in ONE
+# bf16 pass (RN-bf16 weights x RN-bf16 activated input, fp32 accumulation: outside the 1e-3 parity contract, DESIGN.md section 2);
+# "bf16xt": the same arithmetic on the split op list's SHAPE - every wide layer's input is activated, rounded and transposed once
+# into ONE bf16 plane (VB_OP_XT_PLANES with WFMT_BF16) and the BF16 convolution reads it by DMA (a one-pass GEMM where it qualifies)
+NET_PRECISIONS: Dict[str, _Precision] = {
+    #                    x3_like xt_like wfmt       pack        slot   keeps_fp32 buf_wfmt    xt_planes fp32_pairs
+    "split":  _Precision(True,  True,  L.WFMT_X3,   _pack_x3,   "w_x3", True,  L.WFMT_BUF_X3,  2, None),
+    "fp32":   _Precision(False, False, L.WFMT_F32,  None,       "w",    True,  L.WFMT_BUF_F32, 2, "32,64"),
+    "fp32mf": _Precision(False, False, L.WFMT_MF,   _pack_mf,   "w_mf", True,  L.WFMT_BUF_F32, 2, "32"),
+    "bf16":   _Precision(True,  False, L.WFMT_BF16, _pack_bf16, "w_x3", False, L.WFMT_BUF_X3,  2, None),
+    "bf16xt": _Precision(True,  True,  L.WFMT_BF16, _pack_bf16, "w_x3", False, L.WFMT_BUF_X3,  1, None),
+}
+
+# The A/B switches of the conv-net builders: environment variables that keep a measured-against op list, or a tuning knob, alive.
+# Every read goes through _switch: the first four when a builder runs, VB_XT_MIN_CO when this module is imported.
+_SWITCHES = {
+    # exact-fp32 modes: the channel counts whose ResBlock1 pairs run fused (respair_f32_kernel), "32,64" / "" for A/B runs.
+    # (fp32mf: the 32-channel pairs run respair_f32w_kernel - minimal filtering in both convolutions, intermediate in LDS; the 64-channel pairs run
+    #  as two unfused minimal-filtering launches: faster than the direct fused pair (1201 -> 1232 mel-s/s) AND than respair_f32w_kernel's 64-channel
+    #  form (VB_FP32_PAIRS=32,64: 1196-1198 against 1224; a 2 x 2 wave grid leaves 16 MFMAs per ring step).
+    #  A/Bs: profiles/r06_mf_pairs_ab.txt, profiles/r06_mf_pair32.txt)
+    "VB_FP32_PAIRS": "channel counts of the fused fp32 pairs (default: the precision's row, \"32,64\" / fp32mf \"32\")",
+    "VB_MF_PAIRS_OFF": "=1, fp32mf: the 32 / 64-channel pairs run the direct fused pair kernel, not minimal filtering",
+    "VB_LRELU_IN_WINDOW": "=1: an unfused pair's inner LeakyReLU stays in the second convolution's window pass (the op list before round 6)",
+    "VB_FP32_NO_PREPASS": "=1, exact-fp32 modes: GroupNorm (+ swish) stays in the register-staged convolution, no gn_apply pre-pass (the old op list)",
+    "VB_XT_MIN_CO": "output channels from which a layer is wide (tuning knob, default 384; 256 / 128 would pull the wide vocoder stages in)",
+}
+
+
+def _switch(name: str, default: str = "") -> str:
+    assert name in _SWITCHES, name
+    return os.environ.get(name, default)
+
+
 class NetBuilder:
     """Flattens a conv network into the vb_net_op list executed by the C++ runtime."""
 
+    XT_MIN_CO = int(_switch("VB_XT_MIN_CO", "384"))
+
     def __init__(self, device, precision: str = "split"):
-        assert precision in ("split", "fp32", "fp32mf", "bf16", "bf16xt")
+        assert precision in NET_PRECISIONS
         self.device = device
-        # "split": bf16x3 MFMA conv kernels (fp32-class); "fp32": the exact-fp32 MFMA kernels; "fp32mf": the fp32 op list in which the
-        # layers of mf_conv_eligible and the 32 / 64-channel pairs run F(2,3) minimal filtering (fp32 products, ~1.45x fewer);
-        # "bf16": the split op list without the DMA-fed input planes, every static-weight convolution and 32 / 64-channel pair in ONE
-        # bf16 pass (RN-bf16 weights x RN-bf16 activated input, fp32 accumulation: outside the 1e-3 parity contract, DESIGN.md section 2);
-        # "bf16xt": the same arithmetic on the split op list's SHAPE - every wide layer's input is activated, rounded and transposed once
-        # into ONE bf16 plane (VB_OP_XT_PLANES with WFMT_BF16) and the BF16 convolution reads it by DMA (a one-pass GEMM where it qualifies)
         self.precision = precision
-        self.x3_like = precision in ("split", "bf16", "bf16xt")      # the op list's shape: fused input transforms, split planes for per-clip weights
-        self.xt_like = precision in ("split", "bf16xt")              # wide layers read pre-activated transposed planes
+        self.row = NET_PRECISIONS[precision]
         self.ops: List[L.NetOp] = []
         self.bufs: List[Tuple[int, int, int]] = []
         self.free: Dict[Tuple[int, int, int], List[int]] = {}
         self.keep: List[Tensor] = []
+        self._aa_filter: Optional[Tensor] = None        # (BigVGAN's anti-aliasing filter, made by the first aa_act)
 
     def buf(self, channels: int, tmul: int, square: bool = False) -> int:
         key = (channels, tmul, int(square))
@@ -548,22 +611,17 @@ class NetBuilder:
         w: fp32 packed [phase][tap][Ci][Co]; w_buf: per-batch weights in a buffer instead (split: written by split_planes); mf: the
         layer qualifies for minimal filtering (fp32mf only); fallback: an X3 / MF conv keeps w as well (what the one-output-channel
         kernel and the direct kernels read)."""
+        row = self.row
         if w_buf != -1:
-            return dict(wfmt=L.WFMT_BUF_X3 if self.x3_like else L.WFMT_BUF_F32)
-        if self.precision in ("bf16", "bf16xt"):
-            plane, ci_pad = pack.pack_conv_bf16(w.to(self.device))
-            self.keep.append(plane)
-            f = dict(wfmt=L.WFMT_BF16, w_x3=plane.data_ptr(), ci_pad=ci_pad)
-            fallback = fallback and w.shape[-1] == 1       # no fp32 copy except where the op reads w (one output channel)
-        elif self.precision == "split":
-            planes, ci_pad = pack.pack_conv_x3(w.to(self.device))
-            self.keep.append(planes)
-            f = dict(wfmt=L.WFMT_X3, w_x3=planes.data_ptr(), ci_pad=ci_pad)
-        elif self.precision == "fp32mf" and mf:
-            f = dict(wfmt=L.WFMT_MF, w_mf=self._t(pack.pack_conv_mf(w.permute(2, 1, 0))))      # (w arrives packed [k][Ci][Co])
-        else:
+            return dict(wfmt=row.buf_wfmt)
+        if row.pack is None or (row.wfmt == L.WFMT_MF and not mf):
             return dict(wfmt=L.WFMT_F32, w=self._t(w))
-        if fallback:
+        packed, ci_pad = row.pack(w, self.device)
+        self.keep.append(packed)
+        f = {"wfmt": row.wfmt, row.slot: packed.data_ptr()}
+        if ci_pad is not None:
+            f["ci_pad"] = ci_pad
+        if fallback and (row.keeps_fp32 or w.shape[-1] == 1):
             f["w"] = self._t(w)
         return f
 
@@ -572,16 +630,16 @@ class NetBuilder:
         """Fused HiFi-GAN ResBlock1 pair (w1/w2 fp32 packed [k][Ci][Co]); narrow stages only (ch = 32 or 64; fp32 mode: 32 / 64 / 128).
         fp32mf: the 32 / 64-channel pairs of k = 3 / 7 / 11 run minimal filtering in both convolutions (respair_f32w.hip),
         VB_MF_PAIRS_OFF=1 the direct pair kernel."""
-        mf = ch in (32, 64) and k in (3, 7, 11) and not os.environ.get("VB_MF_PAIRS_OFF")
+        mf = ch in (32, 64) and k in (3, 7, 11) and not _switch("VB_MF_PAIRS_OFF")
         f = self.weights(w1, mf=mf, fallback=False)
-        slot = {L.WFMT_F32: "w", L.WFMT_X3: "w_x3", L.WFMT_MF: "w_mf", L.WFMT_BF16: "w_x3"}[f["wfmt"]]     # the second convolution's weights go to w2
+        slot = "w" if f["wfmt"] == L.WFMT_F32 else self.row.slot        # the second convolution's weights go from there to w2
         f["w2"] = self.weights(w2, mf=mf, fallback=False)[slot]
         self.ops.append(L.NetOp(kind=L.OP_RESPAIR, x=x, out=out, res=-1, stats=-1, w_buf=-1, bias=self._t(b1), bias2=self._t(b2), Ci=ch, Co=ch,
                                 ksize=k, dil=dil, in_slope=slope, alpha=alpha, beta=beta, **f))
 
     def aa_act(self, x: int, out: int, ch: int, alpha: Tensor, beta: Optional[Tensor], logscale: bool):
         """BigVGAN Activation1d(Snake / SnakeBeta): out = down2(act(up2(x))) (alias_free_torch/act.py)."""
-        if getattr(self, "_aa_filter", None) is None:
+        if self._aa_filter is None:
             self._aa_filter = pack.kaiser_sinc_filter1d(0.25, 0.3, 12)
         a = alpha.float()
         b = a if beta is None else beta.float()
@@ -599,17 +657,17 @@ class NetBuilder:
              acc_scale=1.0, tr_stride=1, tr_pad=0, tr_k=0, groups=32, in_stride=1, in_phase=0, x_is_planes=False):
         tmp = -1
         x_planes = int(bool(x_is_planes))
-        if (self.xt_like and not x_planes and w is not None and w_buf == -1 and x >= 0 and Co >= self.XT_MIN_CO and Ci % 32 == 0
+        if (self.row.xt_like and not x_planes and w is not None and w_buf == -1 and x >= 0 and Co >= self.XT_MIN_CO and Ci % 32 == 0
                 and tr_stride == 1 and in_stride == 1 and pad <= 64 and (k - 1) * dil <= 64 and (k > 1 or in_act != L.ACT_NONE)):
             # wide layer (>= 3 output-channel tiles): the input is activated, split (bf16xt: rounded) and transposed ONCE (VB_OP_XT_PLANES)
             # and every tile of the convolution DMAs its window from there, instead of each tile redoing norm / swish / split while staging
             tmp = self.xt_planes(x, Ci, stats, gamma, beta_gn, in_act, in_slope, upsample2, groups)
             x, stats, gamma, beta_gn, in_act, x_planes = tmp, -1, None, None, L.ACT_NONE, 1
-        if (not self.x3_like and in_act in (L.ACT_GN_SWISH, L.ACT_GN) and stats >= 0 and w is not None and w_buf == -1 and x >= 0
-                and Ci % 16 == 0 and Co % 4 == 0 and in_stride == 1 and tr_stride == 1 and not os.environ.get("VB_FP32_NO_PREPASS")):
+        if (not self.row.x3_like and in_act in (L.ACT_GN_SWISH, L.ACT_GN) and stats >= 0 and w is not None and w_buf == -1 and x >= 0
+                and Ci % 16 == 0 and Co % 4 == 0 and in_stride == 1 and tr_stride == 1 and not _switch("VB_FP32_NO_PREPASS")):
             # exact-fp32 mode: GroupNorm (+ swish) is applied ONCE by gn_apply_kernel and the DMA-fed fp32 kernel (conv1d_f32g_kernel)
             # reads the activated tensor; the register-staged kernel redid norm + swish + expf for every output-channel tile
-            # (12 times on the 1536-channel layers: 2.3 ms for an 85-GFLOP layer).  VB_FP32_NO_PREPASS=1 keeps the old op list (A/B).
+            # (12 times on the 1536-channel layers: 2.3 ms for an 85-GFLOP layer).
             tmp = self.gn_apply(x, Ci, stats, gamma, beta_gn, in_act, groups)
             x, stats, gamma, beta_gn, in_act = tmp, -1, None, None, L.ACT_NONE
         mf = w is not None and mf_conv_eligible(w, Ci, Co, k, dil, in_act, upsample2, out_transposed, tr_stride, in_stride)
@@ -621,13 +679,10 @@ class NetBuilder:
         self.ops.append(op)
         self.release(tmp)
 
-    GN_PREPASS_MIN_CO = 512
-    XT_MIN_CO = int(os.environ.get("VB_XT_MIN_CO", "384"))      # (tuning knob; 256 / 128 would pull the wide vocoder stages in)
-
     def xt_planes(self, x: int, channels: int, stats: int, gamma, beta_gn, act: int, slope: float, upsample2: int, groups: int = 32) -> int:
         """x -> new buffer of pre-activated, split-bf16, transposed planes with zero halo rows (VB_OP_XT_PLANES); bf16xt: the one-plane
         form (WFMT_BF16, a buffer of square = 4: half the bytes)."""
-        one = self.precision == "bf16xt"
+        one = self.row.xt_planes == 1
         out = self.buf(channels, self.bufs[x][1] * (2 if upsample2 else 1), 4 if one else 3)
         self.ops.append(L.NetOp(kind=L.OP_XT_PLANES, wfmt=L.WFMT_BF16 if one else L.WFMT_NONE, x=x, out=out, res=-1, stats=stats, w_buf=-1,
                                 gn_gamma=self._t(gamma),
@@ -651,17 +706,19 @@ class ConvNet:
         bufs = (L.BufDesc * max(1, len(nb.bufs)))(*[L.BufDesc(*b) for b in nb.bufs])
         L.check(ctx.lib.vb_net_load(ctx.handle, which, ops, len(nb.ops), bufs, len(nb.bufs), in_ch, out_ch, in_tmul, out_tmul),
                 "vb_net_load")
-        self._ws = None
-        self._ws_key = None
-        self._lens_ws = None
-        self._lens_ws_key = None
+        # scratch that is sized for a call's (B, T) and made again when that changes: slot -> ((B, T), the buffers)
+        self._scratch = {"net": (None, None), "lens": (None, None), "chunk": (None, None)}
+
+    def _cached(self, slot: str, key: Tuple[int, int], make):
+        if self._scratch[slot][0] != key:
+            self._scratch[slot] = (key, make())
+        return self._scratch[slot][1]
+
+    def _bytes(self, n: int) -> Tensor:
+        return torch.empty(max(n, 256), dtype=torch.uint8, device=self.ctx.device)
 
     def _workspace(self, B, T):
-        if self._ws_key != (B, T):
-            n = self.ctx.lib.vb_net_workspace_bytes(self.ctx.handle, self.which, B, T)
-            self._ws = torch.empty(max(n, 256), dtype=torch.uint8, device=self.ctx.device)
-            self._ws_key = (B, T)
-        return self._ws
+        return self._cached("net", (B, T), lambda: self._bytes(self.ctx.lib.vb_net_workspace_bytes(self.ctx.handle, self.which, B, T)))
 
     NET_NAMES = {L.NET_VAE: "VAE decoder", L.NET_VOCODER: "vocoder", L.NET_VAE_ENCODER: "VAE encoder"}
 
@@ -679,7 +736,7 @@ class ConvNet:
         if lengths is not None:
             if self.which != L.NET_VOCODER:
                 raise ValueError(f"lengths: the {self.NET_NAMES[self.which]} takes equal-length rows only (row lengths reach the vocoder net alone)")
-            lens, hold, _ = DiTEngine._lens_struct(lengths, B, T, gloss=" (input frames per row)")
+            lens, hold, _ = _lens_struct(lengths, B, T, gloss=" (input frames per row)")
             if lens is not None:
                 return self._run_lens(x, B, T, lens, hold)
         out = torch.empty(B, self.out_ch, T * self.out_tmul, dtype=torch.float32, device=self.ctx.device)
@@ -691,39 +748,30 @@ class ConvNet:
 
     def _run_lens(self, x: Tensor, B: int, T: int, lens, hold) -> Tensor:
         out = torch.empty(B, self.out_ch, T * self.out_tmul, dtype=torch.float32, device=self.ctx.device)
-        if self._lens_ws_key != (B, T):
-            n = self.ctx.lib.vb_hifigan_lens_workspace_bytes(self.ctx.handle, B, T)
-            self._lens_ws = torch.empty(max(n, 256), dtype=torch.uint8, device=self.ctx.device)
-            self._lens_ws_key = (B, T)
-        L.check(self.ctx.lib.vb_hifigan_forward_lens(self.ctx.handle, L.ptr(x), B, T, C.byref(lens), L.ptr(out), L.ptr(self._lens_ws), L.stream_ptr()),
+        ws = self._cached("lens", (B, T), lambda: self._bytes(self.ctx.lib.vb_hifigan_lens_workspace_bytes(self.ctx.handle, B, T)))
+        L.check(self.ctx.lib.vb_hifigan_forward_lens(self.ctx.handle, L.ptr(x), B, T, C.byref(lens), L.ptr(out), L.ptr(ws), L.stream_ptr()),
                 "vb_hifigan_forward_lens")
         del hold                         # (the host array of the lengths: read during the call only)
         return out
 
-
-def _convnet_run_chunked(self, x: Tensor, chunk: int, halo: int) -> Tensor:
-    """vocoder only: mel [B,80,T] -> wav [B,1,T*hop] in chunks of `chunk` frames with `halo` frames of context on both sides, the loop,
-    the slicing and the stitching inside the library (vb_hifigan_forward_chunked); identical to run() when halo >= the receptive field."""
-    assert self.which == L.NET_VOCODER
-    x = x.to(self.ctx.device, torch.float32).contiguous()
-    B, Cin, T = x.shape
-    assert Cin == self.in_ch
-    if T <= chunk + 2 * halo:
-        return self.run(x)
-    tc = chunk + 2 * halo
-    out = torch.empty(B, self.out_ch, T * self.out_tmul, dtype=torch.float32, device=self.ctx.device)
-    ws = self._workspace(B, tc)
-    key = (B, tc)
-    if getattr(self, "_chunk_key", None) != key:
-        self._chunk_in = torch.empty(B * self.in_ch * tc, dtype=torch.float32, device=self.ctx.device)
-        self._chunk_out = torch.empty(B * self.out_ch * tc * self.out_tmul, dtype=torch.float32, device=self.ctx.device)
-        self._chunk_key = key
-    L.check(self.ctx.lib.vb_hifigan_forward_chunked(self.ctx.handle, L.ptr(x), B, T, chunk, halo, L.ptr(out), L.ptr(ws), L.ptr(self._chunk_in),
-                                                    L.ptr(self._chunk_out), L.stream_ptr()), "vb_hifigan_forward_chunked")
-    return out
-
-
-ConvNet.run_chunked = _convnet_run_chunked
+    def run_chunked(self, x: Tensor, chunk: int, halo: int) -> Tensor:
+        """vocoder only: mel [B,80,T] -> wav [B,1,T*hop] in chunks of `chunk` frames with `halo` frames of context on both sides, the loop,
+        the slicing and the stitching inside the library (vb_hifigan_forward_chunked); identical to run() when halo >= the receptive field."""
+        assert self.which == L.NET_VOCODER
+        x = x.to(self.ctx.device, torch.float32).contiguous()
+        B, Cin, T = x.shape
+        assert Cin == self.in_ch
+        if T <= chunk + 2 * halo:
+            return self.run(x)
+        tc = chunk + 2 * halo
+        dev = self.ctx.device
+        out = torch.empty(B, self.out_ch, T * self.out_tmul, dtype=torch.float32, device=dev)
+        ws = self._workspace(B, tc)
+        cin, cout = self._cached("chunk", (B, tc), lambda: (torch.empty(B * self.in_ch * tc, dtype=torch.float32, device=dev),
+                                                            torch.empty(B * self.out_ch * tc * self.out_tmul, dtype=torch.float32, device=dev)))
+        L.check(self.ctx.lib.vb_hifigan_forward_chunked(self.ctx.handle, L.ptr(x), B, T, chunk, halo, L.ptr(out), L.ptr(ws), L.ptr(cin), L.ptr(cout),
+                                                        L.stream_ptr()), "vb_hifigan_forward_chunked")
+        return out
 
 
 def _vae_block_builders(nb: "NetBuilder", g: Dict[str, Tensor]):
@@ -763,10 +811,10 @@ def _vae_block_builders(nb: "NetBuilder", g: Dict[str, Tensor]):
         # "weights" are per-batch activations.  split mode: those activations are split into bf16 hi/lo planes on the
         # device (q as [T][C], v as [C][T padded to 32]) so the bf16x3 MFMA kernel does the products too.
         st = nb.gn_stats(x, c)
-        split = nb.x3_like       # (bf16: the per-clip products stay on the bf16x3 kernel, the q / k / v projections fuse the norm)
+        split = nb.row.x3_like      # (bf16: the per-clip products stay on the bf16x3 kernel, the q / k / v projections fuse the norm)
         q, k, v = nb.buf(c, tm), nb.buf(c, tm), nb.buf(c, tm)
         gam, bet = g[p + "norm.weight"], g[p + "norm.bias"]
-        xn = nb.xt_planes(x, c, st, gam, bet, L.ACT_GN, 0.0, 0) if (nb.xt_like and c >= nb.XT_MIN_CO and c % 32 == 0) else -1
+        xn = nb.xt_planes(x, c, st, gam, bet, L.ACT_GN, 0.0, 0) if (nb.row.xt_like and c >= nb.XT_MIN_CO and c % 32 == 0) else -1
         for name, dst, tr in (("q", q, 1 if split else 0), ("k", k, 0), ("v", v, 0 if split else 1)):
             w, b = cw(p + name)
             if xn >= 0:
@@ -888,25 +936,27 @@ def build_vae_encoder(ctx: Context, sd: Dict[str, Tensor], precision: str = "spl
     return ConvNet(ctx, L.NET_VAE_ENCODER, nb, cin, g["quant_conv.weight"].shape[0], 1, in_tmul=2 ** n_down)
 
 
-def build_hifigan(ctx: Context, sd: Dict[str, Tensor], hp: dict, precision: str = "split", fuse_pairs: Sequence[int] = (32, 64)) -> ConvNet:
-    """HifiGanGenerator.forward (vocoder/hifigan/modules/hifigan.py:126-143) as an op list; fully
-    driven by the vocoder's config.yaml keys (SURVEY Q11)."""
-    nb = NetBuilder(ctx.device, precision)
-    # exact-fp32 mode: channel counts whose ResBlock1 pairs run fused (respair_f32_kernel); VB_FP32_PAIRS="32,64" / "" for A/B runs
-    # (fp32mf: the 32-channel pairs run respair_f32w_kernel - minimal filtering in both convolutions, intermediate in LDS; the 64-channel pairs run
-    #  as two unfused minimal-filtering launches: faster than the direct fused pair (1201 -> 1232 mel-s/s) AND than respair_f32w_kernel's 64-channel
-    #  form (VB_FP32_PAIRS=32,64: 1196-1198 against 1224; a 2 x 2 wave grid leaves 16 MFMAs per ring step).  VB_MF_PAIRS_OFF=1 = the direct fused
-    #  pair kernel.  A/Bs: profiles/r06_mf_pairs_ab.txt, profiles/r06_mf_pair32.txt)
-    fp32_pairs = tuple(int(v) for v in os.environ.get("VB_FP32_PAIRS", "32" if precision == "fp32mf" else "32,64").split(",") if v.strip())
+def _wt(sd: Dict[str, Tensor], name: str) -> Tensor:
+    """a vocoder layer's weight: stored plain, or as a weight-norm pair that is folded here"""
+    if name + ".weight" in sd:
+        return sd[name + ".weight"].float()
+    return pack.fold_weight_norm(sd[name + ".weight_g"].float(), sd[name + ".weight_v"].float())
 
-    def wt(name):
-        if name + ".weight" in sd:
-            return sd[name + ".weight"].float()
-        return pack.fold_weight_norm(sd[name + ".weight_g"].float(), sd[name + ".weight_v"].float())
 
+def _wb(sd: Dict[str, Tensor], name: str) -> Tuple[Tensor, Tensor]:
+    """a vocoder convolution's (packed weight, bias), the two arguments of NetBuilder.conv / respair"""
+    return pack.pack_conv(_wt(sd, name)), sd[name + ".bias"]
+
+
+def _vocoder_walk(ctx: Context, nb: NetBuilder, sd: Dict[str, Tensor], hp: dict, ups: str, ups_act: dict, step, post) -> ConvNet:
+    """The walk HiFi-GAN and BigVGAN share: conv_pre; per stage i a transposed conv (key ups.format(i), input activation ups_act) and
+    the nk residual blocks of the stage averaged into one buffer; conv_post + tanh.  step(p, m, r, dst, ch, tm, rk, d, al, be) emits step m
+    (kernel rk, dilation d) of the block with key prefix p, reading r and leaving al * (r + ...) + be * dst in dst; post(x, ch, tm) gives
+    conv_post's input buffer and its input-activation arguments.  The order of nb.buf, nb.release and the ops is the order of the buffer
+    ids: it is part of the program (and of the workspace layout on the device)."""
     nk = len(hp["resblock_kernel_sizes"])
     c0 = hp["upsample_initial_channel"]
-    wpre = wt("conv_pre")
+    wpre = _wt(sd, "conv_pre")
     x = nb.buf(c0, 1)
     nb.conv(L.BUF_INPUT, x, wpre.shape[1], c0, pack.pack_conv(wpre), sd["conv_pre.bias"], k=7, pad=3)
     tm, ch = 1, c0
@@ -914,52 +964,62 @@ def build_hifigan(ctx: Context, sd: Dict[str, Tensor], hp: dict, precision: str 
         cin, ch = c0 // (2 ** i), c0 // (2 ** (i + 1))
         tm *= u
         xu = nb.buf(ch, tm)
-        nb.conv(x, xu, cin, ch, pack.pack_conv_transpose(wt(f"ups.{i}"), u), sd[f"ups.{i}.bias"], in_act=L.ACT_LRELU, in_slope=0.1,
-                tr_stride=u, tr_pad=(k - u) // 2, tr_k=k)
+        nb.conv(x, xu, cin, ch, pack.pack_conv_transpose(_wt(sd, ups.format(i)), u), sd[ups.format(i) + ".bias"], tr_stride=u,
+                tr_pad=(k - u) // 2, tr_k=k, **ups_act)
         nb.release(x)
         xs = nb.buf(ch, tm)
         for j, (rk, rd) in enumerate(zip(hp["resblock_kernel_sizes"], hp["resblock_dilation_sizes"])):
-            n = i * nk + j
             r = xu
             for m, d in enumerate(rd):
                 last = m == len(rd) - 1
                 dst = xs if last else nb.buf(ch, tm)
                 al, be = (1.0 / nk, 0.0 if j == 0 else 1.0) if last else (1.0, 0.0)
-                # (fp32 pair kernel: 16-byte window DMA needs T % 4 == 0 - guaranteed for every mel length, chunked runs included, when the
-                #  stage's length multiplier is a multiple of 4; other stages keep the two unfused launches)
-                fuse = (ch in fuse_pairs and (rk - 1) * d <= 64) if precision in ("split", "bf16", "bf16xt") else \
-                       (ch in fp32_pairs and (rk - 1) * d <= 60 and rk <= 17 and tm % 4 == 0)
-                if hp["resblock"] == "1" and fuse and rk % 2 == 1:
-                    # narrowest, longest stage: both convolutions of the pair in one launch, intermediate kept in LDS
-                    # (measured: 645 us per pair against 2 x 600 us at 32 channels; at 64 channels the fused kernel
-                    #  fits one workgroup per CU only and loses, 1525 us against 2 x 640 us - so it is not used there)
-                    nb.respair(r, dst, ch, pack.pack_conv(wt(f"resblocks.{n}.convs1.{m}")), sd[f"resblocks.{n}.convs1.{m}.bias"],
-                               pack.pack_conv(wt(f"resblocks.{n}.convs2.{m}")), sd[f"resblocks.{n}.convs2.{m}.bias"], rk, d, 0.1, al, be)
-                elif hp["resblock"] == "1":
-                    t1 = nb.buf(ch, tm)
-                    # the LeakyReLU between the two convolutions is applied by the FIRST one's epilogue (t1 has no other reader), not by the
-                    # second one's window pass: the same values (max(v, 0.1 v) either way), one in-place LDS pass per 16-channel chunk less
-                    # in every second convolution (round 6; VB_LRELU_IN_WINDOW=1 keeps the old op list for the A/B)
-                    mid_out = not os.environ.get("VB_LRELU_IN_WINDOW")
-                    nb.conv(r, t1, ch, ch, pack.pack_conv(wt(f"resblocks.{n}.convs1.{m}")), sd[f"resblocks.{n}.convs1.{m}.bias"], k=rk,
-                            dil=d, pad=(rk * d - d) // 2, in_act=L.ACT_LRELU, in_slope=0.1,
-                            out_act=L.ACT_LRELU if mid_out else L.ACT_NONE, out_slope=0.1 if mid_out else 0.0)
-                    nb.conv(t1, dst, ch, ch, pack.pack_conv(wt(f"resblocks.{n}.convs2.{m}")), sd[f"resblocks.{n}.convs2.{m}.bias"], k=rk,
-                            pad=(rk - 1) // 2, in_act=L.ACT_NONE if mid_out else L.ACT_LRELU, in_slope=0.0 if mid_out else 0.1, res=r, alpha=al,
-                            beta=be)
-                    nb.release(t1)
-                else:
-                    nb.conv(r, dst, ch, ch, pack.pack_conv(wt(f"resblocks.{n}.convs.{m}")), sd[f"resblocks.{n}.convs.{m}.bias"], k=rk,
-                            dil=d, pad=(rk * d - d) // 2, in_act=L.ACT_LRELU, in_slope=0.1, res=r, alpha=al, beta=be)
+                step(f"resblocks.{i * nk + j}.", m, r, dst, ch, tm, rk, d, al, be)
                 if r != xu:
                     nb.release(r)
                 r = dst
         nb.release(xu)
         x = xs
-    wpost = wt("conv_post")
-    nb.conv(x, L.BUF_OUTPUT, ch, wpost.shape[0], pack.pack_conv(wpost), sd["conv_post.bias"], k=7, pad=3, in_act=L.ACT_LRELU,
-            in_slope=0.01, out_act=L.ACT_TANH)
+    x, post_act = post(x, ch, tm)
+    wpost = _wt(sd, "conv_post")
+    nb.conv(x, L.BUF_OUTPUT, ch, wpost.shape[0], pack.pack_conv(wpost), sd["conv_post.bias"], k=7, pad=3, out_act=L.ACT_TANH, **post_act)
     return ConvNet(ctx, L.NET_VOCODER, nb, wpre.shape[1], wpost.shape[0], tm)
+
+
+def build_hifigan(ctx: Context, sd: Dict[str, Tensor], hp: dict, precision: str = "split", fuse_pairs: Sequence[int] = (32, 64)) -> ConvNet:
+    """HifiGanGenerator.forward (vocoder/hifigan/modules/hifigan.py:126-143) as an op list; fully
+    driven by the vocoder's config.yaml keys (SURVEY Q11)."""
+    nb = NetBuilder(ctx.device, precision)
+    fp32_rule = nb.row.fp32_pairs is not None
+    fp32_pairs = tuple(int(v) for v in _switch("VB_FP32_PAIRS", nb.row.fp32_pairs or "32,64").split(",") if v.strip())
+
+    def step(p, m, r, dst, ch, tm, rk, d, al, be):
+        # (fp32 pair kernel: 16-byte window DMA needs T % 4 == 0 - guaranteed for every mel length, chunked runs included, when the
+        #  stage's length multiplier is a multiple of 4; other stages keep the two unfused launches)
+        fuse = (ch in fp32_pairs and (rk - 1) * d <= 60 and rk <= 17 and tm % 4 == 0) if fp32_rule else (ch in fuse_pairs and (rk - 1) * d <= 64)
+        if hp["resblock"] == "1" and fuse and rk % 2 == 1:
+            # narrowest, longest stage: both convolutions of the pair in one launch, intermediate kept in LDS
+            # (measured: 645 us per pair against 2 x 600 us at 32 channels; at 64 channels the fused kernel
+            #  fits one workgroup per CU only and loses, 1525 us against 2 x 640 us - so it is not used there)
+            nb.respair(r, dst, ch, *_wb(sd, f"{p}convs1.{m}"), *_wb(sd, f"{p}convs2.{m}"), rk, d, 0.1, al, be)
+        elif hp["resblock"] == "1":
+            t1 = nb.buf(ch, tm)
+            # the LeakyReLU between the two convolutions is applied by the FIRST one's epilogue (t1 has no other reader), not by the
+            # second one's window pass: the same values (max(v, 0.1 v) either way), one in-place LDS pass per 16-channel chunk less
+            # in every second convolution (round 6)
+            mid_out = not _switch("VB_LRELU_IN_WINDOW")
+            nb.conv(r, t1, ch, ch, *_wb(sd, f"{p}convs1.{m}"), k=rk, dil=d, pad=(rk * d - d) // 2, in_act=L.ACT_LRELU, in_slope=0.1,
+                    out_act=L.ACT_LRELU if mid_out else L.ACT_NONE, out_slope=0.1 if mid_out else 0.0)
+            nb.conv(t1, dst, ch, ch, *_wb(sd, f"{p}convs2.{m}"), k=rk, pad=(rk - 1) // 2, in_act=L.ACT_NONE if mid_out else L.ACT_LRELU,
+                    in_slope=0.0 if mid_out else 0.1, res=r, alpha=al, beta=be)
+            nb.release(t1)
+        else:
+            nb.conv(r, dst, ch, ch, *_wb(sd, f"{p}convs.{m}"), k=rk, dil=d, pad=(rk * d - d) // 2, in_act=L.ACT_LRELU, in_slope=0.1, res=r,
+                    alpha=al, beta=be)
+
+    # differences from the shared walk: the upsampler sits at ups.{i} behind a LeakyReLU(0.1), conv_post behind a LeakyReLU(0.01)
+    return _vocoder_walk(ctx, nb, sd, hp, "ups.{}", dict(in_act=L.ACT_LRELU, in_slope=0.1), step,
+                         lambda x, ch, tm: (x, dict(in_act=L.ACT_LRELU, in_slope=0.01)))
 
 
 def build_bigvgan(ctx: Context, sd: Dict[str, Tensor], hp: dict, precision: str = "split") -> ConvNet:
@@ -967,12 +1027,6 @@ def build_bigvgan(ctx: Context, sd: Dict[str, Tensor], hp: dict, precision: str 
     front of it) + the mean of the AMP blocks (anti-aliased Snake/SnakeBeta -> conv -> ... + x), anti-aliased activation,
     conv_post, tanh.  Driven by the args.yml keys; weights are weight-norm pairs like the HiFi-GAN's."""
     nb = NetBuilder(ctx.device, precision)
-
-    def wt(name):
-        if name + ".weight" in sd:
-            return sd[name + ".weight"].float()
-        return pack.fold_weight_norm(sd[name + ".weight_g"].float(), sd[name + ".weight_v"].float())
-
     logscale = bool(hp["snake_logscale"])
 
     def act(name, x, ch, tm):
@@ -980,48 +1034,20 @@ def build_bigvgan(ctx: Context, sd: Dict[str, Tensor], hp: dict, precision: str 
         nb.aa_act(x, out, ch, sd[name + ".act.alpha"], sd.get(name + ".act.beta"), logscale)
         return out
 
-    nk = len(hp["resblock_kernel_sizes"])
-    c0 = hp["upsample_initial_channel"]
-    wpre = wt("conv_pre")
-    x = nb.buf(c0, 1)
-    nb.conv(L.BUF_INPUT, x, wpre.shape[1], c0, pack.pack_conv(wpre), sd["conv_pre.bias"], k=7, pad=3)
-    tm, ch = 1, c0
-    for i, (u, k) in enumerate(zip(hp["upsample_rates"], hp["upsample_kernel_sizes"])):
-        cin, ch = c0 // (2 ** i), c0 // (2 ** (i + 1))
-        tm *= u
-        xu = nb.buf(ch, tm)
-        nb.conv(x, xu, cin, ch, pack.pack_conv_transpose(wt(f"ups.{i}.0"), u), sd[f"ups.{i}.0.bias"], tr_stride=u, tr_pad=(k - u) // 2, tr_k=k)
-        nb.release(x)
-        xs = nb.buf(ch, tm)
-        for j, (rk, rd) in enumerate(zip(hp["resblock_kernel_sizes"], hp["resblock_dilation_sizes"])):
-            n = i * nk + j
-            r = xu
-            for m, d in enumerate(rd):
-                last = m == len(rd) - 1
-                dst = xs if last else nb.buf(ch, tm)
-                al, be = (1.0 / nk, 0.0 if j == 0 else 1.0) if last else (1.0, 0.0)
-                if hp["resblock"] == "1":
-                    a1 = act(f"resblocks.{n}.activations.{2 * m}", r, ch, tm)
-                    t1 = nb.buf(ch, tm)
-                    nb.conv(a1, t1, ch, ch, pack.pack_conv(wt(f"resblocks.{n}.convs1.{m}")), sd[f"resblocks.{n}.convs1.{m}.bias"], k=rk,
-                            dil=d, pad=(rk * d - d) // 2)
-                    nb.release(a1)
-                    a2 = act(f"resblocks.{n}.activations.{2 * m + 1}", t1, ch, tm)
-                    nb.release(t1)
-                    nb.conv(a2, dst, ch, ch, pack.pack_conv(wt(f"resblocks.{n}.convs2.{m}")), sd[f"resblocks.{n}.convs2.{m}.bias"], k=rk,
-                            pad=(rk - 1) // 2, res=r, alpha=al, beta=be)
-                    nb.release(a2)
-                else:
-                    a1 = act(f"resblocks.{n}.activations.{m}", r, ch, tm)
-                    nb.conv(a1, dst, ch, ch, pack.pack_conv(wt(f"resblocks.{n}.convs.{m}")), sd[f"resblocks.{n}.convs.{m}.bias"], k=rk,
-                            dil=d, pad=(rk * d - d) // 2, res=r, alpha=al, beta=be)
-                    nb.release(a1)
-                if r != xu:
-                    nb.release(r)
-                r = dst
-        nb.release(xu)
-        x = xs
-    ap = act("activation_post", x, ch, tm)
-    wpost = wt("conv_post")
-    nb.conv(ap, L.BUF_OUTPUT, ch, wpost.shape[0], pack.pack_conv(wpost), sd["conv_post.bias"], k=7, pad=3, out_act=L.ACT_TANH)
-    return ConvNet(ctx, L.NET_VOCODER, nb, wpre.shape[1], wpost.shape[0], tm)
+    def step(p, m, r, dst, ch, tm, rk, d, al, be):
+        if hp["resblock"] == "1":
+            a1 = act(f"{p}activations.{2 * m}", r, ch, tm)
+            t1 = nb.buf(ch, tm)
+            nb.conv(a1, t1, ch, ch, *_wb(sd, f"{p}convs1.{m}"), k=rk, dil=d, pad=(rk * d - d) // 2)
+            nb.release(a1)
+            a2 = act(f"{p}activations.{2 * m + 1}", t1, ch, tm)
+            nb.release(t1)
+            nb.conv(a2, dst, ch, ch, *_wb(sd, f"{p}convs2.{m}"), k=rk, pad=(rk - 1) // 2, res=r, alpha=al, beta=be)
+            nb.release(a2)
+        else:
+            a1 = act(f"{p}activations.{m}", r, ch, tm)
+            nb.conv(a1, dst, ch, ch, *_wb(sd, f"{p}convs.{m}"), k=rk, dil=d, pad=(rk * d - d) // 2, res=r, alpha=al, beta=be)
+            nb.release(a1)
+
+    # differences from the shared walk: the upsampler sits at ups.{i}.0 with no activation, conv_post behind an anti-aliased activation
+    return _vocoder_walk(ctx, nb, sd, hp, "ups.{}.0", {}, step, lambda x, ch, tm: (act("activation_post", x, ch, tm), {}))
