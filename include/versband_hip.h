@@ -288,8 +288,8 @@ int vb_sample_cfg_sched(vb_ctx* ctx, float* x, const void* cond, int B, int n_br
  * keep, rows and guidance compose unchanged (all are token-local); single-branch steps read the same table.  The lengths reach the
  * device through a launch argument at the head of the step loop, which a captured graph holds: the graph key holds the VALUES of len,
  * so another set of lengths on the same buffers captures its own graph and a plain call never replays a lengths graph.  Hosts detect
- * the feature by the presence of these symbols (vb_abi_version() stays 3).  The VAE entry points, BigVGAN and the chunked vocoder take equal-length rows only; the HiFi-GAN
- * takes row lengths through vb_hifigan_forward_lens (below). */
+ * the feature by the presence of these symbols (vb_abi_version() stays 3).  The VAE encoder, BigVGAN and the chunked vocoder take equal-length rows only; the HiFi-GAN
+ * takes row lengths through vb_hifigan_forward_lens and the VAE decoder through vb_vae_decode_lens (below). */
 typedef struct { const int32_t* len; } vb_lens;                   /* len: HOST array of B row lengths, 1 <= len[b] <= T */
 int vb_dit_precompute_cond_lens(vb_ctx* ctx, const float* t5, const int64_t* midi, const int64_t* beats, int B, int n_branch, int T,
                                 int T_mel, int L, const vb_lens* lens, void* cond, void* ws, void* stream);
@@ -412,12 +412,47 @@ int vb_hifigan_forward(vb_ctx* ctx, const float* mel, int B, int T, float* wav, 
  * A host that wants bit-exact rows groups its clips by length mod 4 (harness.plan_vocoder_calls).
  * Refused with VB_E_INVALID before anything is launched, naming the op and why: a vocoder program with an op other than VB_OP_CONV /
  * VB_OP_RESPAIR / VB_OP_XT_PLANES (BigVGAN's VB_OP_AA_ACT: its anti-aliasing filters replicate-pad at the row end), an input activation
- * other than none / LeakyReLU, GroupNorm statistics, dynamic channel counts, w_buf weights, a transposed output.  The VAE nets and
- * vb_hifigan_forward_chunked take no lengths.
+ * other than none / LeakyReLU, GroupNorm statistics, dynamic channel counts, w_buf weights, a transposed output.  The VAE encoder and
+ * vb_hifigan_forward_chunked take no lengths; the VAE decoder has its own entry point (vb_vae_decode_lens).
  * ws: vb_hifigan_lens_workspace_bytes(ctx, B, T) bytes = vb_net_workspace_bytes + the masked mel + the length table.  Hosts detect the
  * feature by the presence of these symbols (vb_abi_version() stays 3). */
 size_t vb_hifigan_lens_workspace_bytes(vb_ctx* ctx, int B, int T);
 int vb_hifigan_forward_lens(vb_ctx* ctx, const float* mel, int B, int T, const vb_lens* lens, float* wav, void* ws, void* stream);
+/* VAE decoder with ROW LENGTHS (build-defined): latents of different lengths as rows of one decode call.  z [B][zc][T], T the padded latent
+ * length; lens->len the HOST array of B latent lengths, 1 <= len[b] <= T, B <= 64, checked like the sampler's (VB_E_INVALID names the row,
+ * nothing is launched and mel is unchanged).  mel [B][80][2T]: row b holds 2*len[b] frames that are vb_vae_decode on that clip alone,
+ * followed by exact zeros.  The caller's latent padding is never read into a valid frame (it may hold NaN), and neither is anything
+ * already in the workspace (0xFF bytes give the bits of a zeroed one).  Row b does not depend on the other rows' contents or lengths.
+ * lens == NULL, len == NULL or every row full is vb_vae_decode on the same buffers: same launches, same bits.
+ * How it works.  The latent is copied into the workspace with its tails zeroed and every op that writes an activation buffer is followed
+ * by the tail-zero launch of the HiFi-GAN call (a transposed output [T][C] as one row of T*C samples per clip), so every raw buffer a
+ * convolution reads is zero behind row b's end.  Zero tails alone do not settle the decoder; three things read the device table of lengths:
+ *   GroupNorm statistics     gn_stats_lens_kernel reduces row b's own cpg x len[b]*tmul samples at pitch T*tmul with the thread assignment,
+ *                            the float4 grouping (x+y)+(z+w) and the two-pass final order of the plain kernel on the compacted clip.
+ *   GroupNorm (+ swish) in   every consumer pads the ACTIVATED tensor with zeros from len[b]*tmul on instead of T*tmul: conv_tile's one bound for
+ *                            the register-staged convolutions (fp32, split, bf16), gn_apply_kernel (zeros behind the row end),
+ *                            xt_planes_kernel (zero rows behind it).
+ *   attention                softmax_rows_t_lens_kernel takes max and sum over the keys c < len[b] (lane stride and order of the plain kernel
+ *                            at len[b] columns) and writes exact zeros for the keys and queries behind the row's end; q, k, v (transposed
+ *                            or not) are tail-zeroed and the split planes are made from them, so every added term of the two products -
+ *                            Co or Ci = the padded T - is an exact 0 * 0.  The score buffer gets no tail pass: only the row's own block is read.
+ * THE ROUTE RULE.  Beside (T*tmul) % 4 and row alignment (the vocoder's rule: staged epilogues, quad window rows, minimal filtering, and
+ * here the float4 paths of gn_apply / gn_stats), the attention's two products take a channel count from the length.  None of those
+ * predicates changes a bit: Ci % 16 and Co % 4 choose between the DMA-fed and the register-staged exact-fp32 kernel, which are
+ * bit-identical (one chunk order); the split planes round Ci to 32 (Ci_pad, cpad) with zero columns, and a longer padded Ci only appends
+ * all-zero chunks behind the clip's own; Ci % 64 is a condition of the conv-as-GEMM route, which a product with per-clip weights never
+ * takes.  (T and B also enter the tile choice; tiles never change a bit.)  What changes bits is the vocoder's residue, hence:
+ *   len[b] == T (mod 4)   row b's 2*len[b] frames equal vb_vae_decode on that clip alone BIT FOR BIT, in every precision;
+ *   otherwise             the two agree to the precision's roundoff (an op may run the direct kernel in one call and the F(2,3) kernel in
+ *                         the other, or a glue kernel its float4 path).
+ * No op had to be excepted.  A host that wants bit-exact rows groups its clips by length mod 4 (harness.plan_decode_calls).
+ * Refused with VB_E_INVALID before anything is launched, naming the op and why: VB_OP_AA_ACT, VB_OP_RESPAIR, in_stride > 1, tr_stride > 1
+ * (ops the decoder's program does not contain).  The VAE encoder (Downsample1D pads on the right of the row's own end), BigVGAN and
+ * vb_hifigan_forward_chunked take no lengths.
+ * ws: vb_vae_decode_lens_workspace_bytes(ctx, B, T) bytes = vb_net_workspace_bytes + the masked latent + the length table.  Hosts detect
+ * the feature by the presence of these symbols (vb_abi_version() stays 3, vb_net_op is unchanged). */
+size_t vb_vae_decode_lens_workspace_bytes(vb_ctx* ctx, int B, int T);
+int vb_vae_decode_lens(vb_ctx* ctx, const float* z, int B, int T, const vb_lens* lens, float* mel, void* ws, void* stream);
 
 /* Long-form generation (BASELINE configs[4]; build-defined, the reference stops at max_len = 1500 latent tokens: vocal2music_moe.py:421).
  * vb_crossfade_windows: window results parts [nw*B][C][n] (row = w*B + b; windows of equal length n starting at starts[w], a HOST array,
@@ -590,6 +625,12 @@ int vb_conv1d_bf16_xt(const float* x, const void* w_bf16, int ci_pad, const floa
 size_t vb_xt_planes_bytes(int B, int C, int T_in, int upsample2, int nplanes);
 int vb_xt_planes(const float* x, int B, int C, int T_in, int upsample2, int in_act, float in_slope, const float* gn_mean, const float* gn_rstd,
                  const float* gn_gamma, const float* gn_beta, int gn_groups, int nplanes, void* planes, void* stream);
+/* The two reductions of vb_vae_decode_lens alone (build-defined units).  len: DEVICE array of B row lengths, 1 <= len[b] <= T; NULL runs
+ * the plain kernel.  vb_gn_stats_lens: x [B][C][T] -> mean / rstd [B][groups] (eps 1e-6) over row b's first len[b] samples per channel,
+ * the bits of the plain kernel on the compacted clip [C][len[b]].  vb_softmax_rows_t_lens: s [B][T][T] -> the transposed softmax
+ * out_t [B][T][T] of row b's leading len[b] x len[b] block, exact zeros elsewhere. */
+int vb_gn_stats_lens(const float* x, int B, int C, int T, int groups, const int32_t* len, float* mean, float* rstd, void* stream);
+int vb_softmax_rows_t_lens(const float* s, int B, int T, const int32_t* len, float* out_t, void* stream);
 /* HiFi-GAN ResBlock1 pair in single-pass bf16, one launch (respair_bf16.hip):
  *   out = beta*out + alpha*(x + b2 + conv2_{k,1}( RN_bf16( lrelu(b1 + conv1_{k,dil}( RN_bf16(lrelu(x)) )) ) ))
  * both convolutions with RN-bf16 weights (w1_bf16 / w2_bf16: one plane [k][C co][C ci] each, pack.py:pack_conv_bf16), exact products, fp32

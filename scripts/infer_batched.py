@@ -9,9 +9,9 @@ group is formed, so memory does not grow with the manifest and a crash loses one
 calls of test_final.py's loop, one per (item, scale).  `--synthetic_frames` additionally accepts a comma list that cycles over the
 synthetic items; every other flag is test_final.py's and is parsed by its parser.  `--length_slack N` lets consecutive items whose latent
 lengths differ by at most N tokens share a call too: the group is padded to its longest member and sampled with per-row lengths
-(vb_sample_cfg_lens - a row is the call on that clip alone), then every row is cut to its own length, rows of equal length are
-decoded together, and the decoded mels are vocoded with per-row lengths (vb_hifigan_forward_lens) in one call per residue of the mel
-length mod 4 - two at most - where a row again is the call on that clip alone.
+(vb_sample_cfg_lens - a row is the call on that clip alone), then the rows are decoded with per-row lengths (vb_vae_decode_lens) in one
+call per residue of the latent length mod 4 and cut to their own lengths, and the decoded mels are vocoded with per-row lengths
+(vb_hifigan_forward_lens) in one call per residue of the mel length mod 4 - two at most; in both a row again is the call on that clip alone.
 """
 from __future__ import annotations
 
@@ -31,7 +31,7 @@ for p in (ROOT, HERE):
 import test_final as loop  # noqa: E402
 from versband_amd import dist as vdist  # noqa: E402
 from versband_amd.harness import (MEL_DOWNSAMPLE, InferDataset, check_items_per_batch, parse_frames,  # noqa: E402
-                                  plan_row_batches, plan_vocoder_calls, save_rows_to_tsv, stream_length_groups, write_wav_pcm16)
+                                  plan_decode_calls, plan_row_batches, plan_vocoder_calls, save_rows_to_tsv, stream_length_groups, write_wav_pcm16)
 from versband_amd.model import normalize_loudness  # noqa: E402
 
 
@@ -164,14 +164,15 @@ def sample_group(args, sampler, vocoder, group, scales, device):
             wav = vocoder.spec2wav_batch(mel).cpu().numpy()
             done.update({r: (mel[r], wav[r]) for r in range(len(rows))})
         else:
-            # the VAE takes rows of one length: rows of equal length are decoded together.  The vocoder takes row lengths: the decoded
-            # mels are padded to the longest of their group (harness.plan_vocoder_calls: lengths that agree mod 4, where a row equals
-            # the call on that clip alone bit for bit), vocoded in one call and cut to their own lengths
+            # The VAE decoder and the vocoder take row lengths: the sampled latents are cut to the longest of their group
+            # (harness.plan_decode_calls: lengths that agree mod 4, where a row equals the decode of that clip alone bit for bit), decoded
+            # in one call and cut to their own lengths; the decoded mels are padded to the longest of their group
+            # (harness.plan_vocoder_calls: mod 4), vocoded in one call and cut again
             mels = {}
-            for length in dict.fromkeys(row_lengths):
-                idx = [r for r in range(len(rows)) if row_lengths[r] == length]
-                mel = sampler.model.decode_first_stage(z[idx][:, :, :length].contiguous())
-                mels.update({r: mel[j] for j, r in enumerate(idx)})
+            for dc in plan_decode_calls(row_lengths):
+                zz = z[dc["rows"]][:, :, :dc["length"]].contiguous()
+                mel = sampler.model.decode_first_stage(zz, **({"lengths": dc["lengths"]} if dc["lengths"] else {}))
+                mels.update({r: mel[j, :, :row_lengths[r] * MEL_DOWNSAMPLE] for j, r in enumerate(dc["rows"])})
             for vc in plan_vocoder_calls([mels[r].shape[-1] for r in range(len(rows))]):
                 batch = torch.stack([torch.nn.functional.pad(mels[r], (0, vc["length"] - mels[r].shape[-1])) for r in vc["rows"]])
                 wav = vocoder.spec2wav_batch(batch, **({"lengths": vc["lengths"]} if vc["lengths"] else {})).cpu().numpy()

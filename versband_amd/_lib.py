@@ -146,6 +146,10 @@ PROTOTYPES = {
     "vb_hifigan_forward": (c_int, [P, P, c_int, c_int, P, P, P]),
     "vb_hifigan_lens_workspace_bytes": (c_size_t, [P, c_int, c_int]),
     "vb_hifigan_forward_lens": (c_int, [P, P, c_int, c_int, C.POINTER(Lens), P, P, P]),
+    "vb_vae_decode_lens_workspace_bytes": (c_size_t, [P, c_int, c_int]),
+    "vb_vae_decode_lens": (c_int, [P, P, c_int, c_int, C.POINTER(Lens), P, P, P]),
+    "vb_gn_stats_lens": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "vb_softmax_rows_t_lens": (c_int, [P, c_int, c_int, P, P, P]),
     "vb_crossfade_windows": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
     "vb_hifigan_forward_chunked": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P, P, P]),
     "vb_melnet_load": (c_int, [P, C.POINTER(MelConfig), P, P]),

@@ -188,6 +188,16 @@ int vb_xt_planes(const float* x, int B, int C, int T_in, int upsample2, int in_a
     return launch_xt_planes(x, gn_mean, gn_rstd, gn_gamma, gn_beta, gn_groups, in_act, in_slope, upsample2, B, C, T_in, nplanes, (bf16_t*)planes,
                             (hipStream_t)stream);
 }
+int vb_gn_stats_lens(const float* x, int B, int C, int T, int groups, const int32_t* len, float* mean, float* rstd, void* stream) {
+    if (!x || !mean || !rstd || B < 1 || C < 1 || T < 1 || groups < 1) VB_FAIL(VB_E_INVALID, "gn_stats_lens: null pointer or B/C/T/groups < 1");
+    if (!len) return launch_gn_stats(x, B, C, T, groups, 1e-6f, mean, rstd, (hipStream_t)stream);
+    return launch_gn_stats_lens(x, B, C, T, groups, 1e-6f, len, 1, mean, rstd, (hipStream_t)stream);
+}
+int vb_softmax_rows_t_lens(const float* s, int B, int T, const int32_t* len, float* out_t, void* stream) {
+    if (!s || !out_t || B < 1 || T < 1) VB_FAIL(VB_E_INVALID, "softmax_rows_t_lens: null pointer or B/T < 1");
+    if (!len) return launch_softmax_rows_t(s, B, T, T, out_t, (hipStream_t)stream);
+    return launch_softmax_rows_t_lens(s, B, T, len, 1, out_t, (hipStream_t)stream);
+}
 size_t vb_conv1d_bf16_xt_scratch_bytes(int B, int Ci, int T_in, int upsample2) { return vb_xt_planes_bytes(B, Ci, T_in, upsample2, 1); }
 int vb_conv1d_bf16_xt(const float* x, const void* w_bf16, int ci_pad, const float* bias, int B, int Ci, int T_in, int Co, int ksize, int dil,
                       int pad, int tr_stride, int tr_pad, int tr_k, int T_out, int upsample2, int in_stride, int in_phase, int in_act,

@@ -27,6 +27,8 @@ static int conv1d_fill(const ConvArgs& a, ConvDev& d, int& n_count) {
     if (a.xt && a.T_out > (a.upsample2 ? 2 * a.T_in : a.T_in) + XT_HEAD)
         VB_FAIL(VB_E_INVALID, "conv1d: XT input of %d positions cannot feed %d outputs", a.upsample2 ? 2 * a.T_in : a.T_in, a.T_out);
     d.stage_epi = 0;
+    d.row_len = a.row_len; d.len_mul = a.len_mul;
+    if (a.row_len && (d.in_stride > 1 || a.x_bmod || a.len_mul < 1)) VB_FAIL(VB_E_INVALID, "conv1d: row lengths with in_stride, folded clips or len_mul < 1");
     if (a.tr_stride > 1) {
         d.phases = a.tr_stride; d.tr_pad = a.tr_pad; d.ntaps = (a.tr_k + a.tr_stride - 1) / a.tr_stride; d.dil = 1;
         n_count = cdiv(a.T_out, a.tr_stride);

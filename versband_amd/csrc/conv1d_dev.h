@@ -31,6 +31,7 @@ struct ConvDev {
     int mf_abl;              // conv1d_f32w: timing-only ablations (VB_F32W_ABL: 1 = no in-place window pass, 2 = no epilogue, 4 = no window DMA after the first)
 #endif
     int g_nt, g_nco, g_ntb, g_tbx;   // conv1d_f32g_kernel: time tiles, channel tiles, (time tile, clip, phase) units, units per XCD
+    const int* row_len; int len_mul; // register-staged kernels (conv_tile): row b's activated input ends at row_len[b] * len_mul; null = T_eff
 };
 
 // One output element of the [b][co][t] epilogues.  The arithmetic is pinned (no implicit contraction, one explicit fma): the direct

@@ -37,6 +37,7 @@ __device__ __forceinline__ bool conv_tile(const ConvDev& p, int t_tile, int co_t
     if (g.n0 >= g.n_count) return false;
     g.xw_used = t_tile + (p.ntaps - 1) * p.dil;
     g.T_eff = p.upsample2 ? 2 * p.T_in : (p.T_in - p.in_phase + p.in_stride - 1) / p.in_stride;
+    if (p.row_len) g.T_eff = p.row_len[g.b] * p.len_mul;        // row lengths: the one bound of the window's zero padding
     g.xb = p.x_bmod > 0 ? (g.b % p.x_bmod) : g.b;
     g.xbase = p.x + (int64_t)g.xb * p.x_bstride;
     return true;

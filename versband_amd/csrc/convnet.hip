@@ -16,8 +16,11 @@ static size_t net_ws_bytes(const NetProgram& n, int B, int T, std::vector<size_t
     }
     return off;
 }
-// nl (vb_hifigan_forward_lens, after net_lens_check): `in` is the masked copy of the input, every op that writes an activation buffer is
-// followed by launch_tail_zero on it, and the fused pairs end row b's intermediate at its own length.  Null: the plain run, nothing added.
+// nl (vb_hifigan_forward_lens / vb_vae_decode_lens, after net_lens_check): `in` is the masked copy of the input, every op that writes an
+// activation buffer is followed by launch_tail_zero on it, and the fused pairs end row b's intermediate at its own length.  The VAE decoder's
+// ops that a zero tail does not settle read the device table: GroupNorm statistics run over the row's own samples, every GroupNorm (+ swish)
+// consumer ends the ACTIVATED tensor at the row's own length, the attention softmax runs over the row's own keys.  Null: the plain run,
+// nothing added.
 int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, void* ws, hipStream_t st, const NetLens* nl) {
     NetProgram& n = ctx->nets[which];
     if (!n.loaded) VB_FAIL(VB_E_STATE, "net %d not loaded", which);
@@ -49,9 +52,12 @@ int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, v
         const vb_net_op& o = n.ops[oi];
         if (o.kind == VB_OP_GN_STATS) {
             float* stp = ptr(o.stats);
-            VB_TRY(launch_gn_stats(ptr(o.x), B, o.Ci, tlen(o.x), o.gn_groups, 1e-6f, stp, stp + (size_t)B * o.gn_groups, st));
+            if (nl) VB_TRY(launch_gn_stats_lens(ptr(o.x), B, o.Ci, tlen(o.x), o.gn_groups, 1e-6f, nl->table, tmul(o.x), stp, stp + (size_t)B * o.gn_groups, st));
+            else VB_TRY(launch_gn_stats(ptr(o.x), B, o.Ci, tlen(o.x), o.gn_groups, 1e-6f, stp, stp + (size_t)B * o.gn_groups, st));
         } else if (o.kind == VB_OP_SOFTMAX_T) {
-            VB_TRY(launch_softmax_rows_t(ptr(o.x), B, tlen(o.x), tlen(o.x), ptr(o.out), st));
+            // (lengths: the whole transposed square is written, zeros outside the row's own block - it needs no tail pass)
+            if (nl) VB_TRY(launch_softmax_rows_t_lens(ptr(o.x), B, tlen(o.x), nl->table, tmul(o.x), ptr(o.out), st));
+            else VB_TRY(launch_softmax_rows_t(ptr(o.x), B, tlen(o.x), tlen(o.x), ptr(o.out), st));
         } else if (o.kind == VB_OP_CONV) {
             ConvArgs a;
             a.x = ptr(o.x); a.x_bstride = bstride(o.x); a.T_in = tlen(o.x);
@@ -70,6 +76,8 @@ int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, v
                 a.gn_mean = stp; a.gn_rstd = stp + (size_t)B * o.gn_groups; a.gn_gamma = o.gn_gamma; a.gn_beta = o.gn_beta;
                 a.gn_groups = o.gn_groups;
             }
+            // lengths: GroupNorm maps a zero tail to something else, so the window's zero padding starts at the row's own end
+            if (nl && (o.in_act == ACT_GN || o.in_act == ACT_GN_SWISH)) { a.row_len = nl->table; a.len_mul = tmul(o.x) * (o.upsample2 ? 2 : 1); }
             a.out = ptr(o.out); a.out_bstride = bstride(o.out); a.T_out = tlen(o.out);
             if (o.res != -1) { a.res = ptr(o.res); a.res_bstride = bstride(o.res); }
             a.alpha = o.alpha; a.beta = o.beta; a.acc_scale = o.acc_scale; a.out_act = o.out_act; a.out_slope = o.out_slope;
@@ -102,11 +110,12 @@ int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, v
         } else if (o.kind == VB_OP_GN_APPLY) {
             float* stp = ptr(o.stats);
             VB_TRY(launch_gn_apply(ptr(o.x), stp, stp + (size_t)B * o.gn_groups, o.gn_gamma, o.gn_beta, B, o.Ci, tlen(o.x), o.gn_groups,
-                                   o.in_act == ACT_GN_SWISH ? 1 : 0, ptr(o.out), st));
+                                   o.in_act == ACT_GN_SWISH ? 1 : 0, ptr(o.out), st, nl ? nl->table : nullptr, tmul(o.x)));
         } else if (o.kind == VB_OP_XT_PLANES) {
             const float* stp = o.stats >= 0 ? ptr(o.stats) : nullptr;
             VB_TRY(launch_xt_planes(ptr(o.x), stp, stp ? stp + (size_t)B * o.gn_groups : nullptr, o.gn_gamma, o.gn_beta, o.gn_groups, o.in_act, o.in_slope,
-                                    o.upsample2, B, o.Ci, tlen(o.x), o.wfmt == VB_WFMT_BF16 ? 1 : 2, reinterpret_cast<bf16_t*>(ptr(o.out)), st));
+                                    o.upsample2, B, o.Ci, tlen(o.x), o.wfmt == VB_WFMT_BF16 ? 1 : 2, reinterpret_cast<bf16_t*>(ptr(o.out)), st,
+                                    nl ? nl->table : nullptr, tmul(o.x) * (o.upsample2 ? 2 : 1)));
         } else if (o.kind == VB_OP_AA_ACT) {
             VB_TRY(launch_aa_act(ptr(o.x), o.gn_gamma, o.gn_beta, o.w, B, o.Ci, tlen(o.x), ptr(o.out), st));
         } else if (o.kind == VB_OP_RESPAIR) {
@@ -134,19 +143,38 @@ int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, v
         } else {
             VB_FAIL(VB_E_INVALID, "net op %zu: bad kind %d", oi, o.kind);
         }
-        // (the planes of VB_OP_XT_PLANES need no pass: they are made from a buffer whose tails are zero, and act(0) = 0 rounds to zero rows)
-        if (nl && o.kind != VB_OP_XT_PLANES) VB_TRY(launch_tail_zero(ptr(o.out), nl->lp, nl->table, B, chans(o.out), T, tmul(o.out), st));
+        // The tails of what the op wrote.  No pass: the planes of VB_OP_XT_PLANES (zero rows behind the row's end by its own bound) and of
+        // VB_OP_SPLIT_PLANES (made from buffers whose tails are zero), the statistics, the transposed softmax (writes its zeros itself) and the
+        // square score buffer, of which the lengths softmax reads the row's own block alone.  A transposed output [T][C] ends in the
+        // contiguous rows t >= len: one row of T * C samples per clip.
+        if (!nl || o.kind == VB_OP_XT_PLANES || o.kind == VB_OP_SPLIT_PLANES || o.kind == VB_OP_GN_STATS || o.kind == VB_OP_SOFTMAX_T) continue;
+        if (o.out >= 0 && n.bufs[o.out].square == 1) continue;
+        if (o.kind == VB_OP_CONV && o.out_transposed) VB_TRY(launch_tail_zero(ptr(o.out), nl->lp, nl->table, B, 1, T, tmul(o.out) * chans(o.out), st));
+        else VB_TRY(launch_tail_zero(ptr(o.out), nl->lp, nl->table, B, chans(o.out), T, tmul(o.out), st));
     }
     return VB_OK;
 }
-// What a program must be for row lengths to work by zero tails alone (include/versband_hip.h, vb_hifigan_forward_lens): every op computes
-// a sample from a zero-padded window of its own row, through an input activation with f(0) = 0, into a plain [B][C][T] buffer.
-static int net_lens_check(const NetProgram& n) {
+// What a program must be to take row lengths, per net.  The vocoder (include/versband_hip.h, vb_hifigan_forward_lens) works by zero tails
+// alone: every op computes a sample from a zero-padded window of its own row, through an input activation with f(0) = 0, into a plain
+// [B][C][T] buffer.  The VAE decoder (vb_vae_decode_lens) adds what net_run gives a length table to - GroupNorm statistics and inputs, the
+// attention's dynamic channel counts, w_buf weights, transposed outputs - and refuses whatever its program does not contain.
+static int net_lens_check(const NetProgram& n, int which) {
     static const char* const kinds[] = {"VB_OP_CONV", "VB_OP_GN_STATS", "VB_OP_SOFTMAX_T", "VB_OP_SPLIT_PLANES", "VB_OP_RESPAIR", "VB_OP_GN_APPLY",
                                         "VB_OP_AA_ACT", "VB_OP_XT_PLANES"};
     for (size_t oi = 0; oi < n.ops.size(); ++oi) {
         const vb_net_op& o = n.ops[oi];
         const char* kn = o.kind >= 0 && o.kind <= VB_OP_XT_PLANES ? kinds[o.kind] : "unknown kind";
+        if (which == VB_NET_VAE) {
+            if (o.kind == VB_OP_AA_ACT)
+                VB_FAIL(VB_E_INVALID, "vae_decode_lens: op %zu (%s): its anti-aliasing filters replicate-pad at the row end, which row lengths do not describe", oi, kn);
+            if (o.kind == VB_OP_RESPAIR || o.kind < 0 || o.kind > VB_OP_XT_PLANES)
+                VB_FAIL(VB_E_INVALID, "vae_decode_lens: op %zu (%s): not an op of the VAE decoder's program", oi, kn);
+            if (o.kind == VB_OP_CONV && o.in_stride > 1)
+                VB_FAIL(VB_E_INVALID, "vae_decode_lens: op %zu (%s): in_stride = %d reads across the row's own end (the encoder's down-convolutions)", oi, kn, o.in_stride);
+            if (o.kind == VB_OP_CONV && o.tr_stride > 1)
+                VB_FAIL(VB_E_INVALID, "vae_decode_lens: op %zu (%s): a transposed convolution (tr_stride = %d) is not an op of the VAE decoder's program", oi, kn, o.tr_stride);
+            continue;
+        }
         if (o.kind == VB_OP_AA_ACT)
             VB_FAIL(VB_E_INVALID, "hifigan_forward_lens: op %zu (%s): its anti-aliasing filters replicate-pad at the row end, which a zero tail cannot stand in for", oi, kn);
         if (o.kind != VB_OP_CONV && o.kind != VB_OP_RESPAIR && o.kind != VB_OP_XT_PLANES)
@@ -162,6 +190,32 @@ static int net_lens_check(const NetProgram& n) {
             VB_FAIL(VB_E_INVALID, "hifigan_forward_lens: op %zu (%s): writes a buffer of square = %d, not [B][C][T]", oi, kn, n.bufs[o.out].square);
     }
     return VB_OK;
+}
+
+// The one lengths path of both nets (vb_hifigan_forward_lens, vb_vae_decode_lens).  Workspace: the net's own, the masked input, the table of
+// row lengths.
+static size_t net_lens_ws_bytes(vb_ctx* ctx, int which, int B, int T) {
+    if (!ctx || !ctx->nets[which].loaded || B < 1 || T < 1) return 0;
+    const NetProgram& n = ctx->nets[which];
+    return net_ws_bytes(n, B, T, nullptr) + align_up((size_t)B * n.in_ch * T * n.in_tmul * sizeof(float)) + align_up(64 * sizeof(int));
+}
+static int net_run_lens(vb_ctx* ctx, int which, const char* fn, const char* net, const float* in, int B, int T, const vb_lens* lens, float* out,
+                        void* ws, hipStream_t st) {
+    NetLens nl;
+    if (lens && lens->len) VB_TRY(lens_plan(lens->len, B, T, &nl.lp));
+    if (!nl.lp.B) return net_run(ctx, which, in, B, T, out, ws, st);                   // no lengths, or every row full: the plain entry point
+    NetProgram& n = ctx->nets[which];
+    if (!n.loaded) VB_FAIL(VB_E_STATE, "%s: no %s loaded", fn, net);
+    VB_TRY(net_lens_check(n, which));
+    if (n.in_tmul != 1) VB_FAIL(VB_E_INVALID, "%s: the %s's input runs at %d samples per frame (1)", fn, net, n.in_tmul);
+    VB_HIP(hipSetDevice(ctx->device));
+    char* p = static_cast<char*>(ws) + net_ws_bytes(n, B, T, nullptr);
+    float* masked = reinterpret_cast<float*>(p);
+    int* table = reinterpret_cast<int*>(p + align_up((size_t)B * n.in_ch * T * n.in_tmul * sizeof(float)));
+    VB_TRY(launch_lens_table(nl.lp, table, st));
+    nl.table = table;
+    VB_TRY(launch_mask_latent(in, B, n.in_ch, T, table, masked, st));                  // (a select: the caller's padding, NaN included, is not read)
+    return net_run(ctx, which, masked, B, T, out, ws, st, &nl);
 }
 
 // the weight fields each allowed (kind, wfmt) pair of include/versband_hip.h reads; -1 = the pair is not allowed
@@ -264,31 +318,17 @@ int vb_hifigan_forward(vb_ctx* ctx, const float* mel, int B, int T, float* wav, 
     RoctxRange rr("vb_hifigan_forward");
     return net_run(ctx, VB_NET_VOCODER, mel, B, T, wav, ws, (hipStream_t)stream);
 }
-size_t vb_hifigan_lens_workspace_bytes(vb_ctx* ctx, int B, int T) {
-    if (!ctx || !ctx->nets[VB_NET_VOCODER].loaded || B < 1 || T < 1) return 0;
-    const NetProgram& n = ctx->nets[VB_NET_VOCODER];
-    // the net's workspace, the masked input, the table of row lengths
-    return net_ws_bytes(n, B, T, nullptr) + align_up((size_t)B * n.in_ch * T * n.in_tmul * sizeof(float)) + align_up(64 * sizeof(int));
-}
+size_t vb_hifigan_lens_workspace_bytes(vb_ctx* ctx, int B, int T) { return net_lens_ws_bytes(ctx, VB_NET_VOCODER, B, T); }
 int vb_hifigan_forward_lens(vb_ctx* ctx, const float* mel, int B, int T, const vb_lens* lens, float* wav, void* ws, void* stream) {
     if (!ctx) VB_FAIL(VB_E_INVALID, "hifigan_forward_lens: null ctx");
-    NetLens nl;
-    if (lens && lens->len) VB_TRY(lens_plan(lens->len, B, T, &nl.lp));
     RoctxRange rr("vb_hifigan_forward_lens");
-    hipStream_t st = (hipStream_t)stream;
-    if (!nl.lp.B) return net_run(ctx, VB_NET_VOCODER, mel, B, T, wav, ws, st);       // no lengths, or every row full: vb_hifigan_forward
-    NetProgram& n = ctx->nets[VB_NET_VOCODER];
-    if (!n.loaded) VB_FAIL(VB_E_STATE, "hifigan_forward_lens: no vocoder loaded");
-    VB_TRY(net_lens_check(n));
-    if (n.in_tmul != 1) VB_FAIL(VB_E_INVALID, "hifigan_forward_lens: the vocoder's input runs at %d samples per frame (1)", n.in_tmul);
-    VB_HIP(hipSetDevice(ctx->device));
-    char* p = static_cast<char*>(ws) + net_ws_bytes(n, B, T, nullptr);
-    float* masked = reinterpret_cast<float*>(p);
-    int* table = reinterpret_cast<int*>(p + align_up((size_t)B * n.in_ch * T * n.in_tmul * sizeof(float)));
-    VB_TRY(launch_lens_table(nl.lp, table, st));
-    nl.table = table;
-    VB_TRY(launch_mask_latent(mel, B, n.in_ch, T, table, masked, st));                 // (a select: the caller's padding, NaN included, is not read)
-    return net_run(ctx, VB_NET_VOCODER, masked, B, T, wav, ws, st, &nl);
+    return net_run_lens(ctx, VB_NET_VOCODER, "hifigan_forward_lens", "vocoder", mel, B, T, lens, wav, ws, (hipStream_t)stream);
+}
+size_t vb_vae_decode_lens_workspace_bytes(vb_ctx* ctx, int B, int T) { return net_lens_ws_bytes(ctx, VB_NET_VAE, B, T); }
+int vb_vae_decode_lens(vb_ctx* ctx, const float* z, int B, int T, const vb_lens* lens, float* mel, void* ws, void* stream) {
+    if (!ctx) VB_FAIL(VB_E_INVALID, "vae_decode_lens: null ctx");
+    RoctxRange rr("vb_vae_decode_lens");
+    return net_run_lens(ctx, VB_NET_VAE, "vae_decode_lens", "VAE decoder", z, B, T, lens, mel, ws, (hipStream_t)stream);
 }
 int vb_crossfade_windows(const float* parts, const int32_t* starts, int nw, int B, int C, int n, int T, float* out, void* stream) {
     if (!parts || !starts || !out || nw < 1 || B < 1 || C < 1 || n < 1 || T < 1) VB_FAIL(VB_E_INVALID, "crossfade_windows: null pointer or nw/B/C/n/T < 1");

@@ -140,6 +140,9 @@ struct ConvArgs {
     const bf16_t* xt = nullptr; int xt_np = 2;
     // optional minimal-filtering weights [P][Ci][Co] fp32 (pack.py:pack_conv_mf): selects conv1d_f32w_kernel (fp32 products, F(2,3)) where it applies
     const float* w_mf = nullptr;
+    // row lengths (device [B], in units of len_mul input positions, upsampling counted): the ACTIVATED input of row b ends at
+    // row_len[b] * len_mul, the register-staged kernels zero-pad from there on (GroupNorm maps a zero tail to something else); null = T
+    const int* row_len = nullptr; int len_mul = 1;
 };
 int launch_conv1d(const ConvArgs& a, hipStream_t st);
 // fused HiFi-GAN ResBlock1 pair (respair_x3.hip; checks, descriptor and epilogue shared with the bf16 form: respair_dev.h): out = beta*out + alpha*(x + b2 + conv2(lrelu(b1 + conv1_dil(lrelu(x)))))
@@ -348,19 +351,27 @@ int launch_fill_gumbel(float* out, int B, int n_branch, int T, int width, uint64
 // net_glue.hip: what the conv-net executor runs between its convolutions
 // ---------------------------------------------------------------------------
 int launch_gn_stats(const float* x, int B, int C, int T, int groups, float eps, float* mean, float* rstd, hipStream_t st);
+// row lengths (vb_vae_decode_lens; len: device [B], in units of len_mul samples): the statistics of row b's first len[b] * len_mul samples per
+// channel, the bits of launch_gn_stats on that clip alone
+int launch_gn_stats_lens(const float* x, int B, int C, int T, int groups, float eps, const int* len, int len_mul, float* mean, float* rstd,
+                         hipStream_t st);
+// (len non-null: out is zero from len[b] * len_mul on - the activated tensor ends at the row's own length)
 int launch_gn_apply(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int B, int C, int T,
-                    int groups, int swish, float* out, hipStream_t st);
+                    int groups, int swish, float* out, hipStream_t st, const int* len = nullptr, int len_mul = 1);
 // transposed split planes for the DMA-fed conv path (see xt_planes_kernel): rows of the padded image
 #define XT_HEAD 64
 #define XT_TAIL 384
 static inline int xt_rows(int T_eff) { return T_eff + XT_HEAD + XT_TAIL; }
 // nplanes: 2 = split planes [2][B][xt_rows][C] (hi, lo), 1 = the round-to-nearest plane alone (the single-pass bf16 convolutions)
 int launch_xt_planes(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int groups, int act,
-                     float slope, int upsample2, int B, int C, int T_in, int nplanes, bf16_t* out, hipStream_t st);
+                     float slope, int upsample2, int B, int C, int T_in, int nplanes, bf16_t* out, hipStream_t st, const int* len = nullptr,
+                     int len_mul = 1);       // (len non-null: zero rows from position len[b] * len_mul of the - upsampled - image on)
 int launch_aa_act(const float* x, const float* alpha, const float* inv_beta, const float* filt, int B, int C, int T, float* out, hipStream_t st);
 // f32 [rows][cols] -> split-bf16 planes [2][rows][cpad] (cpad % 4 == 0, columns >= cols zero filled)
 int launch_split_rows(const float* x, int64_t rows, int cols, int cpad, bf16_t* out, int64_t plane, hipStream_t st);
 int launch_softmax_rows_t(const float* s, int B, int R, int Ccols, float* out_t, hipStream_t st);
+// row lengths: s [B][R][R], row b's softmax over its leading len[b] * len_mul keys and queries, exact zeros elsewhere in out_t [B][R][R]
+int launch_softmax_rows_t_lens(const float* s, int B, int R, const int* len, int len_mul, float* out_t, hipStream_t st);
 int launch_crossfade_windows(const float* parts, const int* starts, int nw, int B, int C, int n, int T, float* out, hipStream_t st);   // starts: HOST array
 
 // ---------------------------------------------------------------------------

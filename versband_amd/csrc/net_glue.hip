@@ -59,13 +59,87 @@ int launch_gn_stats(const float* x, int B, int C, int T, int groups, float eps, 
     return VB_OK;
 }
 
+// Row lengths (vb_vae_decode_lens): the group of row b is C/groups channel rows of L = len[b] * len_mul valid samples at pitch T, and the
+// statistics are the plain kernel's on the compacted clip [C/groups][L], bit for bit: valid sample i (flat, channel-major) goes to the thread
+// the plain kernel gives it - float4 group i / 4 to thread (i / 4) % 1024, summed (x + y) + (z + w), exactly when the compacted slab would
+// take that path (n % 4 == 0; its base is then 16-byte aligned in an aligned buffer), one float per thread otherwise - with the same two
+// passes and the same final order.  A group of four inside one channel row is one 16-byte load when the row pieces are aligned
+// (L % 4 == 0, T % 4 == 0), four 4-byte loads where it straddles two rows.  Nothing behind a row's end is read.
+__global__ void __launch_bounds__(GS_T) gn_stats_lens_kernel(const float* __restrict__ x, int C, int T, int groups, float eps,
+                                                            const int* __restrict__ len, int len_mul, float* mean, float* rstd) {
+    // The squares below are written as the compiler contracts the plain kernel's (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3) and v += d * d
+    // - fma(d0, d0, d1 * d1) + fma(d2, d2, d3 * d3), fma(d, d, v) - with contraction off, so that the two kernels round alike whatever
+    // the loads around them look like (tests/test_gpu_vae_lens.py holds the two to the same bits).
+#pragma clang fp contract(off)
+    __shared__ float red[GS_T / 64];
+    __shared__ float s_mean;
+    const int bg = blockIdx.x;
+    const int cpg = C / groups;
+    const int L = len[bg / groups] * len_mul;
+    const int n = cpg * L;
+    const float* p = x + (int64_t)bg * cpg * T;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool vec = (n & 3) == 0;
+    const bool quad = (L & 3) == 0 && (T & 3) == 0 && ((reinterpret_cast<uintptr_t>(p) & 15) == 0);
+    const int n4 = vec ? n / 4 : 0;
+    auto at = [&](int i) -> float { const int r = i / L; return p[(int64_t)r * T + (i - r * L)]; };
+    auto at4 = [&](int i4) -> float4 {
+        const int i = 4 * i4;
+        if (quad) { const int r = i / L; return *reinterpret_cast<const float4*>(p + (int64_t)r * T + (i - r * L)); }
+        return make_float4(at(i), at(i + 1), at(i + 2), at(i + 3));
+    };
+    float s = 0.f;
+    for (int i = threadIdx.x; i < n4; i += GS_T) {
+        const float4 v = at4(i);
+        s += (v.x + v.y) + (v.z + v.w);
+    }
+    for (int i = n4 * 4 + threadIdx.x; i < n; i += GS_T) s += at(i);
+    s = wave_sum(s);
+    if (lane == 0) red[wave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.f;
+        for (int w = 0; w < GS_T / 64; ++w) t += red[w];
+        s_mean = t / (float)n;
+    }
+    __syncthreads();
+    const float m = s_mean;
+    float v = 0.f;
+    for (int i = threadIdx.x; i < n4; i += GS_T) {
+        const float4 q = at4(i);
+        const float d0 = q.x - m, d1 = q.y - m, d2 = q.z - m, d3 = q.w - m;
+        v += fmaf(d0, d0, d1 * d1) + fmaf(d2, d2, d3 * d3);
+    }
+    for (int i = n4 * 4 + threadIdx.x; i < n; i += GS_T) { float d = at(i) - m; v = fmaf(d, d, v); }
+    v = wave_sum(v);
+    __syncthreads();
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.f;
+        for (int w = 0; w < GS_T / 64; ++w) t += red[w];
+        mean[bg] = m;
+        rstd[bg] = rsqrtf(t / (float)n + eps);
+    }
+}
+int launch_gn_stats_lens(const float* x, int B, int C, int T, int groups, float eps, const int* len, int len_mul, float* mean, float* rstd,
+                         hipStream_t st) {
+    if (C % groups) VB_FAIL(VB_E_INVALID, "gn_stats: C%%groups");
+    if (!len || len_mul < 1 || (int64_t)(C / groups) * T >= (1ll << 31)) VB_FAIL(VB_E_INVALID, "gn_stats: no row lengths, len_mul < 1 or a group of 2^31 samples");
+    hipLaunchKernelGGL(gn_stats_lens_kernel, dim3(B * groups), dim3(GS_T), 0, st, x, C, T, groups, eps, len, len_mul, mean, rstd);
+    VB_CHECK_LAUNCH();
+    return VB_OK;
+}
+
 // GroupNorm affine (+ swish) applied once, for the wide VAE layers: the conv kernels can fuse it into their staging, but a
 // layer with Co/128 output-channel tiles would then redo the exp/div of every input element Co/128 times
 __global__ void __launch_bounds__(256) gn_apply_kernel(const float* __restrict__ x, const float* __restrict__ mean,
                                                       const float* __restrict__ rstd, const float* __restrict__ gamma,
-                                                      const float* __restrict__ beta, int C, int T, int groups, int swish, float* out) {
+                                                      const float* __restrict__ beta, int C, int T, int groups, int swish, float* out,
+                                                      const int* __restrict__ len, int len_mul) {
     const int row = blockIdx.y;                 // b * C + c
     const int b = row / C, c = row - b * C;
+    const int L = len ? len[b] * len_mul : T;   // row lengths: the ACTIVATED tensor ends at the row's own length, zeros behind it
     const int grp = c / (C / groups);
     const float rs = rstd[b * groups + grp] * gamma[c];
     const float sh = beta[c] - mean[b * groups + grp] * rs;
@@ -79,20 +153,25 @@ __global__ void __launch_bounds__(256) gn_apply_kernel(const float* __restrict__
 #pragma unroll
                 for (int k = 0; k < 4; ++k) o[k] = o[k] / (1.f + __expf(-o[k]));
             }
+            if (t + 3 >= L) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) o[k] = t + k < L ? o[k] : 0.f;
+            }
             *reinterpret_cast<float4*>(orow + t) = make_float4(o[0], o[1], o[2], o[3]);
         } else {
             for (int k = t; k < min(t + 4, T); ++k) {
                 float o = xr[k] * rs + sh;
                 if (swish) o = o / (1.f + __expf(-o));
-                orow[k] = o;
+                orow[k] = k < L ? o : 0.f;
             }
         }
     }
 }
 int launch_gn_apply(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int B, int C, int T,
-                    int groups, int swish, float* out, hipStream_t st) {
+                    int groups, int swish, float* out, hipStream_t st, const int* len, int len_mul) {
     if (C % groups) VB_FAIL(VB_E_INVALID, "gn_apply: C %% groups");
-    hipLaunchKernelGGL(gn_apply_kernel, dim3(cdiv(T, 1024), B * C), dim3(256), 0, st, x, mean, rstd, gamma, beta, C, T, groups, swish, out);
+    hipLaunchKernelGGL(gn_apply_kernel, dim3(cdiv(T, 1024), B * C), dim3(256), 0, st, x, mean, rstd, gamma, beta, C, T, groups, swish, out, len,
+                       len_mul);
     VB_CHECK_LAUNCH();
     return VB_OK;
 }
@@ -106,10 +185,12 @@ int launch_gn_apply(const float* x, const float* mean, const float* rstd, const 
 template <int NPL>
 __global__ void __launch_bounds__(256) xt_planes_kernel(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta, int groups, int act,
-                                                       float slope, int upsample2, int C, int T_in, int Tp, bf16_t* out, int64_t plane) {
+                                                       float slope, int upsample2, int C, int T_in, int Tp, bf16_t* out, int64_t plane,
+                                                       const int* __restrict__ len, int len_mul) {
     __shared__ float tile[64][65];
     const int b = blockIdx.z, c0 = blockIdx.y * 64, r0 = blockIdx.x * 64;          // r = row of the padded image
-    const int T_eff = upsample2 ? 2 * T_in : T_in;
+    // (row lengths: the activated image of row b ends at len[b] * len_mul positions - len_mul counts the upsampling - zero rows behind it)
+    const int T_eff = len ? len[b] * len_mul : (upsample2 ? 2 * T_in : T_in);
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const int cpg = groups > 0 ? C / groups : 1;
     {
@@ -155,7 +236,7 @@ __global__ void __launch_bounds__(256) xt_planes_kernel(const float* __restrict_
     }
 }
 int launch_xt_planes(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int groups, int act,
-                     float slope, int upsample2, int B, int C, int T_in, int nplanes, bf16_t* out, hipStream_t st) {
+                     float slope, int upsample2, int B, int C, int T_in, int nplanes, bf16_t* out, hipStream_t st, const int* len, int len_mul) {
     if (C % 16) VB_FAIL(VB_E_INVALID, "xt_planes: C %% 16");
     if (nplanes != 1 && nplanes != 2) VB_FAIL(VB_E_INVALID, "xt_planes: %d planes (1 or 2)", nplanes);
     if (!aligned16(out)) VB_FAIL(VB_E_INVALID, "xt_planes: the planes are not 16-byte aligned");
@@ -165,10 +246,10 @@ int launch_xt_planes(const float* x, const float* mean, const float* rstd, const
     const dim3 grid(cdiv(Tp, 64), cdiv(C, 64), B);
     if (nplanes == 1)
         hipLaunchKernelGGL(xt_planes_kernel<1>, grid, dim3(256), 0, st, x, mean, rstd, gamma, beta, groups, act, slope, upsample2, C, T_in, Tp, out,
-                           (int64_t)0);
+                           (int64_t)0, len, len_mul);
     else
         hipLaunchKernelGGL(xt_planes_kernel<2>, grid, dim3(256), 0, st, x, mean, rstd, gamma, beta, groups, act, slope, upsample2, C, T_in, Tp, out,
-                           (int64_t)B * Tp * C);
+                           (int64_t)B * Tp * C, len, len_mul);
     VB_CHECK_LAUNCH();
     return VB_OK;
 }
@@ -271,6 +352,39 @@ __global__ void __launch_bounds__(256) softmax_rows_t_kernel(const float* __rest
 }
 int launch_softmax_rows_t(const float* s, int B, int R, int Ccols, float* out_t, hipStream_t st) {
     hipLaunchKernelGGL(softmax_rows_t_kernel, dim3(cdiv(R, 4), B), dim3(256), 0, st, s, R, Ccols, out_t);
+    VB_CHECK_LAUNCH();
+    return VB_OK;
+}
+
+// Row lengths (vb_vae_decode_lens): s [B][R][R] holds row b's scores in its leading L x L block (L = len[b] * len_mul); query row r < L takes
+// its softmax over the keys c < L with the lane stride and the order of the plain kernel at Cc = L, and everything outside the block of the
+// transposed result - keys and queries behind the row's end - is written as exact zeros.  Nothing outside the block is read.
+__global__ void __launch_bounds__(256) softmax_rows_t_lens_kernel(const float* __restrict__ s, int R, const int* __restrict__ len, int len_mul,
+                                                                 float* out_t) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int b = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    if (row >= R) return;
+    const int L = len[b] * len_mul;
+    float* o = out_t + (int64_t)b * R * R + row;
+    if (row >= L) {
+        for (int c = lane; c < R; c += 64) o[(int64_t)c * R] = 0.f;
+        return;
+    }
+    const float* p = s + ((int64_t)b * R + row) * R;
+    float m = -INFINITY;
+    for (int c = lane; c < L; c += 64) m = fmaxf(m, p[c]);
+    m = wave_max(m);
+    float sum = 0.f;
+    for (int c = lane; c < L; c += 64) sum += expf(p[c] - m);
+    sum = wave_sum(sum);
+    const float inv = 1.f / sum;
+    for (int c = lane; c < L; c += 64) o[(int64_t)c * R] = expf(p[c] - m) * inv;
+    for (int c = L + lane; c < R; c += 64) o[(int64_t)c * R] = 0.f;
+}
+int launch_softmax_rows_t_lens(const float* s, int B, int R, const int* len, int len_mul, float* out_t, hipStream_t st) {
+    if (!len || len_mul < 1) VB_FAIL(VB_E_INVALID, "softmax_rows_t: no row lengths or len_mul < 1");
+    hipLaunchKernelGGL(softmax_rows_t_lens_kernel, dim3(cdiv(R, 4), B), dim3(256), 0, st, s, R, len, len_mul, out_t);
     VB_CHECK_LAUNCH();
     return VB_OK;
 }

@@ -735,7 +735,9 @@ class ConvNet:
         T = Tin // self.in_tmul
         if lengths is not None:
             if self.which != L.NET_VOCODER:
-                raise ValueError(f"lengths: the {self.NET_NAMES[self.which]} takes equal-length rows only (row lengths reach the vocoder net alone)")
+                hint = "; the VAE decoder takes them through decode_lens" if self.which == L.NET_VAE else ""
+                raise ValueError(f"lengths: the {self.NET_NAMES[self.which]} takes equal-length rows only through run (row lengths reach the "
+                                 f"vocoder net alone{hint})")
             lens, hold, _ = _lens_struct(lengths, B, T, gloss=" (input frames per row)")
             if lens is not None:
                 return self._run_lens(x, B, T, lens, hold)
@@ -751,6 +753,27 @@ class ConvNet:
         ws = self._cached("lens", (B, T), lambda: self._bytes(self.ctx.lib.vb_hifigan_lens_workspace_bytes(self.ctx.handle, B, T)))
         L.check(self.ctx.lib.vb_hifigan_forward_lens(self.ctx.handle, L.ptr(x), B, T, C.byref(lens), L.ptr(out), L.ptr(ws), L.stream_ptr()),
                 "vb_hifigan_forward_lens")
+        del hold                         # (the host array of the lengths: read during the call only)
+        return out
+
+    def decode_lens(self, z: Tensor, lengths) -> Tensor:
+        """VAE decoder only (vb_vae_decode_lens): z [B, zc, T] with one latent length per row - latents of different lengths padded to T
+        share the call.  Row b's first 2 * lengths[b] mel frames are the decode of that clip alone (bit for bit when lengths[b] and T
+        agree mod 4, to fp32 roundoff otherwise: harness.plan_decode_calls groups rows accordingly), the rest of the row is zero, and
+        neither the padding of z nor anything in the workspace is read.  None, or every row full, is run(z)."""
+        if self.which != L.NET_VAE:
+            raise ValueError(f"decode_lens: the {self.NET_NAMES[self.which]} has no decode_lens (the VAE decoder alone; the vocoder takes "
+                             f"row lengths through run(lengths=), the VAE encoder takes equal-length rows only)")
+        z = z.to(self.ctx.device, torch.float32).contiguous()
+        B, Cin, T = z.shape
+        assert Cin == self.in_ch, (Cin, self.in_ch)
+        lens, hold, _ = _lens_struct(lengths, B, T, gloss=" (latent tokens per row)")
+        if lens is None:
+            return self.run(z)
+        out = torch.empty(B, self.out_ch, T * self.out_tmul, dtype=torch.float32, device=self.ctx.device)
+        ws = self._cached("lens", (B, T), lambda: self._bytes(self.ctx.lib.vb_vae_decode_lens_workspace_bytes(self.ctx.handle, B, T)))
+        L.check(self.ctx.lib.vb_vae_decode_lens(self.ctx.handle, L.ptr(z), B, T, C.byref(lens), L.ptr(out), L.ptr(ws), L.stream_ptr()),
+                "vb_vae_decode_lens")
         del hold                         # (the host array of the lengths: read during the call only)
         return out
 

@@ -243,6 +243,32 @@ def plan_vocoder_calls(row_lengths_mel) -> List[dict]:
     return calls
 
 
+DECODE_ROUTE_MOD = 4        # the VAE decoder's bits depend on a latent length through its residue mod 4 alone (include/versband_hip.h, vb_vae_decode_lens)
+
+
+def plan_decode_calls(row_lengths) -> List[dict]:
+    """The VAE decoder's twin of plan_vocoder_calls, for rows of the given latent lengths (tokens): a list of
+        {"rows": [row indices, ascending], "length": the padded length = the longest member, "lengths": [latent length per member] | None}
+    Rows whose lengths share a residue mod 4 form one call (decode_first_stage(..., lengths=)): a route that changes bits - minimal
+    filtering against the direct kernels, the float4 paths of the glue kernels - depends on a length through (length * tmul) % 4 alone;
+    what the attention block's two products take from the length (Ci % 16, Co % 4, the rounding of the split planes to 32) chooses
+    between bit-identical kernels and adds exact zeros.  Inside such a group every row equals the decode of that clip alone bit for bit.  The calls come in the order in which their residues first appear; "lengths" is None where the members are all
+    equally long: the plain call."""
+    lens = [int(v) for v in row_lengths]
+    for r, v in enumerate(lens):
+        if v < 1:
+            raise ValueError(f"plan_decode_calls: row {r} has length {v} (at least 1)")
+    groups: Dict[int, List[int]] = {}
+    for r, v in enumerate(lens):
+        groups.setdefault(v % DECODE_ROUTE_MOD, []).append(r)
+    calls = []
+    for rows in groups.values():
+        member = [lens[r] for r in rows]
+        longest = max(member)
+        calls.append({"rows": rows, "length": longest, "lengths": member if any(v != longest for v in member) else None})
+    return calls
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # caption text (the "Musical: ..." half of the prompt)
 # ------------------------------------------------------------------------------------------------------------------

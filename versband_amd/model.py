@@ -385,8 +385,12 @@ class CFM:
         return float(self.scale_factor) * z
 
     @torch.no_grad()
-    def decode_first_stage(self, z, predict_cids=False, force_not_quantize=False):
-        """ddpm_audio.py:379-392: z / scale_factor -> AutoencoderKL.decode."""
+    def decode_first_stage(self, z, predict_cids=False, force_not_quantize=False, lengths=None):
+        """ddpm_audio.py:379-392: z / scale_factor -> AutoencoderKL.decode.
+        lengths (addition; ConvNet.decode_lens): one length in latent tokens per row - latents of different lengths padded to T share the
+        call, row b holds 2 * lengths[b] mel frames of the clip alone followed by zeros, the latent padding is never read."""
+        if lengths is not None:
+            return self.vae_net().decode_lens(z, lengths)
         return self.vae_net().run(z)
 
 
