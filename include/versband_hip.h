@@ -638,6 +638,40 @@ int vb_softmax_rows_t_lens(const float* s, int B, int T, const int32_t* len, flo
  * (k-1)*dil <= 64.  Equals two vb_conv1d_bf16 launches up to the accumulation order. */
 int vb_respair_bf16(const float* x, const void* w1_bf16, const float* b1, const void* w2_bf16, const float* b2, int B, int C, int T, int k,
                     int dil, float slope, float alpha, float beta, float* out, void* stream);
+/* Unit entries of three kernels the net executor alone reached (vb_abi_version() stays 3; as vb_qkv_rope, they exist for the unit tests):
+ * vb_conv1d_f32_ups: vb_conv1d_f32 over the nearest-x2 upsampled input (T_in = the un-upsampled length; stride 1, no transposed form, fp32
+ *   weights only) - conv1d_f32g's upsampled window where it applies, the register-staged kernel otherwise.
+ * vb_conv1d_x3_xt: the split-bf16 convolution over pre-activated planes - the two-plane pre-pass (vb_xt_planes, nplanes = 2, into
+ *   planes_scratch of vb_xt_planes_bytes(B, Ci, T_in, upsample2, 2) bytes, 16-byte aligned), then the three-pass GEMM (Co >= 384,
+ *   Ci % 64 == 0, alpha == 1, beta == 0, T_out == the input length) or conv1d_x3_kernel's DMA-fed input mode; w_x3 = [2][tap][Co][ci_pad].
+ * vb_respair_x3: the split-bf16 ResBlock1 pair (respair_x3.hip), w1_x3 / w2_x3 = split planes [2][k][C][C]; otherwise as vb_respair_bf16. */
+int vb_conv1d_f32_ups(const float* x, const float* w, const float* bias, int B, int Ci, int T_in, int Co, int ksize, int dil, int pad, int T_out,
+                      int in_act, float in_slope, const float* res, float* out, void* stream);
+int vb_conv1d_x3_xt(const float* x, const void* w_x3, int ci_pad, const float* bias, int B, int Ci, int T_in, int Co, int ksize, int dil, int pad,
+                    int T_out, int upsample2, int in_act, float in_slope, const float* res, float alpha, float beta, float* out,
+                    void* planes_scratch, void* stream);
+int vb_respair_x3(const float* x, const void* w1_x3, const float* b1, const void* w2_x3, const float* b2, int B, int C, int T, int k, int dil,
+                  float slope, float alpha, float beta, float* out, void* stream);
+/* The plan of a convolution call, host only: which kernel vb_conv1d_f32 / _f32_mf / _bf16 / _bf16_xt would run on these arguments, on which
+ * tile, with which epilogue - from the same descriptor fill, route and tile pickers the launch goes through, under the tuning knobs as they
+ * stand (vb_tune_reload).  Nothing is launched and no device memory is touched; unit tests assert it so that a case that stops reaching
+ * the kernel and tile it was written for fails.  Shape arguments as vb_conv1d_bf16 (in_act: 0 none, 1 LeakyReLU, 2 GroupNorm + swish,
+ * 4 GroupNorm).  wforms = the weight forms the call carries (VB_PLAN_W_*; ci_pad with X3 / BF16), xt = the input comes as pre-activated
+ * planes (vb_conv1d_bf16_xt), has_res = a residual is passed, misalign = operands that are only 4-byte aligned (VB_PLAN_*_4B; all others
+ * 16-byte).  *route = VB_ROUTE_*, *tile_co x *tile_t = output channels x positions of a workgroup (VB_ROUTE_AS_GEMM: the conv-mode GEMM's
+ * tile, 64 x 64 or 128 x 128), *stage_epi = the 16-byte staged epilogue.  Returns what the launch would return for arguments it refuses. */
+enum { VB_PLAN_W_F32 = 1, VB_PLAN_W_MF = 2, VB_PLAN_W_X3 = 4, VB_PLAN_W_BF16 = 8 };
+enum { VB_PLAN_X_4B = 1, VB_PLAN_OUT_4B = 2, VB_PLAN_RES_4B = 4, VB_PLAN_W_4B = 8 };
+enum { VB_ROUTE_AS_GEMM = 0, VB_ROUTE_F32W = 1, VB_ROUTE_CO1 = 2, VB_ROUTE_BF16_XT = 3, VB_ROUTE_BF16 = 4, VB_ROUTE_X3_XT = 5, VB_ROUTE_X3 = 6,
+       VB_ROUTE_F32G = 7, VB_ROUTE_F32 = 8 };
+int vb_conv1d_plan(int B, int Ci, int T_in, int Co, int ksize, int dil, int pad, int tr_stride, int tr_pad, int tr_k, int T_out,
+                   int upsample2, int in_stride, int in_phase, int in_act, int gn_groups, float alpha, float beta, int wforms, int ci_pad,
+                   int xt, int has_res, int misalign, int* route, int* tile_co, int* tile_t, int* stage_epi);
+/* The same for the fused pairs (form = VB_PAIR_*; misalign: VB_PLAN_X_4B / VB_PLAN_OUT_4B).  No pair launcher picks a tile by grid size: *run =
+ * intermediate positions per workgroup, *outputs = the outputs it writes (run - (k - 1), rounded down to 4), *grid_t = workgroups along
+ * time, *staged = the 16-byte epilogue.  VB_E_INVALID where the launch refuses the arguments. */
+enum { VB_PAIR_F32 = 0, VB_PAIR_MF = 1, VB_PAIR_X3 = 2, VB_PAIR_BF16 = 3 };
+int vb_respair_plan(int form, int B, int C, int T, int k, int dil, int misalign, int* run, int* outputs, int* grid_t, int* staged);
 /* counter-based Gumbel draws: out[rows][w], rows = n_branch*B*T */
 int vb_fill_gumbel(float* out, int B, int n_branch, int T, int width, uint64_t seed, int64_t clip_base, int nfe, int block, int gate,
                    void* stream);

@@ -182,6 +182,12 @@ PROTOTYPES = {
     "vb_xt_planes_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "vb_xt_planes": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_float, P, P, P, P, c_int, c_int, P, P]),
     "vb_respair_bf16": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, P, P]),
+    "vb_conv1d_f32_ups": (c_int, [P, P, P] + [c_int] * 8 + [c_int, c_float, P, P, P]),
+    "vb_conv1d_x3_xt": (c_int, [P, P, c_int, P] + [c_int] * 9 + [c_int, c_float, P, c_float, c_float, P, P, P]),
+    "vb_respair_x3": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, P, P]),
+    # host-only plan queries: (route, tile_co, tile_t, stage_epi) / (run, outputs, grid_t, staged) come back through int pointers
+    "vb_conv1d_plan": (c_int, [c_int] * 16 + [c_float, c_float, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "vb_respair_plan": (c_int, [c_int] * 7 + [P, P, P, P]),
     "vb_fill_gumbel": (c_int, [P, c_int, c_int, c_int, c_int, c_u64, c_i64, c_int, c_int, c_int, P]),
     "vb_cast_planes": (c_int, [P, c_i64, P, c_int, P]),
 }

@@ -225,6 +225,39 @@ int vb_respair_bf16(const float* x, const void* w1_bf16, const float* b1, const 
     a.b1 = b1; a.b2 = b2; a.slope = slope; a.alpha = alpha; a.beta = beta;
     return launch_respair_bf16(a, (hipStream_t)stream);
 }
+int vb_conv1d_f32_ups(const float* x, const float* w, const float* bias, int B, int Ci, int T_in, int Co, int ksize, int dil, int pad, int T_out,
+                      int in_act, float in_slope, const float* res, float* out, void* stream) {
+    if (!x || !w || !out || B < 1 || T_in < 1 || T_out < 1 || Ci < 1 || Co < 1) VB_FAIL(VB_E_INVALID, "conv1d_f32_ups: null pointer or B/T/Ci/Co < 1");
+    ConvArgs a;
+    a.x = x; a.x_bstride = (int64_t)Ci * T_in; a.Ci = Ci; a.T_in = T_in; a.w = w; a.bias = bias; a.Co = Co; a.ksize = ksize;
+    a.dil = dil; a.pad = pad; a.upsample2 = 1; a.in_act = in_act; a.in_slope = in_slope; a.out = out; a.out_bstride = (int64_t)Co * T_out;
+    a.T_out = T_out; a.res = res; a.res_bstride = (int64_t)Co * T_out; a.B = B;
+    return launch_conv1d(a, (hipStream_t)stream);
+}
+int vb_conv1d_x3_xt(const float* x, const void* w_x3, int ci_pad, const float* bias, int B, int Ci, int T_in, int Co, int ksize, int dil, int pad,
+                    int T_out, int upsample2, int in_act, float in_slope, const float* res, float alpha, float beta, float* out,
+                    void* planes_scratch, void* stream) {
+    if (!x || !w_x3 || !out || !planes_scratch || B < 1 || T_in < 1 || T_out < 1 || Ci < 1 || Co < 1)
+        VB_FAIL(VB_E_INVALID, "conv1d_x3_xt: null pointer or B/T/Ci/Co < 1");
+    hipStream_t st = (hipStream_t)stream;
+    VB_TRY(launch_xt_planes(x, nullptr, nullptr, nullptr, nullptr, 0, in_act, in_slope, upsample2, B, Ci, T_in, 2, (bf16_t*)planes_scratch, st));
+    ConvArgs a;
+    a.wp = (const bf16_t*)w_x3; a.Ci_pad = ci_pad; a.wp_plane = (int64_t)ksize * Co * ci_pad;
+    a.xt = (const bf16_t*)planes_scratch; a.xt_np = 2;         // (the activation is in the planes: the convolution itself has none)
+    a.x = x; a.x_bstride = (int64_t)Ci * T_in; a.Ci = Ci; a.T_in = T_in; a.bias = bias; a.Co = Co; a.ksize = ksize;
+    a.dil = dil; a.pad = pad; a.upsample2 = upsample2;
+    a.out = out; a.out_bstride = (int64_t)Co * T_out; a.T_out = T_out; a.res = res; a.res_bstride = (int64_t)Co * T_out; a.B = B;
+    a.alpha = alpha; a.beta = beta;
+    return launch_conv1d(a, st);
+}
+int vb_respair_x3(const float* x, const void* w1_x3, const float* b1, const void* w2_x3, const float* b2, int B, int C, int T, int k, int dil,
+                  float slope, float alpha, float beta, float* out, void* stream) {
+    if (!x || !w1_x3 || !b1 || !w2_x3 || !b2 || !out || B < 1 || T < 1) VB_FAIL(VB_E_INVALID, "respair_x3: null pointer or B/T < 1");
+    RespairArgs a;
+    a.x = x; a.out = out; a.B = B; a.C = C; a.T = T; a.k = k; a.dil = dil; a.w1 = (const bf16_t*)w1_x3; a.w2 = (const bf16_t*)w2_x3;
+    a.b1 = b1; a.b2 = b2; a.slope = slope; a.alpha = alpha; a.beta = beta;
+    return launch_respair(a, (hipStream_t)stream);
+}
 int vb_fill_gumbel(float* out, int B, int n_branch, int T, int width, uint64_t seed, int64_t clip_base, int nfe, int block, int gate,
                    void* stream) {
     return launch_fill_gumbel(out, B, n_branch, T, width, seed, clip_base, nfe, nullptr, block, gate, (hipStream_t)stream);

@@ -3,7 +3,8 @@
 #include <stdlib.h>
 
 #include "kernels.h"
-#include "conv1d_staged.h"
+#include "respair_dev.h"
+#include "../../include/versband_hip.h"
 
 // ---- launch_conv1d: descriptor (+ the checks that fail the call; n_count = output positions per phase) -> route -> launch
 static int conv1d_fill(const ConvArgs& a, ConvDev& d, int& n_count) {
@@ -80,6 +81,9 @@ static bool conv1d_co1_eligible(const ConvArgs& a, const ConvDev& d) {
 static bool conv1d_x3_eligible(const ConvArgs& a) { return a.wp && (!a.w_bstride || a.wp_bstride); }
 
 enum ConvRoute { CONV_AS_GEMM, CONV_F32W, CONV_CO1, CONV_BF16_XT, CONV_BF16, CONV_X3_XT, CONV_X3, CONV_F32G, CONV_F32 };
+static_assert(CONV_AS_GEMM == VB_ROUTE_AS_GEMM && CONV_F32W == VB_ROUTE_F32W && CONV_CO1 == VB_ROUTE_CO1 && CONV_BF16_XT == VB_ROUTE_BF16_XT &&
+              CONV_BF16 == VB_ROUTE_BF16 && CONV_X3_XT == VB_ROUTE_X3_XT && CONV_X3 == VB_ROUTE_X3 && CONV_F32G == VB_ROUTE_F32G &&
+              CONV_F32 == VB_ROUTE_F32, "vb_conv1d_plan reports ConvRoute under the public names");
 // Which kernel runs: the first candidate, in this order, whose conditions hold and whose A/B knob has not switched it off; the register-staged
 // fp32 kernel takes everything.  Settles d.stage_epi on the way (VB_CONV_DIRECT_EPI=1: the direct epilogue - no minimal filtering then).
 static ConvRoute conv1d_route(const ConvArgs& a, ConvDev& d) {
@@ -118,5 +122,75 @@ int launch_conv1d(const ConvArgs& a, hipStream_t st) {
         case CONV_F32: launch_conv1d_f32(d, n_count, a.B, st); break;
     }
     VB_CHECK_LAUNCH();
+    return VB_OK;
+}
+
+// ---- the plan of a call, host only (vb_conv1d_plan): descriptor -> route -> the tile that route's launcher picks.  Nothing is launched and no
+// pointer is read: the operands are stand-in addresses that carry only what the route looks at - presence and 16-byte alignment.
+static void conv_tile_dims(ConvTileId id, int* co, int* t) {
+    static const int dims[4][2] = {{128, 128}, {128, 64}, {64, 128}, {32, 256}};
+    *co = dims[id][0]; *t = dims[id][1];
+}
+extern "C" int vb_conv1d_plan(int B, int Ci, int T_in, int Co, int ksize, int dil, int pad, int tr_stride, int tr_pad, int tr_k, int T_out,
+                              int upsample2, int in_stride, int in_phase, int in_act, int gn_groups, float alpha, float beta, int wforms,
+                              int ci_pad, int xt, int has_res, int misalign, int* route, int* tile_co, int* tile_t, int* stage_epi) {
+    if (B < 1 || Ci < 1 || T_in < 1 || Co < 1 || T_out < 1 || !route || !tile_co || !tile_t || !stage_epi)
+        VB_FAIL(VB_E_INVALID, "conv1d_plan: B/Ci/T/Co < 1 or null result pointer");
+    if (!(wforms & (VB_PLAN_W_F32 | VB_PLAN_W_X3 | VB_PLAN_W_BF16))) VB_FAIL(VB_E_INVALID, "conv1d_plan: no weight form the kernels can run on");
+    auto at = [&](int bit, uintptr_t slot) { return (const void*)(slot * 4096 + ((misalign & bit) ? 4 : 0)); };
+    ConvArgs a;
+    a.B = B; a.x = (const float*)at(VB_PLAN_X_4B, 1); a.x_bstride = (int64_t)Ci * T_in; a.Ci = Ci; a.T_in = T_in; a.Co = Co; a.ksize = ksize;
+    a.dil = dil; a.pad = pad; a.tr_stride = tr_stride; a.tr_pad = tr_pad; a.tr_k = tr_k; a.T_out = T_out; a.upsample2 = upsample2;
+    a.in_stride = in_stride > 1 ? in_stride : 1; a.in_phase = in_phase; a.in_act = in_act; a.gn_groups = gn_groups > 0 ? gn_groups : 32;
+    a.alpha = alpha; a.beta = beta;
+    a.out = (float*)at(VB_PLAN_OUT_4B, 2); a.out_bstride = (int64_t)Co * T_out;
+    if (has_res) { a.res = (const float*)at(VB_PLAN_RES_4B, 3); a.res_bstride = a.out_bstride; }
+    if (wforms & VB_PLAN_W_F32) a.w = (const float*)at(VB_PLAN_W_4B, 4);
+    if (wforms & VB_PLAN_W_MF) a.w_mf = (const float*)at(VB_PLAN_W_4B, 5);
+    if (wforms & (VB_PLAN_W_X3 | VB_PLAN_W_BF16)) {
+        const int phases = tr_stride > 1 ? tr_stride : 1, ntaps = tr_stride > 1 ? (tr_k + tr_stride - 1) / tr_stride : ksize;
+        a.wp = (const bf16_t*)at(0, 6); a.Ci_pad = ci_pad; a.wp_plane = (int64_t)phases * ntaps * Co * ci_pad; a.wp_bf16 = (wforms & VB_PLAN_W_BF16) != 0;
+    }
+    if (xt) { a.xt = (const bf16_t*)at(0, 7); a.xt_np = a.wp_bf16 ? 1 : 2; a.in_act = ACT_NONE; }      // (the activation is in the plane)
+    ConvDev d;
+    int n_count;
+    VB_TRY(conv1d_fill(a, d, n_count));
+    const ConvRoute r = conv1d_route(a, d);
+    *route = (int)r; *stage_epi = d.stage_epi; *tile_co = 0; *tile_t = 0;
+    switch (r) {
+        case CONV_AS_GEMM: gemm_conv_tile(a.B, a.T_out, a.Co, tile_t, tile_co); break;      // (conv mode: 64 x 64 under VB_GEMM_SMALL_TILES workgroups, else 128 x 128)
+        case CONV_F32W: conv1d_f32w_tile(d, tile_co, tile_t); break;
+        case CONV_CO1: conv1d_co1_tile(tile_co, tile_t); break;
+        case CONV_BF16_XT: case CONV_BF16: case CONV_X3_XT: case CONV_X3: conv_tile_dims(conv_staged_tile(a.Co, n_count, a.B, d.phases), tile_co, tile_t); break;
+        case CONV_F32G: conv1d_f32g_tile(d, n_count, a.B, a.upsample2, tile_co, tile_t); break;
+        case CONV_F32: conv1d_f32_tile(d, tile_co, tile_t); break;
+    }
+    return VB_OK;
+}
+// The same for the fused pairs: form = VB_PAIR_F32 / _MF / _X3 / _BF16.  The launchers choose no tile by grid size - a form has one run length
+// per (C, dil) - so the plan is the support check, the run (intermediate positions per workgroup), the outputs a workgroup writes, the
+// workgroups along time and the epilogue form.
+extern "C" int vb_respair_plan(int form, int B, int C, int T, int k, int dil, int misalign, int* run, int* outputs, int* grid_t, int* staged) {
+    if (B < 1 || T < 1 || !run || !outputs || !grid_t || !staged) VB_FAIL(VB_E_INVALID, "respair_plan: B/T < 1 or null result pointer");
+    const float* x = (const float*)(uintptr_t)(4096 + ((misalign & VB_PLAN_X_4B) ? 4 : 0));
+    float* out = (float*)(uintptr_t)(2 * 4096 + ((misalign & VB_PLAN_OUT_4B) ? 4 : 0));
+    const void* w = (const void*)(uintptr_t)(3 * 4096);
+    int r;
+    if (form == VB_PAIR_F32 || form == VB_PAIR_MF) {
+        RespairF32Args a;
+        a.x = x; a.out = out; a.B = B; a.C = C; a.T = T; a.k = k; a.dil = dil; a.w1 = (const float*)w; a.w2 = (const float*)w;
+        if (!(form == VB_PAIR_F32 ? respair_f32_supported(a) : respair_f32w_supported(a))) VB_FAIL(VB_E_INVALID, "respair_plan: C=%d k=%d dil=%d T=%d not supported by form %d", C, k, dil, T, form);
+        r = form == VB_PAIR_F32 ? respair_f32_run() : respair_f32w_run(C, dil);
+        PairLaunchT<PairF32Dev> L{};
+        VB_TRY(pair_fill_common(a, "respair_plan", r, (double)k, L));
+        *staged = L.d.staged;
+    } else if (form == VB_PAIR_X3 || form == VB_PAIR_BF16) {
+        RespairArgs a;
+        a.x = x; a.out = out; a.B = B; a.C = C; a.T = T; a.k = k; a.dil = dil; a.w1 = (const bf16_t*)w; a.w2 = (const bf16_t*)w;
+        PairLaunch L{};
+        VB_TRY(pair_fill(a, "respair_plan", L));
+        r = PAIR_T; *staged = L.d.staged;
+    } else VB_FAIL(VB_E_INVALID, "respair_plan: form %d", form);
+    *run = r; *outputs = pair_run_outputs(r, k); *grid_t = cdiv(T, *outputs);
     return VB_OK;
 }

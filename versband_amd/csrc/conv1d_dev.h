@@ -208,13 +208,17 @@ __device__ __forceinline__ bool conv_xcd_unit(const ConvDev& p, int& ct, int& u)
 // conv1d_f32g.hip: DMA-fed exact-fp32 kernel, bit-identical to conv1d_f32_kernel.  _eligible: ALL of a kernel's launch conditions
 bool conv1d_f32g_eligible(const ConvArgs& a, const ConvDev& d);
 void launch_conv1d_f32g(ConvDev& d, int n_count, int B, int upsample2, hipStream_t st);
+void conv1d_f32g_tile(const ConvDev& d, int n_count, int B, int upsample2, int* co, int* t);      // the tile that launch takes (vb_conv1d_plan)
 // conv1d_f32w.hip: the same rings with F(2,3) minimal filtering (k = 3 / 5 / 7 / 11, stride 1): fp32 products, ~1.4-1.5x fewer of them
 bool conv1d_f32w_eligible(const ConvArgs& a, const ConvDev& d);
 int conv1d_f32w_pseudo_taps(int ksize);
 void launch_conv1d_f32w(ConvDev& d, int B, hipStream_t st);
+void conv1d_f32w_tile(const ConvDev& d, int* co, int* t);
 // conv1d_f32.hip: the register-staged exact-fp32 kernel (takes everything) and the one-output-channel kernel
 void launch_conv1d_f32(const ConvDev& d, int n_count, int B, hipStream_t st);
 void launch_conv1d_co1(const ConvDev& d, int B, hipStream_t st);
+void conv1d_f32_tile(const ConvDev& d, int* co, int* t);      // the tiles those two launches take (vb_conv1d_plan)
+void conv1d_co1_tile(int* co, int* t);
 // The tiles (output channels x positions) of the two bf16-MFMA kernels; conv_staged_tile (conv1d_staged.h) picks one
 enum ConvTileId { CONV_TILE_128x128, CONV_TILE_128x64, CONV_TILE_64x128, CONV_TILE_32x256 };
 // conv1d_x3.hip: split-bf16 (hi*hi + lo*hi + hi*lo, fp32-class); xt: the window comes from pre-activated transposed planes (d.xt)

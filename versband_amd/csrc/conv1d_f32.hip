@@ -121,9 +121,15 @@ static void launch_cfg(const ConvDev& d, int n_count, int B, hipStream_t st) {
     hipLaunchKernelGGL((conv1d_f32_kernel<WM, WN, TM, TN>), grid, dim3(256), 0, st, d);
 }
 // (no 128co x 64t tile here: the kernel is the fallback of shapes nothing else takes)
+// the tile of a launch (output channels x positions): launch_conv1d_f32 switches on it, vb_conv1d_plan reports it
+void conv1d_f32_tile(const ConvDev& d, int* co, int* t) {
+    if (d.Co > 64) { *co = 128; *t = 128; } else if (d.Co > 32) { *co = 64; *t = 128; } else { *co = 32; *t = 256; }
+}
 void launch_conv1d_f32(const ConvDev& d, int n_count, int B, hipStream_t st) {
-    if (d.Co > 64) launch_cfg<2, 2, 2, 2>(d, n_count, B, st);
-    else if (d.Co > 32) launch_cfg<2, 2, 1, 2>(d, n_count, B, st);
+    int co, t;
+    conv1d_f32_tile(d, &co, &t);
+    if (co == 128) launch_cfg<2, 2, 2, 2>(d, n_count, B, st);
+    else if (co == 64) launch_cfg<2, 2, 1, 2>(d, n_count, B, st);
     else launch_cfg<1, 4, 1, 2>(d, n_count, B, st);
 }
 
@@ -175,6 +181,7 @@ __global__ void __launch_bounds__(256) conv1d_co1_kernel(const ConvDev p) {
         p.out[oi] = conv_out_value(p, acc[e], bias, res, old);
     }
 }
+void conv1d_co1_tile(int* co, int* t) { *co = 1; *t = C1_TT; }
 void launch_conv1d_co1(const ConvDev& d, int B, hipStream_t st) {
     hipLaunchKernelGGL(conv1d_co1_kernel, dim3(cdiv(d.T_out, C1_TT), B), dim3(256), 0, st, d);
 }

@@ -338,10 +338,24 @@ bool conv1d_f32g_eligible(const ConvArgs& a, const ConvDev& d) {
            (!a.upsample2 || (a.Co > 64 && d.phases == 1));
 }
 // picks the tile and launches; the caller (launch_conv1d) has checked conv1d_f32g_eligible
+// the upsampled form's tile: 128 x 96 where its rounds of 256 workgroups cover fewer positions than 128 x 128's
+static bool g_ups_96(int n_count, int Co, int B) {
+    const int64_t w128 = (int64_t)cdiv(n_count, 128) * cdiv(Co, 128) * B, w96 = (int64_t)cdiv(n_count, 96) * cdiv(Co, 128) * B;
+    return cdiv(w96, 256) * 96 < cdiv(w128, 256) * 128;
+}
+// the tile launch_conv1d_f32g takes (output channels x positions), from the same pickers: what vb_conv1d_plan reports
+void conv1d_f32g_tile(const ConvDev& d, int n_count, int B, int upsample2, int* co, int* t) {
+    static const int wide[4][2] = {{128, 128}, {128, 96}, {64, 128}, {64, 64}};
+    if (upsample2) { *co = 128; *t = g_ups_96(n_count, d.Co, B) ? 96 : 128; }
+    else if (d.Co > 64) { const int id = g_pick_tile(n_count, d.Co, B, d.phases) & 3; *co = wide[id][0]; *t = wide[id][1]; }
+    else if (d.Co > 32) { *co = 64; *t = 128; }
+    else { *co = 32; *t = 256; }
+}
 void launch_conv1d_f32g(ConvDev& d, int n_count, int B, int upsample2, hipStream_t st) {
+    int tile_co, tile_t;
+    conv1d_f32g_tile(d, n_count, B, upsample2, &tile_co, &tile_t);
     if (upsample2) {
-        const int64_t w128 = (int64_t)cdiv(n_count, 128) * cdiv(d.Co, 128) * B, w96 = (int64_t)cdiv(n_count, 96) * cdiv(d.Co, 128) * B;
-        if (cdiv(w96, 256) * 96 < cdiv(w128, 256) * 128) launch_cfg_g<4, 1, 1, 3, true, 3>(d, n_count, B, st);
+        if (tile_t == 96) launch_cfg_g<4, 1, 1, 3, true, 3>(d, n_count, B, st);
         else launch_cfg_g<2, 2, 2, 2, true, 3>(d, n_count, B, st);
     } else if (d.Co > 64) {
 #ifdef VB_EXPERIMENTS
@@ -369,6 +383,6 @@ void launch_conv1d_f32g(ConvDev& d, int n_count, int B, int upsample2, hipStream
 #endif
                 launch_cfg_g_taps<2, 2, 2, 2, 3>(d, n_count, B, st);     // 3-stage ring: 49 KB, three workgroups per CU (31.3 -> 30.4 ms per pass against 4 stages / two)
         }
-    } else if (d.Co > 32) launch_cfg_g<2, 2, 1, 2, false>(d, n_count, B, st);
+    } else if (tile_co == 64) launch_cfg_g<2, 2, 1, 2, false>(d, n_count, B, st);
     else launch_cfg_g<1, 4, 1, 2, false>(d, n_count, B, st);
 }

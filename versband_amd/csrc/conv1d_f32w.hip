@@ -292,10 +292,12 @@ __global__ void __launch_bounds__(256, OCC) conv1d_f32w_kernel(const ConvDev p) 
     }
 }
 
+// positions of a tile of WN waves along time: two VW-wide halves per wave, VW = the dilation's multiple of MFMA columns
+static int w_t_tile(int wn, int dil) { return wn * 2 * ((32 / dil) * dil); }
 template <int K, int OCC, int WN>
 static void launch_w(ConvDev& d, int B, hipStream_t st) {
     constexpr int CO_TILE = F32wGeo<WN>::CO_TILE, BYTES = F32wGeo<WN>::BYTES;
-    const int T_TILE = WN * 2 * ((32 / d.dil) * d.dil);
+    const int T_TILE = w_t_tile(WN, d.dil);
     const int grid = conv_xcd_grid(d, d.T_out, T_TILE, CO_TILE, B);      // (phases == 1)
 #ifdef VB_EXPERIMENTS
     d.mf_abl = getenv("VB_F32W_ABL") ? atoi(getenv("VB_F32W_ABL")) : 0;
@@ -328,9 +330,17 @@ int conv1d_f32w_pseudo_taps(int ksize) { return mf_ntaps(ksize); }
 // the caller (launch_conv1d) has checked conv1d_f32w_eligible.  Two builds of the same code: <= 168 VGPRs (three
 // workgroups per CU, 49 KB of LDS each) and <= 256 (two).  Two per CU measured 1 % faster end to end (1174 against 1163 mel-s/s, same box):
 // the default; VB_MF_OCC=3 selects the other (A/B knob)
+// 64 co x 8 VW tiles where a 128-channel tile would be half empty (Co <= 64) or leave a half-empty last tile (Co % 128 in (0, 64])
+static bool w_narrow(int Co) { return Co <= 64 || (Co % 128 != 0 && Co % 128 <= 64 && Co < 256); }
+// the tile launch_conv1d_f32w takes (output channels x positions; VW = the dilation's multiple of MFMA columns): what vb_conv1d_plan reports
+void conv1d_f32w_tile(const ConvDev& d, int* co, int* t) {
+    if (w_narrow(d.Co)) { *co = F32wGeo<4>::CO_TILE; *t = w_t_tile(4, d.dil); }
+    else { *co = F32wGeo<2>::CO_TILE; *t = w_t_tile(2, d.dil); }
+}
 void launch_conv1d_f32w(ConvDev& d, int B, hipStream_t st) {
-    // 64 co x 8 VW tiles where a 128-channel tile would be half empty (Co <= 64) or leave a half-empty last tile (Co % 128 in (0, 64])
-    const bool narrow = d.Co <= 64 || (d.Co % 128 != 0 && d.Co % 128 <= 64 && d.Co < 256);
+    int tile_co, tile_t;
+    conv1d_f32w_tile(d, &tile_co, &tile_t);
+    const bool narrow = tile_co == F32wGeo<4>::CO_TILE;
     if (narrow) launch_w_k<2, 4>(d, B, st);          // (five window pieces per wave: 177 VGPRs - the two-per-CU build only)
     else if (vb_tune().conv_mf_occ == 3) launch_w_k<3, 2>(d, B, st);
     else launch_w_k<2, 2>(d, B, st);

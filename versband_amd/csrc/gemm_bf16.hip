@@ -892,6 +892,15 @@ static bool gemm_p8_eligible(const GemmArgs& a, const GemmDev& d) {
 static bool gemm_conv_small_eligible(const GemmArgs& a, const VbTune& tune) {
     return (int64_t)a.ngroups * cdiv(a.group_rows, BM) * cdiv(a.N, BN) < tune.gemm_small_tiles;
 }
+static GemmRoute gemm_conv_route(const GemmArgs& a, const VbTune& tune) {
+    return (tune.gemm_small == 11 && gemm_conv_small_eligible(a, tune)) ? GEMM_SMALL_64 : GEMM_T128;
+}
+// the tile (rows = positions x columns = output channels) a conv-mode launch of B clips x T_out rows x Co columns takes: vb_conv1d_plan
+void gemm_conv_tile(int B, int T_out, int Co, int* bm, int* bn) {
+    GemmArgs a; a.ngroups = B; a.group_rows = T_out; a.N = Co;
+    const GemmTile t = GEMM_TILE[gemm_conv_route(a, vb_tune())];
+    *bm = t.bm; *bn = t.bn;
+}
 
 #ifdef VB_EXPERIMENTS
 // The experiments build's opt-ins, over the product's choice.  None of them is on by default.
@@ -949,7 +958,7 @@ static int gemm_route(const GemmArgs& a, const GemmDev& d, const VbTune& tune, G
 #ifdef VB_EXPERIMENTS
     route = gemm_route_experiments(a, d, tune, route);
 #endif
-    if (a.conv_ci > 0) route = (tune.gemm_small == 11 && gemm_conv_small_eligible(a, tune)) ? GEMM_SMALL_64 : GEMM_T128;
+    if (a.conv_ci > 0) route = gemm_conv_route(a, tune);
     return VB_OK;
 }
 

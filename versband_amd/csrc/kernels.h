@@ -63,6 +63,7 @@ static inline GemmArgs gemm_operands(const void* A, int64_t a_plane, int lda, co
     return g;
 }
 int launch_gemm(const GemmArgs& a, hipStream_t st);
+void gemm_conv_tile(int B, int T_out, int Co, int* bm, int* bn);      // the tile of a conv-mode launch (GemmArgs::conv_*), host only
 // routed experts, second product of BOTH groups in one launch over (caption, acoustic) pair buckets (bf16, E <= 4; moe_w2_pair_kernel):
 // out[tok][:] = Hs[caption slot] W2[c]^T + Hs[acoustic slot] W2[E + a]^T  with the gate weights m_c / m_a already folded into the
 // hidden rows by the SwiGLU epilogue (GemmArgs::row_scale / row_scale2): one accumulator, K = 2H
@@ -168,6 +169,9 @@ int launch_respair_f32(const RespairF32Args& a, hipStream_t st);
 // the same pair with F(2,3) minimal filtering (respair_f32w.hip): w1 / w2 = pseudo-tap weights [P][C][C] (pack.py:pack_conv_mf); C = 32, k = 3 / 7 / 11
 bool respair_f32w_supported(const RespairF32Args& a);
 int launch_respair_f32w(const RespairF32Args& a, hipStream_t st);
+// intermediate positions per workgroup (the `run` of pair_fill_common) of the two fp32 pairs: what vb_respair_plan reports
+int respair_f32_run(void);
+int respair_f32w_run(int C, int dil);
 
 // ---------------------------------------------------------------------------
 // elementwise.hip: norms, casts and small helpers of the DiT, T5 and the sampler's tabulation; rowlin.hip, t5.hip, melnet.hip

@@ -289,6 +289,7 @@ bool respair_f32_supported(const RespairF32Args& a) {
            aligned16(a.x) && aligned16(a.w1) && aligned16(a.w2);
 }
 
+int respair_f32_run(void) { return PF_T; }
 int launch_respair_f32(const RespairF32Args& a, hipStream_t st) {
     if (!respair_f32_supported(a)) VB_FAIL(VB_E_INVALID, "respair_f32: C=%d k=%d dil=%d T=%d (C 32/64/128, odd k <= 17, (k-1) dil <= 60, T %% 4 == 0, 16-B aligned)", a.C, a.k, a.dil, a.T);
     PairLaunchT<PairF32Dev> L{};

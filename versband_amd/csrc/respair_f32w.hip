@@ -243,12 +243,13 @@ bool respair_f32w_supported(const RespairF32Args& a) {
            aligned16(a.x) && aligned16(a.out) && aligned16(a.w1) && aligned16(a.w2);
 }
 
+int respair_f32w_run(int C, int dil) { return C == 32 ? PairWGeo<4, 32>::run(dil) : PairWGeo<2, 64>::run(dil); }
 // a.w1 / a.w2 are the minimal-filtering pseudo-tap weights of the two convolutions ([P][C][C], pack.py:pack_conv_mf)
 int launch_respair_f32w(const RespairF32Args& a, hipStream_t st) {
     if (!respair_f32w_supported(a)) VB_FAIL(VB_E_INVALID, "respair_f32w: C=%d k=%d dil=%d T=%d (C 32 / 64, k 3/7/11, (k-1) dil <= 60, T %% 4 == 0, 16-B aligned)", a.C, a.k, a.dil, a.T);
     // runs of M = 8 VW (C = 32) / 4 VW (C = 64) intermediate positions; executed flops: pseudo-taps / 2 products per output, two convolutions
     PairLaunchT<PairF32Dev> L{};
-    VB_TRY(pair_fill_common(a, "respair_f32w", a.C == 32 ? PairWGeo<4, 32>::run(a.dil) : PairWGeo<2, 64>::run(a.dil), 0.5 * mf_ntaps(a.k), L));      // respair_dev.h
+    VB_TRY(pair_fill_common(a, "respair_f32w", respair_f32w_run(a.C, a.dil), 0.5 * mf_ntaps(a.k), L));      // respair_dev.h
     const PairF32Dev& d = L.d;
     ProfScope prof(3, L.flops, L.act_bytes + 2.0 * 4.0 * mf_ntaps(a.k) * a.C * a.C, st);
     if (a.C == 32) {
