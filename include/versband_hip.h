@@ -282,7 +282,8 @@ int vb_sample_cfg_sched(vb_ctx* ctx, float* x, const void* cond, int B, int n_br
  * are the ones of a plain call and run over every token); a host that wants a defined tensor clears them (the Python host does).
  *   len  int32 [B]  HOST array of row lengths, 1 <= len[b] <= T; read during the call only.
  * VB_E_INVALID, with the row named in vb_last_error(), before anything is launched and with x unchanged, when: len[b] < 1; len[b] > T;
- * B > 64; T_mel != 2 T (precompute); win with nw > 1 beside lengths (joint windows are equal-length by construction).
+ * B > 64; T_mel != 2 T (precompute); win with nw > 1 beside lengths (joint windows are equal-length by construction).  Windows of clips of
+ * different lengths are rows of their own length under a per-row plan: vb_sample_cfg_window_rows (below).
  * lens == NULL, len == NULL or all len[b] == T is exactly the entry point without lengths (vb_sample_cfg_sched, which like the four before
  * it forwards here; vb_dit_forward; vb_dit_precompute_cond - both forward to their _lens forms): same launches, same graph key, same bits.
  * keep, rows and guidance compose unchanged (all are token-local); single-branch steps read the same table.  The lengths reach the
@@ -299,8 +300,39 @@ int vb_sample_cfg_lens(vb_ctx* ctx, float* x, const void* cond, int B, int n_bra
                        const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_lens* lens, const vb_guidance* guidance,
                        const vb_windows* win, const vb_rows* rows, const vb_keep* keep, const vb_noise* noise, float* traj, void* ws,
                        void* stream);
+/* WINDOW ROWS (build-defined): joint windows of long clips of DIFFERENT lengths as rows of one call - a per-row window plan in place of
+ * the one starts[nw] array of vb_windows, beside row lengths.  Row r is a window of long clip group[r] and covers that clip's tokens
+ * [start[r], start[r] + len[r]), with len[r] the row's length from the vb_lens block of the same call, or T without one.  Rows of one
+ * group appear in ascending start; they need not be adjacent (the interleaved layout of vb_windows is the special case
+ * group[r] = r % Bc, start[r] = starts[r / Bc]).  Group ids are labels: any values, equal for the rows of one clip.
+ * For each group, consecutive rows (ra, rb) form a consensus pair with ov = start[ra] + len[ra] - start[rb]: token len[ra] - ov + u of
+ * row ra and token u of row rb are the same token of the clip.  On entry (after the keep projection, before traj[0]) and after every
+ * Euler step both copies take one consensus value, in the arithmetic of vb_sample_cfg_windows, for every u in [0, ov) and channel c:
+ *     ia = (ra*C + c)*T + (len[ra] - ov + u)          ib = (rb*C + c)*T + u
+ *     g  = (float)(u + 1) / (float)(ov + 1);   m = fmaf(g, x[ib] - x[ia], x[ia]);   x[ia] = x[ib] = m
+ * in the documented order within a step: update (with the keep blend), consensus, traj copy.  Only valid tokens are touched: a row's
+ * padding is neither read nor written by the consensus.  It is one kernel in both update forms, so VB_EULER_LAUNCH stays bit-identical.
+ * Everything else of a network evaluation is token-local or reads the length table, so THE CONTRACT of vb_lens extends by groups: the
+ * rows of a group, on their valid tokens, equal the same entry point on that group's rows alone with the same noise keys (rows->clip).
+ *   group, start  int32 [B]  HOST arrays, read during the call only.
+ * VB_E_INVALID, with the row named in vb_last_error(), before anything is launched and with x unchanged, when: group or start is null;
+ * B > 64; start[r] < 0; for consecutive rows (ra, rb) of a group start[rb] <= start[ra] (not ascending), start[rb] > start[ra] + len[ra]
+ * (a gap) or ov > len[rb]; for consecutive rows (ra, rb, rc) of a group start[rc] < start[ra] + len[ra] (a token under three rows - the
+ * pairs would no longer be disjoint); win with nw > 1 beside the block (one plan describes the rows, not two).
+ * A group of one row has no pair.  wrows == NULL, or a block in which no group has two rows, is exactly vb_sample_cfg_lens (which, like
+ * the five before it, forwards here with NULL): same launches, same graph key, same bits.  The captured graph includes the consensus
+ * launches; its key holds the VALUES of group, start and len, so another plan on the same buffers captures its own graph, and a plain
+ * call, a vb_windows call or a lengths-only call never replays a window-rows graph.  vb_windows keeps its own kernel and plan (no 64-row
+ * cap, B / nw clips per pair).  Hosts detect the feature by the presence of these symbols (vb_abi_version() stays 3). */
+typedef struct { const int32_t* group; const int32_t* start; } vb_window_rows;   /* HOST arrays of B entries each */
+int vb_sample_cfg_window_rows(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
+                              const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_window_rows* wrows,
+                              const vb_lens* lens, const vb_guidance* guidance, const vb_windows* win, const vb_rows* rows,
+                              const vb_keep* keep, const vb_noise* noise, float* traj, void* ws, void* stream);
 /* The overlap consensus alone, on x [nw*Bc][C][n] with B = nw*Bc rows (the unit, like vb_euler_cfg_step): same formula, same checks. */
 int vb_window_blend(float* x, const int32_t* starts, int nw, int B, int C, int n, void* stream);
+/* The window-rows consensus alone, on x [B][C][T] (the unit): len is a HOST array of B row lengths in [1, T], NULL = every row has T. */
+int vb_window_rows_blend(float* x, const int32_t* group, const int32_t* start, const int32_t* len, int B, int C, int T, void* stream);
 /* The step loop of vb_sample_cfg is captured into a hipGraph the second time a call arrives with the same buffers / shape on a
  * capturable (non-default) stream and replayed from then on (noise key via device memory: any seed / clip base replays).
  * Number of instantiated graphs this context holds (0 = every call so far ran eagerly): */

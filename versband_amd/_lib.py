@@ -80,6 +80,10 @@ class Lens(C.Structure):
     _fields_ = [("len", C.POINTER(C.c_int32))]
 
 
+class WindowRows(C.Structure):
+    _fields_ = [("group", C.POINTER(C.c_int32)), ("start", C.POINTER(C.c_int32))]
+
+
 class MelConfig(C.Structure):
     _fields_ = [("n_fft", c_int), ("hop", c_int), ("n_mels", c_int)]
 
@@ -133,6 +137,9 @@ PROTOTYPES = {
     "vb_dit_forward_lens": (c_int, [P, P, P, P, C.POINTER(Noise), c_int, c_int, c_int, c_int, C.POINTER(Lens), P, P, P, P]),
     "vb_sample_cfg_lens": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_float, C.POINTER(Lens), C.POINTER(Guidance), C.POINTER(Windows),
                                    C.POINTER(Rows), C.POINTER(Keep), C.POINTER(Noise), P, P, P]),
+    "vb_sample_cfg_window_rows": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_float, C.POINTER(WindowRows), C.POINTER(Lens),
+                                          C.POINTER(Guidance), C.POINTER(Windows), C.POINTER(Rows), C.POINTER(Keep), C.POINTER(Noise), P, P, P]),
+    "vb_window_rows_blend": (c_int, [P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_int, c_int, c_int, P]),
     "vb_attention_lens": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     "vb_window_blend": (c_int, [P, C.POINTER(C.c_int32), c_int, c_int, c_int, c_int, P]),
     "vb_sample_graphs": (c_int, [P]),

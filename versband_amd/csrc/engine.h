@@ -27,8 +27,9 @@ struct SampleGraph {
         const void* rows_scale = nullptr; const void* rows_clip = nullptr;   // vb_sample_cfg_rows: the two POINTERS (cfg_scale is 0 beside rows_scale); their contents are read when the kernels run
         int nw = 0; std::array<int, 64> starts{};    // vb_sample_cfg_windows: the plan's VALUES (the kernel argument holds them); nw = 0: no windows
         int nlens = 0; std::array<int, 64> lens{};   // vb_sample_cfg_lens: the row lengths' VALUES (the table fill at the head of the step loop holds them); nlens = 0: no lengths
+        int nwr = 0; std::array<int, 64> wr_group{}, wr_start{}, wr_len{};   // vb_sample_cfg_window_rows: the VALUES of group, start and the rows' lengths (the pair table in the kernel argument comes from them); nwr = 0: no window rows
         bool sched = false; std::array<float, 64> weights{};   // vb_sample_cfg_sched: the step weights' VALUES (launch arguments, and which steps run one branch); sched = false: no schedule
-        auto tie() const { return std::tie(x, cond, ws, B, nb, T, L, n_steps, cfg_scale, tune_gen, keep_ref, keep_x0, keep_mask, sigma_min, rows_scale, rows_clip, nw, starts, nlens, lens, sched, weights); }
+        auto tie() const { return std::tie(x, cond, ws, B, nb, T, L, n_steps, cfg_scale, tune_gen, keep_ref, keep_x0, keep_mask, sigma_min, rows_scale, rows_clip, nw, starts, nlens, lens, nwr, wr_group, wr_start, wr_len, sched, weights); }
         bool operator==(const Key& o) const { return tie() == o.tie(); }
     } key;
     int seen = 0;                         // calls with this key so far (the first runs eagerly, the second captures)
@@ -155,7 +156,7 @@ struct DitEval {
 int dit_forward(vb_ctx* ctx, const DitEval& ev, hipStream_t st);
 
 // ---- sampler.hip: one sampler call ------------------------------------------------------------
-// One call of vb_sample_cfg_lens (the older entry points forward to it), validated and normalised where it is made
+// One call of vb_sample_cfg_window_rows (the older entry points forward to it), validated and normalised where it is made
 // (sampler.hip:sample_call): the step loop launches from it and the graph cache keys on it, so an option is one member here.
 // THE RULE: anything a launch of the step loop bakes in is in the key (sample_key, below), by ADDRESS where the kernels read through the
 // pointer when they run, by VALUE where the launch argument - or the choice of launch - holds the value itself (SampleGraph::Key says which).
@@ -169,6 +170,9 @@ struct SampleCall {
     // overlapping tokens of neighbouring windows take their consensus value, before the trajectory copy
     WindowPlan wp; bool windows = false;
     LensPlan lens;                          // row lengths: lens.B == B when some row is shorter than T, else 0 (the plain call); the step loop starts by writing them to the workspace table
+    // window rows: the rows are windows of clips of different lengths, described row by row (kernels.h: WindowRowsPlan); the consensus runs
+    // where the windows' does, over the plan's pair table.  wrows = some group has two overlapping rows (none: the call without the block)
+    WindowRowsPlan wr; bool wrows = false;
     const float* gw = nullptr;              // host [n_steps] step weights (sample_steps has the kinds of step); null unless nb == 2 and some weight differs from 1
     const vb_noise* noise = nullptr;        // NOT keyed: the noise key travels through device memory, injected arrays keep a call eager
 };
@@ -181,6 +185,10 @@ inline SampleGraph::Key sample_key(const SampleCall& sc) {
     key.rows_scale = sc.rows.cfg_scale; key.rows_clip = sc.rows.clip;
     if (sc.windows) { key.nw = sc.wp.nw; std::copy(sc.wp.s, sc.wp.s + 64, key.starts.begin()); }
     if (sc.lens.B) { key.nlens = sc.lens.B; std::copy(sc.lens.len, sc.lens.len + 64, key.lens.begin()); }
+    if (sc.wrows) {
+        key.nwr = sc.wr.B; std::copy(sc.wr.group, sc.wr.group + 64, key.wr_group.begin()); std::copy(sc.wr.start, sc.wr.start + 64, key.wr_start.begin());
+        for (int r = 0; r < sc.wr.B; ++r) key.wr_len[r] = sc.lens.B ? sc.lens.len[r] : sc.T;
+    }
     if (sc.gw) { key.sched = true; std::copy(sc.gw, sc.gw + sc.n_steps, key.weights.begin()); }      // (a keyed call is graphable: n_steps <= PRE_STEPS = 64)
     return key;
 }

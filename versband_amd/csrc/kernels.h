@@ -291,6 +291,24 @@ struct WindowPlan { int nw = 0; int s[64] = {}; };
 int window_plan(const int32_t* starts, int nw, int B, int n, WindowPlan* out);
 // x [nw*Bc][C][n] (row = w*Bc + b): both copies of every overlapping token <- fmaf(g, x[ib] - x[ia], x[ia]), g = (u + 1) / (ov + 1)
 int launch_window_blend(float* x, const WindowPlan& wp, int Bc, int C, int n, hipStream_t st);
+// window rows (vb_sample_cfg_window_rows): joint windows of clips of different lengths - the validated pair table, by value in the kernel's
+// argument block like WindowPlan.  Row r is a window of clip group[r] over its tokens [start[r], start[r] + len[r]); consecutive rows
+// (ra, rb) of a group with ov = start[ra] + len[ra] - start[rb] > 0 are one pair: token off_a + u of row ra and token u of row rb,
+// off_a = len[ra] - ov, are the same token.  window_rows_plan checks group / start (HOST arrays; len: the call's LensPlan, B = 0 in it:
+// every row has T) for B <= 64 rows: start[r] >= 0, ascending within a group, no gap, ov <= len[rb], no token under three rows;
+// VB_E_INVALID names the row otherwise.  np = 0: no group has two overlapping rows, the call is the one without the block.  B rows in
+// at least one group give at most 63 pairs.  The kernel is handed the pairs alone; group / start are kept for the graph key.
+struct WindowPairs {
+    struct Pair { int ra, rb, off_a, ov; };
+    int np = 0; Pair p[63] = {};
+};
+struct WindowRowsPlan {
+    WindowPairs pairs; int ov_max = 0;
+    int B = 0; int group[64] = {}; int start[64] = {};
+};
+int window_rows_plan(const int32_t* group, const int32_t* start, const LensPlan& lp, int B, int T, WindowRowsPlan* out);
+// x [B][C][T]: both copies of every overlapping token of every pair <- fmaf(g, x[ib] - x[ia], x[ia]), g = (u + 1) / (ov + 1)
+int launch_window_rows_blend(float* x, const WindowRowsPlan& wr, int C, int T, hipStream_t st);
 int launch_sampler_params(int* step, uint64_t seed, int64_t clip_base, int nfe_base, hipStream_t st);   // step[4..9]: noise key of the call
 int launch_step_ctl(int* step, int64_t* t_idx_cur, const int64_t* t_table, int n_steps, int Beff, int reset, hipStream_t st);
 

@@ -92,6 +92,7 @@ static int sample_steps(vb_ctx* ctx, const SampleCall& sc, float* traj, hipStrea
         if (!fuse_k) VB_TRY(launch_euler_cfg(ek, s.v, B, per, T, n_branch == 2 && !single, 0.f, st));
         advanced = fuse_k;
         if (sc.windows) VB_TRY(launch_window_blend(sc.x, sc.wp, B / sc.wp.nw, c.in_channels, T, st));
+        if (sc.wrows) VB_TRY(launch_window_rows_blend(sc.x, sc.wr, c.in_channels, T, st));
         if (traj) VB_HIP(hipMemcpyAsync(traj + (size_t)(k + 1) * B * per, sc.x, (size_t)B * per * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     return VB_OK;
@@ -118,12 +119,12 @@ static SampleGraph* graph_entry(vb_ctx* ctx, const SampleGraph::Key& key) {
     return e;
 }
 
-// ---- vb_sample_cfg_lens as its steps: sample_call, sample_prologue, sample_graph | sample_steps -------------------------------
+// ---- vb_sample_cfg_window_rows as its steps: sample_call, sample_prologue, sample_graph | sample_steps -------------------------------
 // check the ABI arguments before anything is launched and state the call once.  Every normalisation happens here: per-row scales zero
 // the scalar one, a schedule of all ones or beside one branch (nothing to guide) is the plain call, and so are one window and row
-// lengths that all equal T (lens_plan).
+// lengths that all equal T (lens_plan), and window rows none of whose groups has two overlapping rows (window_rows_plan).
 static int sample_call(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps, float cfg_scale,
-                       const vb_lens* lens, const vb_guidance* guidance, const vb_windows* win, const vb_rows* rows, const vb_keep* keep, const vb_noise* noise,
+                       const vb_window_rows* wrows, const vb_lens* lens, const vb_guidance* guidance, const vb_windows* win, const vb_rows* rows, const vb_keep* keep, const vb_noise* noise,
                        void* ws, SampleCall& sc) {
     sc.x = x; sc.cond = cond; sc.ws = ws; sc.B = B; sc.nb = n_branch; sc.T = T; sc.L = L; sc.n_steps = n_steps; sc.keep = keep; sc.noise = noise;
     if (rows) sc.rows = *rows;
@@ -146,6 +147,12 @@ static int sample_call(vb_ctx* ctx, float* x, const void* cond, int B, int n_bra
             VB_FAIL(VB_E_INVALID, "sample_cfg_lens: row %d has length %d of %d beside %d joint windows, which are equal-length by construction",
                     sc.lens.first_short(T), sc.lens.len[sc.lens.first_short(T)], T, sc.wp.nw);
     }
+    if (wrows) {
+        if (sc.windows)
+            VB_FAIL(VB_E_INVALID, "sample_cfg_window_rows: %d joint windows beside window rows (row 0 would stand under two plans)", sc.wp.nw);
+        VB_TRY(window_rows_plan(wrows->group, wrows->start, sc.lens, B, T, &sc.wr));
+        sc.wrows = sc.wr.pairs.np > 0;
+    }
     return VB_OK;
 }
 
@@ -166,6 +173,7 @@ static int sample_prologue(vb_ctx* ctx, const SampleCall& sc, const int64_t* t_i
     }
     // rows that disagree in their overlaps start from the consensus; rows cut from one start noise are not changed by it
     if (sc.windows) VB_TRY(launch_window_blend(sc.x, sc.wp, sc.B / sc.wp.nw, c.in_channels, sc.T, st));
+    if (sc.wrows) VB_TRY(launch_window_rows_blend(sc.x, sc.wr, c.in_channels, sc.T, st));
     if (traj) VB_HIP(hipMemcpyAsync(traj, sc.x, (size_t)sc.B * per * sizeof(float), hipMemcpyDeviceToDevice, st));
     // the noise key travels through device memory (the router reads it behind the step counter): nothing a replayed graph bakes in
     const vb_noise* noise = sc.noise;
@@ -242,8 +250,22 @@ int vb_sample_cfg_lens(vb_ctx* ctx, float* x, const void* cond, int B, int n_bra
                        const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_lens* lens, const vb_guidance* guidance,
                        const vb_windows* win, const vb_rows* rows, const vb_keep* keep, const vb_noise* noise, float* traj, void* ws,
                        void* stream) {
+    return vb_sample_cfg_window_rows(ctx, x, cond, B, n_branch, T, L, n_steps, t_idx_table, dt_table, cfg_scale, nullptr, lens, guidance, win, rows, keep, noise, traj, ws, stream);
+}
+int vb_window_rows_blend(float* x, const int32_t* group, const int32_t* start, const int32_t* len, int B, int C, int T, void* stream) {
+    if (!x || C < 1) VB_FAIL(VB_E_INVALID, "window_rows_blend: null x or C < 1");
+    LensPlan lp;
+    if (len) VB_TRY(lens_plan(len, B, T, &lp));
+    WindowRowsPlan wr;
+    VB_TRY(window_rows_plan(group, start, lp, B, T, &wr));
+    return launch_window_rows_blend(x, wr, C, T, (hipStream_t)stream);
+}
+int vb_sample_cfg_window_rows(vb_ctx* ctx, float* x, const void* cond, int B, int n_branch, int T, int L, int n_steps,
+                              const int64_t* t_idx_table, const float* dt_table, float cfg_scale, const vb_window_rows* wrows,
+                              const vb_lens* lens, const vb_guidance* guidance, const vb_windows* win, const vb_rows* rows,
+                              const vb_keep* keep, const vb_noise* noise, float* traj, void* ws, void* stream) {
     SampleCall sc;
-    VB_TRY(sample_call(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, lens, guidance, win, rows, keep, noise, ws, sc));
+    VB_TRY(sample_call(ctx, x, cond, B, n_branch, T, L, n_steps, cfg_scale, wrows, lens, guidance, win, rows, keep, noise, ws, sc));
     VB_HIP(hipSetDevice(ctx->device));
     RoctxRange rr("vb_sample_cfg");
     hipStream_t st = (hipStream_t)stream;

@@ -1,7 +1,7 @@
 // The sampler's own kernels (gfx950), called by sampler.hip: the CFG + Euler update where it is a launch of its own (n_branch == 1,
 // VB_EULER_LAUNCH, vb_euler_cfg_step; the sampler's default path fuses it into FinalLayer, rowlin.hip: final_layer_kernel<NQ, true>),
-// the entry projection of a known region, the overlap consensus of joint windows, and the step bookkeeping behind the device-side
-// step counter.
+// the entry projection of a known region, the overlap consensus of joint windows (one starts array, or a per-row pair table), and the
+// step bookkeeping behind the device-side step counter.
 #include <algorithm>
 #include <type_traits>
 
@@ -130,6 +130,70 @@ int launch_window_blend(float* x, const WindowPlan& wp, int Bc, int C, int n, hi
     if (ov_max <= 0) return VB_OK;                               // one window, or windows that only touch
     const int64_t tot = (int64_t)Bc * C * ov_max;
     hipLaunchKernelGGL(window_blend_kernel, dim3((unsigned)((tot + 255) / 256), (unsigned)(wp.nw - 1)), dim3(256), 0, st, x, wp, Bc, C, n);
+    VB_CHECK_LAUNCH();
+    return VB_OK;
+}
+// ---------------------------------------------------------------------------
+// Window rows (vb_sample_cfg_window_rows, vb_window_rows_blend): x [B][C][T], row r a window of clip group[r] with its own length.  The
+// consensus of window_blend_kernel over a pair TABLE instead of one starts array: pair j says that token off_a + u of row ra and token
+// u of row rb are the same token, u in [0, ov).  Same arithmetic, one thread per (ia, ib), pairs disjoint by window_rows_plan (no token
+// under three rows, ov <= len[rb]); off_a + ov = len[ra] <= T and ov <= len[rb] <= T, so only valid tokens are read or written.
+// grid: y = the pair, x over C * ov of that pair (the widest overlap sizes it)
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) window_rows_blend_kernel(float* x, const WindowPairs wp, int C, int T) {
+    const WindowPairs::Pair p = wp.p[blockIdx.y];
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)C * p.ov) return;
+    const int u = (int)(i % p.ov);
+    const int64_t c = i / p.ov;
+    const int64_t ia = ((int64_t)p.ra * C + c) * T + (p.off_a + u);
+    const int64_t ib = ((int64_t)p.rb * C + c) * T + u;
+    const float g = (float)(u + 1) / (float)(p.ov + 1);
+    const float a = x[ia];
+    const float m = fmaf(g, x[ib] - a, a);
+    x[ia] = m;
+    x[ib] = m;
+}
+int window_rows_plan(const int32_t* group, const int32_t* start, const LensPlan& lp, int B, int T, WindowRowsPlan* out) {
+    if (!group || !start) VB_FAIL(VB_E_INVALID, "window_rows: %s is null (row 0 has no plan)", !group ? "group" : "start");
+    if (B < 1 || B > 64) VB_FAIL(VB_E_INVALID, "window_rows: %d rows (1..64); row %d has no slot in the table", B, B < 1 ? 0 : 64);
+    if (T < 1) VB_FAIL(VB_E_INVALID, "window_rows: rows of %d tokens", T);
+    WindowRowsPlan p;
+    p.B = B;
+    int len[64];
+    for (int r = 0; r < B; ++r) { len[r] = lp.B ? lp.len[r] : T; p.group[r] = group[r]; p.start[r] = start[r]; }
+    for (int r = 0; r < B; ++r) {
+        if (start[r] < 0) VB_FAIL(VB_E_INVALID, "window_rows: row %d starts at %d", r, start[r]);
+        int ra = -1, rz = -1;                                      // the rows of r's group before it: the last, and the one before that
+        for (int q = r - 1; q >= 0 && rz < 0; --q)
+            if (group[q] == group[r]) { if (ra < 0) ra = q; else rz = q; }
+        if (ra < 0) continue;
+        const int64_t end_a = (int64_t)start[ra] + len[ra];
+        if (start[r] <= start[ra])
+            VB_FAIL(VB_E_INVALID, "window_rows: row %d at %d does not come after row %d at %d of group %d (rows of a group ascend)", r, start[r],
+                    ra, start[ra], group[r]);
+        if (start[r] > end_a)
+            VB_FAIL(VB_E_INVALID, "window_rows: a gap between row %d at %d (length %d) and row %d at %d of group %d", ra, start[ra], len[ra], r,
+                    start[r], group[r]);
+        const int ov = (int)(end_a - start[r]);
+        if (ov > len[r])
+            VB_FAIL(VB_E_INVALID, "window_rows: row %d of length %d lies inside its overlap of %d tokens with row %d (group %d)", r, len[r], ov, ra,
+                    group[r]);
+        if (rz >= 0 && start[r] < (int64_t)start[rz] + len[rz])
+            VB_FAIL(VB_E_INVALID, "window_rows: row %d at %d reaches into row %d at %d (length %d) of group %d: a token under three rows", r,
+                    start[r], rz, start[rz], len[rz], group[r]);
+        if (ov > 0) {                                              // (rows that only touch have nothing to reconcile)
+            p.pairs.p[p.pairs.np++] = WindowPairs::Pair{ra, r, len[ra] - ov, ov};
+            p.ov_max = std::max(p.ov_max, ov);
+        }
+    }
+    *out = p;
+    return VB_OK;
+}
+int launch_window_rows_blend(float* x, const WindowRowsPlan& wr, int C, int T, hipStream_t st) {
+    if (wr.pairs.np <= 0) return VB_OK;
+    const int64_t tot = (int64_t)C * wr.ov_max;
+    hipLaunchKernelGGL(window_rows_blend_kernel, dim3((unsigned)((tot + 255) / 256), (unsigned)wr.pairs.np), dim3(256), 0, st, x, wr.pairs, C, T);
     VB_CHECK_LAUNCH();
     return VB_OK;
 }

@@ -375,6 +375,52 @@ class DiTEngine:
     _lens_struct = staticmethod(_lens_struct)       # (the name the call sites and the tests use)
 
     @staticmethod
+    def _window_rows_struct(window_rows, B: int, T: int, lens=None, windows=None):
+        """validate the per-row window plan of a joint call over clips of different lengths - window_rows = (group, start), B integers
+        each: row r is a window of long clip group[r] over its tokens [start[r], start[r] + len[r]), len[r] = lens[r] (the call's row
+        lengths) or T - and lay it out as vb_window_rows (two host arrays, read during the call).  The rules are the library's
+        (include/versband_hip.h), stated here first so that the error names the caller's argument and the row.  Returns (struct, the
+        arrays to hold, the consensus pairs [(ra, rb, off_a, ov)])."""
+        try:
+            group, start = window_rows
+        except (TypeError, ValueError):
+            raise TypeError("window_rows must be a pair (group, start) of per-row sequences") from None
+        if group is None or start is None:
+            raise ValueError("window_rows: group and start must both be given (row 0 has no plan)")
+        if windows is not None and len(list(windows)) > 1:
+            raise ValueError("window_rows and windows do not go together: one plan describes the rows, not two (row 0 would stand under both)")
+        if B > 64:
+            raise ValueError(f"window_rows: {B} rows (at most 64; row 64 has no slot in the table)")
+        group = [int(v) for v in _checked_list("window_rows group", group, "integers", (B, "rows"), f"a sequence of {B} clip ids", " (one clip id per row)")]
+        start = [int(v) for v in _checked_list("window_rows start", start, "integers", (B, "rows"), f"a sequence of {B} window starts",
+                                               " (one window start per row)")]
+        ln = list(lens) if lens is not None else [T] * B
+        last, pairs = {}, []               # group -> (its last row, the row before that)
+        for r in range(B):
+            if start[r] < 0:
+                raise ValueError(f"window_rows: start[{r}] = {start[r]} (row {r} starts before its clip)")
+            ra, rz = last.get(group[r], (None, None))
+            last[group[r]] = (r, ra)
+            if ra is None:
+                continue
+            end_a = start[ra] + ln[ra]
+            if start[r] <= start[ra]:
+                raise ValueError(f"window_rows: row {r} at {start[r]} does not come after row {ra} at {start[ra]} of group {group[r]} "
+                                 "(rows of a group ascend)")
+            if start[r] > end_a:
+                raise ValueError(f"window_rows: a gap between row {ra} at {start[ra]} (length {ln[ra]}) and row {r} at {start[r]} of group {group[r]}")
+            ov = end_a - start[r]
+            if ov > ln[r]:
+                raise ValueError(f"window_rows: row {r} of length {ln[r]} lies inside its overlap of {ov} tokens with row {ra} (group {group[r]})")
+            if rz is not None and start[r] < start[rz] + ln[rz]:
+                raise ValueError(f"window_rows: row {r} at {start[r]} reaches into row {rz} at {start[rz]} (length {ln[rz]}) of group {group[r]}: "
+                                 "a token under three rows")
+            if ov > 0:
+                pairs.append((ra, r, ln[ra] - ov, ov))
+        ga, sa = (C.c_int32 * B)(*group), (C.c_int32 * B)(*start)
+        return L.WindowRows(ga, sa), (ga, sa), pairs
+
+    @staticmethod
     def _guidance_struct(guidance, n: int):
         """validate per-step guidance weights - n finite numbers in [0, 16], the library's rules (include/versband_hip.h), stated here
         first so that the error names the caller's argument - and lay them out as vb_guidance (a host array, read during the call).
@@ -391,7 +437,7 @@ class DiTEngine:
 
     def sample_cfg(self, x0: Tensor, cond: dict, t_idx_table: Sequence[int], dt_table: Sequence[float], scale,
                    noise=None, seed: int = 0, clip_base: int = 0, return_traj: bool = False, keep=None, clip_ids=None, windows=None,
-                   guidance=None, lengths=None):
+                   guidance=None, lengths=None, window_rows=None):
         """n Euler steps with classifier-free guidance; x0 [B,C,T] is not modified.
         scale: one number for the batch, or B values (sequence / float32 tensor): row b is guided by scale[b].  clip_ids: B global clip
         indices (sequence / int64 tensor): row b draws its router noise as clip clip_ids[b] instead of clip_base + b (vb_rows).
@@ -408,10 +454,16 @@ class DiTEngine:
         lengths: B row lengths in latent tokens (vb_lens), the ones the conditioning was made with - clips of different lengths as rows of
         one call, padded to T: row b's first lengths[b] tokens are the call on that clip alone, the rest of x0's row is never read into
         them.  The padding of the returned latent (and trajectory) is zero-filled.  Combines with scale, clip_ids, keep and guidance
-        (all per row or per step); not with more than one window."""
+        (all per row or per step); not with more than one window.
+        window_rows = (group, start), B integers each: joint windows of clips of DIFFERENT lengths (vb_window_rows) - row r is a window of
+        long clip group[r] over its tokens [start[r], start[r] + lengths[r]) (T without lengths); rows of a group ascend in start and need
+        not be adjacent.  Neighbouring rows of a group take one consensus value in their overlap after every step, exactly as with
+        windows=; the rows of a group equal the call on that group's rows alone with the same clip_ids.  Combines with lengths, scale,
+        clip_ids, keep and guidance; not with more than one window in windows=."""
         dev = self.ctx.device
         B, nb, T, Lc = cond["B"], cond["nb"], cond["T"], cond["L"]
         ls, held_lens, lens = DiTEngine._lens_struct(lengths, B, T, windows=windows, cond=cond)
+        rstruct, held_wrows = (self._window_rows_struct(window_rows, B, T, lens, windows)[:2] if window_rows is not None else (None, None))
         wstruct, held_win = self._windows_struct(windows, B, T) if windows is not None else (None, None)
         rs, scale, held_rows = self._rows_struct(scale, clip_ids, B, clip_base)
         self._check_cond(cond)
@@ -430,10 +482,14 @@ class DiTEngine:
         ns, held = self._noise_struct(noise, seed, clip_base, 0)
         traj = torch.empty(n + 1, *x.shape, dtype=torch.float32, device=dev) if return_traj else None
         ws = self._workspace(B, nb, T, Lc)
-        # always the most general entry point: an absent option is a null pointer, which is all the older entry points pass in its place
-        L.check(self.ctx.lib.vb_sample_cfg_lens(self.ctx.handle, L.ptr(x), L.ptr(cond["buf"]), B, nb, T, Lc, n, L.ptr(tt), L.ptr(dd),
-                                                float(scale), _ref(ls), _ref(gs), _ref(wstruct), _ref(rs), _ref(ks), _ref(ns), L.ptr(traj),
-                                                L.ptr(ws), L.stream_ptr()), "vb_sample_cfg_lens")
+        if rstruct is not None:         # the per-row window plan has its own entry point, vb_sample_cfg_lens's arguments plus the block
+            L.check(self.ctx.lib.vb_sample_cfg_window_rows(self.ctx.handle, L.ptr(x), L.ptr(cond["buf"]), B, nb, T, Lc, n, L.ptr(tt), L.ptr(dd),
+                                                           float(scale), _ref(rstruct), _ref(ls), _ref(gs), _ref(wstruct), _ref(rs), _ref(ks),
+                                                           _ref(ns), L.ptr(traj), L.ptr(ws), L.stream_ptr()), "vb_sample_cfg_window_rows")
+        else:                           # every other call goes where it always went: an absent option is a null pointer, which is all the older entry points pass in its place
+            L.check(self.ctx.lib.vb_sample_cfg_lens(self.ctx.handle, L.ptr(x), L.ptr(cond["buf"]), B, nb, T, Lc, n, L.ptr(tt), L.ptr(dd),
+                                                    float(scale), _ref(ls), _ref(gs), _ref(wstruct), _ref(rs), _ref(ks), _ref(ns), L.ptr(traj),
+                                                    L.ptr(ws), L.stream_ptr()), "vb_sample_cfg_lens")
         x = x.clone()
         if lens is not None:            # the padding tokens are unspecified (vb_lens): the caller gets a defined tensor
             for b, n_b in enumerate(lens):

@@ -41,6 +41,19 @@ def plan_windows(T: int, window: int, overlap: int) -> List[Tuple[int, int]]:
     return out
 
 
+def plan_window_rows(lengths: Sequence[int], window: int, overlap: int) -> Tuple[List[int], List[int], List[int]]:
+    """(group, start, row_len) of a joint call over clips of different lengths (engine.sample_cfg(window_rows=(group, start),
+    lengths=row_len)): plan_windows(T_b, window, overlap) of every clip, concatenated clip by clip - row r is the window of clip group[r]
+    over its tokens [start[r], start[r] + row_len[r]).  A clip with T_b <= window is one row of its own length."""
+    group, start, row_len = [], [], []
+    for b, T_b in enumerate(lengths):
+        for s, n in plan_windows(int(T_b), window, overlap):
+            group.append(b)
+            start.append(s)
+            row_len.append(n)
+    return group, start, row_len
+
+
 def crossfade_windows_hip(lib, zw: Tensor, plan: Sequence[Tuple[int, int]], B: int, T: int) -> Tensor:
     """the product path of crossfade_windows: window results zw [nw*B, C, n] (row = w*B + b) -> [B, C, T] by vb_crossfade_windows (one kernel,
     same window order and arithmetic as the torch restatement below, which the oracle fixtures were generated with)"""
@@ -90,7 +103,7 @@ def plan_continue(plan: Sequence[Tuple[int, int]]) -> List[Tuple[int, int, int]]
 
 def sample_long(engine, x0: Tensor, t5_cond: Tensor, t5_uncond: Tensor, midi: Tensor, beats: Tensor, t_idx_table, dt_table,
                 scale: float, window: int = 1500, overlap: int = 128, seed: int = 0, clip_base: int = 0, mode: str = "crossfade",
-                t_next=None, sigma_min: float = 1e-4, return_windows: bool = False, guidance=None):
+                t_next=None, sigma_min: float = 1e-4, return_windows: bool = False, guidance=None, lengths=None):
     """x0 [B,C,T], t5_* [B,L,1024], midi/beats [B,1,2T] -> z [B,C,T] for T beyond the DiT's max_len.
     mode "crossfade" (default): all windows as one batch of independent clips, latents cross-faded over the overlaps.
     mode "continue": windows in order, each with its overlap held on the probability path of the previous window's result (needs
@@ -100,12 +113,32 @@ def sample_long(engine, x0: Tensor, t5_cond: Tensor, t5_uncond: Tensor, midi: Te
     (A plan whose shifted last window starts before the end of the window two before it puts a token under three windows and is
     refused by the engine's validation.)
     guidance: per-step guidance weights, handed to every sampler call of the mode (engine.sample_cfg(guidance=...)).
-    return_windows (continue and joint modes) also returns every window's full result, overlaps included: (z, [z_w [B,C,n]])."""
+    return_windows (continue and joint modes) also returns every window's full result, overlaps included: (z, [z_w [B,C,n]]).
+    lengths (mode "joint" only): B clip lengths T_b <= T in latent tokens - long clips of DIFFERENT lengths in one call.  x0 is [B,C,T]
+    and midi / beats hold exactly 2T frames, T the padded length; what lies behind a clip's end is never read.  Every clip gets its own
+    plan_windows(T_b, window, overlap) (plan_window_rows), all windows of all clips are rows of one sampler call
+    (engine.sample_cfg(window_rows=, lengths=)), and the result is [B,C,T] with zeros behind each clip's end.  Clip b equals
+    sample_long on x0[b:b+1, :, :T_b] alone with clip_base + b, bit for bit: its window w draws its router noise under the key it has
+    there, (clip_base + b) * nw_b + w with nw_b the clip's window count.  (Keys of different clips can coincide - clip 0's window 2 of
+    3 and clip 1's window 0 of 2 at clip_base 0 - exactly as they do across separate calls today.)  return_windows then gives
+    (z, [[z_w [1,C,n_w]] per clip]).  None, or all lengths equal to T, is the call without lengths."""
     if mode not in ("crossfade", "continue", "joint"):
         raise ValueError(f"sample_long: mode {mode!r} (crossfade | continue | joint)")
     gk = {} if guidance is None else {"guidance": guidance}        # (None: the calls are the ones they were)
     B, C, T = x0.shape
     window = min(window, engine.cfg.max_len)
+    if lengths is not None:
+        lengths = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        if mode != "joint":
+            raise ValueError(f"sample_long: lengths belong to mode=\"joint\" (mode {mode!r} takes clips of one length)")
+        if len(lengths) != B:
+            raise ValueError(f"sample_long: lengths has {len(lengths)} entries for {B} clips")
+        for b, T_b in enumerate(lengths):
+            if not 1 <= T_b <= T:
+                raise ValueError(f"sample_long: lengths[{b}] = {T_b} is not in [1, T = {T}]")
+        if any(T_b != T for T_b in lengths):
+            return _sample_joint_lengths(engine, x0, t5_cond, t5_uncond, midi, beats, t_idx_table, dt_table, scale, window, overlap, seed,
+                                         clip_base, return_windows, guidance, lengths)
     plan = plan_windows(T, window, overlap)
     nw = len(plan)
     n = plan[0][1]
@@ -147,6 +180,43 @@ def sample_long(engine, x0: Tensor, t5_cond: Tensor, t5_uncond: Tensor, midi: Te
         return crossfade_windows_hip(engine.ctx.lib, zw, plan, B, T)
     parts = [zw[i * B:(i + 1) * B] for i in range(nw)]
     return crossfade_windows(parts, plan, T)
+
+
+def _sample_joint_lengths(engine, x0, t5_cond, t5_uncond, midi, beats, t_idx_table, dt_table, scale, window, overlap, seed, clip_base,
+                          return_windows, guidance, lengths):
+    """mode="joint" of sample_long with clip lengths: every window of every clip as a row of its own length in one sampler call, the rows
+    of a clip reconciled in their overlaps after every step (vb_window_rows), stitched by plain slicing."""
+    B, C, T = x0.shape
+    midi, beats = midi.reshape(B, -1), beats.reshape(B, -1)
+    if midi.shape[1] != 2 * T or beats.shape[1] != 2 * T:
+        raise ValueError(f"sample_long: with lengths, midi / beats hold exactly 2 x {T} frames, got {midi.shape[1]} / {beats.shape[1]}")
+    group, start, row_len = plan_window_rows(lengths, window, overlap)
+    R, n = len(group), max(row_len)
+
+    def rows(src, mul):
+        """the rows cut out of src [B, ..., mul * T] and padded with zeros to mul * n"""
+        out = torch.zeros(R, *src.shape[1:-1], mul * n, dtype=src.dtype, device=src.device)
+        for r, (b, s, m) in enumerate(zip(group, start, row_len)):
+            out[r, ..., :mul * m] = src[b, ..., mul * s:mul * (s + m)]
+        return out
+
+    xw, mw, bw = rows(x0, 1), rows(midi, 2), rows(beats, 2)
+    t5 = torch.cat([t5_cond[group], t5_uncond[group]], dim=0)
+    nw_of = [group.count(b) for b in range(B)]
+    first = [group.index(b) for b in range(B)]
+    keys = [(clip_base + b) * nw_of[b] + (r - first[b]) for r, b in enumerate(group)]       # the key of window w of clip b sampled alone
+    cond = engine.precompute_cond(t5, mw, bw, n, persistent=True, lengths=row_len)
+    zw = engine.sample_cfg(xw, cond, t_idx_table, dt_table, scale, seed=seed, clip_ids=keys, window_rows=(group, start), lengths=row_len,
+                           guidance=guidance)
+    out = torch.zeros(B, C, T, dtype=zw.dtype, device=zw.device)
+    parts = [[] for _ in range(B)]
+    for b in range(B):
+        plan = [(start[r], row_len[r]) for r in range(first[b], first[b] + nw_of[b])]
+        for w, (s, m, known) in enumerate(plan_continue(plan)):
+            p = zw[first[b] + w:first[b] + w + 1, :, :m]
+            out[b:b + 1, :, s + known:s + m] = p[:, :, known:]
+            parts[b].append(p)
+    return (out, parts) if return_windows else out
 
 
 def _sample_continue(engine, x0, t5_cond, t5_uncond, midi, beats, t_idx_table, dt_table, scale, plan, seed, clip_base, t_next, sigma_min,
