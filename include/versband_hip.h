@@ -444,8 +444,8 @@ int vb_hifigan_forward(vb_ctx* ctx, const float* mel, int B, int T, float* wav, 
  * A host that wants bit-exact rows groups its clips by length mod 4 (harness.plan_vocoder_calls).
  * Refused with VB_E_INVALID before anything is launched, naming the op and why: a vocoder program with an op other than VB_OP_CONV /
  * VB_OP_RESPAIR / VB_OP_XT_PLANES (BigVGAN's VB_OP_AA_ACT: its anti-aliasing filters replicate-pad at the row end), an input activation
- * other than none / LeakyReLU, GroupNorm statistics, dynamic channel counts, w_buf weights, a transposed output.  The VAE encoder and
- * vb_hifigan_forward_chunked take no lengths; the VAE decoder has its own entry point (vb_vae_decode_lens).
+ * other than none / LeakyReLU, GroupNorm statistics, dynamic channel counts, w_buf weights, a transposed output.  The VAE encoder takes
+ * no lengths; the VAE decoder and the chunked vocoder have their own entry points (vb_vae_decode_lens, vb_hifigan_forward_chunked_lens).
  * ws: vb_hifigan_lens_workspace_bytes(ctx, B, T) bytes = vb_net_workspace_bytes + the masked mel + the length table.  Hosts detect the
  * feature by the presence of these symbols (vb_abi_version() stays 3). */
 size_t vb_hifigan_lens_workspace_bytes(vb_ctx* ctx, int B, int T);
@@ -479,8 +479,8 @@ int vb_hifigan_forward_lens(vb_ctx* ctx, const float* mel, int B, int T, const v
  *                         the other, or a glue kernel its float4 path).
  * No op had to be excepted.  A host that wants bit-exact rows groups its clips by length mod 4 (harness.plan_decode_calls).
  * Refused with VB_E_INVALID before anything is launched, naming the op and why: VB_OP_AA_ACT, VB_OP_RESPAIR, in_stride > 1, tr_stride > 1
- * (ops the decoder's program does not contain).  The VAE encoder (Downsample1D pads on the right of the row's own end), BigVGAN and
- * vb_hifigan_forward_chunked take no lengths.
+ * (ops the decoder's program does not contain).  The VAE encoder (Downsample1D pads on the right of the row's own end) and BigVGAN
+ * take no lengths.
  * ws: vb_vae_decode_lens_workspace_bytes(ctx, B, T) bytes = vb_net_workspace_bytes + the masked latent + the length table.  Hosts detect
  * the feature by the presence of these symbols (vb_abi_version() stays 3, vb_net_op is unchanged). */
 size_t vb_vae_decode_lens_workspace_bytes(vb_ctx* ctx, int B, int T);
@@ -496,6 +496,42 @@ int vb_vae_decode_lens(vb_ctx* ctx, const float* z, int B, int T, const vb_lens*
 int vb_crossfade_windows(const float* parts, const int32_t* starts, int nw, int B, int C, int n, int T, float* out, void* stream);
 int vb_hifigan_forward_chunked(vb_ctx* ctx, const float* mel, int B, int T, int chunk, int halo, float* wav, void* ws, float* scratch_in,
                                float* scratch_out, void* stream);
+/* The chunked vocoder with ROW LENGTHS (build-defined): long mels of different lengths as rows of one chunked call.  mel [B][in_ch][T], T
+ * the padded length; lens->len the HOST array of B mel-frame lengths, 1 <= len[b] <= T, B <= 64.  wav [B][out_ch][T*hop] is written
+ * completely: row b holds len[b]*hop samples followed by exact zeros.  The mel padding is never read (it may hold NaN).
+ * THE PLAN (vb_hifigan_chunked_lens_plan; host only, launches nothing; the entry point runs the same function).  The chunk grid is the one
+ * of vb_hifigan_forward_chunked: s = 0, chunk, 2*chunk, ... < T, e = min(s + chunk, T), lo = max(0, s - halo); T <= chunk + 2*halo is ONE
+ * step over the whole rows (s = lo = 0, e = T), as there.  In chunk k the ACTIVE rows are those with len[b] > s, in ascending b - a row
+ * that ended before the chunk is not run at all; active row j has n_j = min(len[b], s + chunk + halo) - lo >= 1 frames inside the chunk
+ * (n_j = len[b] in the one-step case); the chunk's width is tc_k = max_j n_j (every row full: the hi - lo of the plain loop).  The export
+ * writes s, lo, tc, n_active [n_chunks] and rows, n [n_chunks][64] (entries j >= n_active: -1 and 0); chunk k keeps the frames
+ * [s_k, min(e_k, len[b])) of an active row, e_k = s_(k+1) or T.  VB_E_INVALID when the grid has more than max_chunks steps (*n_chunks then
+ * holds the count) or an argument is refused.
+ * PER CHUNK: one gather launch copies the active rows into scratch_in, compact [n_active][in_ch][tc_k], exact zeros at t >= n_j by a
+ * select (the masked input: nothing outside [lo, lo + tc_k) of an active row and nothing of an inactive row is read); the length table of
+ * {n_j} is written; the generator runs on n_active rows of tc_k frames with those lengths (vb_hifigan_forward_lens's machinery; the plain
+ * run when every active row is full); one scatter launch writes samples [s*hop, e*hop) of ALL B rows: row b's up to min(e, len[b])*hop
+ * from its compact row at (s - lo)*hop, exact zeros behind, and all of an inactive row.  Both kernels use 16-byte accesses when the base
+ * pointers, the row pitches and lo, tc_k, T (gather) / hop (scatter) allow, 4-byte ones otherwise - same bits either way.
+ * CONTRACT.  Row b's first len[b]*hop samples are the chunk loop over that clip alone ON THE SAME GRID: for each s the plain
+ * vb_hifigan_forward of mel[b, :, lo : min(len[b], s + chunk + halo)], of which the samples of [s, min(e, len[b])) are kept.  They match
+ * BIT FOR BIT in every chunk where n_j == tc_k (mod 4) - kernel routes depend on a length only through that residue (THE ROUTE RULE of
+ * vb_hifigan_forward_lens) - and to fp32 roundoff elsewhere.  The residue condition holds in every chunk when chunk, halo, T and every
+ * len[b] are multiples of 4; the plan export shows, per chunk and row, whether it holds.  (The clip alone on ITS OWN grid -
+ * vb_hifigan_forward_chunked at T = len[b] - differs where a chunk's trailing halo is cut by len[b] < T only in the one-step rule: a clip
+ * with len[b] <= chunk + 2*halo < T is chunked here and run whole there; the two agree like chunked and whole vocoding do.)
+ * lens == NULL, lens->len == NULL or every row full: vb_hifigan_forward_chunked on the same buffers, same launches, same bits.
+ * T <= chunk + 2*halo: vb_hifigan_forward_lens (the workspace below covers it).
+ * Refused with VB_E_INVALID before anything is launched, wav untouched: B > 64 or a length outside [1, T] (the row is named), chunk < 1 or
+ * halo < 0, no vocoder loaded, a program that takes no row lengths (the message of vb_hifigan_forward_lens, naming the op: BigVGAN's
+ * VB_OP_AA_ACT).  scratch_in / scratch_out as for vb_hifigan_forward_chunked at (B, chunk + 2*halo); ws:
+ * vb_hifigan_chunked_lens_workspace_bytes = the net's workspace at (B, chunk + 2*halo) + the length table, or the lens call's at (B, T).
+ * Hosts detect the feature by the presence of these symbols (vb_abi_version() stays 3). */
+size_t vb_hifigan_chunked_lens_workspace_bytes(vb_ctx* ctx, int B, int T, int chunk, int halo);
+int vb_hifigan_forward_chunked_lens(vb_ctx* ctx, const float* mel, int B, int T, int chunk, int halo, const vb_lens* lens, float* wav, void* ws,
+                                    float* scratch_in, float* scratch_out, void* stream);
+int vb_hifigan_chunked_lens_plan(int B, int T, int chunk, int halo, const int32_t* len, int max_chunks, int32_t* s, int32_t* lo, int32_t* tc,
+                                 int32_t* n_active, int32_t* rows, int32_t* n, int* n_chunks);
 
 /* ------------------------------------------------------------ T5 text encoder ----
  * FrozenTextVocalEmbedder.forward (ldm/modules/encoders/modules.py:216-233): T5EncoderModel(input_ids).last_hidden_state, no

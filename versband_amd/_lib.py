@@ -159,6 +159,9 @@ PROTOTYPES = {
     "vb_softmax_rows_t_lens": (c_int, [P, c_int, c_int, P, P, P]),
     "vb_crossfade_windows": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
     "vb_hifigan_forward_chunked": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P, P, P]),
+    "vb_hifigan_chunked_lens_workspace_bytes": (c_size_t, [P, c_int, c_int, c_int, c_int]),
+    "vb_hifigan_forward_chunked_lens": (c_int, [P, P, c_int, c_int, c_int, c_int, C.POINTER(Lens), P, P, P, P, P]),
+    "vb_hifigan_chunked_lens_plan": (c_int, [c_int, c_int, c_int, c_int, P, c_int, P, P, P, P, P, P, C.POINTER(c_int)]),
     "vb_melnet_load": (c_int, [P, C.POINTER(MelConfig), P, P]),
     "vb_melnet_frames": (c_int, [C.POINTER(MelConfig), c_int, c_int]),
     "vb_melnet_workspace_bytes": (C.c_size_t, [C.POINTER(MelConfig), c_int, c_int, c_int]),

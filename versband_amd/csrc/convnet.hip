@@ -218,6 +218,37 @@ static int net_run_lens(vb_ctx* ctx, int which, const char* fn, const char* net,
     return net_run(ctx, which, masked, B, T, out, ws, st, &nl);
 }
 
+// The plan of the chunked vocoder with row lengths (include/versband_hip.h, vb_hifigan_forward_chunked_lens): the chunk grid of
+// vb_hifigan_forward_chunked - T <= chunk + 2 * halo is one step over the whole rows, as there - and per step the rows that have not ended
+// before it with their frames inside it.  The one function behind the entry point and vb_hifigan_chunked_lens_plan.  len: HOST array.
+struct ChunkStep { int s, e, lo, tc; ChunkRows rows; };
+static int chunk_lens_plan(int B, int T, int chunk, int halo, const int32_t* len, std::vector<ChunkStep>* out) {
+    if (chunk < 1 || halo < 0) VB_FAIL(VB_E_INVALID, "hifigan_forward_chunked_lens: chunk=%d halo=%d", chunk, halo);
+    if (T < 1) VB_FAIL(VB_E_INVALID, "hifigan_forward_chunked_lens: T=%d", T);
+    LensPlan lp;
+    VB_TRY(lens_plan(len, B, T, &lp));                 // (B <= 64, 1 <= len[b] <= T: the row is named)
+    out->clear();
+    const bool whole = T <= (int64_t)chunk + 2 * (int64_t)halo;
+    for (int64_t s64 = 0; s64 < T; s64 += whole ? T : chunk) {
+        const int s = (int)s64;
+        ChunkStep c;
+        c.s = s;
+        c.e = whole ? T : (int)std::min<int64_t>(s64 + chunk, T);
+        c.lo = whole ? 0 : std::max(0, s - halo);
+        c.tc = 0;
+        const int64_t hi = whole ? T : s64 + chunk + halo;
+        for (int b = 0; b < B; ++b) {
+            if (len[b] <= s) continue;
+            const int j = c.rows.n_active++;
+            c.rows.row[j] = b;
+            c.rows.n[j] = (int)std::min<int64_t>(len[b], hi) - c.lo;
+            c.tc = std::max(c.tc, c.rows.n[j]);
+        }
+        out->push_back(c);
+    }
+    return VB_OK;
+}
+
 // the weight fields each allowed (kind, wfmt) pair of include/versband_hip.h reads; -1 = the pair is not allowed
 enum { NW_W = 1, NW_X3 = 2, NW_MF = 4, NW_W2 = 8, NW_BUF = 16 };
 static int net_op_fields(int kind, int wfmt, int Co) {
@@ -356,6 +387,77 @@ int vb_hifigan_forward_chunked(vb_ctx* ctx, const float* mel, int B, int T, int 
         VB_TRY(net_run(ctx, VB_NET_VOCODER, scratch_in, B, tc, scratch_out, ws, st));
         VB_HIP(hipMemcpy2DAsync(wav + (size_t)s * hop, (size_t)T * hop * sizeof(float), scratch_out + (size_t)(s - lo) * hop,
                                 (size_t)tc * hop * sizeof(float), (size_t)(e - s) * hop * sizeof(float), rows_out, hipMemcpyDeviceToDevice, st));
+    }
+    return VB_OK;
+}
+size_t vb_hifigan_chunked_lens_workspace_bytes(vb_ctx* ctx, int B, int T, int chunk, int halo) {
+    if (!ctx || !ctx->nets[VB_NET_VOCODER].loaded || B < 1 || T < 1 || chunk < 1 || halo < 0) return 0;
+    const int64_t tc = (int64_t)chunk + 2 * (int64_t)halo;
+    if (T <= tc) return net_lens_ws_bytes(ctx, VB_NET_VOCODER, B, T);                   // (vb_hifigan_forward_lens, or the plain run, of the whole rows)
+    return net_ws_bytes(ctx->nets[VB_NET_VOCODER], B, (int)tc, nullptr) + align_up(64 * sizeof(int));
+}
+int vb_hifigan_chunked_lens_plan(int B, int T, int chunk, int halo, const int32_t* len, int max_chunks, int32_t* s, int32_t* lo, int32_t* tc,
+                                 int32_t* n_active, int32_t* rows, int32_t* n, int* n_chunks) {
+    if (!s || !lo || !tc || !n_active || !rows || !n || !n_chunks || max_chunks < 0) VB_FAIL(VB_E_INVALID, "hifigan_chunked_lens_plan: null output or max_chunks < 0");
+    std::vector<ChunkStep> plan;
+    VB_TRY(chunk_lens_plan(B, T, chunk, halo, len, &plan));
+    *n_chunks = (int)plan.size();
+    if ((int64_t)plan.size() > max_chunks) VB_FAIL(VB_E_INVALID, "hifigan_chunked_lens_plan: %zu chunks, room for %d", plan.size(), max_chunks);
+    for (size_t k = 0; k < plan.size(); ++k) {
+        const ChunkStep& c = plan[k];
+        s[k] = c.s; lo[k] = c.lo; tc[k] = c.tc; n_active[k] = c.rows.n_active;
+        for (int j = 0; j < 64; ++j) {
+            rows[k * 64 + j] = j < c.rows.n_active ? c.rows.row[j] : -1;
+            n[k * 64 + j] = j < c.rows.n_active ? c.rows.n[j] : 0;
+        }
+    }
+    return VB_OK;
+}
+int vb_hifigan_forward_chunked_lens(vb_ctx* ctx, const float* mel, int B, int T, int chunk, int halo, const vb_lens* lens, float* wav, void* ws,
+                                    float* scratch_in, float* scratch_out, void* stream) {
+    if (!ctx) VB_FAIL(VB_E_INVALID, "hifigan_forward_chunked_lens: null ctx");
+    if (chunk < 1 || halo < 0) VB_FAIL(VB_E_INVALID, "hifigan_forward_chunked_lens: chunk=%d halo=%d", chunk, halo);
+    NetProgram& net = ctx->nets[VB_NET_VOCODER];
+    if (!net.loaded) VB_FAIL(VB_E_INVALID, "hifigan_forward_chunked_lens: no vocoder loaded");
+    if (!lens || !lens->len) return vb_hifigan_forward_chunked(ctx, mel, B, T, chunk, halo, wav, ws, scratch_in, scratch_out, stream);
+    std::vector<ChunkStep> plan;
+    VB_TRY(chunk_lens_plan(B, T, chunk, halo, lens->len, &plan));
+    bool full = true;
+    for (int b = 0; b < B; ++b) full = full && lens->len[b] == T;
+    if (full) return vb_hifigan_forward_chunked(ctx, mel, B, T, chunk, halo, wav, ws, scratch_in, scratch_out, stream);
+    if (T <= (int64_t)chunk + 2 * (int64_t)halo) return vb_hifigan_forward_lens(ctx, mel, B, T, lens, wav, ws, stream);
+    VB_TRY(net_lens_check(net, VB_NET_VOCODER));
+    if (net.in_tmul != 1) VB_FAIL(VB_E_INVALID, "hifigan_forward_chunked_lens: the vocoder's input runs at %d samples per frame (1)", net.in_tmul);
+    hipStream_t st = (hipStream_t)stream;
+    RoctxRange rr("vb_hifigan_forward_chunked_lens");
+    VB_HIP(hipSetDevice(ctx->device));
+    const int hop = net.out_tmul;
+    int* table = reinterpret_cast<int*>(static_cast<char*>(ws) + net_ws_bytes(net, B, chunk + 2 * halo, nullptr));
+    for (const ChunkStep& c : plan) {
+        // the rows that reach into the chunk, compact and masked at their own ends; the generator on them with their in-chunk lengths (the
+        // plain run when all are full); samples [s, e) * hop of every row of wav: its own, then zeros
+        ChunkScatter cs;
+        cs.n_active = c.rows.n_active;
+        for (int b = 0; b < 64; ++b) cs.slot[b] = -1;
+        NetLens nl;
+        bool short_row = false;
+        for (int j = 0; j < c.rows.n_active; ++j) {
+            const int b = c.rows.row[j];
+            cs.slot[b] = j;
+            cs.keep[b] = std::min(c.e, (int)lens->len[b]) - c.s;
+            nl.lp.len[j] = c.rows.n[j];
+            short_row = short_row || c.rows.n[j] != c.tc;
+        }
+        if (c.rows.n_active > 0) {
+            VB_TRY(launch_chunk_gather(mel, c.rows, net.in_ch, T, c.lo, c.tc, scratch_in, st));
+            if (short_row) {
+                nl.lp.B = c.rows.n_active;
+                VB_TRY(launch_lens_table(nl.lp, table, st));
+                nl.table = table;
+            }
+            VB_TRY(net_run(ctx, VB_NET_VOCODER, scratch_in, c.rows.n_active, c.tc, scratch_out, ws, st, short_row ? &nl : nullptr));
+        }
+        VB_TRY(launch_chunk_scatter(scratch_out, cs, B, net.out_ch, T, hop, c.s, c.e, c.lo, c.tc, wav, st));
     }
     return VB_OK;
 }

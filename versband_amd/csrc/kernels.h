@@ -395,6 +395,18 @@ int launch_softmax_rows_t(const float* s, int B, int R, int Ccols, float* out_t,
 // row lengths: s [B][R][R], row b's softmax over its leading len[b] * len_mul keys and queries, exact zeros elsewhere in out_t [B][R][R]
 int launch_softmax_rows_t_lens(const float* s, int B, int R, const int* len, int len_mul, float* out_t, hipStream_t st);
 int launch_crossfade_windows(const float* parts, const int* starts, int nw, int B, int C, int n, int T, float* out, hipStream_t st);   // starts: HOST array
+// chunked vocoder with row lengths (vb_hifigan_forward_chunked_lens): the rows of one chunk, by value in the kernels' argument blocks like
+// LensPlan.  row[j] / n[j], j < n_active: the clip of compact row j (ascending) and its frames inside the chunk, 1 <= n[j] <= tc.
+struct ChunkRows { int n_active = 0; int row[64] = {}; int n[64] = {}; };
+// gather: out [n_active][C][tc], out[j][c][t] = t < n[j] ? mel[row[j]][c][lo + t] : 0 (a select: nothing behind a row's own end, nothing
+// outside [lo, lo + tc) and nothing of an inactive row is read).  16-byte accesses when both bases, T, lo and tc allow, 4-byte otherwise.
+int launch_chunk_gather(const float* mel, const ChunkRows& cr, int C, int T, int lo, int tc, float* out, hipStream_t st);
+// scatter: wav [B][C][T*hop], samples [s*hop, e*hop) of EVERY row b: the first keep[b]*hop of them from src [n_active][C][tc*hop] at
+// (s - lo)*hop of compact row slot[b], exact zeros behind them; an inactive row (slot[b] < 0 or keep[b] <= 0) is all zeros and reads
+// nothing.  16-byte accesses when both bases and hop allow (every offset is a multiple of hop), 4-byte otherwise.
+struct ChunkScatter { int n_active = 0; int slot[64] = {}; int keep[64] = {}; };      // (slot[b] < n_active, keep[b] in frames)
+int launch_chunk_scatter(const float* src, const ChunkScatter& cs, int B, int C, int T, int hop, int s, int e, int lo, int tc, float* wav,
+                         hipStream_t st);
 
 // ---------------------------------------------------------------------------
 // per-kernel-class HIP-event timing (bench.py roofline): 0 = bf16 GEMM (incl. the fused expert kernels), 1 = attention,

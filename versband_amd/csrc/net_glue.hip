@@ -436,3 +436,80 @@ int launch_crossfade_windows(const float* parts, const int* starts, int nw, int 
     VB_CHECK_LAUNCH();
     return VB_OK;
 }
+
+// ---------------------------------------------------------------------------
+// chunked vocoder with row lengths (vb_hifigan_forward_chunked_lens): one gather and one scatter per chunk.  Both are copies with a
+// select: grid = (pieces of a row, channels, rows), one float4 (VEC) or one float per lane, the rows' indices and lengths by value.
+// ---------------------------------------------------------------------------
+template <bool VEC>
+__global__ void __launch_bounds__(256) chunk_gather_kernel(const float* __restrict__ mel, const ChunkRows cr, int C, int T, int lo, int tc,
+                                                           float* __restrict__ out) {
+    const int j = blockIdx.z, c = blockIdx.y;
+    const int t = (blockIdx.x * 256 + threadIdx.x) * (VEC ? 4 : 1);
+    if (t >= tc) return;
+    const int n = cr.n[j];
+    const float* src = mel + ((int64_t)cr.row[j] * C + c) * T + lo + t;
+    float* dst = out + ((int64_t)j * C + c) * tc + t;
+    if constexpr (VEC) {
+        // (tc % 4 == 0: the four frames lie inside the chunk; the row's own end may fall among them)
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (t + 4 <= n) v = *reinterpret_cast<const float4*>(src);
+        else if (t < n) {
+            v.x = src[0];
+            if (t + 1 < n) v.y = src[1];
+            if (t + 2 < n) v.z = src[2];
+        }
+        *reinterpret_cast<float4*>(dst) = v;
+    } else {
+        *dst = t < n ? *src : 0.f;
+    }
+}
+int launch_chunk_gather(const float* mel, const ChunkRows& cr, int C, int T, int lo, int tc, float* out, hipStream_t st) {
+    if (cr.n_active < 1 || cr.n_active > 64 || C < 1 || C > 65535 || lo < 0 || tc < 1 || lo + tc > T)
+        VB_FAIL(VB_E_INVALID, "chunk_gather: %d rows, C=%d, frames [%d, %d) of %d", cr.n_active, C, lo, lo + tc, T);
+    for (int j = 0; j < cr.n_active; ++j)
+        if (cr.row[j] < 0 || cr.n[j] < 1 || cr.n[j] > tc) VB_FAIL(VB_E_INVALID, "chunk_gather: compact row %d = clip %d with %d of %d frames", j, cr.row[j], cr.n[j], tc);
+    const bool vec = aligned16(mel) && aligned16(out) && T % 4 == 0 && lo % 4 == 0 && tc % 4 == 0;
+    const dim3 grid(cdiv(tc, vec ? 1024 : 256), C, cr.n_active);
+    if (vec) hipLaunchKernelGGL(chunk_gather_kernel<true>, grid, dim3(256), 0, st, mel, cr, C, T, lo, tc, out);
+    else hipLaunchKernelGGL(chunk_gather_kernel<false>, grid, dim3(256), 0, st, mel, cr, C, T, lo, tc, out);
+    VB_CHECK_LAUNCH();
+    return VB_OK;
+}
+template <bool VEC>
+__global__ void __launch_bounds__(256) chunk_scatter_kernel(const float* __restrict__ src, const ChunkScatter cs, int C, int64_t Tw, int64_t off_w,
+                                                            int nw, int64_t Ts, int64_t off_s, float* __restrict__ wav) {
+    // Tw / Ts: row pitch of wav / src in samples; off_w / off_s: where the chunk's kept samples start in a row of each; nw: how many
+    const int b = blockIdx.z, c = blockIdx.y;
+    const int i = (blockIdx.x * 256 + threadIdx.x) * (VEC ? 4 : 1);
+    if (i >= nw) return;
+    const int slot = cs.slot[b];
+    const int keep = slot < 0 ? 0 : cs.keep[b];        // samples of this row's own; VEC: a multiple of 4 like i and nw (hop % 4 == 0)
+    float* dst = wav + ((int64_t)b * C + c) * Tw + off_w + i;
+    if constexpr (VEC) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i < keep) v = *reinterpret_cast<const float4*>(src + ((int64_t)slot * C + c) * Ts + off_s + i);
+        *reinterpret_cast<float4*>(dst) = v;
+    } else {
+        *dst = i < keep ? src[((int64_t)slot * C + c) * Ts + off_s + i] : 0.f;
+    }
+}
+int launch_chunk_scatter(const float* src, const ChunkScatter& cs, int B, int C, int T, int hop, int s, int e, int lo, int tc, float* wav,
+                         hipStream_t st) {
+    if (B < 1 || B > 64 || C < 1 || C > 65535 || hop < 1 || lo < 0 || lo > s || s >= e || e > T || tc < 0
+        || (int64_t)(e - s) * hop > INT32_MAX)
+        VB_FAIL(VB_E_INVALID, "chunk_scatter: B=%d C=%d hop=%d, frames [%d, %d) of %d from a chunk at [%d, %d)", B, C, hop, s, e, T, lo, lo + tc);
+    ChunkScatter k = cs;                               // keep: frames -> samples
+    for (int b = 0; b < B; ++b) {
+        if (k.slot[b] >= k.n_active || k.n_active > 64 || k.keep[b] > e - s || (k.slot[b] >= 0 && k.keep[b] > 0 && s - lo + k.keep[b] > tc)) VB_FAIL(VB_E_INVALID, "chunk_scatter: row %d keeps %d frames of %d from compact row %d", b, k.keep[b], e - s, k.slot[b]);
+        k.keep[b] = k.slot[b] < 0 || k.keep[b] < 0 ? 0 : k.keep[b] * hop;
+    }
+    const int nw = (e - s) * hop;
+    const bool vec = aligned16(src) && aligned16(wav) && hop % 4 == 0;
+    const dim3 grid(cdiv(nw, vec ? 1024 : 256), C, B);
+    const int64_t Tw = (int64_t)T * hop, Ts = (int64_t)tc * hop, off_w = (int64_t)s * hop, off_s = (int64_t)(s - lo) * hop;
+    if (vec) hipLaunchKernelGGL(chunk_scatter_kernel<true>, grid, dim3(256), 0, st, src, k, C, Tw, off_w, nw, Ts, off_s, wav);
+    else hipLaunchKernelGGL(chunk_scatter_kernel<false>, grid, dim3(256), 0, st, src, k, C, Tw, off_w, nw, Ts, off_s, wav);
+    VB_CHECK_LAUNCH();
+    return VB_OK;
+}

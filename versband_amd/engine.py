@@ -763,7 +763,7 @@ class ConvNet:
         L.check(ctx.lib.vb_net_load(ctx.handle, which, ops, len(nb.ops), bufs, len(nb.bufs), in_ch, out_ch, in_tmul, out_tmul),
                 "vb_net_load")
         # scratch that is sized for a call's (B, T) and made again when that changes: slot -> ((B, T), the buffers)
-        self._scratch = {"net": (None, None), "lens": (None, None), "chunk": (None, None)}
+        self._scratch = {"net": (None, None), "lens": (None, None), "chunk": (None, None), "chunk_lens": (None, None)}
 
     def _cached(self, slot: str, key: Tuple[int, int], make):
         if self._scratch[slot][0] != key:
@@ -833,21 +833,38 @@ class ConvNet:
         del hold                         # (the host array of the lengths: read during the call only)
         return out
 
-    def run_chunked(self, x: Tensor, chunk: int, halo: int) -> Tensor:
+    def run_chunked(self, x: Tensor, chunk: int, halo: int, lengths=None) -> Tensor:
         """vocoder only: mel [B,80,T] -> wav [B,1,T*hop] in chunks of `chunk` frames with `halo` frames of context on both sides, the loop,
-        the slicing and the stitching inside the library (vb_hifigan_forward_chunked); identical to run() when halo >= the receptive field."""
+        the slicing and the stitching inside the library (vb_hifigan_forward_chunked); identical to run() when halo >= the receptive field.
+        lengths (vb_hifigan_forward_chunked_lens): one length in mel frames per row - long mels of different lengths padded to T share
+        the call.  Row b's first lengths[b] * out_tmul samples are the chunk loop over that clip alone on the same grid
+        (harness.plan_chunk_calls; bit for bit in every chunk where the row's frames and the chunk's width agree mod 4 - always when chunk,
+        halo, T and the lengths are multiples of 4 - to fp32 roundoff elsewhere), the rest of the row is zero, a row that ended before a
+        chunk is not run in it, and the padding of x is never read.  None, or every row full, is the call without lengths."""
         assert self.which == L.NET_VOCODER
         x = x.to(self.ctx.device, torch.float32).contiguous()
         B, Cin, T = x.shape
         assert Cin == self.in_ch
+        lens = hold = None
+        if lengths is not None:
+            if chunk < 1 or halo < 0:
+                raise ValueError(f"run_chunked: chunk = {chunk}, halo = {halo} (chunk >= 1, halo >= 0)")
+            lens, hold, _ = _lens_struct(lengths, B, T, gloss=" (input frames per row)")
         if T <= chunk + 2 * halo:
-            return self.run(x)
+            return self.run(x) if lens is None else self._run_lens(x, B, T, lens, hold)
         tc = chunk + 2 * halo
         dev = self.ctx.device
         out = torch.empty(B, self.out_ch, T * self.out_tmul, dtype=torch.float32, device=dev)
-        ws = self._workspace(B, tc)
         cin, cout = self._cached("chunk", (B, tc), lambda: (torch.empty(B * self.in_ch * tc, dtype=torch.float32, device=dev),
                                                             torch.empty(B * self.out_ch * tc * self.out_tmul, dtype=torch.float32, device=dev)))
+        if lens is not None:
+            lib = self.ctx.lib
+            ws = self._cached("chunk_lens", (B, tc), lambda: self._bytes(lib.vb_hifigan_chunked_lens_workspace_bytes(self.ctx.handle, B, T, chunk, halo)))
+            L.check(lib.vb_hifigan_forward_chunked_lens(self.ctx.handle, L.ptr(x), B, T, chunk, halo, C.byref(lens), L.ptr(out), L.ptr(ws), L.ptr(cin),
+                                                        L.ptr(cout), L.stream_ptr()), "vb_hifigan_forward_chunked_lens")
+            del hold                     # (the host array of the lengths: read during the call only)
+            return out
+        ws = self._workspace(B, tc)
         L.check(self.ctx.lib.vb_hifigan_forward_chunked(self.ctx.handle, L.ptr(x), B, T, chunk, halo, L.ptr(out), L.ptr(ws), L.ptr(cin), L.ptr(cout),
                                                         L.stream_ptr()), "vb_hifigan_forward_chunked")
         return out

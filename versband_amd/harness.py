@@ -243,6 +243,35 @@ def plan_vocoder_calls(row_lengths_mel) -> List[dict]:
     return calls
 
 
+def plan_chunk_calls(lengths, T: int, chunk: int, halo: int) -> List[dict]:
+    """The Python mirror of vb_hifigan_chunked_lens_plan (include/versband_hip.h): the steps of the chunked vocoder over B mels of the
+    given lengths (frames) padded to T, as a list of
+        {"s", "e", "lo", "tc", "rows": [active rows, ascending], "n": [frames of each active row inside the chunk]}
+    The grid is the plain loop's: s = 0, chunk, 2 chunk, ... < T, e = min(s + chunk, T), lo = max(0, s - halo); T <= chunk + 2 halo is one
+    step over the whole rows (s = lo = 0, e = T).  A row is active in a step when lengths[b] > s, has n = min(lengths[b], s + chunk + halo)
+    - lo frames in it, and keeps the samples of its frames [s, min(e, lengths[b])); tc = the longest n (0 where no row is active).  A
+    row equals the chunk loop over the clip alone bit for bit in every step where n % 4 == tc % 4."""
+    lens = [int(v) for v in lengths]
+    T, chunk, halo = int(T), int(chunk), int(halo)
+    if chunk < 1 or halo < 0:
+        raise ValueError(f"plan_chunk_calls: chunk = {chunk}, halo = {halo} (chunk >= 1, halo >= 0)")
+    if not 1 <= len(lens) <= 64:
+        raise ValueError(f"plan_chunk_calls: {len(lens)} rows (1..64)")
+    for b, v in enumerate(lens):
+        if not 1 <= v <= T:
+            raise ValueError(f"plan_chunk_calls: row {b} has length {v} (1..T = {T})")
+    whole = T <= chunk + 2 * halo
+    steps = []
+    for s in ([0] if whole else range(0, T, chunk)):
+        e = T if whole else min(s + chunk, T)
+        lo = 0 if whole else max(0, s - halo)
+        hi = T if whole else s + chunk + halo
+        rows = [b for b, v in enumerate(lens) if v > s]
+        n = [min(lens[b], hi) - lo for b in rows]
+        steps.append({"s": s, "e": e, "lo": lo, "tc": max(n, default=0), "rows": rows, "n": n})
+    return steps
+
+
 DECODE_ROUTE_MOD = 4        # the VAE decoder's bits depend on a latent length through its residue mod 4 alone (include/versband_hip.h, vb_vae_decode_lens)
 
 

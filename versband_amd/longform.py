@@ -252,11 +252,43 @@ def _sample_continue(engine, x0, t5_cond, t5_uncond, midi, beats, t_idx_table, d
     return (out, parts) if return_windows else out
 
 
-def vocode_chunked(vocoder_net, mel: Tensor, chunk: int = 2048, halo: int = 32) -> Tensor:
+def vocode_chunked(vocoder_net, mel: Tensor, chunk: int = 2048, halo: int = 32, lengths=None) -> Tensor:
     """mel [B,80,T] -> wav [B,1,T*hop] in chunks of `chunk` frames with `halo` frames of context on both sides;
-    identical to whole-clip vocoding when halo >= the generator's receptive field (in frames)."""
+    identical to whole-clip vocoding when halo >= the generator's receptive field (in frames).
+    lengths: B mel lengths <= T - long mels of DIFFERENT lengths padded to T in one call (ConvNet.run_chunked(lengths=),
+    vb_hifigan_forward_chunked_lens).  Row b holds lengths[b] * hop samples - the chunk loop over that clip alone on the same grid
+    (harness.plan_chunk_calls) - followed by zeros; a row that ended before a chunk is not run in it and the mel padding is never read.
+    None, or every row full, is the call without lengths."""
     B, _, T = mel.shape
     hop = vocoder_net.out_tmul
+    if lengths is not None:
+        lengths = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        if len(lengths) != B:
+            raise ValueError(f"vocode_chunked: lengths has {len(lengths)} entries for {B} rows")
+        for b, n in enumerate(lengths):
+            if not 1 <= n <= T:
+                raise ValueError(f"vocode_chunked: lengths[{b}] = {n} is not in [1, T = {T}]")
+        if all(n == T for n in lengths):
+            lengths = None
+    if lengths is not None:
+        if hasattr(vocoder_net, "run_chunked"):
+            return vocoder_net.run_chunked(mel, chunk, halo, lengths=lengths)
+        if T <= chunk + 2 * halo:
+            return vocoder_net.run(mel, lengths=lengths)
+        # the torch restatement of the plan: per chunk the rows that reach into it, masked at their own ends, through the lengths call
+        from . import harness
+        out = torch.zeros(B, vocoder_net.out_ch, T * hop, dtype=torch.float32, device=mel.device)
+        for c in harness.plan_chunk_calls(lengths, T, chunk, halo):
+            if not c["rows"]:
+                continue
+            x = torch.zeros(len(c["rows"]), mel.shape[1], c["tc"], dtype=mel.dtype, device=mel.device)
+            for j, (b, n) in enumerate(zip(c["rows"], c["n"])):
+                x[j, :, :n] = mel[b, :, c["lo"]:c["lo"] + n]
+            w = vocoder_net.run(x, **({} if all(n == c["tc"] for n in c["n"]) else {"lengths": c["n"]}))
+            for j, b in enumerate(c["rows"]):
+                e = min(c["e"], lengths[b])
+                out[b, :, c["s"] * hop:e * hop] = w[j, :, (c["s"] - c["lo"]) * hop:(e - c["lo"]) * hop]
+        return out
     if T <= chunk + 2 * halo:
         return vocoder_net.run(mel)
     if hasattr(vocoder_net, "run_chunked"):
@@ -269,4 +301,40 @@ def vocode_chunked(vocoder_net, mel: Tensor, chunk: int = 2048, halo: int = 32) 
         w = vocoder_net.run(mel[:, :, lo:hi].contiguous())
         out[:, :, s * hop:e * hop] = w[:, :, (s - lo) * hop:(e - lo) * hop]
         s = e
+    return out
+
+
+def render_long(vae_net, vocoder_net, z: Tensor, lengths=None, chunk: int = 3000, halo: int = 32):
+    """latents z [B,zc,T] of B long clips -> their waveforms: the VAE decode and the chunked vocoder, both with row lengths.
+    lengths: B latent lengths <= T (tokens).  The rows are decoded in one call per residue of the latent length mod 4
+    (harness.plan_decode_calls, ConvNet.decode_lens) and each residue group of the mel lengths (harness.plan_vocoder_calls) is vocoded
+    through the chunked lengths call (vocode_chunked(lengths=)); returns a list of B waveforms [out_ch, mel frames * hop] cut to their
+    own lengths, each the decode + chunk loop on that clip alone (bit for bit when chunk and halo are multiples of 4: the members of a
+    group share their residue, hence so do a row's frames and the width of every chunk).  None: decode + vocode_chunked of the whole
+    batch, returned as one tensor [B, out_ch, mel frames * hop] as today."""
+    from . import harness
+    if lengths is None:
+        return vocode_chunked(vocoder_net, vae_net.run(z), chunk, halo)
+    B, _, T = z.shape
+    lengths = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+    if len(lengths) != B:
+        raise ValueError(f"render_long: lengths has {len(lengths)} entries for {B} clips")
+    for b, n in enumerate(lengths):
+        if not 1 <= n <= T:
+            raise ValueError(f"render_long: lengths[{b}] = {n} is not in [1, T = {T}]")
+    up, hop = vae_net.out_tmul, vocoder_net.out_tmul
+    mels = [None] * B
+    for c in harness.plan_decode_calls(lengths):
+        zz = z[c["rows"], :, :c["length"]].contiguous()
+        mel = vae_net.run(zz) if c["lengths"] is None else vae_net.decode_lens(zz, c["lengths"])
+        for j, b in enumerate(c["rows"]):
+            mels[b] = mel[j, :, :lengths[b] * up]
+    out = [None] * B
+    for c in harness.plan_vocoder_calls([lengths[b] * up for b in range(B)]):
+        x = torch.zeros(len(c["rows"]), mels[0].shape[0], c["length"], dtype=torch.float32, device=mels[0].device)
+        for j, b in enumerate(c["rows"]):
+            x[j, :, :mels[b].shape[1]] = mels[b]
+        wav = vocode_chunked(vocoder_net, x, chunk, halo, lengths=c["lengths"])
+        for j, b in enumerate(c["rows"]):
+            out[b] = wav[j, :, :lengths[b] * up * hop]
     return out

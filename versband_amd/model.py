@@ -660,10 +660,15 @@ class HifiGAN:
         c = c.transpose(2, 1).contiguous()
         return self.net().run(c).view(-1).cpu().numpy()
 
-    def spec2wav_batch(self, mel_bct: Tensor, lengths=None) -> Tensor:
+    def spec2wav_batch(self, mel_bct: Tensor, lengths=None, chunk=None, halo: int = 32) -> Tensor:
         """device-resident batched path: mel [B,80,T] -> wav [B, T*hop] (no host round trip).
         lengths (addition; ConvNet.run): one length in mel frames per row - mels of different lengths padded to T share the call, row b
-        holds lengths[b] * hop samples of the clip alone followed by zeros, the mel padding is never read."""
+        holds lengths[b] * hop samples of the clip alone followed by zeros, the mel padding is never read.
+        chunk (addition; longform.vocode_chunked): long mels in chunks of `chunk` frames with `halo` frames of context on both sides,
+        with or without lengths; None is the whole-row call."""
+        if chunk is not None:
+            from . import longform
+            return longform.vocode_chunked(self.net(), mel_bct, chunk, halo, lengths=lengths).squeeze(1)
         return self.net().run(mel_bct, **({} if lengths is None else {"lengths": lengths})).squeeze(1)
 
     def __call__(self, mel):
