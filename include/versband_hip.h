@@ -445,7 +445,8 @@ int vb_hifigan_forward(vb_ctx* ctx, const float* mel, int B, int T, float* wav, 
  * Refused with VB_E_INVALID before anything is launched, naming the op and why: a vocoder program with an op other than VB_OP_CONV /
  * VB_OP_RESPAIR / VB_OP_XT_PLANES (BigVGAN's VB_OP_AA_ACT: its anti-aliasing filters replicate-pad at the row end), an input activation
  * other than none / LeakyReLU, GroupNorm statistics, dynamic channel counts, w_buf weights, a transposed output.  The VAE encoder takes
- * no lengths; the VAE decoder and the chunked vocoder have their own entry points (vb_vae_decode_lens, vb_hifigan_forward_chunked_lens).
+ * no lengths; the VAE decoder, the chunked vocoder and BigVGAN have their own entry points (vb_vae_decode_lens,
+ * vb_hifigan_forward_chunked_lens, vb_bigvgan_forward_lens / vb_bigvgan_forward_chunked_lens).
  * ws: vb_hifigan_lens_workspace_bytes(ctx, B, T) bytes = vb_net_workspace_bytes + the masked mel + the length table.  Hosts detect the
  * feature by the presence of these symbols (vb_abi_version() stays 3). */
 size_t vb_hifigan_lens_workspace_bytes(vb_ctx* ctx, int B, int T);
@@ -479,8 +480,8 @@ int vb_hifigan_forward_lens(vb_ctx* ctx, const float* mel, int B, int T, const v
  *                         the other, or a glue kernel its float4 path).
  * No op had to be excepted.  A host that wants bit-exact rows groups its clips by length mod 4 (harness.plan_decode_calls).
  * Refused with VB_E_INVALID before anything is launched, naming the op and why: VB_OP_AA_ACT, VB_OP_RESPAIR, in_stride > 1, tr_stride > 1
- * (ops the decoder's program does not contain).  The VAE encoder (Downsample1D pads on the right of the row's own end) and BigVGAN
- * take no lengths.
+ * (ops the decoder's program does not contain).  The VAE encoder (Downsample1D pads on the right of the row's own end) is the one net
+ * that takes equal-length rows only; BigVGAN takes lengths through vb_bigvgan_forward_lens.
  * ws: vb_vae_decode_lens_workspace_bytes(ctx, B, T) bytes = vb_net_workspace_bytes + the masked latent + the length table.  Hosts detect
  * the feature by the presence of these symbols (vb_abi_version() stays 3, vb_net_op is unchanged). */
 size_t vb_vae_decode_lens_workspace_bytes(vb_ctx* ctx, int B, int T);
@@ -524,7 +525,7 @@ int vb_hifigan_forward_chunked(vb_ctx* ctx, const float* mel, int B, int T, int 
  * T <= chunk + 2*halo: vb_hifigan_forward_lens (the workspace below covers it).
  * Refused with VB_E_INVALID before anything is launched, wav untouched: B > 64 or a length outside [1, T] (the row is named), chunk < 1 or
  * halo < 0, no vocoder loaded, a program that takes no row lengths (the message of vb_hifigan_forward_lens, naming the op: BigVGAN's
- * VB_OP_AA_ACT).  scratch_in / scratch_out as for vb_hifigan_forward_chunked at (B, chunk + 2*halo); ws:
+ * VB_OP_AA_ACT, which vb_bigvgan_forward_chunked_lens takes).  scratch_in / scratch_out as for vb_hifigan_forward_chunked at (B, chunk + 2*halo); ws:
  * vb_hifigan_chunked_lens_workspace_bytes = the net's workspace at (B, chunk + 2*halo) + the length table, or the lens call's at (B, T).
  * Hosts detect the feature by the presence of these symbols (vb_abi_version() stays 3). */
 size_t vb_hifigan_chunked_lens_workspace_bytes(vb_ctx* ctx, int B, int T, int chunk, int halo);
@@ -532,6 +533,34 @@ int vb_hifigan_forward_chunked_lens(vb_ctx* ctx, const float* mel, int B, int T,
                                     float* scratch_in, float* scratch_out, void* stream);
 int vb_hifigan_chunked_lens_plan(int B, int T, int chunk, int halo, const int32_t* len, int max_chunks, int32_t* s, int32_t* lo, int32_t* tc,
                                  int32_t* n_active, int32_t* rows, int32_t* n, int* n_chunks);
+/* BigVGAN with ROW LENGTHS (build-defined), for a program loaded as VB_NET_VOCODER: mels of different lengths as rows of one vocoder call,
+ * whole rows or chunked.  Arguments, checks and workspaces as for vb_hifigan_forward_lens / vb_hifigan_forward_chunked_lens: mel
+ * [B][in_ch][T], T the padded length; lens->len the HOST array of B mel-frame lengths, 1 <= len[b] <= T, B <= 64.
+ * CONTRACT.  Row b's first len[b]*hop samples are vb_hifigan_forward on that clip alone - BIT FOR BIT when len[b] == T (mod 4), to the
+ * precision's roundoff otherwise: THE ROUTE RULE of vb_hifigan_forward_lens, unchanged (VB_OP_AA_ACT adds no predicate on a length: one
+ * kernel, one tile grid from sample 0, whatever T).  The rest of the row is exact zeros.  The caller's mel padding is never read into a
+ * valid sample (it may hold NaN).  lens == NULL, len == NULL or every row full is vb_hifigan_forward (chunked: vb_hifigan_forward_chunked)
+ * on the same buffers: same launches, same bits.  The chunked call is the chunk loop over the clip alone on the same grid, in the words
+ * of vb_hifigan_forward_chunked_lens (plan: vb_hifigan_chunked_lens_plan; bit for bit in every chunk where n_j == tc_k (mod 4)).
+ * How it works.  The generator's convolutions have no input activation and zero-pad, its transposed convolutions are the HiFi-GAN's,
+ * residual adds and tanh write buffers that get the tail-zero launch: the zero-tail machinery of vb_hifigan_forward_lens carries them.
+ * VB_OP_AA_ACT, out = down2(snake(up2(x))), REPLICATE-pads at the row end in both filters, which no tail value can stand in for: its kernel
+ * reads the device table of lengths and takes row b's end, len[b]*tmul, for the three bounds that are T in the plain call - the clamp of
+ * the input window, the clamp of the up-sampled index, the store bound.  Nothing at or behind x[b][c][len[b]*tmul] is loaded (whatever an
+ * earlier op left there, NaN included), the outputs behind the row's end are written as exact zeros by the same kernel (no tail-zero
+ * launch follows it), and a workgroup whose 256 outputs all lie behind the end stores zeros and returns before it loads anything.  A
+ * valid output is computed by the instructions of the plain call in their order.
+ * Refused with VB_E_INVALID before anything is launched, wav untouched: B > 64 or a length outside [1, T] (the row is named), chunk < 1
+ * or halo < 0, no vocoder loaded, and a program with an op other than VB_OP_CONV / VB_OP_RESPAIR / VB_OP_XT_PLANES / VB_OP_AA_ACT or with
+ * anything else vb_hifigan_forward_lens refuses (the op is named).  The HiFi-GAN entry points keep refusing VB_OP_AA_ACT.
+ * ws: vb_bigvgan_lens_workspace_bytes = vb_net_workspace_bytes + the masked mel + the length table; chunked:
+ * vb_bigvgan_chunked_lens_workspace_bytes = vb_hifigan_chunked_lens_workspace_bytes, scratch_in / scratch_out as there.  Hosts detect
+ * the feature by the presence of these symbols (vb_abi_version() stays 3, vb_net_op is unchanged). */
+size_t vb_bigvgan_lens_workspace_bytes(vb_ctx* ctx, int B, int T);
+int vb_bigvgan_forward_lens(vb_ctx* ctx, const float* mel, int B, int T, const vb_lens* lens, float* wav, void* ws, void* stream);
+size_t vb_bigvgan_chunked_lens_workspace_bytes(vb_ctx* ctx, int B, int T, int chunk, int halo);
+int vb_bigvgan_forward_chunked_lens(vb_ctx* ctx, const float* mel, int B, int T, int chunk, int halo, const vb_lens* lens, float* wav, void* ws,
+                                    float* scratch_in, float* scratch_out, void* stream);
 
 /* ------------------------------------------------------------ T5 text encoder ----
  * FrozenTextVocalEmbedder.forward (ldm/modules/encoders/modules.py:216-233): T5EncoderModel(input_ids).last_hidden_state, no
@@ -699,6 +728,12 @@ int vb_xt_planes(const float* x, int B, int C, int T_in, int upsample2, int in_a
  * out_t [B][T][T] of row b's leading len[b] x len[b] block, exact zeros elsewhere. */
 int vb_gn_stats_lens(const float* x, int B, int C, int T, int groups, const int32_t* len, float* mean, float* rstd, void* stream);
 int vb_softmax_rows_t_lens(const float* s, int B, int T, const int32_t* len, float* out_t, void* stream);
+/* VB_OP_AA_ACT alone (build-defined unit): x [B][C][T] -> out [B][C][T] = down2(snake(up2(x))) with alpha / inv_beta [C] as the op holds
+ * them (alpha exp'ed when log-scale, inv_beta = 1 / (beta + 1e-9)) and filt the 12-tap Kaiser-sinc filter.  len: DEVICE array of B row
+ * lengths or NULL (the plain kernel); row b ends at len[b] * len_mul <= T samples (len_mul >= 1: the stage's samples per frame): its valid
+ * outputs are the plain kernel's on that clip alone bit for bit, nothing at or behind its end is read, out is exact zeros behind it. */
+int vb_aa_act(const float* x, const float* alpha, const float* inv_beta, const float* filt, int B, int C, int T, const int32_t* len, int len_mul,
+              float* out, void* stream);
 /* HiFi-GAN ResBlock1 pair in single-pass bf16, one launch (respair_bf16.hip):
  *   out = beta*out + alpha*(x + b2 + conv2_{k,1}( RN_bf16( lrelu(b1 + conv1_{k,dil}( RN_bf16(lrelu(x)) )) ) ))
  * both convolutions with RN-bf16 weights (w1_bf16 / w2_bf16: one plane [k][C co][C ci] each, pack.py:pack_conv_bf16), exact products, fp32

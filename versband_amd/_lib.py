@@ -162,6 +162,11 @@ PROTOTYPES = {
     "vb_hifigan_chunked_lens_workspace_bytes": (c_size_t, [P, c_int, c_int, c_int, c_int]),
     "vb_hifigan_forward_chunked_lens": (c_int, [P, P, c_int, c_int, c_int, c_int, C.POINTER(Lens), P, P, P, P, P]),
     "vb_hifigan_chunked_lens_plan": (c_int, [c_int, c_int, c_int, c_int, P, c_int, P, P, P, P, P, P, C.POINTER(c_int)]),
+    "vb_bigvgan_lens_workspace_bytes": (c_size_t, [P, c_int, c_int]),
+    "vb_bigvgan_forward_lens": (c_int, [P, P, c_int, c_int, C.POINTER(Lens), P, P, P]),
+    "vb_bigvgan_chunked_lens_workspace_bytes": (c_size_t, [P, c_int, c_int, c_int, c_int]),
+    "vb_bigvgan_forward_chunked_lens": (c_int, [P, P, c_int, c_int, c_int, c_int, C.POINTER(Lens), P, P, P, P, P]),
+    "vb_aa_act": (c_int, [P, P, P, P, c_int, c_int, c_int, P, c_int, P, P]),
     "vb_melnet_load": (c_int, [P, C.POINTER(MelConfig), P, P]),
     "vb_melnet_frames": (c_int, [C.POINTER(MelConfig), c_int, c_int]),
     "vb_melnet_workspace_bytes": (C.c_size_t, [C.POINTER(MelConfig), c_int, c_int, c_int]),

@@ -198,6 +198,11 @@ int vb_softmax_rows_t_lens(const float* s, int B, int T, const int32_t* len, flo
     if (!len) return launch_softmax_rows_t(s, B, T, T, out_t, (hipStream_t)stream);
     return launch_softmax_rows_t_lens(s, B, T, len, 1, out_t, (hipStream_t)stream);
 }
+int vb_aa_act(const float* x, const float* alpha, const float* inv_beta, const float* filt, int B, int C, int T, const int32_t* len, int len_mul,
+              float* out, void* stream) {
+    if (!x || !alpha || !inv_beta || !filt || !out || B < 1 || C < 1 || T < 1) VB_FAIL(VB_E_INVALID, "aa_act: null pointer or B/C/T < 1");
+    return launch_aa_act(x, alpha, inv_beta, filt, B, C, T, out, (hipStream_t)stream, len, len_mul);
+}
 size_t vb_conv1d_bf16_xt_scratch_bytes(int B, int Ci, int T_in, int upsample2) { return vb_xt_planes_bytes(B, Ci, T_in, upsample2, 1); }
 int vb_conv1d_bf16_xt(const float* x, const void* w_bf16, int ci_pad, const float* bias, int B, int Ci, int T_in, int Co, int ksize, int dil,
                       int pad, int tr_stride, int tr_pad, int tr_k, int T_out, int upsample2, int in_stride, int in_phase, int in_act,

@@ -117,7 +117,8 @@ int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, v
                                     o.upsample2, B, o.Ci, tlen(o.x), o.wfmt == VB_WFMT_BF16 ? 1 : 2, reinterpret_cast<bf16_t*>(ptr(o.out)), st,
                                     nl ? nl->table : nullptr, tmul(o.x) * (o.upsample2 ? 2 : 1)));
         } else if (o.kind == VB_OP_AA_ACT) {
-            VB_TRY(launch_aa_act(ptr(o.x), o.gn_gamma, o.gn_beta, o.w, B, o.Ci, tlen(o.x), ptr(o.out), st));
+            // (lengths: both filters replicate-pad at the row's own end, and the kernel writes the zeros behind it itself)
+            VB_TRY(launch_aa_act(ptr(o.x), o.gn_gamma, o.gn_beta, o.w, B, o.Ci, tlen(o.x), ptr(o.out), st, nl ? nl->table : nullptr, tmul(o.x)));
         } else if (o.kind == VB_OP_RESPAIR) {
             if (o.wfmt == VB_WFMT_X3 || o.wfmt == VB_WFMT_BF16) {
                 RespairArgs r;
@@ -144,10 +145,14 @@ int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, v
             VB_FAIL(VB_E_INVALID, "net op %zu: bad kind %d", oi, o.kind);
         }
         // The tails of what the op wrote.  No pass: the planes of VB_OP_XT_PLANES (zero rows behind the row's end by its own bound) and of
-        // VB_OP_SPLIT_PLANES (made from buffers whose tails are zero), the statistics, the transposed softmax (writes its zeros itself) and the
-        // square score buffer, of which the lengths softmax reads the row's own block alone.  A transposed output [T][C] ends in the
-        // contiguous rows t >= len: one row of T * C samples per clip.
-        if (!nl || o.kind == VB_OP_XT_PLANES || o.kind == VB_OP_SPLIT_PLANES || o.kind == VB_OP_GN_STATS || o.kind == VB_OP_SOFTMAX_T) continue;
+        // VB_OP_SPLIT_PLANES (made from buffers whose tails are zero), the statistics, the transposed softmax (writes its zeros itself), the
+        // anti-aliased activation (VB_OP_AA_ACT: with a length table its store bound is the row's own end and it writes exact zeros from
+        // there to the pitch, whole workgroups of them before they load anything) and the square score buffer, of which the lengths
+        // softmax reads the row's own block alone.  A transposed output [T][C] ends in the contiguous rows t >= len: one row of T * C
+        // samples per clip.
+        if (!nl || o.kind == VB_OP_XT_PLANES || o.kind == VB_OP_SPLIT_PLANES || o.kind == VB_OP_GN_STATS || o.kind == VB_OP_SOFTMAX_T
+            || o.kind == VB_OP_AA_ACT)
+            continue;
         if (o.out >= 0 && n.bufs[o.out].square == 1) continue;
         if (o.kind == VB_OP_CONV && o.out_transposed) VB_TRY(launch_tail_zero(ptr(o.out), nl->lp, nl->table, B, 1, T, tmul(o.out) * chans(o.out), st));
         else VB_TRY(launch_tail_zero(ptr(o.out), nl->lp, nl->table, B, chans(o.out), T, tmul(o.out), st));
@@ -157,14 +162,18 @@ int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, v
 // What a program must be to take row lengths, per net.  The vocoder (include/versband_hip.h, vb_hifigan_forward_lens) works by zero tails
 // alone: every op computes a sample from a zero-padded window of its own row, through an input activation with f(0) = 0, into a plain
 // [B][C][T] buffer.  The VAE decoder (vb_vae_decode_lens) adds what net_run gives a length table to - GroupNorm statistics and inputs, the
-// attention's dynamic channel counts, w_buf weights, transposed outputs - and refuses whatever its program does not contain.
-static int net_lens_check(const NetProgram& n, int which) {
+// attention's dynamic channel counts, w_buf weights, transposed outputs - and refuses whatever its program does not contain.  BigVGAN
+// (vb_bigvgan_forward_lens) is the vocoder's contract plus VB_OP_AA_ACT, whose kernel takes the row's own end from the length table; the
+// HiFi-GAN entry points keep refusing that op, so what they accept is what they accepted before the kernel learned it.
+enum { LENS_VAE_DECODER = 0, LENS_VOCODER = 1, LENS_BIGVGAN = 2 };
+static int net_lens_check(const NetProgram& n, int contract) {
+    const char* const fn = contract == LENS_BIGVGAN ? "bigvgan_forward_lens" : "hifigan_forward_lens";
     static const char* const kinds[] = {"VB_OP_CONV", "VB_OP_GN_STATS", "VB_OP_SOFTMAX_T", "VB_OP_SPLIT_PLANES", "VB_OP_RESPAIR", "VB_OP_GN_APPLY",
                                         "VB_OP_AA_ACT", "VB_OP_XT_PLANES"};
     for (size_t oi = 0; oi < n.ops.size(); ++oi) {
         const vb_net_op& o = n.ops[oi];
         const char* kn = o.kind >= 0 && o.kind <= VB_OP_XT_PLANES ? kinds[o.kind] : "unknown kind";
-        if (which == VB_NET_VAE) {
+        if (contract == LENS_VAE_DECODER) {
             if (o.kind == VB_OP_AA_ACT)
                 VB_FAIL(VB_E_INVALID, "vae_decode_lens: op %zu (%s): its anti-aliasing filters replicate-pad at the row end, which row lengths do not describe", oi, kn);
             if (o.kind == VB_OP_RESPAIR || o.kind < 0 || o.kind > VB_OP_XT_PLANES)
@@ -175,38 +184,45 @@ static int net_lens_check(const NetProgram& n, int which) {
                 VB_FAIL(VB_E_INVALID, "vae_decode_lens: op %zu (%s): a transposed convolution (tr_stride = %d) is not an op of the VAE decoder's program", oi, kn, o.tr_stride);
             continue;
         }
+        if (o.kind == VB_OP_AA_ACT && contract == LENS_BIGVGAN) {
+            // (out = f(x) of the row's own samples, no weights of a whole row, no statistics: all it needs is a plain [B][C][T] pair of buffers)
+            if (o.Ci <= 0 || (o.x >= 0 && n.bufs[o.x].square != 0) || (o.out >= 0 && n.bufs[o.out].square != 0))
+                VB_FAIL(VB_E_INVALID, "%s: op %zu (%s): Ci = %d, or a buffer that is not [B][C][T]", fn, oi, kn, o.Ci);
+            continue;
+        }
         if (o.kind == VB_OP_AA_ACT)
-            VB_FAIL(VB_E_INVALID, "hifigan_forward_lens: op %zu (%s): its anti-aliasing filters replicate-pad at the row end, which a zero tail cannot stand in for", oi, kn);
+            VB_FAIL(VB_E_INVALID, "%s: op %zu (%s): its anti-aliasing filters replicate-pad at the row end, which a zero tail cannot stand in for", fn, oi, kn);
         if (o.kind != VB_OP_CONV && o.kind != VB_OP_RESPAIR && o.kind != VB_OP_XT_PLANES)
-            VB_FAIL(VB_E_INVALID, "hifigan_forward_lens: op %zu (%s): only VB_OP_CONV, VB_OP_RESPAIR and VB_OP_XT_PLANES take row lengths", oi, kn);
+            VB_FAIL(VB_E_INVALID, "%s: op %zu (%s): only VB_OP_CONV, VB_OP_RESPAIR and VB_OP_XT_PLANES%s take row lengths", fn, oi, kn,
+                    contract == LENS_BIGVGAN ? " (and VB_OP_AA_ACT)" : "");
         if (o.in_act != ACT_NONE && o.in_act != ACT_LRELU)
-            VB_FAIL(VB_E_INVALID, "hifigan_forward_lens: op %zu (%s): input activation %d does not map 0 to 0 (none / LeakyReLU only)", oi, kn, o.in_act);
-        if (o.stats != -1) VB_FAIL(VB_E_INVALID, "hifigan_forward_lens: op %zu (%s): GroupNorm statistics run over the whole row", oi, kn);
+            VB_FAIL(VB_E_INVALID, "%s: op %zu (%s): input activation %d does not map 0 to 0 (none / LeakyReLU only)", fn, oi, kn, o.in_act);
+        if (o.stats != -1) VB_FAIL(VB_E_INVALID, "%s: op %zu (%s): GroupNorm statistics run over the whole row", fn, oi, kn);
         if (o.Ci <= 0 || (o.kind != VB_OP_XT_PLANES && o.Co <= 0))
-            VB_FAIL(VB_E_INVALID, "hifigan_forward_lens: op %zu (%s): a dynamic channel count (Ci = %d, Co = %d) contracts over the row length", oi, kn, o.Ci, o.Co);
-        if (o.w_buf != -1) VB_FAIL(VB_E_INVALID, "hifigan_forward_lens: op %zu (%s): w_buf weights are made from whole rows", oi, kn);
-        if (o.out_transposed) VB_FAIL(VB_E_INVALID, "hifigan_forward_lens: op %zu (%s): a transposed output is not a [B][C][T] buffer", oi, kn);
+            VB_FAIL(VB_E_INVALID, "%s: op %zu (%s): a dynamic channel count (Ci = %d, Co = %d) contracts over the row length", fn, oi, kn, o.Ci, o.Co);
+        if (o.w_buf != -1) VB_FAIL(VB_E_INVALID, "%s: op %zu (%s): w_buf weights are made from whole rows", fn, oi, kn);
+        if (o.out_transposed) VB_FAIL(VB_E_INVALID, "%s: op %zu (%s): a transposed output is not a [B][C][T] buffer", fn, oi, kn);
         if (o.kind != VB_OP_XT_PLANES && o.out >= 0 && n.bufs[o.out].square != 0)
-            VB_FAIL(VB_E_INVALID, "hifigan_forward_lens: op %zu (%s): writes a buffer of square = %d, not [B][C][T]", oi, kn, n.bufs[o.out].square);
+            VB_FAIL(VB_E_INVALID, "%s: op %zu (%s): writes a buffer of square = %d, not [B][C][T]", fn, oi, kn, n.bufs[o.out].square);
     }
     return VB_OK;
 }
 
-// The one lengths path of both nets (vb_hifigan_forward_lens, vb_vae_decode_lens).  Workspace: the net's own, the masked input, the table of
-// row lengths.
+// The one lengths path of the nets (vb_hifigan_forward_lens, vb_vae_decode_lens, vb_bigvgan_forward_lens; contract: what net_lens_check
+// holds the program to).  Workspace: the net's own, the masked input, the table of row lengths.
 static size_t net_lens_ws_bytes(vb_ctx* ctx, int which, int B, int T) {
     if (!ctx || !ctx->nets[which].loaded || B < 1 || T < 1) return 0;
     const NetProgram& n = ctx->nets[which];
     return net_ws_bytes(n, B, T, nullptr) + align_up((size_t)B * n.in_ch * T * n.in_tmul * sizeof(float)) + align_up(64 * sizeof(int));
 }
-static int net_run_lens(vb_ctx* ctx, int which, const char* fn, const char* net, const float* in, int B, int T, const vb_lens* lens, float* out,
-                        void* ws, hipStream_t st) {
+static int net_run_lens(vb_ctx* ctx, int which, int contract, const char* fn, const char* net, const float* in, int B, int T, const vb_lens* lens,
+                        float* out, void* ws, hipStream_t st) {
     NetLens nl;
     if (lens && lens->len) VB_TRY(lens_plan(lens->len, B, T, &nl.lp));
     if (!nl.lp.B) return net_run(ctx, which, in, B, T, out, ws, st);                   // no lengths, or every row full: the plain entry point
     NetProgram& n = ctx->nets[which];
     if (!n.loaded) VB_FAIL(VB_E_STATE, "%s: no %s loaded", fn, net);
-    VB_TRY(net_lens_check(n, which));
+    VB_TRY(net_lens_check(n, contract));
     if (n.in_tmul != 1) VB_FAIL(VB_E_INVALID, "%s: the %s's input runs at %d samples per frame (1)", fn, net, n.in_tmul);
     VB_HIP(hipSetDevice(ctx->device));
     char* p = static_cast<char*>(ws) + net_ws_bytes(n, B, T, nullptr);
@@ -276,6 +292,58 @@ static int net_op_fields(int kind, int wfmt, int Co) {
         return wfmt == VB_WFMT_NONE ? 0 : -1;
     }
     return -1;
+}
+
+// The chunked vocoder with row lengths, behind vb_hifigan_forward_chunked_lens (contract LENS_VOCODER, fn "hifigan_forward") and
+// vb_bigvgan_forward_chunked_lens (LENS_BIGVGAN, "bigvgan_forward"): one plan, one gather / scatter, one loop.
+static int chunked_lens_run(vb_ctx* ctx, int contract, const char* fn, const float* mel, int B, int T, int chunk, int halo, const vb_lens* lens,
+                            float* wav, void* ws, float* scratch_in, float* scratch_out, void* stream) {
+    if (!ctx) VB_FAIL(VB_E_INVALID, "%s_chunked_lens: null ctx", fn);
+    if (chunk < 1 || halo < 0) VB_FAIL(VB_E_INVALID, "%s_chunked_lens: chunk=%d halo=%d", fn, chunk, halo);
+    NetProgram& net = ctx->nets[VB_NET_VOCODER];
+    if (!net.loaded) VB_FAIL(VB_E_INVALID, "%s_chunked_lens: no vocoder loaded", fn);
+    if (!lens || !lens->len) return vb_hifigan_forward_chunked(ctx, mel, B, T, chunk, halo, wav, ws, scratch_in, scratch_out, stream);
+    std::vector<ChunkStep> plan;
+    VB_TRY(chunk_lens_plan(B, T, chunk, halo, lens->len, &plan));
+    bool full = true;
+    for (int b = 0; b < B; ++b) full = full && lens->len[b] == T;
+    if (full) return vb_hifigan_forward_chunked(ctx, mel, B, T, chunk, halo, wav, ws, scratch_in, scratch_out, stream);
+    if (T <= (int64_t)chunk + 2 * (int64_t)halo)
+        return contract == LENS_BIGVGAN ? vb_bigvgan_forward_lens(ctx, mel, B, T, lens, wav, ws, stream) : vb_hifigan_forward_lens(ctx, mel, B, T, lens, wav, ws, stream);
+    VB_TRY(net_lens_check(net, contract));
+    if (net.in_tmul != 1) VB_FAIL(VB_E_INVALID, "%s_chunked_lens: the vocoder's input runs at %d samples per frame (1)", fn, net.in_tmul);
+    hipStream_t st = (hipStream_t)stream;
+    RoctxRange rr(contract == LENS_BIGVGAN ? "vb_bigvgan_forward_chunked_lens" : "vb_hifigan_forward_chunked_lens");
+    VB_HIP(hipSetDevice(ctx->device));
+    const int hop = net.out_tmul;
+    int* table = reinterpret_cast<int*>(static_cast<char*>(ws) + net_ws_bytes(net, B, chunk + 2 * halo, nullptr));
+    for (const ChunkStep& c : plan) {
+        // the rows that reach into the chunk, compact and masked at their own ends; the generator on them with their in-chunk lengths (the
+        // plain run when all are full); samples [s, e) * hop of every row of wav: its own, then zeros
+        ChunkScatter cs;
+        cs.n_active = c.rows.n_active;
+        for (int b = 0; b < 64; ++b) cs.slot[b] = -1;
+        NetLens nl;
+        bool short_row = false;
+        for (int j = 0; j < c.rows.n_active; ++j) {
+            const int b = c.rows.row[j];
+            cs.slot[b] = j;
+            cs.keep[b] = std::min(c.e, (int)lens->len[b]) - c.s;
+            nl.lp.len[j] = c.rows.n[j];
+            short_row = short_row || c.rows.n[j] != c.tc;
+        }
+        if (c.rows.n_active > 0) {
+            VB_TRY(launch_chunk_gather(mel, c.rows, net.in_ch, T, c.lo, c.tc, scratch_in, st));
+            if (short_row) {
+                nl.lp.B = c.rows.n_active;
+                VB_TRY(launch_lens_table(nl.lp, table, st));
+                nl.table = table;
+            }
+            VB_TRY(net_run(ctx, VB_NET_VOCODER, scratch_in, c.rows.n_active, c.tc, scratch_out, ws, st, short_row ? &nl : nullptr));
+        }
+        VB_TRY(launch_chunk_scatter(scratch_out, cs, B, net.out_ch, T, hop, c.s, c.e, c.lo, c.tc, wav, st));
+    }
+    return VB_OK;
 }
 
 extern "C" {
@@ -353,13 +421,13 @@ size_t vb_hifigan_lens_workspace_bytes(vb_ctx* ctx, int B, int T) { return net_l
 int vb_hifigan_forward_lens(vb_ctx* ctx, const float* mel, int B, int T, const vb_lens* lens, float* wav, void* ws, void* stream) {
     if (!ctx) VB_FAIL(VB_E_INVALID, "hifigan_forward_lens: null ctx");
     RoctxRange rr("vb_hifigan_forward_lens");
-    return net_run_lens(ctx, VB_NET_VOCODER, "hifigan_forward_lens", "vocoder", mel, B, T, lens, wav, ws, (hipStream_t)stream);
+    return net_run_lens(ctx, VB_NET_VOCODER, LENS_VOCODER, "hifigan_forward_lens", "vocoder", mel, B, T, lens, wav, ws, (hipStream_t)stream);
 }
 size_t vb_vae_decode_lens_workspace_bytes(vb_ctx* ctx, int B, int T) { return net_lens_ws_bytes(ctx, VB_NET_VAE, B, T); }
 int vb_vae_decode_lens(vb_ctx* ctx, const float* z, int B, int T, const vb_lens* lens, float* mel, void* ws, void* stream) {
     if (!ctx) VB_FAIL(VB_E_INVALID, "vae_decode_lens: null ctx");
     RoctxRange rr("vb_vae_decode_lens");
-    return net_run_lens(ctx, VB_NET_VAE, "vae_decode_lens", "VAE decoder", z, B, T, lens, mel, ws, (hipStream_t)stream);
+    return net_run_lens(ctx, VB_NET_VAE, LENS_VAE_DECODER, "vae_decode_lens", "VAE decoder", z, B, T, lens, mel, ws, (hipStream_t)stream);
 }
 int vb_crossfade_windows(const float* parts, const int32_t* starts, int nw, int B, int C, int n, int T, float* out, void* stream) {
     if (!parts || !starts || !out || nw < 1 || B < 1 || C < 1 || n < 1 || T < 1) VB_FAIL(VB_E_INVALID, "crossfade_windows: null pointer or nw/B/C/n/T < 1");
@@ -413,53 +481,22 @@ int vb_hifigan_chunked_lens_plan(int B, int T, int chunk, int halo, const int32_
     }
     return VB_OK;
 }
+size_t vb_bigvgan_lens_workspace_bytes(vb_ctx* ctx, int B, int T) { return net_lens_ws_bytes(ctx, VB_NET_VOCODER, B, T); }
+int vb_bigvgan_forward_lens(vb_ctx* ctx, const float* mel, int B, int T, const vb_lens* lens, float* wav, void* ws, void* stream) {
+    if (!ctx) VB_FAIL(VB_E_INVALID, "bigvgan_forward_lens: null ctx");
+    RoctxRange rr("vb_bigvgan_forward_lens");
+    return net_run_lens(ctx, VB_NET_VOCODER, LENS_BIGVGAN, "bigvgan_forward_lens", "vocoder", mel, B, T, lens, wav, ws, (hipStream_t)stream);
+}
 int vb_hifigan_forward_chunked_lens(vb_ctx* ctx, const float* mel, int B, int T, int chunk, int halo, const vb_lens* lens, float* wav, void* ws,
                                     float* scratch_in, float* scratch_out, void* stream) {
-    if (!ctx) VB_FAIL(VB_E_INVALID, "hifigan_forward_chunked_lens: null ctx");
-    if (chunk < 1 || halo < 0) VB_FAIL(VB_E_INVALID, "hifigan_forward_chunked_lens: chunk=%d halo=%d", chunk, halo);
-    NetProgram& net = ctx->nets[VB_NET_VOCODER];
-    if (!net.loaded) VB_FAIL(VB_E_INVALID, "hifigan_forward_chunked_lens: no vocoder loaded");
-    if (!lens || !lens->len) return vb_hifigan_forward_chunked(ctx, mel, B, T, chunk, halo, wav, ws, scratch_in, scratch_out, stream);
-    std::vector<ChunkStep> plan;
-    VB_TRY(chunk_lens_plan(B, T, chunk, halo, lens->len, &plan));
-    bool full = true;
-    for (int b = 0; b < B; ++b) full = full && lens->len[b] == T;
-    if (full) return vb_hifigan_forward_chunked(ctx, mel, B, T, chunk, halo, wav, ws, scratch_in, scratch_out, stream);
-    if (T <= (int64_t)chunk + 2 * (int64_t)halo) return vb_hifigan_forward_lens(ctx, mel, B, T, lens, wav, ws, stream);
-    VB_TRY(net_lens_check(net, VB_NET_VOCODER));
-    if (net.in_tmul != 1) VB_FAIL(VB_E_INVALID, "hifigan_forward_chunked_lens: the vocoder's input runs at %d samples per frame (1)", net.in_tmul);
-    hipStream_t st = (hipStream_t)stream;
-    RoctxRange rr("vb_hifigan_forward_chunked_lens");
-    VB_HIP(hipSetDevice(ctx->device));
-    const int hop = net.out_tmul;
-    int* table = reinterpret_cast<int*>(static_cast<char*>(ws) + net_ws_bytes(net, B, chunk + 2 * halo, nullptr));
-    for (const ChunkStep& c : plan) {
-        // the rows that reach into the chunk, compact and masked at their own ends; the generator on them with their in-chunk lengths (the
-        // plain run when all are full); samples [s, e) * hop of every row of wav: its own, then zeros
-        ChunkScatter cs;
-        cs.n_active = c.rows.n_active;
-        for (int b = 0; b < 64; ++b) cs.slot[b] = -1;
-        NetLens nl;
-        bool short_row = false;
-        for (int j = 0; j < c.rows.n_active; ++j) {
-            const int b = c.rows.row[j];
-            cs.slot[b] = j;
-            cs.keep[b] = std::min(c.e, (int)lens->len[b]) - c.s;
-            nl.lp.len[j] = c.rows.n[j];
-            short_row = short_row || c.rows.n[j] != c.tc;
-        }
-        if (c.rows.n_active > 0) {
-            VB_TRY(launch_chunk_gather(mel, c.rows, net.in_ch, T, c.lo, c.tc, scratch_in, st));
-            if (short_row) {
-                nl.lp.B = c.rows.n_active;
-                VB_TRY(launch_lens_table(nl.lp, table, st));
-                nl.table = table;
-            }
-            VB_TRY(net_run(ctx, VB_NET_VOCODER, scratch_in, c.rows.n_active, c.tc, scratch_out, ws, st, short_row ? &nl : nullptr));
-        }
-        VB_TRY(launch_chunk_scatter(scratch_out, cs, B, net.out_ch, T, hop, c.s, c.e, c.lo, c.tc, wav, st));
-    }
-    return VB_OK;
+    return chunked_lens_run(ctx, LENS_VOCODER, "hifigan_forward", mel, B, T, chunk, halo, lens, wav, ws, scratch_in, scratch_out, stream);
+}
+size_t vb_bigvgan_chunked_lens_workspace_bytes(vb_ctx* ctx, int B, int T, int chunk, int halo) {
+    return vb_hifigan_chunked_lens_workspace_bytes(ctx, B, T, chunk, halo);
+}
+int vb_bigvgan_forward_chunked_lens(vb_ctx* ctx, const float* mel, int B, int T, int chunk, int halo, const vb_lens* lens, float* wav, void* ws,
+                                    float* scratch_in, float* scratch_out, void* stream) {
+    return chunked_lens_run(ctx, LENS_BIGVGAN, "bigvgan_forward", mel, B, T, chunk, halo, lens, wav, ws, scratch_in, scratch_out, stream);
 }
 
 }  // extern "C"

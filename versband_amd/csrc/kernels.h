@@ -388,7 +388,9 @@ static inline int xt_rows(int T_eff) { return T_eff + XT_HEAD + XT_TAIL; }
 int launch_xt_planes(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int groups, int act,
                      float slope, int upsample2, int B, int C, int T_in, int nplanes, bf16_t* out, hipStream_t st, const int* len = nullptr,
                      int len_mul = 1);       // (len non-null: zero rows from position len[b] * len_mul of the - upsampled - image on)
-int launch_aa_act(const float* x, const float* alpha, const float* inv_beta, const float* filt, int B, int C, int T, float* out, hipStream_t st);
+// (len non-null: row b ends at len[b] * len_mul - both filters replicate-pad from there, nothing behind it is read, out is zero behind it)
+int launch_aa_act(const float* x, const float* alpha, const float* inv_beta, const float* filt, int B, int C, int T, float* out, hipStream_t st,
+                  const int* len = nullptr, int len_mul = 1);
 // f32 [rows][cols] -> split-bf16 planes [2][rows][cpad] (cpad % 4 == 0, columns >= cols zero filled)
 int launch_split_rows(const float* x, int64_t rows, int cols, int cpad, bf16_t* out, int64_t plane, hipStream_t st);
 int launch_softmax_rows_t(const float* s, int B, int R, int Ccols, float* out_t, hipStream_t st);

@@ -259,9 +259,15 @@ int launch_xt_planes(const float* x, const float* mean, const float* rstd, const
 //   s[v]   = up[v] + inv_beta * sin^2(alpha * up[v])                                         (Snake / SnakeBeta, activations.py)
 //   out[t] = sum_k f[k] s[clamp(2 t + k - 5, 0, 2T-1)]                                       (DownSample1d / LowPassFilter1d)
 // One workgroup = 256 outputs of one (batch, channel) row: the 523 intermediate samples are computed once into LDS.
+// Row lengths (vb_bigvgan_forward_lens): row b = row / C ends at Tr = len[b] * len_mul samples of its pitch T, and the replicate padding
+// of both filters starts there - the three bounds below (the fill of xs, the intermediate index, the store) are Tr instead of T, everything
+// else is the one code of the plain form, so a row's valid samples are the bits of the plain kernel on that clip alone at T = Tr (the
+// tiles start at multiples of 256 either way).  Nothing at or behind x[row][Tr] is loaded; out[row][Tr .. T) is written as exact zeros, by a
+// workgroup whose tile lies wholly behind the row's end before it loads anything.  len == nullptr: Tr = T, the plain form.
 #define AA_TT 256
 __global__ void __launch_bounds__(256) aa_act_kernel(const float* __restrict__ x, const float* __restrict__ alpha, const float* __restrict__ inv_beta,
-                                                    const float* __restrict__ filt, int C, int T, float* out) {
+                                                    const float* __restrict__ filt, int C, int T, float* out, const int* __restrict__ len,
+                                                    int len_mul) {
     __shared__ float xs[AA_TT + 16];
     __shared__ float ss[2 * AA_TT + 16];
     __shared__ float f[12];
@@ -269,17 +275,22 @@ __global__ void __launch_bounds__(256) aa_act_kernel(const float* __restrict__ x
     const int t0 = blockIdx.x * AA_TT;
     const float* xr = x + (int64_t)row * T;
     const int tid = threadIdx.x;
+    const int Tr = len ? min(len[row / C] * len_mul, T) : T;        // (uniform over the workgroup)
+    if (t0 >= Tr) {
+        if (t0 + tid < T) out[(int64_t)row * T + t0 + tid] = 0.f;
+        return;
+    }
     if (tid < 12) f[tid] = filt[tid];
     for (int j = tid; j < AA_TT + 16; j += 256) {
         int pos = t0 - 6 + j;
-        pos = pos < 0 ? 0 : (pos > T - 1 ? T - 1 : pos);
+        pos = pos < 0 ? 0 : (pos > Tr - 1 ? Tr - 1 : pos);
         xs[j] = xr[pos];
     }
     __syncthreads();
     const float a = alpha[c], ib = inv_beta[c];
     for (int q = tid; q < 2 * AA_TT + 11; q += 256) {
         int v = 2 * t0 - 5 + q;
-        v = v < 0 ? 0 : (v > 2 * T - 1 ? 2 * T - 1 : v);
+        v = v < 0 ? 0 : (v > 2 * Tr - 1 ? 2 * Tr - 1 : v);
         const int i_lo = (v + 5) >> 1;                      // ceil((v + 4) / 2)
         float up = 0.f;
 #pragma unroll
@@ -296,13 +307,19 @@ __global__ void __launch_bounds__(256) aa_act_kernel(const float* __restrict__ x
     const int t = t0 + tid;
     if (t < T) {
         float acc = 0.f;
+        if (t < Tr) {
 #pragma unroll
-        for (int k = 0; k < 12; ++k) acc += f[k] * ss[2 * tid + k];
+            for (int k = 0; k < 12; ++k) acc += f[k] * ss[2 * tid + k];
+        }
         out[(int64_t)row * T + t] = acc;
     }
 }
-int launch_aa_act(const float* x, const float* alpha, const float* inv_beta, const float* filt, int B, int C, int T, float* out, hipStream_t st) {
-    hipLaunchKernelGGL(aa_act_kernel, dim3(cdiv(T, AA_TT), B * C), dim3(256), 0, st, x, alpha, inv_beta, filt, C, T, out);
+int launch_aa_act(const float* x, const float* alpha, const float* inv_beta, const float* filt, int B, int C, int T, float* out, hipStream_t st,
+                  const int* len, int len_mul) {
+    if (len && len_mul < 1) VB_FAIL(VB_E_INVALID, "aa_act: row lengths with len_mul = %d (>= 1)", len_mul);
+    if (B < 1 || C < 1 || T < 1 || (int64_t)B * C > 65535 || T > (1 << 30))
+        VB_FAIL(VB_E_INVALID, "aa_act: B=%d C=%d T=%d (B * C rows <= 65535, T <= 2^30)", B, C, T);
+    hipLaunchKernelGGL(aa_act_kernel, dim3(cdiv(T, AA_TT), B * C), dim3(256), 0, st, x, alpha, inv_beta, filt, C, T, out, len, len_mul);
     VB_CHECK_LAUNCH();
     return VB_OK;
 }

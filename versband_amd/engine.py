@@ -763,7 +763,8 @@ class ConvNet:
         L.check(ctx.lib.vb_net_load(ctx.handle, which, ops, len(nb.ops), bufs, len(nb.bufs), in_ch, out_ch, in_tmul, out_tmul),
                 "vb_net_load")
         # scratch that is sized for a call's (B, T) and made again when that changes: slot -> ((B, T), the buffers)
-        self._scratch = {"net": (None, None), "lens": (None, None), "chunk": (None, None), "chunk_lens": (None, None)}
+        self._scratch = {"net": (None, None), "lens": (None, None), "chunk": (None, None), "chunk_lens": (None, None),
+                         "vocode_lens": (None, None)}
 
     def _cached(self, slot: str, key: Tuple[int, int], make):
         if self._scratch[slot][0] != key:
@@ -867,6 +868,43 @@ class ConvNet:
         ws = self._workspace(B, tc)
         L.check(self.ctx.lib.vb_hifigan_forward_chunked(self.ctx.handle, L.ptr(x), B, T, chunk, halo, L.ptr(out), L.ptr(ws), L.ptr(cin), L.ptr(cout),
                                                         L.stream_ptr()), "vb_hifigan_forward_chunked")
+        return out
+
+    def vocode_lens(self, x: Tensor, lengths, chunk: Optional[int] = None, halo: int = 32) -> Tensor:
+        """vocoder nets only (vb_bigvgan_forward_lens / vb_bigvgan_forward_chunked_lens): mel [B,80,T] with one length in mel frames per row
+        -> wav [B,1,T*hop], for a program with BigVGAN's anti-aliased activations (VB_OP_AA_ACT, which run(lengths=) and
+        run_chunked(lengths=) refuse; a HiFi-GAN program runs here as it does there).  Row b's first lengths[b] * out_tmul samples are
+        the call on that clip alone - run(), or with chunk the loop of run_chunked() on the same grid (harness.plan_chunk_calls) - bit for
+        bit when lengths[b] and T agree mod 4 (chunked: in every chunk where the row's frames and the chunk's width do; always when chunk,
+        halo, T and the lengths are multiples of 4), to the precision's roundoff otherwise: harness.plan_vocoder_calls groups rows
+        accordingly.  The rest of the row is zero and the padding of x is never read.  lengths None, or every row full, is run() /
+        run_chunked()."""
+        if self.which != L.NET_VOCODER:
+            raise ValueError(f"vocode_lens: the {self.NET_NAMES[self.which]} has no vocode_lens (vocoder nets alone; the VAE decoder takes row "
+                             f"lengths through decode_lens, the VAE encoder takes equal-length rows only)")
+        x = x.to(self.ctx.device, torch.float32).contiguous()
+        B, Cin, T = x.shape
+        assert Cin == self.in_ch, (Cin, self.in_ch)
+        if chunk is not None and (chunk < 1 or halo < 0):
+            raise ValueError(f"vocode_lens: chunk = {chunk}, halo = {halo} (chunk >= 1, halo >= 0)")
+        lens, hold, _ = _lens_struct(lengths, B, T, gloss=" (input frames per row)")
+        if lens is None:
+            return self.run(x) if chunk is None else self.run_chunked(x, chunk, halo)
+        lib, dev = self.ctx.lib, self.ctx.device
+        out = torch.empty(B, self.out_ch, T * self.out_tmul, dtype=torch.float32, device=dev)
+        if chunk is None or T <= chunk + 2 * halo:
+            ws = self._cached("vocode_lens", (B, T), lambda: self._bytes(lib.vb_bigvgan_lens_workspace_bytes(self.ctx.handle, B, T)))
+            L.check(lib.vb_bigvgan_forward_lens(self.ctx.handle, L.ptr(x), B, T, C.byref(lens), L.ptr(out), L.ptr(ws), L.stream_ptr()),
+                    "vb_bigvgan_forward_lens")
+        else:
+            tc = chunk + 2 * halo
+            cin, cout = self._cached("chunk", (B, tc), lambda: (torch.empty(B * self.in_ch * tc, dtype=torch.float32, device=dev),
+                                                                torch.empty(B * self.out_ch * tc * self.out_tmul, dtype=torch.float32, device=dev)))
+            ws = self._cached("vocode_lens", (B, T, chunk, halo),
+                              lambda: self._bytes(lib.vb_bigvgan_chunked_lens_workspace_bytes(self.ctx.handle, B, T, chunk, halo)))
+            L.check(lib.vb_bigvgan_forward_chunked_lens(self.ctx.handle, L.ptr(x), B, T, chunk, halo, C.byref(lens), L.ptr(out), L.ptr(ws), L.ptr(cin),
+                                                        L.ptr(cout), L.stream_ptr()), "vb_bigvgan_forward_chunked_lens")
+        del hold                         # (the host array of the lengths: read during the call only)
         return out
 
 

@@ -710,6 +710,15 @@ class VocoderBigVGAN:
         spec = spec.to(dtype=torch.float32)
         return self.net().run(spec).squeeze().cpu().numpy()
 
+    def vocode_batch(self, spec_bct: Tensor, lengths=None, chunk=None, halo: int = 32) -> Tensor:
+        """device-resident batched path (addition; the counterpart of HifiGAN.spec2wav_batch): spec [B,80,T] -> wav [B, T*hop], no host
+        round trip.  lengths (ConvNet.vocode_lens): one length in mel frames per row - mels of different lengths padded to T share the
+        call, row b holds lengths[b] * hop samples of the clip alone followed by zeros (bit for bit when lengths[b] and T agree mod 4:
+        harness.plan_vocoder_calls groups clips that way), the mel padding is never read.  chunk: long mels in chunks of `chunk` frames
+        with `halo` frames of context on both sides, with or without lengths (harness.plan_chunk_calls shows the grid); None is the
+        whole-row call."""
+        return self.net().vocode_lens(spec_bct, lengths, chunk=chunk, halo=halo).squeeze(1)
+
     def __call__(self, wav):
         return self.vocode(wav)
 
