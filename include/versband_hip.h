@@ -604,6 +604,41 @@ int vb_melnet_load(vb_ctx* ctx, const vb_mel_config* cfg, const float* dft_w, co
 int vb_melnet_frames(const vb_mel_config* cfg, int L, int center);
 size_t vb_melnet_workspace_bytes(const vb_mel_config* cfg, int B, int L, int center);
 int vb_melnet_forward(vb_ctx* ctx, const float* wav, int B, int L, int center, float* mel, float* spec, void* ws, void* stream);
+/* The front-end with ROW LENGTHS (build-defined): waveforms of different lengths as rows of one call.  wav [B][L], L the padded length;
+ * lens->len the HOST array of B lengths in samples, checked like the sampler's (B <= 64, 1 <= len[b] <= L) and then row by row for what the
+ * plain call needs of its one L: pad < len[b], n_fft/2 < len[b] + 2 pad when `center`, T_b = vb_melnet_frames(cfg, len[b], center) >= 1.
+ * VB_E_INVALID names the row; nothing is launched and mel / spec are unchanged.
+ * THE CONTRACT.  Row b's first T_b frames of mel (and of spec) are vb_melnet_forward on that clip alone; the rest of the row, frames
+ * [T_b, T), is exact zero - 0.0f in mel, not log10(1e-5) - and the padding of wav, samples [len[b], L) of a row, is not read (it may
+ * hold NaN).  Row b does not depend on the other rows' contents or lengths.
+ * lens == NULL, len == NULL or every row full is vb_melnet_forward on the same buffers: same launches, same bits.
+ * How it works.  Zero padding cannot imitate the clip alone: both reflections (by pad, and by n_fft/2 when centred) turn round at the
+ * row's own end, so the framing kernel reads the end from a device table of the lengths, writes exact zeros from hop-block
+ * J_b = T_b + n_fft/hop - 1 on and loads nothing behind len[b].  The STFT stays the one convolution over the padded block count.  Its
+ * frames t >= T_b still see row b's last n_fft/hop - 1 blocks, so spec (the caller's, or the workspace's) gets the conv nets' tail pass - one
+ * row of (T - T_b) * Co4 samples per clip - and the mel tail kernel stores 0.0f for t >= T_b from a table of the T_b.
+ * BIT FOR BIT, ALWAYS.  The convolution has fp32 weights, no minimal-filtering form and a transposed output (no staged epilogue), so it
+ * runs one of the two exact-fp32 kernels: the DMA-fed one when T + n_fft/hop - 1 is a multiple of 4, the register-staged one otherwise
+ * (vb_conv1d_plan: VB_ROUTE_F32G / VB_ROUTE_F32).  The two are bit-identical - one chunk, tap and channel-pair order - and so is every
+ * tile of either (T and B enter the tile choice only), so an output element's accumulation order depends on neither T nor B nor the
+ * route: no congruence between len[b] and L is needed, and a host has nothing to group.  The framing and the mel tail are per-element.
+ * ws: vb_melnet_lens_workspace_bytes(cfg, B, L, center) = vb_melnet_workspace_bytes + the two length tables.  Hosts detect the feature by
+ * the presence of these symbols (vb_abi_version() stays 3). */
+size_t vb_melnet_lens_workspace_bytes(const vb_mel_config* cfg, int B, int L, int center);
+int vb_melnet_forward_lens(vb_ctx* ctx, const float* wav, int B, int L, int center, const vb_lens* lens, float* mel, float* spec, void* ws,
+                           void* stream);
+/* Masked mean absolute distance of two log-mels (the two numbers of scripts/infer_batched.py --eval_mel), no vb_ctx: a f32 [B][M][Ta],
+ * b f32 [B][M][Tb], frames the HOST array of B frame counts to compare, checked like row lengths (B <= 64, 1 <= frames[r] <= min(Ta, Tb);
+ * VB_E_INVALID names the row, nothing is launched).  With d = a - b over m < M, t < frames[r] and N = M * frames[r]:
+ *     mu_r = remove_offset ? sum(d) / N : 0;     out[r] = sum |d - mu_r| / N;     out_offset[r] = mu_r   (out_offset may be NULL)
+ * Nothing behind frames[r] is loaded (it may hold NaN).  One launch, one workgroup of 1024 threads per row, two passes over the row.  The
+ * reduction shape is fixed: thread x adds elements i = x, x + 1024, ... (i = m * frames[r] + t) in ascending order into one fp32
+ * accumulator, then an LDS tree of 10 levels; no atomics.  The result is a pure function of the inputs and identical from run to run,
+ * and the longest chain of additions behind a sum is k = ceil(N / 1024) + 10, so |out - exact| <= 2 k 2^-24 (mean |d| + |mu|).
+ * ws: vb_mel_dist_workspace_bytes(B) bytes (the device copy of frames; 0 for a B outside 1..64). */
+size_t vb_mel_dist_workspace_bytes(int B);
+int vb_mel_dist_lens(const float* a, int Ta, const float* b, int Tb, int B, int M, const int32_t* frames /* HOST */, int remove_offset,
+                     float* out, float* out_offset /* nullable */, void* ws, void* stream);
 
 /* ------------------------------------------------------------------- unit kernels ---- */
 /* RMSNorm (flag_large_dit_moe.py:52-77) * w then modulate (:80-81); shift/scale [B][mod_ld] or NULL */

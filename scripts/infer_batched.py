@@ -12,6 +12,9 @@ lengths differ by at most N tokens share a call too: the group is padded to its 
 (vb_sample_cfg_lens - a row is the call on that clip alone), then the rows are decoded with per-row lengths (vb_vae_decode_lens) in one
 call per residue of the latent length mod 4 and cut to their own lengths, and the decoded mels are vocoded with per-row lengths
 (vb_hifigan_forward_lens) in one call per residue of the mel length mod 4 - two at most; in both a row again is the call on that clip alone.
+`--eval_mel` scores a group's clips together: one MelNet call with row lengths (vb_melnet_forward_lens) over the written waveforms and one
+masked distance reduction on the device (vb_mel_dist_lens); mel_l1.tsv keeps its columns and order, its values agree with the per-clip
+path's to fp32 roundoff.
 """
 from __future__ import annotations
 
@@ -61,6 +64,10 @@ def parse_args(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     if "-h" in argv or "--help" in argv:
         own.print_help()
+        print("\n--eval_mel here scores a group's clips together: one MelNet call with row lengths over the written waveforms, one over the "
+              "ground-truth accompaniments, and a device reduction (versband_amd.melnet.mel_distance) for the two mel_l1.tsv columns.  "
+              "Its values agree with the per-clip torch reductions of scripts/test_final.py to 2 k 2^-24 (mean |d| + |offset|), "
+              "k = ceil(80 * frames / 1024) + 10 - fp32 roundoff - not digit for digit; the .wav files and clap.csv are unchanged.")
         print("\nand every flag of scripts/test_final.py:\n")
     mine, rest = own.parse_known_args(argv)
     with mock.patch.object(sys, "argv", [sys.argv[0]] + rest):
@@ -183,8 +190,10 @@ def sample_group(args, sampler, vocoder, group, scales, device):
     return generated
 
 
-def write_item(args, rank, item_idx, item, scales, generated, rows, mel_rows, mel_net):
-    """the files of one item in the per-item loop's order and under its names (test_final.py: gen_song, reference :424-457)"""
+def write_item(args, rank, item_idx, item, scales, generated, rows, pending, mel_net):
+    """the files of one item in the per-item loop's order and under its names (test_final.py: gen_song, reference :424-457).  With
+    --eval_mel every written clip is queued in `pending` - its mel_l1.tsv row without the values, the waveform as written, the decoded
+    mel, the normalised ground-truth accompaniment or None - and the group is scored together by score_group."""
     cap = item["caption"]
     gt_vocal, gt_accomp = loop._load_ground_truth(item)
     for scale in scales:
@@ -203,15 +212,42 @@ def write_item(args, rank, item_idx, item, scales, generated, rows, mel_rows, me
             write_wav_pcm16(stem + "[accomp].wav", wav, args.sample_rate)
             rows.append({"audio_path": stem + "[accomp].wav", "caption": cap if isinstance(cap, str) else item["name"], "name": item["name"]})
             if mel_net is not None:
-                back = mel_net(np.asarray(wav, dtype=np.float32))[0]
-                f = min(back.shape[1], spec.shape[1])
-                d = back[:, :f] - spec[:, :f].to(back.device)
-                row = {"name": item["name"], "scale": scale, "sample": k, "mel_l1_vs_decoded": float((d - d.mean()).abs().mean())}
-                if gt_accomp is not None:
-                    ref = mel_net(np.asarray(gt_accomp, dtype=np.float32))[0]
-                    f = min(back.shape[1], ref.shape[1])
-                    row["mel_l1_vs_gt_accomp"] = float((back[:, :f] - ref[:, :f]).abs().mean())
-                mel_rows.append(row)
+                pending.append(({"name": item["name"], "scale": scale, "sample": k}, np.asarray(wav, dtype=np.float32), spec,
+                                None if gt_accomp is None else np.asarray(gt_accomp, dtype=np.float32)))
+
+
+def _padded_rows(arrays, device):
+    """1-D host arrays or [80, T] device mels of different lengths as the rows of one zero-padded device batch, and their lengths"""
+    lens = [int(a.shape[-1]) for a in arrays]
+    rows = [torch.nn.functional.pad(torch.as_tensor(a, dtype=torch.float32).to(device), (0, max(lens) - n)) for a, n in zip(arrays, lens)]
+    return torch.stack(rows), lens
+
+
+def score_group(pending, mel_net, mel_rows, device):
+    """--eval_mel for the clips of one group (at most 64 per pass, the row limit of a call with lengths): the written waveforms, padded to
+    the longest, go through ONE MelNet call with row lengths (a row is the mel of that clip alone), the ground-truth accompaniments of the
+    items that have them through a second, one mel_distance call scores the mels against the decoded ones (offset removed) and one
+    against the ground truth, and one host copy brings the numbers back.  The rows join mel_rows in the order they were queued."""
+    from versband_amd.melnet import mel_distance
+    for at in range(0, len(pending), 64):
+        part = pending[at:at + 64]
+        wavs, wav_lens = _padded_rows([w for _, w, _, _ in part], device)
+        back = mel_net(wavs, lengths=wav_lens)
+        back_frames = [mel_net.frames(n) for n in wav_lens]
+        specs, spec_frames = _padded_rows([s for _, _, s, _ in part], device)
+        results = [mel_distance(back, specs, [min(a, b) for a, b in zip(back_frames, spec_frames)], remove_offset=True)[0]]
+        with_gt = [r for r, (_, _, _, gt) in enumerate(part) if gt is not None]
+        if with_gt:
+            gts, gt_lens = _padded_rows([part[r][3] for r in with_gt], device)
+            ref = mel_net(gts, lengths=gt_lens)
+            frames = [min(back_frames[r], mel_net.frames(n)) for r, n in zip(with_gt, gt_lens)]
+            results.append(mel_distance(back[with_gt].contiguous(), ref, frames, remove_offset=False)[0])
+        values = torch.cat(results).cpu().tolist()                   # the one device-to-host copy of the pass
+        for r, (row, _, _, _) in enumerate(part):
+            row["mel_l1_vs_decoded"] = values[r]
+            if r in with_gt:
+                row["mel_l1_vs_gt_accomp"] = values[len(part) + with_gt.index(r)]
+            mel_rows.append(row)
 
 
 @torch.no_grad()
@@ -237,10 +273,13 @@ def gen_song(rank, args):
     loaded = ((gi, dataset[gi]) for gi in indices)                  # lazily, in shard order: an item is read when its group is formed
     for group in stream_length_groups(loaded, lambda e: int(e[1]["acoustic"].shape[1] / MEL_DOWNSAMPLE), args.items_per_batch, args.length_slack):
         generated = sample_group(args, sampler, vocoder, group, scales, device)
+        pending = []
         for p, (gi, item) in enumerate(group):
-            write_item(args, rank, item_idx, item, scales, {s: generated[(p, s)] for s in scales}, rows, mel_rows, mel_net)
+            write_item(args, rank, item_idx, item, scales, {s: generated[(p, s)] for s in scales}, rows, pending, mel_net)
             item_idx += 1
-        del generated                                               # the group's conditioning, start noise, mels and wavs end here
+        if pending:
+            score_group(pending, mel_net, mel_rows, device)           # (one path at every --items_per_batch, 1 included)
+        del generated, pending                                               # the group's conditioning, start noise, mels and wavs end here
     tag = "" if args.num_gpus == 1 else f".{rank}"
     csv_path = os.path.join(args.save_dir, f"clap{tag}.csv")
     save_rows_to_tsv(rows, ["audio_path", "caption", "name"], csv_path)

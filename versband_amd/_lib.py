@@ -171,6 +171,10 @@ PROTOTYPES = {
     "vb_melnet_frames": (c_int, [C.POINTER(MelConfig), c_int, c_int]),
     "vb_melnet_workspace_bytes": (C.c_size_t, [C.POINTER(MelConfig), c_int, c_int, c_int]),
     "vb_melnet_forward": (c_int, [P, P, c_int, c_int, c_int, P, P, P, P]),
+    "vb_melnet_lens_workspace_bytes": (C.c_size_t, [C.POINTER(MelConfig), c_int, c_int, c_int]),
+    "vb_melnet_forward_lens": (c_int, [P, P, c_int, c_int, c_int, C.POINTER(Lens), P, P, P, P]),
+    "vb_mel_dist_workspace_bytes": (C.c_size_t, [c_int]),
+    "vb_mel_dist_lens": (c_int, [P, c_int, P, c_int, c_int, c_int, C.POINTER(C.c_int32), c_int, P, P, P, P]),
     "vb_rmsnorm_modulate": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_float, P, c_int, P]),
     "vb_router_top1": (c_int, [P, P, c_int, c_int, P, P]),
     "vb_route_bucket_scratch_ints": (c_int, [c_int, c_int]),

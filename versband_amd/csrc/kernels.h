@@ -228,8 +228,15 @@ int launch_final_layer_fused(const float* h, const float* shift, const float* sc
 int launch_gather_rows(const int64_t* idx, const float* table, int rows, int D, int vocab, float* out, hipStream_t st);
 int launch_t5_attention(Planes qkv, const float* pos_bias, int pos_len, int B, int L, int heads, int dkv, Planes out, hipStream_t st);
 // log-mel front-end (melnet.hip)
-int launch_stft_frames(const float* wav, int B, int L, int hop, int pad, int pad2, int J, float* X, hipStream_t st);
-int launch_mel_tail(const float* spec, int B, int T, int Co4, int nb, int im_off, const float* basisT, int n_mels, float* mel, hipStream_t st);
+// (len: device [B] row lengths in samples - row b reflects at its own end and is zero from its own last hop-block on, taps = n_fft / hop;
+//  tlen: device [B] row lengths in frames - mel is 0 from tlen[b] on; null: the whole row)
+int launch_stft_frames(const float* wav, int B, int L, int hop, int pad, int pad2, int J, float* X, hipStream_t st, const int* len = nullptr, int taps = 0);
+int launch_mel_tail(const float* spec, int B, int T, int Co4, int nb, int im_off, const float* basisT, int n_mels, float* mel, hipStream_t st,
+                    const int* tlen = nullptr);
+// out[r] = mean over m < M, t < frames[r] of |a - b - mu_r|, mu_r = the mean of a - b over the same range (remove_offset) or 0; out_offset
+// (nullable) = mu_r.  frames: device [B].  One workgroup per row, a fixed reduction shape (melnet.hip)
+int launch_mel_dist(const float* a, int Ta, const float* b, int Tb, int B, int M, const int* frames, int remove_offset, float* out, float* out_offset,
+                    hipStream_t st);
 
 // ---------------------------------------------------------------------------
 // sampler_step.hip: the sampler's update and step bookkeeping (+ the fused form of the update, rowlin.hip)

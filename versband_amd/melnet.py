@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .engine import Context
+from .engine import Context, _checked_list, _lens_struct
 
 Tensor = torch.Tensor
 
@@ -93,7 +93,7 @@ def dft_weights(n_fft: int, hop: int, win: int) -> np.ndarray:
 # ------------------------------------------------------------------------------------------------------------------
 class MelNet(torch.nn.Module):
     """Same constructor / call surface as preprocess/NAT_mel.py:42-86: `MelNet(hparams, device)`, `.to(device)`,
-    `forward(y, center=False, complex=False)`.  hparams keys: fft_size, audio_num_mel_bins, audio_sample_rate, hop_size, win_size,
+    `forward(y, center=False, complex=False)` (+ `lengths=`, build-defined).  hparams keys: fft_size, audio_num_mel_bins, audio_sample_rate, hop_size, win_size,
     fmin, fmax.  There is no CPU path: the module needs a GPU device before it is called."""
 
     def __init__(self, hparams: Dict, device="cpu") -> None:
@@ -130,6 +130,7 @@ class MelNet(torch.nn.Module):
             self._cfg = L.MelConfig(self.n_fft, self.hop_size, self.num_mels)
             L.check(self._ctx.lib.vb_melnet_load(self._ctx.handle, C.byref(self._cfg), L.ptr(self._w), L.ptr(self._bt)), "vb_melnet_load")
             self._ws = None
+            self._ws_lens = {}
         return self
 
     def frames(self, n_samples: int, center: bool = False) -> int:
@@ -137,7 +138,11 @@ class MelNet(torch.nn.Module):
         return max(0, 1 + (n_samples + 2 * pad - self.n_fft) // self.hop_size)
 
     @torch.no_grad()
-    def forward(self, y, center: bool = False, complex: bool = False):
+    def forward(self, y, center: bool = False, complex: bool = False, lengths=None):
+        """lengths (vb_melnet_forward_lens): one length in samples per row - waveforms of different lengths padded to y.shape[-1] share
+        the call.  Row b's first frames(lengths[b], center) frames are the call on that clip alone (bit for bit, always: no route of
+        the STFT convolution changes a bit, so there is nothing to group), the rest of the row is zero, and the padding of y is never
+        read.  None, or every row full, is the plain call."""
         if self._ctx is None:
             raise L.VersbandError("MelNet runs on the HIP library only: move it to a GPU device first (.to('cuda:0'))")
         if isinstance(y, np.ndarray):
@@ -152,14 +157,64 @@ class MelNet(torch.nn.Module):
         T = lib.vb_melnet_frames(C.byref(self._cfg), n, ctr)
         if T < 1 or pad >= n or (ctr and self.n_fft // 2 >= n + 2 * pad):
             raise ValueError(f"MelNet: {n} samples are too few for reflect padding {pad} / one {self.n_fft}-sample frame")
-        need = lib.vb_melnet_workspace_bytes(C.byref(self._cfg), B, n, ctr)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        lens = hold = None
+        if lengths is not None:
+            lens, hold, vals = _lens_struct(lengths, B, n, gloss=" (samples per row)")
+            for b, v in enumerate(vals or ()):      # what the plain call asks of its one length, row by row (the library's rule, stated first)
+                if self.frames(v, center) < 1 or pad >= v or (ctr and self.n_fft // 2 >= v + 2 * pad):
+                    raise ValueError(f"lengths[{b}] = {v} samples are too few for reflect padding {pad} / one {self.n_fft}-sample frame")
         nb, off = self.n_fft // 2 + 1, im_offset(self.n_fft)
         mel = None if complex else torch.empty(B, self.num_mels, T, dtype=torch.float32, device=dev)
         spec = torch.empty(B, T, 2 * off, dtype=torch.float32, device=dev) if complex else None
-        L.check(lib.vb_melnet_forward(self._ctx.handle, L.ptr(y), B, n, ctr, L.ptr(mel) if mel is not None else None,
-                                      L.ptr(spec) if spec is not None else None, L.ptr(self._ws), L.stream_ptr()), "vb_melnet_forward")
+        pm, ps = L.ptr(mel) if mel is not None else None, L.ptr(spec) if spec is not None else None
+        if lens is None:
+            need = lib.vb_melnet_workspace_bytes(C.byref(self._cfg), B, n, ctr)
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            L.check(lib.vb_melnet_forward(self._ctx.handle, L.ptr(y), B, n, ctr, pm, ps, L.ptr(self._ws), L.stream_ptr()), "vb_melnet_forward")
+        else:
+            key = (B, n, ctr)
+            if key not in self._ws_lens:
+                if len(self._ws_lens) > 16:
+                    self._ws_lens.clear()
+                self._ws_lens[key] = torch.empty(lib.vb_melnet_lens_workspace_bytes(C.byref(self._cfg), B, n, ctr), dtype=torch.uint8, device=dev)
+            L.check(lib.vb_melnet_forward_lens(self._ctx.handle, L.ptr(y), B, n, ctr, C.byref(lens), pm, ps, L.ptr(self._ws_lens[key]),
+                                               L.stream_ptr()), "vb_melnet_forward_lens")
+            del hold                         # (the host array of the lengths: read during the call only)
         if complex:     # the reference returns view_as_real(stft).transpose(1, 2): [B, T, n_fft/2+1, 2]  (:79-81)
             return torch.stack([spec[:, :, :nb], spec[:, :, off:off + nb]], dim=-1)
         return mel
+
+
+_DIST_WS = {}
+
+
+@torch.no_grad()
+def mel_distance(a: Tensor, b: Tensor, frames, remove_offset: bool = False):
+    """(dist [B], offset [B]) on the device (vb_mel_dist_lens): a [B, M, Ta] and b [B, M, Tb] log-mels on one GPU, frames one count per
+    row, 1 <= frames[r] <= min(Ta, Tb).  dist[r] = mean over the row's first frames[r] frames of |a - b - offset[r]|, offset[r] = the
+    mean of a - b over the same range when remove_offset is set, else 0.  Nothing behind frames[r] is read.  One launch with a fixed
+    reduction shape: the result is identical from run to run and within 2 k 2^-24 (mean |a - b| + |offset|) of the exact value,
+    k = ceil(M * frames[r] / 1024) + 10.  Nothing is copied to the host: a caller that wants floats makes the one copy."""
+    if not (torch.is_tensor(a) and torch.is_tensor(b) and a.dim() == 3 and b.dim() == 3 and a.shape[:2] == b.shape[:2]):
+        raise ValueError("mel_distance: a [B, M, Ta] and b [B, M, Tb] with the same B and M")
+    if a.device.type != "cuda" or b.device != a.device:
+        raise ValueError(f"mel_distance: a on {a.device}, b on {b.device} (one GPU device)")
+    B, M, Ta = a.shape
+    Tb = b.shape[2]
+    vals = [int(v) for v in _checked_list("frames", frames, "integers", (B, "rows"), f"a sequence of {B} frame counts", " (frames per row)")]
+    if B > 64:
+        raise ValueError(f"frames: {B} rows (at most 64)")
+    for r, v in enumerate(vals):
+        if not 1 <= v <= min(Ta, Tb):
+            raise ValueError(f"frames[{r}] = {v} is not in [1, min(Ta, Tb) = {min(Ta, Tb)}]")
+    a, b = a.to(torch.float32).contiguous(), b.to(torch.float32).contiguous()
+    lib = L.load()
+    if a.device not in _DIST_WS:
+        _DIST_WS[a.device] = torch.empty(lib.vb_mel_dist_workspace_bytes(64), dtype=torch.uint8, device=a.device)
+    out = torch.empty(2, B, dtype=torch.float32, device=a.device)
+    arr = (C.c_int32 * B)(*vals)
+    with torch.cuda.device(a.device):
+        L.check(lib.vb_mel_dist_lens(L.ptr(a), Ta, L.ptr(b), Tb, B, M, arr, int(bool(remove_offset)), L.ptr(out[0]), L.ptr(out[1]),
+                                     L.ptr(_DIST_WS[a.device]), L.stream_ptr()), "vb_mel_dist_lens")
+    return out[0], out[1]
