@@ -460,12 +460,12 @@ int vb_hifigan_forward_lens(vb_ctx* ctx, const float* mel, int B, int T, const v
  * How it works.  The latent is copied into the workspace with its tails zeroed and every op that writes an activation buffer is followed
  * by the tail-zero launch of the HiFi-GAN call (a transposed output [T][C] as one row of T*C samples per clip), so every raw buffer a
  * convolution reads is zero behind row b's end.  Zero tails alone do not settle the decoder; three things read the device table of lengths:
- *   GroupNorm statistics     gn_stats_lens_kernel reduces row b's own cpg x len[b]*tmul samples at pitch T*tmul with the thread assignment,
- *                            the float4 grouping (x+y)+(z+w) and the two-pass final order of the plain kernel on the compacted clip.
+ *   GroupNorm statistics     gn_stats_kernel<LENS> reduces row b's own cpg x len[b]*tmul samples at pitch T*tmul with the thread assignment,
+ *                            the float4 grouping (x+y)+(z+w) and the two-pass final order of the plain form on the compacted clip (one body).
  *   GroupNorm (+ swish) in   every consumer pads the ACTIVATED tensor with zeros from len[b]*tmul on instead of T*tmul: conv_tile's one bound for
  *                            the register-staged convolutions (fp32, split, bf16), gn_apply_kernel (zeros behind the row end),
  *                            xt_planes_kernel (zero rows behind it).
- *   attention                softmax_rows_t_lens_kernel takes max and sum over the keys c < len[b] (lane stride and order of the plain kernel
+ *   attention                softmax_rows_t_kernel<LENS> takes max and sum over the keys c < len[b] (lane stride and order of the plain form
  *                            at len[b] columns) and writes exact zeros for the keys and queries behind the row's end; q, k, v (transposed
  *                            or not) are tail-zeroed and the split planes are made from them, so every added term of the two products -
  *                            Co or Ci = the padded T - is an exact 0 * 0.  The score buffer gets no tail pass: only the row's own block is read.

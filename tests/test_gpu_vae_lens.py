@@ -10,6 +10,7 @@ the row's tokens, so the 96- and 70-token sets run the softmax lane loop twice a
 """
 import ctypes as C
 import functools
+import hashlib
 import os
 import subprocess
 import sys
@@ -233,16 +234,38 @@ def _dev_lens(lens):
     return torch.tensor(lens, dtype=torch.int32, device="cuda")
 
 
+STATS_LENS = [70, 65, 64, 63, 22, 13, 7, 4, 3, 2, 1]
+SOFTMAX_LENS = [1, 63, 64, 65, 70]
+
+
+def _stats_inputs(cpg, groups=32, T=70):
+    """x [B][cpg * groups][T] and its copy with NaN behind every row's end (nothing there is read)"""
+    B, Cn = len(STATS_LENS), cpg * groups
+    x = torch.from_numpy(synth.prng.normal(83 + cpg, B * Cn * T).reshape(B, Cn, T).copy()).float()
+    xp = x.clone()
+    for b, n in enumerate(STATS_LENS):
+        xp[b, :, n:] = float("nan")
+    return x, xp
+
+
+def _softmax_inputs(T=70):
+    """scores [B][T][T] and their copy with NaN outside every row's own block"""
+    B = len(SOFTMAX_LENS)
+    s = torch.from_numpy(synth.prng.normal(89, B * T * T).reshape(B, T, T).copy()).float() * 4.0
+    sp = s.clone()
+    for b, n in enumerate(SOFTMAX_LENS):
+        sp[b, n:, :] = float("nan")
+        sp[b, :, n:] = float("nan")
+    return s, sp
+
+
 @pytest.mark.parametrize("cpg", [1, 2, 4, 12])
 def test_gn_stats_lens_unit_equals_the_plain_kernel_on_the_compacted_clip(ctx, cpg):
     lib, groups, T = ctx.lib, 32, 70
     Cn = cpg * groups
-    lens = [70, 65, 64, 63, 22, 13, 7, 4, 3, 2, 1]
+    lens = STATS_LENS
     B = len(lens)
-    x = torch.from_numpy(synth.prng.normal(83 + cpg, B * Cn * T).reshape(B, Cn, T).copy()).float()
-    xp = x.clone()
-    for b, n in enumerate(lens):
-        xp[b, :, n:] = float("nan")                     # nothing behind a row's end is read
+    x, xp = _stats_inputs(cpg)
     xd = xp.cuda()
     mean = torch.full((B, groups), float("nan"), device="cuda")
     rstd = torch.full((B, groups), float("nan"), device="cuda")
@@ -265,13 +288,9 @@ def test_gn_stats_lens_unit_equals_the_plain_kernel_on_the_compacted_clip(ctx, c
 
 def test_softmax_rows_t_lens_unit_equals_the_plain_kernel_on_the_compacted_scores(ctx):
     lib, T = ctx.lib, 70
-    lens = [1, 63, 64, 65, 70]
+    lens = SOFTMAX_LENS
     B = len(lens)
-    s = torch.from_numpy(synth.prng.normal(89, B * T * T).reshape(B, T, T).copy()).float() * 4.0
-    sp = s.clone()
-    for b, n in enumerate(lens):
-        sp[b, n:, :] = float("nan")
-        sp[b, :, n:] = float("nan")
+    s, sp = _softmax_inputs()
     out = torch.full((B, T, T), float("nan"), device="cuda")
     sd = sp.cuda()
     assert lib.vb_softmax_rows_t_lens(L.ptr(sd), B, T, L.ptr(_dev_lens(lens)), L.ptr(out), L.stream_ptr()) == 0, lib.vb_last_error()
@@ -376,3 +395,82 @@ def test_cli_decode_lengths_files_are_byte_identical(tmp_path):
     dec = harness.plan_decode_calls(tokens)
     assert len(dec) < len(set(tokens)) and any(c["lengths"] for c in dec)
     assert [c["rows"] for c in dec] == [[0, 4, 5], [1], [2], [3]] and dec[0]["lengths"] == [150, 150, 154]
+
+
+# --------------------------------------------------------------------------------------------------------------- 10
+def _sha(*tensors):
+    h = hashlib.sha256()
+    for t in tensors:
+        h.update(t.detach().cpu().contiguous().numpy().tobytes())
+    return h.hexdigest()
+
+
+# sha256 of the raw output bytes as commit e576ae7 produced them on an MI355X - the last commit with a statistics kernel and a transposed
+# softmax per form, before the two forms became instantiations of one body (at T = 5 the narrow program runs the same kernels in fp32 and
+# fp32mf, and in bf16 and bf16xt: the equal digests).  "lens": the call with the length table (statistics: mean then
+# rstd [B][groups]; softmax: the whole [B][T][T]); "plain": the calls with len = NULL on the compacted clips, row after row (statistics:
+# mean then rstd of each; softmax: each [n][n] block).  "decode": ConvNet.decode_lens of the narrow program on SAME_ROUTE["one"].
+PARENT_BITS = {
+    "gn_stats cpg 1 lens": "cb7e59582088b752c3e64b04e4117b6f5123c493d7ab596b54eed45027236cb9",
+    "gn_stats cpg 1 plain": "3a5dbe147b98263c5b684cdf1f6bee2cc9a64ddbf3c5d72739f26242fcd9448b",
+    "gn_stats cpg 2 lens": "140295b662f09e50967575f5ce944cc54036a53bbfb539dae4e7189045f0f4eb",
+    "gn_stats cpg 2 plain": "700e5a1f06de96e7c4d528239709d7bf2c6a8ca7c7352ed13b0b45c17461b226",
+    "gn_stats cpg 4 lens": "e31ca822c3ae9ca711c760d81aa8eec659209c61e151f7b846a795d101486143",
+    "gn_stats cpg 4 plain": "327f2de717bf9338449bc17bff92ccdce681c69550139fcd74f7507a9936e24b",
+    "gn_stats cpg 12 lens": "646364e3dd9caf01ec0bf8317b1df3f1e5f0e8c4c5bf1e59af87820ba8be8e06",
+    "gn_stats cpg 12 plain": "47243e63c476e6e9e717a4afbf4196e7477f0ef4142354d9dbf9f07385848870",
+    "softmax_rows_t lens": "cf5edc442e8e60979aa838da409d046aa2ca6800352a773b0e62b87e94b350c7",
+    "softmax_rows_t plain": "8394c62ac345f658fe348b6ce0425c32a9d0af3be58745f6e4d1ce25be68230c",
+    "decode narrow fp32": "deb444bd8b20ae9aa6219d78adb426864b5fce475f544e1aaf815631e15b278b",
+    "decode narrow fp32mf": "deb444bd8b20ae9aa6219d78adb426864b5fce475f544e1aaf815631e15b278b",
+    "decode narrow split": "f67de97be3243582d4672873799a7a5658f5e450295588dc2181aa9d6475ef0b",
+    "decode narrow bf16": "5c45a578ac80a56a01d7afa339ec6fd6cd062255679bcb6855954a0dd14711b1",
+    "decode narrow bf16xt": "5c45a578ac80a56a01d7afa339ec6fd6cd062255679bcb6855954a0dd14711b1",
+}
+
+
+def test_glue_kernels_keep_the_bits_of_the_two_kernel_pairs_they_replace(ctx):
+    lib, groups, T = ctx.lib, 32, 70
+    got = {}
+    for cpg in (1, 2, 4, 12):
+        Cn, B = cpg * groups, len(STATS_LENS)
+        x, xp = _stats_inputs(cpg)
+        mean = torch.full((B, groups), float("nan"), device="cuda")
+        rstd = torch.full((B, groups), float("nan"), device="cuda")
+        assert lib.vb_gn_stats_lens(L.ptr(xp.cuda()), B, Cn, T, groups, L.ptr(_dev_lens(STATS_LENS)), L.ptr(mean), L.ptr(rstd), L.stream_ptr()) == 0, lib.vb_last_error()
+        torch.cuda.synchronize()
+        got[f"gn_stats cpg {cpg} lens"] = _sha(mean, rstd)
+        rows = []
+        for b, n in enumerate(STATS_LENS):
+            clip = x[b:b + 1, :, :n].contiguous().cuda()
+            m1 = torch.full((1, groups), float("nan"), device="cuda")
+            r1 = torch.full((1, groups), float("nan"), device="cuda")
+            assert lib.vb_gn_stats_lens(L.ptr(clip), 1, Cn, n, groups, None, L.ptr(m1), L.ptr(r1), L.stream_ptr()) == 0, lib.vb_last_error()
+            torch.cuda.synchronize()
+            rows += [m1, r1]
+        got[f"gn_stats cpg {cpg} plain"] = _sha(*rows)
+    s, sp = _softmax_inputs()
+    B = len(SOFTMAX_LENS)
+    out = torch.full((B, T, T), float("nan"), device="cuda")
+    assert lib.vb_softmax_rows_t_lens(L.ptr(sp.cuda()), B, T, L.ptr(_dev_lens(SOFTMAX_LENS)), L.ptr(out), L.stream_ptr()) == 0, lib.vb_last_error()
+    torch.cuda.synchronize()
+    got["softmax_rows_t lens"] = _sha(out)
+    rows = []
+    for b, n in enumerate(SOFTMAX_LENS):
+        blk = s[b:b + 1, :n, :n].contiguous().cuda()
+        o1 = torch.full((1, n, n), float("nan"), device="cuda")
+        assert lib.vb_softmax_rows_t_lens(L.ptr(blk), 1, n, None, L.ptr(o1), L.stream_ptr()) == 0, lib.vb_last_error()
+        torch.cuda.synchronize()
+        rows.append(o1)
+    got["softmax_rows_t plain"] = _sha(*rows)
+    assert sorted(got) == sorted(k for k in PARENT_BITS if not k.startswith("decode"))
+    for name, digest in got.items():
+        assert digest == PARENT_BITS.get(name), f"{name}: sha256 {digest}, not the parent's {PARENT_BITS.get(name)}"
+
+
+@pytest.mark.parametrize("prec", PRECISIONS)
+def test_narrow_lens_decode_keeps_the_parent_bits(nets, prec):
+    T, lens = SAME_ROUTE["one"]
+    assert T == min(t for t, _ in SAME_ROUTE.values()) and T < MIXED[0]
+    digest = _sha(lens_run(nets, "narrow", prec, T, lens))
+    assert digest == PARENT_BITS.get(f"decode narrow {prec}"), f"decode narrow {prec}: sha256 {digest}, not the parent's {PARENT_BITS.get(f'decode narrow {prec}')}"

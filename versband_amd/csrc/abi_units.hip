@@ -190,13 +190,11 @@ int vb_xt_planes(const float* x, int B, int C, int T_in, int upsample2, int in_a
 }
 int vb_gn_stats_lens(const float* x, int B, int C, int T, int groups, const int32_t* len, float* mean, float* rstd, void* stream) {
     if (!x || !mean || !rstd || B < 1 || C < 1 || T < 1 || groups < 1) VB_FAIL(VB_E_INVALID, "gn_stats_lens: null pointer or B/C/T/groups < 1");
-    if (!len) return launch_gn_stats(x, B, C, T, groups, 1e-6f, mean, rstd, (hipStream_t)stream);
-    return launch_gn_stats_lens(x, B, C, T, groups, 1e-6f, len, 1, mean, rstd, (hipStream_t)stream);
+    return launch_gn_stats(x, B, C, T, groups, 1e-6f, mean, rstd, (hipStream_t)stream, len);
 }
 int vb_softmax_rows_t_lens(const float* s, int B, int T, const int32_t* len, float* out_t, void* stream) {
     if (!s || !out_t || B < 1 || T < 1) VB_FAIL(VB_E_INVALID, "softmax_rows_t_lens: null pointer or B/T < 1");
-    if (!len) return launch_softmax_rows_t(s, B, T, T, out_t, (hipStream_t)stream);
-    return launch_softmax_rows_t_lens(s, B, T, len, 1, out_t, (hipStream_t)stream);
+    return launch_softmax_rows_t(s, B, T, T, out_t, (hipStream_t)stream, len);
 }
 int vb_aa_act(const float* x, const float* alpha, const float* inv_beta, const float* filt, int B, int C, int T, const int32_t* len, int len_mul,
               float* out, void* stream) {

@@ -52,12 +52,11 @@ int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, v
         const vb_net_op& o = n.ops[oi];
         if (o.kind == VB_OP_GN_STATS) {
             float* stp = ptr(o.stats);
-            if (nl) VB_TRY(launch_gn_stats_lens(ptr(o.x), B, o.Ci, tlen(o.x), o.gn_groups, 1e-6f, nl->table, tmul(o.x), stp, stp + (size_t)B * o.gn_groups, st));
-            else VB_TRY(launch_gn_stats(ptr(o.x), B, o.Ci, tlen(o.x), o.gn_groups, 1e-6f, stp, stp + (size_t)B * o.gn_groups, st));
+            VB_TRY(launch_gn_stats(ptr(o.x), B, o.Ci, tlen(o.x), o.gn_groups, 1e-6f, stp, stp + (size_t)B * o.gn_groups, st, nl ? nl->table : nullptr,
+                                   tmul(o.x)));
         } else if (o.kind == VB_OP_SOFTMAX_T) {
             // (lengths: the whole transposed square is written, zeros outside the row's own block - it needs no tail pass)
-            if (nl) VB_TRY(launch_softmax_rows_t_lens(ptr(o.x), B, tlen(o.x), nl->table, tmul(o.x), ptr(o.out), st));
-            else VB_TRY(launch_softmax_rows_t(ptr(o.x), B, tlen(o.x), tlen(o.x), ptr(o.out), st));
+            VB_TRY(launch_softmax_rows_t(ptr(o.x), B, tlen(o.x), tlen(o.x), ptr(o.out), st, nl ? nl->table : nullptr, tmul(o.x)));
         } else if (o.kind == VB_OP_CONV) {
             ConvArgs a;
             a.x = ptr(o.x); a.x_bstride = bstride(o.x); a.T_in = tlen(o.x);
@@ -208,22 +207,32 @@ static int net_lens_check(const NetProgram& n, int contract) {
     return VB_OK;
 }
 
-// The one lengths path of the nets (vb_hifigan_forward_lens, vb_vae_decode_lens, vb_bigvgan_forward_lens; contract: what net_lens_check
-// holds the program to).  Workspace: the net's own, the masked input, the table of row lengths.
+// The lengths entry points as data, one row per contract of net_lens_check: the net it runs, its own name (also its profiler range; messages
+// drop the "vb_") and what messages call the net; chunked: the entry point that runs the same contract chunk by chunk, where there is one.
+struct LensEntry { int which, contract; const char* name; const char* net; const char* chunked; };
+static const LensEntry LENS_ENTRIES[] = {
+    {VB_NET_VAE, LENS_VAE_DECODER, "vb_vae_decode_lens", "VAE decoder", nullptr},
+    {VB_NET_VOCODER, LENS_VOCODER, "vb_hifigan_forward_lens", "vocoder", "vb_hifigan_forward_chunked_lens"},
+    {VB_NET_VOCODER, LENS_BIGVGAN, "vb_bigvgan_forward_lens", "vocoder", "vb_bigvgan_forward_chunked_lens"}};
+static const char* fn_of(const char* name) { return name + 3; }
+
+// The one lengths path of the nets, behind every row of LENS_ENTRIES.  Workspace: the net's own, the masked input, the table of row lengths.
 static size_t net_lens_ws_bytes(vb_ctx* ctx, int which, int B, int T) {
     if (!ctx || !ctx->nets[which].loaded || B < 1 || T < 1) return 0;
     const NetProgram& n = ctx->nets[which];
     return net_ws_bytes(n, B, T, nullptr) + align_up((size_t)B * n.in_ch * T * n.in_tmul * sizeof(float)) + align_up(64 * sizeof(int));
 }
-static int net_run_lens(vb_ctx* ctx, int which, int contract, const char* fn, const char* net, const float* in, int B, int T, const vb_lens* lens,
-                        float* out, void* ws, hipStream_t st) {
+static int net_run_lens(vb_ctx* ctx, const LensEntry& e, const float* in, int B, int T, const vb_lens* lens, float* out, void* ws, hipStream_t st) {
+    const char* const fn = fn_of(e.name);
+    if (!ctx) VB_FAIL(VB_E_INVALID, "%s: null ctx", fn);
+    RoctxRange rr(e.name);
     NetLens nl;
     if (lens && lens->len) VB_TRY(lens_plan(lens->len, B, T, &nl.lp));
-    if (!nl.lp.B) return net_run(ctx, which, in, B, T, out, ws, st);                   // no lengths, or every row full: the plain entry point
-    NetProgram& n = ctx->nets[which];
-    if (!n.loaded) VB_FAIL(VB_E_STATE, "%s: no %s loaded", fn, net);
-    VB_TRY(net_lens_check(n, contract));
-    if (n.in_tmul != 1) VB_FAIL(VB_E_INVALID, "%s: the %s's input runs at %d samples per frame (1)", fn, net, n.in_tmul);
+    if (!nl.lp.B) return net_run(ctx, e.which, in, B, T, out, ws, st);                 // no lengths, or every row full: the plain entry point
+    NetProgram& n = ctx->nets[e.which];
+    if (!n.loaded) VB_FAIL(VB_E_STATE, "%s: no %s loaded", fn, e.net);
+    VB_TRY(net_lens_check(n, e.contract));
+    if (n.in_tmul != 1) VB_FAIL(VB_E_INVALID, "%s: the %s's input runs at %d samples per frame (1)", fn, e.net, n.in_tmul);
     VB_HIP(hipSetDevice(ctx->device));
     char* p = static_cast<char*>(ws) + net_ws_bytes(n, B, T, nullptr);
     float* masked = reinterpret_cast<float*>(p);
@@ -231,18 +240,20 @@ static int net_run_lens(vb_ctx* ctx, int which, int contract, const char* fn, co
     VB_TRY(launch_lens_table(nl.lp, table, st));
     nl.table = table;
     VB_TRY(launch_mask_latent(in, B, n.in_ch, T, table, masked, st));                  // (a select: the caller's padding, NaN included, is not read)
-    return net_run(ctx, which, masked, B, T, out, ws, st, &nl);
+    return net_run(ctx, e.which, masked, B, T, out, ws, st, &nl);
 }
 
 // The plan of the chunked vocoder with row lengths (include/versband_hip.h, vb_hifigan_forward_chunked_lens): the chunk grid of
 // vb_hifigan_forward_chunked - T <= chunk + 2 * halo is one step over the whole rows, as there - and per step the rows that have not ended
-// before it with their frames inside it.  The one function behind the entry point and vb_hifigan_chunked_lens_plan.  len: HOST array.
+// before it with their frames inside it.  The one function behind the entry point and vb_hifigan_chunked_lens_plan.  len: HOST array;
+// lens: the checked lengths (B = 0 in it when every row is full), for the caller that wants them.
 struct ChunkStep { int s, e, lo, tc; ChunkRows rows; };
-static int chunk_lens_plan(int B, int T, int chunk, int halo, const int32_t* len, std::vector<ChunkStep>* out) {
+static int chunk_lens_plan(int B, int T, int chunk, int halo, const int32_t* len, std::vector<ChunkStep>* out, LensPlan* lens = nullptr) {
     if (chunk < 1 || halo < 0) VB_FAIL(VB_E_INVALID, "hifigan_forward_chunked_lens: chunk=%d halo=%d", chunk, halo);
     if (T < 1) VB_FAIL(VB_E_INVALID, "hifigan_forward_chunked_lens: T=%d", T);
     LensPlan lp;
     VB_TRY(lens_plan(len, B, T, &lp));                 // (B <= 64, 1 <= len[b] <= T: the row is named)
+    if (lens) *lens = lp;
     out->clear();
     const bool whole = T <= (int64_t)chunk + 2 * (int64_t)halo;
     for (int64_t s64 = 0; s64 < T; s64 += whole ? T : chunk) {
@@ -294,26 +305,24 @@ static int net_op_fields(int kind, int wfmt, int Co) {
     return -1;
 }
 
-// The chunked vocoder with row lengths, behind vb_hifigan_forward_chunked_lens (contract LENS_VOCODER, fn "hifigan_forward") and
-// vb_bigvgan_forward_chunked_lens (LENS_BIGVGAN, "bigvgan_forward"): one plan, one gather / scatter, one loop.
-static int chunked_lens_run(vb_ctx* ctx, int contract, const char* fn, const float* mel, int B, int T, int chunk, int halo, const vb_lens* lens,
-                            float* wav, void* ws, float* scratch_in, float* scratch_out, void* stream) {
-    if (!ctx) VB_FAIL(VB_E_INVALID, "%s_chunked_lens: null ctx", fn);
-    if (chunk < 1 || halo < 0) VB_FAIL(VB_E_INVALID, "%s_chunked_lens: chunk=%d halo=%d", fn, chunk, halo);
-    NetProgram& net = ctx->nets[VB_NET_VOCODER];
-    if (!net.loaded) VB_FAIL(VB_E_INVALID, "%s_chunked_lens: no vocoder loaded", fn);
+// The chunked vocoder with row lengths, behind the `chunked` entry points of LENS_ENTRIES: one plan, one gather / scatter, one loop.
+static int chunked_lens_run(vb_ctx* ctx, const LensEntry& e, const float* mel, int B, int T, int chunk, int halo, const vb_lens* lens, float* wav,
+                            void* ws, float* scratch_in, float* scratch_out, void* stream) {
+    const char* const fn = fn_of(e.chunked);
+    if (!ctx) VB_FAIL(VB_E_INVALID, "%s: null ctx", fn);
+    if (chunk < 1 || halo < 0) VB_FAIL(VB_E_INVALID, "%s: chunk=%d halo=%d", fn, chunk, halo);
+    NetProgram& net = ctx->nets[e.which];
+    if (!net.loaded) VB_FAIL(VB_E_INVALID, "%s: no vocoder loaded", fn);
     if (!lens || !lens->len) return vb_hifigan_forward_chunked(ctx, mel, B, T, chunk, halo, wav, ws, scratch_in, scratch_out, stream);
     std::vector<ChunkStep> plan;
-    VB_TRY(chunk_lens_plan(B, T, chunk, halo, lens->len, &plan));
-    bool full = true;
-    for (int b = 0; b < B; ++b) full = full && lens->len[b] == T;
-    if (full) return vb_hifigan_forward_chunked(ctx, mel, B, T, chunk, halo, wav, ws, scratch_in, scratch_out, stream);
-    if (T <= (int64_t)chunk + 2 * (int64_t)halo)
-        return contract == LENS_BIGVGAN ? vb_bigvgan_forward_lens(ctx, mel, B, T, lens, wav, ws, stream) : vb_hifigan_forward_lens(ctx, mel, B, T, lens, wav, ws, stream);
-    VB_TRY(net_lens_check(net, contract));
-    if (net.in_tmul != 1) VB_FAIL(VB_E_INVALID, "%s_chunked_lens: the vocoder's input runs at %d samples per frame (1)", fn, net.in_tmul);
+    LensPlan lp;
+    VB_TRY(chunk_lens_plan(B, T, chunk, halo, lens->len, &plan, &lp));
+    if (!lp.B) return vb_hifigan_forward_chunked(ctx, mel, B, T, chunk, halo, wav, ws, scratch_in, scratch_out, stream);      // every row full
     hipStream_t st = (hipStream_t)stream;
-    RoctxRange rr(contract == LENS_BIGVGAN ? "vb_bigvgan_forward_chunked_lens" : "vb_hifigan_forward_chunked_lens");
+    if (T <= (int64_t)chunk + 2 * (int64_t)halo) return net_run_lens(ctx, e, mel, B, T, lens, wav, ws, st);                  // whole rows
+    VB_TRY(net_lens_check(net, e.contract));
+    if (net.in_tmul != 1) VB_FAIL(VB_E_INVALID, "%s: the vocoder's input runs at %d samples per frame (1)", fn, net.in_tmul);
+    RoctxRange rr(e.chunked);
     VB_HIP(hipSetDevice(ctx->device));
     const int hop = net.out_tmul;
     int* table = reinterpret_cast<int*>(static_cast<char*>(ws) + net_ws_bytes(net, B, chunk + 2 * halo, nullptr));
@@ -339,7 +348,7 @@ static int chunked_lens_run(vb_ctx* ctx, int contract, const char* fn, const flo
                 VB_TRY(launch_lens_table(nl.lp, table, st));
                 nl.table = table;
             }
-            VB_TRY(net_run(ctx, VB_NET_VOCODER, scratch_in, c.rows.n_active, c.tc, scratch_out, ws, st, short_row ? &nl : nullptr));
+            VB_TRY(net_run(ctx, e.which, scratch_in, c.rows.n_active, c.tc, scratch_out, ws, st, short_row ? &nl : nullptr));
         }
         VB_TRY(launch_chunk_scatter(scratch_out, cs, B, net.out_ch, T, hop, c.s, c.e, c.lo, c.tc, wav, st));
     }
@@ -417,17 +426,13 @@ int vb_hifigan_forward(vb_ctx* ctx, const float* mel, int B, int T, float* wav, 
     RoctxRange rr("vb_hifigan_forward");
     return net_run(ctx, VB_NET_VOCODER, mel, B, T, wav, ws, (hipStream_t)stream);
 }
-size_t vb_hifigan_lens_workspace_bytes(vb_ctx* ctx, int B, int T) { return net_lens_ws_bytes(ctx, VB_NET_VOCODER, B, T); }
+size_t vb_hifigan_lens_workspace_bytes(vb_ctx* ctx, int B, int T) { return net_lens_ws_bytes(ctx, LENS_ENTRIES[LENS_VOCODER].which, B, T); }
 int vb_hifigan_forward_lens(vb_ctx* ctx, const float* mel, int B, int T, const vb_lens* lens, float* wav, void* ws, void* stream) {
-    if (!ctx) VB_FAIL(VB_E_INVALID, "hifigan_forward_lens: null ctx");
-    RoctxRange rr("vb_hifigan_forward_lens");
-    return net_run_lens(ctx, VB_NET_VOCODER, LENS_VOCODER, "hifigan_forward_lens", "vocoder", mel, B, T, lens, wav, ws, (hipStream_t)stream);
+    return net_run_lens(ctx, LENS_ENTRIES[LENS_VOCODER], mel, B, T, lens, wav, ws, (hipStream_t)stream);
 }
-size_t vb_vae_decode_lens_workspace_bytes(vb_ctx* ctx, int B, int T) { return net_lens_ws_bytes(ctx, VB_NET_VAE, B, T); }
+size_t vb_vae_decode_lens_workspace_bytes(vb_ctx* ctx, int B, int T) { return net_lens_ws_bytes(ctx, LENS_ENTRIES[LENS_VAE_DECODER].which, B, T); }
 int vb_vae_decode_lens(vb_ctx* ctx, const float* z, int B, int T, const vb_lens* lens, float* mel, void* ws, void* stream) {
-    if (!ctx) VB_FAIL(VB_E_INVALID, "vae_decode_lens: null ctx");
-    RoctxRange rr("vb_vae_decode_lens");
-    return net_run_lens(ctx, VB_NET_VAE, LENS_VAE_DECODER, "vae_decode_lens", "VAE decoder", z, B, T, lens, mel, ws, (hipStream_t)stream);
+    return net_run_lens(ctx, LENS_ENTRIES[LENS_VAE_DECODER], z, B, T, lens, mel, ws, (hipStream_t)stream);
 }
 int vb_crossfade_windows(const float* parts, const int32_t* starts, int nw, int B, int C, int n, int T, float* out, void* stream) {
     if (!parts || !starts || !out || nw < 1 || B < 1 || C < 1 || n < 1 || T < 1) VB_FAIL(VB_E_INVALID, "crossfade_windows: null pointer or nw/B/C/n/T < 1");
@@ -481,22 +486,20 @@ int vb_hifigan_chunked_lens_plan(int B, int T, int chunk, int halo, const int32_
     }
     return VB_OK;
 }
-size_t vb_bigvgan_lens_workspace_bytes(vb_ctx* ctx, int B, int T) { return net_lens_ws_bytes(ctx, VB_NET_VOCODER, B, T); }
+size_t vb_bigvgan_lens_workspace_bytes(vb_ctx* ctx, int B, int T) { return net_lens_ws_bytes(ctx, LENS_ENTRIES[LENS_BIGVGAN].which, B, T); }
 int vb_bigvgan_forward_lens(vb_ctx* ctx, const float* mel, int B, int T, const vb_lens* lens, float* wav, void* ws, void* stream) {
-    if (!ctx) VB_FAIL(VB_E_INVALID, "bigvgan_forward_lens: null ctx");
-    RoctxRange rr("vb_bigvgan_forward_lens");
-    return net_run_lens(ctx, VB_NET_VOCODER, LENS_BIGVGAN, "bigvgan_forward_lens", "vocoder", mel, B, T, lens, wav, ws, (hipStream_t)stream);
+    return net_run_lens(ctx, LENS_ENTRIES[LENS_BIGVGAN], mel, B, T, lens, wav, ws, (hipStream_t)stream);
 }
 int vb_hifigan_forward_chunked_lens(vb_ctx* ctx, const float* mel, int B, int T, int chunk, int halo, const vb_lens* lens, float* wav, void* ws,
                                     float* scratch_in, float* scratch_out, void* stream) {
-    return chunked_lens_run(ctx, LENS_VOCODER, "hifigan_forward", mel, B, T, chunk, halo, lens, wav, ws, scratch_in, scratch_out, stream);
+    return chunked_lens_run(ctx, LENS_ENTRIES[LENS_VOCODER], mel, B, T, chunk, halo, lens, wav, ws, scratch_in, scratch_out, stream);
 }
 size_t vb_bigvgan_chunked_lens_workspace_bytes(vb_ctx* ctx, int B, int T, int chunk, int halo) {
     return vb_hifigan_chunked_lens_workspace_bytes(ctx, B, T, chunk, halo);
 }
 int vb_bigvgan_forward_chunked_lens(vb_ctx* ctx, const float* mel, int B, int T, int chunk, int halo, const vb_lens* lens, float* wav, void* ws,
                                     float* scratch_in, float* scratch_out, void* stream) {
-    return chunked_lens_run(ctx, LENS_BIGVGAN, "bigvgan_forward", mel, B, T, chunk, halo, lens, wav, ws, scratch_in, scratch_out, stream);
+    return chunked_lens_run(ctx, LENS_ENTRIES[LENS_BIGVGAN], mel, B, T, chunk, halo, lens, wav, ws, scratch_in, scratch_out, stream);
 }
 
 }  // extern "C"

@@ -379,11 +379,10 @@ int launch_fill_gumbel(float* out, int B, int n_branch, int T, int width, uint64
 // ---------------------------------------------------------------------------
 // net_glue.hip: what the conv-net executor runs between its convolutions
 // ---------------------------------------------------------------------------
-int launch_gn_stats(const float* x, int B, int C, int T, int groups, float eps, float* mean, float* rstd, hipStream_t st);
-// row lengths (vb_vae_decode_lens; len: device [B], in units of len_mul samples): the statistics of row b's first len[b] * len_mul samples per
-// channel, the bits of launch_gn_stats on that clip alone
-int launch_gn_stats_lens(const float* x, int B, int C, int T, int groups, float eps, const int* len, int len_mul, float* mean, float* rstd,
-                         hipStream_t st);
+// (len non-null - row lengths, vb_vae_decode_lens; device [B], in units of len_mul samples: the statistics of row b's first len[b] * len_mul
+//  samples per channel, the bits of the plain form on that clip alone)
+int launch_gn_stats(const float* x, int B, int C, int T, int groups, float eps, float* mean, float* rstd, hipStream_t st, const int* len = nullptr,
+                    int len_mul = 1);
 // (len non-null: out is zero from len[b] * len_mul on - the activated tensor ends at the row's own length)
 int launch_gn_apply(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int B, int C, int T,
                     int groups, int swish, float* out, hipStream_t st, const int* len = nullptr, int len_mul = 1);
@@ -400,9 +399,8 @@ int launch_aa_act(const float* x, const float* alpha, const float* inv_beta, con
                   const int* len = nullptr, int len_mul = 1);
 // f32 [rows][cols] -> split-bf16 planes [2][rows][cpad] (cpad % 4 == 0, columns >= cols zero filled)
 int launch_split_rows(const float* x, int64_t rows, int cols, int cpad, bf16_t* out, int64_t plane, hipStream_t st);
-int launch_softmax_rows_t(const float* s, int B, int R, int Ccols, float* out_t, hipStream_t st);
-// row lengths: s [B][R][R], row b's softmax over its leading len[b] * len_mul keys and queries, exact zeros elsewhere in out_t [B][R][R]
-int launch_softmax_rows_t_lens(const float* s, int B, int R, const int* len, int len_mul, float* out_t, hipStream_t st);
+// (len non-null: s [B][R][R], row b's softmax over its leading len[b] * len_mul keys and queries, exact zeros elsewhere in out_t [B][R][R])
+int launch_softmax_rows_t(const float* s, int B, int R, int Ccols, float* out_t, hipStream_t st, const int* len = nullptr, int len_mul = 1);
 int launch_crossfade_windows(const float* parts, const int* starts, int nw, int B, int C, int n, int T, float* out, hipStream_t st);   // starts: HOST array
 // chunked vocoder with row lengths (vb_hifigan_forward_chunked_lens): the rows of one chunk, by value in the kernels' argument blocks like
 // LensPlan.  row[j] / n[j], j < n_active: the clip of compact row j (ascending) and its frames inside the chunk, 1 <= n[j] <= tc.

@@ -6,94 +6,55 @@
 // ---------------------------------------------------------------------------
 // GroupNorm statistics (autoencoder1d.py:165-166): one block per (b, group); the group's
 // channels are contiguous in [B][C][T].  Two-pass mean / biased variance.
+//
+// One body, two instantiations that differ in indexing alone.  Plain: the group is one flat slab of n = C/groups * T samples, read as
+// p[i], as float4 when n % 4 == 0 and the slab is 16-byte aligned.  LENS (row lengths, vb_vae_decode_lens): the group of row b is C/groups
+// channel rows of L = len[b] * len_mul valid samples at pitch T, and valid sample i (flat, channel-major) of the compacted clip [C/groups][L]
+// goes to the thread the plain form gives it - float4 group i / 4 to thread (i / 4) % 1024 exactly when the compacted slab would take that
+// path (n % 4 == 0; its base is then 16-byte aligned in an aligned buffer), one float per thread otherwise.  A group of four inside one
+// channel row is one 16-byte load when the row pieces are aligned (L % 4 == 0, T % 4 == 0), four 4-byte loads where it straddles two
+// rows.  Nothing behind a row's end is read.  The arithmetic is the body's own, so row b's statistics are the plain form's on the clip
+// alone, bit for bit.
 // ---------------------------------------------------------------------------
 #define GS_T 1024
-__global__ void __launch_bounds__(GS_T) gn_stats_kernel(const float* __restrict__ x, int C, int T, int groups, float eps, float* mean,
-                                                       float* rstd) {
-    __shared__ float red[GS_T / 64];
-    __shared__ float s_mean;
-    const int bg = blockIdx.x;
-    const int64_t n = (int64_t)(C / groups) * T;
-    const float* p = x + (int64_t)bg * n;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool vec = (n & 3) == 0 && ((reinterpret_cast<uintptr_t>(p) & 15) == 0);
-    const int64_t n4 = vec ? n / 4 : 0;
-    float s = 0.f;
-    for (int64_t i = threadIdx.x; i < n4; i += GS_T) {
-        const float4 v = reinterpret_cast<const float4*>(p)[i];
-        s += (v.x + v.y) + (v.z + v.w);
-    }
-    for (int64_t i = n4 * 4 + threadIdx.x; i < n; i += GS_T) s += p[i];
-    s = wave_sum(s);
-    if (lane == 0) red[wave] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int w = 0; w < GS_T / 64; ++w) t += red[w];
-        s_mean = t / (float)n;
-    }
-    __syncthreads();
-    const float m = s_mean;
-    float v = 0.f;
-    for (int64_t i = threadIdx.x; i < n4; i += GS_T) {
-        const float4 q = reinterpret_cast<const float4*>(p)[i];
-        const float d0 = q.x - m, d1 = q.y - m, d2 = q.z - m, d3 = q.w - m;
-        v += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-    }
-    for (int64_t i = n4 * 4 + threadIdx.x; i < n; i += GS_T) { float d = p[i] - m; v += d * d; }
-    v = wave_sum(v);
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int w = 0; w < GS_T / 64; ++w) t += red[w];
-        mean[bg] = m;
-        rstd[bg] = rsqrtf(t / (float)n + eps);
-    }
-}
-int launch_gn_stats(const float* x, int B, int C, int T, int groups, float eps, float* mean, float* rstd, hipStream_t st) {
-    if (C % groups) VB_FAIL(VB_E_INVALID, "gn_stats: C%%groups");
-    hipLaunchKernelGGL(gn_stats_kernel, dim3(B * groups), dim3(GS_T), 0, st, x, C, T, groups, eps, mean, rstd);
-    VB_CHECK_LAUNCH();
-    return VB_OK;
-}
-
-// Row lengths (vb_vae_decode_lens): the group of row b is C/groups channel rows of L = len[b] * len_mul valid samples at pitch T, and the
-// statistics are the plain kernel's on the compacted clip [C/groups][L], bit for bit: valid sample i (flat, channel-major) goes to the thread
-// the plain kernel gives it - float4 group i / 4 to thread (i / 4) % 1024, summed (x + y) + (z + w), exactly when the compacted slab would
-// take that path (n % 4 == 0; its base is then 16-byte aligned in an aligned buffer), one float per thread otherwise - with the same two
-// passes and the same final order.  A group of four inside one channel row is one 16-byte load when the row pieces are aligned
-// (L % 4 == 0, T % 4 == 0), four 4-byte loads where it straddles two rows.  Nothing behind a row's end is read.
-__global__ void __launch_bounds__(GS_T) gn_stats_lens_kernel(const float* __restrict__ x, int C, int T, int groups, float eps,
-                                                            const int* __restrict__ len, int len_mul, float* mean, float* rstd) {
-    // The squares below are written as the compiler contracts the plain kernel's (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3) and v += d * d
-    // - fma(d0, d0, d1 * d1) + fma(d2, d2, d3 * d3), fma(d, d, v) - with contraction off, so that the two kernels round alike whatever
-    // the loads around them look like (tests/test_gpu_vae_lens.py holds the two to the same bits).
+template <bool LENS>
+__global__ void __launch_bounds__(GS_T) gn_stats_kernel(const float* __restrict__ x, int C, int T, int groups, float eps,
+                                                       const int* __restrict__ len, int len_mul, float* mean, float* rstd) {
+    // Contraction is off and every fused multiply-add is spelled out, so that both instantiations round alike whatever the loads around
+    // the arithmetic look like (tests/test_gpu_vae_lens.py holds the two to the same bits, and to those of the kernels before them).
 #pragma clang fp contract(off)
+    using idx_t = std::conditional_t<LENS, int, int64_t>;          // (LENS: the launcher keeps a group under 2^31 samples)
     __shared__ float red[GS_T / 64];
     __shared__ float s_mean;
     const int bg = blockIdx.x;
     const int cpg = C / groups;
-    const int L = len[bg / groups] * len_mul;
-    const int n = cpg * L;
+    const int L = LENS ? len[bg / groups] * len_mul : T;
+    const idx_t n = (idx_t)cpg * L;
     const float* p = x + (int64_t)bg * cpg * T;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool vec = (n & 3) == 0;
-    const bool quad = (L & 3) == 0 && (T & 3) == 0 && ((reinterpret_cast<uintptr_t>(p) & 15) == 0);
-    const int n4 = vec ? n / 4 : 0;
-    auto at = [&](int i) -> float { const int r = i / L; return p[(int64_t)r * T + (i - r * L)]; };
-    auto at4 = [&](int i4) -> float4 {
-        const int i = 4 * i4;
-        if (quad) { const int r = i / L; return *reinterpret_cast<const float4*>(p + (int64_t)r * T + (i - r * L)); }
-        return make_float4(at(i), at(i + 1), at(i + 2), at(i + 3));
+    const bool aligned = (reinterpret_cast<uintptr_t>(p) & 15) == 0;
+    const bool vec = (n & 3) == 0 && (LENS || aligned);
+    const bool quad = (L & 3) == 0 && (T & 3) == 0 && aligned;     // (LENS only)
+    const idx_t n4 = vec ? n / 4 : 0;
+    auto at = [&](idx_t i) -> float {
+        if constexpr (LENS) { const int r = i / L; return p[(int64_t)r * T + (i - r * L)]; }
+        else return p[i];
+    };
+    auto at4 = [&](idx_t i4) -> float4 {
+        if constexpr (LENS) {
+            const int i = 4 * i4;
+            if (quad) { const int r = i / L; return *reinterpret_cast<const float4*>(p + (int64_t)r * T + (i - r * L)); }
+            return make_float4(at(i), at(i + 1), at(i + 2), at(i + 3));
+        } else {
+            return reinterpret_cast<const float4*>(p)[i4];
+        }
     };
     float s = 0.f;
-    for (int i = threadIdx.x; i < n4; i += GS_T) {
+    for (idx_t i = threadIdx.x; i < n4; i += GS_T) {
         const float4 v = at4(i);
         s += (v.x + v.y) + (v.z + v.w);
     }
-    for (int i = n4 * 4 + threadIdx.x; i < n; i += GS_T) s += at(i);
+    for (idx_t i = n4 * 4 + threadIdx.x; i < n; i += GS_T) s += at(i);
     s = wave_sum(s);
     if (lane == 0) red[wave] = s;
     __syncthreads();
@@ -105,12 +66,12 @@ __global__ void __launch_bounds__(GS_T) gn_stats_lens_kernel(const float* __rest
     __syncthreads();
     const float m = s_mean;
     float v = 0.f;
-    for (int i = threadIdx.x; i < n4; i += GS_T) {
+    for (idx_t i = threadIdx.x; i < n4; i += GS_T) {
         const float4 q = at4(i);
         const float d0 = q.x - m, d1 = q.y - m, d2 = q.z - m, d3 = q.w - m;
         v += fmaf(d0, d0, d1 * d1) + fmaf(d2, d2, d3 * d3);
     }
-    for (int i = n4 * 4 + threadIdx.x; i < n; i += GS_T) { float d = at(i) - m; v = fmaf(d, d, v); }
+    for (idx_t i = n4 * 4 + threadIdx.x; i < n; i += GS_T) { float d = at(i) - m; v = fmaf(d, d, v); }
     v = wave_sum(v);
     __syncthreads();
     if (lane == 0) red[wave] = v;
@@ -122,11 +83,12 @@ __global__ void __launch_bounds__(GS_T) gn_stats_lens_kernel(const float* __rest
         rstd[bg] = rsqrtf(t / (float)n + eps);
     }
 }
-int launch_gn_stats_lens(const float* x, int B, int C, int T, int groups, float eps, const int* len, int len_mul, float* mean, float* rstd,
-                         hipStream_t st) {
+int launch_gn_stats(const float* x, int B, int C, int T, int groups, float eps, float* mean, float* rstd, hipStream_t st, const int* len,
+                    int len_mul) {
     if (C % groups) VB_FAIL(VB_E_INVALID, "gn_stats: C%%groups");
-    if (!len || len_mul < 1 || (int64_t)(C / groups) * T >= (1ll << 31)) VB_FAIL(VB_E_INVALID, "gn_stats: no row lengths, len_mul < 1 or a group of 2^31 samples");
-    hipLaunchKernelGGL(gn_stats_lens_kernel, dim3(B * groups), dim3(GS_T), 0, st, x, C, T, groups, eps, len, len_mul, mean, rstd);
+    if (len && (len_mul < 1 || (int64_t)(C / groups) * T >= (1ll << 31))) VB_FAIL(VB_E_INVALID, "gn_stats: len_mul < 1 or a group of 2^31 samples");
+    hipLaunchKernelGGL(len ? gn_stats_kernel<true> : gn_stats_kernel<false>, dim3(B * groups), dim3(GS_T), 0, st, x, C, T, groups, eps, len, len_mul,
+                       mean, rstd);
     VB_CHECK_LAUNCH();
     return VB_OK;
 }
@@ -351,44 +313,24 @@ int launch_split_rows(const float* x, int64_t rows, int cols, int cpad, bf16_t* 
     return VB_OK;
 }
 
-// softmax over the last dim of s[B][R][Cc], written transposed: out_t[b][c][r]
-__global__ void __launch_bounds__(256) softmax_rows_t_kernel(const float* __restrict__ s, int R, int Cc, float* out_t) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int b = blockIdx.y;
-    const int lane = threadIdx.x & 63;
-    if (row >= R) return;
-    const float* p = s + ((int64_t)b * R + row) * Cc;
-    float m = -INFINITY;
-    for (int c = lane; c < Cc; c += 64) m = fmaxf(m, p[c]);
-    m = wave_max(m);
-    float sum = 0.f;
-    for (int c = lane; c < Cc; c += 64) sum += expf(p[c] - m);
-    sum = wave_sum(sum);
-    const float inv = 1.f / sum;
-    for (int c = lane; c < Cc; c += 64) out_t[((int64_t)b * Cc + c) * R + row] = expf(p[c] - m) * inv;
-}
-int launch_softmax_rows_t(const float* s, int B, int R, int Ccols, float* out_t, hipStream_t st) {
-    hipLaunchKernelGGL(softmax_rows_t_kernel, dim3(cdiv(R, 4), B), dim3(256), 0, st, s, R, Ccols, out_t);
-    VB_CHECK_LAUNCH();
-    return VB_OK;
-}
-
-// Row lengths (vb_vae_decode_lens): s [B][R][R] holds row b's scores in its leading L x L block (L = len[b] * len_mul); query row r < L takes
-// its softmax over the keys c < L with the lane stride and the order of the plain kernel at Cc = L, and everything outside the block of the
+// softmax over the last dim of s[B][R][Cc], written transposed: out_t[b][c][r].  One body, two instantiations.  LENS (row lengths,
+// vb_vae_decode_lens; Cc = R): s [B][R][R] holds row b's scores in its leading L x L block (L = len[b] * len_mul); query row r < L takes its
+// softmax over the keys c < L with the lane stride and the order of the plain form at Cc = L, and everything outside the block of the
 // transposed result - keys and queries behind the row's end - is written as exact zeros.  Nothing outside the block is read.
-__global__ void __launch_bounds__(256) softmax_rows_t_lens_kernel(const float* __restrict__ s, int R, const int* __restrict__ len, int len_mul,
-                                                                 float* out_t) {
+template <bool LENS>
+__global__ void __launch_bounds__(256) softmax_rows_t_kernel(const float* __restrict__ s, int R, int Cc, const int* __restrict__ len, int len_mul,
+                                                            float* out_t) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int b = blockIdx.y;
     const int lane = threadIdx.x & 63;
     if (row >= R) return;
-    const int L = len[b] * len_mul;
-    float* o = out_t + (int64_t)b * R * R + row;
-    if (row >= L) {
-        for (int c = lane; c < R; c += 64) o[(int64_t)c * R] = 0.f;
+    const int L = LENS ? len[b] * len_mul : Cc;                  // the keys of this row's softmax
+    float* o = out_t + (int64_t)b * Cc * R + row;
+    if (LENS && row >= L) {
+        for (int c = lane; c < Cc; c += 64) o[(int64_t)c * R] = 0.f;
         return;
     }
-    const float* p = s + ((int64_t)b * R + row) * R;
+    const float* p = s + ((int64_t)b * R + row) * Cc;
     float m = -INFINITY;
     for (int c = lane; c < L; c += 64) m = fmaxf(m, p[c]);
     m = wave_max(m);
@@ -397,11 +339,13 @@ __global__ void __launch_bounds__(256) softmax_rows_t_lens_kernel(const float* _
     sum = wave_sum(sum);
     const float inv = 1.f / sum;
     for (int c = lane; c < L; c += 64) o[(int64_t)c * R] = expf(p[c] - m) * inv;
-    for (int c = L + lane; c < R; c += 64) o[(int64_t)c * R] = 0.f;
+    if (LENS)
+        for (int c = L + lane; c < Cc; c += 64) o[(int64_t)c * R] = 0.f;
 }
-int launch_softmax_rows_t_lens(const float* s, int B, int R, const int* len, int len_mul, float* out_t, hipStream_t st) {
-    if (!len || len_mul < 1) VB_FAIL(VB_E_INVALID, "softmax_rows_t: no row lengths or len_mul < 1");
-    hipLaunchKernelGGL(softmax_rows_t_lens_kernel, dim3(cdiv(R, 4), B), dim3(256), 0, st, s, R, len, len_mul, out_t);
+int launch_softmax_rows_t(const float* s, int B, int R, int Ccols, float* out_t, hipStream_t st, const int* len, int len_mul) {
+    if (len && (len_mul < 1 || Ccols != R)) VB_FAIL(VB_E_INVALID, "softmax_rows_t: len_mul < 1, or row lengths on scores that are not square");
+    hipLaunchKernelGGL(len ? softmax_rows_t_kernel<true> : softmax_rows_t_kernel<false>, dim3(cdiv(R, 4), B), dim3(256), 0, st, s, R, Ccols, len,
+                       len_mul, out_t);
     VB_CHECK_LAUNCH();
     return VB_OK;
 }

@@ -762,12 +762,12 @@ class ConvNet:
         bufs = (L.BufDesc * max(1, len(nb.bufs)))(*[L.BufDesc(*b) for b in nb.bufs])
         L.check(ctx.lib.vb_net_load(ctx.handle, which, ops, len(nb.ops), bufs, len(nb.bufs), in_ch, out_ch, in_tmul, out_tmul),
                 "vb_net_load")
-        # scratch that is sized for a call's (B, T) and made again when that changes: slot -> ((B, T), the buffers)
-        self._scratch = {"net": (None, None), "lens": (None, None), "chunk": (None, None), "chunk_lens": (None, None),
-                         "vocode_lens": (None, None)}
+        # scratch that is sized for a call's shape and made again when that changes: slot -> (the shape, the buffers).  Slots: "net" (the
+        # plain workspace), "chunk" (the chunk scratch) and one per lengths entry point, under its own name
+        self._scratch = {}
 
-    def _cached(self, slot: str, key: Tuple[int, int], make):
-        if self._scratch[slot][0] != key:
+    def _cached(self, slot: str, key: Tuple[int, ...], make):
+        if self._scratch.get(slot, (None, None))[0] != key:
             self._scratch[slot] = (key, make())
         return self._scratch[slot][1]
 
@@ -797,7 +797,7 @@ class ConvNet:
                                  f"vocoder net alone{hint})")
             lens, hold, _ = _lens_struct(lengths, B, T, gloss=" (input frames per row)")
             if lens is not None:
-                return self._run_lens(x, B, T, lens, hold)
+                return self._lens_call("vb_hifigan_forward_lens", x, B, T, lens, hold)
         out = torch.empty(B, self.out_ch, T * self.out_tmul, dtype=torch.float32, device=self.ctx.device)
         ws = self._workspace(B, T)
         fn = {L.NET_VAE: self.ctx.lib.vb_vae_decode, L.NET_VOCODER: self.ctx.lib.vb_hifigan_forward,
@@ -805,11 +805,28 @@ class ConvNet:
         L.check(fn(self.ctx.handle, L.ptr(x), B, T, L.ptr(out), L.ptr(ws), L.stream_ptr()), "conv net run")
         return out
 
-    def _run_lens(self, x: Tensor, B: int, T: int, lens, hold) -> Tensor:
+    def _chunk_scratch(self, B: int, tc: int):
+        """(cin, cout) of the chunked entry points: one chunk with its halos, tc frames, of every row - gathered input, generator output"""
+        dev = self.ctx.device
+        return self._cached("chunk", (B, tc), lambda: (torch.empty(B * self.in_ch * tc, dtype=torch.float32, device=dev),
+                                                       torch.empty(B * self.out_ch * tc * self.out_tmul, dtype=torch.float32, device=dev)))
+
+    # the lengths entry points and the function that sizes each one's workspace (with B, T and, chunked, chunk and halo)
+    LENS_WORKSPACE = {"vb_hifigan_forward_lens": "vb_hifigan_lens_workspace_bytes",
+                      "vb_vae_decode_lens": "vb_vae_decode_lens_workspace_bytes",
+                      "vb_bigvgan_forward_lens": "vb_bigvgan_lens_workspace_bytes",
+                      "vb_hifigan_forward_chunked_lens": "vb_hifigan_chunked_lens_workspace_bytes",
+                      "vb_bigvgan_forward_chunked_lens": "vb_bigvgan_chunked_lens_workspace_bytes"}
+
+    def _lens_call(self, name: str, x: Tensor, B: int, T: int, lens, hold, chunked: Tuple[int, ...] = ()) -> Tensor:
+        """the lengths entry point `name` on rows x [B, in_ch, T] (contiguous fp32 on the device); lens / hold: the vb_lens struct and
+        its host array (_lens_struct); chunked: (chunk, halo) for the chunked entry points, which also take the chunk scratch"""
+        lib, handle = self.ctx.lib, self.ctx.handle
         out = torch.empty(B, self.out_ch, T * self.out_tmul, dtype=torch.float32, device=self.ctx.device)
-        ws = self._cached("lens", (B, T), lambda: self._bytes(self.ctx.lib.vb_hifigan_lens_workspace_bytes(self.ctx.handle, B, T)))
-        L.check(self.ctx.lib.vb_hifigan_forward_lens(self.ctx.handle, L.ptr(x), B, T, C.byref(lens), L.ptr(out), L.ptr(ws), L.stream_ptr()),
-                "vb_hifigan_forward_lens")
+        shape = (B, T) + tuple(chunked)
+        ws = self._cached(name, shape, lambda: self._bytes(getattr(lib, self.LENS_WORKSPACE[name])(handle, *shape)))
+        scratch = [L.ptr(t) for t in self._chunk_scratch(B, chunked[0] + 2 * chunked[1])] if chunked else []
+        L.check(getattr(lib, name)(handle, L.ptr(x), *shape, C.byref(lens), L.ptr(out), L.ptr(ws), *scratch, L.stream_ptr()), name)
         del hold                         # (the host array of the lengths: read during the call only)
         return out
 
@@ -827,12 +844,7 @@ class ConvNet:
         lens, hold, _ = _lens_struct(lengths, B, T, gloss=" (latent tokens per row)")
         if lens is None:
             return self.run(z)
-        out = torch.empty(B, self.out_ch, T * self.out_tmul, dtype=torch.float32, device=self.ctx.device)
-        ws = self._cached("lens", (B, T), lambda: self._bytes(self.ctx.lib.vb_vae_decode_lens_workspace_bytes(self.ctx.handle, B, T)))
-        L.check(self.ctx.lib.vb_vae_decode_lens(self.ctx.handle, L.ptr(z), B, T, C.byref(lens), L.ptr(out), L.ptr(ws), L.stream_ptr()),
-                "vb_vae_decode_lens")
-        del hold                         # (the host array of the lengths: read during the call only)
-        return out
+        return self._lens_call("vb_vae_decode_lens", z, B, T, lens, hold)
 
     def run_chunked(self, x: Tensor, chunk: int, halo: int, lengths=None) -> Tensor:
         """vocoder only: mel [B,80,T] -> wav [B,1,T*hop] in chunks of `chunk` frames with `halo` frames of context on both sides, the loop,
@@ -852,19 +864,12 @@ class ConvNet:
                 raise ValueError(f"run_chunked: chunk = {chunk}, halo = {halo} (chunk >= 1, halo >= 0)")
             lens, hold, _ = _lens_struct(lengths, B, T, gloss=" (input frames per row)")
         if T <= chunk + 2 * halo:
-            return self.run(x) if lens is None else self._run_lens(x, B, T, lens, hold)
-        tc = chunk + 2 * halo
-        dev = self.ctx.device
-        out = torch.empty(B, self.out_ch, T * self.out_tmul, dtype=torch.float32, device=dev)
-        cin, cout = self._cached("chunk", (B, tc), lambda: (torch.empty(B * self.in_ch * tc, dtype=torch.float32, device=dev),
-                                                            torch.empty(B * self.out_ch * tc * self.out_tmul, dtype=torch.float32, device=dev)))
+            return self.run(x) if lens is None else self._lens_call("vb_hifigan_forward_lens", x, B, T, lens, hold)
         if lens is not None:
-            lib = self.ctx.lib
-            ws = self._cached("chunk_lens", (B, tc), lambda: self._bytes(lib.vb_hifigan_chunked_lens_workspace_bytes(self.ctx.handle, B, T, chunk, halo)))
-            L.check(lib.vb_hifigan_forward_chunked_lens(self.ctx.handle, L.ptr(x), B, T, chunk, halo, C.byref(lens), L.ptr(out), L.ptr(ws), L.ptr(cin),
-                                                        L.ptr(cout), L.stream_ptr()), "vb_hifigan_forward_chunked_lens")
-            del hold                     # (the host array of the lengths: read during the call only)
-            return out
+            return self._lens_call("vb_hifigan_forward_chunked_lens", x, B, T, lens, hold, (chunk, halo))
+        tc = chunk + 2 * halo
+        out = torch.empty(B, self.out_ch, T * self.out_tmul, dtype=torch.float32, device=self.ctx.device)
+        cin, cout = self._chunk_scratch(B, tc)
         ws = self._workspace(B, tc)
         L.check(self.ctx.lib.vb_hifigan_forward_chunked(self.ctx.handle, L.ptr(x), B, T, chunk, halo, L.ptr(out), L.ptr(ws), L.ptr(cin), L.ptr(cout),
                                                         L.stream_ptr()), "vb_hifigan_forward_chunked")
@@ -890,22 +895,9 @@ class ConvNet:
         lens, hold, _ = _lens_struct(lengths, B, T, gloss=" (input frames per row)")
         if lens is None:
             return self.run(x) if chunk is None else self.run_chunked(x, chunk, halo)
-        lib, dev = self.ctx.lib, self.ctx.device
-        out = torch.empty(B, self.out_ch, T * self.out_tmul, dtype=torch.float32, device=dev)
         if chunk is None or T <= chunk + 2 * halo:
-            ws = self._cached("vocode_lens", (B, T), lambda: self._bytes(lib.vb_bigvgan_lens_workspace_bytes(self.ctx.handle, B, T)))
-            L.check(lib.vb_bigvgan_forward_lens(self.ctx.handle, L.ptr(x), B, T, C.byref(lens), L.ptr(out), L.ptr(ws), L.stream_ptr()),
-                    "vb_bigvgan_forward_lens")
-        else:
-            tc = chunk + 2 * halo
-            cin, cout = self._cached("chunk", (B, tc), lambda: (torch.empty(B * self.in_ch * tc, dtype=torch.float32, device=dev),
-                                                                torch.empty(B * self.out_ch * tc * self.out_tmul, dtype=torch.float32, device=dev)))
-            ws = self._cached("vocode_lens", (B, T, chunk, halo),
-                              lambda: self._bytes(lib.vb_bigvgan_chunked_lens_workspace_bytes(self.ctx.handle, B, T, chunk, halo)))
-            L.check(lib.vb_bigvgan_forward_chunked_lens(self.ctx.handle, L.ptr(x), B, T, chunk, halo, C.byref(lens), L.ptr(out), L.ptr(ws), L.ptr(cin),
-                                                        L.ptr(cout), L.stream_ptr()), "vb_bigvgan_forward_chunked_lens")
-        del hold                         # (the host array of the lengths: read during the call only)
-        return out
+            return self._lens_call("vb_bigvgan_forward_lens", x, B, T, lens, hold)
+        return self._lens_call("vb_bigvgan_forward_chunked_lens", x, B, T, lens, hold, (chunk, halo))
 
 
 def _vae_block_builders(nb: "NetBuilder", g: Dict[str, Tensor]):

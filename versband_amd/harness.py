@@ -221,6 +221,23 @@ def plan_row_batches(lengths, scales, n_samples: int, items_per_batch: int, indi
     return calls
 
 
+def _plan_route_calls(caller: str, row_lengths, mod: int) -> List[dict]:
+    """plan_vocoder_calls / plan_decode_calls: one call per residue of the lengths mod `mod`, in the order in which the residues appear"""
+    lens = [int(v) for v in row_lengths]
+    for r, v in enumerate(lens):
+        if v < 1:
+            raise ValueError(f"{caller}: row {r} has length {v} (at least 1)")
+    groups: Dict[int, List[int]] = {}
+    for r, v in enumerate(lens):
+        groups.setdefault(v % mod, []).append(r)
+    calls = []
+    for rows in groups.values():
+        member = [lens[r] for r in rows]
+        longest = max(member)
+        calls.append({"rows": rows, "length": longest, "lengths": member if any(v != longest for v in member) else None})
+    return calls
+
+
 def plan_vocoder_calls(row_lengths_mel) -> List[dict]:
     """The vocoder calls for rows of the given mel lengths (frames), as a list of
         {"rows": [row indices, ascending], "length": the padded length = the longest member, "lengths": [mel length per member] | None}
@@ -228,19 +245,7 @@ def plan_vocoder_calls(row_lengths_mel) -> List[dict]:
     a length only through that residue, so inside such a group every row equals the call on that clip alone bit for bit
     (include/versband_hip.h, vb_hifigan_forward_lens).  At most 4 calls, in the order in which their residues first appear; latent
     lengths make even mel lengths, hence at most 2.  "lengths" is None where the members are all equally long: the plain call."""
-    lens = [int(v) for v in row_lengths_mel]
-    for r, v in enumerate(lens):
-        if v < 1:
-            raise ValueError(f"plan_vocoder_calls: row {r} has length {v} (at least 1)")
-    groups: Dict[int, List[int]] = {}
-    for r, v in enumerate(lens):
-        groups.setdefault(v % 4, []).append(r)
-    calls = []
-    for rows in groups.values():
-        member = [lens[r] for r in rows]
-        longest = max(member)
-        calls.append({"rows": rows, "length": longest, "lengths": member if any(v != longest for v in member) else None})
-    return calls
+    return _plan_route_calls("plan_vocoder_calls", row_lengths_mel, 4)
 
 
 def plan_chunk_calls(lengths, T: int, chunk: int, halo: int) -> List[dict]:
@@ -283,19 +288,7 @@ def plan_decode_calls(row_lengths) -> List[dict]:
     what the attention block's two products take from the length (Ci % 16, Co % 4, the rounding of the split planes to 32) chooses
     between bit-identical kernels and adds exact zeros.  Inside such a group every row equals the decode of that clip alone bit for bit.  The calls come in the order in which their residues first appear; "lengths" is None where the members are all
     equally long: the plain call."""
-    lens = [int(v) for v in row_lengths]
-    for r, v in enumerate(lens):
-        if v < 1:
-            raise ValueError(f"plan_decode_calls: row {r} has length {v} (at least 1)")
-    groups: Dict[int, List[int]] = {}
-    for r, v in enumerate(lens):
-        groups.setdefault(v % DECODE_ROUTE_MOD, []).append(r)
-    calls = []
-    for rows in groups.values():
-        member = [lens[r] for r in rows]
-        longest = max(member)
-        calls.append({"rows": rows, "length": longest, "lengths": member if any(v != longest for v in member) else None})
-    return calls
+    return _plan_route_calls("plan_decode_calls", row_lengths, DECODE_ROUTE_MOD)
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -101,6 +101,18 @@ def plan_continue(plan: Sequence[Tuple[int, int]]) -> List[Tuple[int, int, int]]
     return out
 
 
+def _checked_lengths(caller: str, lengths, B: int, T: int, rows: str) -> List[int]:
+    """the `lengths` argument of sample_long / vocode_chunked / render_long as a list of B integers in [1, T] (rows: what the caller's
+    message calls the B entries)"""
+    lengths = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+    if len(lengths) != B:
+        raise ValueError(f"{caller}: lengths has {len(lengths)} entries for {B} {rows}")
+    for b, n in enumerate(lengths):
+        if not 1 <= n <= T:
+            raise ValueError(f"{caller}: lengths[{b}] = {n} is not in [1, T = {T}]")
+    return lengths
+
+
 def sample_long(engine, x0: Tensor, t5_cond: Tensor, t5_uncond: Tensor, midi: Tensor, beats: Tensor, t_idx_table, dt_table,
                 scale: float, window: int = 1500, overlap: int = 128, seed: int = 0, clip_base: int = 0, mode: str = "crossfade",
                 t_next=None, sigma_min: float = 1e-4, return_windows: bool = False, guidance=None, lengths=None):
@@ -128,14 +140,9 @@ def sample_long(engine, x0: Tensor, t5_cond: Tensor, t5_uncond: Tensor, midi: Te
     B, C, T = x0.shape
     window = min(window, engine.cfg.max_len)
     if lengths is not None:
-        lengths = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
         if mode != "joint":
             raise ValueError(f"sample_long: lengths belong to mode=\"joint\" (mode {mode!r} takes clips of one length)")
-        if len(lengths) != B:
-            raise ValueError(f"sample_long: lengths has {len(lengths)} entries for {B} clips")
-        for b, T_b in enumerate(lengths):
-            if not 1 <= T_b <= T:
-                raise ValueError(f"sample_long: lengths[{b}] = {T_b} is not in [1, T = {T}]")
+        lengths = _checked_lengths("sample_long", lengths, B, T, "clips")
         if any(T_b != T for T_b in lengths):
             return _sample_joint_lengths(engine, x0, t5_cond, t5_uncond, midi, beats, t_idx_table, dt_table, scale, window, overlap, seed,
                                          clip_base, return_windows, guidance, lengths)
@@ -262,12 +269,7 @@ def vocode_chunked(vocoder_net, mel: Tensor, chunk: int = 2048, halo: int = 32, 
     B, _, T = mel.shape
     hop = vocoder_net.out_tmul
     if lengths is not None:
-        lengths = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
-        if len(lengths) != B:
-            raise ValueError(f"vocode_chunked: lengths has {len(lengths)} entries for {B} rows")
-        for b, n in enumerate(lengths):
-            if not 1 <= n <= T:
-                raise ValueError(f"vocode_chunked: lengths[{b}] = {n} is not in [1, T = {T}]")
+        lengths = _checked_lengths("vocode_chunked", lengths, B, T, "rows")
         if all(n == T for n in lengths):
             lengths = None
     if lengths is not None:
@@ -316,12 +318,7 @@ def render_long(vae_net, vocoder_net, z: Tensor, lengths=None, chunk: int = 3000
     if lengths is None:
         return vocode_chunked(vocoder_net, vae_net.run(z), chunk, halo)
     B, _, T = z.shape
-    lengths = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
-    if len(lengths) != B:
-        raise ValueError(f"render_long: lengths has {len(lengths)} entries for {B} clips")
-    for b, n in enumerate(lengths):
-        if not 1 <= n <= T:
-            raise ValueError(f"render_long: lengths[{b}] = {n} is not in [1, T = {T}]")
+    lengths = _checked_lengths("render_long", lengths, B, T, "clips")
     up, hop = vae_net.out_tmul, vocoder_net.out_tmul
     mels = [None] * B
     for c in harness.plan_decode_calls(lengths):
