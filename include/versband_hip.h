@@ -289,8 +289,8 @@ int vb_sample_cfg_sched(vb_ctx* ctx, float* x, const void* cond, int B, int n_br
  * keep, rows and guidance compose unchanged (all are token-local); single-branch steps read the same table.  The lengths reach the
  * device through a launch argument at the head of the step loop, which a captured graph holds: the graph key holds the VALUES of len,
  * so another set of lengths on the same buffers captures its own graph and a plain call never replays a lengths graph.  Hosts detect
- * the feature by the presence of these symbols (vb_abi_version() stays 3).  The VAE encoder, BigVGAN and the chunked vocoder take equal-length rows only; the HiFi-GAN
- * takes row lengths through vb_hifigan_forward_lens and the VAE decoder through vb_vae_decode_lens (below). */
+ * the feature by the presence of these symbols (vb_abi_version() stays 3).  Every conv net takes row lengths through an entry point of its own
+ * (below): vb_hifigan_forward_lens, vb_vae_decode_lens, vb_vae_encode_lens, vb_bigvgan_forward_lens and the chunked forms. */
 typedef struct { const int32_t* len; } vb_lens;                   /* len: HOST array of B row lengths, 1 <= len[b] <= T */
 int vb_dit_precompute_cond_lens(vb_ctx* ctx, const float* t5, const int64_t* midi, const int64_t* beats, int B, int n_branch, int T,
                                 int T_mel, int L, const vb_lens* lens, void* cond, void* ws, void* stream);
@@ -444,8 +444,8 @@ int vb_hifigan_forward(vb_ctx* ctx, const float* mel, int B, int T, float* wav, 
  * A host that wants bit-exact rows groups its clips by length mod 4 (harness.plan_vocoder_calls).
  * Refused with VB_E_INVALID before anything is launched, naming the op and why: a vocoder program with an op other than VB_OP_CONV /
  * VB_OP_RESPAIR / VB_OP_XT_PLANES (BigVGAN's VB_OP_AA_ACT: its anti-aliasing filters replicate-pad at the row end), an input activation
- * other than none / LeakyReLU, GroupNorm statistics, dynamic channel counts, w_buf weights, a transposed output.  The VAE encoder takes
- * no lengths; the VAE decoder, the chunked vocoder and BigVGAN have their own entry points (vb_vae_decode_lens,
+ * other than none / LeakyReLU, GroupNorm statistics, dynamic channel counts, w_buf weights, a transposed output.  The VAE decoder,
+ * the VAE encoder, the chunked vocoder and BigVGAN have their own entry points (vb_vae_decode_lens, vb_vae_encode_lens,
  * vb_hifigan_forward_chunked_lens, vb_bigvgan_forward_lens / vb_bigvgan_forward_chunked_lens).
  * ws: vb_hifigan_lens_workspace_bytes(ctx, B, T) bytes = vb_net_workspace_bytes + the masked mel + the length table.  Hosts detect the
  * feature by the presence of these symbols (vb_abi_version() stays 3). */
@@ -480,12 +480,58 @@ int vb_hifigan_forward_lens(vb_ctx* ctx, const float* mel, int B, int T, const v
  *                         the other, or a glue kernel its float4 path).
  * No op had to be excepted.  A host that wants bit-exact rows groups its clips by length mod 4 (harness.plan_decode_calls).
  * Refused with VB_E_INVALID before anything is launched, naming the op and why: VB_OP_AA_ACT, VB_OP_RESPAIR, in_stride > 1, tr_stride > 1
- * (ops the decoder's program does not contain).  The VAE encoder (Downsample1D pads on the right of the row's own end) is the one net
- * that takes equal-length rows only; BigVGAN takes lengths through vb_bigvgan_forward_lens.
+ * (ops the decoder's program does not contain).  The VAE encoder (Downsample1D pads on the right of the row's own end) takes lengths
+ * through vb_vae_encode_lens (below), BigVGAN through vb_bigvgan_forward_lens.
  * ws: vb_vae_decode_lens_workspace_bytes(ctx, B, T) bytes = vb_net_workspace_bytes + the masked latent + the length table.  Hosts detect
  * the feature by the presence of these symbols (vb_abi_version() stays 3, vb_net_op is unchanged). */
 size_t vb_vae_decode_lens_workspace_bytes(vb_ctx* ctx, int B, int T);
 int vb_vae_decode_lens(vb_ctx* ctx, const float* z, int B, int T, const vb_lens* lens, float* mel, void* ws, void* stream);
+/* VAE encoder with ROW LENGTHS (build-defined): mels of different lengths as rows of one encode call.  ONE UNIT, LATENT TOKENS, serves
+ * encode, sample and decode: T is the padded LATENT length and lens->len the HOST array of B latent lengths, 1 <= len[b] <= T, B <= 64,
+ * checked like the sampler's (VB_E_INVALID names the row, nothing is launched and moments is unchanged).  mel [B][in_ch][T*in_tmul]
+ * (in_tmul = 2^downsamplings, 2 in the shipped config): row b owns mel frames [0, len[b]*in_tmul); a mel whose length is no multiple of
+ * in_tmul has no latent length and is not described by this call.  moments [B][2*embed][T]: row b holds len[b] columns that are
+ * vb_vae_encode on that clip alone, followed by exact zeros.  The caller's mel padding is never read into a valid value (it may hold NaN),
+ * and neither is anything already in the workspace (0xFF bytes give the bits of a zeroed one).  Row b does not depend on the other rows'
+ * contents or lengths.  lens == NULL, len == NULL or every row full is vb_vae_encode on the same buffers: same launches, same bits.
+ * How it works.  The decoder's scheme (above) on the encoder's program: the mel is copied into the workspace with its tails zeroed from
+ * len[b]*in_tmul on, every op that writes an activation buffer is followed by the tail-zero launch at that buffer's own rate, and GroupNorm
+ * statistics, GroupNorm (+ swish) inputs - the k = 5 convolutions, gn_apply, xt_planes - and the mid attention read the device table of
+ * lengths exactly as there.  What the decoder does not contain is Downsample1D: one zero on the right of the clip, then a k = 3 stride-2
+ * convolution, which the program runs as two polyphase VB_OP_CONVs with in_stride = 2 (phase 0: taps 0 and 2 with the bias; phase 1: tap
+ * 1 with beta = 1), both without input activation.  They get NO length table (launch_conv1d goes on refusing row lengths with in_stride):
+ * the last output of row b reaches for x[2*len'] (len' = the row's length at the output's rate), the first sample of the tail the previous
+ * op's tail pass zeroed - the reference's right pad on the clip alone - and for a full row it is the kernel's own zero padding behind
+ * T_eff = T_in / 2, as in the plain call.  The tail pass after the first of the two clears the bias it wrote behind the row's end, the
+ * second adds w1 * 0 to that zero.
+ * THE ROUTE RULE.  The stages run at tmul = in_tmul .. 1, so the predicates see (T*tmul) % 4.  Everything that looks at a length on the
+ * encoder's routes: T_eff of the strided convolutions (T_in / in_stride of the PADDED row for both phases, a function of T alone - the row's
+ * own end is the zero tail, not a bound); staged (16-byte) epilogues (T_out % 4, row alignment); quad window rows and F(2,3) eligibility of
+ * the stride-1 k = 3 / 5 convolutions without GroupNorm input (T % 4; the strided pair never qualifies for either: in_stride == 1 is a
+ * condition of the DMA-fed and the minimal-filtering kernels); the float4 paths of gn_stats (cpg * len * tmul % 4) and gn_apply (T % 4), which
+ * regroup loads, and in gn_stats the partial sums; the attention's channel counts (Ci % 16 / Co % 4 between two bit-identical fp32 kernels,
+ * Ci_pad rounding with zero columns, Ci % 64 of a route per-clip weights never take).  Tiles never change a bit.  (T*tmul) % 4 for every
+ * tmul in {in_tmul .. 1} is a function of T % 4, so the decoder's rule holds with the same modulus:
+ *   len[b] == T (mod 4)   row b's len[b] columns equal vb_vae_encode on that clip alone BIT FOR BIT, in every precision;
+ *   otherwise             the two agree to the precision's roundoff.
+ * A host that wants bit-exact rows groups its clips by latent length mod 4 (harness.plan_encode_calls).
+ * Refused with VB_E_INVALID before anything is launched, naming the op and why: upsample2, tr_stride > 1, VB_OP_AA_ACT and VB_OP_RESPAIR
+ * (not ops of the encoder's program), and in_stride > 1 on anything but a VB_OP_CONV with in_act none and stats = -1 (an activated
+ * down-convolution would pad the activated row).  vb_vae_decode_lens goes on refusing in_stride > 1.
+ * ws: vb_vae_encode_lens_workspace_bytes(ctx, B, T) bytes = vb_net_workspace_bytes + the masked mel + the length table.  Hosts detect
+ * the feature by the presence of these symbols (vb_abi_version() stays 3, vb_net_op is unchanged). */
+size_t vb_vae_encode_lens_workspace_bytes(vb_ctx* ctx, int B, int T);
+int vb_vae_encode_lens(vb_ctx* ctx, const float* mel, int B, int T, const vb_lens* lens, float* moments, void* ws, void* stream);
+/* The posterior of those moments with row lengths (build-defined; DiagonalGaussianDistribution.sample / .mode and the scale of
+ * get_first_stage_encoding in one launch).  moments [B][2E][T] (mean = channels [0, E), logvar = [E, 2E)), noise [B][E][T] or NULL, in fp32:
+ *   z[b][c][t] = scale * (mean + expf(0.5f * clamp(logvar, -30, 20)) * noise)   for t <  len[b]       (noise == NULL: scale * mean)
+ *   z[b][c][t] = 0                                                              for t >= len[b]
+ * len: HOST array of B lengths (1 <= len[b] <= T, B <= 64, checked as above; they travel by value in the launch, nothing is allocated);
+ * NULL = full rows.  Neither the noise nor the moments are read behind a row's end (both may hold NaN there): the zero tail of the moments is
+ * logvar = 0, std = 1, so the elementwise form would leave the noise in z's padding, which the sampler's contract forbids.  16-byte
+ * accesses when T % 4 == 0 and the three bases are 16-byte aligned, 4-byte otherwise; same values either way. */
+int vb_posterior_lens(const float* moments, const float* noise /* NULL = mode */, int B, int E, int T,
+                      const int32_t* len /* HOST, NULL = full rows */, float scale, float* z, void* stream);
 
 /* Long-form generation (BASELINE configs[4]; build-defined, the reference stops at max_len = 1500 latent tokens: vocal2music_moe.py:421).
  * vb_crossfade_windows: window results parts [nw*B][C][n] (row = w*B + b; windows of equal length n starting at starts[w], a HOST array,

@@ -155,6 +155,9 @@ PROTOTYPES = {
     "vb_hifigan_forward_lens": (c_int, [P, P, c_int, c_int, C.POINTER(Lens), P, P, P]),
     "vb_vae_decode_lens_workspace_bytes": (c_size_t, [P, c_int, c_int]),
     "vb_vae_decode_lens": (c_int, [P, P, c_int, c_int, C.POINTER(Lens), P, P, P]),
+    "vb_vae_encode_lens_workspace_bytes": (c_size_t, [P, c_int, c_int]),
+    "vb_vae_encode_lens": (c_int, [P, P, c_int, c_int, C.POINTER(Lens), P, P, P]),
+    "vb_posterior_lens": (c_int, [P, P, c_int, c_int, c_int, C.POINTER(C.c_int32), c_float, P, P]),
     "vb_gn_stats_lens": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, P]),
     "vb_softmax_rows_t_lens": (c_int, [P, c_int, c_int, P, P, P]),
     "vb_crossfade_windows": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P]),

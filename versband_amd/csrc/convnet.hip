@@ -16,7 +16,7 @@ static size_t net_ws_bytes(const NetProgram& n, int B, int T, std::vector<size_t
     }
     return off;
 }
-// nl (vb_hifigan_forward_lens / vb_vae_decode_lens, after net_lens_check): `in` is the masked copy of the input, every op that writes an
+// nl (vb_hifigan_forward_lens / vb_vae_decode_lens / vb_vae_encode_lens, after net_lens_check): `in` is the masked copy of the input, every op that writes an
 // activation buffer is followed by launch_tail_zero on it, and the fused pairs end row b's intermediate at its own length.  The VAE decoder's
 // ops that a zero tail does not settle read the device table: GroupNorm statistics run over the row's own samples, every GroupNorm (+ swish)
 // consumer ends the ACTIVATED tensor at the row's own length, the attention softmax runs over the row's own keys.  Null: the plain run,
@@ -163,8 +163,12 @@ int net_run(vb_ctx* ctx, int which, const float* in, int B, int T, float* out, v
 // [B][C][T] buffer.  The VAE decoder (vb_vae_decode_lens) adds what net_run gives a length table to - GroupNorm statistics and inputs, the
 // attention's dynamic channel counts, w_buf weights, transposed outputs - and refuses whatever its program does not contain.  BigVGAN
 // (vb_bigvgan_forward_lens) is the vocoder's contract plus VB_OP_AA_ACT, whose kernel takes the row's own end from the length table; the
-// HiFi-GAN entry points keep refusing that op, so what they accept is what they accepted before the kernel learned it.
-enum { LENS_VAE_DECODER = 0, LENS_VOCODER = 1, LENS_BIGVGAN = 2 };
+// HiFi-GAN entry points keep refusing that op, so what they accept is what they accepted before the kernel learned it.  The VAE encoder
+// (vb_vae_encode_lens) is the decoder's contract, turned round at the one op that changes the row's rate: it refuses upsample2 and admits
+// in_stride > 1 on a convolution with no input activation and no statistics - Downsample1D as two polyphase sums, which net_run gives no
+// length table (conv1d's refusal of row_len with in_stride stays): the right pad of the reference is the zeroed tail of the buffer they
+// read, and the tail pass after each of the two keeps the output's own tail zero (the second adds w1 * 0, no bias, to a zeroed tail).
+enum { LENS_VAE_DECODER = 0, LENS_VOCODER = 1, LENS_BIGVGAN = 2, LENS_VAE_ENCODER = 3 };
 static int net_lens_check(const NetProgram& n, int contract) {
     const char* const fn = contract == LENS_BIGVGAN ? "bigvgan_forward_lens" : "hifigan_forward_lens";
     static const char* const kinds[] = {"VB_OP_CONV", "VB_OP_GN_STATS", "VB_OP_SOFTMAX_T", "VB_OP_SPLIT_PLANES", "VB_OP_RESPAIR", "VB_OP_GN_APPLY",
@@ -181,6 +185,20 @@ static int net_lens_check(const NetProgram& n, int contract) {
                 VB_FAIL(VB_E_INVALID, "vae_decode_lens: op %zu (%s): in_stride = %d reads across the row's own end (the encoder's down-convolutions)", oi, kn, o.in_stride);
             if (o.kind == VB_OP_CONV && o.tr_stride > 1)
                 VB_FAIL(VB_E_INVALID, "vae_decode_lens: op %zu (%s): a transposed convolution (tr_stride = %d) is not an op of the VAE decoder's program", oi, kn, o.tr_stride);
+            continue;
+        }
+        if (contract == LENS_VAE_ENCODER) {
+            if (o.kind == VB_OP_AA_ACT || o.kind == VB_OP_RESPAIR || o.kind < 0 || o.kind > VB_OP_XT_PLANES)
+                VB_FAIL(VB_E_INVALID, "vae_encode_lens: op %zu (%s): not an op of the VAE encoder's program", oi, kn);
+            if ((o.kind == VB_OP_CONV || o.kind == VB_OP_XT_PLANES) && o.upsample2)
+                VB_FAIL(VB_E_INVALID, "vae_encode_lens: op %zu (%s): upsample2 is not an op of the VAE encoder's program", oi, kn);
+            if (o.kind == VB_OP_CONV && o.tr_stride > 1)
+                VB_FAIL(VB_E_INVALID, "vae_encode_lens: op %zu (%s): a transposed convolution (tr_stride = %d) is not an op of the VAE encoder's program", oi, kn, o.tr_stride);
+            if (o.in_stride > 1 && o.kind != VB_OP_CONV)
+                VB_FAIL(VB_E_INVALID, "vae_encode_lens: op %zu (%s): in_stride = %d on an op that is not a convolution", oi, kn, o.in_stride);
+            if (o.kind == VB_OP_CONV && o.in_stride > 1 && (o.in_act != ACT_NONE || o.stats != -1))
+                VB_FAIL(VB_E_INVALID, "vae_encode_lens: op %zu (%s): in_stride = %d with input activation %d / statistics %d: an activated down-convolution "
+                        "pads the ACTIVATED row, which a zero tail does not stand in for (none and -1 only)", oi, kn, o.in_stride, o.in_act, o.stats);
             continue;
         }
         if (o.kind == VB_OP_AA_ACT && contract == LENS_BIGVGAN) {
@@ -213,7 +231,8 @@ struct LensEntry { int which, contract; const char* name; const char* net; const
 static const LensEntry LENS_ENTRIES[] = {
     {VB_NET_VAE, LENS_VAE_DECODER, "vb_vae_decode_lens", "VAE decoder", nullptr},
     {VB_NET_VOCODER, LENS_VOCODER, "vb_hifigan_forward_lens", "vocoder", "vb_hifigan_forward_chunked_lens"},
-    {VB_NET_VOCODER, LENS_BIGVGAN, "vb_bigvgan_forward_lens", "vocoder", "vb_bigvgan_forward_chunked_lens"}};
+    {VB_NET_VOCODER, LENS_BIGVGAN, "vb_bigvgan_forward_lens", "vocoder", "vb_bigvgan_forward_chunked_lens"},
+    {VB_NET_VAE_ENCODER, LENS_VAE_ENCODER, "vb_vae_encode_lens", "VAE encoder", nullptr}};
 static const char* fn_of(const char* name) { return name + 3; }
 
 // The one lengths path of the nets, behind every row of LENS_ENTRIES.  Workspace: the net's own, the masked input, the table of row lengths.
@@ -232,14 +251,15 @@ static int net_run_lens(vb_ctx* ctx, const LensEntry& e, const float* in, int B,
     NetProgram& n = ctx->nets[e.which];
     if (!n.loaded) VB_FAIL(VB_E_STATE, "%s: no %s loaded", fn, e.net);
     VB_TRY(net_lens_check(n, e.contract));
-    if (n.in_tmul != 1) VB_FAIL(VB_E_INVALID, "%s: the %s's input runs at %d samples per frame (1)", fn, e.net, n.in_tmul);
+    // (the encoder alone takes its input at in_tmul samples per unit of len: T and len count latent tokens, row b owns len[b] * in_tmul frames)
+    if (n.in_tmul != 1 && e.contract != LENS_VAE_ENCODER) VB_FAIL(VB_E_INVALID, "%s: the %s's input runs at %d samples per frame (1)", fn, e.net, n.in_tmul);
     VB_HIP(hipSetDevice(ctx->device));
     char* p = static_cast<char*>(ws) + net_ws_bytes(n, B, T, nullptr);
     float* masked = reinterpret_cast<float*>(p);
     int* table = reinterpret_cast<int*>(p + align_up((size_t)B * n.in_ch * T * n.in_tmul * sizeof(float)));
     VB_TRY(launch_lens_table(nl.lp, table, st));
     nl.table = table;
-    VB_TRY(launch_mask_latent(in, B, n.in_ch, T, table, masked, st));                  // (a select: the caller's padding, NaN included, is not read)
+    VB_TRY(launch_mask_latent(in, B, n.in_ch, T * n.in_tmul, table, masked, st, n.in_tmul));      // (a select: the caller's padding, NaN included, is not read)
     return net_run(ctx, e.which, masked, B, T, out, ws, st, &nl);
 }
 
@@ -433,6 +453,16 @@ int vb_hifigan_forward_lens(vb_ctx* ctx, const float* mel, int B, int T, const v
 size_t vb_vae_decode_lens_workspace_bytes(vb_ctx* ctx, int B, int T) { return net_lens_ws_bytes(ctx, LENS_ENTRIES[LENS_VAE_DECODER].which, B, T); }
 int vb_vae_decode_lens(vb_ctx* ctx, const float* z, int B, int T, const vb_lens* lens, float* mel, void* ws, void* stream) {
     return net_run_lens(ctx, LENS_ENTRIES[LENS_VAE_DECODER], z, B, T, lens, mel, ws, (hipStream_t)stream);
+}
+size_t vb_vae_encode_lens_workspace_bytes(vb_ctx* ctx, int B, int T) { return net_lens_ws_bytes(ctx, LENS_ENTRIES[LENS_VAE_ENCODER].which, B, T); }
+int vb_vae_encode_lens(vb_ctx* ctx, const float* mel, int B, int T, const vb_lens* lens, float* moments, void* ws, void* stream) {
+    return net_run_lens(ctx, LENS_ENTRIES[LENS_VAE_ENCODER], mel, B, T, lens, moments, ws, (hipStream_t)stream);
+}
+int vb_posterior_lens(const float* moments, const float* noise, int B, int E, int T, const int32_t* len, float scale, float* z, void* stream) {
+    if (!moments || !z || B < 1 || E < 1 || T < 1) VB_FAIL(VB_E_INVALID, "posterior_lens: null pointer or B/E/T < 1");
+    LensPlan lp;
+    if (len) VB_TRY(lens_plan(len, B, T, &lp));      // (B <= 64, 1 <= len[b] <= T: the row is named; B = 0 in lp: every row full)
+    return launch_posterior_lens(moments, noise, B, E, T, lp, scale, z, (hipStream_t)stream);
 }
 int vb_crossfade_windows(const float* parts, const int32_t* starts, int nw, int B, int C, int n, int T, float* out, void* stream) {
     if (!parts || !starts || !out || nw < 1 || B < 1 || C < 1 || n < 1 || T < 1) VB_FAIL(VB_E_INVALID, "crossfade_windows: null pointer or nw/B/C/n/T < 1");

@@ -324,16 +324,18 @@ int launch_im2col_latent(const float* x, int B, int C, int T, int taps, int pad,
     VB_CHECK_LAUNCH();
     return VB_OK;
 }
-// the same mask for the proj_in routes that are a general convolution kernel: out[b][c][t] = t < len[b] ? x[b][c][t] : 0 (a select: x's
-// padding, NaN included, is not read into the copy)
-__global__ void mask_latent_kernel(const float* __restrict__ x, int B, int C, int T, const int* __restrict__ len, float* __restrict__ out) {
+// the same mask for the proj_in routes that are a general convolution kernel: out[b][c][t] = t < len[b] * len_mul ? x[b][c][t] : 0 (a select:
+// x's padding, NaN included, is not read into the copy).  len_mul: samples of x per unit of len (the VAE encoder's mel frames per latent token)
+__global__ void mask_latent_kernel(const float* __restrict__ x, int B, int C, int T, const int* __restrict__ len, int len_mul,
+                                   float* __restrict__ out) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (int64_t)B * C * T) return;
     const int t = (int)(idx % T), b = (int)(idx / ((int64_t)C * T));
-    out[idx] = t < len[b] ? x[idx] : 0.f;
+    out[idx] = t < len[b] * len_mul ? x[idx] : 0.f;
 }
-int launch_mask_latent(const float* x, int B, int C, int T, const int* len, float* out, hipStream_t st) {
-    hipLaunchKernelGGL(mask_latent_kernel, dim3(cdiv((int64_t)B * C * T, 256)), dim3(256), 0, st, x, B, C, T, len, out);
+int launch_mask_latent(const float* x, int B, int C, int T, const int* len, float* out, hipStream_t st, int len_mul) {
+    if (len_mul < 1) VB_FAIL(VB_E_INVALID, "mask_latent: len_mul = %d (>= 1)", len_mul);
+    hipLaunchKernelGGL(mask_latent_kernel, dim3(cdiv((int64_t)B * C * T, 256)), dim3(256), 0, st, x, B, C, T, len, len_mul, out);
     VB_CHECK_LAUNCH();
     return VB_OK;
 }

@@ -191,8 +191,9 @@ int launch_transpose_bct_btc(const float* in, int B, int C, int T_in, int T_out,
 // proj_in as a GEMM: latent windows as K-contiguous split planes, conv weights re-laid as a GEMM operand
 // (len: device [B] row lengths - the clip of row b ends at len[b], taps beyond it are zero; null: T)
 int launch_im2col_latent(const float* x, int B, int C, int T, int taps, int pad, int KP, bf16_t* out, int64_t plane, hipStream_t st, const int* len = nullptr);
-// row lengths of a call (vb_lens): out[b][c][t] = t < len[b] ? x[b][c][t] : 0, what a general convolution kernel reads in place of x
-int launch_mask_latent(const float* x, int B, int C, int T, const int* len, float* out, hipStream_t st);
+// row lengths of a call (vb_lens): out[b][c][t] = t < len[b] * len_mul ? x[b][c][t] : 0, what a general convolution kernel reads in place of x
+// (T: the pitch of x in samples; len_mul: samples per unit of len - the VAE encoder's input runs at in_tmul mel frames per latent token)
+int launch_mask_latent(const float* x, int B, int C, int T, const int* len, float* out, hipStream_t st, int len_mul = 1);
 // the validated lengths of a call, by value in the kernel's argument block like WindowPlan, and their way into the workspace table.
 // lens_plan checks len (HOST array) for B rows of T tokens: B <= 64, 1 <= len[b] <= T; VB_E_INVALID names the row otherwise.  B = 0 in
 // the plan: every row is full, the call is the plain one.
@@ -414,6 +415,10 @@ int launch_chunk_gather(const float* mel, const ChunkRows& cr, int C, int T, int
 struct ChunkScatter { int n_active = 0; int slot[64] = {}; int keep[64] = {}; };      // (slot[b] < n_active, keep[b] in frames)
 int launch_chunk_scatter(const float* src, const ChunkScatter& cs, int B, int C, int T, int hop, int s, int e, int lo, int tc, float* wav,
                          hipStream_t st);
+// The VAE posterior with row lengths (vb_posterior_lens): moments [B][2E][T] = (mean, logvar), noise [B][E][T] or null (the mode),
+// z[b][c][t] = t < len[b] ? scale * (mean + expf(0.5f * clamp(logvar, -30, 20)) * noise) : 0.  lp: the checked lengths by value (B = 0 in it:
+// full rows).  One launch; 16-byte accesses when T % 4 == 0 and the bases allow; neither noise nor moments are read behind a row's end.
+int launch_posterior_lens(const float* moments, const float* noise, int B, int E, int T, const LensPlan& lp, float scale, float* z, hipStream_t st);
 
 // ---------------------------------------------------------------------------
 // per-kernel-class HIP-event timing (bench.py roofline): 0 = bf16 GEMM (incl. the fused expert kernels), 1 = attention,

@@ -1,6 +1,6 @@
 // Glue kernels of the conv-net executor (gfx950), called by convnet.hip only (VAE, HiFi-GAN / BigVGAN, long-form windows): GroupNorm
 // statistics and apply, the pre-activated transposed planes of the DMA-fed convs, the anti-aliased periodic activation, the split
-// planes and the transposed softmax of the VAE attention, and the cross-fade of long-form windows.
+// planes and the transposed softmax of the VAE attention, the cross-fade of long-form windows, and the VAE posterior with row lengths.
 #include "kernels.h"
 
 // ---------------------------------------------------------------------------
@@ -394,6 +394,64 @@ int launch_crossfade_windows(const float* parts, const int* starts, int nw, int 
     if (xs.s[0] != 0 || xs.s[nw - 1] + n != T) VB_FAIL(VB_E_INVALID, "crossfade: the windows do not cover [0, %d)", T);
     const int64_t tot = (int64_t)B * C * T;
     hipLaunchKernelGGL(crossfade_windows_kernel, dim3(cdiv(tot, 256)), dim3(256), 0, st, parts, xs, nw, B, C, n, T, out);
+    VB_CHECK_LAUNCH();
+    return VB_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The VAE posterior with row lengths (vb_posterior_lens; DiagonalGaussianDistribution.sample / .mode followed by the scale of
+// get_first_stage_encoding, cfm1_audio.py): moments [B][2E][T], mean = channels [0, E), logvar = channels [E, 2E), in fp32
+//   z[b][c][t] = scale * (mean + expf(0.5f * clamp(logvar, -30, 20)) * noise)   t <  len[b]      (NOISE = false: scale * mean)
+//   z[b][c][t] = 0                                                              t >= len[b]
+// The zero tail of the moments is logvar = 0, std = 1: the elementwise path would leave the noise in z's padding, so the tail is a select
+// here and neither the noise nor the moments are loaded behind a row's end (they may hold NaN).  grid = (pieces of a row, E, B), the
+// lengths by value in the argument block (lp.B = 0: full rows).  VEC: one float4 per lane (T % 4 == 0 and 16-byte bases, the host checked);
+// the group a row ends in takes 4-byte loads of its own samples.  Contraction is off: product, sum and scale round one by one, as written.
+// ---------------------------------------------------------------------------
+template <bool NOISE>
+__device__ __forceinline__ float posterior_value(float mean, float logvar, float eps, float scale) {
+#pragma clang fp contract(off)
+    if constexpr (!NOISE) return scale * mean;
+    const float sd = expf(0.5f * fminf(fmaxf(logvar, -30.f), 20.f));
+    return scale * (mean + sd * eps);
+}
+template <bool VEC, bool NOISE>
+__global__ void __launch_bounds__(256) posterior_lens_kernel(const float* __restrict__ mom, const float* __restrict__ noise, const LensPlan lp, int E,
+                                                            int T, float scale, float* __restrict__ z) {
+    const int b = blockIdx.z, c = blockIdx.y;
+    const int t = (blockIdx.x * 256 + threadIdx.x) * (VEC ? 4 : 1);
+    if (t >= T) return;
+    const int L = lp.B ? lp.len[b] : T;
+    const float* mp = mom + ((int64_t)b * 2 * E + c) * T + t;
+    const float* vp = mp + (int64_t)E * T;
+    const float* np = NOISE ? noise + ((int64_t)b * E + c) * T + t : nullptr;
+    float* zp = z + ((int64_t)b * E + c) * T + t;
+    if constexpr (VEC) {
+        float o[4] = {0.f, 0.f, 0.f, 0.f};
+        if (t + 4 <= L) {
+            const float4 m = *reinterpret_cast<const float4*>(mp);
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f), n = v;
+            if constexpr (NOISE) { v = *reinterpret_cast<const float4*>(vp); n = *reinterpret_cast<const float4*>(np); }
+            o[0] = posterior_value<NOISE>(m.x, v.x, n.x, scale); o[1] = posterior_value<NOISE>(m.y, v.y, n.y, scale);
+            o[2] = posterior_value<NOISE>(m.z, v.z, n.z, scale); o[3] = posterior_value<NOISE>(m.w, v.w, n.w, scale);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                if (t + k < L) o[k] = posterior_value<NOISE>(mp[k], NOISE ? vp[k] : 0.f, NOISE ? np[k] : 0.f, scale);
+        }
+        *reinterpret_cast<float4*>(zp) = make_float4(o[0], o[1], o[2], o[3]);
+    } else {
+        *zp = t < L ? posterior_value<NOISE>(*mp, NOISE ? *vp : 0.f, NOISE ? *np : 0.f, scale) : 0.f;
+    }
+}
+int launch_posterior_lens(const float* moments, const float* noise, int B, int E, int T, const LensPlan& lp, float scale, float* z, hipStream_t st) {
+    if (B < 1 || B > 65535 || E < 1 || E > 65535 || T < 1 || (lp.B && lp.B != B))
+        VB_FAIL(VB_E_INVALID, "posterior_lens: B=%d E=%d T=%d with %d lengths (B, E in 1..65535, T >= 1, one length per row)", B, E, T, lp.B);
+    const bool vec = T % 4 == 0 && aligned16(moments) && aligned16(z) && (!noise || aligned16(noise));
+    const dim3 grid(cdiv(T, vec ? 1024 : 256), E, B);
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, moments, noise, lp, E, T, scale, z); };
+    if (vec) { if (noise) go(posterior_lens_kernel<true, true>); else go(posterior_lens_kernel<true, false>); }
+    else { if (noise) go(posterior_lens_kernel<false, true>); else go(posterior_lens_kernel<false, false>); }
     VB_CHECK_LAUNCH();
     return VB_OK;
 }

@@ -792,7 +792,7 @@ class ConvNet:
         T = Tin // self.in_tmul
         if lengths is not None:
             if self.which != L.NET_VOCODER:
-                hint = "; the VAE decoder takes them through decode_lens" if self.which == L.NET_VAE else ""
+                hint = "; the VAE decoder takes them through decode_lens" if self.which == L.NET_VAE else "; the VAE encoder takes them through encode_lens"
                 raise ValueError(f"lengths: the {self.NET_NAMES[self.which]} takes equal-length rows only through run (row lengths reach the "
                                  f"vocoder net alone{hint})")
             lens, hold, _ = _lens_struct(lengths, B, T, gloss=" (input frames per row)")
@@ -814,12 +814,13 @@ class ConvNet:
     # the lengths entry points and the function that sizes each one's workspace (with B, T and, chunked, chunk and halo)
     LENS_WORKSPACE = {"vb_hifigan_forward_lens": "vb_hifigan_lens_workspace_bytes",
                       "vb_vae_decode_lens": "vb_vae_decode_lens_workspace_bytes",
+                      "vb_vae_encode_lens": "vb_vae_encode_lens_workspace_bytes",
                       "vb_bigvgan_forward_lens": "vb_bigvgan_lens_workspace_bytes",
                       "vb_hifigan_forward_chunked_lens": "vb_hifigan_chunked_lens_workspace_bytes",
                       "vb_bigvgan_forward_chunked_lens": "vb_bigvgan_chunked_lens_workspace_bytes"}
 
     def _lens_call(self, name: str, x: Tensor, B: int, T: int, lens, hold, chunked: Tuple[int, ...] = ()) -> Tensor:
-        """the lengths entry point `name` on rows x [B, in_ch, T] (contiguous fp32 on the device); lens / hold: the vb_lens struct and
+        """the lengths entry point `name` on rows x [B, in_ch, T * in_tmul] (contiguous fp32 on the device); lens / hold: the vb_lens struct and
         its host array (_lens_struct); chunked: (chunk, halo) for the chunked entry points, which also take the chunk scratch"""
         lib, handle = self.ctx.lib, self.ctx.handle
         out = torch.empty(B, self.out_ch, T * self.out_tmul, dtype=torch.float32, device=self.ctx.device)
@@ -837,7 +838,7 @@ class ConvNet:
         neither the padding of z nor anything in the workspace is read.  None, or every row full, is run(z)."""
         if self.which != L.NET_VAE:
             raise ValueError(f"decode_lens: the {self.NET_NAMES[self.which]} has no decode_lens (the VAE decoder alone; the vocoder takes "
-                             f"row lengths through run(lengths=), the VAE encoder takes equal-length rows only)")
+                             f"row lengths through run(lengths=), the VAE encoder through encode_lens)")
         z = z.to(self.ctx.device, torch.float32).contiguous()
         B, Cin, T = z.shape
         assert Cin == self.in_ch, (Cin, self.in_ch)
@@ -845,6 +846,27 @@ class ConvNet:
         if lens is None:
             return self.run(z)
         return self._lens_call("vb_vae_decode_lens", z, B, T, lens, hold)
+
+    def encode_lens(self, mel: Tensor, lengths) -> Tensor:
+        """VAE encoder only (vb_vae_encode_lens): mel [B, in_ch, T * in_tmul] with one LATENT length per row - the unit of the sampler and
+        of decode_lens - so mels of different lengths padded to T * in_tmul frames share the call and row b owns its first
+        lengths[b] * in_tmul frames.  Row b's first lengths[b] columns of the moments [B, 2 * embed, T] are the encode of that clip alone
+        (bit for bit when lengths[b] and T agree mod 4, to the precision's roundoff otherwise: harness.plan_encode_calls groups rows
+        accordingly), the rest of the row is zero, and neither the padding of mel nor anything in the workspace is read.  None, or every
+        row full, is run(mel)."""
+        if self.which != L.NET_VAE_ENCODER:
+            raise ValueError(f"encode_lens: the {self.NET_NAMES[self.which]} has no encode_lens (the VAE encoder alone; the vocoder takes "
+                             f"row lengths through run(lengths=), the VAE decoder through decode_lens)")
+        mel = mel.to(self.ctx.device, torch.float32).contiguous()
+        B, Cin, Tin = mel.shape
+        assert Cin == self.in_ch, (Cin, self.in_ch)
+        if Tin % self.in_tmul:
+            raise ValueError(f"encode_lens: input length {Tin} is not a multiple of {self.in_tmul} (mel frames per latent token)")
+        T = Tin // self.in_tmul
+        lens, hold, _ = _lens_struct(lengths, B, T, gloss=" (latent tokens per row)")
+        if lens is None:
+            return self.run(mel)
+        return self._lens_call("vb_vae_encode_lens", mel, B, T, lens, hold)
 
     def run_chunked(self, x: Tensor, chunk: int, halo: int, lengths=None) -> Tensor:
         """vocoder only: mel [B,80,T] -> wav [B,1,T*hop] in chunks of `chunk` frames with `halo` frames of context on both sides, the loop,
@@ -886,7 +908,7 @@ class ConvNet:
         run_chunked()."""
         if self.which != L.NET_VOCODER:
             raise ValueError(f"vocode_lens: the {self.NET_NAMES[self.which]} has no vocode_lens (vocoder nets alone; the VAE decoder takes row "
-                             f"lengths through decode_lens, the VAE encoder takes equal-length rows only)")
+                             f"lengths through decode_lens, the VAE encoder through encode_lens)")
         x = x.to(self.ctx.device, torch.float32).contiguous()
         B, Cin, T = x.shape
         assert Cin == self.in_ch, (Cin, self.in_ch)

@@ -222,7 +222,7 @@ def plan_row_batches(lengths, scales, n_samples: int, items_per_batch: int, indi
 
 
 def _plan_route_calls(caller: str, row_lengths, mod: int) -> List[dict]:
-    """plan_vocoder_calls / plan_decode_calls: one call per residue of the lengths mod `mod`, in the order in which the residues appear"""
+    """plan_vocoder_calls / plan_decode_calls / plan_encode_calls: one call per residue of the lengths mod `mod`, in the order in which the residues appear"""
     lens = [int(v) for v in row_lengths]
     for r, v in enumerate(lens):
         if v < 1:
@@ -289,6 +289,21 @@ def plan_decode_calls(row_lengths) -> List[dict]:
     between bit-identical kernels and adds exact zeros.  Inside such a group every row equals the decode of that clip alone bit for bit.  The calls come in the order in which their residues first appear; "lengths" is None where the members are all
     equally long: the plain call."""
     return _plan_route_calls("plan_decode_calls", row_lengths, DECODE_ROUTE_MOD)
+
+
+ENCODE_ROUTE_MOD = 4        # the VAE encoder's stages run at tmul = in_tmul .. 1 and (length * tmul) % 4 is a function of length % 4 (include/versband_hip.h, vb_vae_encode_lens)
+
+
+def plan_encode_calls(row_lengths) -> List[dict]:
+    """The VAE encoder's twin of plan_decode_calls, for mels of the given LATENT lengths (tokens; a mel of n frames has n / in_tmul): a list of
+        {"rows": [row indices, ascending], "length": the padded length = the longest member, "lengths": [latent length per member] | None}
+    Rows whose lengths share a residue mod 4 form one call (encode_first_stage(..., lengths=)).  The predicates of the encoder's routes
+    that change bits are the decoder's - minimal filtering against the direct kernels, staged epilogues, the float4 paths of the glue
+    kernels - at (length * tmul) % 4; the strided down-convolutions bound their window by the padded row (T_in / 2, no length enters), and
+    the attention's channel counts choose between bit-identical kernels and add exact zeros.  Inside such a group every row equals the
+    encode of that clip alone bit for bit.  The calls come in the order in which their residues first appear; "lengths" is None where the
+    members are all equally long: the plain call."""
+    return _plan_route_calls("plan_encode_calls", row_lengths, ENCODE_ROUTE_MOD)
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -123,13 +123,18 @@ class AutoencoderKL:
     _device = None
     _precision = "fp32mf"        # VAE arithmetic: fp32 with minimal filtering (default), "fp32" = direct fp32 kernels, "split" = bf16x3, "bf16" = single-pass bf16, "bf16xt" = the same with the wide layers as one-plane DMA-fed GEMMs (set by CFM(vocoder_precision=...))
 
-    def encode(self, x):
-        """:49-53  mel [B,80,T_mel] -> DiagonalGaussianDistribution over z [B,embed_dim,T_mel/2] (HIP encoder net)."""
+    def encode(self, x, lengths=None):
+        """:49-53  mel [B,80,T_mel] -> DiagonalGaussianDistribution over z [B,embed_dim,T_mel/2] (HIP encoder net).
+        lengths (addition; ConvNet.encode_lens): one length in LATENT tokens per row - mels of different lengths padded to T_mel share the
+        call, row b owns its first 2 * lengths[b] frames and the moments of row b are those of the clip alone followed by zeros (mean 0,
+        logvar 0 behind the row's end: CFM.get_first_stage_encoding(..., lengths=) ends the sample there too)."""
         from .engine import Context, build_vae_encoder
         if self.enc_net is None:
             if not self.enc_state:
                 raise RuntimeError("AutoencoderKL.encode: no encoder.* / quant_conv.* weights loaded")
             self.enc_net = build_vae_encoder(Context(self._device or "cuda:0"), self.enc_state, precision=self._precision)
+        if lengths is not None:
+            return DiagonalGaussianDistribution(self.enc_net.encode_lens(x, lengths))
         return DiagonalGaussianDistribution(self.enc_net.run(x))
 
 
@@ -369,13 +374,24 @@ class CFM:
         return v, torch.zeros((), device=v.device)
 
     @torch.no_grad()
-    def encode_first_stage(self, x):
-        """ddpm_audio.py:411-412."""
+    def encode_first_stage(self, x, lengths=None):
+        """ddpm_audio.py:411-412.
+        lengths (addition; ConvNet.encode_lens): one length in latent tokens per row, the unit of sample_cfg(lengths=) and
+        decode_first_stage(lengths=) - mels of different lengths padded to x.shape[-1] share the call."""
         self.first_stage_model._device = self._context().device
+        if lengths is not None:
+            return self.first_stage_model.encode(x, lengths=lengths)
         return self.first_stage_model.encode(x)
 
-    def get_first_stage_encoding(self, encoder_posterior):
-        """ddpm_audio.py:163-170."""
+    def get_first_stage_encoding(self, encoder_posterior, lengths=None, noise=None, mode=False):
+        """ddpm_audio.py:163-170.
+        lengths (addition; vb_posterior_lens): the posterior of encode_first_stage(x, lengths=) - or its moments [B, 2E, T] - sampled and
+        scaled in one launch, row b's latent exactly zero from lengths[b] on (what sample_cfg(x_known=, lengths=) expects of a padded
+        latent; the elementwise path leaves the noise there, the moments' zero tail being std = 1).  noise: the draw [B, E, T] to use,
+        None = torch.randn on the device as DiagonalGaussianDistribution.sample does; mode = True: the mean, no draw.  Without lengths
+        the reference path, unchanged (noise and mode are then not read)."""
+        if lengths is not None:
+            return self._posterior_lens(encoder_posterior, lengths, noise, mode)
         if isinstance(encoder_posterior, DiagonalGaussianDistribution):
             z = encoder_posterior.sample()
         elif isinstance(encoder_posterior, torch.Tensor):
@@ -383,6 +399,27 @@ class CFM:
         else:
             raise NotImplementedError(f"encoder_posterior of type '{type(encoder_posterior)}' not yet implemented")
         return float(self.scale_factor) * z
+
+    def _posterior_lens(self, encoder_posterior, lengths, noise, mode) -> Tensor:
+        from . import _lib as L
+        from .engine import _lens_struct
+        mom = encoder_posterior.parameters if isinstance(encoder_posterior, DiagonalGaussianDistribution) else encoder_posterior
+        if not isinstance(mom, torch.Tensor) or mom.dim() != 3 or mom.shape[1] % 2:
+            raise ValueError("get_first_stage_encoding(lengths=): a DiagonalGaussianDistribution or its moments [B, 2E, T]")
+        dev = self._context().device
+        mom = mom.to(dev, torch.float32).contiguous()
+        B, E, T = mom.shape[0], mom.shape[1] // 2, mom.shape[2]
+        lens, hold, _ = _lens_struct(lengths, B, T, gloss=" (latent tokens per row)")
+        eps = None
+        if not mode:
+            eps = torch.randn(B, E, T, device=dev) if noise is None else noise.to(dev, torch.float32).contiguous()
+            if tuple(eps.shape) != (B, E, T):
+                raise ValueError(f"get_first_stage_encoding: noise of shape {tuple(eps.shape)}, not {(B, E, T)}")
+        z = torch.empty(B, E, T, dtype=torch.float32, device=dev)
+        L.check(self._context().lib.vb_posterior_lens(L.ptr(mom), L.ptr(eps) if eps is not None else None, B, E, T, lens.len if lens is not None else None,
+                                                     float(self.scale_factor), L.ptr(z), L.stream_ptr()), "vb_posterior_lens")
+        del hold
+        return z
 
     @torch.no_grad()
     def decode_first_stage(self, z, predict_cids=False, force_not_quantize=False, lengths=None):
